@@ -18,6 +18,11 @@ jorge.json with rho = 0.3 and as shipped), `class_api_1e7` (configs[2] through t
 `search` (configs[4]: the whole bracket + bisection search at 50 000 paths per probe and the 10^6-path
 final run, through the drop-in class) and `numpy_stream` (the literal-seed mode's rate).  `config.ranks_seen` / `config.devices` say what the process
 group actually contained.
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path computed in its LAST step: the launch's counter
+vector split as a caller of `DeviceBatch` receives it (`counters` = [successes, paths], `wr_obs_counts`, `ruin_year_bins`),
+summed over the ranks, as DIR/<name>.npy in float64, plus `success_probability`.  The inputs depend only on the arguments
+(fixed seed, global path offsets from --warmup / --steps / --paths / --gpus), so two builds can be compared file for file.
 """
 
 from __future__ import annotations
@@ -464,6 +469,30 @@ def search_block(torch, dist, world, device, grouped, reps=3):
     return out
 
 
+def dump_last_step(batch, before, out_dir, dist, comm_dev, rank):
+    """Write the last timed step's outputs (its share of `batch.reduce_vec`, summed over the ranks when `dist` is given)
+    as out_dir/<name>.npy, float64 (the counts are exact in float64).  Every rank takes part in the all-reduce; rank 0 writes."""
+    import numpy as np
+
+    last = (batch.reduce_vec - before).to(comm_dev)
+    if dist is not None:
+        dist.all_reduce(last)
+    if rank != 0:
+        return
+    last = last.cpu().numpy().astype(np.float64)
+    base = batch.reduce_vec.storage_offset()
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for name in ("counters", "wr_obs_counts", "ruin_year_bins", "hist_bins"):
+        view = getattr(batch, name)
+        if view is not None:
+            off = view.storage_offset() - base
+            arrays[name] = last[off:off + view.numel()]
+    arrays["success_probability"] = np.array([arrays["counters"][0] / max(1.0, arrays["counters"][1])])
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+
+
 def launch_ranks(n_ranks: int) -> int:
     """`python bench.py --gpus N` without an outer launcher: start N copies of this script, one rank per GPU
     (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment, as torch.distributed.run would), wait, and
@@ -557,7 +586,11 @@ def main():
     ap.add_argument("--cpu-paths-per-thread", type=int, default=60_000)
     ap.add_argument("--cpu-single-thread-paths", type=int, default=20_000)
     ap.add_argument("--cpu-all-cores-seconds", type=float, default=10.0, help="target wall time of the all-core oracle run (0 = skip it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))  # before torch is imported: the launcher never touches a GPU
@@ -658,8 +691,12 @@ def main():
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
     batch.zero_counters()
     fence()
+    last_prev = None
     t0 = time.perf_counter()
     for i in range(args.steps):
+        if args.dump_outputs and i == args.steps - 1:
+            # running totals before the last step, on the launch stream (no sync): last step = after - before
+            last_prev = batch.reduce_vec.clone()
         ev[i][0].record()
         batch.launch(12345, 1, ((args.warmup + i) * world + rank) * n)
         ev[i][1].record()
@@ -675,6 +712,8 @@ def main():
     kern_ms = sum(a.elapsed_time(b) for a, b in ev) / args.steps  # HIP events on the launch stream
     # local running totals of the timed steps; with N ranks the last exchange holds the job's totals
     counters = (exch2[(args.steps - 1) & 1] if grouped else batch.reduce_vec)[:2].cpu().tolist()
+    if args.dump_outputs:
+        dump_last_step(batch, last_prev, args.dump_outputs, dist if grouped else None, comm_dev, rank)
 
     def guarded(fn, *a, **kw):
         try:

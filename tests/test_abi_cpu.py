@@ -25,6 +25,25 @@ def lib():
     return N.load_library()
 
 
+def _child(code: str) -> str:
+    """Run `code` in a fresh Python process at the repository root and return its stdout.  Calls that initialise the HIP
+    runtime (device queries, compute entry points) go there: in the test runner they would hold the GPU open for the rest
+    of the session, and the multi-rank tests of tests/test_bench_gpu.py need every slot of the per-GPU process bound."""
+    import subprocess
+    import sys
+
+    r = subprocess.run([sys.executable, *(["-s"] if sys.flags.no_user_site else []), "-c", code], cwd=REPO,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return r.stdout
+
+
+@pytest.fixture(scope="module")
+def gpu_present(lib):
+    return int(_child("from monte_carlo_retirement_amd import _native as N\n"
+                      "print(N.load_library().mcr_device_count())").split()[-1]) > 0
+
+
 def test_header_and_binding_agree_on_symbols(lib):
     hdr = open(os.path.join(REPO, "include", "mcr.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)  # prose in comments mentions call syntax too
@@ -100,10 +119,15 @@ def test_validate_params_rejects_what_the_config_would(lib):
     assert lib.mcr_validate_params(C.byref(bad)) == -1 and "streams[0]" in N.last_error()
     # the compute entry points apply the same check before anything else that needs a device... or after: either
     # way an out-of-range block never computes
-    bad = params_from_config(cfg)
-    bad.inv1_realized_gains_tax_rate = 1.5
-    o = N.McrOutputs()
-    assert lib.mcr_run_batch_host(C.byref(bad), 1, 1, 0, 8, 12, None, C.byref(o), 0) != 0
+    rc = _child("import ctypes as C, json\n"
+                "from monte_carlo_retirement_amd import Config, params_from_config\n"
+                "from monte_carlo_retirement_amd import _native as N\n"
+                "cfg = Config(**json.load(open('tests/golden/paths_injected.json'))[0]['cfg'])\n"
+                "bad = params_from_config(cfg)\n"
+                "bad.inv1_realized_gains_tax_rate = 1.5\n"
+                "o = N.McrOutputs()\n"
+                "print(N.load_library().mcr_run_batch_host(C.byref(bad), 1, 1, 0, 8, 12, None, C.byref(o), 0))")
+    assert int(rc.split()[-1]) != 0
     assert lib.mcr_validate_params(None) == -1
 
 
@@ -127,9 +151,9 @@ def test_stream_lists_of_any_length_are_valid(lib):
     assert few.n_streams == 16 and not bool(few.extra_streams)
 
 
-def test_no_cpu_fallback(lib):
+def test_no_cpu_fallback(lib, gpu_present):
     """Without a HIP device the compute entry points must fail loudly, never compute on the CPU."""
-    if lib.mcr_device_count() > 0:
+    if gpu_present:
         pytest.skip("a GPU is present")
     cfg = Config(**load_golden("paths_injected.json")[0]["cfg"])
     with pytest.raises(RuntimeError, match="no usable HIP device"):
@@ -168,13 +192,13 @@ def build_c_caller(tmp_path) -> str:
     return exe
 
 
-def test_plain_c_caller_compiles_and_fails_loudly_without_a_gpu(lib, tmp_path):
+def test_plain_c_caller_compiles_and_fails_loudly_without_a_gpu(lib, gpu_present, tmp_path):
     """The boundary is a C ABI: the header is valid C99 (-pedantic -Werror), a C program links against the library
     with nothing but libm, and without a HIP device it exits with an error instead of computing anything."""
     import subprocess
 
     exe = build_c_caller(tmp_path)
-    if lib.mcr_device_count() > 0:
+    if gpu_present:
         pytest.skip("a GPU is present (the run itself is tests/test_gpu_edge_cases.py)")
     r = subprocess.run([exe, "1000"], capture_output=True, text=True)
     assert r.returncode == 3 and "no HIP device" in r.stderr and r.stdout == ""

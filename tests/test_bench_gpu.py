@@ -111,6 +111,31 @@ def test_bench_single_gpu_line_has_the_contract_keys():
     assert acc["abs_error"] <= 1e-4 and acc["flipped_success_flags"] == 0
 
 
+def test_bench_dump_outputs_are_the_last_steps_and_repeat(tmp_path):
+    """--dump-outputs DIR: the last timed step's outputs as float64 .npy files; the same arguments give the same files."""
+    import numpy as np
+
+    n, steps = 200_000, 3
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        out = _run("--steps", str(steps), "--warmup", "1", "--paths", str(n), "--no-aux", "--no-s60", "--no-search",
+                   "--no-cpu-baseline", "--dump-outputs", str(d))
+        assert out["steps"] == steps and out["paths_counted"] == steps * n and out["ms_per_step"] > 0
+    names = sorted(f.name for f in dirs[0].iterdir())
+    assert names == sorted(f.name for f in dirs[1].iterdir())
+    assert {"counters.npy", "ruin_year_bins.npy", "success_probability.npy"} <= set(names)
+    total = 0
+    for name in names:
+        a, b = np.load(dirs[0] / name), np.load(dirs[1] / name)
+        assert a.dtype == np.float64 and np.array_equal(a, b, equal_nan=True), name
+        total += a.nbytes
+    assert total <= 64 << 20
+    c = np.load(dirs[0] / "counters.npy")
+    assert c[1] == n and 0.9 < c[0] / n <= 1.0                            # ONE step's paths, not the running total
+    assert np.load(dirs[0] / "ruin_year_bins.npy").sum() == n - c[0]        # every failed path falls in one year bin
+    assert np.load(dirs[0] / "success_probability.npy")[0] == c[0] / n
+
+
 def test_bench_group_code_path_over_rccl_with_one_rank():
     """The N > 1 code path of bench.py — process group with device_id, asynchronous per-step all-reduce on alternating
     copies, barrier, max-over-ranks timing, the s60 block's barrier/all-reduce, teardown — with the `nccl` (= RCCL)
@@ -174,7 +199,9 @@ def test_launcher_deadline_kills_hung_ranks_and_reports(tmp_path):
 def test_bench_under_the_drivers_launcher(world):
     """The driver's own command for N > 1: `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
     127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W` (ranks from the environment, no self-launch) — here
-    with N = 2 and N = 5 on the box's one GPU and the gloo backend."""
+    with N = 2 and N = 5 on the box's one GPU and the gloo backend.  The launcher's agent opens the GPU as well (torch's
+    NUMA-binding default calls torch.cuda.is_available()), so N = 5 is six processes on the card and the test runner must
+    not hold it: the CPU tests that run before this module (tests/test_abi_cpu.py) query the device in child processes."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     port = 29700 + (os.getpid() + world) % 200
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
