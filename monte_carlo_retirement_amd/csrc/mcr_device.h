@@ -542,33 +542,52 @@ __device__ __forceinline__ void rebalance_path(const LaneParams& P, double& b1, 
 // Every other difference is a relative perturbation of ~1e-16 per operation — what a rounding is; measured against the oracle
 // (profiles/r04/k1_accuracy_*.txt): worst path-level error relative to the path's money scale, flips of Success flags.
 
-// liquidation values (:256-272, :726-737); returns cap1 + cap2
-template <bool T1, bool T2 = T1, bool MM = true>
+// WAVE-UNIFORM fix-ups (UNIFORM = true below; the issue-bound launches, MM = true).  The dust / empty tests of the month
+// (balance <= 1e-6: :218-219, :245-247, :290-296, :355-358) almost never hold, yet every one of them costs its lane-mask round
+// trip (compare, s_and_saveexec, a taken s_cbranch_execz, s_or exec) every month.  With UNIFORM the compare goes into one
+// wave ballot instead: when no active lane of the wave qualifies, every fix-up would have been a no-op and the straight-line
+// body runs; otherwise the fix-ups run exactly as in the UNIFORM = false form.  The same values by construction.
+__device__ __forceinline__ bool wave_any(bool c) { return __builtin_amdgcn_ballot_w64(c) != 0ull; }
+
+// liquidation values (:256-272, :726-737); returns cap1 + cap2.  UNIFORM: the caller has established that no active lane of the
+// wave holds a balance <= 1e-6 (the two fix-ups are no-ops).
+template <bool T1, bool T2 = T1, bool MM = true, bool UNIFORM = false>
 __device__ __forceinline__ double capacity_tol(double b1, double c1, double r1, double b2, double c2, double r2) {
     double v1 = b1, v2 = b2;
     if (T1) v1 = __builtin_fma(-fmax(0.0, b1 - c1), r1, b1);
     if (T2) v2 = __builtin_fma(-fmax(0.0, b2 - c2), r2, b2);
-    if (b1 <= kEps) { MCR_MASKED_MOVE; v1 = 0.0; }
-    if (b2 <= kEps) { MCR_MASKED_MOVE; v2 = 0.0; }
+    if (!UNIFORM) {
+        if (b1 <= kEps) { MCR_MASKED_MOVE; v1 = 0.0; }
+        if (b2 <= kEps) { MCR_MASKED_MOVE; v2 = 0.0; }
+    }
     return v1 + v2;
 }
-// both assets sell the fraction phi (:757-776 as derived above)
-template <bool MM = true>
+// both assets sell the fraction phi (:757-776 as derived above).  UNIFORM: as capacity_tol (the last two fix-ups are no-ops).
+template <bool MM = true, bool UNIFORM = false>
 __device__ __forceinline__ void sell_fraction_tol(double phi, double& b1, double& c1, double& b2, double& c2) {
     double nb1 = __builtin_fma(-b1, phi, b1), nc1 = __builtin_fma(-c1, phi, c1);     // :243-244
     double nb2 = __builtin_fma(-b2, phi, b2), nc2 = __builtin_fma(-c2, phi, c2);
-    if (nb1 <= kEps) { MCR_MASKED_MOVE; nb1 = 0.0; nc1 = 0.0; }                       // :245-247
-    if (nb2 <= kEps) { MCR_MASKED_MOVE; nb2 = 0.0; nc2 = 0.0; }
-    if (b1 <= kEps) { MCR_MASKED_MOVE; nb1 = b1; nc1 = c1; }                         // :218-219: an asset without a balance is left alone
-    if (b2 <= kEps) { MCR_MASKED_MOVE; nb2 = b2; nc2 = c2; }
+    if (!UNIFORM || wave_any(fmin(nb1, nb2) <= kEps)) {
+        if (nb1 <= kEps) { MCR_MASKED_MOVE; nb1 = 0.0; nc1 = 0.0; }                   // :245-247
+        if (nb2 <= kEps) { MCR_MASKED_MOVE; nb2 = 0.0; nc2 = 0.0; }
+    }
+    if (!UNIFORM) {
+        if (b1 <= kEps) { MCR_MASKED_MOVE; nb1 = b1; nc1 = c1; }                     // :218-219: an asset without a balance is left alone
+        if (b2 <= kEps) { MCR_MASKED_MOVE; nb2 = b2; nc2 = c2; }
+    }
     b1 = nb1; c1 = nc1; b2 = nb2; c2 = nc2;
 }
-// (:274-359)  L = lane_params_tol(P): L.alloc1 / L.alloc2 hold weight x rate of asset 1 / 2.
-template <bool TAXED, bool MM = true>
+// (:274-359)  L = lane_params_tol(P): L.alloc1 / L.alloc2 hold weight x rate of asset 1 / 2.  UNIFORM: the guard and the dust
+// fix-ups are tested wave-wide (self-contained: no precondition); a wave with a lane that does not act takes the UNIFORM = false form.
+template <bool TAXED, bool MM = true, bool UNIFORM = false>
 __device__ __forceinline__ void rebalance_tol(const DevParams& P, const LaneParams& L, double& b1, double& c1, double& b2, double& c2) {
     const double total = b1 + b2;                                  // :288
     const double drift1 = __builtin_fma(-total, P.alloc1, b1);     // :293-294
-    if ((total > kEps) && (fabs(drift1) > kEps)) {                 // :290-296
+    if (UNIFORM && wave_any(fmin(total, fabs(drift1)) <= kEps)) {  // (one compare: a ballot of an OR comes out as a 0/1 VGPR compared again)
+        rebalance_tol<TAXED, MM, false>(P, L, b1, c1, b2, c2);
+        return;
+    }
+    if (UNIFORM || ((total > kEps) && (fabs(drift1) > kEps))) {   // :290-296
         MCR_MASKED_MOVE;
         const bool sell1 = drift1 > 0.0;                           // :298
         const double bs = sell1 ? b1 : b2, cs = sell1 ? c1 : c2;   // seller
@@ -590,8 +609,10 @@ __device__ __forceinline__ void rebalance_tol(const DevParams& P, const LanePara
         double r2b = b2 + net_purchase, r2c = c2 + net_purchase;
         if (sell1) { MCR_MASKED_MOVE; r1b = nbs; r1c = ncs; }
         else { MCR_MASKED_MOVE; r2b = nbs; r2c = ncs; }
-        if (r1b <= kEps) { MCR_MASKED_MOVE; r1b = 0.0; r1c = 0.0; }  // :355-358
-        if (r2b <= kEps) { MCR_MASKED_MOVE; r2b = 0.0; r2c = 0.0; }
+        if (!UNIFORM || wave_any(fmin(r1b, r2b) <= kEps)) {
+            if (r1b <= kEps) { MCR_MASKED_MOVE; r1b = 0.0; r1c = 0.0; }  // :355-358
+            if (r2b <= kEps) { MCR_MASKED_MOVE; r2b = 0.0; r2c = 0.0; }
+        }
         b1 = r1b; c1 = r1c; b2 = r2b; c2 = r2c;
     }
 }

@@ -24,6 +24,7 @@
 #include <algorithm>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -117,6 +118,13 @@ constexpr bool kExactMonthDefault = true;
 #else
 constexpr bool kExactMonthDefault = false;
 #endif
+// -DMCR_K1_GENERAL_MONTH (tests only: tests/test_gpu_month_fast_path.py) builds a library whose tolerance month always takes the
+// lane-masked fix-ups: the reference the wave-uniform form is compared with, bit for bit.
+#ifdef MCR_K1_GENERAL_MONTH
+constexpr bool kUniformFixups = false;
+#else
+constexpr bool kUniformFixups = true;
+#endif
 template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault>
 __global__ __launch_bounds__(SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
                                                          const DevParams* __restrict__ cand_params) {
@@ -134,6 +142,8 @@ __global__ __launch_bounds__(SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0
     static_assert(!EXACT || XS || kExactMonthDefault, "the exact month is instantiated for the generic variants only");
     constexpr bool TOL = !EXACT;         // the month in its tolerance form (mcr_device.h: "TOLERANCE FORM of the month")
     constexpr bool MM = !SPLIT;          // exec-masked moves (issue-bound launches) vs the compiler's selects (latency-bound SPLIT launches): MCR_MASKED_MOVE, mcr_device.h
+    // the tolerance month's dust / empty fix-ups tested once per wave (mcr_device.h: WAVE-UNIFORM fix-ups), issue-bound launches only
+    constexpr bool kFastMonth = TOL && MM && kUniformFixups;
     constexpr int kThreads = SPLIT ? 2 * kBlock : kBlock;
     const int tid = SPLIT ? (int)(threadIdx.x & (kBlock - 1)) : (int)threadIdx.x;    // the path's lane column in every per-path LDS array
     const bool producer = SPLIT && threadIdx.x >= (unsigned)kBlock;                  // wave-uniform (kBlock = 4 wavefronts)
@@ -392,7 +402,7 @@ __global__ __launch_bounds__(SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0
         const double k1 = contrib * P.alloc1;                          // :540-542
         const double k2 = contrib - k1;                                // :543
         b1 += k1; c1 += k1; b2 += k2; c2 += k2;                        // :544-547
-        if (TOL) rebalance_tol<TANY, MM>(P, L, b1, c1, b2, c2);        // :549-553
+        if (TOL) rebalance_tol<TANY, MM, kFastMonth>(P, L, b1, c1, b2, c2);  // :549-553
         else rebalance_path<TANY, MM>(L, b1, c1, b2, c2);
         if (m % kMPY == 0) {                                           // :557
             pre_fail |= annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, TOL>(P, L, b1, c1, b2, c2, gacc1, gacc2);  // :558-573
@@ -496,33 +506,42 @@ __global__ __launch_bounds__(SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0
                 if (b1 + b2 <= kEps && need > kEps) {                  // :684-690 (FAIL-1, no shock consumed)
                     yfail = true; stop = true;
                 }
-                if (!stop) {
-                    if (!kStaged) growth(wm + rmi, g1, ginf, g2);      // :692-705 (sequential generators draw here)
-                    market_step<ANNUAL, TOL>(g1, ginf, g2, b1, b2, gacc1, gacc2, infl);  // :706-714
-                    if (b1 + b2 <= kEps && need > kEps) {              // :717-724 (FAIL-2)
-                        MCR_MASKED_MOVE;                              // keep it a branch: no lane takes it in most months
-                        b1 = fmax(0.0, b1); b2 = fmax(0.0, b2);
-                        yfail = true; stop = true;
-                    }
-                }
-                if (!stop && TOL) {
-                    // the withdrawal in closed form (mcr_device.h): both assets sell the fraction target / capacity
-                    const double cap = capacity_tol<T1, T2, MM>(b1, c1, L.real_rate1, b2, c2, L.real_rate2);   // :726-738
+                // the withdrawal in closed form (mcr_device.h): both assets sell the fraction target / capacity.  FAST: no active
+                // lane of the wave holds a balance <= 1e-6 after the market step (kFastMonth below)
+                auto tol_month = [&](auto fast_tag) {
+                    constexpr bool FAST = decltype(fast_tag)::value;
+                    const double cap = capacity_tol<T1, T2, MM, FAST>(b1, c1, L.real_rate1, b2, c2, L.real_rate2);   // :726-738
                     const double target = fmin(need, cap);                            // :739-742
                     if (need > kEps && target < need - kEps) yfail = true;            // :743-748 (FAIL-3) = :784-790 (FAIL-4): the net cash is the target
                     double phi = target * recip_nr<false>(cap);                       // :750-765
-                    if (!(cap > 0.0)) { MCR_MASKED_MOVE; phi = 0.0; }                 // (0 < cap <= 1e-6: still the capacity shares, see mcr_device.h)
+                    if (!FAST && !(cap > 0.0)) { MCR_MASKED_MOVE; phi = 0.0; }       // (0 < cap <= 1e-6: still the capacity shares, see mcr_device.h)
                     if (kSummary) {
                         const double gross = phi * (b1 + b2);                         // :766, :777: gross withdrawals of the month
                         tg1 += gross;
                         treal = __builtin_fma(gross * infl_ret, recip_nr<false>(fmax(price, kEps)), treal);  // :778-782
                     }
-                    sell_fraction_tol<MM>(phi, b1, c1, b2, c2);                       // :757-776
-                    rebalance_tol<TANY, MM>(P, L, b1, c1, b2, c2);                    // :792-796
+                    sell_fraction_tol<MM, FAST>(phi, b1, c1, b2, c2);                 // :757-776
+                    rebalance_tol<TANY, MM, kFastMonth>(P, L, b1, c1, b2, c2);        // :792-796
                     if (!yfail && (wm + rmi + 1) % kMPY == 0) {                       // :798-804
                         const bool tf = annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, true>(P, L, b1, c1, b2, c2, gacc1, gacc2);  // :805-818
                         gacc1 = 0.0; gacc2 = 0.0;                                     // :819-820
                         yfail = yfail || tf;                                          // :821-822
+                    }
+                };
+                if (!stop) {
+                    if (!kStaged) growth(wm + rmi, g1, ginf, g2);      // :692-705 (sequential generators draw here)
+                    market_step<ANNUAL, TOL>(g1, ginf, g2, b1, b2, gacc1, gacc2, infl);  // :706-714
+                    // Both balances > 1e-6 in every active lane: FAIL-2 cannot fire (b1 + b2 > 1e-6), no capacity is zeroed and
+                    // each is > 0 (cap_i >= b_i (1 - r_i), r_i <= 1 - 1e-6 in the tolerance form), no asset is left alone.
+                    if (kFastMonth && !wave_any(fmin(b1, b2) <= kEps)) {
+                        tol_month(std::true_type{});
+                    } else {
+                        if (b1 + b2 <= kEps && need > kEps) {          // :717-724 (FAIL-2)
+                            MCR_MASKED_MOVE;                          // keep it a branch: no lane takes it in most months
+                            b1 = fmax(0.0, b1); b2 = fmax(0.0, b2);
+                            yfail = true; stop = true;
+                        }
+                        if (!stop && TOL) tol_month(std::false_type{});
                     }
                 }
                 if (!stop && !TOL) {
