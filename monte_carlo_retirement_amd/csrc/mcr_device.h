@@ -79,6 +79,7 @@ struct DevParams {
     const DevStream* extra_streams;    // DEVICE table [n_extra_streams] (read through DevStreamTable), nullptr if none
     double* lock_overflow;             // DEVICE [n_lock_slots_total - n_lock_slots][lock_stride]: the slots that did not fit in LDS
     int64_t lock_stride;               // = grid.x * kBlock: every lane of the launch has its own column
+    double fast_floor;                 // 1e-6 / (1 - max(real_rate1, real_rate2)) (>= 1e-6): both balances above it -> capacity > 1e-6
 };
 
 // The four parameters that feed per-lane SELECTS (seller's weight / seller's rate).  They are
@@ -535,12 +536,13 @@ __device__ __forceinline__ void rebalance_path(const LaneParams& P, double& b1, 
 // Validity: the reference clamps its denominators at 1e-6 (:227, :307-310).  1 - gf r >= 1 - r and 1 - a gf r >= 1 - r, so
 // with both effective realized-gains rates <= 1 - 1e-6 the clamps never bind and the closed form is the reference's
 // arithmetic up to roundings (DevParams::exact_month = 0, derive_params).  Configurations with a rate above that (a 100 % tax
-// on realized gains) run the exact forms in the generic kernel variants.  One sub-case is resolved differently: alive, total
-// balance > 1e-6 but total liquidation value <= 1e-6 (needs a balance below 1e-6 / (1 - r) dollars in the very month the path
-// fails): the reference then splits the target by the allocation weights instead of the capacity shares (:750-755), the closed
-// form keeps the capacity shares — the two differ by at most 1e-6 / (1 - r) dollars in the failing year's residual sample.
-// Every other difference is a relative perturbation of ~1e-16 per operation — what a rounding is; measured against the oracle
-// (profiles/r04/k1_accuracy_*.txt): worst path-level error relative to the path's money scale, flips of Success flags.
+// on realized gains) run the exact forms in the generic kernel variants.  One sub-case is not covered by the closed form:
+// alive, total balance > 1e-6 but total liquidation value <= 1e-6 (needs a total balance below 1e-6 / (1 - r) dollars): the
+// reference then splits the target by the allocation weights instead of the capacity shares (:750-755), which leaves up to
+// 1e-6 / (1 - r) dollars where the closed form sells out.  Those lanes run the exact forms (the path kernel's wave-uniform
+// slow month; DevParams::fast_floor keeps them out of the straight-line one).  Every other difference is a relative
+// perturbation of ~1e-16 per operation — what a rounding is; measured against the oracle (profiles/r04/k1_accuracy_*.txt,
+// tests/test_gpu_high_rate_month.py): worst path-level error relative to the path's money scale, flips of Success flags.
 
 // WAVE-UNIFORM fix-ups (UNIFORM = true below; the issue-bound launches, MM = true).  The dust / empty tests of the month
 // (balance <= 1e-6: :218-219, :245-247, :290-296, :355-358) almost never hold, yet every one of them costs its lane-mask round

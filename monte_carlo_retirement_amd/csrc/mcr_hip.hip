@@ -512,11 +512,29 @@ __global__ __launch_bounds__(SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0
                     constexpr bool FAST = decltype(fast_tag)::value;
                     const double cap = capacity_tol<T1, T2, MM, FAST>(b1, c1, L.real_rate1, b2, c2, L.real_rate2);   // :726-738
                     const double target = fmin(need, cap);                            // :739-742
-                    if (need > kEps && target < need - kEps) yfail = true;            // :743-748 (FAIL-3) = :784-790 (FAIL-4): the net cash is the target
+                    bool fail = need > kEps && target < need - kEps;                  // :743-748 (FAIL-3) = :784-790 (FAIL-4): the net cash is the target
                     double phi = target * recip_nr<false>(cap);                       // :750-765
-                    if (!FAST && !(cap > 0.0)) { MCR_MASKED_MOVE; phi = 0.0; }       // (0 < cap <= 1e-6: still the capacity shares, see mcr_device.h)
+                    // :766, :777: gross withdrawals of the month (an asset holding <= 1e-6 is left alone, :218-219: it sells nothing)
+                    double gross = phi * (FAST ? b1 + b2 : (b1 > kEps ? b1 : 0.0) + (b2 > kEps ? b2 : 0.0));
+                    // The dust sub-case (mcr_device.h; FAST excludes it): the reference's allocation-weight split (:739-790) in the
+                    // exact forms, FAIL-3 and FAIL-4 on its values; phi = 0 leaves the result alone below.  Behind a wave ballot: the
+                    // SPLIT variants (MM = false) would otherwise select-convert the block and run it every month.
+                    if (!FAST && wave_any(!(cap > kEps))) {
+                        if (!(cap > kEps)) {
+                            MCR_MASKED_MOVE;
+                            double cap1, cap2, gw1, nw1, gw2, nw2;
+                            net_liquidation_values2<T1, T2, MM>(b1, c1, L.real_rate1, b2, c2, L.real_rate2, cap1, cap2);
+                            const double xcap = cap1 + cap2, xtarget = fmin(need, xcap);
+                            const double prop1 = xcap > kEps ? fdiv<false>(cap1, xcap) : P.alloc1;
+                            withdraw2<T1, T2, MM>(b1, c1, xtarget * prop1, L.real_rate1, gw1, nw1,
+                                                  b2, c2, xtarget * (1.0 - prop1), L.real_rate2, gw2, nw2);
+                            fail = need > kEps && (xtarget < need - kEps || nw1 + nw2 < need - kEps);
+                            phi = 0.0;
+                            gross = gw1 + gw2;
+                        }
+                    }
+                    if (fail) yfail = true;
                     if (kSummary) {
-                        const double gross = phi * (b1 + b2);                         // :766, :777: gross withdrawals of the month
                         tg1 += gross;
                         treal = __builtin_fma(gross * infl_ret, recip_nr<false>(fmax(price, kEps)), treal);  // :778-782
                     }
@@ -531,9 +549,10 @@ __global__ __launch_bounds__(SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0
                 if (!stop) {
                     if (!kStaged) growth(wm + rmi, g1, ginf, g2);      // :692-705 (sequential generators draw here)
                     market_step<ANNUAL, TOL>(g1, ginf, g2, b1, b2, gacc1, gacc2, infl);  // :706-714
-                    // Both balances > 1e-6 in every active lane: FAIL-2 cannot fire (b1 + b2 > 1e-6), no capacity is zeroed and
-                    // each is > 0 (cap_i >= b_i (1 - r_i), r_i <= 1 - 1e-6 in the tolerance form), no asset is left alone.
-                    if (kFastMonth && !wave_any(fmin(b1, b2) <= kEps)) {
+                    // Both balances > fast_floor >= 1e-6 in every active lane: FAIL-2 cannot fire (b1 + b2 > 1e-6), no capacity is
+                    // zeroed, each is > 0 (cap_i >= b_i (1 - r_i), r_i <= 1 - 1e-6 in the tolerance form), no asset is left alone,
+                    // and cap >= (b1 + b2) (1 - r_max) > 2e-6: no lane is in the dust sub-case.
+                    if (kFastMonth && !wave_any(fmin(b1, b2) <= P.fast_floor)) {
                         tol_month(std::true_type{});
                     } else {
                         if (b1 + b2 <= kEps && need > kEps) {          // :717-724 (FAIL-2)
@@ -821,10 +840,18 @@ __global__ void helper_kernel(int which, const DevParams P, const double* in, do
                                  : P.tax_mask == 1 ? capacity_tol<true, false>(b1, c1, L.real_rate1, b2, c2, L.real_rate2)
                                                    : capacity_tol<false, false>(b1, c1, L.real_rate1, b2, c2, L.real_rate2);
                 const double target = fmin(need, cap);
-                double phi = target * recip_nr<false>(cap);
-                if (!(cap > 0.0)) phi = 0.0;
-                gross = phi * (b1 + b2); net = target;
-                sell_fraction_tol<true>(phi, b1, c1, b2, c2);
+                if (cap > kEps) {
+                    const double phi = target * recip_nr<false>(cap);
+                    gross = phi * ((b1 > kEps ? b1 : 0.0) + (b2 > kEps ? b2 : 0.0)); net = target;   // (:218-219)
+                    sell_fraction_tol<true>(phi, b1, c1, b2, c2);
+                } else {                    // the dust sub-case: the reference's allocation-weight split in the exact forms
+                    double cap1, cap2, g1, n1, g2, n2;
+                    net_liquidation_values2<true, true>(b1, c1, L.real_rate1, b2, c2, L.real_rate2, cap1, cap2);
+                    const double xcap = cap1 + cap2, xtarget = fmin(need, xcap);
+                    const double prop1 = xcap > kEps ? fdiv<false>(cap1, xcap) : P.alloc1;
+                    withdraw2<true, true>(b1, c1, xtarget * prop1, L.real_rate1, g1, n1, b2, c2, xtarget * (1.0 - prop1), L.real_rate2, g2, n2);
+                    gross = g1 + g2; net = n1 + n2;
+                }
             }
             double* o = out + 6 * i;
             o[0] = b1; o[1] = c1; o[2] = b2; o[3] = c2; o[4] = gross; o[5] = net;
@@ -1143,6 +1170,9 @@ static int derive_params(const mcr_params* p, int32_t wm, DevParams* d, std::vec
     // the tolerance form of the month is the reference's arithmetic while its denominator clamps (max(1e-6, 1 - gf r), :227,
     // :307-310) cannot bind: both effective rates <= 1 - 1e-6 (mcr_device.h).  Otherwise: exact forms, generic variants.
     d->exact_month = (d->real_rate1 > 1.0 - kEps || d->real_rate2 > 1.0 - kEps) ? 1 : 0;
+    // the straight-line month's ballot (path kernel): both balances above this floor -> capacity >= (b1 + b2)(1 - r_max) > 2e-6,
+    // outside the dust sub-case.  1e-6 itself without a realized-gains rate.
+    d->fast_floor = d->exact_month ? kEps : kEps / (1.0 - std::fmax(d->real_rate1, d->real_rate2));
     const double sqrt12 = std::sqrt((double)kMPY);
     d->a1 = p->inv1_mu_log / (double)kMPY;   d->b1 = p->inv1_sigma_log / sqrt12;     // :473
     d->ainf = p->inf_mu_log / (double)kMPY;  d->binf = p->inf_sigma_log / sqrt12;

@@ -404,6 +404,59 @@ def gen_fuzz():
     return groups + gen_many_streams()
 
 
+def gen_high_rate():
+    """Realized-gains rates near 100 %: the band around the switch between the closed-form month and the exact forms
+    (DevParams::exact_month).  One or both assets taxed, allocations 0.5 / 0.999 / 1.0, long accumulation at high means (the
+    gain fraction nears 1 by retirement), expenses that fail some paths, and sub-cent portfolios (both assets taxed) whose
+    failing months reach a liquidation value <= 1e-6 below a larger balance: each such group starts at a path the oracle
+    sees end in that band, if one of the first 20 000 does.  Engine shocks injected; own generator state and file."""
+    rng = np.random.default_rng(20261015)
+    rates = [0.99, 0.999, 0.9999, 1 - 1e-5, 1 - 2e-6, float(np.nextafter(1 - 1e-6, 0.0)), 1 - 1e-6,
+             float(np.nextafter(1 - 1e-6, 1.0)), 1 - 1e-7, 1.0]
+    groups = []
+    for k in range(24):
+        rate = rates[k % len(rates)]
+        cents = k % 3 == 2
+        mask = 3 if cents else (1, 2, 3)[(k // 3) % 3]   # (the cents family needs both assets taxed to reach the sub-case)
+        cfgd = base_test_config(
+            initial_balance=float(rng.uniform(5e-4, 1.5e-3)) if cents else float(rng.uniform(2e4, 1e5)),
+            monthly_contribution=0.0 if cents else float(rng.uniform(500, 2000)),
+            monthly_expenses=3e-6 if cents else float(rng.choice([900.0, 2300.0, 3500.0])),
+            current_age=40.0, retirement_years=int(rng.integers(14, 21)) if cents else int(rng.integers(6, 13)),
+            allocation_inv1_pct=float(rng.choice([0.5, 0.999, 1.0])),
+            inv1_returns_mean=0.6 if cents else float(rng.uniform(0.1, 0.16)),
+            inv1_returns_volatility=0.5 if cents else float(rng.uniform(0.1, 0.4)),
+            inv1_realized_gains_tax_rate=rate if mask & 1 else 0.2, inv1_use_realized_gains_tax_system=bool(mask & 1),
+            inv2_realized_gains_tax_rate=rate if mask & 2 else 0.2, inv2_use_realized_gains_tax_system=bool(mask & 2),
+            inv2_premium_over_inflation_mean=0.5 if cents else float(rng.uniform(0.04, 0.09)),
+            inv2_premium_over_inflation_volatility=0.4 if cents else float(rng.uniform(0.05, 0.3)),
+            inflation_rate_mean=0.03, inflation_rate_volatility=0.01,
+        )
+        wm = 36 if cents else int(rng.choice([120, 180]))
+        seed = int(rng.integers(0, 2**40))
+        stream = "search" if k % 2 else "final"
+        sim = make_sim(cfgd, seed=seed)
+        getattr(sim, f"use_{stream}_seeds")()
+        inject_engine_shocks(sim, seed)
+        n = int(rng.integers(4, 9))
+        pb = 0
+        if cents:   # start the group at a path the oracle (bit-exact to the reference) sees fail with a dust-band residual
+            from monte_carlo_retirement_amd import Config as EngineConfig, params_from_config
+            res = O.run_batch(params_from_config(EngineConfig(**cfgd)), seed, STREAM_ID[stream], 0, 20_000, wm,
+                              want_trajectories=False)
+            top = 1e-6 / (1.0 - rate) if rate < 1.0 else math.inf
+            hit = np.nonzero((res["success"] == 0) & (res["final_balance"] > 1e-6) & (res["final_balance"] <= top))[0]
+            pb = int(hit[0]) if hit.size else 0
+        paths = [result_to_jsonable(sim._run_single_simulation_path(wm, pb + i)) for i in range(n)]
+        groups.append({"name": f"high_rate{k:02d}", "cfg": cfgd, "working_months": wm, "stream": stream,
+                       "seed": seed, "path_begin": pb, "n_paths": n, "results": paths})
+    nfail = sum(1 for g in groups for p in g["results"] if not p["Success"])
+    dust = sum(1 for g in groups for p in g["results"] if not p["Success"] and 1e-6 < p["Final Balance"] < 1.0
+               and g["cfg"]["initial_balance"] < 1.0)
+    print(f"  high_rate: {len(groups)} scenarios, {nfail} failing paths, {dust} failing with a residual balance", flush=True)
+    return groups
+
+
 def gen_many_streams():
     """Scenarios with MORE other_income_streams than the engine's by-value block holds (16): the reference takes any list
     (backend/config.py:99; loops backend/simulation.py:602-621, 649-677).  Indexed / frozen, finite / endless / zero-length,
@@ -742,6 +795,8 @@ def main():
         dump("paths_injected.json", gen_injected_paths())
     if want("fuzz"):
         dump("paths_fuzz.json", gen_fuzz())
+    if want("high_rate"):
+        dump("paths_high_rate.json", gen_high_rate())
     if want("native_shocks"):
         dump("numpy_native_paths.json", gen_numpy_native(HERE))
     if want("aggregation"):

@@ -100,7 +100,7 @@ def test_deterministic_paths_vs_reference():
             raise AssertionError(f"{case['name']}: {e}") from e
 
 
-@pytest.mark.parametrize("fname", ["paths_injected.json", "paths_fuzz.json"])
+@pytest.mark.parametrize("fname", ["paths_injected.json", "paths_fuzz.json", "paths_high_rate.json"])
 def test_stochastic_paths_vs_reference(fname):
     """Kernel with its own in-register RNG vs the reference run on the same (injected) Philox shocks."""
     for g in load_golden(fname):

@@ -99,7 +99,7 @@ def test_deterministic_paths_match_reference_exactly(oracle):
             raise AssertionError(f"{case['name']}: {e}") from e
 
 
-@pytest.mark.parametrize("fname", ["paths_injected.json", "paths_fuzz.json"])
+@pytest.mark.parametrize("fname", ["paths_injected.json", "paths_fuzz.json", "paths_high_rate.json"])
 def test_stochastic_paths_match_reference_exactly(oracle, fname):
     """Same Philox shocks in the reference loop (injected) and in the oracle (own RNG)."""
     for g in load_golden(fname):
