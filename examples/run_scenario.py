@@ -7,12 +7,15 @@ switch to the final seed stream, run the final batch, print the response documen
     python examples/run_scenario.py scenarios/jorge.json --seed 12345 --rng numpy
     python examples/run_scenario.py scenarios/config.json --paths 10000000 --working-months 233 --compact
     python examples/run_scenario.py scenarios/config.json --events --full > response.json
+    python examples/run_scenario.py scenarios/config.json --working-months 240 --max-expenses
 
 `--rng numpy` uses the reference's own NumPy stream (same seed -> the reference's numbers); `--rng philox`
 (default) the engine's counter-based stream.  `--compact` assembles the document from device-side aggregates
 only (no per-path lists: for batches far beyond the UI's).  `--events` writes the progress events the SSE
 endpoint would stream to stderr, one JSON per line.  Without `--full` only the `summary` block (plus timings
-and sizes) is printed."""
+and sizes) is printed.  `--max-expenses` answers the other planning question instead: the largest monthly spending
+(whole cents) that still reaches the target when retiring after `--working-months` (or the searched minimum), printed
+with its probability and the search curve as one JSON object."""
 
 from __future__ import annotations
 
@@ -40,6 +43,8 @@ def main() -> int:
     ap.add_argument("--compact", action="store_true", help="device-aggregated document (large batches)")
     ap.add_argument("--events", action="store_true", help="progress events to stderr")
     ap.add_argument("--full", action="store_true", help="print the whole response document")
+    ap.add_argument("--max-expenses", action="store_true", help="search the maximum monthly expenses instead")
+    ap.add_argument("--resolution", type=float, default=1.0, help="--max-expenses: stop when the bracket is this narrow")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -69,6 +74,8 @@ def main() -> int:
         if args.events and rank0 and event["type"] != "result":
             print(json.dumps(event), file=sys.stderr)
 
+    if args.max_expenses:
+        return max_expenses(args, config, world, rank0)
     builder = R.compact_result if args.compact else R.build_result
     doc = R.run_scenario(config, args.working_months, emit=emit, result_builder=builder,
                          main_seed_override=args.seed, rng=args.rng)
@@ -89,6 +96,39 @@ def main() -> int:
             "document_bytes": len(json.dumps(doc)),
             "seconds": {"search": round(marks.get("search_done", t_end) - marks["t0"], 3),
                         "final_run_and_document": round(t_end - marks.get("search_done", t_end), 3)},
+        }
+    if rank0:
+        print(json.dumps(out))
+    if world > 1:
+        import torch.distributed as dist
+
+        dist.barrier()
+        dist.destroy_process_group()
+    return rc
+
+
+def max_expenses(args, config: Config, world: int, rank0: bool) -> int:
+    from monte_carlo_retirement_amd.simulation import RetirementMonteCarloSimulator
+
+    t0 = time.perf_counter()
+    sim = RetirementMonteCarloSimulator(config, main_seed_override=args.seed, rng=args.rng)
+    wm = args.working_months
+    searched = wm is None
+    if searched:
+        wm = sim.find_minimum_working_months(verbose=False)[0]
+    rc = 0
+    if wm < 0:
+        out = {"error": "the target is not reachable within the working-month search horizon"}
+        rc = 1
+    else:
+        events = []
+        expenses, prob, curve = sim.find_maximum_monthly_expenses(wm, verbose=False, progress_callback=events.append,
+                                                                  resolution=args.resolution)
+        out = {
+            "scenario": config.Nickname, "rng": args.rng, "working_months": int(wm), "working_months_searched": searched,
+            "target_probability": config.target_probability, "max_monthly_expenses": expenses, "probability": prob,
+            "probes": len({e["iteration"] for e in events}), "curve": curve,
+            "seconds": round(time.perf_counter() - t0, 3),
         }
     if rank0:
         print(json.dumps(out))

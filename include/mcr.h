@@ -24,10 +24,11 @@
 extern "C" {
 #endif
 
-#define MCR_ABI_VERSION 7
+#define MCR_ABI_VERSION 8
 #define MCR_INLINE_STREAMS 16   /* other_income_streams entries carried INSIDE mcr_params; the rest of the list (any length,
                                    backend/config.py:99) follows through mcr_params.extra_streams */
 #define MCR_MAX_PROBE_CANDIDATES 32 /* candidates of one mcr_probe_months_rng call that can share their accumulation sweep */
+#define MCR_MAX_EXPENSE_FANOUT 15  /* spending levels one expense fan-out workgroup evaluates (mcr_probe_expenses_rng) */
 #define MCR_MAX_HIST_BINS 4096  /* bins of the in-kernel final-balance histogram (mcr_outputs.hist_bins) */
 #define MCR_MONTHS_PER_YEAR 12  /* backend/constants.py:1 */
 #define MCR_SMALL_EPSILON 1e-6  /* backend/constants.py:3 (absolute dollar threshold) */
@@ -291,6 +292,22 @@ int mcr_run_batch_multi_host_rng(const mcr_params* p, const mcr_rng* rng, uint32
 int mcr_probe_months_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
                          uint64_t n_paths, const int32_t* working_months, int32_t n_candidates,
                          uint64_t* counts, int device, void* hip_stream);
+
+/*
+ * Maximum-spending search support: success counts of SEVERAL monthly_expenses levels at one working-month count over the
+ * same path range.  counts[k] equals, bit for bit, the counters of a count-only mcr_run_batch_rng call with the same
+ * arguments and p->monthly_expenses = monthly_expenses[k].  monthly_expenses is a HOST array of n_levels >= 0 values (duplicates
+ * allowed), each finite and >= 0 (config.py:59); every level is validated before anything is enqueued.  One level: the plain
+ * count-only launch.  Philox stream, at most MCR_INLINE_STREAMS income streams, the tolerance month: ONE accumulation sweep
+ * to working_months stores its state (80 B per path, a stream-ordered allocation), then EXPENSE FAN-OUT launches resume it:
+ * a workgroup per 64 paths, one wave generating the random numbers for up to MCR_MAX_EXPENSE_FANOUT consumer waves, one per
+ * level.  Otherwise (NumPy stream, longer stream lists, the exact month, allocation refused): one count-only launch per level
+ * on internal side streams, joined back onto `hip_stream`.  counts: DEVICE uint64 [n_levels][MCR_N_COUNTERS] = {successes,
+ * paths} (zeroed by the call).  Asynchronous like mcr_probe_months_rng.
+ */
+int mcr_probe_expenses_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                           uint64_t n_paths, int32_t working_months, const double* monthly_expenses, int32_t n_levels,
+                           uint64_t* counts, int device, void* hip_stream);
 
 /* _draw_shock_path (simulation.py:452-466) for n_paths paths: host out [n_paths][n_months][3]. */
 int mcr_draw_shocks_host(uint64_t seed, uint32_t stream_id, uint64_t path_begin,

@@ -12,7 +12,7 @@ import os
 import threading
 from typing import Optional
 
-MCR_ABI_VERSION = 7
+MCR_ABI_VERSION = 8
 MCR_INLINE_STREAMS = 16  # other_income_streams records inside mcr_params; the rest follow through extra_streams
 MCR_N_COUNTERS = 2
 MCR_N_STAT_ROWS = 4
@@ -25,6 +25,7 @@ MCR_RNG_NUMPY = 1
 MCR_MAX_ENTROPY_WORDS = 8
 MCR_DEVICE_ALL = -2
 MCR_MAX_HIST_BINS = 4096
+MCR_MAX_EXPENSE_FANOUT = 15  # spending levels one expense fan-out workgroup evaluates (mcr_probe_expenses_rng)
 
 MCR_HELPER_WITHDRAW = 0
 MCR_HELPER_NLV = 1
@@ -229,6 +230,7 @@ ABI_SYMBOLS = (
     "mcr_run_batch_host_rng",
     "mcr_draw_shocks_host_rng",
     "mcr_probe_months_rng",
+    "mcr_probe_expenses_rng",
     "mcr_run_batch_multi_host_rng",
     "mcr_validate_params",
     "mcr_release_cached",
@@ -293,6 +295,11 @@ def _declare(lib: C.CDLL) -> None:
     lib.mcr_probe_months_rng.restype = C.c_int
     lib.mcr_probe_months_rng.argtypes = [
         P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, P(C.c_int32), C.c_int32,
+        C.c_void_p, C.c_int, C.c_void_p,
+    ]
+    lib.mcr_probe_expenses_rng.restype = C.c_int
+    lib.mcr_probe_expenses_rng.argtypes = [
+        P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32, P(C.c_double), C.c_int32,
         C.c_void_p, C.c_int, C.c_void_p,
     ]
     lib.mcr_run_batch_host_rng.restype = C.c_int

@@ -218,11 +218,12 @@ __device__ __forceinline__ double monthly_gross(double a, double b, double z, co
 //                             rows = (P3.c, P3.s, P4.c), (P4.s, P5.c, P5.s)
 // The path kernel calls this at every even row (wave-uniform) and stages the two months' gross factors
 // (g1, g_inflation, g2 = g_inflation * g_premium; :522-532) in the lane's own LDS column:
-// `stage[j * kBlock]`, j = 3 * (row & 1) + {0, 1, 2} (12 KB per workgroup).  The six pairs of a HALF are
+// `stage[j * COLS]`, j = 3 * (row & 1) + {0, 1, 2} (COLS = kBlock: 12 KB per workgroup; the expense fan-out's 64-path
+// workgroups stage 64 columns).  The six pairs of a HALF are
 // independent straight-line work (lots of instruction-level parallelism next to the serial month bodies of
 // the other waves).  The normals are shock_row_seq's; the log-returns are associated on their parts (below).
 struct PairCarry { uint32_t w2, w3; };
-template <int HALF>
+template <int HALF, int COLS = kBlock>
 __device__ __forceinline__ void growth_rows2(const DevParams& P, const MathRegs& M, uint64_t seed, uint32_t stream_id, uint64_t path,
                                              uint32_t t, const double* tab, double* stage, PairCarry& C) {
     // pair i: radius rad[i], trig[2 i] = cos, trig[2 i + 1] = sin; normal j of the half = rad[j >> 1] * trig[j]
@@ -263,9 +264,9 @@ __device__ __forceinline__ void growth_rows2(const DevParams& P, const MathRegs&
         const double g1 = fexp<true>(x_eq, tab, M);
         const double ginf = fexp<true>(x_inf, tab, M);
         const double gprem = fexp<true>(x_prem, tab, M);
-        stage[(3 * r + 0) * kBlock] = g1;
-        stage[(3 * r + 1) * kBlock] = ginf;
-        stage[(3 * r + 2) * kBlock] = ginf * gprem;                             // :532
+        stage[(3 * r + 0) * COLS] = g1;
+        stage[(3 * r + 1) * COLS] = ginf;
+        stage[(3 * r + 2) * COLS] = ginf * gprem;                               // :532
     }
 }
 constexpr int kStageDoubles = 6 * kBlock;   // 12 KB of LDS per workgroup

@@ -64,6 +64,10 @@ struct KernelIO {
     int32_t seg_year[kMaxSegments + 1];              // segment k covers retirement years [seg_year[k], seg_year[k + 1]); segment 0 also the accumulation
     unsigned int* seg_flags;                         // [seg_n_split][seg_q], zeroed before the launch
     int32_t seg_max_polls;                           // x ~1 us: how long a successor looks for its predecessor's flag before it recomputes the block itself
+    // PHASE 5 (expense fan-out, mcr_probe_expenses_rng): consumer wave j runs monthly_expenses = fan_expenses[j] and adds its
+    // counts to counters + j * MCR_N_COUNTERS; fan_n = blockDim.x / 64 - 1 levels
+    int32_t fan_n;
+    double fan_expenses[MCR_MAX_EXPENSE_FANOUT];
 };
 constexpr int kSplitVotePairs = 16;   // SPLIT: pairs of months between two stop votes of a workgroup (a power of two)
 constexpr int kSnapFields = 10;   // b1 b2 c1 c2 gacc1 gacc2 infl contrib | pre_fail | Philox carry words
@@ -110,6 +114,14 @@ __device__ __forceinline__ void store_bits(double* p, unsigned long long bits) {
 // other_income_streams has no length limit in the reference, config.py:99).  A compile-time variant because the headline
 // kernels have no SGPR to spare for the two extra tests a month; instantiated for the generic tax form only (TAXED = 3,
 // ANNUAL = true: exact zeros for a zero rate, like the NumPy-stream variants).
+// PHASE 5 (SPLIT = true; mcr_probe_expenses_rng): EXPENSE FAN-OUT.  The workgroup covers ONE 64-path block with 64 (L + 1)
+// threads: the last wave is the producer (the SPLIT producer, resumed like PHASE 2 from the single PHASE 1 snapshot), waves
+// 0 .. L - 1 are consumers that all resume the same 64 paths from that snapshot and run the retirement months with their own
+// wave-uniform monthly_expenses = io.fan_expenses[j].  The factors a producer stages once feed L months, so the random-number
+// half of the month (growth_rows2, ~64 % of its cost) is shared by L spending levels.  Every consumer wave executes the
+// barriers of PHASE 2's SPLIT consumers (same row range, same vote schedule); each keeps its own lock columns in LDS and its
+// own success count (blk[j]).  The month is the issue-bound one (MM, WAVE-UNIFORM fix-ups): counts are bit-identical to a
+// count-only launch with monthly_expenses = fan_expenses[j].
 // EXACT = true: the month in its exact-rounding forms (mcr_device.h) instead of the tolerance form — for configurations whose
 // realized-gains rate lets the reference's denominator clamps bind (DevParams::exact_month), instantiated for the generic XS
 // variants only; -DMCR_K1_EXACT_MONTH builds a library that runs every variant that way (A/B).
@@ -126,13 +138,15 @@ constexpr bool kUniformFixups = false;
 constexpr bool kUniformFixups = true;
 #endif
 template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault>
-__global__ __launch_bounds__(SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
+__global__ __launch_bounds__(PHASE == 5 ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
                                                          const DevParams* __restrict__ cand_params) {
     static_assert(!SPLIT || (MODE == 0 && RNG == 0 && !INJ), "the producer / consumer split exists for the count-only Philox variants");
     static_assert(!XS || (PHASE == 0 && !SPLIT && TAXED == 3 && ANNUAL), "extended stream lists run the generic whole-path form");
+    static_assert(PHASE != 5 || SPLIT, "the expense fan-out is a producer / consumer form");
     // PHASE 4 = PHASE 2 (a candidate's decumulation resumed from its accumulation snapshot) time-sliced like PHASE 3: the
     // 17-month verification window of the search is 17 x 196 workgroups = 2.17 rounds of the resident slots.
-    constexpr bool kCand = PHASE == 2 || PHASE == 4;      // resumes a search candidate from its snapshot; per-candidate parameter block
+    constexpr bool kFan = PHASE == 5;                     // expense fan-out: one 64-path block, L consumer waves (levels), one producer wave
+    constexpr bool kCand = PHASE == 2 || PHASE == 4 || kFan;   // resumes from a PHASE 1 snapshot (PHASE 2 / 4: per-candidate parameter block)
     constexpr bool kSliced = PHASE == 3 || PHASE == 4;    // time-sliced path blocks
     static_assert(!kSliced || (RNG == 0 && !INJ && !SPLIT && !XS), "time-sliced blocks exist for the plain Philox variants");
     static_assert(PHASE != 4 || MODE == 0, "the search probes count only");
@@ -141,12 +155,15 @@ __global__ __launch_bounds__(SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0
     constexpr bool T1 = (TAXED & 1) != 0, T2 = (TAXED & 2) != 0, TANY = TAXED != 0;
     static_assert(!EXACT || XS || kExactMonthDefault, "the exact month is instantiated for the generic variants only");
     constexpr bool TOL = !EXACT;         // the month in its tolerance form (mcr_device.h: "TOLERANCE FORM of the month")
-    constexpr bool MM = !SPLIT;          // exec-masked moves (issue-bound launches) vs the compiler's selects (latency-bound SPLIT launches): MCR_MASKED_MOVE, mcr_device.h
+    constexpr bool MM = !SPLIT || kFan;  // exec-masked moves (issue-bound launches) vs the compiler's selects (latency-bound SPLIT launches): MCR_MASKED_MOVE, mcr_device.h
     // the tolerance month's dust / empty fix-ups tested once per wave (mcr_device.h: WAVE-UNIFORM fix-ups), issue-bound launches only
     constexpr bool kFastMonth = TOL && MM && kUniformFixups;
-    constexpr int kThreads = SPLIT ? 2 * kBlock : kBlock;
-    const int tid = SPLIT ? (int)(threadIdx.x & (kBlock - 1)) : (int)threadIdx.x;    // the path's lane column in every per-path LDS array
-    const bool producer = SPLIT && threadIdx.x >= (unsigned)kBlock;                  // wave-uniform (kBlock = 4 wavefronts)
+    constexpr int kPaths = kFan ? 64 : kBlock;           // paths of a workgroup = columns of every per-path LDS array
+    const int kThreads = kFan ? (int)blockDim.x : SPLIT ? 2 * kBlock : kBlock;
+    const int tid = SPLIT ? (int)(threadIdx.x & (kPaths - 1)) : (int)threadIdx.x;    // the path's lane column in every per-path LDS array
+    // PHASE 5: the wave's level (wave-uniform: an SGPR); the producer is wave fan_n
+    const int fan_j = kFan ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
+    const bool producer = kFan ? fan_j == io.fan_n : (SPLIT && threadIdx.x >= (unsigned)kBlock);   // wave-uniform (kBlock = 4 wavefronts)
     // PHASE 2: the parameter block of candidate blockIdx.y, in device memory (a separate const __restrict__ kernel
     // argument so that its loads are provably invariant and uniform: scalar loads, like the by-value block)
     // time-sliced launches (1-D grid): which path block (of which candidate) and which segment of it this workgroup runs (seg < 0: a whole block)
@@ -160,7 +177,7 @@ __global__ __launch_bounds__(SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0
         if (PHASE == 4) { cand = lb / (unsigned)io.seg_blocks_per_cand; path_block = lb % (unsigned)io.seg_blocks_per_cand; }
         else path_block = lb;
     }
-    const DevParams& P = kCand ? cand_params[cand] : P_arg;
+    const DevParams& P = (kCand && !kFan) ? cand_params[cand] : P_arg;
     // LDS.  STATIC: the math tables (mcr_math.h) and, for the Philox stream, the [6][kBlock] stage of two months' gross
     // factors — static because the compiler then knows their addresses (offset 0 ...) and a table lookup is index << 3 +
     // ds_read with an immediate offset; against the dynamic region every address is `base + ...` with a base it only learns
@@ -169,7 +186,8 @@ __global__ __launch_bounds__(SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0
     // the block counters.
     constexpr bool kStaged = RNG == (int)MCR_RNG_PHILOX && !INJ;
     __shared__ __align__(16) double tab_s[kTabDoubles];
-    __shared__ __align__(16) double stage_s[kStaged ? (SPLIT ? 2 : 1) * kStageDoubles : 1];
+    constexpr int kStageLen = 6 * kPaths;                // = kStageDoubles for kBlock-path workgroups
+    __shared__ __align__(16) double stage_s[kStaged ? (SPLIT ? 2 : 1) * kStageLen : 1];
     // Per-path values that are written once or twice in a lifetime and read at the very end (first-year withdrawals,
     // YearsToRuin) live in the lane's own LDS column in the variants with per-path outputs: held to 5 waves per SIMD those
     // variants had no registers for them (round 2: 12 / 36 bytes of scratch per lane, 4-12 VGPRs spilled).
@@ -190,17 +208,19 @@ __global__ __launch_bounds__(SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0
     // Philox stream: the gross factors of two months at a time, staged per lane (growth_rows2)
     double* stage = stage_s + (kStaged ? tid : 0);
     double* sum_col = sum_s + (kSumLds ? tid : 0);     // [0] first-year gross, [kBlock] first-year real gross, [2 kBlock] YearsToRuin bits
+    // lock columns: [n_lock_slots][kPaths] doubles; PHASE 5: one such block per consumer wave
     double* lock_lds = reinterpret_cast<double*>(smem_raw + (RNG == (int)MCR_RNG_NUMPY ? kZigLdsBytes : 0));
-    unsigned int* blk = reinterpret_cast<unsigned int*>(lock_lds + (size_t)P.n_lock_slots * kBlock);
+    unsigned int* blk = reinterpret_cast<unsigned int*>(lock_lds + (size_t)P.n_lock_slots * kPaths * (kFan ? io.fan_n : 1));
+    if (kFan && !producer) lock_lds += (size_t)fan_j * P.n_lock_slots * kPaths;
     // blk[0] = success count; blk[1 .. 1+ry+2) = ruin bins; then [ry+1] done-years histogram; then the
     // [hist_n_bins] final-balance histogram of the workgroup (mcr_outputs.hist_bins), when requested
     const int ry = P.retirement_years;
-    const int n_blk = 1 + (ry + 2) + (ry + 1);
+    const int n_blk = kFan ? MCR_MAX_EXPENSE_FANOUT : 1 + (ry + 2) + (ry + 1);   // (PHASE 5: blk[j] = level j's success count)
     const int n_hist = ((PHASE == 0 || PHASE == 3) && io.out.hist_bins != nullptr) ? io.out.hist_n_bins : 0;
     for (int k = threadIdx.x; k < n_blk + n_hist; k += kThreads) blk[k] = 0u;
     __syncthreads();
 
-    const uint64_t local = (uint64_t)path_block * kBlock + (unsigned)tid;
+    const uint64_t local = (uint64_t)path_block * kPaths + (unsigned)tid;
     const bool valid = local < io.n_paths;
     const uint64_t li = valid ? local : (io.n_paths - 1);  // tail lanes shadow the last path, write nothing
     const uint64_t path = io.path_begin + li;
@@ -252,16 +272,16 @@ __global__ __launch_bounds__(SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0
                 if (((row >> 1) & (kSplitVotePairs - 1)) == 0) { if (__syncthreads_or(__builtin_amdgcn_ballot_w64(lane_alive) != 0ull ? 1 : 0) == 0) wg_dead = true; }
                 else __syncthreads();
             } else {
-                if ((row & 2) == 0) growth_rows2<0>(P, GR, io.seed, io.stream_id, path, (uint32_t)row >> 2, tab, stage, carry);
-                else growth_rows2<1>(P, GR, io.seed, io.stream_id, path, (uint32_t)row >> 2, tab, stage, carry);
+                if ((row & 2) == 0) growth_rows2<0, kPaths>(P, GR, io.seed, io.stream_id, path, (uint32_t)row >> 2, tab, stage, carry);
+                else growth_rows2<1, kPaths>(P, GR, io.seed, io.stream_id, path, (uint32_t)row >> 2, tab, stage, carry);
             }
         }
     };
     // gross factors of month `row` (:522-532)
     auto growth = [&](int row, double& g1, double& ginf, double& g2) {
         if (kStaged) {
-            const double* c = stage + (size_t)(3 * (row & 1)) * kBlock + (SPLIT ? (size_t)((row >> 1) & 1) * kStageDoubles : 0);
-            g1 = c[0]; ginf = c[kBlock]; g2 = c[2 * kBlock];
+            const double* c = stage + (size_t)(3 * (row & 1)) * kPaths + (SPLIT ? (size_t)((row >> 1) & 1) * kStageLen : 0);
+            g1 = c[0]; ginf = c[kPaths]; g2 = c[2 * kPaths];
             return;
         }
         double ze, zi, zp;
@@ -309,10 +329,10 @@ __global__ __launch_bounds__(SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0
     if (SPLIT && producer) {
         // Rows [first_row, last_row), a pair per iteration, one barrier per pair: exactly the barriers the consumers execute
         // in begin_month at every even row they visit (they visit every row of this range, in order, and never leave early).
-        const int first_row = PHASE == 2 ? (wm & ~1) : 0;                 // PHASE 2 resumes with the pair that holds row wm
+        const int first_row = kCand ? (wm & ~1) : 0;                      // PHASE 2 / 5 resume with the pair that holds row wm
         const int last_row = PHASE == 1 ? wm : P.total_months;
-        if (PHASE == 2) {
-            const unsigned long long cw = f64_bits(*snap_at((int)blockIdx.y, 9));
+        if (kCand) {
+            const unsigned long long cw = f64_bits(*snap_at((int)cand, 9));
             carry.w2 = (uint32_t)cw; carry.w3 = (uint32_t)(cw >> 32);
         }
         // PHASE 1: the Philox words carried past the end of candidate month m are those in hand once the pair that holds row
@@ -323,9 +343,9 @@ __global__ __launch_bounds__(SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0
         };
         if (PHASE == 1) while (snap_i < io.n_snap && io.snap_months[snap_i] == 0) put_carry();
         for (int row = first_row; row < last_row; row += 2) {
-            double* st = stage + (size_t)((row >> 1) & 1) * kStageDoubles;
-            if ((row & 2) == 0) growth_rows2<0>(P, GR, io.seed, io.stream_id, path, (uint32_t)row >> 2, tab, st, carry);
-            else growth_rows2<1>(P, GR, io.seed, io.stream_id, path, (uint32_t)row >> 2, tab, st, carry);
+            double* st = stage + (size_t)((row >> 1) & 1) * kStageLen;
+            if ((row & 2) == 0) growth_rows2<0, kPaths>(P, GR, io.seed, io.stream_id, path, (uint32_t)row >> 2, tab, st, carry);
+            else growth_rows2<1, kPaths>(P, GR, io.seed, io.stream_id, path, (uint32_t)row >> 2, tab, st, carry);
             if (PHASE == 1) while (snap_i < io.n_snap && ((io.snap_months[snap_i] - 1) >> 1) == (row >> 1)) put_carry();
             if (((row >> 1) & (kSplitVotePairs - 1)) == 0) { if (__syncthreads_or(0) == 0) return; }   // (the consumers' vote, begin_month)
             else __syncthreads();
@@ -439,6 +459,8 @@ __global__ __launch_bounds__(SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0
             asm volatile("" : "+s"(S1.amount), "+s"(S1.keep), "+s"(S1.start_month), "+s"(S1.end_month), "+s"(S1.indexed), "+s"(S1.lock_slot));
         }
     }
+    // PHASE 5: this wave's spending level, an SGPR (kernel-argument array, wave-uniform index)
+    const double fan_expenses = kFan ? io.fan_expenses[fan_j] : 0.0;
     int ruin_bin = pre_fail ? 0 : -1;
     int done_years = 0;  // completed (observed) retirement years = non-NaN WR entries
     int year = 0;
@@ -462,7 +484,7 @@ __global__ __launch_bounds__(SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0
                 double g1, ginf, g2;
                 if (kStaged) growth(wm + rmi, g1, ginf, g2);           // staged factors: the LDS reads are issued early
                 const double price = infl;                             // :644
-                const double expenses = P.monthly_expenses * price;    // :645-647
+                const double expenses = (kFan ? fan_expenses : P.monthly_expenses) * price;   // :645-647
                 // exact form: income accumulates (:649-677) and need = max(0, expenses - income); tolerance form: `income` runs
                 // DOWN from the expenses, one FMA per indexed stream ((amount keep) price), one subtraction per frozen stream
                 // (its slot holds the netted amount): need = max(0, what is left)
@@ -474,7 +496,7 @@ __global__ __launch_bounds__(SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0
                         if (TOL) { income = __builtin_fma(-S.amount_keep, price, income); return; }
                         nominal = S.amount * price;                    // :661-665
                     } else if (!XS || S.lock_slot < P.n_lock_slots) {      // (wave-uniform; without XS every slot is an LDS column)
-                        double* slot = lock_lds + (size_t)S.lock_slot * kBlock + tid;
+                        double* slot = lock_lds + (size_t)S.lock_slot * kPaths + tid;
                         if (rmi == S.start_month) *slot = (TOL ? S.amount_keep : S.amount) * price;  // :667-671 (first active month)
                         nominal = *slot;                               // :672-674
                     } else {                                           // a slot beyond the LDS budget: the lane's column of the overflow block
@@ -673,6 +695,18 @@ __global__ __launch_bounds__(SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0
 #endif
     // success count: wave ballot + popcount -> LDS -> one atomic per workgroup
     const unsigned long long ok = __builtin_amdgcn_ballot_w64(valid && succeeded);
+    if (kFan) {   // one count per level: consumer wave j -> blk[j] -> counters of level j (the producer has returned)
+        if ((threadIdx.x & 63) == 0) blk[fan_j] = (unsigned int)__popcll(ok);
+        __syncthreads();
+        if (threadIdx.x < (unsigned)io.fan_n && io.out.counters) {
+            uint64_t* c = io.out.counters + (size_t)threadIdx.x * MCR_N_COUNTERS;
+            const uint64_t first = (uint64_t)path_block * kPaths;
+            const uint64_t cnt = io.n_paths - first < (uint64_t)kPaths ? io.n_paths - first : (uint64_t)kPaths;
+            atomicAdd((unsigned long long*)&c[MCR_CTR_SUCCESS], (unsigned long long)blk[threadIdx.x]);
+            atomicAdd((unsigned long long*)&c[MCR_CTR_PATHS], (unsigned long long)cnt);
+        }
+        return;
+    }
     if ((threadIdx.x & 63) == 0) atomicAdd(&blk[0], (unsigned int)__popcll(ok));
     const bool want_bins = io.out.ruin_year_bins != nullptr || io.out.wr_obs_counts != nullptr;
     if (want_bins && valid) {
@@ -1669,6 +1703,136 @@ int mcr_probe_months_rng(const mcr_params* p, const mcr_rng* rng, uint32_t strea
         std::memset(&o, 0, sizeof(o));
         o.counters = counts + (size_t)c * MCR_N_COUNTERS;
         first_rc = launch_paths(p, rng, stream_id, path_begin, n_paths, working_months[c], nullptr, &o, f->side[c % used]);
+    }
+    // always join, also after a failed launch: `main` must not run ahead of work already forked
+    for (int i = 0; i < used; ++i) {
+        if ((e = hipEventRecord(f->done[i], f->side[i])) != hipSuccess) return hip_fail(e, "probe join record");
+        if ((e = hipStreamWaitEvent(main, f->done[i], 0)) != hipSuccess) return hip_fail(e, "probe join wait");
+    }
+    return first_rc;
+}
+
+// LDS of an expense fan-out launch (path_kernel PHASE 5): STATIC = the math tables and the double-buffered 64-column stage
+// (+ the unused summary / segment words); DYNAMIC = the level counters and [n_lock_slots][64] lock columns per consumer wave.
+// Every lock slot stays in LDS (no overflow block in this form): the levels per launch are lowered until they fit.
+static size_t fanout_static_lds() { return (size_t)kMathTabBytes + (size_t)2 * 6 * 64 * sizeof(double) + 512; }   // (16 640 B compiled)
+static size_t fanout_dynamic_lds(const DevParams& d, int levels) {
+    return (size_t)MCR_MAX_EXPENSE_FANOUT * sizeof(unsigned int) + (size_t)levels * (size_t)d.n_lock_slots_total * 64 * sizeof(double);
+}
+static int fanout_max_levels(const DevParams& d) {
+    int l = MCR_MAX_EXPENSE_FANOUT;
+    while (l > 0 && fanout_static_lds() + fanout_dynamic_lds(d, l) > kLdsPerWorkgroup) --l;
+    return l;
+}
+// Below this many path-wavefronts per level (n_paths / 64) the per-level route runs instead: MCR_EXPENSE_FANOUT_MIN_WAVES
+// overrides it (0 = always fan out where the shape allows; a huge value = never).
+static uint64_t fanout_min_waves() {
+    const char* e = std::getenv("MCR_EXPENSE_FANOUT_MIN_WAVES");
+    return (e && *e) ? (uint64_t)std::strtoull(e, nullptr, 10) : 0u;
+}
+
+// Several spending levels over the same paths, Philox stream: ONE accumulation sweep to working_months (PHASE 1, one
+// snapshot), then expense fan-out launches (PHASE 5) over groups of at most MCR_MAX_EXPENSE_FANOUT levels.  Returns
+// MCR_ERR_UNSUPPORTED, having enqueued nothing, for shapes this form does not cover.
+static int probe_expenses_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                                 int32_t wm, const double* levels, int32_t n_levels, uint64_t* counts, hipStream_t stream) {
+    if (rng->kind != MCR_RNG_PHILOX || n_levels < 2 || n_paths == 0 || n_paths > ((uint64_t)1 << 31)) return MCR_ERR_UNSUPPORTED;
+    if ((n_paths + 63) / 64 < fanout_min_waves()) return MCR_ERR_UNSUPPORTED;
+    DevParams d;
+    int rc = derive_params(p, wm, &d);
+    if (rc != MCR_OK) return rc;
+    if (d.n_extra_streams > 0 || (d.exact_month && !kExactMonthDefault)) return MCR_ERR_UNSUPPORTED;
+    // the producer / consumer barrier counts (see launch_paths): producers run rows [wm & ~1, total_months)
+    if (d.total_months != d.working_months + kMPY * d.retirement_years) { set_error("internal: total_months != working_months + 12 retirement_years"); return MCR_ERR_INVALID_ARG; }
+    const int lmax = fanout_max_levels(d);
+    if (lmax < 2) return MCR_ERR_UNSUPPORTED;
+    DevParams d1 = d;    // (PHASE 1 never reads a lock column: its plan may lower the LDS slots)
+    size_t lds1 = 0;
+    if (plan_path_kernel_lds(d1, 0, false, false, true, 0, &lds1) != MCR_OK) { (void)hipGetLastError(); return MCR_ERR_UNSUPPORTED; }
+    d.n_lock_slots = d.n_lock_slots_total;
+    KernelIO io;
+    std::memset(&io, 0, sizeof(io));
+    fill_io_rng(io, rng, nullptr);
+    io.stream_id = stream_id; io.path_begin = path_begin; io.n_paths = n_paths;
+    io.n_snap = 1;
+    io.snap_stride = (int64_t)((n_paths + 63) / 64 * 64);
+    io.snap_months[0] = wm;
+    const size_t snap_bytes = (size_t)kSnapFields * (size_t)io.snap_stride * sizeof(double);
+    void* mem = nullptr;
+    if (hipMallocAsync(&mem, snap_bytes, stream) != hipSuccess) { (void)hipGetLastError(); return MCR_ERR_UNSUPPORTED; }
+    io.snap = (double*)mem;
+    const dim3 block(kBlock), block2(2 * kBlock), g1((unsigned)((n_paths + kBlock - 1) / kBlock)), g5((unsigned)((n_paths + 63) / 64));
+    const bool split1 = (uint64_t)g1.x * (kBlock / 64) <= split_max_waves();
+    const int n_groups = (n_levels + lmax - 1) / lmax;   // groups of near-equal size
+#define MCR_FAN(T, A)                                                                                                   \
+    do {                                                                                                               \
+        if (split1) hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 1, true>), g1, block2, lds1, stream, d1, io, (const DevParams*)nullptr); \
+        else hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 1>), g1, block, lds1, stream, d1, io, (const DevParams*)nullptr);            \
+        for (int g = 0, first = 0; g < n_groups; ++g) {                                                                 \
+            const int lg = n_levels / n_groups + (g < n_levels % n_groups ? 1 : 0);                                    \
+            KernelIO fio = io;                                                                                         \
+            fio.out.counters = counts + (size_t)first * MCR_N_COUNTERS;                                                \
+            fio.fan_n = lg;                                                                                            \
+            for (int k = 0; k < lg; ++k) fio.fan_expenses[k] = levels[first + k];                                     \
+            hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 5, true>), g5, dim3(64 * (lg + 1)), fanout_dynamic_lds(d, lg), \
+                               stream, d, fio, (const DevParams*)nullptr);                                             \
+            first += lg;                                                                                               \
+        }                                                                                                              \
+    } while (0)
+#define MCR_FAN_A(T) do { if (d.any_annual_tax) MCR_FAN(T, true); else MCR_FAN(T, false); } while (0)
+    switch (d.tax_mask) { case 0: MCR_FAN_A(0); break; case 1: MCR_FAN_A(1); break; case 2: MCR_FAN_A(2); break; default: MCR_FAN_A(3); break; }
+#undef MCR_FAN_A
+#undef MCR_FAN
+    const hipError_t e = hipGetLastError();
+    const hipError_t ef = hipFreeAsync(mem, stream);
+    if (e != hipSuccess) return hip_fail(e, "expense fan-out probe");
+    if (ef != hipSuccess) return hip_fail(ef, "expense fan-out probe (free)");
+    return MCR_OK;
+}
+
+int mcr_probe_expenses_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                           uint64_t n_paths, int32_t working_months, const double* monthly_expenses, int32_t n_levels,
+                           uint64_t* counts, int device, void* hip_stream) {
+    MCR_ENTER_DEVICE(device);
+    if (n_levels < 0) { set_error("n_levels %d must be >= 0", n_levels); return MCR_ERR_INVALID_ARG; }
+    if (n_levels == 0) return MCR_OK;
+    if (!monthly_expenses || !counts) { set_error("null levels / counts"); return MCR_ERR_INVALID_ARG; }
+    // validate every level BEFORE enqueueing anything (counts stay untouched on an error)
+    DevParams d;
+    int rc = derive_params(p, working_months, &d);
+    if (rc != MCR_OK) return rc;
+    rc = check_rng(rng);
+    if (rc != MCR_OK) return rc;
+    for (int32_t k = 0; k < n_levels; ++k)
+        if (!(std::isfinite(monthly_expenses[k]) && monthly_expenses[k] >= 0.0)) {
+            set_error("monthly_expenses[%d] = %g: must be finite and >= 0 (config.py:59)", k, monthly_expenses[k]);
+            return MCR_ERR_INVALID_ARG;
+        }
+    hipStream_t main = (hipStream_t)hip_stream;
+    hipError_t e = hipMemsetAsync(counts, 0, sizeof(uint64_t) * MCR_N_COUNTERS * (size_t)n_levels, main);
+    if (e != hipSuccess) return hip_fail(e, "probe counters memset");
+    mcr_params q = *p;
+    mcr_outputs o;
+    std::memset(&o, 0, sizeof(o));
+    if (n_levels == 1) {
+        q.monthly_expenses = monthly_expenses[0];
+        o.counters = counts;
+        return launch_paths(&q, rng, stream_id, path_begin, n_paths, working_months, nullptr, &o, main);
+    }
+    const int frc = probe_expenses_fanout(p, rng, stream_id, path_begin, n_paths, working_months, monthly_expenses, n_levels, counts, main);
+    if (frc != MCR_ERR_UNSUPPORTED) return frc;     // (unsupported shape / allocation refused: one launch per level below)
+    StreamForkLease fork_lease(device);
+    StreamFork* f = fork_lease.f;
+    if (!f) { set_error("could not create probe streams"); return MCR_ERR_HIP; }
+    const int used = n_levels < kForkStreams ? n_levels : kForkStreams;
+    if ((e = hipEventRecord(f->fork, main)) != hipSuccess) return hip_fail(e, "probe fork");
+    for (int i = 0; i < used; ++i)
+        if ((e = hipStreamWaitEvent(f->side[i], f->fork, 0)) != hipSuccess) return hip_fail(e, "probe fork wait");
+    int first_rc = MCR_OK;
+    for (int32_t k = 0; k < n_levels && first_rc == MCR_OK; ++k) {
+        q.monthly_expenses = monthly_expenses[k];
+        o.counters = counts + (size_t)k * MCR_N_COUNTERS;
+        first_rc = launch_paths(&q, rng, stream_id, path_begin, n_paths, working_months, nullptr, &o, f->side[k % used]);
     }
     // always join, also after a failed launch: `main` must not run ahead of work already forked
     for (int i = 0; i < used; ++i) {

@@ -786,6 +786,64 @@ class RetirementMonteCarloSimulator:
         return best, best_prob, curve
 
 
+    # ---- maximum-spending search -----------------------------------------------------------------
+    def success_probability_by_expenses(self, working_months: int, monthly_expenses: Sequence[float],
+                                        num_simulations: Optional[int] = None) -> np.ndarray:
+        """Success % of each ``monthly_expenses`` level at ``working_months``, over the active seed stream's batch of
+        ``num_simulations`` paths (default ``num_simulations_main``), from the expense fan-out probe
+        (``mcr_probe_expenses_rng``).  Aligned with the input; each value equals, bit for bit,
+        ``_success_probability(run_monte_carlo_simulations(working_months, n)[0])`` of a simulator whose config differs
+        only in ``monthly_expenses``.  Under a process group the levels go through ``distributed.probe_candidates`` (as
+        candidate indices), so every rank returns the same array."""
+        levels = [float(x) for x in monthly_expenses]
+        n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
+        wm = int(working_months)
+        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
+
+        def probe(path_begin, count, idx):
+            return E.probe_expenses(params, rng, self._stream_id, path_begin, count, wm, [levels[i] for i in idx], device=dev)
+
+        if not levels:
+            return np.zeros(0, dtype=np.float64)
+        counts = D.probe_candidates(list(range(len(levels))), n, self.shard_min_paths, probe)
+        return np.array([float(np.float64(int(counts[i, N.MCR_CTR_SUCCESS])) / np.float64(n) * 100.0)
+                         for i in range(len(levels))], dtype=np.float64)
+
+    def find_maximum_monthly_expenses(
+        self,
+        working_months: int,
+        verbose: bool = True,
+        progress_callback: Optional[Callable[[dict], None]] = None,
+        resolution: float = 1.0,
+    ) -> Tuple[float, float, List[Dict[str, float]]]:
+        """Largest ``monthly_expenses`` (whole cents) that still reaches ``target_probability`` when retiring after
+        ``working_months``: search stream, ``num_simulations_search`` paths, ``MCR_MAX_EXPENSE_FANOUT`` levels per probe
+        (`spending.search_maximum_expenses`).  Returns ``(expenses, probability, curve)``; ``expenses == -1.0`` when even
+        zero spending misses the target.  Deterministic for a given seed, and the same on every rank."""
+        from .spending import EXPENSE_CAP, search_maximum_expenses
+
+        self.use_search_seeds()
+        p = self.params_model
+        n_sims, target = int(p.num_simulations_search), float(p.target_probability)
+        if verbose:
+            logger.info(f"Searching the maximum monthly expenses at {int(working_months)} working months for '{p.Nickname}' "
+                        f"(target {target:.2f}%, {n_sims} sims per level, resolution {resolution}).")
+
+        def probe_levels(levels):
+            return list(self.success_probability_by_expenses(working_months, levels, n_sims))
+
+        expenses, prob, curve = search_maximum_expenses(
+            probe_levels, target, max(float(p.monthly_expenses), 1.0), levels_per_call=N.MCR_MAX_EXPENSE_FANOUT,
+            resolution=resolution, cap=EXPENSE_CAP, on_level=progress_callback)
+        if verbose:
+            if expenses < 0:
+                logger.warning(f"Target not met even without spending: {prob:.2f}% at {int(working_months)} months.")
+            else:
+                logger.info(f"  Expense search complete: {expenses:.2f} per month with prob {prob:.2f}% "
+                            f"({len(curve)} levels evaluated).")
+        return expenses, prob, curve
+
+
 #: the engine's own batch driver: the search takes the count-only fast path only while this is what a call reaches
 _ENGINE_RUN = RetirementMonteCarloSimulator.run_monte_carlo_simulations
 
