@@ -8,6 +8,8 @@ switch to the final seed stream, run the final batch, print the response documen
     python examples/run_scenario.py scenarios/config.json --paths 10000000 --working-months 233 --compact
     python examples/run_scenario.py scenarios/config.json --events --full > response.json
     python examples/run_scenario.py scenarios/config.json --working-months 240 --max-expenses
+    python examples/run_scenario.py scenarios/config.json --frontier 180,240,300
+    python examples/run_scenario.py scenarios/config.json --grid-months 180,240 --grid-expenses 3000,4000,5000
 
 `--rng numpy` uses the reference's own NumPy stream (same seed -> the reference's numbers); `--rng philox`
 (default) the engine's counter-based stream.  `--compact` assembles the document from device-side aggregates
@@ -15,7 +17,9 @@ only (no per-path lists: for batches far beyond the UI's).  `--events` writes th
 endpoint would stream to stderr, one JSON per line.  Without `--full` only the `summary` block (plus timings
 and sizes) is printed.  `--max-expenses` answers the other planning question instead: the largest monthly spending
 (whole cents) that still reaches the target when retiring after `--working-months` (or the searched minimum), printed
-with its probability and the search curve as one JSON object."""
+with its probability and the search curve as one JSON object.  `--frontier` runs that search for several retirement months
+at once (one grid probe per round) and prints a JSON list of `{working_months, max_monthly_expenses, probability,
+levels_evaluated}`; `--grid-months` with `--grid-expenses` prints the success-probability table of those months x levels."""
 
 from __future__ import annotations
 
@@ -45,6 +49,9 @@ def main() -> int:
     ap.add_argument("--full", action="store_true", help="print the whole response document")
     ap.add_argument("--max-expenses", action="store_true", help="search the maximum monthly expenses instead")
     ap.add_argument("--resolution", type=float, default=1.0, help="--max-expenses: stop when the bracket is this narrow")
+    ap.add_argument("--frontier", default=None, help="comma-separated working months: maximum monthly expenses at each")
+    ap.add_argument("--grid-months", default=None, help="comma-separated working months of a success-probability table")
+    ap.add_argument("--grid-expenses", default=None, help="comma-separated monthly expenses of that table")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -76,6 +83,12 @@ def main() -> int:
 
     if args.max_expenses:
         return max_expenses(args, config, world, rank0)
+    if args.frontier or args.grid_months or args.grid_expenses:
+        if args.frontier and (args.grid_months or args.grid_expenses):
+            ap.error("--frontier and --grid-* are separate questions")
+        if not args.frontier and not (args.grid_months and args.grid_expenses):
+            ap.error("--grid-months and --grid-expenses go together")
+        return frontier_or_grid(args, config, world, rank0)
     builder = R.compact_result if args.compact else R.build_result
     doc = R.run_scenario(config, args.working_months, emit=emit, result_builder=builder,
                          main_seed_override=args.seed, rng=args.rng)
@@ -138,6 +151,34 @@ def max_expenses(args, config: Config, world: int, rank0: bool) -> int:
         dist.barrier()
         dist.destroy_process_group()
     return rc
+
+
+def _csv(text: str, kind):
+    return [kind(x) for x in text.split(",") if x.strip()]
+
+
+def frontier_or_grid(args, config: Config, world: int, rank0: bool) -> int:
+    from monte_carlo_retirement_amd.simulation import RetirementMonteCarloSimulator
+
+    sim = RetirementMonteCarloSimulator(config, main_seed_override=args.seed, rng=args.rng)
+    if args.frontier:
+        months = _csv(args.frontier, int)
+        results = sim.find_maximum_monthly_expenses_by_months(months, verbose=False, resolution=args.resolution)
+        out = [{"working_months": m, "max_monthly_expenses": expenses, "probability": prob, "levels_evaluated": len(curve)}
+               for m, (expenses, prob, curve) in zip(months, results)]
+    else:
+        months, levels = _csv(args.grid_months, int), _csv(args.grid_expenses, float)
+        table = sim.success_probability_grid(months, levels)
+        out = {"scenario": config.Nickname, "rng": args.rng, "num_simulations": int(config.num_simulations_main),
+               "working_months": months, "monthly_expenses": levels, "probability": table.tolist()}
+    if rank0:
+        print(json.dumps(out))
+    if world > 1:
+        import torch.distributed as dist
+
+        dist.barrier()
+        dist.destroy_process_group()
+    return 0
 
 
 if __name__ == "__main__":

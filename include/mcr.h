@@ -309,6 +309,22 @@ int mcr_probe_expenses_rng(const mcr_params* p, const mcr_rng* rng, uint32_t str
                            uint64_t n_paths, int32_t working_months, const double* monthly_expenses, int32_t n_levels,
                            uint64_t* counts, int device, void* hip_stream);
 
+/*
+ * Retirement-month x spending grid: counts[c][k] equals, bit for bit, the counters of a count-only mcr_run_batch_rng call with
+ * working_months[c] and p->monthly_expenses = monthly_expenses[c][k], everything else unchanged.  working_months: n_candidates
+ * >= 0 months (any order, repeats allowed); monthly_expenses: HOST [n_candidates][n_levels] row-major, each finite and >= 0.
+ * Every month and level is validated before anything is enqueued (counts stay untouched on an error); n_candidates == 0 or
+ * n_levels == 0 does nothing.  Philox stream, at most MCR_INLINE_STREAMS income streams, the tolerance month, 2 ..
+ * MCR_MAX_PROBE_CANDIDATES distinct months and at most 4 GiB of snapshots: ONE accumulation sweep stores the state at every
+ * distinct month, then one GRID FAN-OUT launch per group of levels resumes every row (grid.y) with one consumer wave per
+ * level.  One distinct month: mcr_probe_expenses_rng over the rows' levels.  Otherwise: mcr_probe_expenses_rng per row.
+ * counts: DEVICE uint64 [n_candidates][n_levels][MCR_N_COUNTERS] = {successes, paths} (zeroed by the call).  Asynchronous like
+ * mcr_probe_months_rng.
+ */
+int mcr_probe_grid_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                       uint64_t n_paths, const int32_t* working_months, int32_t n_candidates,
+                       const double* monthly_expenses, int32_t n_levels, uint64_t* counts, int device, void* hip_stream);
+
 /* _draw_shock_path (simulation.py:452-466) for n_paths paths: host out [n_paths][n_months][3]. */
 int mcr_draw_shocks_host(uint64_t seed, uint32_t stream_id, uint64_t path_begin,
                          uint64_t n_paths, int32_t n_months, double rho, double* out,

@@ -69,6 +69,15 @@ struct KernelIO {
     int32_t fan_n;
     double fan_expenses[MCR_MAX_EXPENSE_FANOUT];
 };
+// PHASE 6 (grid probe, mcr_probe_grid_rng): one record per grid row (blockIdx.y) of a launch, in device memory; path_kernel's
+// `cand_params` points at the launch's records.  Everything a row needs is wave-uniform there: scalar loads.
+struct GridCell {
+    DevParams p;                                  // the row's parameter block (working_months, stream start months, horizon)
+    double levels[MCR_MAX_EXPENSE_FANOUT];        // consumer wave j runs monthly_expenses = levels[j]
+    uint64_t* counters;                           // level j's counters: counters + j * MCR_N_COUNTERS
+    int32_t snap;                                 // the snapshot column of the row's month
+    int32_t pad;
+};
 constexpr int kSplitVotePairs = 16;   // SPLIT: pairs of months between two stop votes of a workgroup (a power of two)
 constexpr int kSnapFields = 10;   // b1 b2 c1 c2 gacc1 gacc2 infl contrib | pre_fail | Philox carry words
 
@@ -122,6 +131,9 @@ __device__ __forceinline__ void store_bits(double* p, unsigned long long bits) {
 // barriers of PHASE 2's SPLIT consumers (same row range, same vote schedule); each keeps its own lock columns in LDS and its
 // own success count (blk[j]).  The month is the issue-bound one (MM, WAVE-UNIFORM fix-ups): counts are bit-identical to a
 // count-only launch with monthly_expenses = fan_expenses[j].
+// PHASE 6 (SPLIT = true; mcr_probe_grid_rng): GRID FAN-OUT = PHASE 5 with grid.y = grid row (a working month and its own
+// levels).  Same workgroup shape, barriers and votes; the row's record (GridCell, through `cand_params`) holds its parameter
+// block (as in PHASE 2), its snapshot column of a PHASE 1 sweep that stored every distinct month, its levels and its counters.
 // EXACT = true: the month in its exact-rounding forms (mcr_device.h) instead of the tolerance form — for configurations whose
 // realized-gains rate lets the reference's denominator clamps bind (DevParams::exact_month), instantiated for the generic XS
 // variants only; -DMCR_K1_EXACT_MONTH builds a library that runs every variant that way (A/B).
@@ -138,14 +150,16 @@ constexpr bool kUniformFixups = false;
 constexpr bool kUniformFixups = true;
 #endif
 template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault>
-__global__ __launch_bounds__(PHASE == 5 ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
+__global__ __launch_bounds__((PHASE == 5 || PHASE == 6) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
                                                          const DevParams* __restrict__ cand_params) {
     static_assert(!SPLIT || (MODE == 0 && RNG == 0 && !INJ), "the producer / consumer split exists for the count-only Philox variants");
     static_assert(!XS || (PHASE == 0 && !SPLIT && TAXED == 3 && ANNUAL), "extended stream lists run the generic whole-path form");
     static_assert(PHASE != 5 || SPLIT, "the expense fan-out is a producer / consumer form");
+    static_assert(PHASE != 6 || SPLIT, "the grid fan-out is a producer / consumer form");
     // PHASE 4 = PHASE 2 (a candidate's decumulation resumed from its accumulation snapshot) time-sliced like PHASE 3: the
     // 17-month verification window of the search is 17 x 196 workgroups = 2.17 rounds of the resident slots.
-    constexpr bool kFan = PHASE == 5;                     // expense fan-out: one 64-path block, L consumer waves (levels), one producer wave
+    constexpr bool kFan = PHASE == 5 || PHASE == 6;       // expense fan-out: one 64-path block, L consumer waves (levels), one producer wave
+    constexpr bool kGrid = PHASE == 6;                    // ... of grid row blockIdx.y (GridCell)
     constexpr bool kCand = PHASE == 2 || PHASE == 4 || kFan;   // resumes from a PHASE 1 snapshot (PHASE 2 / 4: per-candidate parameter block)
     constexpr bool kSliced = PHASE == 3 || PHASE == 4;    // time-sliced path blocks
     static_assert(!kSliced || (RNG == 0 && !INJ && !SPLIT && !XS), "time-sliced blocks exist for the plain Philox variants");
@@ -168,7 +182,7 @@ __global__ __launch_bounds__(PHASE == 5 ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SP
     // argument so that its loads are provably invariant and uniform: scalar loads, like the by-value block)
     // time-sliced launches (1-D grid): which path block (of which candidate) and which segment of it this workgroup runs (seg < 0: a whole block)
     int seg = -1, seg_block = 0;
-    unsigned int path_block = blockIdx.x, cand = PHASE == 2 ? blockIdx.y : 0u;
+    unsigned int path_block = blockIdx.x, cand = (PHASE == 2 || kGrid) ? blockIdx.y : 0u;
     if (kSliced) {
         const int S = io.seg_n_split, F = io.seg_n_full, bid = (int)blockIdx.x;
         unsigned int lb = (unsigned)bid;                  // the block's position in the launch's list of (candidate, path block) pairs
@@ -177,7 +191,9 @@ __global__ __launch_bounds__(PHASE == 5 ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SP
         if (PHASE == 4) { cand = lb / (unsigned)io.seg_blocks_per_cand; path_block = lb % (unsigned)io.seg_blocks_per_cand; }
         else path_block = lb;
     }
-    const DevParams& P = (kCand && !kFan) ? cand_params[cand] : P_arg;
+    const GridCell* cell = kGrid ? reinterpret_cast<const GridCell*>(cand_params) + cand : nullptr;   // PHASE 6: the row's record
+    const DevParams& P = kGrid ? cell->p : (kCand && !kFan) ? cand_params[cand] : P_arg;
+    const int snap_c = kGrid ? cell->snap : (int)cand;   // snapshot column the row resumes from
     // LDS.  STATIC: the math tables (mcr_math.h) and, for the Philox stream, the [6][kBlock] stage of two months' gross
     // factors — static because the compiler then knows their addresses (offset 0 ...) and a table lookup is index << 3 +
     // ds_read with an immediate offset; against the dynamic region every address is `base + ...` with a base it only learns
@@ -332,7 +348,7 @@ __global__ __launch_bounds__(PHASE == 5 ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SP
         const int first_row = kCand ? (wm & ~1) : 0;                      // PHASE 2 / 5 resume with the pair that holds row wm
         const int last_row = PHASE == 1 ? wm : P.total_months;
         if (kCand) {
-            const unsigned long long cw = f64_bits(*snap_at((int)cand, 9));
+            const unsigned long long cw = f64_bits(*snap_at(snap_c, 9));
             carry.w2 = (uint32_t)cw; carry.w3 = (uint32_t)(cw >> 32);
         }
         // PHASE 1: the Philox words carried past the end of candidate month m are those in hand once the pair that holds row
@@ -401,7 +417,7 @@ __global__ __launch_bounds__(PHASE == 5 ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SP
     }
 
     if (kCand && !seg_resumed) {   // (a segment that took its predecessor's state over needs neither the snapshot nor the re-staged pair)
-        const int c = (int)cand;
+        const int c = snap_c;
         b1 = *snap_at(c, 0); b2 = *snap_at(c, 1); c1 = *snap_at(c, 2); c2 = *snap_at(c, 3);
         gacc1 = *snap_at(c, 4); gacc2 = *snap_at(c, 5); infl = *snap_at(c, 6); contrib = *snap_at(c, 7);
         pre_fail = *snap_at(c, 8) != 0.0;
@@ -460,7 +476,7 @@ __global__ __launch_bounds__(PHASE == 5 ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SP
         }
     }
     // PHASE 5: this wave's spending level, an SGPR (kernel-argument array, wave-uniform index)
-    const double fan_expenses = kFan ? io.fan_expenses[fan_j] : 0.0;
+    const double fan_expenses = kGrid ? cell->levels[fan_j] : kFan ? io.fan_expenses[fan_j] : 0.0;
     int ruin_bin = pre_fail ? 0 : -1;
     int done_years = 0;  // completed (observed) retirement years = non-NaN WR entries
     int year = 0;
@@ -698,8 +714,9 @@ __global__ __launch_bounds__(PHASE == 5 ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SP
     if (kFan) {   // one count per level: consumer wave j -> blk[j] -> counters of level j (the producer has returned)
         if ((threadIdx.x & 63) == 0) blk[fan_j] = (unsigned int)__popcll(ok);
         __syncthreads();
-        if (threadIdx.x < (unsigned)io.fan_n && io.out.counters) {
-            uint64_t* c = io.out.counters + (size_t)threadIdx.x * MCR_N_COUNTERS;
+        uint64_t* const fan_ctr = kGrid ? cell->counters : io.out.counters;
+        if (threadIdx.x < (unsigned)io.fan_n && fan_ctr) {
+            uint64_t* c = fan_ctr + (size_t)threadIdx.x * MCR_N_COUNTERS;
             const uint64_t first = (uint64_t)path_block * kPaths;
             const uint64_t cnt = io.n_paths - first < (uint64_t)kPaths ? io.n_paths - first : (uint64_t)kPaths;
             atomicAdd((unsigned long long*)&c[MCR_CTR_SUCCESS], (unsigned long long)blk[threadIdx.x]);
@@ -1570,6 +1587,25 @@ int mcr_run_batch_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_i
                         (hipStream_t)hip_stream);
 }
 
+// Ascending order of a probe's candidate months (stable): order[i] = index into `months` of the i-th smallest
+static void sort_candidates(const int32_t* months, int n, int* order) {
+    for (int i = 0; i < n; ++i) {
+        int k = i;
+        while (k > 0 && months[order[k - 1]] > months[i]) { order[k] = order[k - 1]; --k; }
+        order[k] = i;
+    }
+}
+// The device memory of a shared-accumulation probe: ONE stream-ordered allocation of snap_bytes of snapshots followed by the
+// launch's parameter records (`blocks`, uploaded from the host).  false: the allocation was refused (nothing enqueued);
+// otherwise *mem is the allocation and *copy the upload's status.
+static bool alloc_snapshots_and_blocks(size_t snap_bytes, const void* blocks, size_t blocks_bytes, hipStream_t stream, void** mem,
+                                       hipError_t* copy) {
+    *mem = nullptr;
+    if (hipMallocAsync(mem, snap_bytes + blocks_bytes, stream) != hipSuccess) { (void)hipGetLastError(); return false; }
+    *copy = hipMemcpyAsync((char*)*mem + snap_bytes, blocks, blocks_bytes, hipMemcpyHostToDevice, stream);
+    return true;
+}
+
 // Several candidates over the same paths, Philox stream: ONE accumulation sweep to the largest candidate that stores the
 // state at the end of every candidate month (PHASE 1), then ONE launch whose grid.y is the candidate and which resumes
 // every decumulation from its snapshot (PHASE 2).  The candidates' parameter blocks (stream start months, horizon) go to
@@ -1578,11 +1614,7 @@ static int probe_shared_prefix(const mcr_params* p, const mcr_rng* rng, uint32_t
                                const int32_t* working_months, int32_t n_cand, uint64_t* counts, hipStream_t stream) {
     if (n_cand < 2 || n_paths == 0 || n_paths > ((uint64_t)1 << 31)) return MCR_ERR_UNSUPPORTED;
     int order[MCR_MAX_PROBE_CANDIDATES];
-    for (int i = 0; i < n_cand; ++i) {
-        int k = i;
-        while (k > 0 && working_months[order[k - 1]] > working_months[i]) { order[k] = order[k - 1]; --k; }
-        order[k] = i;
-    }
+    sort_candidates(working_months, n_cand, order);
     for (int i = 1; i < n_cand; ++i)
         if (working_months[order[i]] == working_months[order[i - 1]]) return MCR_ERR_UNSUPPORTED;   // duplicates: plain route
     std::vector<DevParams> blocks((size_t)n_cand);
@@ -1609,10 +1641,10 @@ static int probe_shared_prefix(const mcr_params* p, const mcr_rng* rng, uint32_t
     const size_t blocks_bytes = (size_t)n_cand * sizeof(DevParams);
     if (snap_bytes > ((size_t)4 << 30)) return MCR_ERR_UNSUPPORTED;   // huge probes are throughput-bound anyway: plain route
     void* mem = nullptr;
-    if (hipMallocAsync(&mem, snap_bytes + blocks_bytes, stream) != hipSuccess) { (void)hipGetLastError(); return MCR_ERR_UNSUPPORTED; }
+    hipError_t e = hipSuccess;
+    if (!alloc_snapshots_and_blocks(snap_bytes, blocks.data(), blocks_bytes, stream, &mem, &e)) return MCR_ERR_UNSUPPORTED;
     io.snap = (double*)mem;
     const DevParams* d_blocks = (const DevParams*)((char*)mem + snap_bytes);
-    hipError_t e = hipMemcpyAsync((char*)mem + snap_bytes, blocks.data(), blocks_bytes, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) {
         const dim3 block(kBlock), g1((unsigned)((n_paths + kBlock - 1) / kBlock)), g2(g1.x, (unsigned)n_cand);
         // (either phase takes the producer / consumer split on its own while its launch leaves SIMDs idle)
@@ -1840,6 +1872,137 @@ int mcr_probe_expenses_rng(const mcr_params* p, const mcr_rng* rng, uint32_t str
         if ((e = hipStreamWaitEvent(main, f->done[i], 0)) != hipSuccess) return hip_fail(e, "probe join wait");
     }
     return first_rc;
+}
+
+// A grid of working months x spending levels over the same paths, Philox stream: ONE accumulation sweep (PHASE 1) stores
+// the state at the end of every distinct month, then grid fan-out launches (PHASE 6, grid.y = row) resume every row's
+// decumulation with up to fanout_max_levels of its levels per launch.  Rows of a repeated month share its snapshot column.
+// Returns MCR_ERR_UNSUPPORTED, having enqueued nothing, for shapes this form does not cover.
+static int probe_grid_shared(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                             const int32_t* working_months, int32_t n_rows, const double* levels, int32_t n_levels, uint64_t* counts,
+                             hipStream_t stream) {
+    if (rng->kind != MCR_RNG_PHILOX || n_rows < 2 || n_paths == 0 || n_paths > ((uint64_t)1 << 31)) return MCR_ERR_UNSUPPORTED;
+    if ((n_paths + 63) / 64 < fanout_min_waves()) return MCR_ERR_UNSUPPORTED;
+    std::vector<int> order((size_t)n_rows), col((size_t)n_rows);
+    sort_candidates(working_months, n_rows, order.data());
+    std::vector<int32_t> months;    // distinct months, ascending = the snapshot columns
+    for (int i = 0; i < n_rows; ++i) {
+        const int32_t m = working_months[order[(size_t)i]];
+        if (months.empty() || months.back() != m) months.push_back(m);
+        col[(size_t)order[(size_t)i]] = (int)months.size() - 1;
+    }
+    const int n_cand = (int)months.size();
+    if (n_cand < 2 || n_cand > MCR_MAX_PROBE_CANDIDATES) return MCR_ERR_UNSUPPORTED;
+    std::vector<DevParams> blocks((size_t)n_cand);
+    for (int c = 0; c < n_cand; ++c) {
+        const int rc = derive_params(p, months[(size_t)c], &blocks[(size_t)c]);
+        if (rc != MCR_OK) return rc;
+        DevParams& b = blocks[(size_t)c];
+        // the producer / consumer barrier counts (see launch_paths): producers run rows [wm & ~1, total_months)
+        if (b.total_months != b.working_months + kMPY * b.retirement_years) { set_error("internal: total_months != working_months + 12 retirement_years"); return MCR_ERR_INVALID_ARG; }
+        b.n_lock_slots = b.n_lock_slots_total;   // (the same for every month: it depends on the stream list only)
+    }
+    const DevParams& top = blocks[(size_t)n_cand - 1];
+    if (top.n_extra_streams > 0 || (top.exact_month && !kExactMonthDefault)) return MCR_ERR_UNSUPPORTED;
+    const int lmax = fanout_max_levels(top);
+    if (lmax < 1) return MCR_ERR_UNSUPPORTED;
+    DevParams d1 = top;    // (PHASE 1 never reads a lock column: its plan may lower the LDS slots)
+    size_t lds1 = 0;
+    if (plan_path_kernel_lds(d1, 0, false, false, true, 0, &lds1) != MCR_OK) { (void)hipGetLastError(); return MCR_ERR_UNSUPPORTED; }
+    KernelIO io;
+    std::memset(&io, 0, sizeof(io));
+    fill_io_rng(io, rng, nullptr);
+    io.stream_id = stream_id; io.path_begin = path_begin; io.n_paths = n_paths;
+    io.n_snap = n_cand;
+    io.snap_stride = (int64_t)((n_paths + 63) / 64 * 64);
+    for (int c = 0; c < n_cand; ++c) io.snap_months[c] = months[(size_t)c];
+    const size_t snap_bytes = (size_t)n_cand * kSnapFields * (size_t)io.snap_stride * sizeof(double);
+    if (snap_bytes > ((size_t)4 << 30)) return MCR_ERR_UNSUPPORTED;   // huge probes are throughput-bound anyway: per-month route
+    // the rows' records, level group by level group: group g covers levels [first_g, first_g + lg) of every row
+    const int n_groups = (n_levels + lmax - 1) / lmax;   // groups of near-equal size
+    std::vector<GridCell> cells((size_t)n_groups * (size_t)n_rows);
+    std::memset(cells.data(), 0, cells.size() * sizeof(GridCell));
+    for (int g = 0, first = 0; g < n_groups; ++g) {
+        const int lg = n_levels / n_groups + (g < n_levels % n_groups ? 1 : 0);
+        for (int r = 0; r < n_rows; ++r) {
+            GridCell& x = cells[(size_t)g * n_rows + r];
+            x.p = blocks[(size_t)col[(size_t)r]];
+            x.snap = col[(size_t)r];
+            x.counters = counts + ((size_t)r * n_levels + first) * MCR_N_COUNTERS;
+            for (int k = 0; k < lg; ++k) x.levels[k] = levels[(size_t)r * n_levels + first + k];
+        }
+        first += lg;
+    }
+    void* mem = nullptr;
+    hipError_t e = hipSuccess;
+    if (!alloc_snapshots_and_blocks(snap_bytes, cells.data(), cells.size() * sizeof(GridCell), stream, &mem, &e)) return MCR_ERR_UNSUPPORTED;
+    io.snap = (double*)mem;
+    const GridCell* d_cells = (const GridCell*)((char*)mem + snap_bytes);
+    if (e == hipSuccess) {
+        const dim3 block(kBlock), block2(2 * kBlock), g1((unsigned)((n_paths + kBlock - 1) / kBlock)), g6((unsigned)((n_paths + 63) / 64), (unsigned)n_rows);
+        const bool split1 = (uint64_t)g1.x * (kBlock / 64) <= split_max_waves();
+#define MCR_GRID(T, A)                                                                                                  \
+        do {                                                                                                           \
+            if (split1) hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 1, true>), g1, block2, lds1, stream, d1, io, (const DevParams*)nullptr); \
+            else hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 1>), g1, block, lds1, stream, d1, io, (const DevParams*)nullptr);            \
+            for (int g = 0; g < n_groups; ++g) {                                                                       \
+                const int lg = n_levels / n_groups + (g < n_levels % n_groups ? 1 : 0);                                \
+                KernelIO gio = io;                                                                                     \
+                gio.fan_n = lg;                                                                                        \
+                hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 6, true>), g6, dim3(64 * (lg + 1)), fanout_dynamic_lds(top, lg), \
+                                   stream, top, gio, (const DevParams*)(d_cells + (size_t)g * n_rows));               \
+            }                                                                                                          \
+        } while (0)
+#define MCR_GRID_A(T) do { if (top.any_annual_tax) MCR_GRID(T, true); else MCR_GRID(T, false); } while (0)
+        switch (top.tax_mask) { case 0: MCR_GRID_A(0); break; case 1: MCR_GRID_A(1); break; case 2: MCR_GRID_A(2); break; default: MCR_GRID_A(3); break; }
+#undef MCR_GRID_A
+#undef MCR_GRID
+        e = hipGetLastError();
+    }
+    const hipError_t ef = hipFreeAsync(mem, stream);
+    if (e != hipSuccess) return hip_fail(e, "grid probe");
+    if (ef != hipSuccess) return hip_fail(ef, "grid probe (free)");
+    return MCR_OK;
+}
+
+int mcr_probe_grid_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                       uint64_t n_paths, const int32_t* working_months, int32_t n_candidates,
+                       const double* monthly_expenses, int32_t n_levels, uint64_t* counts, int device, void* hip_stream) {
+    MCR_ENTER_DEVICE(device);
+    if (n_candidates < 0 || n_levels < 0) { set_error("n_candidates %d / n_levels %d must be >= 0", n_candidates, n_levels); return MCR_ERR_INVALID_ARG; }
+    if (n_candidates == 0 || n_levels == 0) return MCR_OK;
+    if (!working_months || !monthly_expenses || !counts) { set_error("null months / levels / counts"); return MCR_ERR_INVALID_ARG; }
+    // validate every month and every level BEFORE enqueueing anything (counts stay untouched on an error)
+    for (int32_t c = 0; c < n_candidates; ++c) {
+        DevParams d;
+        const int rc = derive_params(p, working_months[c], &d);
+        if (rc != MCR_OK) return rc;
+    }
+    int rc = check_rng(rng);
+    if (rc != MCR_OK) return rc;
+    const size_t n_cells = (size_t)n_candidates * (size_t)n_levels;
+    for (size_t k = 0; k < n_cells; ++k)
+        if (!(std::isfinite(monthly_expenses[k]) && monthly_expenses[k] >= 0.0)) {
+            set_error("monthly_expenses[%d][%d] = %g: must be finite and >= 0 (config.py:59)", (int)(k / (size_t)n_levels),
+                      (int)(k % (size_t)n_levels), monthly_expenses[k]);
+            return MCR_ERR_INVALID_ARG;
+        }
+    bool one_month = true;
+    for (int32_t c = 1; c < n_candidates; ++c) one_month = one_month && working_months[c] == working_months[0];
+    // one distinct month: the rows' levels, concatenated, are one expense probe whose counters are the [rows][levels] block
+    if (one_month && n_cells <= (size_t)INT32_MAX)
+        return mcr_probe_expenses_rng(p, rng, stream_id, path_begin, n_paths, working_months[0], monthly_expenses, (int32_t)n_cells,
+                                      counts, device, hip_stream);
+    hipStream_t main = (hipStream_t)hip_stream;
+    hipError_t e = hipMemsetAsync(counts, 0, sizeof(uint64_t) * MCR_N_COUNTERS * n_cells, main);
+    if (e != hipSuccess) return hip_fail(e, "probe counters memset");
+    rc = probe_grid_shared(p, rng, stream_id, path_begin, n_paths, working_months, n_candidates, monthly_expenses, n_levels, counts, main);
+    if (rc != MCR_ERR_UNSUPPORTED) return rc;     // (unsupported shape / allocation refused: the per-month route below)
+    rc = MCR_OK;
+    for (int32_t c = 0; c < n_candidates && rc == MCR_OK; ++c)
+        rc = mcr_probe_expenses_rng(p, rng, stream_id, path_begin, n_paths, working_months[c], monthly_expenses + (size_t)c * n_levels,
+                                    n_levels, counts + (size_t)c * n_levels * MCR_N_COUNTERS, device, hip_stream);
+    return rc;
 }
 
 int mcr_run_batch(const mcr_params* p, uint64_t seed, uint32_t stream_id, uint64_t path_begin,

@@ -351,3 +351,37 @@ def probe_expenses(params: McrParams, seed, stream_id: int, path_begin: int, n_p
     )
     N.check(rc, "mcr_probe_expenses_rng")
     return counts
+
+
+def probe_grid(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months, levels_2d,
+               device: int = 0):
+    """Success counters of a grid of working-month counts x ``monthly_expenses`` levels over the same path range
+    (``mcr_probe_grid_rng``): cell ``[c, k]`` counts exactly what a count-only launch at ``working_months[c]`` with
+    ``monthly_expenses = levels_2d[c][k]`` counts.  ``levels_2d`` is rectangular, one row per month (rows may differ).  The
+    accumulation runs once for every month and one launch per level group covers all of them.  Returns a device int64
+    tensor ``[len(working_months), n_levels, 2]`` = ``{successes, paths}``; asynchronous (reading it synchronises)."""
+    import torch
+
+    N.require_device()
+    months = [int(m) for m in working_months]
+    rows = [[float(x) for x in row] for row in levels_2d]
+    if len(rows) != len(months):
+        raise ValueError(f"levels_2d has {len(rows)} rows for {len(months)} working months")
+    n_levels = len(rows[0]) if rows else 0
+    if any(len(r) != n_levels for r in rows):
+        raise ValueError("levels_2d must be rectangular")
+    counts = torch.empty((len(months), n_levels, N.MCR_N_COUNTERS), dtype=torch.int64,
+                         device=torch.device("cuda", int(device)))
+    if not months or n_levels == 0:
+        return counts
+    marr = (C.c_int32 * len(months))(*months)
+    flat = [x for r in rows for x in r]
+    larr = (C.c_double * len(flat))(*flat)
+    rng = _as_rng(seed)
+    stream = torch.cuda.current_stream(int(device)).cuda_stream
+    rc = N.load_library().mcr_probe_grid_rng(
+        C.byref(params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), marr, len(months), larr, n_levels,
+        counts.data_ptr(), int(device), C.c_void_p(stream),
+    )
+    N.check(rc, "mcr_probe_grid_rng")
+    return counts

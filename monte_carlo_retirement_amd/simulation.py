@@ -844,6 +844,78 @@ class RetirementMonteCarloSimulator:
         return expenses, prob, curve
 
 
+    def _grid_probabilities(self, working_months: Sequence[int], levels_2d: Sequence[Sequence[float]],
+                            num_simulations: int) -> np.ndarray:
+        """Success % ``[len(working_months), n_levels]`` of month ``c`` at the levels of row ``c`` (rectangular), over the
+        active stream's batch, from the grid probe (``mcr_probe_grid_rng``).  Under a process group the rows go through
+        ``distributed.probe_candidates`` (candidate = row, ``2 n_levels`` counters each): one all-reduce, the same matrix
+        on every rank."""
+        months = [int(m) for m in working_months]
+        rows = [[float(x) for x in r] for r in levels_2d]
+        n_levels = len(rows[0]) if rows else 0
+        if not months or n_levels == 0:
+            return np.zeros((len(months), n_levels), dtype=np.float64)
+        n = int(num_simulations)
+        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
+
+        def probe(path_begin, count, idx):
+            return E.probe_grid(params, rng, self._stream_id, path_begin, count, [months[i] for i in idx],
+                                [rows[i] for i in idx], device=dev)
+
+        counts = D.probe_candidates(list(range(len(months))), n, self.shard_min_paths, probe,
+                                    width=n_levels * N.MCR_N_COUNTERS).reshape(len(months), n_levels, N.MCR_N_COUNTERS)
+        return np.array([[float(np.float64(int(counts[c, k, N.MCR_CTR_SUCCESS])) / np.float64(n) * 100.0)
+                          for k in range(n_levels)] for c in range(len(months))], dtype=np.float64).reshape(len(months), n_levels)
+
+    def success_probability_grid(self, working_months: Sequence[int], monthly_expenses: Sequence[float],
+                                 num_simulations: Optional[int] = None) -> np.ndarray:
+        """Success % of every (working month, ``monthly_expenses`` level) pair over the active seed stream's batch of
+        ``num_simulations`` paths (default ``num_simulations_main``): ``[len(working_months), len(monthly_expenses)]``.  Row
+        ``c`` equals, bit for bit, ``success_probability_by_expenses(working_months[c], monthly_expenses)``; the
+        accumulation runs once for all months (``mcr_probe_grid_rng``).  The same matrix on every rank."""
+        months = [int(m) for m in working_months]
+        levels = [float(x) for x in monthly_expenses]
+        n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
+        return self._grid_probabilities(months, [levels] * len(months), n)
+
+    def find_maximum_monthly_expenses_by_months(
+        self,
+        working_months: Sequence[int],
+        verbose: bool = True,
+        progress_callback: Optional[Callable[[dict], None]] = None,
+        resolution: float = 1.0,
+    ) -> List[Tuple[float, float, List[Dict[str, float]]]]:
+        """`find_maximum_monthly_expenses` for several retirement months at once (the max-spending frontier): one
+        ``(expenses, probability, curve)`` per entry of ``working_months``, each equal to what
+        ``find_maximum_monthly_expenses(working_months[i])`` returns for the same seed.  The searches run in lockstep
+        (`spending.search_maximum_expenses_many`): every round is ONE grid probe over the unfinished months' levels.
+        ``progress_callback`` events also carry ``working_months``."""
+        from .spending import EXPENSE_CAP, search_maximum_expenses_many
+
+        months = [int(m) for m in working_months]
+        self.use_search_seeds()
+        p = self.params_model
+        n_sims, target = int(p.num_simulations_search), float(p.target_probability)
+        if verbose:
+            logger.info(f"Searching the maximum monthly expenses at {len(months)} retirement months for '{p.Nickname}' "
+                        f"(target {target:.2f}%, {n_sims} sims per level, resolution {resolution}).")
+
+        def probe_rows(rows, levels_2d):
+            return self._grid_probabilities([months[i] for i in rows], levels_2d, n_sims).tolist()
+
+        start = max(float(p.monthly_expenses), 1.0)
+        results = search_maximum_expenses_many(
+            probe_rows, target, [start] * len(months), levels_per_call=N.MCR_MAX_EXPENSE_FANOUT, resolution=resolution,
+            cap=EXPENSE_CAP, on_level=progress_callback, working_months=months)
+        if verbose:
+            for m, (expenses, prob, curve) in zip(months, results):
+                if expenses < 0:
+                    logger.warning(f"Target not met even without spending: {prob:.2f}% at {m} months.")
+                else:
+                    logger.info(f"  {m} months: {expenses:.2f} per month with prob {prob:.2f}% ({len(curve)} levels evaluated).")
+        return results
+
+
 #: the engine's own batch driver: the search takes the count-only fast path only while this is what a call reaches
 _ENGINE_RUN = RetirementMonteCarloSimulator.run_monte_carlo_simulations
 
