@@ -62,7 +62,9 @@ struct KernelIO {
     int32_t seg_blocks_per_cand;                     // PHASE 4: path blocks per search candidate (the launch lists candidate-major)
     double* seg_state;                               // [seg_n_split][fields][kBlock] hand-over state
     int32_t seg_year[kMaxSegments + 1];              // segment k covers retirement years [seg_year[k], seg_year[k + 1]); segment 0 also the accumulation
-    unsigned int* seg_flags;                         // [seg_n_split][seg_q], zeroed before the launch
+    int32_t seg_bid_base;                            // MCR_K1_SEGMENT_ORDER (launch_sliced): workgroup blockIdx.x of this launch is workgroup
+                                                     // seg_bid_base + blockIdx.x of the single sliced launch (0 when it is one launch)
+    unsigned int* seg_flags;                         // [seg_n_split][seg_q], zeroed before the launch: 0 pending, 1 state handed over, 2 recomputed
     int32_t seg_max_polls;                           // x ~1 us: how long a successor looks for its predecessor's flag before it recomputes the block itself
     // PHASE 5 (expense fan-out, mcr_probe_expenses_rng): consumer wave j runs monthly_expenses = fan_expenses[j] and adds its
     // counts to counters + j * MCR_N_COUNTERS; fan_n = blockDim.x / 64 - 1 levels
@@ -116,7 +118,8 @@ __device__ __forceinline__ void store_bits(double* p, unsigned long long bits) {
 // other blocks, whole] [segment 1 x S] ... [segment Q - 1 x S].  A segment ends by storing its lanes' state (balances, bases,
 // gain accumulators, price level, flags, Philox carry, lock columns) and raising a flag; its successor — dispatched at least
 // S workgroups later, i.e. after it has long finished — loads it.  A successor that does not see the flag within a bounded
-// number of polls recomputes the block from month 0 itself: no workgroup ever waits on another one to make progress.
+// number of polls recomputes the block from month 0 itself: no workgroup ever waits on another one to make progress.  Such a
+// segment does not write the hand-over state (flag 2, not 1), and its successors recompute too: one writer per slot at a time.
 // The arithmetic of every path is unchanged: counts and bins are bit-identical to PHASE 0.
 // XS = true ("extended streams"): the variants that can read income-stream records beyond the by-value block from the device
 // table and keep lock slots beyond the LDS budget in the global overflow block (DevParams::extra_streams / lock_overflow:
@@ -184,7 +187,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6) ? 64 * (MCR_MAX_EXPENSE_
     int seg = -1, seg_block = 0;
     unsigned int path_block = blockIdx.x, cand = (PHASE == 2 || kGrid) ? blockIdx.y : 0u;
     if (kSliced) {
-        const int S = io.seg_n_split, F = io.seg_n_full, bid = (int)blockIdx.x;
+        const int S = io.seg_n_split, F = io.seg_n_full, bid = (int)blockIdx.x + io.seg_bid_base;
         unsigned int lb = (unsigned)bid;                  // the block's position in the launch's list of (candidate, path block) pairs
         if (bid < S) { seg = 0; seg_block = bid; }
         else if (bid >= S + F) { const int k = bid - S - F; seg = 1 + k / S; seg_block = k % S; lb = (unsigned)seg_block; }
@@ -383,13 +386,15 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6) ? 64 * (MCR_MAX_EXPENSE_
         y_end = io.seg_year[seg + 1];
         if (seg > 0) {
             if (threadIdx.x == 0) {
+                // the predecessor's flag: 0 pending, 1 state handed over, 2 recomputed (the slot is not its state).  Resume on 1
+                // only; on 2, or when the budget runs out, recompute at once (see the hand-over at the end of the segment)
                 const unsigned int* f = io.seg_flags + (size_t)seg_block * (size_t)io.seg_q + (size_t)(seg - 1);
-                int ok = 0;
+                unsigned int v = 0u;
                 for (int spin = 0; spin < io.seg_max_polls; ++spin) {
-                    if (__hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != 0u) { ok = 1; break; }
+                    if ((v = __hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT)) != 0u) break;
                     __builtin_amdgcn_s_sleep(32);
                 }
-                seg_ok_s = ok;
+                seg_ok_s = v == 1u;
             }
             __syncthreads();
             seg_resumed = seg_ok_s != 0;     // (otherwise: this workgroup runs the block from month 0 itself, up to its own end)
@@ -659,21 +664,34 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6) ? 64 * (MCR_MAX_EXPENSE_
         if (kTraj && valid && wrt) store_bits(&wrt[(int64_t)year * stride + (int64_t)li], kNanBits);
     }
     if (kSliced && seg >= 0 && seg < io.seg_q - 1) {
-        // not the block's last segment: hand the lanes' state over and raise the flag (every wave gets here: no early return above)
-        *seg_at(0) = b1; *seg_at(1) = b2; *seg_at(2) = c1; *seg_at(3) = c2;
-        if (ANNUAL) { *seg_at(4) = gacc1; *seg_at(5) = gacc2; }
-        *seg_at(6) = infl;
-        store_bits(seg_at(7), (alive ? 1ull : 0ull) | (succeeded ? 2ull : 0ull) | ((unsigned long long)(ruin_bin + 1) << 8) | ((unsigned long long)done_years << 24));
-        store_bits(seg_at(8), ((unsigned long long)carry.w3 << 32) | (unsigned long long)carry.w2);
-        for (int k = 0; k < P.n_lock_slots; ++k) *seg_at(kSegFixedFields + k) = lock_lds[(size_t)k * kBlock + tid];
-        if (MODE >= 1) {
-            *seg_at(9) = start_balance; *seg_at(10) = infl_ret;
-            *seg_at(11) = sum_col[0]; *seg_at(12) = sum_col[kBlock]; *seg_at(13) = sum_col[2 * kBlock];
+        // Not the block's last segment: raise the flag, to 1 with the lanes' state handed over, or to 2 (every wave gets here:
+        // no early return above).  SINGLE WRITER: only segment 0 and a segment that resumed from flag 1 write the block's one
+        // slot; a segment that recomputed (its predecessor's flag stayed 0 for the whole budget, or was 2) leaves the slot alone
+        // and raises 2, and its successors recompute too.  So the writers of a slot are segments 0, 1, ..., j, each the end of a
+        // chain of flag-1 hand-overs back to segment 0: segment k reads and then writes (each lane its own column, in program
+        // order) only after its acquire of flag k - 1 == 1, which segment k - 1 released after its own write.  The slot's reads
+        // and writes are totally ordered by those release / acquire pairs: a resumed segment reads exactly its predecessor's
+        // state, never a stale or torn one.  (A late predecessor of a segment that timed out still writes, but no one reads the
+        // slot after that: the timed-out segment raised 2, and every later segment of the block recomputes.)
+        // (seg_resumed re-read from LDS: kept live to here it costs the summary variants 3 VGPRs; an atomic load, or the compiler
+        // forwards the first load)
+        const bool hand_over = seg == 0 || __hip_atomic_load(&seg_ok_s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0;
+        if (hand_over) {
+            *seg_at(0) = b1; *seg_at(1) = b2; *seg_at(2) = c1; *seg_at(3) = c2;
+            if (ANNUAL) { *seg_at(4) = gacc1; *seg_at(5) = gacc2; }
+            *seg_at(6) = infl;
+            store_bits(seg_at(7), (alive ? 1ull : 0ull) | (succeeded ? 2ull : 0ull) | ((unsigned long long)(ruin_bin + 1) << 8) | ((unsigned long long)done_years << 24));
+            store_bits(seg_at(8), ((unsigned long long)carry.w3 << 32) | (unsigned long long)carry.w2);
+            for (int k = 0; k < P.n_lock_slots; ++k) *seg_at(kSegFixedFields + k) = lock_lds[(size_t)k * kBlock + tid];
+            if (MODE >= 1) {
+                *seg_at(9) = start_balance; *seg_at(10) = infl_ret;
+                *seg_at(11) = sum_col[0]; *seg_at(12) = sum_col[kBlock]; *seg_at(13) = sum_col[2 * kBlock];
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         __syncthreads();
         if (threadIdx.x == 0)
-            __hip_atomic_store(io.seg_flags + (size_t)seg_block * (size_t)io.seg_q + (size_t)seg, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(io.seg_flags + (size_t)seg_block * (size_t)io.seg_q + (size_t)seg, hand_over ? 1u : 2u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
         return;
     }
 
@@ -1377,6 +1395,52 @@ static bool plan_segments(const DevParams& d, unsigned n_blocks, int mode, Segme
     plan->year[q] = d.retirement_years;
     return true;
 }
+// MCR_K1_SEGMENT_ORDER=k_0,k_1,...,k_(q-1) (tests; read at every launch): a time-sliced grid goes out as 1 + q launches on the
+// stream instead of one — the whole blocks first, then the pieces of n_split workgroups of segment k_0, k_1, ... — so that every
+// order in which the segments of a block can run is reproducible: launches on one stream run one after another, so a segment
+// whose predecessor's piece comes later sees its flag at 0 for its whole poll budget, and one whose predecessor's piece came
+// earlier sees it raised at its first poll.  Set on a launch that does not slice, or not a permutation of 0 .. q - 1: an error
+// (a test must never pass by comparing the plain launch with itself).
+static const char* segment_order_env() {
+    const char* e = std::getenv("MCR_K1_SEGMENT_ORDER");
+    return (e && *e) ? e : nullptr;
+}
+static int parse_segment_order(const char* e, int q, int* order) {
+    int n = 0;
+    unsigned seen = 0u;
+    for (const char* s = e;; ) {
+        char* end = nullptr;
+        const long k = std::strtol(s, &end, 10);
+        if (end == s || k < 0 || k >= q || n >= q || ((seen >> k) & 1u) || (*end != ',' && *end != '\0')) {
+            set_error("MCR_K1_SEGMENT_ORDER=%s is not a permutation of the launch's %d segments 0..%d", e, q, q - 1);
+            return MCR_ERR_INVALID_ARG;
+        }
+        seen |= 1u << k;
+        order[n++] = (int)k;
+        if (*end == '\0') break;
+        s = end + 1;
+    }
+    if (n != q) { set_error("MCR_K1_SEGMENT_ORDER=%s is not a permutation of the launch's %d segments 0..%d", e, q, q - 1); return MCR_ERR_INVALID_ARG; }
+    return MCR_OK;
+}
+// The time-sliced grid [segment 0 x S] [F whole blocks] [segment 1 x S] ... [segment q - 1 x S]: one launch, or (order != nullptr,
+// MCR_K1_SEGMENT_ORDER) the F whole blocks followed by one launch of S workgroups per segment in the given order.
+template <typename Kernel>
+static void launch_sliced(Kernel kernel, const SegmentPlan& plan, const int* order, dim3 block, size_t lds, hipStream_t stream,
+                          const DevParams& d, KernelIO io, const DevParams* cand) {
+    if (!order) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(plan.n_full + plan.q * plan.n_split)), block, lds, stream, d, io, cand);
+        return;
+    }
+    if (plan.n_full > 0) {
+        io.seg_bid_base = plan.n_split;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)plan.n_full), block, lds, stream, d, io, cand);
+    }
+    for (int i = 0; i < plan.q; ++i) {
+        io.seg_bid_base = order[i] == 0 ? 0 : plan.n_split + plan.n_full + (order[i] - 1) * plan.n_split;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)plan.n_split), block, lds, stream, d, io, cand);
+    }
+}
 
 static int check_rng(const mcr_rng* rng) {
     if (!rng) { set_error("null rng"); return MCR_ERR_INVALID_ARG; }
@@ -1452,6 +1516,12 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
     //     (and configurations that need the exact month: the generic variants carry both forms of it)
     const bool exact = d.exact_month && !kExactMonthDefault;
     const bool xs = d.n_lock_slots < d.n_lock_slots_total || d.n_extra_streams > 0 || exact;
+    const char* seg_order = segment_order_env();
+    if (seg_order && (np_rng || injected || xs || split)) {
+        set_error("MCR_K1_SEGMENT_ORDER=%s set on a launch that is not time-sliced (%s)", seg_order,
+                  np_rng ? "NumPy stream" : injected ? "injected shocks" : xs ? "extended streams / exact month" : "producer / consumer split");
+        return MCR_ERR_INVALID_ARG;
+    }
     StreamSideBlock side;
     rc = side.attach(d, extra, grid.x, stream);
     if (rc != MCR_OK) { (void)side.release(stream); return rc; }
@@ -1472,7 +1542,14 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
     // would be mostly empty (plan_segments).  MCR_K1_SEGMENTS = segments per sliced block (default 6 or 8; 0 or 1 = never).
     if (!np_rng && !injected && !xs && !split) {
         SegmentPlan plan;
-        if (plan_segments(d, grid.x, mode, &plan)) {
+        const bool sliced = plan_segments(d, grid.x, mode, &plan);
+        int order[kMaxSegments];
+        if (seg_order) {
+            if (!sliced) { set_error("MCR_K1_SEGMENT_ORDER=%s set on a launch that is not time-sliced (%u workgroups)", seg_order, grid.x); return MCR_ERR_INVALID_ARG; }
+            rc = parse_segment_order(seg_order, plan.q, order);
+            if (rc != MCR_OK) return rc;
+        }
+        if (sliced) {
             const size_t state_bytes = (size_t)plan.n_split * (size_t)((mode >= 1 ? 14 : 9) + d.n_lock_slots) * kBlock * sizeof(double);
             const size_t flag_bytes = (size_t)plan.n_split * (size_t)plan.q * sizeof(unsigned int);
             void* mem = nullptr;
@@ -1483,8 +1560,7 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
                 io.seg_n_split = plan.n_split; io.seg_n_full = plan.n_full; io.seg_q = plan.q; io.seg_max_polls = plan.max_polls;
                 for (int k = 0; k <= plan.q; ++k) io.seg_year[k] = plan.year[k];
                 e = hipMemsetAsync(io.seg_flags, 0, flag_bytes, stream);
-                const dim3 gseg((unsigned)(plan.n_full + plan.q * plan.n_split));
-#define MCR_LAUNCH_GM(M, T, A) hipLaunchKernelGGL((path_kernel<M, 0, T, A, false, 3>), gseg, block, lds, stream, d, io, (const DevParams*)nullptr)
+#define MCR_LAUNCH_GM(M, T, A) launch_sliced(&path_kernel<M, 0, T, A, false, 3>, plan, seg_order ? order : nullptr, block, lds, stream, d, io, (const DevParams*)nullptr)
 #define MCR_LAUNCH_G(T, A) do { if (mode == 2) MCR_LAUNCH_GM(2, T, A); else if (mode == 1) MCR_LAUNCH_GM(1, T, A); else MCR_LAUNCH_GM(0, T, A); } while (0)
 #define MCR_LAUNCH_GA(T) do { if (d.any_annual_tax) MCR_LAUNCH_G(T, true); else MCR_LAUNCH_G(T, false); } while (0)
                 if (e == hipSuccess) {
@@ -1500,6 +1576,7 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
                 return MCR_OK;
             }
             (void)hipGetLastError();   // (allocation refused: the plain launch below)
+            if (seg_order) { set_error("MCR_K1_SEGMENT_ORDER=%s: the hand-over state could not be allocated", seg_order); return MCR_ERR_HIP; }
         }
     }
     if (split) {
@@ -1657,7 +1734,11 @@ static int probe_shared_prefix(const mcr_params* p, const mcr_rng* rng, uint32_t
         SegmentPlan plan;
         void* seg_mem = nullptr;
         dim3 g4(0);
+        const char* seg_order = segment_order_env();
+        int order[kMaxSegments];
         if (!split2 && plan_segments(top, g2.x * g2.y, 0, &plan, true)) {
+            const int orc = seg_order ? parse_segment_order(seg_order, plan.q, order) : MCR_OK;
+            if (orc != MCR_OK) { (void)hipFreeAsync(mem, stream); return orc; }
             const size_t state_bytes = (size_t)plan.n_split * (size_t)(9 + top.n_lock_slots) * kBlock * sizeof(double);
             const size_t flag_bytes = (size_t)plan.n_split * (size_t)plan.q * sizeof(unsigned int);
             if (hipMallocAsync(&seg_mem, state_bytes + flag_bytes, stream) == hipSuccess &&
@@ -1673,12 +1754,17 @@ static int probe_shared_prefix(const mcr_params* p, const mcr_rng* rng, uint32_t
                 if (seg_mem) { (void)hipFreeAsync(seg_mem, stream); seg_mem = nullptr; }
             }
         }
+        if (seg_order && !g4.x) {
+            (void)hipFreeAsync(mem, stream);
+            set_error("MCR_K1_SEGMENT_ORDER=%s set on a shared-prefix probe whose decumulation launch is not time-sliced", seg_order);
+            return MCR_ERR_INVALID_ARG;
+        }
 #define MCR_PHASES(T, A)                                                                                          \
         do {                                                                                                       \
             if (split1) hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 1, true>), g1, block2, lds, stream, top, io, d_blocks); \
             else hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 1>), g1, block, lds, stream, top, io, d_blocks);    \
             if (split2) hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 2, true>), g2, block2, lds, stream, top, io, d_blocks); \
-            else if (g4.x) hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 4>), g4, block, lds, stream, top, io, d_blocks);    \
+            else if (g4.x) launch_sliced(&path_kernel<0, 0, T, A, false, 4>, plan, seg_order ? order : nullptr, block, lds, stream, top, io, d_blocks); \
             else hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 2>), g2, block, lds, stream, top, io, d_blocks);    \
         } while (0)
 #define MCR_PHASES_A(T) do { if (top.any_annual_tax) MCR_PHASES(T, true); else MCR_PHASES(T, false); } while (0)

@@ -33,7 +33,7 @@ RATES = [0.99, 0.999, 0.9999, 1 - 1e-5, 1 - 2e-6, float(np.nextafter(1 - 1e-6, 0
          float(np.nextafter(1 - 1e-6, 1.0)), 1 - 1e-7, 1.0]
 SEED = int(os.environ.get("MCR_HIGH_RATE_SEED", "20261015"))
 N_PATHS = int(os.environ.get("MCR_HIGH_RATE_PATHS", "20000"))
-KNOBS = ("MCR_K1_SEGMENTS", "MCR_K1_SEGMENTS_ALWAYS", "MCR_K1_SEGMENT_POLLS")
+KNOBS = ("MCR_K1_SEGMENTS", "MCR_K1_SEGMENTS_ALWAYS", "MCR_K1_SEGMENT_POLLS", "MCR_K1_SEGMENT_ORDER")
 
 
 def _helper_cfg(rate, mask, alloc):

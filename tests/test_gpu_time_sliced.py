@@ -17,7 +17,7 @@ from monte_carlo_retirement_amd import engine as E
 
 pytestmark = pytest.mark.gpu
 
-KNOBS = ("MCR_K1_SEGMENTS", "MCR_K1_SEGMENTS_ALWAYS", "MCR_K1_SEGMENT_POLLS")
+KNOBS = ("MCR_K1_SEGMENTS", "MCR_K1_SEGMENTS_ALWAYS", "MCR_K1_SEGMENT_POLLS", "MCR_K1_SEGMENT_ORDER")
 
 
 def _run(p, wm, n, begin, env, edges):
@@ -129,8 +129,12 @@ def test_sliced_probe_window_equals_plain_and_single_launches():
 def test_sliced_launch_fuzz():
     """Random scenarios (the reference-fixture fuzz set: zero allocations, annual taxes, frozen and indexed streams, odd working
     months, terminal tax periods, 1-8 retirement years ...), random batch sizes just above the resident capacity, random segment
-    counts and output modes: sliced == plain in every output.  MCR_SLICE_FUZZ_ROUNDS / MCR_SLICE_FUZZ_SEED for soaks."""
-    rng = np.random.default_rng(int(os.environ.get("MCR_SLICE_FUZZ_SEED", "2026")))
+    counts and output modes: sliced == plain in every output.  MCR_SLICE_FUZZ_ROUNDS / MCR_SLICE_FUZZ_SEED for soaks.
+    Some rounds also run a small poll budget with a random segment order (MCR_K1_SEGMENT_ORDER), drawn from a second
+    generator so that the draws above stay as they were."""
+    seed = int(os.environ.get("MCR_SLICE_FUZZ_SEED", "2026"))
+    rng = np.random.default_rng(seed)
+    rng_order = np.random.default_rng(seed + 1)
     groups = [g for g in load_golden("paths_fuzz.json") if len(g["cfg"]["other_income_streams"]) <= 16] + load_golden("paths_injected.json")
     checked = 0
     for _ in range(int(os.environ.get("MCR_SLICE_FUZZ_ROUNDS", "10"))):
@@ -149,13 +153,13 @@ def test_sliced_launch_fuzz():
         begin = int(rng.choice([0, 2**32 - 3, 2**40 + 17]))
         kw = dict(want_summary=mode >= 1, want_trajectories=mode == 2)
 
-        def run(e):
+        def run(e, draw=rng):
             old = {k: os.environ.get(k) for k in KNOBS}
             for k in KNOBS:
                 os.environ.pop(k, None)
             os.environ.update(e)
             try:
-                return E.run_batch_host(p, 99, int(rng.integers(2)) * 0 + 1, begin, n, wm, **kw)
+                return E.run_batch_host(p, 99, int(draw.integers(2)) * 0 + 1, begin, n, wm, **kw)
             finally:
                 for k, v in old.items():
                     os.environ.pop(k, None)
@@ -165,5 +169,16 @@ def test_sliced_launch_fuzz():
         plain, sliced = run({"MCR_K1_SEGMENTS": "0"}), run(env)
         for k in plain:
             assert np.array_equal(plain[k], sliced[k], equal_nan=True), (g["name"], wm, cfgd["retirement_years"], mode, n, env, k)
+        if rng_order.random() < 0.5:
+            q = min(int(env["MCR_K1_SEGMENTS"]), 8, cfgd["retirement_years"] // 2)
+            env2 = dict(env, MCR_K1_SEGMENT_POLLS=str(int(rng_order.integers(1, 4))),
+                        MCR_K1_SEGMENT_ORDER=",".join(str(k) for k in rng_order.permutation(q)))
+            try:
+                ordered = run(env2, rng_order)
+            except RuntimeError as ex:            # (a scenario the launcher does not slice: lock columns beyond LDS, < 4 years ...)
+                assert "not time-sliced" in str(ex), ex
+            else:
+                for k in plain:
+                    assert np.array_equal(plain[k], ordered[k], equal_nan=True), (g["name"], wm, cfgd["retirement_years"], mode, n, env2, k)
         checked += 1
     assert checked > 0
