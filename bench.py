@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: paths/sec of the per-path Monte Carlo kernel (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]        (N > 1: starts its own N ranks, one per GPU)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full]   (N > 1: starts its own N ranks, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (same ranks, outer launcher)
 
 A "step" is one pass of the hot path over one batch of synthetic paths: ONE launch of the path
@@ -10,14 +10,18 @@ working_months=233 (833 months/path), success-count only (BASELINE.json configs[
 when N > 1 — by the single all-reduce of the counter vector (RCCL).  Independent path ranges
 shard across ranks by GLOBAL path index (weak scaling: per-GPU work is fixed).
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel: algorithmic fp64 ops / measured
-kernel time vs the fp64 vector-issue peak) and `cpu_baseline` (the CPU oracle timed on this box's
-host cores on a bounded sample of the same workload: one thread, 16 threads and every usable core), plus one block per
-remaining BASELINE config: `accuracy_10k` (configs[0]'s 10k-path fixture), `hbm_kernels` / `hbm_kernels_rho0` (configs[2]:
-jorge.json with rho = 0.3 and as shipped), `class_api_1e7` (configs[2] through the drop-in class), `s60` (configs[3]),
-`search` (configs[4]: the whole bracket + bisection search at 50 000 paths per probe and the 10^6-path
-final run, through the drop-in class) and `numpy_stream` (the literal-seed mode's rate).  `config.ranks_seen` / `config.devices` say what the process
-group actually contained.
+Prints ONE JSON line (rank 0) with the headline figure and `roofline` (dominant kernel: algorithmic fp64 ops / the
+HIP-event kernel time of the timed steps vs the fp64 vector-issue peak).  A plain run does nothing else: set-up, warm-up,
+the timed steps, `--dump-outputs`, the line.
+
+`--full` adds what takes runs of its own: `cpu_baseline` (the CPU oracle timed on this box's host cores on a bounded
+sample of the same workload: one thread, 16 threads and every usable core) and one block per remaining BASELINE config:
+`accuracy_10k` (configs[0]'s 10k-path fixture), `hbm_kernels` / `hbm_kernels_rho0` (configs[2]: jorge.json with rho = 0.3
+and as shipped), `class_api_1e7` (configs[2] through the drop-in class), `s60` (configs[3]), `search` (configs[4]: the
+whole bracket + bisection search at 50 000 paths per probe and the 10^6-path final run, through the drop-in class) and
+`numpy_stream` (the literal-seed mode's rate); the `--no-*` options skip single blocks of it.  They run after the timed
+steps and the dump, so the headline figure is the same with or without them.  `config.ranks_seen` / `config.devices` say
+what the process group actually contained.
 
 `--dump-outputs DIR` writes, after the timed steps, what the timed path computed in its LAST step: the launch's counter
 vector split as a caller of `DeviceBatch` receives it (`counters` = [successes, paths], `wr_obs_counts`, `ruin_year_bins`),
@@ -576,6 +580,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--paths", type=int, default=1_000_000, help="paths per GPU per step")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse on one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run, also run the CPU baseline and the blocks of the other BASELINE configs")
+    # the options below shape the --full blocks only
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-aux", action="store_true", help="skip the HBM-side kernels (trajectory write / quantiles / histogram)")
     ap.add_argument("--aux-paths", type=int, default=10_000_000, help="paths of the BASELINE configs[2] block (hbm_kernels)")
@@ -722,10 +729,10 @@ def main():
             return {"error": f"{type(exc).__name__}: {exc}"}
 
     s60 = s60_ranged = search = None
-    if not args.no_s60:
+    if args.full and not args.no_s60:
         s60 = guarded(s60_block, torch, dist, world, args.s60_paths, grouped=grouped, fixed_edges=True)
         s60_ranged = guarded(s60_block, torch, dist, world, args.s60_paths, grouped=grouped, fixed_edges=False)
-    if not args.no_search:
+    if args.full and not args.no_search:
         search = guarded(search_block, torch, dist, world, device, grouped)
 
     if rank == 0:
@@ -788,26 +795,24 @@ def main():
             "success_probability": counters[0] / max(1, counters[1]),
             "paths_counted": counters[1],
         }
-        try:
-            out["accuracy_10k"] = accuracy_10k()
-        except Exception as exc:  # never lose the headline line to an auxiliary block
-            out["accuracy_10k"] = {"error": f"{type(exc).__name__}: {exc}"}
-        if s60 is not None:
-            out["s60"] = s60
-            out["s60_data_ranged"] = s60_ranged
-        if search is not None:
-            out["search"] = search
-        if not args.no_aux and world == 1:
-            out["hbm_kernels"] = guarded(aux_hbm_kernels, torch, args.aux_paths)
-            out["hbm_kernels_rho0"] = guarded(aux_hbm_kernels, torch, args.aux_paths, rho=None, allocations=1)
-            out["numpy_stream"] = guarded(numpy_stream_block, torch, args.paths)
-            out["class_api_1e7"] = guarded(class_api_block, torch, args.aux_paths, out["hbm_kernels"])
-        if not args.no_cpu_baseline:
-            # rank 0 only; with N > 1 the other ranks wait at the closing barrier (outside every timed region), so the
-            # sample is a quarter of the single-GPU run's
-            scale = 1 if world == 1 else 4
-            out["cpu_baseline"] = guarded(cpu_baseline_block, params, args.cpu_threads, max(1, args.cpu_paths_per_thread // scale),
-                                          max(1, args.cpu_single_thread_paths // scale), args.cpu_all_cores_seconds / scale)
+        if args.full:
+            out["accuracy_10k"] = guarded(accuracy_10k)
+            if s60 is not None:
+                out["s60"] = s60
+                out["s60_data_ranged"] = s60_ranged
+            if search is not None:
+                out["search"] = search
+            if not args.no_aux and world == 1:
+                out["hbm_kernels"] = guarded(aux_hbm_kernels, torch, args.aux_paths)
+                out["hbm_kernels_rho0"] = guarded(aux_hbm_kernels, torch, args.aux_paths, rho=None, allocations=1)
+                out["numpy_stream"] = guarded(numpy_stream_block, torch, args.paths)
+                out["class_api_1e7"] = guarded(class_api_block, torch, args.aux_paths, out["hbm_kernels"])
+            if not args.no_cpu_baseline:
+                # rank 0 only; with N > 1 the other ranks wait at the closing barrier (outside every timed region), so the
+                # sample is a quarter of the single-GPU run's
+                scale = 1 if world == 1 else 4
+                out["cpu_baseline"] = guarded(cpu_baseline_block, params, args.cpu_threads, max(1, args.cpu_paths_per_thread // scale),
+                                              max(1, args.cpu_single_thread_paths // scale), args.cpu_all_cores_seconds / scale)
         print(json.dumps(out), flush=True)
     if grouped:
         dist.barrier()

@@ -30,7 +30,7 @@ def _run(*args, timeout=600):
 @pytest.mark.parametrize("world,n,s60_paths", [(2, 200_000, 300_001), (5, 50_000, 800_001)])
 def test_bench_self_launches_its_ranks(world, n, s60_paths):
     steps = 3
-    out = _run("--gpus", str(world), "--backend", "gloo", "--steps", str(steps), "--warmup", "1", "--paths", str(n), "--s60-paths", str(s60_paths),
+    out = _run("--full", "--gpus", str(world), "--backend", "gloo", "--steps", str(steps), "--warmup", "1", "--paths", str(n), "--s60-paths", str(s60_paths),
                "--cpu-threads", "2", "--cpu-paths-per-thread", "4000", "--cpu-single-thread-paths", "4000", "--cpu-all-cores-seconds", "0",
                timeout=900)
     assert out["n_gpus"] == world and out["steps"] == steps and out["scaling"] == "weak" and out["unit"] == "paths/s"
@@ -63,7 +63,7 @@ def test_bench_self_launches_its_ranks(world, n, s60_paths):
 
 
 def test_bench_single_gpu_line_has_the_contract_keys():
-    out = _run("--steps", "3", "--warmup", "1", "--paths", "200000", "--aux-paths", "2200000", "--s60-paths", "400000",
+    out = _run("--full", "--steps", "3", "--warmup", "1", "--paths", "200000", "--aux-paths", "2200000", "--s60-paths", "400000",
                "--cpu-threads", "4", "--cpu-paths-per-thread", "2000", "--cpu-single-thread-paths", "2000", "--cpu-all-cores-seconds", "1.5")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "cpu_baseline", "hbm_kernels", "hbm_kernels_rho0", "numpy_stream", "class_api_1e7",
@@ -112,15 +112,18 @@ def test_bench_single_gpu_line_has_the_contract_keys():
 
 
 def test_bench_dump_outputs_are_the_last_steps_and_repeat(tmp_path):
-    """--dump-outputs DIR: the last timed step's outputs as float64 .npy files; the same arguments give the same files."""
+    """--dump-outputs DIR: the last timed step's outputs as float64 .npy files; the same arguments give the same files.
+    Without --full the run is the headline figure alone: none of the --full blocks is in the line."""
     import numpy as np
 
     n, steps = 200_000, 3
     dirs = [tmp_path / "a", tmp_path / "b"]
     for d in dirs:
-        out = _run("--steps", str(steps), "--warmup", "1", "--paths", str(n), "--no-aux", "--no-s60", "--no-search",
-                   "--no-cpu-baseline", "--dump-outputs", str(d))
+        out = _run("--steps", str(steps), "--warmup", "1", "--paths", str(n), "--dump-outputs", str(d))
         assert out["steps"] == steps and out["paths_counted"] == steps * n and out["ms_per_step"] > 0
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"} <= set(out)
+        assert not set(out) & {"cpu_baseline", "accuracy_10k", "hbm_kernels", "hbm_kernels_rho0", "numpy_stream", "class_api_1e7",
+                               "s60", "s60_data_ranged", "search"}
     names = sorted(f.name for f in dirs[0].iterdir())
     assert names == sorted(f.name for f in dirs[1].iterdir())
     assert {"counters.npy", "ruin_year_bins.npy", "success_probability.npy"} <= set(names)
@@ -143,7 +146,7 @@ def test_bench_group_code_path_over_rccl_with_one_rank():
     n, steps = 200_000, 4
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(MCR_BENCH_FORCE_GROUP="1", MASTER_PORT=str(29600 + os.getpid() % 300))
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", str(steps), "--warmup", "2", "--paths", str(n),
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", str(steps), "--warmup", "2", "--paths", str(n),
                         "--s60-paths", "300001", "--no-aux", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -206,7 +209,7 @@ def test_bench_under_the_drivers_launcher(world):
     port = 29700 + (os.getpid() + world) % 200
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1",
-           "--backend", "gloo", "--paths", "200000", "--s60-paths", "300001", "--no-search", "--no-cpu-baseline"]
+           "--backend", "gloo", "--paths", "200000", "--full", "--s60-paths", "300001", "--no-search", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

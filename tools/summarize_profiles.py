@@ -132,7 +132,7 @@ def main(src: str, dst: str) -> None:
                   "K1_count_kernel_ms": k1_ms, "K3_slab_kernel_ms": kb_ms}
     derived["provenance"] = provenance
     json.dump({
-        "command": "rocprofv3 --pmc <set> --output-format csv -- python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-s60 --no-search "
+        "command": "rocprofv3 --pmc <set> --output-format csv -- python3 bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-s60 --no-search "
                    "(separate passes: SQ, SQ instruction mix, FETCH_SIZE, WRITE_SIZE; tools/collect_profiles.sh)",
         "note": "FETCH_SIZE/WRITE_SIZE in KiB; FETCH_SIZE doubled per the gfx950 correction (MI355X_MICROARCH.md, HBM)",
         "kernels": summ, "derived": derived,
