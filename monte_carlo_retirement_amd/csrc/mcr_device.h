@@ -130,6 +130,66 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
+// The same generator for the path kernel's blocks, counter = (path_lo, path_hi, block, stream_id) with the parts of rounds
+// 0 and 1 that do not depend on the block computed once per path (philox_path, at a point where the whole wave is
+// active): round 0's M0 path_lo, and round 1's M1 c2 — c2 = hi(M0 path_lo) ^ stream_id ^ key_hi is block-free.  path_hi is
+// the same in every lane unless the wave straddles a 2^32 path boundary; one ballot per path decides, and then round 0's
+// c0 and round 1's M0 c0 are scalar work.  Same words as philox4x32_10 for every counter and key.
+struct PhiloxPath {
+    uint64_t hi_mask;      // lanes whose path_hi is not hi_s (wave-uniform; 0 on all but a wave that straddles 2^32)
+    uint32_t hi_s, hi_o;   // path_hi of the wave's first active lane, and of the others (the paths of a wave span < 2^32)
+    uint32_t lo0;          // lo(M0 path_lo): word 3 after round 0
+    uint32_t b_lo, b_hi;   // M1 (hi(M0 path_lo) ^ stream_id ^ key_hi): round 1's second product
+    bool hi_uniform;       // hi_mask == 0 (readfirstlane: a scalar branch, not an exec-masked one)
+};
+__device__ __forceinline__ PhiloxPath philox_path(uint64_t path, uint32_t stream_id, uint64_t seed) {
+    PhiloxPath Q;
+    const uint32_t hi = (uint32_t)(path >> 32);
+    Q.hi_s = (uint32_t)__builtin_amdgcn_readfirstlane((int)hi);
+    Q.hi_mask = __builtin_amdgcn_ballot_w64(hi != Q.hi_s);
+    Q.hi_uniform = __builtin_amdgcn_readfirstlane((int)(Q.hi_mask == 0ull)) != 0;
+    Q.hi_o = Q.hi_mask ? (uint32_t)__builtin_amdgcn_readlane((int)hi, (int)__builtin_ctzll(Q.hi_mask)) : Q.hi_s;
+    const uint64_t p0 = (uint64_t)0xD2511F53u * (uint32_t)path;
+    Q.lo0 = (uint32_t)p0;
+    const uint64_t p1 = (uint64_t)0xCD9E8D57u * ((uint32_t)(p0 >> 32) ^ stream_id ^ (uint32_t)(seed >> 32));
+    Q.b_lo = (uint32_t)p1;
+    Q.b_hi = (uint32_t)(p1 >> 32);
+    return Q;
+}
+template <bool HI_UNIFORM>
+__device__ __forceinline__ void philox_path_rounds(const PhiloxPath& Q, uint32_t block, uint32_t k0, uint32_t k1, uint32_t (&out)[4]) {
+    asm volatile("" : "+s"(k0), "+s"(k1));          // (the key barrier of philox4x32_10)
+    // round 0 (key k): c0 = hi(M1 block) ^ path_hi ^ k0; c1 = lo(M1 block); c2, c3 from Q
+    const uint64_t q1 = (uint64_t)0xCD9E8D57u * block;
+    // path_hi: rebuilt from the wave's mask on the rare straddling wave (no VGPR held for it through the path)
+    const uint32_t ph = HI_UNIFORM ? Q.hi_s : (((Q.hi_mask >> __lane_id()) & 1ull) ? Q.hi_o : Q.hi_s);
+    const uint32_t n0 = (uint32_t)(q1 >> 32) ^ ph ^ k0;
+    // round 1 (key k + W): the products M0 n0 (scalar when path_hi is) and Q.b
+    const uint64_t r0 = (uint64_t)0xD2511F53u * n0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+    uint32_t c0 = Q.b_hi ^ ((uint32_t)q1 ^ k0);
+    uint32_t c1 = Q.b_lo;
+    uint32_t c2 = (uint32_t)(r0 >> 32) ^ Q.lo0 ^ k1;
+    uint32_t c3 = (uint32_t)r0;
+#pragma unroll
+    for (int r = 2; r < 10; ++r) {
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0r = __builtin_amdgcn_bitop3_b32((uint32_t)(p1 >> 32), c1, k0, 0x96);
+        // round 2's c3 is still wave-uniform when path_hi is: one xor with a scalar
+        const uint32_t n2r = (HI_UNIFORM && r == 2) ? (uint32_t)(p0 >> 32) ^ (c3 ^ k1)
+                                                     : __builtin_amdgcn_bitop3_b32((uint32_t)(p0 >> 32), c3, k1, 0x96);
+        c1 = (uint32_t)p1;
+        c3 = (uint32_t)p0;
+        c0 = n0r;
+        c2 = n2r;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
 // The path's standard-normal sequence n[0], n[1], ... : pair j = Box-Muller of Philox words
 // (2(j&1), 2(j&1)+1) of block j>>1 (counter = (path_lo, path_hi, block, stream_id)):
 //   n[2j] = sqrt(-2 ln u_r) cos(2 pi u_a), n[2j+1] = ... sin(...),  u = (x + 0.5) 2^-32.
@@ -147,8 +207,9 @@ __device__ __forceinline__ void bm_pair(uint32_t xr, uint32_t xa, const double* 
 
 // The same pair as its PARTS: radius r and the angle's (cos, sin), the two normals being r cos and r sin.  growth_rows2
 // folds the products into the log-returns instead of forming the normals first.
+template <bool BYTE_OFFSET = false>
 __device__ __forceinline__ void bm_parts(uint32_t xr, uint32_t xa, const double* tab, const MathRegs& R, double& r, double& c, double& s) {
-    r = fsqrt(neg2_log_u32<true>(xr, tab, R));      // path forms of the series (mcr_math.h)
+    r = fsqrt(neg2_log_u32<true, BYTE_OFFSET>(xr, tab, R));      // path forms of the series (mcr_math.h)
     sincos_u32<true, true>(xa, tab, R, s, c);
 }
 
@@ -223,24 +284,37 @@ __device__ __forceinline__ double monthly_gross(double a, double b, double z, co
 // independent straight-line work (lots of instruction-level parallelism next to the serial month bodies of
 // the other waves).  The normals are shock_row_seq's; the log-returns are associated on their parts (below).
 struct PairCarry { uint32_t w2, w3; };
-template <int HALF, int COLS = kBlock>
-__device__ __forceinline__ void growth_rows2(const DevParams& P, const MathRegs& M, uint64_t seed, uint32_t stream_id, uint64_t path,
-                                             uint32_t t, const double* tab, double* stage, PairCarry& C) {
+// GEN: how the Philox blocks are drawn.  kGenPlain = philox4x32_10 on the whole counter; kGenUniform = philox_path_rounds
+// with the wave's path_hi (wave-uniform: right only when PhiloxPath::hi_uniform); kGenGeneral = philox_path_rounds with each
+// lane's path_hi.  All three give the same words wherever they are right.
+// Side effects: the six stage slots of the lane and, in HALF 0, the carry — nothing else.  growth_rows2 relies on that (a
+// straddling wave runs the form twice and the second pass overwrites the first); an output added here must be
+// overwritten the same way.
+enum { kGenPlain = 0, kGenUniform = 1, kGenGeneral = 2 };
+template <int HALF, int COLS, int GEN>
+__device__ __forceinline__ void growth_rows2_form(const DevParams& P, const MathRegs& M, uint64_t seed, uint32_t stream_id, uint64_t path,
+                                                  const PhiloxPath& Q, uint32_t t, const double* tab, double* stage, PairCarry& C) {
+    auto draw = [&](uint32_t block, uint32_t (&x)[4]) {
+        if (GEN == kGenPlain)
+            philox4x32_10((uint32_t)path, (uint32_t)(path >> 32), block, stream_id, (uint32_t)seed, (uint32_t)(seed >> 32), x);
+        else
+            philox_path_rounds<GEN == kGenUniform>(Q, block, (uint32_t)seed, (uint32_t)(seed >> 32), x);
+    };
     // pair i: radius rad[i], trig[2 i] = cos, trig[2 i + 1] = sin; normal j of the half = rad[j >> 1] * trig[j]
     double rad[3], trig[6];
     uint32_t x[4];
     if (HALF == 0) {
-        philox4x32_10((uint32_t)path, (uint32_t)(path >> 32), 3u * t, stream_id, (uint32_t)seed, (uint32_t)(seed >> 32), x);
-        bm_parts(x[0], x[1], tab, M, rad[0], trig[0], trig[1]);
-        bm_parts(x[2], x[3], tab, M, rad[1], trig[2], trig[3]);
-        philox4x32_10((uint32_t)path, (uint32_t)(path >> 32), 3u * t + 1u, stream_id, (uint32_t)seed, (uint32_t)(seed >> 32), x);
-        bm_parts(x[0], x[1], tab, M, rad[2], trig[4], trig[5]);
+        draw(3u * t, x);
+        bm_parts<GEN != kGenPlain>(x[0], x[1], tab, M, rad[0], trig[0], trig[1]);
+        bm_parts<GEN != kGenPlain>(x[2], x[3], tab, M, rad[1], trig[2], trig[3]);
+        draw(3u * t + 1u, x);
+        bm_parts<GEN != kGenPlain>(x[0], x[1], tab, M, rad[2], trig[4], trig[5]);
         C.w2 = x[2]; C.w3 = x[3];
     } else {
-        bm_parts(C.w2, C.w3, tab, M, rad[0], trig[0], trig[1]);
-        philox4x32_10((uint32_t)path, (uint32_t)(path >> 32), 3u * t + 2u, stream_id, (uint32_t)seed, (uint32_t)(seed >> 32), x);
-        bm_parts(x[0], x[1], tab, M, rad[1], trig[2], trig[3]);
-        bm_parts(x[2], x[3], tab, M, rad[2], trig[4], trig[5]);
+        bm_parts<GEN != kGenPlain>(C.w2, C.w3, tab, M, rad[0], trig[0], trig[1]);
+        draw(3u * t + 2u, x);
+        bm_parts<GEN != kGenPlain>(x[0], x[1], tab, M, rad[1], trig[2], trig[3]);
+        bm_parts<GEN != kGenPlain>(x[2], x[3], tab, M, rad[2], trig[4], trig[5]);
     }
     // The three log-returns of a month, x = a + b z (:473) with z_inf = rho n0 + rho_c n1 (:461-464), written on the
     // PARTS of the normals: x_eq = (b1 r) t + a1, x_inf = (binf rho r0) t0 + ((binf rho_c r1) t1 + a_inf), x_prem
@@ -267,6 +341,30 @@ __device__ __forceinline__ void growth_rows2(const DevParams& P, const MathRegs&
         stage[(3 * r + 0) * COLS] = g1;
         stage[(3 * r + 1) * COLS] = ginf;
         stage[(3 * r + 2) * COLS] = ginf * gprem;                               // :532
+    }
+}
+// PER_PATH (the count-only kernels without an annual-gains tax: the issue-bound launches): every wavefront runs the form
+// with a wave-uniform path_hi — one straight-line block, the Philox words interleaved with the fp64 work of the pairs (a
+// wave-uniform branch around the first rounds alone split that block and cost as much time as the rounds saved).  The rare
+// wavefront whose paths straddle a multiple of 2^32 then runs the general form as well, which overwrites what the first
+// pass staged and carried with the right words (HALF 0 carries only words it draws, HALF 1 only reads the carry).
+// Otherwise the plain generator: in the variants with per-path outputs or an annual-gains tax the second form's registers
+// cost scratch, and those launches are not bound by the generator's issue slots.
+template <int HALF, int COLS = kBlock, bool PER_PATH = false>
+__device__ __forceinline__ void growth_rows2(const DevParams& P, const MathRegs& M, uint64_t seed, uint32_t stream_id, uint64_t path,
+                                             const PhiloxPath& Q, uint32_t t, const double* tab, double* stage, PairCarry& C) {
+    if (!PER_PATH) {
+        growth_rows2_form<HALF, COLS, kGenPlain>(P, M, seed, stream_id, path, Q, t, tab, stage, C);
+        return;
+    }
+    growth_rows2_form<HALF, COLS, kGenUniform>(P, M, seed, stream_id, path, Q, t, tab, stage, C);
+    if (__builtin_expect(!Q.hi_uniform, 0)) {
+        // the barrier keeps the general form a branch (left alone the compiler computes both forms and selects) and its
+        // inputs opaque (no values of the first pass kept live into it: both forms then fit the same registers)
+        PairCarry C2 = C;
+        asm volatile("" : "+v"(C2.w2), "+v"(C2.w3));
+        growth_rows2_form<HALF, COLS, kGenGeneral>(P, M, seed, stream_id, path, Q, t, tab, stage, C2);
+        C = C2;
     }
 }
 constexpr int kStageDoubles = 6 * kBlock;   // 12 KB of LDS per workgroup

@@ -243,6 +243,9 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6) ? 64 * (MCR_MAX_EXPENSE_
     const bool valid = local < io.n_paths;
     const uint64_t li = valid ? local : (io.n_paths - 1);  // tail lanes shadow the last path, write nothing
     const uint64_t path = io.path_begin + li;
+    // growth_rows2's per-path Philox rounds (mcr_device.h), in the count-only kernels without an annual-gains tax
+    constexpr bool kPerPathPhilox = MODE == 0 && !ANNUAL;
+    const PhiloxPath PQ = kPerPathPhilox ? philox_path(path, io.stream_id, io.seed) : PhiloxPath{};   // (the whole wave is here: philox_path's ballot)
     const int64_t stride = io.out.path_stride;
     const double* inj = INJ ? io.injected + (size_t)li * 3u * (size_t)P.shock_rows : nullptr;
 
@@ -291,8 +294,8 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6) ? 64 * (MCR_MAX_EXPENSE_
                 if (((row >> 1) & (kSplitVotePairs - 1)) == 0) { if (__syncthreads_or(__builtin_amdgcn_ballot_w64(lane_alive) != 0ull ? 1 : 0) == 0) wg_dead = true; }
                 else __syncthreads();
             } else {
-                if ((row & 2) == 0) growth_rows2<0, kPaths>(P, GR, io.seed, io.stream_id, path, (uint32_t)row >> 2, tab, stage, carry);
-                else growth_rows2<1, kPaths>(P, GR, io.seed, io.stream_id, path, (uint32_t)row >> 2, tab, stage, carry);
+                if ((row & 2) == 0) growth_rows2<0, kPaths, kPerPathPhilox>(P, GR, io.seed, io.stream_id, path, PQ, (uint32_t)row >> 2, tab, stage, carry);
+                else growth_rows2<1, kPaths, kPerPathPhilox>(P, GR, io.seed, io.stream_id, path, PQ, (uint32_t)row >> 2, tab, stage, carry);
             }
         }
     };
@@ -363,8 +366,8 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6) ? 64 * (MCR_MAX_EXPENSE_
         if (PHASE == 1) while (snap_i < io.n_snap && io.snap_months[snap_i] == 0) put_carry();
         for (int row = first_row; row < last_row; row += 2) {
             double* st = stage + (size_t)((row >> 1) & 1) * kStageLen;
-            if ((row & 2) == 0) growth_rows2<0, kPaths>(P, GR, io.seed, io.stream_id, path, (uint32_t)row >> 2, tab, st, carry);
-            else growth_rows2<1, kPaths>(P, GR, io.seed, io.stream_id, path, (uint32_t)row >> 2, tab, st, carry);
+            if ((row & 2) == 0) growth_rows2<0, kPaths, kPerPathPhilox>(P, GR, io.seed, io.stream_id, path, PQ, (uint32_t)row >> 2, tab, st, carry);
+            else growth_rows2<1, kPaths, kPerPathPhilox>(P, GR, io.seed, io.stream_id, path, PQ, (uint32_t)row >> 2, tab, st, carry);
             if (PHASE == 1) while (snap_i < io.n_snap && ((io.snap_months[snap_i] - 1) >> 1) == (row >> 1)) put_carry();
             if (((row >> 1) & (kSplitVotePairs - 1)) == 0) { if (__syncthreads_or(0) == 0) return; }   // (the consumers' vote, begin_month)
             else __syncthreads();

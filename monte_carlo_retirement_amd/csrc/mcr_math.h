@@ -120,14 +120,23 @@ __device__ __forceinline__ double fexp(double x, const double* tab, const MathRe
     return __longlong_as_double((long long)(((uint64_t)hi << 32) | (vb & 0xFFFFFFFFull)));
 }
 
-template <bool PATH = false>
+template <bool PATH = false, bool BYTE_OFFSET = false>
 __device__ __forceinline__ double neg2_log_u32(uint32_t x, const double* tab, const MathRegs& R) {
     const double d = __builtin_fma((double)x, 2.0, 1.0);  // 2x+1, exact, in [1, 2^33);  u = d 2^-33
     const uint32_t hi = (uint32_t)((uint64_t)__double_as_longlong(d) >> 32);
     const int i = (int)((hi >> 13) & 127u);               // top 7 fraction bits
     const double m = __builtin_amdgcn_frexp_mant(d);      // d = m 2^ex, m in [1/2, 1): v_frexp_mant_f64 / v_frexp_exp_i32_f64
     const int ex = __builtin_amdgcn_frexp_exp(d);
-    const double inv_c = tab[kTabLog + 2 * i], w_i = tab[kTabLog + 2 * i + 1];   // 1/c_i and -2 ln c_i, c_i in [1, 2)
+    // BYTE_OFFSET: i straight to the byte offset 16 i of its pair, (hi >> 9) & 0x7f0 — one shift and one and where the index
+    // costs three (the same loads; used where growth_rows2 draws per path: elsewhere the register allocation it perturbs cost
+    // scratch in kernels at their VGPR bound)
+    double inv_c, w_i;                                    // 1/c_i and -2 ln c_i, c_i in [1, 2)
+    if (BYTE_OFFSET) {
+        const double* pair = reinterpret_cast<const double*>(reinterpret_cast<const char*>(tab + kTabLog) + ((hi >> 9) & (127u << 4)));
+        inv_c = pair[0]; w_i = pair[1];
+    } else {
+        inv_c = tab[kTabLog + 2 * i]; w_i = tab[kTabLog + 2 * i + 1];
+    }
     // r = 2m / c_i - 1, |r| <= 2^-8; the code works with s = r/2 = m / c_i - 1/2 (no mantissa rebuilt in integer ops):
     // -2 ln(1+r) = -2r + r^2 (1 - 2r/3 + r^2/2 - 2r^3/5 + r^4/3) = 4 (s^2 p(2s) - s); every coefficient below is a
     // power-of-two multiple of the series', so the Horner values are the same bits as in terms of r

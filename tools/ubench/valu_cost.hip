@@ -79,6 +79,14 @@ KERNEL(exp_f32, float, seed + threadIdx.x + c, ASM1("v_exp_f32"))
 KERNEL(bfi_b32, uint32_t, seed + threadIdx.x + c, ASM3("v_bfi_b32"))
 KERNEL(bitop3_b32, uint32_t, seed + threadIdx.x + c, asm volatile("v_bitop3_b32 %0, %0, %1, %0 bitop3:0x96" : "+v"(x) : "v"(seed)))
 KERNEL(bitop3_sgpr, uint32_t, seed + threadIdx.x + c, asm volatile("v_bitop3_b32 %0, %0, %1, s20 bitop3:0x96" : "+v"(x) : "v"(seed)))
+// operand placement of the Philox round (lead of R5.5): the multiplier and the round key in an SGPR vs a VGPR, alone and
+// one per fp64 FMA
+KERNEL(mad_u64_u32_sgpr, uint64_t, seed + threadIdx.x + c, asm volatile("v_mad_u64_u32 %0, vcc, %1, s20, %0" : "+v"(x) : "v"((uint32_t)seed) : "vcc"))
+KERNEL(xor_b32_sgpr, uint32_t, seed + threadIdx.x + c, asm volatile("v_xor_b32 %0, s20, %0" : "+v"(x)))
+KERNEL(mix_mad64_sgpr_per_fma, double, seed + threadIdx.x + c, { uint64_t t; asm volatile("v_mad_u64_u32 %0, vcc, %1, s20, 0" : "=v"(t) : "v"((uint32_t)c) : "vcc"); FMA1; })
+KERNEL(mix_bitop3_per_fma, double, seed + threadIdx.x + c, { uint32_t t; asm volatile("v_bitop3_b32 %0, %1, %1, %1 bitop3:0x96" : "=v"(t) : "v"((uint32_t)c)); FMA1; })
+KERNEL(mix_bitop3_sgpr_per_fma, double, seed + threadIdx.x + c, { uint32_t t; asm volatile("v_bitop3_b32 %0, %1, %1, s20 bitop3:0x96" : "=v"(t) : "v"((uint32_t)c)); FMA1; })
+KERNEL(mix_xor_per_fma, double, seed + threadIdx.x + c, { uint32_t t; asm volatile("v_xor_b32 %0, %1, %1" : "=v"(t) : "v"((uint32_t)c)); FMA1; })
 KERNEL(lshl_add_u32, uint32_t, seed + threadIdx.x + c, asm volatile("v_lshl_add_u32 %0, %0, 3, %1" : "+v"(x) : "v"(seed)))
 KERNEL(add3_u32, uint32_t, seed + threadIdx.x + c, ASM3("v_add3_u32"))
 KERNEL(frexp_exp_f64, double, seed + threadIdx.x + c, { uint32_t e; asm volatile("v_frexp_exp_i32_f64 %0, %1" : "=v"(e) : "v"(x)); })
@@ -124,5 +132,7 @@ int main() {
     RUN(frexp_exp_f64, double, 1.5); RUN(exp_f32, float, 1.5f);
     RUN(mix_rcp64_per_4fma, double, 1.0000001); RUN(mix_rcp32_per_4fma, double, 1.0000001); RUN(mix_4xor_per_4fma, double, 1.0000001);
     RUN(mix_mad64_per_fma, double, 1.0000001);
+    RUN(mad_u64_u32_sgpr, uint64_t, 3); RUN(xor_b32_sgpr, uint32_t, 3); RUN(mix_mad64_sgpr_per_fma, double, 1.0000001);
+    RUN(mix_bitop3_per_fma, double, 1.0000001); RUN(mix_bitop3_sgpr_per_fma, double, 1.0000001); RUN(mix_xor_per_fma, double, 1.0000001);
     return 0;
 }
