@@ -8,6 +8,7 @@ switch to the final seed stream, run the final batch, print the response documen
     python examples/run_scenario.py scenarios/config.json --paths 10000000 --working-months 233 --compact
     python examples/run_scenario.py scenarios/config.json --events --full > response.json
     python examples/run_scenario.py scenarios/config.json --working-months 240 --max-expenses
+    python examples/run_scenario.py scenarios/config.json --working-months 180 --min-contribution
     python examples/run_scenario.py scenarios/config.json --frontier 180,240,300
     python examples/run_scenario.py scenarios/config.json --grid-months 180,240 --grid-expenses 3000,4000,5000
 
@@ -19,7 +20,9 @@ and sizes) is printed.  `--max-expenses` answers the other planning question ins
 (whole cents) that still reaches the target when retiring after `--working-months` (or the searched minimum), printed
 with its probability and the search curve as one JSON object.  `--frontier` runs that search for several retirement months
 at once (one grid probe per round) and prints a JSON list of `{working_months, max_monthly_expenses, probability,
-levels_evaluated}`; `--grid-months` with `--grid-expenses` prints the success-probability table of those months x levels."""
+levels_evaluated}`; `--grid-months` with `--grid-expenses` prints the success-probability table of those months x levels.
+`--min-contribution` answers the third one: the smallest monthly contribution (whole cents) that reaches the target when
+retiring after `--working-months` (required), printed with its probability and the search curve as one JSON object."""
 
 from __future__ import annotations
 
@@ -48,11 +51,18 @@ def main() -> int:
     ap.add_argument("--events", action="store_true", help="progress events to stderr")
     ap.add_argument("--full", action="store_true", help="print the whole response document")
     ap.add_argument("--max-expenses", action="store_true", help="search the maximum monthly expenses instead")
-    ap.add_argument("--resolution", type=float, default=1.0, help="--max-expenses: stop when the bracket is this narrow")
+    ap.add_argument("--min-contribution", action="store_true",
+                    help="search the minimum monthly contribution at --working-months instead")
+    ap.add_argument("--resolution", type=float, default=1.0,
+                    help="--max-expenses / --min-contribution: stop when the bracket is this narrow")
     ap.add_argument("--frontier", default=None, help="comma-separated working months: maximum monthly expenses at each")
     ap.add_argument("--grid-months", default=None, help="comma-separated working months of a success-probability table")
     ap.add_argument("--grid-expenses", default=None, help="comma-separated monthly expenses of that table")
     args = ap.parse_args()
+    if args.min_contribution and args.working_months is None:
+        ap.error("--min-contribution needs --working-months")
+    if args.min_contribution and args.max_expenses:
+        ap.error("--min-contribution and --max-expenses are separate questions")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank0 = int(os.environ.get("RANK", "0")) == 0
@@ -83,6 +93,8 @@ def main() -> int:
 
     if args.max_expenses:
         return max_expenses(args, config, world, rank0)
+    if args.min_contribution:
+        return min_contribution(args, config, world, rank0)
     if args.frontier or args.grid_months or args.grid_expenses:
         if args.frontier and (args.grid_months or args.grid_expenses):
             ap.error("--frontier and --grid-* are separate questions")
@@ -151,6 +163,31 @@ def max_expenses(args, config: Config, world: int, rank0: bool) -> int:
         dist.barrier()
         dist.destroy_process_group()
     return rc
+
+
+def min_contribution(args, config: Config, world: int, rank0: bool) -> int:
+    from monte_carlo_retirement_amd.simulation import RetirementMonteCarloSimulator
+
+    t0 = time.perf_counter()
+    sim = RetirementMonteCarloSimulator(config, main_seed_override=args.seed, rng=args.rng)
+    events = []
+    contribution, prob, curve = sim.find_minimum_monthly_contribution(args.working_months, verbose=False,
+                                                                      progress_callback=events.append,
+                                                                      resolution=args.resolution)
+    out = {
+        "scenario": config.Nickname, "rng": args.rng, "working_months": int(args.working_months),
+        "target_probability": config.target_probability, "min_monthly_contribution": contribution, "probability": prob,
+        "probes": len({e["iteration"] for e in events}), "curve": curve,
+        "seconds": round(time.perf_counter() - t0, 3),
+    }
+    if rank0:
+        print(json.dumps(out))
+    if world > 1:
+        import torch.distributed as dist
+
+        dist.barrier()
+        dist.destroy_process_group()
+    return 0
 
 
 def _csv(text: str, kind):

@@ -310,6 +310,23 @@ int mcr_probe_expenses_rng(const mcr_params* p, const mcr_rng* rng, uint32_t str
                            uint64_t* counts, int device, void* hip_stream);
 
 /*
+ * Minimum-contribution search support: success counts of SEVERAL monthly_contribution levels at one working-month count over
+ * the same path range.  counts[k] equals, bit for bit, the counters of a count-only mcr_run_batch_rng call with the same
+ * arguments and p->monthly_contribution = monthly_contributions[k].  monthly_contributions is a HOST array of n_levels >= 0
+ * values (duplicates allowed), each finite and >= 0 (config.py:57); every level is validated before anything is enqueued
+ * (counts stay untouched on an error).  One level: the plain count-only launch.  Philox stream, at most MCR_INLINE_STREAMS
+ * income streams, the tolerance month, n_paths <= 2^31: CONTRIBUTION FAN-OUT launches, a workgroup per 64 paths, one wave
+ * generating the random numbers of the whole path for up to MCR_MAX_EXPENSE_FANOUT consumer waves, one per level (the levels
+ * differ from month 0: nothing is shared but the random numbers, and nothing is allocated).  Otherwise (NumPy stream, longer
+ * stream lists, the exact month, or fewer path-wavefronts than MCR_CONTRIBUTION_FANOUT_MIN_WAVES in the environment): one
+ * count-only launch per level on internal side streams, joined back onto `hip_stream`.  counts: DEVICE uint64
+ * [n_levels][MCR_N_COUNTERS] = {successes, paths} (zeroed by the call).  Asynchronous like mcr_probe_months_rng.
+ */
+int mcr_probe_contributions_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                uint64_t n_paths, int32_t working_months, const double* monthly_contributions, int32_t n_levels,
+                                uint64_t* counts, int device, void* hip_stream);
+
+/*
  * Retirement-month x spending grid: counts[c][k] equals, bit for bit, the counters of a count-only mcr_run_batch_rng call with
  * working_months[c] and p->monthly_expenses = monthly_expenses[c][k], everything else unchanged.  working_months: n_candidates
  * >= 0 months (any order, repeats allowed); monthly_expenses: HOST [n_candidates][n_levels] row-major, each finite and >= 0.

@@ -231,6 +231,7 @@ ABI_SYMBOLS = (
     "mcr_draw_shocks_host_rng",
     "mcr_probe_months_rng",
     "mcr_probe_expenses_rng",
+    "mcr_probe_contributions_rng",
     "mcr_probe_grid_rng",
     "mcr_run_batch_multi_host_rng",
     "mcr_validate_params",
@@ -300,6 +301,11 @@ def _declare(lib: C.CDLL) -> None:
     ]
     lib.mcr_probe_expenses_rng.restype = C.c_int
     lib.mcr_probe_expenses_rng.argtypes = [
+        P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32, P(C.c_double), C.c_int32,
+        C.c_void_p, C.c_int, C.c_void_p,
+    ]
+    lib.mcr_probe_contributions_rng.restype = C.c_int
+    lib.mcr_probe_contributions_rng.argtypes = [
         P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32, P(C.c_double), C.c_int32,
         C.c_void_p, C.c_int, C.c_void_p,
     ]

@@ -66,10 +66,11 @@ struct KernelIO {
                                                      // seg_bid_base + blockIdx.x of the single sliced launch (0 when it is one launch)
     unsigned int* seg_flags;                         // [seg_n_split][seg_q], zeroed before the launch: 0 pending, 1 state handed over, 2 recomputed
     int32_t seg_max_polls;                           // x ~1 us: how long a successor looks for its predecessor's flag before it recomputes the block itself
-    // PHASE 5 (expense fan-out, mcr_probe_expenses_rng): consumer wave j runs monthly_expenses = fan_expenses[j] and adds its
-    // counts to counters + j * MCR_N_COUNTERS; fan_n = blockDim.x / 64 - 1 levels
+    // PHASE 5 / 7 (expense / contribution fan-out, mcr_probe_expenses_rng / mcr_probe_contributions_rng): consumer wave j runs
+    // level fan_expenses[j] (monthly_expenses / monthly_contribution) and adds its counts to counters + j * MCR_N_COUNTERS;
+    // fan_n = blockDim.x / 64 - 1 levels
     int32_t fan_n;
-    double fan_expenses[MCR_MAX_EXPENSE_FANOUT];
+    double fan_expenses[MCR_MAX_EXPENSE_FANOUT];   // the fan-out levels
 };
 // PHASE 6 (grid probe, mcr_probe_grid_rng): one record per grid row (blockIdx.y) of a launch, in device memory; path_kernel's
 // `cand_params` points at the launch's records.  Everything a row needs is wave-uniform there: scalar loads.
@@ -137,6 +138,13 @@ __device__ __forceinline__ void store_bits(double* p, unsigned long long bits) {
 // PHASE 6 (SPLIT = true; mcr_probe_grid_rng): GRID FAN-OUT = PHASE 5 with grid.y = grid row (a working month and its own
 // levels).  Same workgroup shape, barriers and votes; the row's record (GridCell, through `cand_params`) holds its parameter
 // block (as in PHASE 2), its snapshot column of a PHASE 1 sweep that stored every distinct month, its levels and its counters.
+// PHASE 7 (SPLIT = true; mcr_probe_contributions_rng): CONTRIBUTION FAN-OUT = PHASE 5's workgroup over the WHOLE path.  The
+// levels differ from month 0 (contributions enter every accumulation month), so there is no snapshot to share: the producer
+// wave stages rows [0, total_months) from a zero Philox carry (PHASE 0's SPLIT producer), and consumer wave j starts from
+// the initial state with its own wave-uniform monthly_contribution = io.fan_expenses[j], runs the accumulation and then the
+// retirement months with the scenario's own monthly_expenses.  Consumers execute the barriers and votes of PHASE 0's SPLIT
+// consumers over rows 0 .. total_months - 1; lock columns and success counts per level as in PHASE 5.  The month is the
+// issue-bound one (MM): counts are bit-identical to a count-only launch with monthly_contribution = fan_expenses[j].
 // EXACT = true: the month in its exact-rounding forms (mcr_device.h) instead of the tolerance form — for configurations whose
 // realized-gains rate lets the reference's denominator clamps bind (DevParams::exact_month), instantiated for the generic XS
 // variants only; -DMCR_K1_EXACT_MONTH builds a library that runs every variant that way (A/B).
@@ -153,17 +161,20 @@ constexpr bool kUniformFixups = false;
 constexpr bool kUniformFixups = true;
 #endif
 template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault>
-__global__ __launch_bounds__((PHASE == 5 || PHASE == 6) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
+__global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
                                                          const DevParams* __restrict__ cand_params) {
     static_assert(!SPLIT || (MODE == 0 && RNG == 0 && !INJ), "the producer / consumer split exists for the count-only Philox variants");
     static_assert(!XS || (PHASE == 0 && !SPLIT && TAXED == 3 && ANNUAL), "extended stream lists run the generic whole-path form");
     static_assert(PHASE != 5 || SPLIT, "the expense fan-out is a producer / consumer form");
     static_assert(PHASE != 6 || SPLIT, "the grid fan-out is a producer / consumer form");
+    static_assert(PHASE != 7 || SPLIT, "the contribution fan-out is a producer / consumer form");
     // PHASE 4 = PHASE 2 (a candidate's decumulation resumed from its accumulation snapshot) time-sliced like PHASE 3: the
     // 17-month verification window of the search is 17 x 196 workgroups = 2.17 rounds of the resident slots.
-    constexpr bool kFan = PHASE == 5 || PHASE == 6;       // expense fan-out: one 64-path block, L consumer waves (levels), one producer wave
+    constexpr bool kExpFan = PHASE == 5 || PHASE == 6;    // expense fan-out: the levels are monthly_expenses, resumed at retirement
+    constexpr bool kConFan = PHASE == 7;                  // contribution fan-out: the levels are monthly_contribution, the whole path
+    constexpr bool kFan = kExpFan || kConFan;             // fan-out workgroup: one 64-path block, L consumer waves (levels), one producer wave
     constexpr bool kGrid = PHASE == 6;                    // ... of grid row blockIdx.y (GridCell)
-    constexpr bool kCand = PHASE == 2 || PHASE == 4 || kFan;   // resumes from a PHASE 1 snapshot (PHASE 2 / 4: per-candidate parameter block)
+    constexpr bool kCand = PHASE == 2 || PHASE == 4 || kExpFan;   // resumes from a PHASE 1 snapshot (PHASE 2 / 4: per-candidate parameter block)
     constexpr bool kSliced = PHASE == 3 || PHASE == 4;    // time-sliced path blocks
     static_assert(!kSliced || (RNG == 0 && !INJ && !SPLIT && !XS), "time-sliced blocks exist for the plain Philox variants");
     static_assert(PHASE != 4 || MODE == 0, "the search probes count only");
@@ -178,7 +189,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6) ? 64 * (MCR_MAX_EXPENSE_
     constexpr int kPaths = kFan ? 64 : kBlock;           // paths of a workgroup = columns of every per-path LDS array
     const int kThreads = kFan ? (int)blockDim.x : SPLIT ? 2 * kBlock : kBlock;
     const int tid = SPLIT ? (int)(threadIdx.x & (kPaths - 1)) : (int)threadIdx.x;    // the path's lane column in every per-path LDS array
-    // PHASE 5: the wave's level (wave-uniform: an SGPR); the producer is wave fan_n
+    // PHASE 5 / 7: the wave's level (wave-uniform: an SGPR); the producer is wave fan_n
     const int fan_j = kFan ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
     const bool producer = kFan ? fan_j == io.fan_n : (SPLIT && threadIdx.x >= (unsigned)kBlock);   // wave-uniform (kBlock = 4 wavefronts)
     // PHASE 2: the parameter block of candidate blockIdx.y, in device memory (a separate const __restrict__ kernel
@@ -374,6 +385,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6) ? 64 * (MCR_MAX_EXPENSE_
         }
         return;
     }
+    if (kConFan) contrib = io.fan_expenses[fan_j];   // PHASE 7: this consumer wave's contribution level (the producer has returned)
     if (PHASE == 1) while (snap_i < io.n_snap && io.snap_months[snap_i] == 0) save_snapshot();
     // PHASE 3: a later segment of a time-sliced block takes its lanes' state over from its predecessor
     // b1 b2 c1 c2 gacc1 gacc2 infl | flags | Philox carry | (per-path outputs: balance and price level at retirement, the
@@ -484,7 +496,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6) ? 64 * (MCR_MAX_EXPENSE_
         }
     }
     // PHASE 5: this wave's spending level, an SGPR (kernel-argument array, wave-uniform index)
-    const double fan_expenses = kGrid ? cell->levels[fan_j] : kFan ? io.fan_expenses[fan_j] : 0.0;
+    const double fan_expenses = kGrid ? cell->levels[fan_j] : kExpFan ? io.fan_expenses[fan_j] : 0.0;
     int ruin_bin = pre_fail ? 0 : -1;
     int done_years = 0;  // completed (observed) retirement years = non-NaN WR entries
     int year = 0;
@@ -508,7 +520,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6) ? 64 * (MCR_MAX_EXPENSE_
                 double g1, ginf, g2;
                 if (kStaged) growth(wm + rmi, g1, ginf, g2);           // staged factors: the LDS reads are issued early
                 const double price = infl;                             // :644
-                const double expenses = (kFan ? fan_expenses : P.monthly_expenses) * price;   // :645-647
+                const double expenses = (kExpFan ? fan_expenses : P.monthly_expenses) * price;   // :645-647
                 // exact form: income accumulates (:649-677) and need = max(0, expenses - income); tolerance form: `income` runs
                 // DOWN from the expenses, one FMA per indexed stream ((amount keep) price), one subtraction per frozen stream
                 // (its slot holds the netted amount): need = max(0, what is left)
@@ -1952,6 +1964,111 @@ int mcr_probe_expenses_rng(const mcr_params* p, const mcr_rng* rng, uint32_t str
     int first_rc = MCR_OK;
     for (int32_t k = 0; k < n_levels && first_rc == MCR_OK; ++k) {
         q.monthly_expenses = monthly_expenses[k];
+        o.counters = counts + (size_t)k * MCR_N_COUNTERS;
+        first_rc = launch_paths(&q, rng, stream_id, path_begin, n_paths, working_months, nullptr, &o, f->side[k % used]);
+    }
+    // always join, also after a failed launch: `main` must not run ahead of work already forked
+    for (int i = 0; i < used; ++i) {
+        if ((e = hipEventRecord(f->done[i], f->side[i])) != hipSuccess) return hip_fail(e, "probe join record");
+        if ((e = hipStreamWaitEvent(main, f->done[i], 0)) != hipSuccess) return hip_fail(e, "probe join wait");
+    }
+    return first_rc;
+}
+
+// Below this many path-wavefronts per level (n_paths / 64) the contribution probe takes the per-level route:
+// MCR_CONTRIBUTION_FANOUT_MIN_WAVES overrides it (0 = always fan out where the shape allows; a huge value = never).
+static uint64_t contribution_fanout_min_waves() {
+    const char* e = std::getenv("MCR_CONTRIBUTION_FANOUT_MIN_WAVES");
+    return (e && *e) ? (uint64_t)std::strtoull(e, nullptr, 10) : 0u;
+}
+
+// Several contribution levels over the same paths, Philox stream: contribution fan-out launches (PHASE 7) over groups of at
+// most fanout_max_levels levels.  The levels differ from month 0, so there is no accumulation sweep and no snapshot: each
+// launch runs the whole path.  Returns MCR_ERR_UNSUPPORTED, having enqueued nothing, for shapes this form does not cover.
+static int probe_contributions_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                      uint64_t n_paths, int32_t wm, const double* levels, int32_t n_levels, uint64_t* counts,
+                                      hipStream_t stream) {
+    if (rng->kind != MCR_RNG_PHILOX || n_levels < 2 || n_paths == 0 || n_paths > ((uint64_t)1 << 31)) return MCR_ERR_UNSUPPORTED;
+    if ((n_paths + 63) / 64 < contribution_fanout_min_waves()) return MCR_ERR_UNSUPPORTED;
+    DevParams d;
+    int rc = derive_params(p, wm, &d);
+    if (rc != MCR_OK) return rc;
+    if (d.n_extra_streams > 0 || (d.exact_month && !kExactMonthDefault)) return MCR_ERR_UNSUPPORTED;
+    // the producer / consumer barrier counts (see launch_paths): producers run rows [0, total_months)
+    if (d.total_months != d.working_months + kMPY * d.retirement_years) { set_error("internal: total_months != working_months + 12 retirement_years"); return MCR_ERR_INVALID_ARG; }
+    const int lmax = fanout_max_levels(d);
+    if (lmax < 2) return MCR_ERR_UNSUPPORTED;
+    d.n_lock_slots = d.n_lock_slots_total;
+    KernelIO io;
+    std::memset(&io, 0, sizeof(io));
+    fill_io_rng(io, rng, nullptr);
+    io.stream_id = stream_id; io.path_begin = path_begin; io.n_paths = n_paths;
+    const dim3 g7((unsigned)((n_paths + 63) / 64));
+    const int n_groups = (n_levels + lmax - 1) / lmax;   // groups of near-equal size
+#define MCR_CFAN(T, A)                                                                                                  \
+    do {                                                                                                               \
+        for (int g = 0, first = 0; g < n_groups; ++g) {                                                                 \
+            const int lg = n_levels / n_groups + (g < n_levels % n_groups ? 1 : 0);                                    \
+            KernelIO fio = io;                                                                                         \
+            fio.out.counters = counts + (size_t)first * MCR_N_COUNTERS;                                                \
+            fio.fan_n = lg;                                                                                            \
+            for (int k = 0; k < lg; ++k) fio.fan_expenses[k] = levels[first + k];                                     \
+            hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 7, true>), g7, dim3(64 * (lg + 1)), fanout_dynamic_lds(d, lg), \
+                               stream, d, fio, (const DevParams*)nullptr);                                             \
+            first += lg;                                                                                               \
+        }                                                                                                              \
+    } while (0)
+#define MCR_CFAN_A(T) do { if (d.any_annual_tax) MCR_CFAN(T, true); else MCR_CFAN(T, false); } while (0)
+    switch (d.tax_mask) { case 0: MCR_CFAN_A(0); break; case 1: MCR_CFAN_A(1); break; case 2: MCR_CFAN_A(2); break; default: MCR_CFAN_A(3); break; }
+#undef MCR_CFAN_A
+#undef MCR_CFAN
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "contribution fan-out probe");
+    return MCR_OK;
+}
+
+int mcr_probe_contributions_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                uint64_t n_paths, int32_t working_months, const double* monthly_contributions, int32_t n_levels,
+                                uint64_t* counts, int device, void* hip_stream) {
+    MCR_ENTER_DEVICE(device);
+    if (n_levels < 0) { set_error("n_levels %d must be >= 0", n_levels); return MCR_ERR_INVALID_ARG; }
+    if (n_levels == 0) return MCR_OK;
+    if (!monthly_contributions || !counts) { set_error("null levels / counts"); return MCR_ERR_INVALID_ARG; }
+    // validate every level BEFORE enqueueing anything (counts stay untouched on an error)
+    DevParams d;
+    int rc = derive_params(p, working_months, &d);
+    if (rc != MCR_OK) return rc;
+    rc = check_rng(rng);
+    if (rc != MCR_OK) return rc;
+    for (int32_t k = 0; k < n_levels; ++k)
+        if (!(std::isfinite(monthly_contributions[k]) && monthly_contributions[k] >= 0.0)) {
+            set_error("monthly_contribution[%d] = %g: must be finite and >= 0 (config.py:57)", k, monthly_contributions[k]);
+            return MCR_ERR_INVALID_ARG;
+        }
+    hipStream_t main = (hipStream_t)hip_stream;
+    hipError_t e = hipMemsetAsync(counts, 0, sizeof(uint64_t) * MCR_N_COUNTERS * (size_t)n_levels, main);
+    if (e != hipSuccess) return hip_fail(e, "probe counters memset");
+    mcr_params q = *p;
+    mcr_outputs o;
+    std::memset(&o, 0, sizeof(o));
+    if (n_levels == 1) {
+        q.monthly_contribution = monthly_contributions[0];
+        o.counters = counts;
+        return launch_paths(&q, rng, stream_id, path_begin, n_paths, working_months, nullptr, &o, main);
+    }
+    const int frc = probe_contributions_fanout(p, rng, stream_id, path_begin, n_paths, working_months, monthly_contributions, n_levels,
+                                               counts, main);
+    if (frc != MCR_ERR_UNSUPPORTED) return frc;     // (unsupported shape: one launch per level below)
+    StreamForkLease fork_lease(device);
+    StreamFork* f = fork_lease.f;
+    if (!f) { set_error("could not create probe streams"); return MCR_ERR_HIP; }
+    const int used = n_levels < kForkStreams ? n_levels : kForkStreams;
+    if ((e = hipEventRecord(f->fork, main)) != hipSuccess) return hip_fail(e, "probe fork");
+    for (int i = 0; i < used; ++i)
+        if ((e = hipStreamWaitEvent(f->side[i], f->fork, 0)) != hipSuccess) return hip_fail(e, "probe fork wait");
+    int first_rc = MCR_OK;
+    for (int32_t k = 0; k < n_levels && first_rc == MCR_OK; ++k) {
+        q.monthly_contribution = monthly_contributions[k];
         o.counters = counts + (size_t)k * MCR_N_COUNTERS;
         first_rc = launch_paths(&q, rng, stream_id, path_begin, n_paths, working_months, nullptr, &o, f->side[k % used]);
     }

@@ -353,6 +353,30 @@ def probe_expenses(params: McrParams, seed, stream_id: int, path_begin: int, n_p
     return counts
 
 
+def probe_contributions(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
+                        monthly_contributions, device: int = 0):
+    """Success counters of several ``monthly_contribution`` levels at one working-month count over the same path range
+    (``mcr_probe_contributions_rng``): level k counts exactly what a count-only launch with ``monthly_contribution =
+    monthly_contributions[k]`` counts.  Up to ``MCR_MAX_EXPENSE_FANOUT`` levels share each path's random numbers (the
+    levels differ from month 0, so each runs the whole path).  Returns a device int64 tensor
+    ``[len(monthly_contributions), 2]`` = ``{successes, paths}``; asynchronous (reading it synchronises)."""
+    import torch
+
+    N.require_device()
+    levels = [float(x) for x in monthly_contributions]
+    arr = (C.c_double * max(1, len(levels)))(*levels)
+    counts = torch.empty((len(levels), N.MCR_N_COUNTERS), dtype=torch.int64, device=torch.device("cuda", int(device)))
+    if not levels:
+        return counts
+    rng = _as_rng(seed)
+    stream = torch.cuda.current_stream(int(device)).cuda_stream
+    rc = N.load_library().mcr_probe_contributions_rng(
+        C.byref(params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), int(working_months), arr,
+        len(levels), counts.data_ptr(), int(device), C.c_void_p(stream),
+    )
+    N.check(rc, "mcr_probe_contributions_rng")
+    return counts
+
 def probe_grid(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months, levels_2d,
                device: int = 0):
     """Success counters of a grid of working-month counts x ``monthly_expenses`` levels over the same path range

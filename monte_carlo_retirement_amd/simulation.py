@@ -843,6 +843,75 @@ class RetirementMonteCarloSimulator:
                             f"({len(curve)} levels evaluated).")
         return expenses, prob, curve
 
+    # ---- minimum-contribution search ---------------------------------------------------------------
+    def success_probability_by_contributions(self, working_months: int, monthly_contributions: Sequence[float],
+                                             num_simulations: Optional[int] = None) -> np.ndarray:
+        """Success % of each ``monthly_contribution`` level at ``working_months``, over the active seed stream's batch of
+        ``num_simulations`` paths (default ``num_simulations_main``), from the contribution fan-out probe
+        (``mcr_probe_contributions_rng``).  Aligned with the input; each value equals, bit for bit,
+        ``_success_probability(run_monte_carlo_simulations(working_months, n)[0])`` of a simulator whose config differs
+        only in ``monthly_contribution``.  Under a process group the levels go through ``distributed.probe_candidates`` (as
+        candidate indices), so every rank returns the same array."""
+        levels = [float(x) for x in monthly_contributions]
+        n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
+        wm = int(working_months)
+        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
+
+        def probe(path_begin, count, idx):
+            return E.probe_contributions(params, rng, self._stream_id, path_begin, count, wm, [levels[i] for i in idx],
+                                         device=dev)
+
+        if not levels:
+            return np.zeros(0, dtype=np.float64)
+        counts = D.probe_candidates(list(range(len(levels))), n, self.shard_min_paths, probe)
+        return np.array([float(np.float64(int(counts[i, N.MCR_CTR_SUCCESS])) / np.float64(n) * 100.0)
+                         for i in range(len(levels))], dtype=np.float64)
+
+    def find_minimum_monthly_contribution(
+        self,
+        working_months: int,
+        verbose: bool = True,
+        progress_callback: Optional[Callable[[dict], None]] = None,
+        resolution: float = 1.0,
+    ) -> Tuple[float, float, List[Dict[str, float]]]:
+        """Smallest ``monthly_contribution`` (whole cents) that reaches ``target_probability`` when retiring after
+        ``working_months``: search stream, ``num_simulations_search`` paths, ``MCR_MAX_EXPENSE_FANOUT`` levels per probe
+        (`saving.search_minimum_contribution`, starting at ``max(monthly_contribution, 1)``).  Returns ``(contribution,
+        probability, curve)``; ``contribution == 0.0`` when nothing needs to be saved and ``-1.0`` when even the cap misses
+        the target.  At ``working_months == 0`` no contribution is ever made: level 0 is probed once.  Deterministic for a
+        given seed, and the same on every rank."""
+        from .saving import CONTRIBUTION_CAP, search_minimum_contribution
+
+        self.use_search_seeds()
+        p = self.params_model
+        wm = int(working_months)
+        n_sims, target = int(p.num_simulations_search), float(p.target_probability)
+        if verbose:
+            logger.info(f"Searching the minimum monthly contribution at {wm} working months for '{p.Nickname}' "
+                        f"(target {target:.2f}%, {n_sims} sims per level, resolution {resolution}).")
+
+        def probe_levels(levels):
+            return list(self.success_probability_by_contributions(wm, levels, n_sims))
+
+        if wm == 0:   # nothing is ever contributed: every level has P(0)
+            prob = probe_levels([0.0])[0]
+            curve = [{"monthly_contribution": 0.0, "probability": prob}]
+            if progress_callback:
+                progress_callback({"type": "contribution_search_iter", "iteration": 1, "monthly_contribution": 0.0,
+                                   "probability": round(prob, 2), "target": target, "lo": None, "hi": None})
+            contribution = 0.0 if prob >= target else -1.0
+        else:
+            contribution, prob, curve = search_minimum_contribution(
+                probe_levels, target, max(float(p.monthly_contribution), 1.0), levels_per_call=N.MCR_MAX_EXPENSE_FANOUT,
+                resolution=resolution, cap=CONTRIBUTION_CAP, on_level=progress_callback)
+        if verbose:
+            if contribution < 0:
+                logger.warning(f"Target not met at any monthly contribution: {prob:.2f}% at {wm} months.")
+            else:
+                logger.info(f"  Contribution search complete: {contribution:.2f} per month with prob {prob:.2f}% "
+                            f"({len(curve)} levels evaluated).")
+        return contribution, prob, curve
+
 
     def _grid_probabilities(self, working_months: Sequence[int], levels_2d: Sequence[Sequence[float]],
                             num_simulations: int) -> np.ndarray:
