@@ -83,6 +83,9 @@ struct GridCell {
 };
 constexpr int kSplitVotePairs = 16;   // SPLIT: pairs of months between two stop votes of a workgroup (a power of two)
 constexpr int kSnapFields = 10;   // b1 b2 c1 c2 gacc1 gacc2 infl contrib | pre_fail | Philox carry words
+// Fields per lane of a time-sliced block's hand-over state in front of its lock columns: path_kernel's kSegFixedFields
+// (PHASE 3 in the three output modes; PHASE 4 is count-only)
+constexpr int seg_fixed_fields(int mode) { return mode >= 1 ? 14 : 9; }
 
 // NaN OUTPUT values travel as integer bit patterns (robust against any no-NaN math assumption: the
 // state machine itself never produces a NaN for valid scenarios).
@@ -1476,6 +1479,88 @@ static void fill_io_rng(KernelIO& io, const mcr_rng* rng, const uint32_t* device
     io.path_seeds = device_path_seeds;
 }
 
+static KernelIO make_io(const mcr_rng* rng, const uint32_t* device_path_seeds, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths) {
+    KernelIO io;
+    std::memset(&io, 0, sizeof(io));
+    fill_io_rng(io, rng, device_path_seeds);
+    io.stream_id = stream_id; io.path_begin = path_begin; io.n_paths = n_paths;
+    return io;
+}
+static mcr_outputs counters_only(uint64_t* counters) {
+    mcr_outputs o;
+    std::memset(&o, 0, sizeof(o));
+    o.counters = counters;
+    return o;
+}
+
+// Run-time properties of a launch -> template arguments of path_kernel: each helper calls the generic lambda `f` with
+// std::integral_constant values, and the lambda names its variant with decltype(T)::value.  A call site instantiates its
+// lambda for every value its helper can pass, no more: the helpers a launch goes through ARE its list of compiled variants.
+template <int V> using int_c = std::integral_constant<int, V>;
+template <typename F> static inline void for_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+// f(T, A): T = the tax mask (which of the two assets is taxed on realized gains), A = any annual-gains tax
+template <typename F> static inline void for_tax_variant(const DevParams& d, F&& f) {
+    for_bool(d.any_annual_tax, [&](auto A) {
+        switch (d.tax_mask) { case 0: f(int_c<0>{}, A); break; case 1: f(int_c<1>{}, A); break; case 2: f(int_c<2>{}, A); break; default: f(int_c<3>{}, A); break; }
+    });
+}
+template <typename F> static inline void for_output_mode(int mode, F&& f) {
+    if (mode == 2) f(int_c<2>{}); else if (mode == 1) f(int_c<1>{}); else f(int_c<0>{});
+}
+
+// The generic variants (XS) carry what the lean ones leave out: records beyond the by-value block and both forms of the month
+static bool needs_exact_month(const DevParams& d) { return d.exact_month && !kExactMonthDefault; }
+static bool needs_generic_variant(const DevParams& d) { return d.n_extra_streams > 0 || needs_exact_month(d); }
+// The producer / consumer forms count on both halves of a workgroup executing the same number of barriers: producers run
+// rows [first, total_months), consumers the accumulation months + 12 months per retirement year.  (They also count on gfx9's
+// s_barrier not waiting for waves that have ended — producers return while consumers still reduce their counts.)
+static int check_barrier_counts(const DevParams& d) {
+    if (d.total_months == d.working_months + kMPY * d.retirement_years) return MCR_OK;
+    set_error("internal: total_months != working_months + 12 retirement_years");
+    return MCR_ERR_INVALID_ARG;
+}
+
+// Scope guard of one stream-ordered allocation: freed behind the work enqueued so far, by release() or at scope exit
+struct StreamAlloc {
+    void* p = nullptr;
+    hipStream_t stream;
+    explicit StreamAlloc(hipStream_t s) : stream(s) {}
+    StreamAlloc(const StreamAlloc&) = delete;
+    StreamAlloc& operator=(const StreamAlloc&) = delete;
+    ~StreamAlloc() { (void)release(); }
+    bool alloc(size_t bytes) {     // false: refused (nothing enqueued, the HIP error cleared)
+        if (hipMallocAsync(&p, bytes, stream) == hipSuccess) return true;
+        (void)hipGetLastError();
+        p = nullptr;
+        return false;
+    }
+    hipError_t release() {
+        if (!p) return hipSuccess;
+        const hipError_t e = hipFreeAsync(p, stream);
+        p = nullptr;
+        return e;
+    }
+};
+// The hand-over memory of a time-sliced launch (PHASE 3 / 4): [n_split][n_fields][kBlock] state + [n_split][q] flags, zeroed.
+struct SegmentHandOver {
+    StreamAlloc mem;
+    explicit SegmentHandOver(hipStream_t s) : mem(s) {}
+    // false: the allocation was refused; otherwise *zeroed is the status of the flags' memset, and io.seg_* are filled if it succeeded
+    bool attach(KernelIO& io, const SegmentPlan& plan, int n_fields, hipError_t* zeroed) {
+        const size_t state_bytes = (size_t)plan.n_split * (size_t)n_fields * kBlock * sizeof(double);
+        const size_t flag_bytes = (size_t)plan.n_split * (size_t)plan.q * sizeof(unsigned int);
+        if (!mem.alloc(state_bytes + flag_bytes)) return false;
+        *zeroed = hipMemsetAsync((char*)mem.p + state_bytes, 0, flag_bytes, mem.stream);
+        if (*zeroed != hipSuccess) return true;
+        io.seg_state = (double*)mem.p;
+        io.seg_flags = (unsigned int*)((char*)mem.p + state_bytes);
+        io.seg_n_split = plan.n_split; io.seg_n_full = plan.n_full; io.seg_q = plan.q; io.seg_max_polls = plan.max_polls;
+        for (int k = 0; k <= plan.q; ++k) io.seg_year[k] = plan.year[k];
+        return true;
+    }
+    hipError_t release() { return mem.release(); }
+};
+
 static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
                         uint64_t n_paths, int32_t wm, const double* injected, const mcr_outputs* out,
                         hipStream_t stream) {
@@ -1493,10 +1578,7 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
     const bool want_summary = out->start_balance || out->final_balance || out->years_to_ruin ||
                               out->first_year_gross_withdrawal || out->first_year_real_gross_withdrawal ||
                               out->inflation_at_retirement || out->success;
-    KernelIO io;
-    std::memset(&io, 0, sizeof(io));
-    fill_io_rng(io, rng, rng->path_seeds);
-    io.stream_id = stream_id; io.path_begin = path_begin; io.n_paths = n_paths;
+    KernelIO io = make_io(rng, rng->path_seeds, stream_id, path_begin, n_paths);
     io.injected = injected; io.out = *out;
     if (io.out.path_stride <= 0) io.out.path_stride = (int64_t)n_paths;
     if (want_traj && (uint64_t)io.out.path_stride < n_paths) {
@@ -1514,14 +1596,11 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
     // kernel variant: output mode x RNG x (any effective realized-gains rate?) x (any annual-gains tax?); injected
     // shocks (parity hook) always take the full-output variant, whose every store is null-checked
     bool split = !injected && !np_rng && mode == 0 && (uint64_t)grid.x * (kBlock / 64) <= split_max_waves();
-    // The producer / consumer form counts on both halves of a workgroup executing the same number of barriers: producers run
-    // rows [0, total_months), consumers wm accumulation months + 12 months per retirement year.  (It also counts on gfx9's
-    // s_barrier not waiting for waves that have ended — producers return while consumers still reduce their counts.)
-    if (split && d.total_months != d.working_months + kMPY * d.retirement_years) { set_error("internal: total_months != working_months + 12 retirement_years"); return MCR_ERR_INVALID_ARG; }
+    if (split && (rc = check_barrier_counts(d)) != MCR_OK) return rc;
     size_t lds = 0;
     rc = plan_path_kernel_lds(d, mode, np_rng, injected != nullptr, split, io.out.hist_n_bins, &lds);
     if (rc != MCR_OK) return rc;
-    if (split && (d.n_lock_slots < d.n_lock_slots_total || d.n_extra_streams > 0 || (d.exact_month && !kExactMonthDefault))) {
+    if (split && (d.n_lock_slots < d.n_lock_slots_total || needs_generic_variant(d))) {
         // the producer / consumer form doubles the stage: where only IT cannot hold every lock column, the unsplit kernel runs
         split = false;
         rc = plan_path_kernel_lds(d, mode, np_rng, false, false, io.out.hist_n_bins, &lds);
@@ -1529,8 +1608,8 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
     }
     // XS: records beyond the by-value block and / or lock slots beyond the LDS budget -> the extended-stream variants
     //     (and configurations that need the exact month: the generic variants carry both forms of it)
-    const bool exact = d.exact_month && !kExactMonthDefault;
-    const bool xs = d.n_lock_slots < d.n_lock_slots_total || d.n_extra_streams > 0 || exact;
+    const bool exact = needs_exact_month(d);
+    const bool xs = d.n_lock_slots < d.n_lock_slots_total || needs_generic_variant(d);
     const char* seg_order = segment_order_env();
     if (seg_order && (np_rng || injected || xs || split)) {
         set_error("MCR_K1_SEGMENT_ORDER=%s set on a launch that is not time-sliced (%s)", seg_order,
@@ -1540,13 +1619,19 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
     StreamSideBlock side;
     rc = side.attach(d, extra, grid.x, stream);
     if (rc != MCR_OK) { (void)side.release(stream); return rc; }
+    const DevParams* const no_cand = nullptr;
+    // f(M, R, I) = (output mode, stream, injection) of the launches that are not time-sliced
+    auto for_family = [&](auto&& f) {
+        if (injected) f(int_c<2>{}, int_c<0>{}, std::true_type{});
+        else for_output_mode(mode, [&](auto M) { if (np_rng) f(M, int_c<1>{}, std::false_type{}); else f(M, int_c<0>{}, std::false_type{}); });
+    };
     if (xs) {
-#define MCR_LAUNCH_X(M, R, I) do { if (exact) hipLaunchKernelGGL((path_kernel<M, R, 3, true, I, 0, false, true, true>), grid, block, lds, stream, d, io, (const DevParams*)nullptr); \
-                                   else hipLaunchKernelGGL((path_kernel<M, R, 3, true, I, 0, false, true>), grid, block, lds, stream, d, io, (const DevParams*)nullptr); } while (0)
-        if (injected) MCR_LAUNCH_X(2, 0, true);
-        else if (!np_rng) { if (mode == 2) MCR_LAUNCH_X(2, 0, false); else if (mode == 1) MCR_LAUNCH_X(1, 0, false); else MCR_LAUNCH_X(0, 0, false); }
-        else { if (mode == 2) MCR_LAUNCH_X(2, 1, false); else if (mode == 1) MCR_LAUNCH_X(1, 1, false); else MCR_LAUNCH_X(0, 1, false); }
-#undef MCR_LAUNCH_X
+        for_family([&](auto M, auto R, auto I) {
+            constexpr int m = decltype(M)::value, r = decltype(R)::value;
+            constexpr bool inj = decltype(I)::value;
+            if (exact) hipLaunchKernelGGL((path_kernel<m, r, 3, true, inj, 0, false, true, true>), grid, block, lds, stream, d, io, no_cand);
+            else hipLaunchKernelGGL((path_kernel<m, r, 3, true, inj, 0, false, true>), grid, block, lds, stream, d, io, no_cand);
+        });
         hipError_t ex = hipGetLastError();
         const hipError_t ef = side.release(stream);
         if (ex != hipSuccess) return hip_fail(ex, "path_kernel launch (extended streams)");
@@ -1564,75 +1649,407 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
             rc = parse_segment_order(seg_order, plan.q, order);
             if (rc != MCR_OK) return rc;
         }
-        if (sliced) {
-            const size_t state_bytes = (size_t)plan.n_split * (size_t)((mode >= 1 ? 14 : 9) + d.n_lock_slots) * kBlock * sizeof(double);
-            const size_t flag_bytes = (size_t)plan.n_split * (size_t)plan.q * sizeof(unsigned int);
-            void* mem = nullptr;
-            hipError_t e = hipMallocAsync(&mem, state_bytes + flag_bytes, stream);
+        SegmentHandOver hand(stream);
+        hipError_t e = hipSuccess;
+        if (sliced && hand.attach(io, plan, seg_fixed_fields(mode) + d.n_lock_slots, &e)) {
             if (e == hipSuccess) {
-                io.seg_state = (double*)mem;
-                io.seg_flags = (unsigned int*)((char*)mem + state_bytes);
-                io.seg_n_split = plan.n_split; io.seg_n_full = plan.n_full; io.seg_q = plan.q; io.seg_max_polls = plan.max_polls;
-                for (int k = 0; k <= plan.q; ++k) io.seg_year[k] = plan.year[k];
-                e = hipMemsetAsync(io.seg_flags, 0, flag_bytes, stream);
-#define MCR_LAUNCH_GM(M, T, A) launch_sliced(&path_kernel<M, 0, T, A, false, 3>, plan, seg_order ? order : nullptr, block, lds, stream, d, io, (const DevParams*)nullptr)
-#define MCR_LAUNCH_G(T, A) do { if (mode == 2) MCR_LAUNCH_GM(2, T, A); else if (mode == 1) MCR_LAUNCH_GM(1, T, A); else MCR_LAUNCH_GM(0, T, A); } while (0)
-#define MCR_LAUNCH_GA(T) do { if (d.any_annual_tax) MCR_LAUNCH_G(T, true); else MCR_LAUNCH_G(T, false); } while (0)
-                if (e == hipSuccess) {
-                    switch (d.tax_mask) { case 0: MCR_LAUNCH_GA(0); break; case 1: MCR_LAUNCH_GA(1); break; case 2: MCR_LAUNCH_GA(2); break; default: MCR_LAUNCH_GA(3); break; }
-                    e = hipGetLastError();
-                }
-#undef MCR_LAUNCH_GA
-#undef MCR_LAUNCH_G
-#undef MCR_LAUNCH_GM
-                const hipError_t ef = hipFreeAsync(mem, stream);
-                if (e != hipSuccess) return hip_fail(e, "path_kernel launch (time-sliced blocks)");
-                if (ef != hipSuccess) return hip_fail(ef, "path_kernel launch (time-sliced blocks): state release");
-                return MCR_OK;
+                for_output_mode(mode, [&](auto M) {
+                    for_tax_variant(d, [&](auto T, auto A) {
+                        launch_sliced(&path_kernel<decltype(M)::value, 0, decltype(T)::value, decltype(A)::value, false, 3>, plan,
+                                      seg_order ? order : nullptr, block, lds, stream, d, io, no_cand);
+                    });
+                });
+                e = hipGetLastError();
             }
-            (void)hipGetLastError();   // (allocation refused: the plain launch below)
-            if (seg_order) { set_error("MCR_K1_SEGMENT_ORDER=%s: the hand-over state could not be allocated", seg_order); return MCR_ERR_HIP; }
+            const hipError_t ef = hand.release();
+            if (e != hipSuccess) return hip_fail(e, "path_kernel launch (time-sliced blocks)");
+            if (ef != hipSuccess) return hip_fail(ef, "path_kernel launch (time-sliced blocks): state release");
+            return MCR_OK;
         }
+        // (allocation refused: the plain launch below)
+        if (sliced && seg_order) { set_error("MCR_K1_SEGMENT_ORDER=%s: the hand-over state could not be allocated", seg_order); return MCR_ERR_HIP; }
     }
     if (split) {
-        const dim3 block2(2 * kBlock);
-#define MCR_LAUNCH_S(T, A) hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 0, true>), grid, block2, lds, stream, d, io, (const DevParams*)nullptr)
-#define MCR_LAUNCH_SA(T) do { if (d.any_annual_tax) MCR_LAUNCH_S(T, true); else MCR_LAUNCH_S(T, false); } while (0)
-        switch (d.tax_mask) { case 0: MCR_LAUNCH_SA(0); break; case 1: MCR_LAUNCH_SA(1); break; case 2: MCR_LAUNCH_SA(2); break; default: MCR_LAUNCH_SA(3); break; }
-#undef MCR_LAUNCH_SA
-#undef MCR_LAUNCH_S
+        for_tax_variant(d, [&](auto T, auto A) {
+            hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 0, true>), grid, dim3(2 * kBlock), lds, stream, d, io, no_cand);
+        });
         hipError_t es = hipGetLastError();
         if (es != hipSuccess) return hip_fail(es, "path_kernel launch (split)");
         return MCR_OK;
     }
-#define MCR_LAUNCH(M, R, T, A, I) hipLaunchKernelGGL((path_kernel<M, R, T, A, I>), grid, block, lds, stream, d, io, (const DevParams*)nullptr)
     // the engine's own stream: one variant per tax mask (which of the two assets is taxed on realized gains); the parity
     // hook and the NumPy stream: taxed / untaxed only (mask 3 computes a zero-rate asset's tax arithmetic as exact zeros)
-#define MCR_LAUNCH_A(M, R, T, I) do { if (d.any_annual_tax) MCR_LAUNCH(M, R, T, true, I); else MCR_LAUNCH(M, R, T, false, I); } while (0)
-#define MCR_LAUNCH_T(M, R, I)                                                                      \
-    do {                                                                                           \
-        if (R == 0 && !I) {                                                                        \
-            switch (d.tax_mask) { case 0: MCR_LAUNCH_A(M, 0, 0, false); break; case 1: MCR_LAUNCH_A(M, 0, 1, false); break; \
-                                  case 2: MCR_LAUNCH_A(M, 0, 2, false); break; default: MCR_LAUNCH_A(M, 0, 3, false); break; } \
-        } else if (d.any_real_rate) MCR_LAUNCH_A(M, R, 3, I);                                       \
-        else MCR_LAUNCH_A(M, R, 0, I);                                                              \
-    } while (0)
-    if (injected) {
-        MCR_LAUNCH_T(2, 0, true);
-    } else if (!np_rng) {
-        if (mode == 2) MCR_LAUNCH_T(2, 0, false);
-        else if (mode == 1) MCR_LAUNCH_T(1, 0, false);
-        else MCR_LAUNCH_T(0, 0, false);
-    } else {
-        if (mode == 2) MCR_LAUNCH_T(2, 1, false);
-        else if (mode == 1) MCR_LAUNCH_T(1, 1, false);
-        else MCR_LAUNCH_T(0, 1, false);
-    }
-#undef MCR_LAUNCH_T
-#undef MCR_LAUNCH_A
-#undef MCR_LAUNCH
+    for_family([&](auto M, auto R, auto I) {
+        constexpr int m = decltype(M)::value, r = decltype(R)::value;
+        constexpr bool inj = decltype(I)::value;
+        auto launch = [&](auto T, auto A) {
+            hipLaunchKernelGGL((path_kernel<m, r, decltype(T)::value, decltype(A)::value, inj>), grid, block, lds, stream, d, io, no_cand);
+        };
+        if constexpr (r == 0 && !inj) for_tax_variant(d, launch);
+        else for_bool(d.any_annual_tax, [&](auto A) { if (d.any_real_rate) launch(int_c<3>{}, A); else launch(int_c<0>{}, A); });
+    });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "path_kernel launch");
+    return MCR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Search probes: several candidates (months, spending or contribution levels, or a grid of both) over the same paths
+// ---------------------------------------------------------------------------------------------
+// The route every probe can fall back to: one count-only launch per candidate, launch(k, side stream) for k in [0, n), on the
+// side streams of a leased StreamFork; the caller's stream waits for all of them.  Returns the first error.
+template <typename Launch>
+static int fork_join(int device, hipStream_t main, int n, Launch&& launch) {
+    StreamForkLease fork_lease(device);
+    StreamFork* f = fork_lease.f;
+    if (!f) { set_error("could not create probe streams"); return MCR_ERR_HIP; }
+    const int used = n < kForkStreams ? n : kForkStreams;
+    hipError_t e;
+    if ((e = hipEventRecord(f->fork, main)) != hipSuccess) return hip_fail(e, "probe fork");
+    for (int i = 0; i < used; ++i)
+        if ((e = hipStreamWaitEvent(f->side[i], f->fork, 0)) != hipSuccess) return hip_fail(e, "probe fork wait");
+    int first_rc = MCR_OK;
+    for (int k = 0; k < n && first_rc == MCR_OK; ++k) first_rc = launch(k, f->side[k % used]);
+    // always join, also after a failed launch: `main` must not run ahead of work already forked
+    for (int i = 0; i < used; ++i) {
+        if ((e = hipEventRecord(f->done[i], f->side[i])) != hipSuccess) return hip_fail(e, "probe join record");
+        if ((e = hipStreamWaitEvent(main, f->done[i], 0)) != hipSuccess) return hip_fail(e, "probe join wait");
+    }
+    return first_rc;
+}
+// Probes validate every candidate BEFORE enqueueing anything, so a bad one leaves no half-forked work behind and `counts` untouched
+static int validate_months(const mcr_params* p, const int32_t* working_months, int32_t n) {
+    for (int32_t c = 0; c < n; ++c) {
+        DevParams d;
+        const int rc = derive_params(p, working_months[c], &d);
+        if (rc != MCR_OK) return rc;
+    }
+    return MCR_OK;
+}
+static int zero_counters(uint64_t* counts, size_t n_blocks, hipStream_t stream) {
+    const hipError_t e = hipMemsetAsync(counts, 0, sizeof(uint64_t) * MCR_N_COUNTERS * n_blocks, stream);
+    return e == hipSuccess ? MCR_OK : hip_fail(e, "probe counters memset");
+}
+
+// Ascending order of a probe's candidate months (stable): order[i] = index into `months` of the i-th smallest
+static void sort_candidates(const int32_t* months, int n, int* order) {
+    for (int i = 0; i < n; ++i) {
+        int k = i;
+        while (k > 0 && months[order[k - 1]] > months[i]) { order[k] = order[k - 1]; --k; }
+        order[k] = i;
+    }
+}
+// The device memory of a shared-accumulation probe: ONE stream-ordered allocation of n_snap snapshot columns (io.snap, the
+// paths padded to whole wavefronts) followed by the launch's parameter records, uploaded from the host.
+constexpr size_t kSnapshotCapBytes = (size_t)4 << 30;   // huge probes are throughput-bound anyway: they take the plain route
+struct SnapshotBlock {
+    StreamAlloc mem;
+    const void* records = nullptr;
+    explicit SnapshotBlock(hipStream_t s) : mem(s) {}
+    // false: snapshots above `cap`, or the allocation was refused (nothing enqueued); otherwise *upload is the copy's status
+    bool attach(KernelIO& io, int n_snap, const void* host_records, size_t records_bytes, hipError_t* upload, size_t cap = kSnapshotCapBytes) {
+        io.n_snap = n_snap;
+        io.snap_stride = (int64_t)((io.n_paths + 63) / 64 * 64);
+        const size_t snap_bytes = (size_t)n_snap * kSnapFields * (size_t)io.snap_stride * sizeof(double);
+        if (snap_bytes > cap || !mem.alloc(snap_bytes + records_bytes)) return false;
+        io.snap = (double*)mem.p;
+        records = (char*)mem.p + snap_bytes;
+        *upload = records_bytes ? hipMemcpyAsync((char*)mem.p + snap_bytes, host_records, records_bytes, hipMemcpyHostToDevice, mem.stream) : hipSuccess;
+        return true;
+    }
+};
+// The accumulation sweep of a shared-accumulation probe (PHASE 1: stores the state at the end of every io.snap_months[c]); it
+// takes the producer / consumer split on its own while its launch leaves SIMDs idle
+static void launch_accumulation(const DevParams& d, const KernelIO& io, const DevParams* cand, size_t lds, hipStream_t stream) {
+    const dim3 g1((unsigned)((io.n_paths + kBlock - 1) / kBlock));
+    const bool split1 = (uint64_t)g1.x * (kBlock / 64) <= split_max_waves();
+    for_tax_variant(d, [&](auto T, auto A) {
+        constexpr int t = decltype(T)::value;
+        constexpr bool a = decltype(A)::value;
+        if (split1) hipLaunchKernelGGL((path_kernel<0, 0, t, a, false, 1, true>), g1, dim3(2 * kBlock), lds, stream, d, io, cand);
+        else hipLaunchKernelGGL((path_kernel<0, 0, t, a, false, 1>), g1, dim3(kBlock), lds, stream, d, io, cand);
+    });
+}
+
+// Several candidates over the same paths, Philox stream: ONE accumulation sweep to the largest candidate that stores the
+// state at the end of every candidate month (PHASE 1), then ONE launch whose grid.y is the candidate and which resumes
+// every decumulation from its snapshot (PHASE 2).  The candidates' parameter blocks (stream start months, horizon) go to
+// device memory; snapshots and blocks are stream-ordered allocations.  Counts are identical to one launch per candidate.
+static int probe_shared_prefix(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                               const int32_t* working_months, int32_t n_cand, uint64_t* counts, hipStream_t stream) {
+    if (n_cand < 2 || n_paths == 0 || n_paths > ((uint64_t)1 << 31)) return MCR_ERR_UNSUPPORTED;
+    int order[MCR_MAX_PROBE_CANDIDATES];
+    sort_candidates(working_months, n_cand, order);
+    for (int i = 1; i < n_cand; ++i)
+        if (working_months[order[i]] == working_months[order[i - 1]]) return MCR_ERR_UNSUPPORTED;   // duplicates: plain route
+    std::vector<DevParams> blocks((size_t)n_cand);
+    for (int i = 0; i < n_cand; ++i) {
+        const int rc = derive_params(p, working_months[order[i]], &blocks[(size_t)i]);
+        if (rc != MCR_OK) return rc;
+    }
+    DevParams& top = blocks[(size_t)n_cand - 1];
+    // (stream lists beyond the by-value block, or lock slots beyond the LDS of the split form, take one launch per candidate:
+    //  each then carries its own device table / overflow block)
+    if (needs_generic_variant(top)) return MCR_ERR_UNSUPPORTED;
+    size_t lds = 0;
+    if (plan_path_kernel_lds(top, 0, false, false, true, 0, &lds) != MCR_OK || top.n_lock_slots < top.n_lock_slots_total) return MCR_ERR_UNSUPPORTED;
+    for (DevParams& b : blocks) b.n_lock_slots = top.n_lock_slots;
+    KernelIO io = make_io(rng, nullptr, stream_id, path_begin, n_paths);
+    io.out.counters = counts;
+    for (int i = 0; i < n_cand; ++i) { io.snap_months[i] = working_months[order[i]]; io.cand_out[i] = order[i]; }
+    SnapshotBlock snap(stream);
+    hipError_t e = hipSuccess;
+    if (!snap.attach(io, n_cand, blocks.data(), (size_t)n_cand * sizeof(DevParams), &e)) return MCR_ERR_UNSUPPORTED;
+    const DevParams* d_blocks = (const DevParams*)snap.records;
+    if (e == hipSuccess) {
+        if (int rc = check_barrier_counts(top)) return rc;
+        // (the decumulation launch takes the producer / consumer split on its own, like the sweep)
+        const dim3 g2((unsigned)((n_paths + kBlock - 1) / kBlock), (unsigned)n_cand);
+        const bool split2 = (uint64_t)g2.x * g2.y * (kBlock / 64) <= split_max_waves();
+        // the candidates' decumulations time-sliced (PHASE 4) where their workgroups are a few rounds of the resident slots
+        // with a mostly empty last one: the search's 17-month verification window at 50 000 paths is 3 332 workgroups = 2.17 rounds
+        SegmentPlan plan;
+        SegmentHandOver hand(stream);
+        bool sliced = false;
+        const char* seg_order = segment_order_env();
+        int seg_perm[kMaxSegments];
+        if (!split2 && plan_segments(top, g2.x * g2.y, 0, &plan, true)) {
+            if (seg_order)
+                if (int rc = parse_segment_order(seg_order, plan.q, seg_perm)) return rc;
+            hipError_t ez = hipSuccess;
+            sliced = hand.attach(io, plan, seg_fixed_fields(0) + top.n_lock_slots, &ez) && ez == hipSuccess;
+            if (sliced) io.seg_blocks_per_cand = (int32_t)g2.x;
+            else { (void)hipGetLastError(); (void)hand.release(); }   // (refused: the un-sliced launch)
+        }
+        if (seg_order && !sliced) {
+            set_error("MCR_K1_SEGMENT_ORDER=%s set on a shared-prefix probe whose decumulation launch is not time-sliced", seg_order);
+            return MCR_ERR_INVALID_ARG;
+        }
+        launch_accumulation(top, io, d_blocks, lds, stream);
+        for_tax_variant(top, [&](auto T, auto A) {
+            constexpr int t = decltype(T)::value;
+            constexpr bool a = decltype(A)::value;
+            if (split2) hipLaunchKernelGGL((path_kernel<0, 0, t, a, false, 2, true>), g2, dim3(2 * kBlock), lds, stream, top, io, d_blocks);
+            else if (sliced) launch_sliced(&path_kernel<0, 0, t, a, false, 4>, plan, seg_order ? seg_perm : nullptr, dim3(kBlock), lds, stream, top, io, d_blocks);
+            else hipLaunchKernelGGL((path_kernel<0, 0, t, a, false, 2>), g2, dim3(kBlock), lds, stream, top, io, d_blocks);
+        });
+        e = hipGetLastError();
+        (void)hand.release();
+    }
+    const hipError_t ef = snap.mem.release();
+    if (e != hipSuccess) return hip_fail(e, "shared-prefix probe");
+    if (ef != hipSuccess) return hip_fail(ef, "shared-prefix probe (free)");
+    return MCR_OK;
+}
+
+// LDS of a level fan-out launch (path_kernel PHASE 5 / 6 / 7): STATIC = the math tables and the double-buffered 64-column stage
+// (+ the unused summary / segment words); DYNAMIC = the level counters and [n_lock_slots][64] lock columns per consumer wave.
+// Every lock slot stays in LDS (no overflow block in this form): the levels per launch are lowered until they fit.
+static size_t fanout_static_lds() { return (size_t)kMathTabBytes + (size_t)2 * 6 * 64 * sizeof(double) + 512; }   // (16 640 B compiled)
+static size_t fanout_dynamic_lds(const DevParams& d, int levels) {
+    return (size_t)MCR_MAX_EXPENSE_FANOUT * sizeof(unsigned int) + (size_t)levels * (size_t)d.n_lock_slots_total * 64 * sizeof(double);
+}
+static int fanout_max_levels(const DevParams& d) {
+    int l = MCR_MAX_EXPENSE_FANOUT;
+    while (l > 0 && fanout_static_lds() + fanout_dynamic_lds(d, l) > kLdsPerWorkgroup) --l;
+    return l;
+}
+// Below this many path-wavefronts per level (n_paths / 64) the per-level route runs instead of a fan-out: the environment
+// variable overrides it (0 = always fan out where the shape allows; a huge value = never).
+static uint64_t fanout_min_waves(const char* env_name = "MCR_EXPENSE_FANOUT_MIN_WAVES") {
+    const char* e = std::getenv(env_name);
+    return (e && *e) ? (uint64_t)std::strtoull(e, nullptr, 10) : 0u;
+}
+// Fan-out launches take n_levels in groups of near-equal size, none above lmax: f(g, first, lg) for group g = levels [first, first + lg)
+struct LevelGroups {
+    int n_levels, n_groups;
+    LevelGroups(int n_levels, int lmax) : n_levels(n_levels), n_groups((n_levels + lmax - 1) / lmax) {}
+    template <typename F> void for_each(F&& f) const {
+        for (int g = 0, first = 0; g < n_groups; ++g) {
+            const int lg = n_levels / n_groups + (g < n_levels % n_groups ? 1 : 0);
+            f(g, first, lg);
+            first += lg;
+        }
+    }
+};
+// What the expense and the contribution fan-out ask of a probe's shape.  MCR_OK: *d = the parameter block with every lock slot
+// in LDS, *lmax = levels per launch; MCR_ERR_UNSUPPORTED for shapes the form does not cover.
+static int plan_level_fanout(const mcr_params* p, const mcr_rng* rng, uint64_t n_paths, int32_t wm, int32_t n_levels, uint64_t min_waves,
+                             DevParams* d, int* lmax) {
+    if (rng->kind != MCR_RNG_PHILOX || n_levels < 2 || n_paths == 0 || n_paths > ((uint64_t)1 << 31)) return MCR_ERR_UNSUPPORTED;
+    if ((n_paths + 63) / 64 < min_waves) return MCR_ERR_UNSUPPORTED;
+    int rc = derive_params(p, wm, d);
+    if (rc != MCR_OK) return rc;
+    if (needs_generic_variant(*d)) return MCR_ERR_UNSUPPORTED;
+    if ((rc = check_barrier_counts(*d)) != MCR_OK) return rc;
+    *lmax = fanout_max_levels(*d);
+    if (*lmax < 2) return MCR_ERR_UNSUPPORTED;
+    d->n_lock_slots = d->n_lock_slots_total;
+    return MCR_OK;
+}
+// The fan-out launches of a level probe: consumer wave j of a group's launch runs level first + j and counts into its block.
+// PHASE 5: spending levels, resumed from the snapshot; PHASE 7: contribution levels, from month 0.
+template <int PHASE>
+static void launch_level_fanout(const DevParams& d, const KernelIO& io, const double* levels, const LevelGroups& groups, uint64_t* counts,
+                                hipStream_t stream) {
+    const dim3 grid((unsigned)((io.n_paths + 63) / 64));
+    for_tax_variant(d, [&](auto T, auto A) {
+        groups.for_each([&](int, int first, int lg) {
+            KernelIO fio = io;
+            fio.out.counters = counts + (size_t)first * MCR_N_COUNTERS;
+            fio.fan_n = lg;
+            for (int k = 0; k < lg; ++k) fio.fan_expenses[k] = levels[first + k];
+            hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, PHASE, true>), grid, dim3(64 * (lg + 1)),
+                               fanout_dynamic_lds(d, lg), stream, d, fio, (const DevParams*)nullptr);
+        });
+    });
+}
+
+// Several spending levels over the same paths, Philox stream: ONE accumulation sweep to working_months (PHASE 1, one
+// snapshot), then expense fan-out launches (PHASE 5) over groups of at most MCR_MAX_EXPENSE_FANOUT levels.  Returns
+// MCR_ERR_UNSUPPORTED, having enqueued nothing, for shapes this form does not cover.
+static int probe_expenses_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                                 int32_t wm, const double* levels, int32_t n_levels, uint64_t* counts, hipStream_t stream) {
+    DevParams d;
+    int lmax = 0;
+    if (int rc = plan_level_fanout(p, rng, n_paths, wm, n_levels, fanout_min_waves(), &d, &lmax)) return rc;
+    DevParams d1 = d;    // (PHASE 1 never reads a lock column: its plan may lower the LDS slots)
+    size_t lds1 = 0;
+    if (plan_path_kernel_lds(d1, 0, false, false, true, 0, &lds1) != MCR_OK) { (void)hipGetLastError(); return MCR_ERR_UNSUPPORTED; }
+    KernelIO io = make_io(rng, nullptr, stream_id, path_begin, n_paths);
+    io.snap_months[0] = wm;
+    SnapshotBlock snap(stream);
+    hipError_t e = hipSuccess;
+    if (!snap.attach(io, 1, nullptr, 0, &e, SIZE_MAX)) return MCR_ERR_UNSUPPORTED;   // (one column: no cap, the allocator decides)
+    launch_accumulation(d1, io, nullptr, lds1, stream);
+    launch_level_fanout<5>(d, io, levels, LevelGroups(n_levels, lmax), counts, stream);
+    e = hipGetLastError();
+    const hipError_t ef = snap.mem.release();
+    if (e != hipSuccess) return hip_fail(e, "expense fan-out probe");
+    if (ef != hipSuccess) return hip_fail(ef, "expense fan-out probe (free)");
+    return MCR_OK;
+}
+
+// Several contribution levels over the same paths, Philox stream: contribution fan-out launches (PHASE 7) over groups of at
+// most fanout_max_levels levels.  The levels differ from month 0, so there is no accumulation sweep and no snapshot: each
+// launch runs the whole path.  Returns MCR_ERR_UNSUPPORTED, having enqueued nothing, for shapes this form does not cover.
+static int probe_contributions_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                      uint64_t n_paths, int32_t wm, const double* levels, int32_t n_levels, uint64_t* counts,
+                                      hipStream_t stream) {
+    DevParams d;
+    int lmax = 0;
+    if (int rc = plan_level_fanout(p, rng, n_paths, wm, n_levels, fanout_min_waves("MCR_CONTRIBUTION_FANOUT_MIN_WAVES"), &d, &lmax)) return rc;
+    const KernelIO io = make_io(rng, nullptr, stream_id, path_begin, n_paths);
+    launch_level_fanout<7>(d, io, levels, LevelGroups(n_levels, lmax), counts, stream);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "contribution fan-out probe");
+    return MCR_OK;
+}
+
+// A level probe (mcr_probe_expenses_rng / mcr_probe_contributions_rng): n_levels values of one field of the parameter block,
+// `name` (config.py:`config_line`) in messages.  kFanout, the shared-work route, is tried first; where it answers
+// MCR_ERR_UNSUPPORTED (unsupported shape / allocation refused) one launch per level runs instead.
+using LevelFanout = int(const mcr_params*, const mcr_rng*, uint32_t, uint64_t, uint64_t, int32_t, const double*, int32_t, uint64_t*, hipStream_t);
+template <LevelFanout* kFanout>
+static int probe_levels(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths, int32_t wm,
+                        double mcr_params::*field, const char* name, int config_line, const double* levels, int32_t n_levels,
+                        uint64_t* counts, int device, hipStream_t main) {
+    if (n_levels < 0) { set_error("n_levels %d must be >= 0", n_levels); return MCR_ERR_INVALID_ARG; }
+    if (n_levels == 0) return MCR_OK;
+    if (!levels || !counts) { set_error("null levels / counts"); return MCR_ERR_INVALID_ARG; }
+    // validate every level BEFORE enqueueing anything (counts stay untouched on an error)
+    int rc = validate_months(p, &wm, 1);
+    if (rc != MCR_OK) return rc;
+    rc = check_rng(rng);
+    if (rc != MCR_OK) return rc;
+    for (int32_t k = 0; k < n_levels; ++k)
+        if (!(std::isfinite(levels[k]) && levels[k] >= 0.0)) {
+            set_error("%s[%d] = %g: must be finite and >= 0 (config.py:%d)", name, k, levels[k], config_line);
+            return MCR_ERR_INVALID_ARG;
+        }
+    rc = zero_counters(counts, (size_t)n_levels, main);
+    if (rc != MCR_OK) return rc;
+    mcr_params q = *p;
+    auto launch_level = [&](int k, hipStream_t s) {
+        q.*field = levels[k];
+        const mcr_outputs o = counters_only(counts + (size_t)k * MCR_N_COUNTERS);
+        return launch_paths(&q, rng, stream_id, path_begin, n_paths, wm, nullptr, &o, s);
+    };
+    if (n_levels == 1) return launch_level(0, main);
+    rc = kFanout(p, rng, stream_id, path_begin, n_paths, wm, levels, n_levels, counts, main);
+    if (rc != MCR_ERR_UNSUPPORTED) return rc;
+    return fork_join(device, main, n_levels, launch_level);
+}
+
+// A grid of working months x spending levels over the same paths, Philox stream: ONE accumulation sweep (PHASE 1) stores
+// the state at the end of every distinct month, then grid fan-out launches (PHASE 6, grid.y = row) resume every row's
+// decumulation with up to fanout_max_levels of its levels per launch.  Rows of a repeated month share its snapshot column.
+// Returns MCR_ERR_UNSUPPORTED, having enqueued nothing, for shapes this form does not cover.
+static int probe_grid_shared(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                             const int32_t* working_months, int32_t n_rows, const double* levels, int32_t n_levels, uint64_t* counts,
+                             hipStream_t stream) {
+    if (rng->kind != MCR_RNG_PHILOX || n_rows < 2 || n_paths == 0 || n_paths > ((uint64_t)1 << 31)) return MCR_ERR_UNSUPPORTED;
+    if ((n_paths + 63) / 64 < fanout_min_waves()) return MCR_ERR_UNSUPPORTED;
+    std::vector<int> order((size_t)n_rows), col((size_t)n_rows);
+    sort_candidates(working_months, n_rows, order.data());
+    std::vector<int32_t> months;    // distinct months, ascending = the snapshot columns
+    for (int i = 0; i < n_rows; ++i) {
+        const int32_t m = working_months[order[(size_t)i]];
+        if (months.empty() || months.back() != m) months.push_back(m);
+        col[(size_t)order[(size_t)i]] = (int)months.size() - 1;
+    }
+    const int n_cand = (int)months.size();
+    if (n_cand < 2 || n_cand > MCR_MAX_PROBE_CANDIDATES) return MCR_ERR_UNSUPPORTED;
+    std::vector<DevParams> blocks((size_t)n_cand);
+    for (int c = 0; c < n_cand; ++c) {
+        DevParams& b = blocks[(size_t)c];
+        int rc = derive_params(p, months[(size_t)c], &b);
+        if (rc != MCR_OK) return rc;
+        if ((rc = check_barrier_counts(b)) != MCR_OK) return rc;
+        b.n_lock_slots = b.n_lock_slots_total;   // (the same for every month: it depends on the stream list only)
+    }
+    const DevParams& top = blocks[(size_t)n_cand - 1];
+    if (needs_generic_variant(top)) return MCR_ERR_UNSUPPORTED;
+    const int lmax = fanout_max_levels(top);
+    if (lmax < 1) return MCR_ERR_UNSUPPORTED;
+    DevParams d1 = top;    // (PHASE 1 never reads a lock column: its plan may lower the LDS slots)
+    size_t lds1 = 0;
+    if (plan_path_kernel_lds(d1, 0, false, false, true, 0, &lds1) != MCR_OK) { (void)hipGetLastError(); return MCR_ERR_UNSUPPORTED; }
+    KernelIO io = make_io(rng, nullptr, stream_id, path_begin, n_paths);
+    for (int c = 0; c < n_cand; ++c) io.snap_months[c] = months[(size_t)c];
+    // the rows' records, level group by level group: group g covers levels [first, first + lg) of every row
+    const LevelGroups groups(n_levels, lmax);
+    std::vector<GridCell> cells((size_t)groups.n_groups * (size_t)n_rows);
+    std::memset(cells.data(), 0, cells.size() * sizeof(GridCell));
+    groups.for_each([&](int g, int first, int lg) {
+        for (int r = 0; r < n_rows; ++r) {
+            GridCell& x = cells[(size_t)g * n_rows + r];
+            x.p = blocks[(size_t)col[(size_t)r]];
+            x.snap = col[(size_t)r];
+            x.counters = counts + ((size_t)r * n_levels + first) * MCR_N_COUNTERS;
+            for (int k = 0; k < lg; ++k) x.levels[k] = levels[(size_t)r * n_levels + first + k];
+        }
+    });
+    SnapshotBlock snap(stream);
+    hipError_t e = hipSuccess;
+    if (!snap.attach(io, n_cand, cells.data(), cells.size() * sizeof(GridCell), &e)) return MCR_ERR_UNSUPPORTED;
+    const GridCell* d_cells = (const GridCell*)snap.records;
+    if (e == hipSuccess) {
+        const dim3 g6((unsigned)((n_paths + 63) / 64), (unsigned)n_rows);
+        launch_accumulation(d1, io, nullptr, lds1, stream);
+        for_tax_variant(top, [&](auto T, auto A) {
+            groups.for_each([&](int g, int, int lg) {
+                KernelIO gio = io;
+                gio.fan_n = lg;
+                hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 6, true>), g6, dim3(64 * (lg + 1)),
+                                   fanout_dynamic_lds(top, lg), stream, top, gio, (const DevParams*)(d_cells + (size_t)g * n_rows));
+            });
+        });
+        e = hipGetLastError();
+    }
+    const hipError_t ef = snap.mem.release();
+    if (e != hipSuccess) return hip_fail(e, "grid probe");
+    if (ef != hipSuccess) return hip_fail(ef, "grid probe (free)");
     return MCR_OK;
 }
 
@@ -1679,496 +2096,45 @@ int mcr_run_batch_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_i
                         (hipStream_t)hip_stream);
 }
 
-// Ascending order of a probe's candidate months (stable): order[i] = index into `months` of the i-th smallest
-static void sort_candidates(const int32_t* months, int n, int* order) {
-    for (int i = 0; i < n; ++i) {
-        int k = i;
-        while (k > 0 && months[order[k - 1]] > months[i]) { order[k] = order[k - 1]; --k; }
-        order[k] = i;
-    }
-}
-// The device memory of a shared-accumulation probe: ONE stream-ordered allocation of snap_bytes of snapshots followed by the
-// launch's parameter records (`blocks`, uploaded from the host).  false: the allocation was refused (nothing enqueued);
-// otherwise *mem is the allocation and *copy the upload's status.
-static bool alloc_snapshots_and_blocks(size_t snap_bytes, const void* blocks, size_t blocks_bytes, hipStream_t stream, void** mem,
-                                       hipError_t* copy) {
-    *mem = nullptr;
-    if (hipMallocAsync(mem, snap_bytes + blocks_bytes, stream) != hipSuccess) { (void)hipGetLastError(); return false; }
-    *copy = hipMemcpyAsync((char*)*mem + snap_bytes, blocks, blocks_bytes, hipMemcpyHostToDevice, stream);
-    return true;
-}
-
-// Several candidates over the same paths, Philox stream: ONE accumulation sweep to the largest candidate that stores the
-// state at the end of every candidate month (PHASE 1), then ONE launch whose grid.y is the candidate and which resumes
-// every decumulation from its snapshot (PHASE 2).  The candidates' parameter blocks (stream start months, horizon) go to
-// device memory; snapshots and blocks are stream-ordered allocations.  Counts are identical to one launch per candidate.
-static int probe_shared_prefix(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
-                               const int32_t* working_months, int32_t n_cand, uint64_t* counts, hipStream_t stream) {
-    if (n_cand < 2 || n_paths == 0 || n_paths > ((uint64_t)1 << 31)) return MCR_ERR_UNSUPPORTED;
-    int order[MCR_MAX_PROBE_CANDIDATES];
-    sort_candidates(working_months, n_cand, order);
-    for (int i = 1; i < n_cand; ++i)
-        if (working_months[order[i]] == working_months[order[i - 1]]) return MCR_ERR_UNSUPPORTED;   // duplicates: plain route
-    std::vector<DevParams> blocks((size_t)n_cand);
-    for (int i = 0; i < n_cand; ++i) {
-        const int rc = derive_params(p, working_months[order[i]], &blocks[(size_t)i]);
-        if (rc != MCR_OK) return rc;
-    }
-    DevParams& top = blocks[(size_t)n_cand - 1];
-    // (stream lists beyond the by-value block, or lock slots beyond the LDS of the split form, take one launch per candidate:
-    //  each then carries its own device table / overflow block)
-    if (top.n_extra_streams > 0 || (top.exact_month && !kExactMonthDefault)) return MCR_ERR_UNSUPPORTED;
-    size_t lds = 0;
-    if (plan_path_kernel_lds(top, 0, false, false, true, 0, &lds) != MCR_OK || top.n_lock_slots < top.n_lock_slots_total) return MCR_ERR_UNSUPPORTED;
-    for (DevParams& b : blocks) b.n_lock_slots = top.n_lock_slots;
-    KernelIO io;
-    std::memset(&io, 0, sizeof(io));
-    fill_io_rng(io, rng, nullptr);
-    io.stream_id = stream_id; io.path_begin = path_begin; io.n_paths = n_paths;
-    io.out.counters = counts;
-    io.n_snap = n_cand;
-    io.snap_stride = (int64_t)((n_paths + 63) / 64 * 64);
-    for (int i = 0; i < n_cand; ++i) { io.snap_months[i] = working_months[order[i]]; io.cand_out[i] = order[i]; }
-    const size_t snap_bytes = (size_t)n_cand * kSnapFields * (size_t)io.snap_stride * sizeof(double);
-    const size_t blocks_bytes = (size_t)n_cand * sizeof(DevParams);
-    if (snap_bytes > ((size_t)4 << 30)) return MCR_ERR_UNSUPPORTED;   // huge probes are throughput-bound anyway: plain route
-    void* mem = nullptr;
-    hipError_t e = hipSuccess;
-    if (!alloc_snapshots_and_blocks(snap_bytes, blocks.data(), blocks_bytes, stream, &mem, &e)) return MCR_ERR_UNSUPPORTED;
-    io.snap = (double*)mem;
-    const DevParams* d_blocks = (const DevParams*)((char*)mem + snap_bytes);
-    if (e == hipSuccess) {
-        const dim3 block(kBlock), g1((unsigned)((n_paths + kBlock - 1) / kBlock)), g2(g1.x, (unsigned)n_cand);
-        // (either phase takes the producer / consumer split on its own while its launch leaves SIMDs idle)
-        if (top.total_months != top.working_months + kMPY * top.retirement_years) { (void)hipFreeAsync(mem, stream); set_error("internal: total_months != working_months + 12 retirement_years"); return MCR_ERR_INVALID_ARG; }   // (the split forms' barrier counts, see launch_paths)
-        const bool split1 = (uint64_t)g1.x * (kBlock / 64) <= split_max_waves();
-        const bool split2 = (uint64_t)g2.x * g2.y * (kBlock / 64) <= split_max_waves();
-        const dim3 block2(2 * kBlock);
-        // the candidates' decumulations time-sliced (PHASE 4) where their workgroups are a few rounds of the resident slots
-        // with a mostly empty last one: the search's 17-month verification window at 50 000 paths is 3 332 workgroups = 2.17 rounds
-        SegmentPlan plan;
-        void* seg_mem = nullptr;
-        dim3 g4(0);
-        const char* seg_order = segment_order_env();
-        int order[kMaxSegments];
-        if (!split2 && plan_segments(top, g2.x * g2.y, 0, &plan, true)) {
-            const int orc = seg_order ? parse_segment_order(seg_order, plan.q, order) : MCR_OK;
-            if (orc != MCR_OK) { (void)hipFreeAsync(mem, stream); return orc; }
-            const size_t state_bytes = (size_t)plan.n_split * (size_t)(9 + top.n_lock_slots) * kBlock * sizeof(double);
-            const size_t flag_bytes = (size_t)plan.n_split * (size_t)plan.q * sizeof(unsigned int);
-            if (hipMallocAsync(&seg_mem, state_bytes + flag_bytes, stream) == hipSuccess &&
-                hipMemsetAsync((char*)seg_mem + state_bytes, 0, flag_bytes, stream) == hipSuccess) {
-                io.seg_state = (double*)seg_mem;
-                io.seg_flags = (unsigned int*)((char*)seg_mem + state_bytes);
-                io.seg_n_split = plan.n_split; io.seg_n_full = plan.n_full; io.seg_q = plan.q; io.seg_max_polls = plan.max_polls;
-                io.seg_blocks_per_cand = (int32_t)g2.x;
-                for (int k = 0; k <= plan.q; ++k) io.seg_year[k] = plan.year[k];
-                g4 = dim3((unsigned)(plan.n_full + plan.q * plan.n_split));
-            } else {
-                (void)hipGetLastError();
-                if (seg_mem) { (void)hipFreeAsync(seg_mem, stream); seg_mem = nullptr; }
-            }
-        }
-        if (seg_order && !g4.x) {
-            (void)hipFreeAsync(mem, stream);
-            set_error("MCR_K1_SEGMENT_ORDER=%s set on a shared-prefix probe whose decumulation launch is not time-sliced", seg_order);
-            return MCR_ERR_INVALID_ARG;
-        }
-#define MCR_PHASES(T, A)                                                                                          \
-        do {                                                                                                       \
-            if (split1) hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 1, true>), g1, block2, lds, stream, top, io, d_blocks); \
-            else hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 1>), g1, block, lds, stream, top, io, d_blocks);    \
-            if (split2) hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 2, true>), g2, block2, lds, stream, top, io, d_blocks); \
-            else if (g4.x) launch_sliced(&path_kernel<0, 0, T, A, false, 4>, plan, seg_order ? order : nullptr, block, lds, stream, top, io, d_blocks); \
-            else hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 2>), g2, block, lds, stream, top, io, d_blocks);    \
-        } while (0)
-#define MCR_PHASES_A(T) do { if (top.any_annual_tax) MCR_PHASES(T, true); else MCR_PHASES(T, false); } while (0)
-        switch (top.tax_mask) { case 0: MCR_PHASES_A(0); break; case 1: MCR_PHASES_A(1); break; case 2: MCR_PHASES_A(2); break; default: MCR_PHASES_A(3); break; }
-#undef MCR_PHASES_A
-#undef MCR_PHASES
-        e = hipGetLastError();
-        if (seg_mem) (void)hipFreeAsync(seg_mem, stream);
-    }
-    const hipError_t ef = hipFreeAsync(mem, stream);
-    if (e != hipSuccess) return hip_fail(e, "shared-prefix probe");
-    if (ef != hipSuccess) return hip_fail(ef, "shared-prefix probe (free)");
-    return MCR_OK;
-}
-
 int mcr_probe_months_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
                          uint64_t n_paths, const int32_t* working_months, int32_t n_candidates,
                          uint64_t* counts, int device, void* hip_stream) {
     MCR_ENTER_DEVICE(device);
-    int rc = MCR_OK;
     if (!working_months || !counts || n_candidates < 0) { set_error("null candidates / counts"); return MCR_ERR_INVALID_ARG; }
     if (n_candidates == 0) return MCR_OK;
-    // validate every candidate BEFORE enqueueing anything, so a bad one leaves no half-forked work behind
-    for (int32_t c = 0; c < n_candidates; ++c) {
-        DevParams d;
-        rc = derive_params(p, working_months[c], &d);
-        if (rc != MCR_OK) return rc;
-    }
+    int rc = validate_months(p, working_months, n_candidates);
+    if (rc != MCR_OK) return rc;
     rc = check_rng(rng);
     if (rc != MCR_OK) return rc;
     hipStream_t main = (hipStream_t)hip_stream;
-    hipError_t e = hipMemsetAsync(counts, 0, sizeof(uint64_t) * MCR_N_COUNTERS * (size_t)n_candidates, main);
-    if (e != hipSuccess) return hip_fail(e, "probe counters memset");
-    if (n_candidates == 1) {
-        mcr_outputs o;
-        std::memset(&o, 0, sizeof(o));
-        o.counters = counts;
-        return launch_paths(p, rng, stream_id, path_begin, n_paths, working_months[0], nullptr, &o, main);
-    }
-    if (rng->kind == MCR_RNG_PHILOX && n_candidates <= MCR_MAX_PROBE_CANDIDATES) {
-        const int prc = probe_shared_prefix(p, rng, stream_id, path_begin, n_paths, working_months, n_candidates, counts, main);
-        if (prc != MCR_ERR_UNSUPPORTED) return prc;     // (unsupported shape / allocation refused: one launch per candidate below)
-    }
-    StreamForkLease fork_lease(device);
-    StreamFork* f = fork_lease.f;
-    if (!f) { set_error("could not create probe streams"); return MCR_ERR_HIP; }
-    const int used = n_candidates < kForkStreams ? n_candidates : kForkStreams;
-    if ((e = hipEventRecord(f->fork, main)) != hipSuccess) return hip_fail(e, "probe fork");
-    for (int i = 0; i < used; ++i)
-        if ((e = hipStreamWaitEvent(f->side[i], f->fork, 0)) != hipSuccess) return hip_fail(e, "probe fork wait");
-    int first_rc = MCR_OK;
-    for (int32_t c = 0; c < n_candidates && first_rc == MCR_OK; ++c) {
-        mcr_outputs o;
-        std::memset(&o, 0, sizeof(o));
-        o.counters = counts + (size_t)c * MCR_N_COUNTERS;
-        first_rc = launch_paths(p, rng, stream_id, path_begin, n_paths, working_months[c], nullptr, &o, f->side[c % used]);
-    }
-    // always join, also after a failed launch: `main` must not run ahead of work already forked
-    for (int i = 0; i < used; ++i) {
-        if ((e = hipEventRecord(f->done[i], f->side[i])) != hipSuccess) return hip_fail(e, "probe join record");
-        if ((e = hipStreamWaitEvent(main, f->done[i], 0)) != hipSuccess) return hip_fail(e, "probe join wait");
-    }
-    return first_rc;
-}
-
-// LDS of an expense fan-out launch (path_kernel PHASE 5): STATIC = the math tables and the double-buffered 64-column stage
-// (+ the unused summary / segment words); DYNAMIC = the level counters and [n_lock_slots][64] lock columns per consumer wave.
-// Every lock slot stays in LDS (no overflow block in this form): the levels per launch are lowered until they fit.
-static size_t fanout_static_lds() { return (size_t)kMathTabBytes + (size_t)2 * 6 * 64 * sizeof(double) + 512; }   // (16 640 B compiled)
-static size_t fanout_dynamic_lds(const DevParams& d, int levels) {
-    return (size_t)MCR_MAX_EXPENSE_FANOUT * sizeof(unsigned int) + (size_t)levels * (size_t)d.n_lock_slots_total * 64 * sizeof(double);
-}
-static int fanout_max_levels(const DevParams& d) {
-    int l = MCR_MAX_EXPENSE_FANOUT;
-    while (l > 0 && fanout_static_lds() + fanout_dynamic_lds(d, l) > kLdsPerWorkgroup) --l;
-    return l;
-}
-// Below this many path-wavefronts per level (n_paths / 64) the per-level route runs instead: MCR_EXPENSE_FANOUT_MIN_WAVES
-// overrides it (0 = always fan out where the shape allows; a huge value = never).
-static uint64_t fanout_min_waves() {
-    const char* e = std::getenv("MCR_EXPENSE_FANOUT_MIN_WAVES");
-    return (e && *e) ? (uint64_t)std::strtoull(e, nullptr, 10) : 0u;
-}
-
-// Several spending levels over the same paths, Philox stream: ONE accumulation sweep to working_months (PHASE 1, one
-// snapshot), then expense fan-out launches (PHASE 5) over groups of at most MCR_MAX_EXPENSE_FANOUT levels.  Returns
-// MCR_ERR_UNSUPPORTED, having enqueued nothing, for shapes this form does not cover.
-static int probe_expenses_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
-                                 int32_t wm, const double* levels, int32_t n_levels, uint64_t* counts, hipStream_t stream) {
-    if (rng->kind != MCR_RNG_PHILOX || n_levels < 2 || n_paths == 0 || n_paths > ((uint64_t)1 << 31)) return MCR_ERR_UNSUPPORTED;
-    if ((n_paths + 63) / 64 < fanout_min_waves()) return MCR_ERR_UNSUPPORTED;
-    DevParams d;
-    int rc = derive_params(p, wm, &d);
+    rc = zero_counters(counts, (size_t)n_candidates, main);
     if (rc != MCR_OK) return rc;
-    if (d.n_extra_streams > 0 || (d.exact_month && !kExactMonthDefault)) return MCR_ERR_UNSUPPORTED;
-    // the producer / consumer barrier counts (see launch_paths): producers run rows [wm & ~1, total_months)
-    if (d.total_months != d.working_months + kMPY * d.retirement_years) { set_error("internal: total_months != working_months + 12 retirement_years"); return MCR_ERR_INVALID_ARG; }
-    const int lmax = fanout_max_levels(d);
-    if (lmax < 2) return MCR_ERR_UNSUPPORTED;
-    DevParams d1 = d;    // (PHASE 1 never reads a lock column: its plan may lower the LDS slots)
-    size_t lds1 = 0;
-    if (plan_path_kernel_lds(d1, 0, false, false, true, 0, &lds1) != MCR_OK) { (void)hipGetLastError(); return MCR_ERR_UNSUPPORTED; }
-    d.n_lock_slots = d.n_lock_slots_total;
-    KernelIO io;
-    std::memset(&io, 0, sizeof(io));
-    fill_io_rng(io, rng, nullptr);
-    io.stream_id = stream_id; io.path_begin = path_begin; io.n_paths = n_paths;
-    io.n_snap = 1;
-    io.snap_stride = (int64_t)((n_paths + 63) / 64 * 64);
-    io.snap_months[0] = wm;
-    const size_t snap_bytes = (size_t)kSnapFields * (size_t)io.snap_stride * sizeof(double);
-    void* mem = nullptr;
-    if (hipMallocAsync(&mem, snap_bytes, stream) != hipSuccess) { (void)hipGetLastError(); return MCR_ERR_UNSUPPORTED; }
-    io.snap = (double*)mem;
-    const dim3 block(kBlock), block2(2 * kBlock), g1((unsigned)((n_paths + kBlock - 1) / kBlock)), g5((unsigned)((n_paths + 63) / 64));
-    const bool split1 = (uint64_t)g1.x * (kBlock / 64) <= split_max_waves();
-    const int n_groups = (n_levels + lmax - 1) / lmax;   // groups of near-equal size
-#define MCR_FAN(T, A)                                                                                                   \
-    do {                                                                                                               \
-        if (split1) hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 1, true>), g1, block2, lds1, stream, d1, io, (const DevParams*)nullptr); \
-        else hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 1>), g1, block, lds1, stream, d1, io, (const DevParams*)nullptr);            \
-        for (int g = 0, first = 0; g < n_groups; ++g) {                                                                 \
-            const int lg = n_levels / n_groups + (g < n_levels % n_groups ? 1 : 0);                                    \
-            KernelIO fio = io;                                                                                         \
-            fio.out.counters = counts + (size_t)first * MCR_N_COUNTERS;                                                \
-            fio.fan_n = lg;                                                                                            \
-            for (int k = 0; k < lg; ++k) fio.fan_expenses[k] = levels[first + k];                                     \
-            hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 5, true>), g5, dim3(64 * (lg + 1)), fanout_dynamic_lds(d, lg), \
-                               stream, d, fio, (const DevParams*)nullptr);                                             \
-            first += lg;                                                                                               \
-        }                                                                                                              \
-    } while (0)
-#define MCR_FAN_A(T) do { if (d.any_annual_tax) MCR_FAN(T, true); else MCR_FAN(T, false); } while (0)
-    switch (d.tax_mask) { case 0: MCR_FAN_A(0); break; case 1: MCR_FAN_A(1); break; case 2: MCR_FAN_A(2); break; default: MCR_FAN_A(3); break; }
-#undef MCR_FAN_A
-#undef MCR_FAN
-    const hipError_t e = hipGetLastError();
-    const hipError_t ef = hipFreeAsync(mem, stream);
-    if (e != hipSuccess) return hip_fail(e, "expense fan-out probe");
-    if (ef != hipSuccess) return hip_fail(ef, "expense fan-out probe (free)");
-    return MCR_OK;
+    auto launch_candidate = [&](int c, hipStream_t s) {
+        const mcr_outputs o = counters_only(counts + (size_t)c * MCR_N_COUNTERS);
+        return launch_paths(p, rng, stream_id, path_begin, n_paths, working_months[c], nullptr, &o, s);
+    };
+    if (n_candidates == 1) return launch_candidate(0, main);
+    if (rng->kind == MCR_RNG_PHILOX && n_candidates <= MCR_MAX_PROBE_CANDIDATES) {
+        rc = probe_shared_prefix(p, rng, stream_id, path_begin, n_paths, working_months, n_candidates, counts, main);
+        if (rc != MCR_ERR_UNSUPPORTED) return rc;     // (unsupported shape / allocation refused: one launch per candidate below)
+    }
+    return fork_join(device, main, n_candidates, launch_candidate);
 }
 
 int mcr_probe_expenses_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
                            uint64_t n_paths, int32_t working_months, const double* monthly_expenses, int32_t n_levels,
                            uint64_t* counts, int device, void* hip_stream) {
     MCR_ENTER_DEVICE(device);
-    if (n_levels < 0) { set_error("n_levels %d must be >= 0", n_levels); return MCR_ERR_INVALID_ARG; }
-    if (n_levels == 0) return MCR_OK;
-    if (!monthly_expenses || !counts) { set_error("null levels / counts"); return MCR_ERR_INVALID_ARG; }
-    // validate every level BEFORE enqueueing anything (counts stay untouched on an error)
-    DevParams d;
-    int rc = derive_params(p, working_months, &d);
-    if (rc != MCR_OK) return rc;
-    rc = check_rng(rng);
-    if (rc != MCR_OK) return rc;
-    for (int32_t k = 0; k < n_levels; ++k)
-        if (!(std::isfinite(monthly_expenses[k]) && monthly_expenses[k] >= 0.0)) {
-            set_error("monthly_expenses[%d] = %g: must be finite and >= 0 (config.py:59)", k, monthly_expenses[k]);
-            return MCR_ERR_INVALID_ARG;
-        }
-    hipStream_t main = (hipStream_t)hip_stream;
-    hipError_t e = hipMemsetAsync(counts, 0, sizeof(uint64_t) * MCR_N_COUNTERS * (size_t)n_levels, main);
-    if (e != hipSuccess) return hip_fail(e, "probe counters memset");
-    mcr_params q = *p;
-    mcr_outputs o;
-    std::memset(&o, 0, sizeof(o));
-    if (n_levels == 1) {
-        q.monthly_expenses = monthly_expenses[0];
-        o.counters = counts;
-        return launch_paths(&q, rng, stream_id, path_begin, n_paths, working_months, nullptr, &o, main);
-    }
-    const int frc = probe_expenses_fanout(p, rng, stream_id, path_begin, n_paths, working_months, monthly_expenses, n_levels, counts, main);
-    if (frc != MCR_ERR_UNSUPPORTED) return frc;     // (unsupported shape / allocation refused: one launch per level below)
-    StreamForkLease fork_lease(device);
-    StreamFork* f = fork_lease.f;
-    if (!f) { set_error("could not create probe streams"); return MCR_ERR_HIP; }
-    const int used = n_levels < kForkStreams ? n_levels : kForkStreams;
-    if ((e = hipEventRecord(f->fork, main)) != hipSuccess) return hip_fail(e, "probe fork");
-    for (int i = 0; i < used; ++i)
-        if ((e = hipStreamWaitEvent(f->side[i], f->fork, 0)) != hipSuccess) return hip_fail(e, "probe fork wait");
-    int first_rc = MCR_OK;
-    for (int32_t k = 0; k < n_levels && first_rc == MCR_OK; ++k) {
-        q.monthly_expenses = monthly_expenses[k];
-        o.counters = counts + (size_t)k * MCR_N_COUNTERS;
-        first_rc = launch_paths(&q, rng, stream_id, path_begin, n_paths, working_months, nullptr, &o, f->side[k % used]);
-    }
-    // always join, also after a failed launch: `main` must not run ahead of work already forked
-    for (int i = 0; i < used; ++i) {
-        if ((e = hipEventRecord(f->done[i], f->side[i])) != hipSuccess) return hip_fail(e, "probe join record");
-        if ((e = hipStreamWaitEvent(main, f->done[i], 0)) != hipSuccess) return hip_fail(e, "probe join wait");
-    }
-    return first_rc;
-}
-
-// Below this many path-wavefronts per level (n_paths / 64) the contribution probe takes the per-level route:
-// MCR_CONTRIBUTION_FANOUT_MIN_WAVES overrides it (0 = always fan out where the shape allows; a huge value = never).
-static uint64_t contribution_fanout_min_waves() {
-    const char* e = std::getenv("MCR_CONTRIBUTION_FANOUT_MIN_WAVES");
-    return (e && *e) ? (uint64_t)std::strtoull(e, nullptr, 10) : 0u;
-}
-
-// Several contribution levels over the same paths, Philox stream: contribution fan-out launches (PHASE 7) over groups of at
-// most fanout_max_levels levels.  The levels differ from month 0, so there is no accumulation sweep and no snapshot: each
-// launch runs the whole path.  Returns MCR_ERR_UNSUPPORTED, having enqueued nothing, for shapes this form does not cover.
-static int probe_contributions_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
-                                      uint64_t n_paths, int32_t wm, const double* levels, int32_t n_levels, uint64_t* counts,
-                                      hipStream_t stream) {
-    if (rng->kind != MCR_RNG_PHILOX || n_levels < 2 || n_paths == 0 || n_paths > ((uint64_t)1 << 31)) return MCR_ERR_UNSUPPORTED;
-    if ((n_paths + 63) / 64 < contribution_fanout_min_waves()) return MCR_ERR_UNSUPPORTED;
-    DevParams d;
-    int rc = derive_params(p, wm, &d);
-    if (rc != MCR_OK) return rc;
-    if (d.n_extra_streams > 0 || (d.exact_month && !kExactMonthDefault)) return MCR_ERR_UNSUPPORTED;
-    // the producer / consumer barrier counts (see launch_paths): producers run rows [0, total_months)
-    if (d.total_months != d.working_months + kMPY * d.retirement_years) { set_error("internal: total_months != working_months + 12 retirement_years"); return MCR_ERR_INVALID_ARG; }
-    const int lmax = fanout_max_levels(d);
-    if (lmax < 2) return MCR_ERR_UNSUPPORTED;
-    d.n_lock_slots = d.n_lock_slots_total;
-    KernelIO io;
-    std::memset(&io, 0, sizeof(io));
-    fill_io_rng(io, rng, nullptr);
-    io.stream_id = stream_id; io.path_begin = path_begin; io.n_paths = n_paths;
-    const dim3 g7((unsigned)((n_paths + 63) / 64));
-    const int n_groups = (n_levels + lmax - 1) / lmax;   // groups of near-equal size
-#define MCR_CFAN(T, A)                                                                                                  \
-    do {                                                                                                               \
-        for (int g = 0, first = 0; g < n_groups; ++g) {                                                                 \
-            const int lg = n_levels / n_groups + (g < n_levels % n_groups ? 1 : 0);                                    \
-            KernelIO fio = io;                                                                                         \
-            fio.out.counters = counts + (size_t)first * MCR_N_COUNTERS;                                                \
-            fio.fan_n = lg;                                                                                            \
-            for (int k = 0; k < lg; ++k) fio.fan_expenses[k] = levels[first + k];                                     \
-            hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 7, true>), g7, dim3(64 * (lg + 1)), fanout_dynamic_lds(d, lg), \
-                               stream, d, fio, (const DevParams*)nullptr);                                             \
-            first += lg;                                                                                               \
-        }                                                                                                              \
-    } while (0)
-#define MCR_CFAN_A(T) do { if (d.any_annual_tax) MCR_CFAN(T, true); else MCR_CFAN(T, false); } while (0)
-    switch (d.tax_mask) { case 0: MCR_CFAN_A(0); break; case 1: MCR_CFAN_A(1); break; case 2: MCR_CFAN_A(2); break; default: MCR_CFAN_A(3); break; }
-#undef MCR_CFAN_A
-#undef MCR_CFAN
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "contribution fan-out probe");
-    return MCR_OK;
+    return probe_levels<probe_expenses_fanout>(p, rng, stream_id, path_begin, n_paths, working_months, &mcr_params::monthly_expenses,
+                                               "monthly_expenses", 59, monthly_expenses, n_levels, counts, device, (hipStream_t)hip_stream);
 }
 
 int mcr_probe_contributions_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
                                 uint64_t n_paths, int32_t working_months, const double* monthly_contributions, int32_t n_levels,
                                 uint64_t* counts, int device, void* hip_stream) {
     MCR_ENTER_DEVICE(device);
-    if (n_levels < 0) { set_error("n_levels %d must be >= 0", n_levels); return MCR_ERR_INVALID_ARG; }
-    if (n_levels == 0) return MCR_OK;
-    if (!monthly_contributions || !counts) { set_error("null levels / counts"); return MCR_ERR_INVALID_ARG; }
-    // validate every level BEFORE enqueueing anything (counts stay untouched on an error)
-    DevParams d;
-    int rc = derive_params(p, working_months, &d);
-    if (rc != MCR_OK) return rc;
-    rc = check_rng(rng);
-    if (rc != MCR_OK) return rc;
-    for (int32_t k = 0; k < n_levels; ++k)
-        if (!(std::isfinite(monthly_contributions[k]) && monthly_contributions[k] >= 0.0)) {
-            set_error("monthly_contribution[%d] = %g: must be finite and >= 0 (config.py:57)", k, monthly_contributions[k]);
-            return MCR_ERR_INVALID_ARG;
-        }
-    hipStream_t main = (hipStream_t)hip_stream;
-    hipError_t e = hipMemsetAsync(counts, 0, sizeof(uint64_t) * MCR_N_COUNTERS * (size_t)n_levels, main);
-    if (e != hipSuccess) return hip_fail(e, "probe counters memset");
-    mcr_params q = *p;
-    mcr_outputs o;
-    std::memset(&o, 0, sizeof(o));
-    if (n_levels == 1) {
-        q.monthly_contribution = monthly_contributions[0];
-        o.counters = counts;
-        return launch_paths(&q, rng, stream_id, path_begin, n_paths, working_months, nullptr, &o, main);
-    }
-    const int frc = probe_contributions_fanout(p, rng, stream_id, path_begin, n_paths, working_months, monthly_contributions, n_levels,
-                                               counts, main);
-    if (frc != MCR_ERR_UNSUPPORTED) return frc;     // (unsupported shape: one launch per level below)
-    StreamForkLease fork_lease(device);
-    StreamFork* f = fork_lease.f;
-    if (!f) { set_error("could not create probe streams"); return MCR_ERR_HIP; }
-    const int used = n_levels < kForkStreams ? n_levels : kForkStreams;
-    if ((e = hipEventRecord(f->fork, main)) != hipSuccess) return hip_fail(e, "probe fork");
-    for (int i = 0; i < used; ++i)
-        if ((e = hipStreamWaitEvent(f->side[i], f->fork, 0)) != hipSuccess) return hip_fail(e, "probe fork wait");
-    int first_rc = MCR_OK;
-    for (int32_t k = 0; k < n_levels && first_rc == MCR_OK; ++k) {
-        q.monthly_contribution = monthly_contributions[k];
-        o.counters = counts + (size_t)k * MCR_N_COUNTERS;
-        first_rc = launch_paths(&q, rng, stream_id, path_begin, n_paths, working_months, nullptr, &o, f->side[k % used]);
-    }
-    // always join, also after a failed launch: `main` must not run ahead of work already forked
-    for (int i = 0; i < used; ++i) {
-        if ((e = hipEventRecord(f->done[i], f->side[i])) != hipSuccess) return hip_fail(e, "probe join record");
-        if ((e = hipStreamWaitEvent(main, f->done[i], 0)) != hipSuccess) return hip_fail(e, "probe join wait");
-    }
-    return first_rc;
-}
-
-// A grid of working months x spending levels over the same paths, Philox stream: ONE accumulation sweep (PHASE 1) stores
-// the state at the end of every distinct month, then grid fan-out launches (PHASE 6, grid.y = row) resume every row's
-// decumulation with up to fanout_max_levels of its levels per launch.  Rows of a repeated month share its snapshot column.
-// Returns MCR_ERR_UNSUPPORTED, having enqueued nothing, for shapes this form does not cover.
-static int probe_grid_shared(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
-                             const int32_t* working_months, int32_t n_rows, const double* levels, int32_t n_levels, uint64_t* counts,
-                             hipStream_t stream) {
-    if (rng->kind != MCR_RNG_PHILOX || n_rows < 2 || n_paths == 0 || n_paths > ((uint64_t)1 << 31)) return MCR_ERR_UNSUPPORTED;
-    if ((n_paths + 63) / 64 < fanout_min_waves()) return MCR_ERR_UNSUPPORTED;
-    std::vector<int> order((size_t)n_rows), col((size_t)n_rows);
-    sort_candidates(working_months, n_rows, order.data());
-    std::vector<int32_t> months;    // distinct months, ascending = the snapshot columns
-    for (int i = 0; i < n_rows; ++i) {
-        const int32_t m = working_months[order[(size_t)i]];
-        if (months.empty() || months.back() != m) months.push_back(m);
-        col[(size_t)order[(size_t)i]] = (int)months.size() - 1;
-    }
-    const int n_cand = (int)months.size();
-    if (n_cand < 2 || n_cand > MCR_MAX_PROBE_CANDIDATES) return MCR_ERR_UNSUPPORTED;
-    std::vector<DevParams> blocks((size_t)n_cand);
-    for (int c = 0; c < n_cand; ++c) {
-        const int rc = derive_params(p, months[(size_t)c], &blocks[(size_t)c]);
-        if (rc != MCR_OK) return rc;
-        DevParams& b = blocks[(size_t)c];
-        // the producer / consumer barrier counts (see launch_paths): producers run rows [wm & ~1, total_months)
-        if (b.total_months != b.working_months + kMPY * b.retirement_years) { set_error("internal: total_months != working_months + 12 retirement_years"); return MCR_ERR_INVALID_ARG; }
-        b.n_lock_slots = b.n_lock_slots_total;   // (the same for every month: it depends on the stream list only)
-    }
-    const DevParams& top = blocks[(size_t)n_cand - 1];
-    if (top.n_extra_streams > 0 || (top.exact_month && !kExactMonthDefault)) return MCR_ERR_UNSUPPORTED;
-    const int lmax = fanout_max_levels(top);
-    if (lmax < 1) return MCR_ERR_UNSUPPORTED;
-    DevParams d1 = top;    // (PHASE 1 never reads a lock column: its plan may lower the LDS slots)
-    size_t lds1 = 0;
-    if (plan_path_kernel_lds(d1, 0, false, false, true, 0, &lds1) != MCR_OK) { (void)hipGetLastError(); return MCR_ERR_UNSUPPORTED; }
-    KernelIO io;
-    std::memset(&io, 0, sizeof(io));
-    fill_io_rng(io, rng, nullptr);
-    io.stream_id = stream_id; io.path_begin = path_begin; io.n_paths = n_paths;
-    io.n_snap = n_cand;
-    io.snap_stride = (int64_t)((n_paths + 63) / 64 * 64);
-    for (int c = 0; c < n_cand; ++c) io.snap_months[c] = months[(size_t)c];
-    const size_t snap_bytes = (size_t)n_cand * kSnapFields * (size_t)io.snap_stride * sizeof(double);
-    if (snap_bytes > ((size_t)4 << 30)) return MCR_ERR_UNSUPPORTED;   // huge probes are throughput-bound anyway: per-month route
-    // the rows' records, level group by level group: group g covers levels [first_g, first_g + lg) of every row
-    const int n_groups = (n_levels + lmax - 1) / lmax;   // groups of near-equal size
-    std::vector<GridCell> cells((size_t)n_groups * (size_t)n_rows);
-    std::memset(cells.data(), 0, cells.size() * sizeof(GridCell));
-    for (int g = 0, first = 0; g < n_groups; ++g) {
-        const int lg = n_levels / n_groups + (g < n_levels % n_groups ? 1 : 0);
-        for (int r = 0; r < n_rows; ++r) {
-            GridCell& x = cells[(size_t)g * n_rows + r];
-            x.p = blocks[(size_t)col[(size_t)r]];
-            x.snap = col[(size_t)r];
-            x.counters = counts + ((size_t)r * n_levels + first) * MCR_N_COUNTERS;
-            for (int k = 0; k < lg; ++k) x.levels[k] = levels[(size_t)r * n_levels + first + k];
-        }
-        first += lg;
-    }
-    void* mem = nullptr;
-    hipError_t e = hipSuccess;
-    if (!alloc_snapshots_and_blocks(snap_bytes, cells.data(), cells.size() * sizeof(GridCell), stream, &mem, &e)) return MCR_ERR_UNSUPPORTED;
-    io.snap = (double*)mem;
-    const GridCell* d_cells = (const GridCell*)((char*)mem + snap_bytes);
-    if (e == hipSuccess) {
-        const dim3 block(kBlock), block2(2 * kBlock), g1((unsigned)((n_paths + kBlock - 1) / kBlock)), g6((unsigned)((n_paths + 63) / 64), (unsigned)n_rows);
-        const bool split1 = (uint64_t)g1.x * (kBlock / 64) <= split_max_waves();
-#define MCR_GRID(T, A)                                                                                                  \
-        do {                                                                                                           \
-            if (split1) hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 1, true>), g1, block2, lds1, stream, d1, io, (const DevParams*)nullptr); \
-            else hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 1>), g1, block, lds1, stream, d1, io, (const DevParams*)nullptr);            \
-            for (int g = 0; g < n_groups; ++g) {                                                                       \
-                const int lg = n_levels / n_groups + (g < n_levels % n_groups ? 1 : 0);                                \
-                KernelIO gio = io;                                                                                     \
-                gio.fan_n = lg;                                                                                        \
-                hipLaunchKernelGGL((path_kernel<0, 0, T, A, false, 6, true>), g6, dim3(64 * (lg + 1)), fanout_dynamic_lds(top, lg), \
-                                   stream, top, gio, (const DevParams*)(d_cells + (size_t)g * n_rows));               \
-            }                                                                                                          \
-        } while (0)
-#define MCR_GRID_A(T) do { if (top.any_annual_tax) MCR_GRID(T, true); else MCR_GRID(T, false); } while (0)
-        switch (top.tax_mask) { case 0: MCR_GRID_A(0); break; case 1: MCR_GRID_A(1); break; case 2: MCR_GRID_A(2); break; default: MCR_GRID_A(3); break; }
-#undef MCR_GRID_A
-#undef MCR_GRID
-        e = hipGetLastError();
-    }
-    const hipError_t ef = hipFreeAsync(mem, stream);
-    if (e != hipSuccess) return hip_fail(e, "grid probe");
-    if (ef != hipSuccess) return hip_fail(ef, "grid probe (free)");
-    return MCR_OK;
+    return probe_levels<probe_contributions_fanout>(p, rng, stream_id, path_begin, n_paths, working_months, &mcr_params::monthly_contribution,
+                                                    "monthly_contribution", 57, monthly_contributions, n_levels, counts, device, (hipStream_t)hip_stream);
 }
 
 int mcr_probe_grid_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
@@ -2178,13 +2144,9 @@ int mcr_probe_grid_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_
     if (n_candidates < 0 || n_levels < 0) { set_error("n_candidates %d / n_levels %d must be >= 0", n_candidates, n_levels); return MCR_ERR_INVALID_ARG; }
     if (n_candidates == 0 || n_levels == 0) return MCR_OK;
     if (!working_months || !monthly_expenses || !counts) { set_error("null months / levels / counts"); return MCR_ERR_INVALID_ARG; }
-    // validate every month and every level BEFORE enqueueing anything (counts stay untouched on an error)
-    for (int32_t c = 0; c < n_candidates; ++c) {
-        DevParams d;
-        const int rc = derive_params(p, working_months[c], &d);
-        if (rc != MCR_OK) return rc;
-    }
-    int rc = check_rng(rng);
+    int rc = validate_months(p, working_months, n_candidates);
+    if (rc != MCR_OK) return rc;
+    rc = check_rng(rng);
     if (rc != MCR_OK) return rc;
     const size_t n_cells = (size_t)n_candidates * (size_t)n_levels;
     for (size_t k = 0; k < n_cells; ++k)
@@ -2200,8 +2162,8 @@ int mcr_probe_grid_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_
         return mcr_probe_expenses_rng(p, rng, stream_id, path_begin, n_paths, working_months[0], monthly_expenses, (int32_t)n_cells,
                                       counts, device, hip_stream);
     hipStream_t main = (hipStream_t)hip_stream;
-    hipError_t e = hipMemsetAsync(counts, 0, sizeof(uint64_t) * MCR_N_COUNTERS * n_cells, main);
-    if (e != hipSuccess) return hip_fail(e, "probe counters memset");
+    rc = zero_counters(counts, n_cells, main);
+    if (rc != MCR_OK) return rc;
     rc = probe_grid_shared(p, rng, stream_id, path_begin, n_paths, working_months, n_candidates, monthly_expenses, n_levels, counts, main);
     if (rc != MCR_ERR_UNSUPPORTED) return rc;     // (unsupported shape / allocation refused: the per-month route below)
     rc = MCR_OK;

@@ -328,6 +328,27 @@ def probe_months(params: McrParams, seed, stream_id: int, path_begin: int, n_pat
     return counts
 
 
+def _probe_levels(symbol: str, params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
+                  levels, device: int):
+    """The body of `probe_expenses` / `probe_contributions`: `symbol` is the library entry that takes the levels."""
+    import torch
+
+    N.require_device()
+    levels = [float(x) for x in levels]
+    arr = (C.c_double * max(1, len(levels)))(*levels)
+    counts = torch.empty((len(levels), N.MCR_N_COUNTERS), dtype=torch.int64, device=torch.device("cuda", int(device)))
+    if not levels:
+        return counts
+    rng = _as_rng(seed)
+    stream = torch.cuda.current_stream(int(device)).cuda_stream
+    rc = getattr(N.load_library(), symbol)(
+        C.byref(params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), int(working_months), arr,
+        len(levels), counts.data_ptr(), int(device), C.c_void_p(stream),
+    )
+    N.check(rc, symbol)
+    return counts
+
+
 def probe_expenses(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
                    monthly_expenses, device: int = 0):
     """Success counters of several ``monthly_expenses`` levels at one working-month count over the same path range
@@ -335,22 +356,8 @@ def probe_expenses(params: McrParams, seed, stream_id: int, path_begin: int, n_p
     monthly_expenses[k]`` counts.  The accumulation runs once and up to ``MCR_MAX_EXPENSE_FANOUT`` levels share each
     path's random numbers.  Returns a device int64 tensor ``[len(monthly_expenses), 2]`` = ``{successes, paths}``;
     asynchronous (reading it synchronises)."""
-    import torch
-
-    N.require_device()
-    levels = [float(x) for x in monthly_expenses]
-    arr = (C.c_double * max(1, len(levels)))(*levels)
-    counts = torch.empty((len(levels), N.MCR_N_COUNTERS), dtype=torch.int64, device=torch.device("cuda", int(device)))
-    if not levels:
-        return counts
-    rng = _as_rng(seed)
-    stream = torch.cuda.current_stream(int(device)).cuda_stream
-    rc = N.load_library().mcr_probe_expenses_rng(
-        C.byref(params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), int(working_months), arr,
-        len(levels), counts.data_ptr(), int(device), C.c_void_p(stream),
-    )
-    N.check(rc, "mcr_probe_expenses_rng")
-    return counts
+    return _probe_levels("mcr_probe_expenses_rng", params, seed, stream_id, path_begin, n_paths, working_months,
+                         monthly_expenses, device)
 
 
 def probe_contributions(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
@@ -360,22 +367,9 @@ def probe_contributions(params: McrParams, seed, stream_id: int, path_begin: int
     monthly_contributions[k]`` counts.  Up to ``MCR_MAX_EXPENSE_FANOUT`` levels share each path's random numbers (the
     levels differ from month 0, so each runs the whole path).  Returns a device int64 tensor
     ``[len(monthly_contributions), 2]`` = ``{successes, paths}``; asynchronous (reading it synchronises)."""
-    import torch
+    return _probe_levels("mcr_probe_contributions_rng", params, seed, stream_id, path_begin, n_paths, working_months,
+                         monthly_contributions, device)
 
-    N.require_device()
-    levels = [float(x) for x in monthly_contributions]
-    arr = (C.c_double * max(1, len(levels)))(*levels)
-    counts = torch.empty((len(levels), N.MCR_N_COUNTERS), dtype=torch.int64, device=torch.device("cuda", int(device)))
-    if not levels:
-        return counts
-    rng = _as_rng(seed)
-    stream = torch.cuda.current_stream(int(device)).cuda_stream
-    rc = N.load_library().mcr_probe_contributions_rng(
-        C.byref(params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), int(working_months), arr,
-        len(levels), counts.data_ptr(), int(device), C.c_void_p(stream),
-    )
-    N.check(rc, "mcr_probe_contributions_rng")
-    return counts
 
 def probe_grid(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months, levels_2d,
                device: int = 0):

@@ -599,6 +599,11 @@ class RetirementMonteCarloSimulator:
         return float((summary_df["Final Balance"] > SMALL_EPSILON).mean() * 100.0)
 
     # ---- count-only probes used by the search ------------------------------------------------------
+    @staticmethod
+    def _count_percent(count, n: int) -> float:
+        """Success % from a probe's counter: the per-path route's ``mean() * 100`` bit for bit, count/n*100 in fp64."""
+        return float(np.float64(int(count)) / np.float64(n) * 100.0)
+
     def _probe_many(self, months: Sequence[int], num_simulations: int) -> Dict[int, float]:
         """Success % of several candidate working-month counts over the same paths, from count-only
         kernels run concurrently (``mcr_probe_months_rng``).  Each value equals
@@ -616,7 +621,7 @@ class RetirementMonteCarloSimulator:
             return E.probe_months(params, rng, self._stream_id, path_begin, count, ms, device=dev)
 
         counts = D.probe_candidates(months, n, self.shard_min_paths, probe)
-        return {m: float(np.float64(int(counts[i, N.MCR_CTR_SUCCESS])) / np.float64(n) * 100.0) for i, m in enumerate(months)}
+        return {m: self._count_percent(counts[i, N.MCR_CTR_SUCCESS], n) for i, m in enumerate(months)}
 
     def _probe_success_probability(self, working_months: int, num_simulations: int) -> float:
         """Success % of one batch from the count-only kernel (no per-path HBM traffic)."""
@@ -787,6 +792,23 @@ class RetirementMonteCarloSimulator:
 
 
     # ---- maximum-spending search -----------------------------------------------------------------
+    def _level_probabilities(self, engine_probe, working_months: int, levels: Sequence[float],
+                             num_simulations: Optional[int]) -> np.ndarray:
+        """The body of `success_probability_by_expenses` / `..._by_contributions`: `engine_probe` is `E.probe_expenses` or
+        `E.probe_contributions`."""
+        levels = [float(x) for x in levels]
+        n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
+        wm = int(working_months)
+        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
+
+        def probe(path_begin, count, idx):
+            return engine_probe(params, rng, self._stream_id, path_begin, count, wm, [levels[i] for i in idx], device=dev)
+
+        if not levels:
+            return np.zeros(0, dtype=np.float64)
+        counts = D.probe_candidates(list(range(len(levels))), n, self.shard_min_paths, probe)
+        return np.array([self._count_percent(counts[i, N.MCR_CTR_SUCCESS], n) for i in range(len(levels))], dtype=np.float64)
+
     def success_probability_by_expenses(self, working_months: int, monthly_expenses: Sequence[float],
                                         num_simulations: Optional[int] = None) -> np.ndarray:
         """Success % of each ``monthly_expenses`` level at ``working_months``, over the active seed stream's batch of
@@ -795,19 +817,7 @@ class RetirementMonteCarloSimulator:
         ``_success_probability(run_monte_carlo_simulations(working_months, n)[0])`` of a simulator whose config differs
         only in ``monthly_expenses``.  Under a process group the levels go through ``distributed.probe_candidates`` (as
         candidate indices), so every rank returns the same array."""
-        levels = [float(x) for x in monthly_expenses]
-        n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
-        wm = int(working_months)
-        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
-
-        def probe(path_begin, count, idx):
-            return E.probe_expenses(params, rng, self._stream_id, path_begin, count, wm, [levels[i] for i in idx], device=dev)
-
-        if not levels:
-            return np.zeros(0, dtype=np.float64)
-        counts = D.probe_candidates(list(range(len(levels))), n, self.shard_min_paths, probe)
-        return np.array([float(np.float64(int(counts[i, N.MCR_CTR_SUCCESS])) / np.float64(n) * 100.0)
-                         for i in range(len(levels))], dtype=np.float64)
+        return self._level_probabilities(E.probe_expenses, working_months, monthly_expenses, num_simulations)
 
     def find_maximum_monthly_expenses(
         self,
@@ -852,20 +862,7 @@ class RetirementMonteCarloSimulator:
         ``_success_probability(run_monte_carlo_simulations(working_months, n)[0])`` of a simulator whose config differs
         only in ``monthly_contribution``.  Under a process group the levels go through ``distributed.probe_candidates`` (as
         candidate indices), so every rank returns the same array."""
-        levels = [float(x) for x in monthly_contributions]
-        n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
-        wm = int(working_months)
-        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
-
-        def probe(path_begin, count, idx):
-            return E.probe_contributions(params, rng, self._stream_id, path_begin, count, wm, [levels[i] for i in idx],
-                                         device=dev)
-
-        if not levels:
-            return np.zeros(0, dtype=np.float64)
-        counts = D.probe_candidates(list(range(len(levels))), n, self.shard_min_paths, probe)
-        return np.array([float(np.float64(int(counts[i, N.MCR_CTR_SUCCESS])) / np.float64(n) * 100.0)
-                         for i in range(len(levels))], dtype=np.float64)
+        return self._level_probabilities(E.probe_contributions, working_months, monthly_contributions, num_simulations)
 
     def find_minimum_monthly_contribution(
         self,
@@ -933,7 +930,7 @@ class RetirementMonteCarloSimulator:
 
         counts = D.probe_candidates(list(range(len(months))), n, self.shard_min_paths, probe,
                                     width=n_levels * N.MCR_N_COUNTERS).reshape(len(months), n_levels, N.MCR_N_COUNTERS)
-        return np.array([[float(np.float64(int(counts[c, k, N.MCR_CTR_SUCCESS])) / np.float64(n) * 100.0)
+        return np.array([[self._count_percent(counts[c, k, N.MCR_CTR_SUCCESS], n)
                           for k in range(n_levels)] for c in range(len(months))], dtype=np.float64).reshape(len(months), n_levels)
 
     def success_probability_grid(self, working_months: Sequence[int], monthly_expenses: Sequence[float],

@@ -65,14 +65,15 @@ def main():
         old = json.load(open(args.compare))
         same = [k for k in fp if k in old and fp[k] == old[k]]
         changed = [k for k in fp if k in old and fp[k] != old[k]]
-        print(f"{len(same)} kernels identical, {len(changed)} changed, {len(set(fp) - set(old))} new, {len(set(old) - set(fp))} gone")
+        new, gone = sorted(set(fp) - set(old)), sorted(set(old) - set(fp))
+        print(f"{len(same)} kernels identical, {len(changed)} changed, {len(new)} new, {len(gone)} gone")
         for k in changed:
             print("  changed:", k[:150], old[k], "->", fp[k])
-        for k in sorted(set(fp) - set(old)):
+        for k in new:
             print("  new:", k[:150])
-        for k in sorted(set(old) - set(fp)):
+        for k in gone:
             print("  gone:", k[:150])
-        sys.exit(1 if changed else 0)
+        sys.exit(1 if changed or new or gone else 0)
 
 
 if __name__ == "__main__":
