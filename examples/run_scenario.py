@@ -14,7 +14,8 @@ switch to the final seed stream, run the final batch, print the response documen
 
 `--rng numpy` uses the reference's own NumPy stream (same seed -> the reference's numbers); `--rng philox`
 (default) the engine's counter-based stream.  `--compact` assembles the document from device-side aggregates
-only (no per-path lists: for batches far beyond the UI's).  `--events` writes the progress events the SSE
+only (no per-path lists: for batches far beyond the UI's); `--streamed` from yearly bins taken inside the path kernel (no
+memory per path at all: any number of paths, under `torchrun` too; bands are known to within one bin).  `--events` writes the progress events the SSE
 endpoint would stream to stderr, one JSON per line.  Without `--full` only the `summary` block (plus timings
 and sizes) is printed.  `--max-expenses` answers the other planning question instead: the largest monthly spending
 (whole cents) that still reaches the target when retiring after `--working-months` (or the searched minimum), printed
@@ -48,6 +49,8 @@ def main() -> int:
     ap.add_argument("--search-paths", type=int, default=None, help="override num_simulations_search")
     ap.add_argument("--working-months", type=int, default=None, help="skip the search")
     ap.add_argument("--compact", action="store_true", help="device-aggregated document (large batches)")
+    ap.add_argument("--streamed", action="store_true",
+                    help="document from in-kernel yearly bins: no memory per path, any number of paths (bands bracketed)")
     ap.add_argument("--events", action="store_true", help="progress events to stderr")
     ap.add_argument("--full", action="store_true", help="print the whole response document")
     ap.add_argument("--max-expenses", action="store_true", help="search the maximum monthly expenses instead")
@@ -101,7 +104,9 @@ def main() -> int:
         if not args.frontier and not (args.grid_months and args.grid_expenses):
             ap.error("--grid-months and --grid-expenses go together")
         return frontier_or_grid(args, config, world, rank0)
-    builder = R.compact_result if args.compact else R.build_result
+    if args.compact and args.streamed:
+        ap.error("--compact and --streamed are two ways to build the document")
+    builder = R.streamed_result if args.streamed else R.compact_result if args.compact else R.build_result
     doc = R.run_scenario(config, args.working_months, emit=emit, result_builder=builder,
                          main_seed_override=args.seed, rng=args.rng)
     t_end = time.perf_counter()

@@ -30,6 +30,9 @@ extern "C" {
 #define MCR_MAX_PROBE_CANDIDATES 32 /* candidates of one mcr_probe_months_rng call that can share their accumulation sweep */
 #define MCR_MAX_EXPENSE_FANOUT 15  /* spending levels one expense fan-out workgroup evaluates (mcr_probe_expenses_rng) */
 #define MCR_MAX_HIST_BINS 4096  /* bins of the in-kernel final-balance histogram (mcr_outputs.hist_bins) */
+#define MCR_MAX_YEAR_BINS 512   /* bins per row of the yearly-bins tables (mcr_year_bins); each balance bin costs 28 bytes of a
+                                   workgroup's LDS and each withdrawal-rate bin 16: 2.9 KB at 64 + 64 bins, 11.4 KB at 256 + 256,
+                                   22.6 KB at the cap — above about 256 + 256 a CU holds one workgroup fewer */
 #define MCR_MONTHS_PER_YEAR 12  /* backend/constants.py:1 */
 #define MCR_SMALL_EPSILON 1e-6  /* backend/constants.py:3 (absolute dollar threshold) */
 
@@ -341,6 +344,47 @@ int mcr_probe_contributions_rng(const mcr_params* p, const mcr_rng* rng, uint32_
 int mcr_probe_grid_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
                        uint64_t n_paths, const int32_t* working_months, int32_t n_candidates,
                        const double* monthly_expenses, int32_t n_levels, uint64_t* counts, int device, void* hip_stream);
+
+/*
+ * YEARLY BINS: the fan chart of any number of paths with no per-path output.  The whole-path kernel runs as for full output, but
+ * wherever it would store a yearly sample every lane bins the value on CALLER-SUPPLIED edges instead:
+ *   trajectory_bins[t]       <- the nominal balance of yearly sample t            (mcr_outputs.trajectory[t])
+ *   real_trajectory_bins[t]  <- the same in today's money                         (mcr_outputs.real_trajectory[t])
+ *   wr_bins[y]               <- the withdrawal rate of retirement year y, percent (mcr_outputs.withdrawal_rate_trajectory[y]; NaN
+ *                               entries are not counted)
+ *   final_success_bins       <- Final Balance of the successful paths
+ * Every row has n + 2 cells: cell 0 counts values below edges[0], cells 1 .. n are exactly np.histogram(row, bins=edges) (bin k =
+ * [e_k, e_k+1), the last one closed on the right, zero-width bins allowed), cell n + 1 counts values above edges[n].  So every
+ * trajectory row sums to the number of paths, wr_bins[y] to wr_obs_counts[y] and final_success_bins to the success counter, and
+ * each quantile of a row is known to within one bin.  The values binned are bit for bit those the full-output launch stores.
+ * Tables are accumulated into like the counters (the caller zeroes them); any table may be NULL = not requested.  Rows are
+ * accumulated per workgroup in LDS and added to the tables with contiguous 64-bit atomic adds: nothing is allocated per path, and a
+ * multi-GPU caller that keeps counters and tables in one vector sums everything with ONE all-reduce.
+ * edges / wr_edges: [n + 1] ascending finite doubles, n in 1..MCR_MAX_YEAR_BINS (required under a requested table; the *_host
+ * forms check finiteness and order, the device form cannot).
+ */
+typedef struct mcr_year_bins {
+    const double* edges;     int32_t n_bins;     /* trajectory, real trajectory, final_success: [n_bins+1] ascending finite */
+    const double* wr_edges;  int32_t n_wr_bins;  /* withdrawal rate (percent) */
+    uint64_t* trajectory_bins;       /* [T][n_bins+2]   any table may be NULL = not requested */
+    uint64_t* real_trajectory_bins;  /* [T][n_bins+2] */
+    uint64_t* wr_bins;               /* [ry][n_wr_bins+2] */
+    uint64_t* final_success_bins;    /* [n_bins+2] */
+} mcr_year_bins;
+/* `out` may carry only counters, wr_obs_counts, ruin_year_bins and the hist_* fields (any per-path or trajectory pointer in it:
+ * MCR_ERR_INVALID_ARG).  Philox and NumPy streams, every tax variant, stream lists of any length; there are no injected shocks
+ * on this route.  Everything is validated before anything is enqueued: on an error the tables are untouched.
+ * mcr_run_year_bins_rng: DEVICE pointers in `out` / `yb`, asynchronous on hip_stream like mcr_run_batch_rng.
+ * mcr_run_year_bins_host_rng: HOST pointers; leases a pooled context like mcr_run_batch_host_rng; device = a HIP ordinal or
+ * MCR_DEVICE_ALL.  mcr_run_year_bins_multi_host_rng: the same over an explicit device list (entries may repeat), sharded and
+ * summed on the host like mcr_run_batch_multi_host_rng: the same tables whatever the list. */
+int mcr_run_year_bins_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                          int32_t working_months, const mcr_outputs* out, const mcr_year_bins* yb, int device, void* hip_stream);
+int mcr_run_year_bins_host_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                               int32_t working_months, const mcr_outputs* out, const mcr_year_bins* yb, int device);
+int mcr_run_year_bins_multi_host_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                     uint64_t n_paths, int32_t working_months, const mcr_outputs* out, const mcr_year_bins* yb,
+                                     const int32_t* devices, int32_t n_devices);
 
 /* _draw_shock_path (simulation.py:452-466) for n_paths paths: host out [n_paths][n_months][3]. */
 int mcr_draw_shocks_host(uint64_t seed, uint32_t stream_id, uint64_t path_begin,

@@ -25,6 +25,8 @@ MCR_RNG_NUMPY = 1
 MCR_MAX_ENTROPY_WORDS = 8
 MCR_DEVICE_ALL = -2
 MCR_MAX_HIST_BINS = 4096
+MCR_MAX_YEAR_BINS = 512  # bins per row of the yearly-bins tables (mcr_year_bins)
+MCR_ERR_INVALID_ARG = -1
 MCR_MAX_EXPENSE_FANOUT = 15  # spending levels one expense fan-out workgroup evaluates (mcr_probe_expenses_rng)
 
 MCR_HELPER_WITHDRAW = 0
@@ -216,6 +218,21 @@ class McrOutputs(C.Structure):
     ]
 
 
+class McrYearBins(C.Structure):
+    """Edges and tables of a yearly-bins launch (include/mcr.h: mcr_year_bins); addresses like McrOutputs."""
+
+    _fields_ = [
+        ("edges", C.c_void_p),
+        ("n_bins", C.c_int32),
+        ("wr_edges", C.c_void_p),
+        ("n_wr_bins", C.c_int32),
+        ("trajectory_bins", C.c_void_p),
+        ("real_trajectory_bins", C.c_void_p),
+        ("wr_bins", C.c_void_p),
+        ("final_success_bins", C.c_void_p),
+    ]
+
+
 #: The symbols include/mcr.h declares; tests check that the built library exports them all.
 ABI_SYMBOLS = (
     "mcr_abi_version",
@@ -234,6 +251,9 @@ ABI_SYMBOLS = (
     "mcr_probe_contributions_rng",
     "mcr_probe_grid_rng",
     "mcr_run_batch_multi_host_rng",
+    "mcr_run_year_bins_rng",
+    "mcr_run_year_bins_host_rng",
+    "mcr_run_year_bins_multi_host_rng",
     "mcr_validate_params",
     "mcr_release_cached",
     "mcr_sample_columns",
@@ -323,6 +343,18 @@ def _declare(lib: C.CDLL) -> None:
     lib.mcr_run_batch_multi_host_rng.argtypes = [
         P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32,
         C.c_void_p, P(McrOutputs), P(C.c_int32), C.c_int32,
+    ]
+    lib.mcr_run_year_bins_rng.restype = C.c_int
+    lib.mcr_run_year_bins_rng.argtypes = [
+        P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32, P(McrOutputs), P(McrYearBins), C.c_int, C.c_void_p,
+    ]
+    lib.mcr_run_year_bins_host_rng.restype = C.c_int
+    lib.mcr_run_year_bins_host_rng.argtypes = [
+        P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32, P(McrOutputs), P(McrYearBins), C.c_int,
+    ]
+    lib.mcr_run_year_bins_multi_host_rng.restype = C.c_int
+    lib.mcr_run_year_bins_multi_host_rng.argtypes = [
+        P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32, P(McrOutputs), P(McrYearBins), P(C.c_int32), C.c_int32,
     ]
     lib.mcr_validate_params.restype = C.c_int
     lib.mcr_validate_params.argtypes = [P(McrParams)]

@@ -35,6 +35,58 @@ def band_quantiles(batch, n: int, reduce_counts=None, n_total: Optional[int] = N
     return q[:T], q[T:2 * T], np.ascontiguousarray(q[2 * T:][:, _WR_COLS]), counts[2 * T:]
 
 
+def bands_from_bins(bins, edges, qs: Sequence[float]):
+    """Quantile brackets of rows that exist only as yearly bins (``mcr_year_bins``; pure NumPy, no device).
+
+    ``bins[rows, n + 2]``: cell 0 = below ``edges[0]``, cells 1..n = ``np.histogram(row, bins=edges)``, cell n + 1 = above
+    ``edges[n]``.  For every row and q, with ``m`` the row sum, ``h = (m - 1) q``, ``k = floor(h)``: ``lo`` is the left edge
+    of the bin that holds order statistic k and ``hi`` the right edge of the bin that holds order statistic ``ceil(h)`` — the
+    pandas / linear quantile ``x_k + (h - k)(x_k+1 - x_k)`` of the binned data lies in ``[lo, hi]`` BY CONSTRUCTION.
+    ``estimate`` places each of the two order statistics inside its bin by its rank among the bin's entries (entry j of c at
+    ``left + (j + 1/2) / c`` of the width) and interpolates between them like the quantile itself.  An order statistic in
+    the below / above cell makes that side ``-inf`` / ``+inf`` and the estimate NaN; an empty row gives NaN everywhere.
+    Returns ``(lo, hi, estimate)``, each ``[rows, len(qs)]``."""
+    b = np.asarray(bins)
+    if b.ndim == 1:
+        b = b[None, :]
+    e = np.asarray(edges, dtype=np.float64).reshape(-1)
+    if b.ndim != 2 or b.shape[1] != e.shape[0] + 1:
+        raise ValueError(f"bins {b.shape} do not match {e.shape[0]} edges (need [rows, n_bins + 2])")
+    if e.shape[0] < 2 or not np.all(np.isfinite(e)) or np.any(e[1:] < e[:-1]):
+        raise ValueError("edges must be finite and increase monotonically")
+    q = _pandas_q(qs)
+    if np.any(q < 0.0) or np.any(q > 1.0):
+        raise ValueError("quantiles must be within [0, 1]")
+    left = np.concatenate(([-np.inf], e))          # per cell: [left, right]
+    right = np.concatenate((e, [np.inf]))
+    shape = (b.shape[0], q.shape[0])
+    lo, hi, est = np.full(shape, np.nan), np.full(shape, np.nan), np.full(shape, np.nan)
+    for r in range(b.shape[0]):
+        c = b[r].astype(np.int64)
+        m = int(c.sum())
+        if m == 0:
+            continue
+        cum = np.cumsum(c)                         # order statistic k (0-based) sits in the first cell with cum > k
+        h = (m - 1) * q
+        k0 = np.floor(h).astype(np.int64)
+        k1 = np.ceil(h).astype(np.int64)
+        c0 = np.searchsorted(cum, k0, side="right")
+        c1 = np.searchsorted(cum, k1, side="right")
+        lo[r], hi[r] = left[c0], right[c1]
+
+        def place(k, cell):                        # the rank-interpolated position of order statistic k inside its cell
+            j = k - (cum[cell] - c[cell])
+            with np.errstate(invalid="ignore"):
+                return left[cell] + (j + 0.5) / c[cell] * (right[cell] - left[cell])
+
+        x0, x1 = place(k0, c0), place(k1, c1)
+        with np.errstate(invalid="ignore"):
+            v = x0 + (h - k0) * (x1 - x0)
+        v[~(np.isfinite(lo[r]) & np.isfinite(hi[r]))] = np.nan
+        est[r] = np.clip(v, lo[r], hi[r])
+    return lo, hi, est
+
+
 def _pandas_q(qs: Sequence[float]) -> np.ndarray:
     """pandas hands ``qs * 100`` to np.percentile, which divides by 100 again
     (pandas/core/array_algos/quantile.py, numpy percentile): reproduce that round trip."""

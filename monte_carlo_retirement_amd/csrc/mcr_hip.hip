@@ -4,6 +4,7 @@
 //       MODE 0: success count only          (no per-path HBM traffic; BASELINE config 2)
 //       MODE 1: + per-path summary fields   (SoA, 49 B/path)
 //       MODE 2: + yearly trajectories       (time-major [T][N]: 512 contiguous bytes per wave store)
+//       MODE 3: yearly bins                 (every lane bins its yearly samples on the caller's edges: no per-path HBM traffic)
 //       RNG 0: Philox4x32-10 + Box-Muller (mcr_device.h);  RNG 1: NumPy's SeedSequence -> PCG64 ->
 //              ziggurat stream (mcr_numpy_rng.h), for literal seed parity with the reference
 //     reductions: wave ballot+popcount -> LDS -> one global atomic per workgroup.
@@ -70,8 +71,23 @@ struct KernelIO {
     // level fan_expenses[j] (monthly_expenses / monthly_contribution) and adds its counts to counters + j * MCR_N_COUNTERS;
     // fan_n = blockDim.x / 64 - 1 levels
     int32_t fan_n;
-    double fan_expenses[MCR_MAX_EXPENSE_FANOUT];   // the fan-out levels
+    // MODE 3 (yearly bins, mcr_run_year_bins_rng) shares the bytes of the fan-out levels: no launch is both, and the layout
+    // of the kernel arguments every other variant reads stays what it was
+    struct YearBins {
+        const double* edges;                  // [n_bins + 1]
+        const double* wr_edges;               // [n_wr_bins + 1]
+        unsigned long long* trajectory;       // [T][n_bins + 2] or nullptr
+        unsigned long long* real_trajectory;  // [T][n_bins + 2] or nullptr
+        unsigned long long* wr;               // [ry][n_wr_bins + 2] or nullptr
+        unsigned long long* final_success;    // [n_bins + 2] or nullptr
+        int32_t n_bins, n_wr_bins;            // (0: the group is not requested)
+    };
+    union {
+        double fan_expenses[MCR_MAX_EXPENSE_FANOUT];   // the fan-out levels
+        YearBins yb;
+    };
 };
+static_assert(sizeof(KernelIO::YearBins) <= sizeof(double) * MCR_MAX_EXPENSE_FANOUT, "the yearly-bins block must fit the bytes it overlays");
 // PHASE 6 (grid probe, mcr_probe_grid_rng): one record per grid row (blockIdx.y) of a launch, in device memory; path_kernel's
 // `cand_params` points at the launch's records.  Everything a row needs is wave-uniform there: scalar loads.
 struct GridCell {
@@ -93,6 +109,77 @@ constexpr int seg_fixed_fields(int mode) { return mode >= 1 ? 14 : 9; }
 constexpr unsigned long long kNanBits = 0x7ff8000000000000ull;
 __device__ __forceinline__ unsigned long long f64_bits(double x) { return (unsigned long long)__double_as_longlong(x); }
 __device__ __forceinline__ void store_bits(double* p, unsigned long long bits) { *reinterpret_cast<unsigned long long*>(p) = bits; }
+
+// MODE 3 of path_kernel (yearly bins): the workgroup's LDS behind its block counters — both edge arrays, two row buffers
+// [trajectory | real | wr] of 32-bit cells and the cells of final_success_bins
+struct YearBinsLds {
+    double* edges; double* wedges;       // [n + 1], [wn + 1]
+    unsigned int* buf; unsigned int* fin;  // [2][row], [cells]
+    int n, wn, cells, wcells, row;       // row = 2 cells + wcells
+};
+// per-thread state of the form: the LDS plan, rows binned so far (picks the row buffer), and the value of row T - 1 where the
+// terminal partial period writes that row a second time (the row is binned once, after it)
+struct YearBinsState { YearBinsLds L; int k; double last; };
+struct NoYearBins {};
+__device__ __forceinline__ YearBinsLds year_bins_lds(const KernelIO::YearBins& yb, unsigned int* after_blk) {
+    YearBinsLds L;
+    L.n = yb.n_bins; L.wn = yb.n_wr_bins;
+    L.cells = L.n + 2; L.wcells = L.wn + 2; L.row = 2 * L.cells + L.wcells;
+    L.edges = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(after_blk) + 7u) & ~(uintptr_t)7u);
+    L.wedges = L.edges + (L.n + 1);
+    L.buf = reinterpret_cast<unsigned int*>(L.wedges + (L.wn + 1));
+    L.fin = L.buf + 2 * L.row;
+    return L;
+}
+// the cell of x in a row of n bins: 0 below e[0], n + 1 above e[n], else 1 + np.histogram's bin (the last one closed)
+__device__ __forceinline__ int year_bins_cell(const double* e, int n, double x) {
+    if (x < e[0]) return 0;
+    if (x > e[n]) return n + 1;
+    int lo = 0, hi = n;                  // e[lo] <= x and (hi == n or x < e[hi])
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (e[mid] <= x) lo = mid; else hi = mid;
+    }
+    return lo + 1;
+}
+// One row of the tables; call k of the workgroup (every thread makes the same calls: one barrier each).  nominal / px go to row t
+// of trajectory_bins / real_trajectory_bins (has_sample), wr_bits (NaN: not counted) to row y of wr_bins (y < 0: none).
+__device__ __forceinline__ void year_bins_row(const KernelIO::YearBins& yb, const YearBinsLds& L, int k, bool valid, int t, bool has_sample,
+                                              double nominal, double px, int y, unsigned long long wr_bits) {
+    unsigned int* const b = L.buf + (k & 1) * L.row;
+    if (valid) {
+        if (has_sample) {
+            if (yb.trajectory) atomicAdd(&b[year_bins_cell(L.edges, L.n, nominal)], 1u);
+            if (yb.real_trajectory) atomicAdd(&b[L.cells + year_bins_cell(L.edges, L.n, px > kEps ? nominal / px : 0.0)], 1u);
+        }
+        if (y >= 0 && yb.wr && wr_bits != kNanBits)
+            atomicAdd(&b[2 * L.cells + year_bins_cell(L.wedges, L.wn, __longlong_as_double((long long)wr_bits))], 1u);
+    }
+    __syncthreads();
+    for (int c0 = 0; c0 < L.row; c0 += kBlock) {      // (wave-uniform trip count: the ballot below)
+        const int c = c0 + (int)threadIdx.x;
+        const unsigned int v = c < L.row ? b[c] : 0u;
+        if (__builtin_amdgcn_ballot_w64(v != 0u) == 0ull) continue;    // an all-zero group of 64 cells
+        if (c >= L.row) continue;
+        if (v) b[c] = 0u;
+        unsigned long long* dst = nullptr;
+        if (c < L.cells) dst = yb.trajectory ? yb.trajectory + (size_t)t * L.cells + c : nullptr;
+        else if (c < 2 * L.cells) dst = yb.real_trajectory ? yb.real_trajectory + (size_t)t * L.cells + (c - L.cells) : nullptr;
+        else if (y >= 0 && yb.wr) dst = yb.wr + (size_t)y * L.wcells + (c - 2 * L.cells);
+        // every lane of the group adds, zeros included: consecutive cells, contiguous 8-byte atomics.  Adding only the non-zero
+        // cells measured the same (LABNOTES R10: 6.33 / 6.47 ms against 6.30 / 6.51 at 64 / 256 bins)
+        if (dst) atomicAdd(dst, (unsigned long long)v);
+    }
+}
+__device__ __forceinline__ void year_bins_flush_final(const KernelIO::YearBins& yb, const YearBinsLds& L) {   // (behind a barrier)
+    if (!yb.final_success) return;
+    for (int c0 = 0; c0 < L.cells; c0 += kBlock) {
+        const int c = c0 + (int)threadIdx.x;
+        const unsigned int v = c < L.cells ? L.fin[c] : 0u;
+        if (__builtin_amdgcn_ballot_w64(v != 0u) == 0ull) continue;
+        if (c < L.cells) atomicAdd(yb.final_success + c, (unsigned long long)v);
+    }
+}
 
 // Resident waves per SIMD are worth more than a few spilled registers: the trimmed count-only kernel loses 4.4 % on
 // large batches at 4 instead of 6 workgroups per CU (measured with a larger LDS footprint, LABNOTES.md rounds 1-3 section 9), and the Philox
@@ -166,6 +253,18 @@ constexpr bool kUniformFixups = true;
 template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault>
 __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
                                                          const DevParams* __restrict__ cand_params) {
+    // MODE 3 (mcr_run_year_bins_rng): YEARLY BINS.  The arithmetic of MODE 2, but wherever that variant stores a yearly sample
+    // (nominal balance, real balance, withdrawal rate) the lane bins it instead: cell 0 = below edges[0], cells 1 .. n = the
+    // bins of np.histogram(row, bins=edges), cell n + 1 = above edges[n].  A row of a table is accumulated by the WORKGROUP in
+    // LDS (32-bit cells, ds atomics) and flushed once: after one barrier every wave adds its 64-cell groups of the row to the
+    // global table with contiguous 64-bit atomic adds, skipping groups that are all zero.  Two row buffers alternate, so one
+    // barrier per row is enough (a buffer is binned into again two rows later, i.e. behind the NEXT row's barrier, which every
+    // wave passes after its own flush).  Every wave of the workgroup executes the same number of barriers: it visits every row
+    // exactly once, in the year loop or, once all its lanes have failed, in the pad loop.  The row the trajectory variant writes
+    // twice (the terminal partial period overwrites row T - 1 of successful paths) is binned once, after the settlement, with
+    // the value that variant leaves in memory.  The edges live in LDS (two 8-step searches per path-year are dependent reads).
+    // Held to 4 waves per SIMD (<= 128 VGPRs): no scratch.
+    static_assert(MODE != 3 || (PHASE == 0 && !SPLIT && !INJ), "the yearly-bins form is a whole-path launch on the engine's own streams");
     static_assert(!SPLIT || (MODE == 0 && RNG == 0 && !INJ), "the producer / consumer split exists for the count-only Philox variants");
     static_assert(!XS || (PHASE == 0 && !SPLIT && TAXED == 3 && ANNUAL), "extended stream lists run the generic whole-path form");
     static_assert(PHASE != 5 || SPLIT, "the expense fan-out is a producer / consumer form");
@@ -228,7 +327,8 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MC
     // 50.28 -> 50.07 ms, 4e6 config.json paths 29.59 -> 29.40 ms.  A fourth column (the start-of-retirement balance) frees the
     // trajectory variant of its last 12 bytes of scratch but its 2 KB cost a resident workgroup as soon as the scenario has a
     // non-indexed income stream (one more LDS column): 50.07 -> 52.2 ms on jorge.json.  Three it is.
-    constexpr bool kSumLds = MODE >= 1 && kStaged;
+    constexpr bool kBins = MODE == 3;
+    constexpr bool kSumLds = (MODE == 1 || MODE == 2) && kStaged;
     __shared__ __align__(16) double sum_s[kSumLds ? 3 * kBlock : 1];
     extern __shared__ __align__(16) unsigned char smem_raw[];
 #ifdef MCR_K1_TIMELINE   // diagnostic build only (tools/k1_timeline.py): per-wave start / end stamps and placement
@@ -251,6 +351,16 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MC
     const int n_blk = kFan ? MCR_MAX_EXPENSE_FANOUT : 1 + (ry + 2) + (ry + 1);   // (PHASE 5: blk[j] = level j's success count)
     const int n_hist = ((PHASE == 0 || PHASE == 3) && io.out.hist_bins != nullptr) ? io.out.hist_n_bins : 0;
     for (int k = threadIdx.x; k < n_blk + n_hist; k += kThreads) blk[k] = 0u;
+    // MODE 3: behind the block counters the edge arrays, the row buffers and the final_success cells (YearBinsLds)
+    [[maybe_unused]] std::conditional_t<kBins, YearBinsState, NoYearBins> YB;    // (an empty object in every other variant)
+    if constexpr (kBins) {
+        YB.L = year_bins_lds(io.yb, blk + n_blk + n_hist);
+        YB.k = 0; YB.last = 0.0;
+        const YearBinsLds& YL = YB.L;
+        if (YL.n > 0) for (int k = threadIdx.x; k <= YL.n; k += kThreads) YL.edges[k] = io.yb.edges[k];
+        if (YL.wn > 0) for (int k = threadIdx.x; k <= YL.wn; k += kThreads) YL.wedges[k] = io.yb.wr_edges[k];
+        for (int k = threadIdx.x; k < 2 * YL.row + YL.cells; k += kThreads) YL.buf[k] = 0u;
+    }
     __syncthreads();
 
     const uint64_t local = (uint64_t)path_block * kPaths + (unsigned)tid;
@@ -264,7 +374,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MC
     const double* inj = INJ ? io.injected + (size_t)li * 3u * (size_t)P.shock_rows : nullptr;
 
     constexpr bool kSummary = MODE >= 1;
-    constexpr bool kTraj = MODE >= 2;
+    constexpr bool kTraj = MODE == 2;
     double* traj = kTraj ? io.out.trajectory : nullptr;
     double* rtraj = kTraj ? io.out.real_trajectory : nullptr;
     double* wrt = kTraj ? io.out.withdrawal_rate_trajectory : nullptr;
@@ -274,6 +384,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MC
             if (traj) traj[(int64_t)t * stride + (int64_t)li] = nominal;
             if (rtraj) rtraj[(int64_t)t * stride + (int64_t)li] = px > kEps ? nominal / px : 0.0;
         }
+        if constexpr (kBins) year_bins_row(io.yb, YB.L, YB.k++, valid, t, true, nominal, px, -1, kNanBits);
     };
     Pcg64 gen;  // NumPy stream: one generator per path, rows are consumed strictly in order
     if (RNG == (int)MCR_RNG_NUMPY && !INJ) {
@@ -673,12 +784,19 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MC
                 done_years = year + 1;
             }
         }
-        put_sample(t_idx, sample, infl);  // dead lanes: 0 / px = 0 (:906-916, :928-931)
+        if constexpr (kBins) {   // the year's row of all three tables behind one barrier; a last row that is written again below waits for that value
+            // (ry >= 1 on every launch: query_sizes, through derive_params, rejects retirement_years <= 0 — so the year of row T - 1
+            //  always comes up here or in the pad loop, and the row is binned exactly once)
+            const bool defer = P.total_months % kMPY != 0 && year == ry - 1;     // wave-uniform
+            if (defer) YB.last = sample;
+            year_bins_row(io.yb, YB.L, YB.k++, valid, t_idx, !defer, sample, infl, year, wr_bits);
+        } else put_sample(t_idx, sample, infl);  // dead lanes: 0 / px = 0 (:906-916, :928-931)
         ++t_idx;
         if (kTraj && valid && wrt) store_bits(&wrt[(int64_t)year * stride + (int64_t)li], wr_bits);  // :851, :859, :934-935
     }
     for (; year < (kSliced ? y_end : ry); ++year) {  // the whole wave failed early: pad (:902-916, :934-935)
-        put_sample(t_idx++, 0.0, infl);
+        if constexpr (kBins) year_bins_row(io.yb, YB.L, YB.k++, valid, t_idx++, !(P.total_months % kMPY != 0 && year == ry - 1), 0.0, infl, year, kNanBits);
+        else put_sample(t_idx++, 0.0, infl);
         if (kTraj && valid && wrt) store_bits(&wrt[(int64_t)year * stride + (int64_t)li], kNanBits);
     }
     if (kSliced && seg >= 0 && seg < io.seg_q - 1) {
@@ -721,8 +839,10 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MC
                 succeeded = false; ruin_bin = ry + 1;
                 if (kSumLds) sum_col[2 * kBlock] = (double)ry; else ytr_bits = f64_bits((double)ry);
             }
-            put_sample(P.trajectory_len - 1, b1 + b2, infl);                     // :897-898
+            if constexpr (kBins) YB.last = b1 + b2;                              // (binned below: no barrier under a lane mask)
+            else put_sample(P.trajectory_len - 1, b1 + b2, infl);                // :897-898
         }
+        if constexpr (kBins) year_bins_row(io.yb, YB.L, YB.k++, valid, P.trajectory_len - 1, true, YB.last, infl, -1, kNanBits);
     }
     const double final_balance = fmax(0.0, b1 + b2);  // :900, :941
 
@@ -780,7 +900,9 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MC
             atomicAdd(&blk[n_blk + lo], 1u);
         }
     }
+    if constexpr (kBins) { if (io.yb.final_success && valid && succeeded) atomicAdd(&YB.L.fin[year_bins_cell(YB.L.edges, YB.L.n, final_balance)], 1u); }
     __syncthreads();
+    if constexpr (kBins) year_bins_flush_final(io.yb, YB.L);
     uint64_t* ctr = io.out.counters ? io.out.counters + (kCand ? (size_t)io.cand_out[cand] * MCR_N_COUNTERS : 0) : nullptr;
     if (threadIdx.x == 0 && ctr) {
         atomicAdd((unsigned long long*)&ctr[MCR_CTR_SUCCESS], (unsigned long long)blk[0]);
@@ -1316,11 +1438,19 @@ constexpr size_t kLdsForFourResident = 40 * 1024;
 static size_t path_kernel_static_lds(int mode, bool numpy_rng, bool injected, bool split) {
     const bool staged = !numpy_rng && !injected;
     return (size_t)kMathTabBytes + (staged ? (size_t)(split ? 2 : 1) * kStageDoubles * sizeof(double) : 16) +
-           ((mode >= 1 && staged) ? (size_t)3 * kBlock * sizeof(double) : 16);
+           (((mode == 1 || mode == 2) && staged) ? (size_t)3 * kBlock * sizeof(double) : 16);
 }
-static int plan_path_kernel_lds(DevParams& d, int mode, bool numpy_rng, bool injected, bool split, int n_hist_bins, size_t* dynamic_bytes) {
+// LDS of the yearly-bins form (MODE 3 of path_kernel) behind the block counters: both edge arrays as doubles, two row buffers
+// [trajectory | real | wr] and the final_success cells as 32-bit counts — 8 + 5 x 4 = 28 bytes per balance bin, 8 + 2 x 4 = 16
+// per withdrawal-rate bin (+ 8 of alignment)
+static size_t year_bins_lds(int n_bins, int n_wr_bins) {
+    const size_t cells = (size_t)n_bins + 2, wcells = (size_t)n_wr_bins + 2;
+    return 8 + ((size_t)n_bins + 1 + (size_t)n_wr_bins + 1) * sizeof(double) + (2 * (2 * cells + wcells) + cells) * sizeof(unsigned int);
+}
+static int plan_path_kernel_lds(DevParams& d, int mode, bool numpy_rng, bool injected, bool split, int n_hist_bins, size_t* dynamic_bytes,
+                                size_t year_bins_bytes = 0) {
     const size_t fixed = path_kernel_static_lds(mode, numpy_rng, injected, split) + (numpy_rng ? (size_t)kZigLdsBytes : (size_t)0) +
-                         (size_t)(1 + (d.retirement_years + 2) + (d.retirement_years + 1) + n_hist_bins) * sizeof(unsigned int);
+                         (size_t)(1 + (d.retirement_years + 2) + (d.retirement_years + 1) + n_hist_bins) * sizeof(unsigned int) + year_bins_bytes;
     if (fixed > kLdsPerWorkgroup) { set_error("too many retirement years / histogram bins for the LDS of a workgroup"); return MCR_ERR_UNSUPPORTED; }
     constexpr size_t kSlotBytes = (size_t)kBlock * sizeof(double);
     long slots = (long)((kLdsPerWorkgroup - fixed) / kSlotBytes);
@@ -1508,6 +1638,26 @@ template <typename F> static inline void for_output_mode(int mode, F&& f) {
     if (mode == 2) f(int_c<2>{}); else if (mode == 1) f(int_c<1>{}); else f(int_c<0>{});
 }
 
+// f(R, T, A, X, E) = (stream, tax mask, annual-gains tax, extended streams, exact month) of a whole-path launch (PHASE 0, not
+// split, no injection) — the one place that says which variants such a launch has: the generic form (mask 3, annual) for
+// extended streams / the exact month; the engine's own stream per tax mask; the NumPy stream taxed / untaxed only (mask 3
+// computes a zero-rate asset's tax arithmetic as exact zeros)
+template <typename F> static inline void for_whole_path_variant(const DevParams& d, bool np_rng, bool xs, bool exact, F&& f) {
+    auto with_stream = [&](auto R) {
+        if (xs) {
+            if (exact) f(R, int_c<3>{}, std::true_type{}, std::true_type{}, std::true_type{});
+            else f(R, int_c<3>{}, std::true_type{}, std::true_type{}, std::false_type{});
+        } else if constexpr (decltype(R)::value == 0) {
+            for_tax_variant(d, [&](auto T, auto A) { f(R, T, A, std::false_type{}, std::false_type{}); });
+        } else {
+            for_bool(d.any_annual_tax, [&](auto A) {
+                if (d.any_real_rate) f(R, int_c<3>{}, A, std::false_type{}, std::false_type{});
+                else f(R, int_c<0>{}, A, std::false_type{}, std::false_type{});
+            });
+        }
+    };
+    if (np_rng) with_stream(int_c<1>{}); else with_stream(int_c<0>{});
+}
 // The generic variants (XS) carry what the lean ones leave out: records beyond the by-value block and both forms of the month
 static bool needs_exact_month(const DevParams& d) { return d.exact_month && !kExactMonthDefault; }
 static bool needs_generic_variant(const DevParams& d) { return d.n_extra_streams > 0 || needs_exact_month(d); }
@@ -1620,18 +1770,21 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
     rc = side.attach(d, extra, grid.x, stream);
     if (rc != MCR_OK) { (void)side.release(stream); return rc; }
     const DevParams* const no_cand = nullptr;
-    // f(M, R, I) = (output mode, stream, injection) of the launches that are not time-sliced
-    auto for_family = [&](auto&& f) {
-        if (injected) f(int_c<2>{}, int_c<0>{}, std::true_type{});
-        else for_output_mode(mode, [&](auto M) { if (np_rng) f(M, int_c<1>{}, std::false_type{}); else f(M, int_c<0>{}, std::false_type{}); });
+    // the whole-path variants of the engine's streams (for_whole_path_variant), output mode M
+    auto launch_whole_path = [&]() {
+        for_output_mode(mode, [&](auto M) {
+            for_whole_path_variant(d, np_rng, xs, exact, [&](auto R, auto T, auto A, auto X, auto EX) {
+                hipLaunchKernelGGL((path_kernel<decltype(M)::value, decltype(R)::value, decltype(T)::value, decltype(A)::value, false, 0, false,
+                                                decltype(X)::value, (decltype(X)::value && decltype(EX)::value) || kExactMonthDefault>),
+                                   grid, block, lds, stream, d, io, no_cand);
+            });
+        });
     };
     if (xs) {
-        for_family([&](auto M, auto R, auto I) {
-            constexpr int m = decltype(M)::value, r = decltype(R)::value;
-            constexpr bool inj = decltype(I)::value;
-            if (exact) hipLaunchKernelGGL((path_kernel<m, r, 3, true, inj, 0, false, true, true>), grid, block, lds, stream, d, io, no_cand);
-            else hipLaunchKernelGGL((path_kernel<m, r, 3, true, inj, 0, false, true>), grid, block, lds, stream, d, io, no_cand);
-        });
+        if (injected) {
+            if (exact) hipLaunchKernelGGL((path_kernel<2, 0, 3, true, true, 0, false, true, true>), grid, block, lds, stream, d, io, no_cand);
+            else hipLaunchKernelGGL((path_kernel<2, 0, 3, true, true, 0, false, true>), grid, block, lds, stream, d, io, no_cand);
+        } else launch_whole_path();
         hipError_t ex = hipGetLastError();
         const hipError_t ef = side.release(stream);
         if (ex != hipSuccess) return hip_fail(ex, "path_kernel launch (extended streams)");
@@ -1677,19 +1830,93 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
         if (es != hipSuccess) return hip_fail(es, "path_kernel launch (split)");
         return MCR_OK;
     }
-    // the engine's own stream: one variant per tax mask (which of the two assets is taxed on realized gains); the parity
-    // hook and the NumPy stream: taxed / untaxed only (mask 3 computes a zero-rate asset's tax arithmetic as exact zeros)
-    for_family([&](auto M, auto R, auto I) {
-        constexpr int m = decltype(M)::value, r = decltype(R)::value;
-        constexpr bool inj = decltype(I)::value;
-        auto launch = [&](auto T, auto A) {
-            hipLaunchKernelGGL((path_kernel<m, r, decltype(T)::value, decltype(A)::value, inj>), grid, block, lds, stream, d, io, no_cand);
-        };
-        if constexpr (r == 0 && !inj) for_tax_variant(d, launch);
-        else for_bool(d.any_annual_tax, [&](auto A) { if (d.any_real_rate) launch(int_c<3>{}, A); else launch(int_c<0>{}, A); });
-    });
+    // the parity hook: taxed / untaxed only, like the NumPy stream
+    if (injected) {
+        for_bool(d.any_annual_tax, [&](auto A) {
+            if (d.any_real_rate) hipLaunchKernelGGL((path_kernel<2, 0, 3, decltype(A)::value, true>), grid, block, lds, stream, d, io, no_cand);
+            else hipLaunchKernelGGL((path_kernel<2, 0, 0, decltype(A)::value, true>), grid, block, lds, stream, d, io, no_cand);
+        });
+    } else launch_whole_path();
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "path_kernel launch");
+    return MCR_OK;
+}
+
+// Yearly bins (MODE 3 of path_kernel; mcr_run_year_bins_rng).  Checks of the arguments both entry points share: nothing is
+// enqueued, and no table touched, unless they all pass.
+static int check_year_bins(const mcr_outputs* out, const mcr_year_bins* yb) {
+    if (!out || !yb) { set_error("null outputs / year bins"); return MCR_ERR_INVALID_ARG; }
+    if (out->start_balance || out->final_balance || out->years_to_ruin || out->first_year_gross_withdrawal ||
+        out->first_year_real_gross_withdrawal || out->inflation_at_retirement || out->success || out->trajectory ||
+        out->real_trajectory || out->withdrawal_rate_trajectory) {
+        set_error("year bins: `out` may carry counters, wr_obs_counts, ruin_year_bins and hist_* only (no per-path or trajectory output)");
+        return MCR_ERR_INVALID_ARG;
+    }
+    if (yb->trajectory_bins || yb->real_trajectory_bins || yb->final_success_bins) {
+        if (yb->n_bins < 1 || yb->n_bins > MCR_MAX_YEAR_BINS) { set_error("year bins: n_bins = %d (1..%d)", yb->n_bins, MCR_MAX_YEAR_BINS); return MCR_ERR_INVALID_ARG; }
+        if (!yb->edges) { set_error("year bins: null edges under a requested table"); return MCR_ERR_INVALID_ARG; }
+    }
+    if (yb->wr_bins) {
+        if (yb->n_wr_bins < 1 || yb->n_wr_bins > MCR_MAX_YEAR_BINS) { set_error("year bins: n_wr_bins = %d (1..%d)", yb->n_wr_bins, MCR_MAX_YEAR_BINS); return MCR_ERR_INVALID_ARG; }
+        if (!yb->wr_edges) { set_error("year bins: null wr_edges under wr_bins"); return MCR_ERR_INVALID_ARG; }
+    }
+    if (out->hist_bins && out->hist_n_bins != 0 && (out->hist_n_bins < 0 || out->hist_n_bins > MCR_MAX_HIST_BINS || !out->hist_edges)) {
+        set_error("hist_bins requested with hist_n_bins = %d (1..%d) / hist_edges = %p", out->hist_n_bins, MCR_MAX_HIST_BINS, (const void*)out->hist_edges);
+        return MCR_ERR_INVALID_ARG;
+    }
+    return MCR_OK;
+}
+static int check_edges_host(const char* what, const double* e, int n) {   // np.histogram: "bins must increase monotonically"
+    for (int k = 0; k <= n; ++k)
+        if (!std::isfinite(e[k]) || (k > 0 && e[k] < e[k - 1])) { set_error("%s[%d] = %g: edges must be finite and ascending", what, k, e[k]); return MCR_ERR_INVALID_ARG; }
+    return MCR_OK;
+}
+// The launch: device pointers in `out` / `yb`.  Variants: the Philox stream per tax mask, the NumPy stream taxed / untaxed, and
+// the generic (XS) form for stream lists beyond the by-value block, lock slots beyond the LDS budget and the exact month.
+static int launch_year_bins(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                            int32_t wm, const mcr_outputs* out, const mcr_year_bins* yb, hipStream_t stream) {
+    DevParams d;
+    std::vector<DevStream> extra;
+    int rc = derive_params(p, wm, &d, &extra);
+    if (rc != MCR_OK) return rc;
+    if ((rc = check_rng(rng)) != MCR_OK) return rc;
+    if ((rc = check_year_bins(out, yb)) != MCR_OK) return rc;
+    if (n_paths == 0) return MCR_OK;
+    if (n_paths > (uint64_t)INT32_MAX * kBlock) { set_error("n_paths too large for one launch"); return MCR_ERR_INVALID_ARG; }
+    if (path_begin + n_paths < path_begin) { set_error("path range overflows 64 bits"); return MCR_ERR_INVALID_ARG; }
+    KernelIO io = make_io(rng, rng->path_seeds, stream_id, path_begin, n_paths);
+    io.out = *out;
+    io.out.path_stride = (int64_t)n_paths;
+    if (io.out.hist_bins == nullptr || io.out.hist_n_bins == 0) { io.out.hist_bins = nullptr; io.out.hist_edges = nullptr; io.out.hist_n_bins = 0; }
+    const bool balance_tables = yb->trajectory_bins || yb->real_trajectory_bins || yb->final_success_bins;
+    io.yb.edges = balance_tables ? yb->edges : nullptr;
+    io.yb.n_bins = balance_tables ? yb->n_bins : 0;
+    io.yb.wr_edges = yb->wr_bins ? yb->wr_edges : nullptr;
+    io.yb.n_wr_bins = yb->wr_bins ? yb->n_wr_bins : 0;
+    io.yb.trajectory = (unsigned long long*)yb->trajectory_bins;
+    io.yb.real_trajectory = (unsigned long long*)yb->real_trajectory_bins;
+    io.yb.wr = (unsigned long long*)yb->wr_bins;
+    io.yb.final_success = (unsigned long long*)yb->final_success_bins;
+    const bool np_rng = rng->kind == MCR_RNG_NUMPY;
+    const dim3 grid((unsigned)((n_paths + kBlock - 1) / kBlock)), block(kBlock);
+    size_t lds = 0;
+    rc = plan_path_kernel_lds(d, 3, np_rng, false, false, io.out.hist_n_bins, &lds, year_bins_lds(io.yb.n_bins, io.yb.n_wr_bins));
+    if (rc != MCR_OK) return rc;
+    const bool exact = needs_exact_month(d);
+    const bool xs = d.n_lock_slots < d.n_lock_slots_total || needs_generic_variant(d);
+    StreamSideBlock side;
+    rc = side.attach(d, extra, grid.x, stream);
+    if (rc != MCR_OK) { (void)side.release(stream); return rc; }
+    const DevParams* const no_cand = nullptr;
+    for_whole_path_variant(d, np_rng, xs, exact, [&](auto R, auto T, auto A, auto X, auto EX) {
+        hipLaunchKernelGGL((path_kernel<3, decltype(R)::value, decltype(T)::value, decltype(A)::value, false, 0, false, decltype(X)::value,
+                                        (decltype(X)::value && decltype(EX)::value) || kExactMonthDefault>),
+                           grid, block, lds, stream, d, io, no_cand);
+    });
+    const hipError_t e = hipGetLastError();
+    const hipError_t ef = side.release(stream);
+    if (e != hipSuccess) return hip_fail(e, "path_kernel launch (yearly bins)");
+    if (ef != hipSuccess) return hip_fail(ef, "path_kernel launch (yearly bins): side block release");
     return MCR_OK;
 }
 
@@ -2358,6 +2585,169 @@ int mcr_run_batch_multi_host_rng(const mcr_params* p, const mcr_rng* rng, uint32
                                  uint64_t n_paths, int32_t working_months, const double* injected_shocks,
                                  const mcr_outputs* out, const int32_t* devices, int32_t n_devices) {
     return run_batch_host_multi(devices, n_devices, p, rng, stream_id, path_begin, n_paths, working_months, injected_shocks, out);
+}
+
+// ---- yearly bins -------------------------------------------------------------------------------------------------------
+int mcr_run_year_bins_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                          int32_t working_months, const mcr_outputs* out, const mcr_year_bins* yb, int device, void* hip_stream) {
+    MCR_ENTER_DEVICE(device);
+    return launch_year_bins(p, rng, stream_id, path_begin, n_paths, working_months, out, yb, (hipStream_t)hip_stream);
+}
+
+// The accumulated integer blocks of a yearly-bins call, in one list: the host forms upload, download and sum them alike
+struct YearBinsBlock { uint64_t* const* src; uint64_t** dst; size_t n; };
+static std::vector<YearBinsBlock> year_bins_blocks(const mcr_sizes& sz, const mcr_outputs* in, const mcr_year_bins* yin, mcr_outputs* o, mcr_year_bins* y) {
+    const size_t T = (size_t)sz.trajectory_len, ry = (size_t)sz.retirement_years;
+    const size_t cells = (size_t)yin->n_bins + 2, wcells = (size_t)yin->n_wr_bins + 2;
+    const bool hist = in->hist_bins && in->hist_n_bins > 0;
+    return {
+        {&in->counters, &o->counters, MCR_N_COUNTERS}, {&in->wr_obs_counts, &o->wr_obs_counts, ry}, {&in->ruin_year_bins, &o->ruin_year_bins, (size_t)sz.ruin_bins},
+        {&in->hist_bins, &o->hist_bins, hist ? (size_t)in->hist_n_bins : 0},
+        {&yin->trajectory_bins, &y->trajectory_bins, T * cells}, {&yin->real_trajectory_bins, &y->real_trajectory_bins, T * cells},
+        {&yin->wr_bins, &y->wr_bins, ry * wcells}, {&yin->final_success_bins, &y->final_success_bins, cells},
+    };
+}
+// Everything that can be checked on the host, before any device work
+static int check_year_bins_host(const mcr_params* p, const mcr_rng* rng, int32_t working_months, const mcr_outputs* out,
+                                const mcr_year_bins* yb, mcr_sizes* sz) {
+    int rc = check_rng(rng);
+    if (rc != MCR_OK) return rc;
+    if ((rc = query_sizes(p, working_months, sz)) != MCR_OK) return rc;
+    if ((rc = validate_params(p)) != MCR_OK) return rc;
+    if ((rc = check_year_bins(out, yb)) != MCR_OK) return rc;
+    if ((yb->trajectory_bins || yb->real_trajectory_bins || yb->final_success_bins) && (rc = check_edges_host("edges", yb->edges, yb->n_bins)) != MCR_OK) return rc;
+    if (yb->wr_bins && (rc = check_edges_host("wr_edges", yb->wr_edges, yb->n_wr_bins)) != MCR_OK) return rc;
+    if (out->hist_bins && out->hist_n_bins > 0 && (rc = check_edges_host("hist_edges", out->hist_edges, out->hist_n_bins)) != MCR_OK) return rc;
+    return MCR_OK;
+}
+static int run_year_bins_host_on(int device, const mcr_params* p, const mcr_rng* rng_in, uint32_t stream_id, uint64_t path_begin,
+                                 uint64_t n_paths, int32_t working_months, const mcr_outputs* out, const mcr_year_bins* yb) {
+    MCR_ENTER_DEVICE(device);
+    mcr_sizes sz;
+    int rc = check_year_bins_host(p, rng_in, working_months, out, yb, &sz);
+    if (rc != MCR_OK) return rc;
+    if (n_paths == 0) return MCR_OK;
+    mcr_outputs d = {};
+    mcr_year_bins dy = {};
+    dy.n_bins = yb->n_bins; dy.n_wr_bins = yb->n_wr_bins;
+    if (out->hist_bins && out->hist_n_bins > 0) d.hist_n_bins = out->hist_n_bins;
+    // plan: every device buffer is a slice of the leased context's block (256-byte aligned)
+    struct Buf { void** dev; void* host; size_t bytes, offset; bool download; };
+    std::vector<Buf> bufs;
+    size_t total = 0;
+    auto plan = [&](void** dev, const void* host, size_t bytes, bool down) {
+        if (!host || bytes == 0) return;
+        bufs.push_back({dev, const_cast<void*>(host), bytes, total, down});
+        total += (bytes + 255) & ~(size_t)255;
+    };
+    for (const YearBinsBlock& b : year_bins_blocks(sz, out, yb, &d, &dy)) plan((void**)b.dst, *b.src, b.n * sizeof(uint64_t), true);
+    if (d.hist_n_bins > 0) plan((void**)&d.hist_edges, out->hist_edges, (size_t)(d.hist_n_bins + 1) * sizeof(double), false);
+    if (yb->trajectory_bins || yb->real_trajectory_bins || yb->final_success_bins) plan((void**)&dy.edges, yb->edges, (size_t)(yb->n_bins + 1) * sizeof(double), false);
+    if (yb->wr_bins) plan((void**)&dy.wr_edges, yb->wr_edges, (size_t)(yb->n_wr_bins + 1) * sizeof(double), false);
+    mcr_rng rng = *rng_in;
+    uint32_t* d_seeds = nullptr;
+    plan((void**)&d_seeds, rng.path_seeds, (size_t)n_paths * sizeof(uint32_t), false);
+
+    HostCtxLease lease(device);
+    HostCtx* ctx = lease.ctx;
+    if (!ctx) return MCR_ERR_HIP;
+    hipError_t e = host_ctx_reserve(ctx, total);
+    if (e != hipSuccess) return hip_fail(e, "device allocation (yearly bins)");
+    for (Buf& b : bufs) {   // accumulated blocks start from the caller's current values
+        *b.dev = (char*)ctx->block + b.offset;
+        if (e == hipSuccess) e = hipMemcpyAsync(*b.dev, b.host, b.bytes, hipMemcpyHostToDevice, ctx->stream);
+    }
+    if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return hip_fail(e, "upload"); }
+    if (rng.path_seeds) rng.path_seeds = d_seeds;
+    rc = launch_year_bins(p, &rng, stream_id, path_begin, n_paths, working_months, &d, &dy, ctx->stream);
+    // the tables come back through a staging copy: the caller's stay untouched unless the whole call succeeds
+    std::vector<std::vector<unsigned char>> staged(bufs.size());
+    if (rc == MCR_OK)
+        for (size_t i = 0; i < bufs.size(); ++i) {
+            if (!bufs[i].download || e != hipSuccess) continue;
+            staged[i].resize(bufs[i].bytes);
+            e = hipMemcpyAsync(staged[i].data(), *bufs[i].dev, bufs[i].bytes, hipMemcpyDeviceToHost, ctx->stream);
+        }
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    if (rc != MCR_OK) return rc;
+    if (e != hipSuccess) return hip_fail(e, "download");
+    if (es != hipSuccess) return hip_fail(es, "path_kernel execution (yearly bins)");
+    for (size_t i = 0; i < bufs.size(); ++i)
+        if (!staged[i].empty()) std::memcpy(bufs[i].host, staged[i].data(), bufs[i].bytes);
+    return MCR_OK;
+}
+
+// Sharded over a device list like run_batch_host_multi: contiguous global path ranges, one host thread per entry, every
+// integer block summed on the host.
+static int run_year_bins_host_multi(const int32_t* devices, int32_t n_devices, const mcr_params* p, const mcr_rng* rng_in, uint32_t stream_id,
+                                    uint64_t path_begin, uint64_t n_paths, int32_t working_months, const mcr_outputs* out, const mcr_year_bins* yb) {
+    if (!rng_in) { set_error("null rng"); return MCR_ERR_INVALID_ARG; }
+    mcr_sizes sz;
+    int rc = check_year_bins_host(p, rng_in, working_months, out, yb, &sz);
+    if (rc != MCR_OK) return rc;
+    std::vector<int> devs;
+    if (!devices || n_devices <= 0) {
+        const int n = mcr_device_count();
+        if (n <= 0) { set_error("no usable HIP device (the engine has no CPU fallback)"); return MCR_ERR_NO_DEVICE; }
+        for (int i = 0; i < n; ++i) devs.push_back(i);
+    } else {
+        devs.assign(devices, devices + n_devices);
+    }
+    const size_t W = devs.size();
+    if (W == 1) return run_year_bins_host_on(devs[0], p, rng_in, stream_id, path_begin, n_paths, working_months, out, yb);
+    const uint64_t per = (n_paths + W - 1) / W;
+    struct Shard {
+        int rc = MCR_OK;
+        char err[512] = "";
+        bool ran = false;
+        mcr_outputs o;
+        mcr_year_bins y;
+        std::vector<std::vector<uint64_t>> mem;
+    };
+    std::vector<Shard> shards(W);
+    std::vector<std::thread> threads;
+    for (size_t w = 0; w < W; ++w) {
+        const uint64_t begin = std::min<uint64_t>(w * per, n_paths);
+        const uint64_t count = std::min<uint64_t>(per, n_paths - begin);
+        if (count == 0) continue;
+        Shard& S = shards[w];
+        S.ran = true;
+        S.o = *out; S.y = *yb;
+        for (const YearBinsBlock& b : year_bins_blocks(sz, out, yb, &S.o, &S.y)) {   // zeroed blocks of the shard's own
+            S.mem.emplace_back(*b.src && b.n ? b.n : 0, 0);
+            *b.dst = S.mem.back().empty() ? nullptr : S.mem.back().data();
+        }
+        threads.emplace_back([&, w, begin, count]() {
+            Shard& T = shards[w];
+            mcr_rng r = *rng_in;
+            if (r.path_seeds) r.path_seeds += begin;
+            T.rc = run_year_bins_host_on(devs[w], p, &r, stream_id, path_begin + begin, count, working_months, &T.o, &T.y);
+            if (T.rc != MCR_OK) std::snprintf(T.err, sizeof(T.err), "device %d: %s", devs[w], mcr_last_error());
+        });
+    }
+    for (std::thread& t : threads) t.join();
+    for (const Shard& S : shards)
+        if (S.rc != MCR_OK) { set_error("%s", S.err); return S.rc; }
+    for (Shard& S : shards) {
+        if (!S.ran) continue;
+        mcr_outputs o2; mcr_year_bins y2;
+        const std::vector<YearBinsBlock> blocks = year_bins_blocks(sz, out, yb, &o2, &y2);
+        for (size_t i = 0; i < blocks.size(); ++i)
+            for (size_t k = 0; k < S.mem[i].size(); ++k) (*blocks[i].src)[k] += S.mem[i][k];
+    }
+    return MCR_OK;
+}
+
+int mcr_run_year_bins_host_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                               int32_t working_months, const mcr_outputs* out, const mcr_year_bins* yb, int device) {
+    if (device == MCR_DEVICE_ALL) return run_year_bins_host_multi(nullptr, 0, p, rng, stream_id, path_begin, n_paths, working_months, out, yb);
+    return run_year_bins_host_on(device, p, rng, stream_id, path_begin, n_paths, working_months, out, yb);
+}
+
+int mcr_run_year_bins_multi_host_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                                     int32_t working_months, const mcr_outputs* out, const mcr_year_bins* yb, const int32_t* devices,
+                                     int32_t n_devices) {
+    return run_year_bins_host_multi(devices, n_devices, p, rng, stream_id, path_begin, n_paths, working_months, out, yb);
 }
 
 int mcr_validate_params(const mcr_params* p) { return validate_params(p); }

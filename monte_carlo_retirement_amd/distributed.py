@@ -262,6 +262,39 @@ def run_sharded_bands(params, rng_or_seed, stream_id: int, n_total: int, working
     return out
 
 
+def run_sharded_year_bins(params, rng_or_seed, stream_id: int, n_total: int, working_months: int, edges=None, wr_edges=None):
+    """The fan chart of ``n_total`` paths on N GPUs with no trajectory slab: every rank runs the yearly-bins kernel over its
+    shard of the global path range (``engine.YearBinsBatch``; nothing is kept per path) and the exchange is ONE sum
+    all-reduce of the integer vector ``[success, paths | wr_obs[ry] | ruin_bins[ry+2] | trajectory_bins[T][n+2] |
+    real_trajectory_bins[T][n+2] | wr_bins[ry][nw+2] | final_success_bins[n+2]]``.  Returns the same dict on every rank:
+    the named blocks (numpy int64), ``vector`` (the whole block), ``edges`` / ``wr_edges``, ``counts``, ``shard`` and
+    ``exchange`` (the collectives that ran); quantile brackets come from ``aggregation.bands_from_bins``."""
+    import torch
+    import torch.distributed as dist
+
+    from . import engine as E
+
+    rank, world = (dist.get_rank(), dist.get_world_size()) if is_active() else (0, 1)
+    begin, count = shard_range(int(n_total), rank, world)
+    batch = E.YearBinsBatch(params, working_months, edges, wr_edges, device=torch.cuda.current_device())
+    if count > 0:
+        batch.launch(rng_or_seed, stream_id, begin, count)
+    vec = batch.reduce_vec
+    if world > 1:
+        if dist.get_backend() != "nccl":
+            vec = vec.cpu()
+        all_reduce_sum_(vec)
+    host = vec.cpu().numpy()
+    res = E.split_year_bins(host, batch.sizes, batch.n_bins, batch.n_wr_bins)
+    ry = batch.sizes.retirement_years
+    res.update({
+        "vector": host, "edges": batch.edges, "wr_edges": batch.wr_edges, "shard": (begin, count),
+        "counts": unpack_counts(host[:E.N.MCR_N_COUNTERS + ry + batch.sizes.ruin_bins], ry),
+        "exchange": "none (1 GPU)" if world == 1 else f"1 all-reduce(sum) of {host.shape[0]} int64 words",
+    })
+    return res
+
+
 def run_sharded_histogram(params, rng_or_seed, stream_id: int, n_total: int, working_months: int, n_bins: int = 100,
                           value_range: Optional[Tuple[float, float]] = None, hist_edges=None):
     """BASELINE configs[3] on N GPUs (success counts + histogram of successful final balances, no trajectories).

@@ -17,7 +17,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from . import _native as N
-from ._native import McrOutputs, McrParams, McrRng, McrSizes
+from ._native import McrOutputs, McrParams, McrRng, McrSizes, McrYearBins
 
 SUMMARY_FIELDS = (
     "start_balance",
@@ -202,6 +202,179 @@ def eval_helper_host(which: int, params: Optional[McrParams], rows, device: int 
     )
     N.check(rc, "mcr_eval_helper_host")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Yearly bins: the fan chart without a trajectory slab (mcr_run_year_bins_rng)
+# ---------------------------------------------------------------------------------------------
+def year_edge_array(edges, what: str = "edges") -> np.ndarray:
+    """Bin edges of a yearly-bins table as the contiguous float64 array the ABI wants; ``ValueError`` unless they are
+    finite, ascending (equal neighbours allowed: zero-width bins) and 2..MCR_MAX_YEAR_BINS+1 long."""
+    e = np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1))
+    if not (2 <= e.shape[0] <= N.MCR_MAX_YEAR_BINS + 1):
+        raise ValueError(f"{what}: need 2..{N.MCR_MAX_YEAR_BINS + 1} edges, got {e.shape[0]}")
+    if not np.all(np.isfinite(e)) or np.any(e[1:] < e[:-1]):
+        raise ValueError(f"{what} must be finite and increase monotonically")
+    return e
+
+
+def default_year_edges(n_bins: int = 256, lo: float = 1.0, hi: float = 1e12) -> np.ndarray:
+    """Edges for balances in dollars: bin 0 = ``[0, lo)`` holds the exact zeros of failed paths (and the dust below one
+    dollar) on its own, the other ``n_bins - 1`` bins are log-spaced from ``lo`` to ``hi`` — a constant RELATIVE width of
+    ``(hi / lo) ** (1 / (n_bins - 1))``: 11.4 % at 256 bins, 55 % at 64."""
+    n_bins = int(n_bins)
+    if not (2 <= n_bins <= N.MCR_MAX_YEAR_BINS):
+        raise ValueError(f"default_year_edges: n_bins must be 2..{N.MCR_MAX_YEAR_BINS}, got {n_bins}")
+    if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 < lo < hi):
+        raise ValueError("default_year_edges: need 0 < lo < hi, both finite")
+    return np.concatenate(([0.0], np.geomspace(float(lo), float(hi), n_bins)))
+
+
+def default_wr_edges(n_bins: int = 256, hi: float = 100.0) -> np.ndarray:
+    """Edges for yearly withdrawal rates in percent of the start balance: ``n_bins`` equal bins over ``[0, hi]``
+    (0.39 points wide at 256 bins); rates above ``hi`` land in the `above` cell."""
+    n_bins = int(n_bins)
+    if not (1 <= n_bins <= N.MCR_MAX_YEAR_BINS):
+        raise ValueError(f"default_wr_edges: n_bins must be 1..{N.MCR_MAX_YEAR_BINS}, got {n_bins}")
+    if not (np.isfinite(hi) and hi > 0.0):
+        raise ValueError("default_wr_edges: need a finite hi > 0")
+    return np.linspace(0.0, float(hi), n_bins + 1)
+
+
+#: (name, rows, cells) of the blocks of a yearly-bins result, in the order of the one vector; T / ry / nb / nw filled in
+def _year_bins_layout(sz: McrSizes, n_bins: int, n_wr_bins: int):
+    T, ry = sz.trajectory_len, sz.retirement_years
+    return (
+        ("counters", 1, N.MCR_N_COUNTERS), ("wr_obs_counts", 1, ry), ("ruin_year_bins", 1, sz.ruin_bins),
+        ("trajectory_bins", T, n_bins + 2), ("real_trajectory_bins", T, n_bins + 2), ("wr_bins", ry, n_wr_bins + 2),
+        ("final_success_bins", 1, n_bins + 2),
+    )
+
+
+def split_year_bins(vec, sz: McrSizes, n_bins: int, n_wr_bins: int) -> dict:
+    """Named views of the one vector ``[counters | wr_obs | ruin | trajectory | real | wr | final_success]`` (numpy
+    array or torch tensor): tables ``[rows, cells]``, the others flat."""
+    out, at = {}, 0
+    for name, rows, cells in _year_bins_layout(sz, n_bins, n_wr_bins):
+        v = vec[at:at + rows * cells]
+        out[name] = v.reshape(rows, cells) if name.endswith("_bins") and name not in ("ruin_year_bins", "final_success_bins") else v
+        at += rows * cells
+    assert at == vec.shape[0]
+    return out
+
+
+class YearBinsBatch:
+    """The integer block of a yearly-bins run resident in HBM: ONE contiguous int64 device vector ``reduce_vec`` =
+    ``[counters | wr_obs_counts | ruin_year_bins | trajectory_bins | real_trajectory_bins | wr_bins | final_success_bins]``
+    with named views into it, accumulated into by every :meth:`launch` (``mcr_run_year_bins_rng`` on torch's current
+    stream).  Nothing is kept per path: the vector is all a multi-GPU caller has to sum."""
+
+    def __init__(self, params: McrParams, working_months: int, edges=None, wr_edges=None, device: int = 0):
+        import torch
+
+        N.require_device()
+        self.torch = torch
+        self.params = params
+        self.working_months = int(working_months)
+        self.device = int(device)
+        self.sizes = query_sizes(params, working_months)
+        self.edges = year_edge_array(default_year_edges() if edges is None else edges)
+        self.wr_edges = year_edge_array(default_wr_edges() if wr_edges is None else wr_edges, "wr_edges")
+        self.n_bins, self.n_wr_bins = self.edges.shape[0] - 1, self.wr_edges.shape[0] - 1
+        dev = torch.device("cuda", self.device)
+        n_words = sum(rows * cells for _, rows, cells in _year_bins_layout(self.sizes, self.n_bins, self.n_wr_bins))
+        self.reduce_vec = torch.zeros(n_words, dtype=torch.int64, device=dev)
+        for name, view in split_year_bins(self.reduce_vec, self.sizes, self.n_bins, self.n_wr_bins).items():
+            setattr(self, name, view)
+        self._edges_dev = torch.as_tensor(self.edges, device=dev)
+        self._wr_edges_dev = torch.as_tensor(self.wr_edges, device=dev)
+        o = McrOutputs()
+        o.counters = self.counters.data_ptr()
+        o.wr_obs_counts = self.wr_obs_counts.data_ptr()
+        o.ruin_year_bins = self.ruin_year_bins.data_ptr()
+        y = McrYearBins()
+        y.edges, y.n_bins = self._edges_dev.data_ptr(), self.n_bins
+        y.wr_edges, y.n_wr_bins = self._wr_edges_dev.data_ptr(), self.n_wr_bins
+        y.trajectory_bins = self.trajectory_bins.data_ptr()
+        y.real_trajectory_bins = self.real_trajectory_bins.data_ptr()
+        y.wr_bins = self.wr_bins.data_ptr()
+        y.final_success_bins = self.final_success_bins.data_ptr()
+        self._out, self._yb = o, y
+        self._lib = N.load_library()
+
+    def zero(self) -> None:
+        self.reduce_vec.zero_()
+
+    def launch(self, seed, stream_id: int, path_begin: int, n_paths: int) -> None:
+        """Enqueue one launch over global paths ``[path_begin, path_begin + n_paths)`` on the current stream; the tables
+        accumulate.  ``seed``: int (Philox key) or an ``McrRng`` descriptor."""
+        stream = self.torch.cuda.current_stream(self.device).cuda_stream
+        rng = _as_rng(seed)
+        rc = self._lib.mcr_run_year_bins_rng(
+            C.byref(self.params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), self.working_months,
+            C.byref(self._out), C.byref(self._yb), self.device, C.c_void_p(stream),
+        )
+        N.check(rc, "mcr_run_year_bins_rng")
+
+    def host(self) -> Dict[str, np.ndarray]:
+        """The block on the host (synchronises): named numpy arrays, plus the edges."""
+        res = split_year_bins(self.reduce_vec.cpu().numpy(), self.sizes, self.n_bins, self.n_wr_bins)
+        res["edges"], res["wr_edges"] = self.edges, self.wr_edges
+        return res
+
+
+def run_year_bins_host(
+    params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
+    edges=None, wr_edges=None, device: int = 0, devices: Optional[Sequence[int]] = None,
+    path_seeds: Optional[np.ndarray] = None, into: Optional[Dict[str, np.ndarray]] = None,
+) -> Dict[str, np.ndarray]:
+    """Yearly bins of paths ``[path_begin, path_begin + n_paths)`` through host buffers (``mcr_run_year_bins_host_rng``;
+    ``devices``: ``mcr_run_year_bins_multi_host_rng``).  Returns uint64 arrays ``counters`` ``[2]``, ``wr_obs_counts``
+    ``[ry]``, ``ruin_year_bins`` ``[ry+2]``, ``trajectory_bins`` / ``real_trajectory_bins`` ``[T, n_bins+2]``, ``wr_bins``
+    ``[ry, n_wr_bins+2]``, ``final_success_bins`` ``[n_bins+2]`` and the two edge arrays.  ``into``: a previous result to
+    accumulate into (same edges).  There are no injected shocks on this route: the entry points take none."""
+    lib = N.load_library()
+    N.require_device()
+    sz = query_sizes(params, working_months)
+    e = year_edge_array(default_year_edges() if edges is None else edges)
+    we = year_edge_array(default_wr_edges() if wr_edges is None else wr_edges, "wr_edges")
+    nb, nw = e.shape[0] - 1, we.shape[0] - 1
+    if into is not None:
+        res = into
+        if not (np.array_equal(res["edges"], e) and np.array_equal(res["wr_edges"], we)):
+            raise ValueError("`into` was binned on other edges")
+    else:
+        res = {name: np.zeros((rows, cells) if rows > 1 or name in ("trajectory_bins", "real_trajectory_bins", "wr_bins") else cells,
+                              dtype=np.uint64)
+               for name, rows, cells in _year_bins_layout(sz, nb, nw)}
+        res["edges"], res["wr_edges"] = e, we
+    o = McrOutputs()
+    o.counters = res["counters"].ctypes.data
+    o.wr_obs_counts = res["wr_obs_counts"].ctypes.data
+    o.ruin_year_bins = res["ruin_year_bins"].ctypes.data
+    y = McrYearBins()
+    y.edges, y.n_bins, y.wr_edges, y.n_wr_bins = e.ctypes.data, nb, we.ctypes.data, nw
+    for name in ("trajectory_bins", "real_trajectory_bins", "wr_bins", "final_success_bins"):
+        setattr(y, name, res[name].ctypes.data)
+    rng = _as_rng(seed)
+    seeds_arr = None
+    if path_seeds is not None:
+        seeds_arr = np.ascontiguousarray(path_seeds, dtype=np.uint32)
+        if seeds_arr.shape != (int(n_paths),):
+            raise ValueError("path_seeds must have one uint32 per path")
+        rng.path_seeds = seeds_arr.ctypes.data
+    if devices is not None:
+        devs = (C.c_int32 * len(devices))(*[int(d) for d in devices])
+        rc = lib.mcr_run_year_bins_multi_host_rng(
+            C.byref(params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), int(working_months),
+            C.byref(o), C.byref(y), devs, len(devices))
+        N.check(rc, "mcr_run_year_bins_multi_host_rng")
+        return res
+    rc = lib.mcr_run_year_bins_host_rng(
+        C.byref(params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), int(working_months),
+        C.byref(o), C.byref(y), int(device))
+    N.check(rc, "mcr_run_year_bins_host_rng")
+    return res
 
 
 # ---------------------------------------------------------------------------------------------

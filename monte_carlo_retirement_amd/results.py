@@ -272,6 +272,126 @@ def compact_result(config: Config, simulator: RetirementMonteCarloSimulator, req
 
 
 # ---------------------------------------------------------------------------------------------------
+# any number of paths: the document from yearly bins (no per-path memory at all)
+# ---------------------------------------------------------------------------------------------------
+def _bracket_payload(lo: np.ndarray, hi: np.ndarray, qs, digits: int) -> dict:
+    """`lo` / `hi` of `aggregation.bands_from_bins` per percentile key; an infinite side (the value lies outside the
+    edges) and an empty row are None."""
+    def col(a, j):
+        return [round(float(v), digits) if math.isfinite(v) else None for v in a[:, j]]
+    return {"lo": {_pct_key(q): col(lo, j) for j, q in enumerate(qs)}, "hi": {_pct_key(q): col(hi, j) for j, q in enumerate(qs)}}
+
+
+def streamed_result(config: Config, simulator: RetirementMonteCarloSimulator, required_w_months: int,
+                    search_curve: Optional[List[dict]] = None, num_simulations: Optional[int] = None,
+                    edges=None, wr_edges=None) -> dict:
+    """The keys of ``compact_result`` for ANY number of paths: the path kernel bins every yearly sample itself
+    (``mcr_run_year_bins_rng``), so nothing is kept per path — the document comes out of a few hundred KB of integers, and
+    under a process group out of ONE all-reduce (``distributed.run_sharded_year_bins``).
+
+    EXACT (equal to ``compact_result``): success probability, ``ruin_histogram``, the withdrawal-rate observation counts,
+    the five sample paths (each picked global path is simulated again as a one-path full-output launch: both random
+    streams address a path by its global index), ``reference_lines``.
+    BRACKETED (known to within one bin of ``edges`` / ``wr_edges``): the trajectory, real-trajectory and withdrawal-rate
+    bands, the median start balance (row ``num_working_years`` of the trajectory table), the final-balance percentiles
+    (row T - 1) and the median final balance of successful paths (``final_success_bins``).  The document carries the
+    rank-interpolated estimate of each; ``band_brackets`` carries the ``lo`` / ``hi`` that contain the exact value.
+    NOT AVAILABLE: ``summary.swr`` (the first-year withdrawal-rate median is taken over another cohort than ``wr_bins[0]``:
+    it leaves out paths whose start balance is <= 1e-6 and includes paths that fail in year 0) — None, and named in
+    ``not_available``; a median whose order statistic falls outside the caller's edges is None and named there too.
+    ``histogram_binned`` is ``final_success_bins`` on ``edges`` (with its below / above counts)."""
+    wm = int(required_w_months)
+    n = int(config.num_simulations_main if num_simulations is None else num_simulations)
+    if n <= 0:
+        raise ValueError(f"Simulation for '{config.Nickname}' yielded no results.")
+    params = simulator._current_params()
+    rng = simulator._batch_rng(n)
+    if D.is_active():
+        yb = D.run_sharded_year_bins(params, rng, simulator._stream_id, n, wm, edges, wr_edges)
+    else:
+        import torch
+
+        with torch.cuda.device(simulator._local_device()):
+            yb = D.run_sharded_year_bins(params, rng, simulator._stream_id, n, wm, edges, wr_edges)
+    e, we = yb["edges"], yb["wr_edges"]
+    ok_count = int(yb["counters"][0])
+    tq, wq = list(A.TRAJECTORY_QUANTILES), list(A.WR_QUANTILES)
+    t_lo, t_hi, t_est = A.bands_from_bins(yb["trajectory_bins"], e, tq)
+    r_lo, r_hi, r_est = A.bands_from_bins(yb["real_trajectory_bins"], e, tq)
+    w_lo, w_hi, w_est = A.bands_from_bins(yb["wr_bins"], we, wq)
+    T = yb["trajectory_bins"].shape[0]
+    row_start = wm // MONTHS_PER_YEAR + (1 if wm % MONTHS_PER_YEAR else 0)   # the sample at retirement: row num_working_years
+    s_lo, s_hi, s_est = A.bands_from_bins(yb["trajectory_bins"][row_start], e, [0.50])
+    f_lo, f_hi, f_est = A.bands_from_bins(yb["trajectory_bins"][T - 1], e, FINAL_BALANCE_PERCENTILES)
+    m_lo, m_hi, m_est = A.bands_from_bins(yb["final_success_bins"], e, [0.50])
+    # the five sample paths, exactly: one-path full-output launches at the picked global indices
+    picked = simulator._sample_columns(n)
+    samples = real_samples = None
+    if picked is not None:
+        samples, real_samples = [], []
+        for g in picked:
+            one = E.run_batch_host(params, rng, simulator._stream_id, int(g), 1, wm, want_summary=False, want_bins=False,
+                                   device=simulator._local_device())
+            samples.append(one["trajectory"][:, 0].tolist())
+            real_samples.append(one["real_trajectory"][:, 0].tolist())
+    years = trajectory_time_points(wm, config.retirement_years)
+    qcols = pd.Index(tq, dtype="float64")
+    ruin_bins = yb["ruin_year_bins"]
+
+    # an estimate is NaN where the order statistic lies outside the edges (or the row is empty): None in the document, and the
+    # field is named in not_available
+    not_available = ["summary.swr"]
+
+    def value(a, field):
+        if math.isfinite(a[0, 0]):
+            return round(float(a[0, 0]), 2)
+        not_available.append(field)
+        return None
+
+    median_start = value(s_est, "summary.median_start_balance")
+    median_final_ok = value(m_est, "summary.median_final_balance_successful") if ok_count else 0.0
+    summary = _summary_block(
+        config, wm, bool(search_curve), float(np.float64(ok_count) / np.float64(n) * 100.0), 0.0, 0.0, float("nan"),
+        {_pct_key(q): (round(max(0.0, float(v)), 2) if math.isfinite(v) else None)
+         for q, v in zip(FINAL_BALANCE_PERCENTILES, f_est[0])})
+    summary["median_start_balance"], summary["median_final_balance_successful"] = median_start, median_final_ok
+    fin = yb["final_success_bins"]
+    doc = {
+        "scenario": config.Nickname,
+        "summary": summary,
+        "trajectory": _band_payload(pd.DataFrame(t_est, columns=qcols), samples, years),
+        "trajectory_real": _band_payload(pd.DataFrame(r_est, columns=qcols), real_samples, years),
+        "withdrawal_rate": _withdrawal_rate_payload(
+            pd.DataFrame(w_est, columns=pd.Index(wq, dtype="float64")), [int(v) for v in yb["wr_obs_counts"].tolist()], wm, n),
+        "search_curve": None,
+        "ruin_histogram": {"years_to_ruin": [], "failure_count": int(ruin_bins.sum()), "total_paths": n,
+                           "bins": [int(v) for v in ruin_bins.tolist()]},
+        "histogram": {"final_balances": [], "start_balances": [], "success_flags": []},
+        "histogram_binned": {"edges": [float(x) for x in e], "success_counts": [int(b) for b in fin[1:-1].tolist()],
+                             "below": int(fin[0]), "above": int(fin[-1]), "successful_paths": ok_count, "total_paths": n},
+        "reference_lines": _reference_lines(config, wm),
+        "band_brackets": {
+            "trajectory": _bracket_payload(t_lo, t_hi, tq, 2),
+            "trajectory_real": _bracket_payload(r_lo, r_hi, tq, 2),
+            "withdrawal_rate": _bracket_payload(w_lo, w_hi, wq, 3),
+            "median_start_balance": _bracket_payload(s_lo, s_hi, [0.50], 2),
+            "final_balance_percentiles": _bracket_payload(f_lo, f_hi, FINAL_BALANCE_PERCENTILES, 2),
+            "median_final_balance_successful": _bracket_payload(m_lo, m_hi, [0.50], 2),
+        },
+        "not_available": not_available,
+        "exchange": yb["exchange"],
+    }
+    for fam in ("trajectory", "trajectory_real"):       # an estimate outside the edges is None, like its bracket side
+        cols = doc[fam]["percentiles"]
+        for key in cols:
+            cols[key] = [v if math.isfinite(v) else None for v in cols[key]]
+    if search_curve:
+        doc["search_curve"] = {"points": dedupe_search_curve(search_curve), "target_probability": config.target_probability,
+                               "selected_working_months": wm}
+    return doc
+
+
+# ---------------------------------------------------------------------------------------------------
 # the run flow (search -> final run -> document) with the reference's progress events
 # ---------------------------------------------------------------------------------------------------
 def run_scenario(config: Config, working_months_override: Optional[int] = None,
