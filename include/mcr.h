@@ -190,6 +190,11 @@ int mcr_release_cached(int device);
 /* Shapes for (params, working_months).  Returns MCR_ERR_INVALID_ARG for working_months<0,
  * retirement_years<=0, n_streams<0. */
 int mcr_query_sizes(const mcr_params* p, int32_t working_months, mcr_sizes* out);
+/* The growth form a whole-path count-only launch of (params, working_months) on the engine's own stream runs (DESIGN.md,
+ * "growth forms"): bit 0 = every argument of the month's exps lies in the narrow window, bit 1 = rho is 0; masks 0, 1 and 3.
+ * MCR_K1_GROWTH_FORM in the environment forces a lower mask, as at a launch; a mask the parameters do not qualify for
+ * returns MCR_ERR_INVALID_ARG. */
+int mcr_k1_growth_form(const mcr_params* p, int32_t working_months, int32_t* mask);
 /* Range check of a parameter block — what the reference's pydantic Config enforces (backend/config.py:56-99)
  * and the kernel relies on: amounts finite and >= 0, rates / allocation / stream tax rates in [0, 1], rho in
  * [-1, 1], finite log-parameters with sigma >= 0 and |mu|/12 + 40 sigma/sqrt(12) < 700 (domain of the kernel's
@@ -424,6 +429,9 @@ int mcr_draw_shocks_host(uint64_t seed, uint32_t stream_id, uint64_t path_begin,
  * forms above (the reference's denominator clamps, simulation.py:227,:307-310, can bind there), and so do these two helpers. */
 #define MCR_HELPER_WITHDRAW_MONTH 18   /* :726-790  in[5]=(b1,cb1,b2,cb2,need) out[6]=(b1,cb1,b2,cb2,gross withdrawn,net cash) */
 #define MCR_HELPER_REBALANCE_MONTH 19  /* :274-359  in[4]=(b1,cb1,b2,cb2) out[4] */
+/* exp's path form as the general kernels run it and in its narrow-window form (csrc/mcr_math.h: fexp<., NARROW>, for
+ * k = rint(x 512 / ln 2) in [-256, 255]; the two agree bit for bit there — tests/test_gpu_growth_forms.py) */
+#define MCR_HELPER_MATH_EXP_FORMS 20   /* in[1]=(x)  out[2]=(general form, narrow form) */
 /* Evaluates helper `which` ON THE DEVICE for n rows (host buffers, row-major). */
 int mcr_eval_helper_host(int which, const mcr_params* p, const double* in, double* out,
                          int64_t n, int device);

@@ -49,6 +49,7 @@ MCR_HELPER_MATH_NEG2LOG_PATH = 16
 MCR_HELPER_MATH_SINCOS_PATH = 17
 MCR_HELPER_WITHDRAW_MONTH = 18
 MCR_HELPER_REBALANCE_MONTH = 19
+MCR_HELPER_MATH_EXP_FORMS = 20
 _HELPER_ARITY = {  # which -> (n_in, n_out)
     MCR_HELPER_WITHDRAW: (5, 4),
     MCR_HELPER_NLV: (4, 1),
@@ -70,6 +71,7 @@ _HELPER_ARITY = {  # which -> (n_in, n_out)
     MCR_HELPER_MATH_SINCOS_PATH: (1, 2),
     MCR_HELPER_WITHDRAW_MONTH: (5, 6),
     MCR_HELPER_REBALANCE_MONTH: (4, 4),
+    MCR_HELPER_MATH_EXP_FORMS: (1, 2),
 }
 
 
@@ -240,6 +242,7 @@ ABI_SYMBOLS = (
     "mcr_last_error",
     "mcr_query_sizes",
     "mcr_stream_start_month_index",
+    "mcr_k1_growth_form",
     "mcr_run_batch",
     "mcr_run_batch_host",
     "mcr_draw_shocks_host",
@@ -294,6 +297,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.mcr_query_sizes.argtypes = [P(McrParams), C.c_int32, P(McrSizes)]
     lib.mcr_stream_start_month_index.restype = C.c_int32
     lib.mcr_stream_start_month_index.argtypes = [C.c_double, C.c_int32, C.c_double]
+    lib.mcr_k1_growth_form.restype = C.c_int
+    lib.mcr_k1_growth_form.argtypes = [P(McrParams), C.c_int32, P(C.c_int32)]
     lib.mcr_run_batch.restype = C.c_int
     lib.mcr_run_batch.argtypes = [
         P(McrParams), C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32,

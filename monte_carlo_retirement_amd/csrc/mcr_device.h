@@ -291,7 +291,13 @@ struct PairCarry { uint32_t w2, w3; };
 // straddling wave runs the form twice and the second pass overwrites the first); an output added here must be
 // overwritten the same way.
 enum { kGenPlain = 0, kGenUniform = 1, kGenGeneral = 2 };
-template <int HALF, int COLS, int GEN>
+// GF: the launch's GROWTH FORM, a two-bit mask of what its parameters make unnecessary (chosen on the host, mcr_hip.hip:
+// growth_form_of; every value is bit for bit the general form's wherever it may be used).
+//   kGrowthNarrowExp: every argument of exp has k in fexp's narrow window -> fexp<., NARROW> on a CENTRED table (mcr_math.h)
+//   kGrowthRhoZero:   rho = 0 -> binf_rho is an exact zero and x_inf's first term, fma(+-0 r0, t0, y) = y, is dropped (only the
+//                     sign of a zero sum can differ, and exp maps both zeros to 1)
+enum { kGrowthNarrowExp = 1, kGrowthRhoZero = 2 };
+template <int HALF, int COLS, int GEN, int GF = 0>
 __device__ __forceinline__ void growth_rows2_form(const DevParams& P, const MathRegs& M, uint64_t seed, uint32_t stream_id, uint64_t path,
                                                   const PhiloxPath& Q, uint32_t t, const double* tab, double* stage, PairCarry& C) {
     auto draw = [&](uint32_t block, uint32_t (&x)[4]) {
@@ -333,11 +339,13 @@ __device__ __forceinline__ void growth_rows2_form(const DevParams& P, const Math
     for (int r = 0; r < 2; ++r) {
         const int je = 3 * r, ji = 3 * r + 1, jp = 3 * r + 2;
         const double x_eq = fma_vvs(P.b1 * rad[je >> 1], trig[je], P.a1);
-        const double x_inf = __builtin_fma(P.binf_rho * rad[je >> 1], trig[je], fma_vvs(P.binf_rho_c * rad[ji >> 1], trig[ji], P.ainf));
+        const double x_inf = (GF & kGrowthRhoZero) ? fma_vvs(P.binf_rho_c * rad[ji >> 1], trig[ji], P.ainf)
+                                                   : __builtin_fma(P.binf_rho * rad[je >> 1], trig[je], fma_vvs(P.binf_rho_c * rad[ji >> 1], trig[ji], P.ainf));
         const double x_prem = fma_vvs(P.bprem * rad[jp >> 1], trig[jp], P.aprem);
-        const double g1 = fexp<true>(x_eq, tab, M);
-        const double ginf = fexp<true>(x_inf, tab, M);
-        const double gprem = fexp<true>(x_prem, tab, M);
+        constexpr bool kNarrow = (GF & kGrowthNarrowExp) != 0;
+        const double g1 = fexp<true, kNarrow>(x_eq, tab, M);
+        const double ginf = fexp<true, kNarrow>(x_inf, tab, M);
+        const double gprem = fexp<true, kNarrow>(x_prem, tab, M);
         stage[(3 * r + 0) * COLS] = g1;
         stage[(3 * r + 1) * COLS] = ginf;
         stage[(3 * r + 2) * COLS] = ginf * gprem;                               // :532
@@ -350,20 +358,21 @@ __device__ __forceinline__ void growth_rows2_form(const DevParams& P, const Math
 // pass staged and carried with the right words (HALF 0 carries only words it draws, HALF 1 only reads the carry).
 // Otherwise the plain generator: in the variants with per-path outputs or an annual-gains tax the second form's registers
 // cost scratch, and those launches are not bound by the generator's issue slots.
-template <int HALF, int COLS = kBlock, bool PER_PATH = false>
+template <int HALF, int COLS = kBlock, bool PER_PATH = false, int GF = 0>
 __device__ __forceinline__ void growth_rows2(const DevParams& P, const MathRegs& M, uint64_t seed, uint32_t stream_id, uint64_t path,
                                              const PhiloxPath& Q, uint32_t t, const double* tab, double* stage, PairCarry& C) {
+    static_assert(GF == 0 || PER_PATH, "the growth forms exist for the issue-bound per-path launches");
     if (!PER_PATH) {
         growth_rows2_form<HALF, COLS, kGenPlain>(P, M, seed, stream_id, path, Q, t, tab, stage, C);
         return;
     }
-    growth_rows2_form<HALF, COLS, kGenUniform>(P, M, seed, stream_id, path, Q, t, tab, stage, C);
+    growth_rows2_form<HALF, COLS, kGenUniform, GF>(P, M, seed, stream_id, path, Q, t, tab, stage, C);
     if (__builtin_expect(!Q.hi_uniform, 0)) {
         // the barrier keeps the general form a branch (left alone the compiler computes both forms and selects) and its
         // inputs opaque (no values of the first pass kept live into it: both forms then fit the same registers)
         PairCarry C2 = C;
         asm volatile("" : "+v"(C2.w2), "+v"(C2.w3));
-        growth_rows2_form<HALF, COLS, kGenGeneral>(P, M, seed, stream_id, path, Q, t, tab, stage, C2);
+        growth_rows2_form<HALF, COLS, kGenGeneral, GF>(P, M, seed, stream_id, path, Q, t, tab, stage, C2);
         C = C2;
     }
 }

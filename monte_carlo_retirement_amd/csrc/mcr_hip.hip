@@ -250,7 +250,7 @@ constexpr bool kUniformFixups = false;
 #else
 constexpr bool kUniformFixups = true;
 #endif
-template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault>
+template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault, int GF = 0>
 __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
                                                          const DevParams* __restrict__ cand_params) {
     // MODE 3 (mcr_run_year_bins_rng): YEARLY BINS.  The arithmetic of MODE 2, but wherever that variant stores a yearly sample
@@ -284,6 +284,12 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MC
     static_assert(TAXED >= 0 && TAXED <= 3, "TAXED is a two-bit mask");
     constexpr bool T1 = (TAXED & 1) != 0, T2 = (TAXED & 2) != 0, TANY = TAXED != 0;
     static_assert(!EXACT || XS || kExactMonthDefault, "the exact month is instantiated for the generic variants only");
+    // GF: the launch's growth form (mcr_device.h: kGrowthNarrowExp | kGrowthRhoZero; masks 0, 1 and 3), for the issue-bound
+    // whole-path count-only launches, plain or time-sliced.  Last, with a default: the names of the mask-0 variants are a prefix
+    // of the others'.  A kernel with kGrowthNarrowExp loads the exp2 table CENTRED: growth_rows2 is its only reader there.
+    static_assert(GF == 0 || GF == kGrowthNarrowExp || GF == (kGrowthNarrowExp | kGrowthRhoZero), "growth forms: masks 0, 1 and 3");
+    static_assert(GF == 0 || (MODE == 0 && RNG == (int)MCR_RNG_PHILOX && !ANNUAL && !INJ && (PHASE == 0 || PHASE == 3) && !SPLIT && !XS),
+                  "growth forms exist for the per-path Philox count-only launches (kPerPathPhilox), whole path or time-sliced");
     constexpr bool TOL = !EXACT;         // the month in its tolerance form (mcr_device.h: "TOLERANCE FORM of the month")
     constexpr bool MM = !SPLIT || kFan;  // exec-masked moves (issue-bound launches) vs the compiler's selects (latency-bound SPLIT launches): MCR_MASKED_MOVE, mcr_device.h
     // the tolerance month's dust / empty fix-ups tested once per wave (mcr_device.h: WAVE-UNIFORM fix-ups), issue-bound launches only
@@ -335,7 +341,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MC
     const unsigned long long tl_t0 = wall_clock64();
 #endif
     double* tab = tab_s;
-    load_math_tables(tab, threadIdx.x, kThreads);
+    load_math_tables<(GF & kGrowthNarrowExp) != 0>(tab, threadIdx.x, kThreads);
     ZigTables zig{nullptr, nullptr, nullptr, nullptr};
     if (RNG == (int)MCR_RNG_NUMPY) { zig = load_zig_tables(smem_raw, threadIdx.x, kThreads); zig.math_tab = tab; }
     // Philox stream: the gross factors of two months at a time, staged per lane (growth_rows2)
@@ -419,8 +425,8 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MC
                 if (((row >> 1) & (kSplitVotePairs - 1)) == 0) { if (__syncthreads_or(__builtin_amdgcn_ballot_w64(lane_alive) != 0ull ? 1 : 0) == 0) wg_dead = true; }
                 else __syncthreads();
             } else {
-                if ((row & 2) == 0) growth_rows2<0, kPaths, kPerPathPhilox>(P, GR, io.seed, io.stream_id, path, PQ, (uint32_t)row >> 2, tab, stage, carry);
-                else growth_rows2<1, kPaths, kPerPathPhilox>(P, GR, io.seed, io.stream_id, path, PQ, (uint32_t)row >> 2, tab, stage, carry);
+                if ((row & 2) == 0) growth_rows2<0, kPaths, kPerPathPhilox, GF>(P, GR, io.seed, io.stream_id, path, PQ, (uint32_t)row >> 2, tab, stage, carry);
+                else growth_rows2<1, kPaths, kPerPathPhilox, GF>(P, GR, io.seed, io.stream_id, path, PQ, (uint32_t)row >> 2, tab, stage, carry);
             }
         }
     };
@@ -930,6 +936,19 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MC
 // ---------------------------------------------------------------------------------------------
 // Device unit functions exposed for the reference's helper-level tests
 // ---------------------------------------------------------------------------------------------
+// MCR_HELPER_MATH_EXP_FORMS: the path form of exp as the general kernels run it and as the narrow-window growth form runs it
+// (fexp<true, true> on a CENTRED table), side by side: out = (general, narrow).  A kernel of its own: the two forms read
+// different tables.
+__global__ void exp_forms_kernel(const double* in, double* out, int64_t n) {
+    __shared__ double tab[kTabDoubles], tab_c[kTabDoubles];
+    load_math_tables(tab, threadIdx.x, blockDim.x);
+    load_math_tables<true>(tab_c, threadIdx.x, blockDim.x);
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[2 * i] = fexp<true>(in[i], tab, MathRegs::literals_path());
+    out[2 * i + 1] = fexp<true, true>(in[i], tab_c, MathRegs::literals_path());
+}
 __global__ void helper_kernel(int which, const DevParams P, const double* in, double* out, int64_t n) {
     __shared__ double tab[kTabDoubles];
     load_math_tables(tab, threadIdx.x, blockDim.x);
@@ -1423,6 +1442,53 @@ static int derive_params(const mcr_params* p, int32_t wm, DevParams* d, std::vec
     return MCR_OK;
 }
 
+// The GROWTH FORM of a launch (mcr_device.h: kGrowthNarrowExp | kGrowthRhoZero), from its parameter block alone.
+// Narrow exp window: every argument of the month's three exps is x = a + b z, and |z| is bounded by the generator itself — a
+// normal is radius x (cos | sin), the radius sqrt(-2 ln u) with u = (w + 0.5) 2^-32 >= 2^-33: kGrowthZMax.  So
+//     xmax = |a| + c |b| kGrowthZMax,    c = 1 (equity, premium),  c = |rho| + |rho_c| (inflation: rho n0 + rho_c n1),
+// and the form holds when xmax 512 / ln 2 <= kExpNarrowMaxK - 1 for all three series: k = rint(x 512 / ln 2) then lies in
+// fexp's window [-256, 255].  The 1 of margin covers rint's half step and the roundings of a + b z and of the kernel's radius
+// and sine / cosine (1e-14 relative: 1e-11 of a step).
+// rho = 0: binf_rho = binf * rho is then an exact zero (of either sign).
+static const double kGrowthZMax = std::sqrt(66.0 * std::log(2.0));   // sqrt(-2 ln 2^-33) = 6.7637
+static int growth_form_qualified(const DevParams& d) {
+    const double k_per_x = 512.0 / std::log(2.0), kmax = (double)(kExpNarrowMaxK - 1);
+    const double c_inf = std::fabs(d.rho) + std::fabs(d.rho_c);
+    const double x_eq = std::fabs(d.a1) + std::fabs(d.b1) * kGrowthZMax;
+    const double x_inf = std::fabs(d.ainf) + c_inf * std::fabs(d.binf) * kGrowthZMax;
+    const double x_prem = std::fabs(d.aprem) + std::fabs(d.bprem) * kGrowthZMax;
+    const bool narrow = x_eq * k_per_x <= kmax && x_inf * k_per_x <= kmax && x_prem * k_per_x <= kmax;
+    if (!narrow) return 0;
+    return d.rho == 0.0 ? (kGrowthNarrowExp | kGrowthRhoZero) : kGrowthNarrowExp;
+}
+// ... and what the launch runs: MCR_K1_GROWTH_FORM=0|1|3 (A/B, tests; read at every launch) forces a LOWER mask.  A bit the
+// parameters do not qualify for, or a non-zero mask on a launch whose kernel has no growth variants (`has_variants` false:
+// anything but a whole-path or time-sliced count-only Philox launch without an annual-gains tax), is an error: the knob never
+// yields a wrong table, and a test never compares a kernel with itself.
+static int growth_form_of(const DevParams& d, bool has_variants, int* mask) {
+    const int q = growth_form_qualified(d);
+    *mask = has_variants ? q : 0;
+    const char* e = std::getenv("MCR_K1_GROWTH_FORM");
+    if (!e || !*e) return MCR_OK;
+    char* end = nullptr;
+    const long want = std::strtol(e, &end, 10);
+    if (*end != '\0' || (want != 0 && want != kGrowthNarrowExp && want != (kGrowthNarrowExp | kGrowthRhoZero))) {
+        set_error("MCR_K1_GROWTH_FORM=%s: the growth forms are 0, 1 and 3", e);
+        return MCR_ERR_INVALID_ARG;
+    }
+    if (want != 0 && !has_variants) {
+        set_error("MCR_K1_GROWTH_FORM=%s set on a launch whose kernel has no growth variants", e);
+        return MCR_ERR_INVALID_ARG;
+    }
+    if (((int)want & ~q) != 0) {
+        set_error("MCR_K1_GROWTH_FORM=%s: the parameters qualify for mask %d only (narrow exp window: |a| + c |b| %.4f <= %d ln 2 / 512; rho = 0)",
+                  e, q, kGrowthZMax, kExpNarrowMaxK - 1);
+        return MCR_ERR_INVALID_ARG;
+    }
+    *mask = (int)want;
+    return MCR_OK;
+}
+
 // LDS of one path_kernel launch.  STATIC part of the variant — it mirrors the __shared__ declarations at the top of the
 // kernel: the math tables, the stage of growth factors (Philox stream without injection; twice for the producer / consumer
 // form) and the three per-path summary columns (those variants with per-path outputs) — plus the launch's DYNAMIC part: the
@@ -1634,6 +1700,14 @@ template <typename F> static inline void for_tax_variant(const DevParams& d, F&&
         switch (d.tax_mask) { case 0: f(int_c<0>{}, A); break; case 1: f(int_c<1>{}, A); break; case 2: f(int_c<2>{}, A); break; default: f(int_c<3>{}, A); break; }
     });
 }
+// f(G): G = the launch's growth form (growth_form_of): the masks path_kernel is instantiated for
+template <typename F> static inline void for_growth_form(int gf, F&& f) {
+    if (gf == (kGrowthNarrowExp | kGrowthRhoZero)) f(int_c<kGrowthNarrowExp | kGrowthRhoZero>{});
+    else if (gf == kGrowthNarrowExp) f(int_c<kGrowthNarrowExp>{});
+    else f(int_c<0>{});
+}
+// whether path_kernel<MODE, RNG, ., ANNUAL, ...> of a whole-path or time-sliced launch has growth variants (kPerPathPhilox)
+template <int MODE, int RNG, bool ANNUAL, bool XS> constexpr bool kHasGrowthForms = MODE == 0 && RNG == 0 && !ANNUAL && !XS;
 template <typename F> static inline void for_output_mode(int mode, F&& f) {
     if (mode == 2) f(int_c<2>{}); else if (mode == 1) f(int_c<1>{}); else f(int_c<0>{});
 }
@@ -1766,6 +1840,10 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
                   np_rng ? "NumPy stream" : injected ? "injected shocks" : xs ? "extended streams / exact month" : "producer / consumer split");
         return MCR_ERR_INVALID_ARG;
     }
+    // growth form of the launch: the whole-path and time-sliced count-only kernels of the engine's own stream have the variants
+    int gf = 0;
+    rc = growth_form_of(d, !np_rng && !injected && !xs && !split && mode == 0 && !d.any_annual_tax, &gf);
+    if (rc != MCR_OK) return rc;
     StreamSideBlock side;
     rc = side.attach(d, extra, grid.x, stream);
     if (rc != MCR_OK) { (void)side.release(stream); return rc; }
@@ -1774,9 +1852,16 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
     auto launch_whole_path = [&]() {
         for_output_mode(mode, [&](auto M) {
             for_whole_path_variant(d, np_rng, xs, exact, [&](auto R, auto T, auto A, auto X, auto EX) {
-                hipLaunchKernelGGL((path_kernel<decltype(M)::value, decltype(R)::value, decltype(T)::value, decltype(A)::value, false, 0, false,
-                                                decltype(X)::value, (decltype(X)::value && decltype(EX)::value) || kExactMonthDefault>),
-                                   grid, block, lds, stream, d, io, no_cand);
+                if constexpr (kHasGrowthForms<decltype(M)::value, decltype(R)::value, decltype(A)::value, decltype(X)::value>) {
+                    for_growth_form(gf, [&](auto G) {
+                        hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, false, false, 0, false, false, kExactMonthDefault, decltype(G)::value>),
+                                           grid, block, lds, stream, d, io, no_cand);
+                    });
+                } else {
+                    hipLaunchKernelGGL((path_kernel<decltype(M)::value, decltype(R)::value, decltype(T)::value, decltype(A)::value, false, 0, false,
+                                                    decltype(X)::value, (decltype(X)::value && decltype(EX)::value) || kExactMonthDefault>),
+                                       grid, block, lds, stream, d, io, no_cand);
+                }
             });
         });
     };
@@ -1808,8 +1893,15 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
             if (e == hipSuccess) {
                 for_output_mode(mode, [&](auto M) {
                     for_tax_variant(d, [&](auto T, auto A) {
-                        launch_sliced(&path_kernel<decltype(M)::value, 0, decltype(T)::value, decltype(A)::value, false, 3>, plan,
-                                      seg_order ? order : nullptr, block, lds, stream, d, io, no_cand);
+                        if constexpr (kHasGrowthForms<decltype(M)::value, 0, decltype(A)::value, false>) {
+                            for_growth_form(gf, [&](auto G) {
+                                launch_sliced(&path_kernel<0, 0, decltype(T)::value, false, false, 3, false, false, kExactMonthDefault, decltype(G)::value>, plan,
+                                              seg_order ? order : nullptr, block, lds, stream, d, io, no_cand);
+                            });
+                        } else {
+                            launch_sliced(&path_kernel<decltype(M)::value, 0, decltype(T)::value, decltype(A)::value, false, 3>, plan,
+                                          seg_order ? order : nullptr, block, lds, stream, d, io, no_cand);
+                        }
                     });
                 });
                 e = hipGetLastError();
@@ -2301,6 +2393,18 @@ const char* mcr_last_error(void) { return g_err; }
 
 int mcr_query_sizes(const mcr_params* p, int32_t working_months, mcr_sizes* out) {
     return query_sizes(p, working_months, out);
+}
+
+int mcr_k1_growth_form(const mcr_params* p, int32_t working_months, int32_t* mask) {
+    if (!mask) { set_error("null mask"); return MCR_ERR_INVALID_ARG; }
+    DevParams d;
+    int rc = derive_params(p, working_months, &d);
+    if (rc != MCR_OK) return rc;
+    int m = 0;
+    rc = growth_form_of(d, true, &m);
+    if (rc != MCR_OK) return rc;
+    *mask = m;
+    return MCR_OK;
 }
 
 int32_t mcr_stream_start_month_index(double current_age, int32_t working_months, double start_at_age) {
@@ -2949,6 +3053,7 @@ int mcr_eval_helper_host(int which, const mcr_params* p, const double* in, doubl
         case MCR_HELPER_MATH_SINCOS_PATH: n_in = 1; n_out = 2; break;
         case MCR_HELPER_WITHDRAW_MONTH: n_in = 5; n_out = 6; break;
         case MCR_HELPER_REBALANCE_MONTH: n_in = 4; n_out = 4; break;
+        case MCR_HELPER_MATH_EXP_FORMS: n_in = 1; n_out = 2; break;
         default: set_error("unknown helper %d", which); return MCR_ERR_INVALID_ARG;
     }
     if (!in || !out || n < 0) { set_error("bad arguments"); return MCR_ERR_INVALID_ARG; }
@@ -2968,7 +3073,8 @@ int mcr_eval_helper_host(int which, const mcr_params* p, const double* in, doubl
     if (e == hipSuccess) e = arena.alloc((void**)&dout, (size_t)n * n_out * sizeof(double));
     if (e == hipSuccess) e = hipMemcpy(din, in, (size_t)n * n_in * sizeof(double), hipMemcpyHostToDevice);
     if (e != hipSuccess) return hip_fail(e, "helper upload");
-    hipLaunchKernelGGL(helper_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, which, d, din, dout, n);
+    if (which == MCR_HELPER_MATH_EXP_FORMS) hipLaunchKernelGGL(exp_forms_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, din, dout, n);
+    else hipLaunchKernelGGL(helper_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, which, d, din, dout, n);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)n * n_out * sizeof(double), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail(e, "helper_kernel");

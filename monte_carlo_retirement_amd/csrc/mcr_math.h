@@ -38,8 +38,15 @@ namespace mcr {
 constexpr int kMathTabBytes = kTabDoubles * (int)sizeof(double);  // 10 240 B of LDS
 
 // every thread of a kBlockThreads-wide workgroup calls this once; caller syncs afterwards
+// CENTRED (the narrow-window exp, fexp<., true>): entries 256 .. 511 of the exp2 part are stored HALVED, 2^(j/512) / 2 — exact,
+// they lie in [sqrt 2, 2) — so that entry k & 511 is 2^(k/512) itself for every k in [-256, 255].  Such a table serves the
+// narrow form only; the other parts (logarithm, sine / cosine) are the same.
+template <bool CENTRED = false>
 __device__ __forceinline__ void load_math_tables(double* lds_tab, int tid, int nthreads) {
-    for (int i = tid; i < kTabDoubles; i += nthreads) lds_tab[i] = kMathTab[i];
+    for (int i = tid; i < kTabDoubles; i += nthreads) {
+        const double v = kMathTab[i];
+        lds_tab[i] = (CENTRED && i >= kTabExp2 + (1 << (kExp2Bits - 1)) && i < kTabExp2 + (1 << kExp2Bits)) ? 0.5 * v : v;
+    }
 }
 
 // 1/b: v_rcp_f64 seed + Newton steps.  FULL = two steps (the core of LLVM's IEEE fdiv lowering; with div_by below the
@@ -86,7 +93,13 @@ constexpr double kExpStep = 0x1.62e42fefa39efp-10;   // ln 2 / 512, correctly ro
 constexpr double kExpPathHalf = 0.5 + (0x1.62e42fefa39efp-11 * 0x1.62e42fefa39efp-11) / 40.0;   // 1/2 + a^2/40, a = ln 2 / 1024
 constexpr double kM2Ln2 = -0x1.62e42fefa39efp+0;     // -2 ln 2, correctly rounded
 
-template <bool PATH = false>
+// NARROW (with a table loaded CENTRED, load_math_tables): the form for launches whose every argument has
+// k = rint(x 512 / ln 2) in [-256, 255] (kExpNarrowMaxK; the host proves it from the launch's parameters, mcr_hip.hip:
+// growth_form_of).  k >> 9 is then 0 or -1, and the table holds that factor: entry k & 511 is 2^(j/512) for j < 256 and
+// 2^(j/512) / 2 for j >= 256.  fma(t/2, p, t/2) is fma(t, p, t) / 2 exactly (a power-of-two scale of a normal result), so the
+// value is the general form's bit for bit, without the two 32-bit instructions of the exponent insertion.
+constexpr int kExpNarrowMaxK = (1 << (kExp2Bits - 1)) - 1;   // 255: the window is [-256, 255]
+template <bool PATH = false, bool NARROW = false>
 __device__ __forceinline__ double fexp(double x, const double* tab, const MathRegs& R) {
     // k = rint(x 512/ln2) by the shifter trick: the sum lands on the unit grid of [2^52, 2^53), so its low word IS k
     // (two's complement) and subtracting the shifter gives k as a double: no v_rndne / v_cvt_i32.
@@ -114,6 +127,7 @@ __device__ __forceinline__ double fexp(double x, const double* tab, const MathRe
     // t (1 + p) 2^(k >> 9): the scale goes straight into the exponent field of the high word (v_ashr + v_lshl_add_u32,
     // both 32-bit) instead of v_ashr + v_ldexp_f64.  Exact while the result is a normal number (|x| < 700).
     const double v = __builtin_fma(t, p, t);
+    if (NARROW) return v;                                 // (the centred table's t already carries 2^(k >> 9))
     const uint64_t vb = (uint64_t)__double_as_longlong(v);
     uint32_t hi;
     asm("v_lshl_add_u32 %0, %1, 20, %2" : "=v"(hi) : "v"(k >> kExp2Bits), "v"((uint32_t)(vb >> 32)));  // (the compiler splits it in three)

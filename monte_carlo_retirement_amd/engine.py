@@ -38,6 +38,16 @@ def query_sizes(params: McrParams, working_months: int) -> McrSizes:
     return sz
 
 
+def growth_form(params: McrParams, working_months: int) -> int:
+    """Growth form (0, 1 or 3) a whole-path count-only launch of these parameters runs (mcr_k1_growth_form; honours
+    MCR_K1_GROWTH_FORM); ``ValueError`` if the parameters, or a forced form they do not qualify for, are invalid."""
+    mask = C.c_int32(-1)
+    rc = N.load_library().mcr_k1_growth_form(C.byref(params), int(working_months), C.byref(mask))
+    if rc != 0:
+        raise ValueError(N.last_error() or "invalid params / growth form")
+    return int(mask.value)
+
+
 def stream_start_month_index(current_age: float, working_months: int, start_at_age: float) -> int:
     return int(N.load_library().mcr_stream_start_month_index(current_age, working_months, start_at_age))
 

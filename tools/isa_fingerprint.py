@@ -4,7 +4,11 @@
 register budget, so that a refactoring that must not change the generated code can be checked kernel by kernel.
 
     python tools/isa_fingerprint.py --out before.json            (then edit)
-    python tools/isa_fingerprint.py --compare before.json [--flags "..."]
+    python tools/isa_fingerprint.py --compare before.json [--flags "..."] [--rename OLD=NEW ...]
+
+--rename rewrites the assembly text before it is split into kernels: a template parameter appended with a default value
+changes every instantiation's mangled name (and the names of its static LDS symbols) although the code is the same, e.g.
+--rename ELi0EEEvNS_9DevParams=EEEvNS_9DevParams compares path_kernel<..., GF = 0> with the path_kernel<...> before it.
 """
 from __future__ import annotations
 
@@ -21,7 +25,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 
-def fingerprints(extra_flags=()):
+def fingerprints(extra_flags=(), renames=()):
     from monte_carlo_retirement_amd.csrc import build as B
 
     res = {}
@@ -32,6 +36,8 @@ def fingerprints(extra_flags=()):
         subprocess.check_call([B.hipcc(), *flags, *extra_flags, "--cuda-device-only", "-S", "-o", out, os.path.join(B.HERE, src)],
                               stderr=subprocess.DEVNULL)
         text = open(out).read()
+        for old, new in renames:
+            text = text.replace(old, new)
         for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)^\.Lfunc_end\d+:", text, re.S | re.M):
             name, body = m.group(1), m.group(2)
             lines = []
@@ -56,8 +62,9 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--compare")
     ap.add_argument("--flags", default="")
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW")
     args = ap.parse_args()
-    fp = fingerprints(args.flags.split())
+    fp = fingerprints(args.flags.split(), [tuple(r.split("=", 1)) for r in args.rename])
     if args.out:
         json.dump(fp, open(args.out, "w"), indent=1)
         print(f"{len(fp)} kernels -> {args.out}")
