@@ -195,6 +195,15 @@ int mcr_query_sizes(const mcr_params* p, int32_t working_months, mcr_sizes* out)
  * MCR_K1_GROWTH_FORM in the environment forces a lower mask, as at a launch; a mask the parameters do not qualify for
  * returns MCR_ERR_INVALID_ARG. */
 int mcr_k1_growth_form(const mcr_params* p, int32_t working_months, int32_t* mask);
+/* The month form of the same launch ("month forms"): bit 0 = both assets are taxed on realized gains at the same
+ * rate, with no annual-gains tax; masks 0 and 1.  MCR_K1_MONTH_FORM in the environment forces a lower mask, as at a launch; a
+ * mask the parameters do not qualify for returns MCR_ERR_INVALID_ARG. */
+int mcr_k1_month_form(const mcr_params* p, int32_t working_months, int32_t* mask);
+/* The other_income_streams records the path kernel is given for (params, working_months), in list order: a record with
+ * monthly_amount_today == 0 pays an exact zero every month and is left out; lock slots (non-indexed streams; -1 for an indexed
+ * one) are numbered over the kept records.  Writes min(*n, cap) entries of index[] (position in the caller's list) and
+ * lock_slot[]; *n = the number kept. */
+int mcr_k1_kept_streams(const mcr_params* p, int32_t working_months, int32_t* index, int32_t* lock_slot, int32_t cap, int32_t* n);
 /* Range check of a parameter block — what the reference's pydantic Config enforces (backend/config.py:56-99)
  * and the kernel relies on: amounts finite and >= 0, rates / allocation / stream tax rates in [0, 1], rho in
  * [-1, 1], finite log-parameters with sigma >= 0 and |mu|/12 + 40 sigma/sqrt(12) < 700 (domain of the kernel's

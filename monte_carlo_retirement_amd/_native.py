@@ -243,6 +243,8 @@ ABI_SYMBOLS = (
     "mcr_query_sizes",
     "mcr_stream_start_month_index",
     "mcr_k1_growth_form",
+    "mcr_k1_month_form",
+    "mcr_k1_kept_streams",
     "mcr_run_batch",
     "mcr_run_batch_host",
     "mcr_draw_shocks_host",
@@ -299,6 +301,11 @@ def _declare(lib: C.CDLL) -> None:
     lib.mcr_stream_start_month_index.argtypes = [C.c_double, C.c_int32, C.c_double]
     lib.mcr_k1_growth_form.restype = C.c_int
     lib.mcr_k1_growth_form.argtypes = [P(McrParams), C.c_int32, P(C.c_int32)]
+    if hasattr(lib, "mcr_k1_month_form"):   # (an MCR_HIP_LIBRARY built from an earlier tree, for A/B runs, has neither)
+        lib.mcr_k1_month_form.restype = C.c_int
+        lib.mcr_k1_month_form.argtypes = [P(McrParams), C.c_int32, P(C.c_int32)]
+        lib.mcr_k1_kept_streams.restype = C.c_int
+        lib.mcr_k1_kept_streams.argtypes = [P(McrParams), C.c_int32, P(C.c_int32), P(C.c_int32), C.c_int32, P(C.c_int32)]
     lib.mcr_run_batch.restype = C.c_int
     lib.mcr_run_batch.argtypes = [
         P(McrParams), C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32,

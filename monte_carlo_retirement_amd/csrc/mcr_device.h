@@ -97,9 +97,16 @@ __device__ __forceinline__ LaneParams lane_params(const DevParams& P) {
 // The tolerance form of the month (below) selects the seller's rate and the seller's weight x rate; it needs neither weight
 // on its own (the drift of asset 2 is minus the drift of asset 1).  In the SAME struct, so that the helpers keep one
 // signature: alloc1 / alloc2 then hold the products.
+// EQR (the month form kMonthEqualRates, below): the two rates are one value — one VGPR pair holds it for both assets.
+template <bool EQR = false>
 __device__ __forceinline__ LaneParams lane_params_tol(const DevParams& P) {
     LaneParams L{P.alloc1 * P.real_rate1, P.alloc2 * P.real_rate2, P.real_rate1, P.real_rate2};
-    asm volatile("" : "+v"(L.alloc1), "+v"(L.alloc2), "+v"(L.real_rate1), "+v"(L.real_rate2));
+    if (EQR) {
+        asm volatile("" : "+v"(L.alloc1), "+v"(L.alloc2), "+v"(L.real_rate1));
+        L.real_rate2 = L.real_rate1;
+    } else {
+        asm volatile("" : "+v"(L.alloc1), "+v"(L.alloc2), "+v"(L.real_rate1), "+v"(L.real_rate2));
+    }
     return L;
 }
 
@@ -622,6 +629,12 @@ __device__ __forceinline__ void rebalance_path(const LaneParams& P, double& b1, 
     }
 }
 
+// MF: the launch's MONTH FORM, a mask of what its parameters make unnecessary in the month's own arithmetic (chosen on the
+// host, mcr_hip.hip: month_form_of; the kernels that have growth forms have month forms).  Every value is bit for bit the
+// general form's wherever the bit may be used.
+//   kMonthEqualRates: both assets are taxed on realized gains at the SAME rate -> rebalance_tol<..., EQR>
+enum { kMonthEqualRates = 1 };
+
 // ---------------------------------------------------------------------------------------------
 // TOLERANCE FORM of the month (what the path kernel runs since round 4; the forms above stay the unit API, the corner
 // configurations below and the A/B build -DMCR_K1_EXACT_MONTH).  The forms above mirror the reference's roundings operation
@@ -689,12 +702,16 @@ __device__ __forceinline__ void sell_fraction_tol(double phi, double& b1, double
 }
 // (:274-359)  L = lane_params_tol(P): L.alloc1 / L.alloc2 hold weight x rate of asset 1 / 2.  UNIFORM: the guard and the dust
 // fix-ups are tested wave-wide (self-contained: no precondition); a wave with a lane that does not act takes the UNIFORM = false form.
-template <bool TAXED, bool MM = true, bool UNIFORM = false>
+// EQR (the launch's MONTH FORM has kMonthEqualRates, below): both assets carry the SAME realized-gains rate, so the seller's
+// rate is not a per-lane choice and its select goes (the seller's weight x rate keeps its own).  The rate is read from the
+// lanes' resident copy, not from the scalar block: the kernel has no SGPR pair to spare (as a scalar operand it came back as
+// v_readlane + s_nop at every use).
+template <bool TAXED, bool MM = true, bool UNIFORM = false, bool EQR = false>
 __device__ __forceinline__ void rebalance_tol(const DevParams& P, const LaneParams& L, double& b1, double& c1, double& b2, double& c2) {
     const double total = b1 + b2;                                  // :288
     const double drift1 = __builtin_fma(-total, P.alloc1, b1);     // :293-294
     if (UNIFORM && wave_any(fmin(total, fabs(drift1)) <= kEps)) {  // (one compare: a ballot of an OR comes out as a 0/1 VGPR compared again)
-        rebalance_tol<TAXED, MM, false>(P, L, b1, c1, b2, c2);
+        rebalance_tol<TAXED, MM, false, EQR>(P, L, b1, c1, b2, c2);
         return;
     }
     if (UNIFORM || ((total > kEps) && (fabs(drift1) > kEps))) {   // :290-296
@@ -704,7 +721,7 @@ __device__ __forceinline__ void rebalance_tol(const DevParams& P, const LanePara
         const double drift = fabs(drift1);                         // :328: b2 - total (1 - alloc1) = -(b1 - total alloc1)
         double fraction_sold, net_purchase;
         if (TAXED) {
-            const double rate_s = sell1 ? L.real_rate1 : L.real_rate2;
+            const double rate_s = EQR ? L.real_rate1 : sell1 ? L.real_rate1 : L.real_rate2;
             const double ar_s = sell1 ? L.alloc1 : L.alloc2;       // the SOLD asset's own weight (:309,:337) x its rate
             const double G = fmax(0.0, bs - cs);                   // :301 / :329 (x bs)
             fraction_sold = fmin(1.0, drift * recip_nr<false>(__builtin_fma(-ar_s, G, bs)));   // :302-312
@@ -727,8 +744,8 @@ __device__ __forceinline__ void rebalance_tol(const DevParams& P, const LanePara
     }
 }
 
-// TOL: the closing rebalance in its tolerance form (then L = lane_params_tol(P)).
-template <bool STRICT = true, bool TAXED = true, bool ANNUAL = true, bool T1 = TAXED, bool T2 = TAXED, bool MM = true, bool TOL = false>
+// TOL: the closing rebalance in its tolerance form (then L = lane_params_tol(P)); EQR: rebalance_tol's.
+template <bool STRICT = true, bool TAXED = true, bool ANNUAL = true, bool T1 = TAXED, bool T2 = TAXED, bool MM = true, bool TOL = false, bool EQR = false>
 __device__ __forceinline__ bool annual_gain_taxes(const DevParams& P, const LaneParams& L, double& b1, double& c1,
                                                   double& b2, double& c2, double gain1, double gain2) {
     bool tax_failed = false;
@@ -751,7 +768,7 @@ __device__ __forceinline__ bool annual_gain_taxes(const DevParams& P, const Lane
         }
     }
     if (STRICT) rebalance<true, TAXED, MM>(L, b1, c1, b2, c2);  // :432-442 (always)
-    else if (TOL) rebalance_tol<TAXED, MM>(P, L, b1, c1, b2, c2);
+    else if (TOL) rebalance_tol<TAXED, MM, false, EQR>(P, L, b1, c1, b2, c2);
     else rebalance_path<TAXED, MM>(L, b1, c1, b2, c2);
     return tax_failed;
 }

@@ -250,7 +250,7 @@ constexpr bool kUniformFixups = false;
 #else
 constexpr bool kUniformFixups = true;
 #endif
-template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault, int GF = 0>
+template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault, int GF = 0, int MF = 0>
 __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
                                                          const DevParams* __restrict__ cand_params) {
     // MODE 3 (mcr_run_year_bins_rng): YEARLY BINS.  The arithmetic of MODE 2, but wherever that variant stores a yearly sample
@@ -290,6 +290,13 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MC
     static_assert(GF == 0 || GF == kGrowthNarrowExp || GF == (kGrowthNarrowExp | kGrowthRhoZero), "growth forms: masks 0, 1 and 3");
     static_assert(GF == 0 || (MODE == 0 && RNG == (int)MCR_RNG_PHILOX && !ANNUAL && !INJ && (PHASE == 0 || PHASE == 3) && !SPLIT && !XS),
                   "growth forms exist for the per-path Philox count-only launches (kPerPathPhilox), whole path or time-sliced");
+    // MF: the launch's month form (mcr_device.h: kMonthEqualRates; masks 0 and 1), for the kernels that have growth forms.  Behind
+    // GF, with a default, for the same reason.
+    static_assert(MF == 0 || MF == kMonthEqualRates, "month forms: masks 0 and 1");
+    static_assert(MF == 0 || (MODE == 0 && RNG == (int)MCR_RNG_PHILOX && !ANNUAL && !INJ && (PHASE == 0 || PHASE == 3) && !SPLIT && !XS && !EXACT),
+                  "month forms exist for the kernels that have growth forms, in the tolerance form of the month");
+    static_assert(!(MF & kMonthEqualRates) || TAXED == 3, "equal realized-gains rates: both assets are taxed");
+    constexpr bool EQR = (MF & kMonthEqualRates) != 0;
     constexpr bool TOL = !EXACT;         // the month in its tolerance form (mcr_device.h: "TOLERANCE FORM of the month")
     constexpr bool MM = !SPLIT || kFan;  // exec-masked moves (issue-bound launches) vs the compiler's selects (latency-bound SPLIT launches): MCR_MASKED_MOVE, mcr_device.h
     // the tolerance month's dust / empty fix-ups tested once per wave (mcr_device.h: WAVE-UNIFORM fix-ups), issue-bound launches only
@@ -454,7 +461,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MC
         g2 = ginf * monthly_gross(P.aprem, P.bprem, zp, tab);  // :532
     };
 
-    const LaneParams L = TOL ? lane_params_tol(P) : lane_params(P);
+    const LaneParams L = TOL ? lane_params_tol<EQR>(P) : lane_params(P);
 
     // ---- initial state (:490-510) ----
     double b1 = P.initial_balance * P.alloc1;  // :499
@@ -578,10 +585,10 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MC
         const double k1 = contrib * P.alloc1;                          // :540-542
         const double k2 = contrib - k1;                                // :543
         b1 += k1; c1 += k1; b2 += k2; c2 += k2;                        // :544-547
-        if (TOL) rebalance_tol<TANY, MM, kFastMonth>(P, L, b1, c1, b2, c2);  // :549-553
+        if (TOL) rebalance_tol<TANY, MM, kFastMonth, EQR>(P, L, b1, c1, b2, c2);  // :549-553
         else rebalance_path<TANY, MM>(L, b1, c1, b2, c2);
         if (m % kMPY == 0) {                                           // :557
-            pre_fail |= annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, TOL>(P, L, b1, c1, b2, c2, gacc1, gacc2);  // :558-573
+            pre_fail |= annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, TOL, EQR>(P, L, b1, c1, b2, c2, gacc1, gacc2);  // :558-573
             put_sample(t_idx++, b1 + b2, infl);                        // :574-576
             gacc1 = 0.0; gacc2 = 0.0;                                  // :578-579
         }
@@ -717,9 +724,9 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MC
                         treal = __builtin_fma(gross * infl_ret, recip_nr<false>(fmax(price, kEps)), treal);  // :778-782
                     }
                     sell_fraction_tol<MM, FAST>(phi, b1, c1, b2, c2);                 // :757-776
-                    rebalance_tol<TANY, MM, kFastMonth>(P, L, b1, c1, b2, c2);        // :792-796
+                    rebalance_tol<TANY, MM, kFastMonth, EQR>(P, L, b1, c1, b2, c2);   // :792-796
                     if (!yfail && (wm + rmi + 1) % kMPY == 0) {                       // :798-804
-                        const bool tf = annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, true>(P, L, b1, c1, b2, c2, gacc1, gacc2);  // :805-818
+                        const bool tf = annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, true, EQR>(P, L, b1, c1, b2, c2, gacc1, gacc2);  // :805-818
                         gacc1 = 0.0; gacc2 = 0.0;                                     // :819-820
                         yfail = yfail || tf;                                          // :821-822
                     }
@@ -840,7 +847,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MC
     // ---- terminal partial tax period (:873-898) ----
     if (P.total_months % kMPY != 0) {  // wave-uniform
         if (succeeded) {
-            const bool tf = annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, TOL>(P, L, b1, c1, b2, c2, gacc1, gacc2);  // :880-893
+            const bool tf = annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, TOL, EQR>(P, L, b1, c1, b2, c2, gacc1, gacc2);  // :880-893
             if (tf) {                                                            // :894-896
                 succeeded = false; ruin_bin = ry + 1;
                 if (kSumLds) sum_col[2 * kBlock] = (double)ry; else ytr_bits = f64_bits((double)ry);
@@ -1372,7 +1379,8 @@ static int32_t start_month_index(double current_age, int32_t wm, double start_at
 // Host-side derivation of the wave-uniform parameter block (same fp64 expressions as the reference).
 // `extra` receives the records of the streams beyond the by-value block (device-table layout); callers that cannot carry
 // such a table pass nullptr and get MCR_ERR_UNSUPPORTED for longer lists.
-static int derive_params(const mcr_params* p, int32_t wm, DevParams* d, std::vector<DevStream>* extra = nullptr) {
+static int derive_params(const mcr_params* p, int32_t wm, DevParams* d, std::vector<DevStream>* extra = nullptr,
+                         std::vector<std::pair<int, int>>* kept = nullptr /* (list index, lock slot) of the records the kernel gets */) {
     mcr_sizes sz;
     int rc = query_sizes(p, wm, &sz);
     if (rc != MCR_OK) return rc;
@@ -1416,14 +1424,23 @@ static int derive_params(const mcr_params* p, int32_t wm, DevParams* d, std::vec
     d->shock_rows = sz.shock_rows;
     d->num_working_years = sz.num_working_years;
     d->trajectory_len = sz.trajectory_len;
-    d->n_streams = p->n_streams < MCR_INLINE_STREAMS ? p->n_streams : MCR_INLINE_STREAMS;
-    d->n_extra_streams = p->n_streams - d->n_streams;
+    // A record that pays nothing (monthly_amount_today == 0) contributes an exact zero to every month's income, frozen or
+    // indexed: income - 0 and fma(-0, price, income) are `income` (the price level is finite), and the exact form adds 0 keep
+    // = +0 to a non-negative sum.  The kernel is not given it: no record to test every month, no lock column, no field in a
+    // time-sliced block's hand-over.  The kept records keep their list order; lock slots are numbered over them.
+    int kept_n = 0;
+    for (int s = 0; s < p->n_streams; ++s) kept_n += stream_at(p, s).monthly_amount_today != 0.0;
+    d->n_streams = kept_n < MCR_INLINE_STREAMS ? kept_n : MCR_INLINE_STREAMS;
+    d->n_extra_streams = kept_n - d->n_streams;
     if (extra) extra->assign((size_t)d->n_extra_streams, DevStream{});
-    int slots = 0;
+    if (kept) kept->clear();
+    int slots = 0, k = 0;
     for (int s = 0; s < p->n_streams; ++s) {
         const mcr_stream& in = stream_at(p, s);
+        if (in.monthly_amount_today == 0.0) continue;
         DevStream scratch;
-        DevStream& o = s < MCR_INLINE_STREAMS ? d->streams[s] : (extra ? (*extra)[(size_t)(s - MCR_INLINE_STREAMS)] : scratch);
+        DevStream& o = k < MCR_INLINE_STREAMS ? d->streams[k] : (extra ? (*extra)[(size_t)(k - MCR_INLINE_STREAMS)] : scratch);
+        ++k;
         o.amount = in.monthly_amount_today;
         o.keep = 1.0 - in.tax_rate;  // :676
         o.amount_keep = o.amount * o.keep;
@@ -1436,6 +1453,7 @@ static int derive_params(const mcr_params* p, int32_t wm, DevParams* d, std::vec
         }
         o.indexed = in.inflation_indexed ? 1 : 0;
         o.lock_slot = o.indexed ? -1 : slots++;
+        if (kept) kept->push_back({s, o.lock_slot});
     }
     d->n_lock_slots_total = slots;
     d->n_lock_slots = slots;     // (the launcher lowers it to what its kernel variant's LDS budget holds: plan_lock_slots)
@@ -1483,6 +1501,38 @@ static int growth_form_of(const DevParams& d, bool has_variants, int* mask) {
     if (((int)want & ~q) != 0) {
         set_error("MCR_K1_GROWTH_FORM=%s: the parameters qualify for mask %d only (narrow exp window: |a| + c |b| %.4f <= %d ln 2 / 512; rho = 0)",
                   e, q, kGrowthZMax, kExpNarrowMaxK - 1);
+        return MCR_ERR_INVALID_ARG;
+    }
+    *mask = (int)want;
+    return MCR_OK;
+}
+
+// The MONTH FORM of a launch (mcr_device.h: kMonthEqualRates), from its parameter block alone: both assets taxed on realized
+// gains (tax mask 3) at the same rate, in the tolerance form of the month, with no annual-gains tax (the kernels that have the
+// variants).  MCR_K1_MONTH_FORM=0|1 forces a LOWER mask, under the rules of MCR_K1_GROWTH_FORM: a bit the parameters do not
+// qualify for, or a non-zero mask on a launch whose kernel has no variants, is an error.  A library built with
+// -DMCR_K1_EXACT_MONTH runs every kernel in the exact month, which has no month forms: no launch qualifies there.
+static int month_form_qualified(const DevParams& d) {
+    if (kExactMonthDefault) return 0;
+    return (d.tax_mask == 3 && d.real_rate1 == d.real_rate2 && !d.any_annual_tax && !d.exact_month) ? kMonthEqualRates : 0;
+}
+static int month_form_of(const DevParams& d, bool has_variants, int* mask) {
+    const int q = month_form_qualified(d);
+    *mask = has_variants ? q : 0;
+    const char* e = std::getenv("MCR_K1_MONTH_FORM");
+    if (!e || !*e) return MCR_OK;
+    char* end = nullptr;
+    const long want = std::strtol(e, &end, 10);
+    if (*end != '\0' || (want != 0 && want != kMonthEqualRates)) {
+        set_error("MCR_K1_MONTH_FORM=%s: the month forms are 0 and 1", e);
+        return MCR_ERR_INVALID_ARG;
+    }
+    if (want != 0 && !has_variants) {
+        set_error("MCR_K1_MONTH_FORM=%s set on a launch whose kernel has no month variants", e);
+        return MCR_ERR_INVALID_ARG;
+    }
+    if (((int)want & ~q) != 0) {
+        set_error("MCR_K1_MONTH_FORM=%s: the parameters qualify for mask %d only (both assets taxed on realized gains at one rate, no annual-gains tax)", e, q);
         return MCR_ERR_INVALID_ARG;
     }
     *mask = (int)want;
@@ -1706,6 +1756,13 @@ template <typename F> static inline void for_growth_form(int gf, F&& f) {
     else if (gf == kGrowthNarrowExp) f(int_c<kGrowthNarrowExp>{});
     else f(int_c<0>{});
 }
+// f(F): F = the launch's month form (month_form_of).  T = the kernel's tax mask: only mask 3 has the equal-rates variant
+// (month_form_of gives the bit to no other launch), so the others instantiate the general month alone — as does every kernel
+// of the exact-month build (kExactMonthDefault), where the variant does not exist
+template <int T, typename F> static inline void for_month_form(int mf, F&& f) {
+    if constexpr (T == 3 && !kExactMonthDefault) { if (mf == kMonthEqualRates) { f(int_c<kMonthEqualRates>{}); return; } }
+    f(int_c<0>{});
+}
 // whether path_kernel<MODE, RNG, ., ANNUAL, ...> of a whole-path or time-sliced launch has growth variants (kPerPathPhilox)
 template <int MODE, int RNG, bool ANNUAL, bool XS> constexpr bool kHasGrowthForms = MODE == 0 && RNG == 0 && !ANNUAL && !XS;
 template <typename F> static inline void for_output_mode(int mode, F&& f) {
@@ -1844,6 +1901,9 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
     int gf = 0;
     rc = growth_form_of(d, !np_rng && !injected && !xs && !split && mode == 0 && !d.any_annual_tax, &gf);
     if (rc != MCR_OK) return rc;
+    int mf = 0;     // ... and its month form: the same kernels
+    rc = month_form_of(d, !np_rng && !injected && !xs && !split && mode == 0 && !d.any_annual_tax, &mf);
+    if (rc != MCR_OK) return rc;
     StreamSideBlock side;
     rc = side.attach(d, extra, grid.x, stream);
     if (rc != MCR_OK) { (void)side.release(stream); return rc; }
@@ -1854,8 +1914,10 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
             for_whole_path_variant(d, np_rng, xs, exact, [&](auto R, auto T, auto A, auto X, auto EX) {
                 if constexpr (kHasGrowthForms<decltype(M)::value, decltype(R)::value, decltype(A)::value, decltype(X)::value>) {
                     for_growth_form(gf, [&](auto G) {
-                        hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, false, false, 0, false, false, kExactMonthDefault, decltype(G)::value>),
-                                           grid, block, lds, stream, d, io, no_cand);
+                        for_month_form<decltype(T)::value>(mf, [&](auto F) {
+                            hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, false, false, 0, false, false, kExactMonthDefault, decltype(G)::value, decltype(F)::value>),
+                                               grid, block, lds, stream, d, io, no_cand);
+                        });
                     });
                 } else {
                     hipLaunchKernelGGL((path_kernel<decltype(M)::value, decltype(R)::value, decltype(T)::value, decltype(A)::value, false, 0, false,
@@ -1895,8 +1957,10 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
                     for_tax_variant(d, [&](auto T, auto A) {
                         if constexpr (kHasGrowthForms<decltype(M)::value, 0, decltype(A)::value, false>) {
                             for_growth_form(gf, [&](auto G) {
-                                launch_sliced(&path_kernel<0, 0, decltype(T)::value, false, false, 3, false, false, kExactMonthDefault, decltype(G)::value>, plan,
-                                              seg_order ? order : nullptr, block, lds, stream, d, io, no_cand);
+                                for_month_form<decltype(T)::value>(mf, [&](auto F) {
+                                    launch_sliced(&path_kernel<0, 0, decltype(T)::value, false, false, 3, false, false, kExactMonthDefault, decltype(G)::value, decltype(F)::value>, plan,
+                                                  seg_order ? order : nullptr, block, lds, stream, d, io, no_cand);
+                                });
                             });
                         } else {
                             launch_sliced(&path_kernel<decltype(M)::value, 0, decltype(T)::value, decltype(A)::value, false, 3>, plan,
@@ -2404,6 +2468,30 @@ int mcr_k1_growth_form(const mcr_params* p, int32_t working_months, int32_t* mas
     rc = growth_form_of(d, true, &m);
     if (rc != MCR_OK) return rc;
     *mask = m;
+    return MCR_OK;
+}
+
+int mcr_k1_month_form(const mcr_params* p, int32_t working_months, int32_t* mask) {
+    if (!mask) { set_error("null mask"); return MCR_ERR_INVALID_ARG; }
+    DevParams d;
+    int rc = derive_params(p, working_months, &d);
+    if (rc != MCR_OK) return rc;
+    int m = 0;
+    rc = month_form_of(d, true, &m);
+    if (rc != MCR_OK) return rc;
+    *mask = m;
+    return MCR_OK;
+}
+
+int mcr_k1_kept_streams(const mcr_params* p, int32_t working_months, int32_t* index, int32_t* lock_slot, int32_t cap, int32_t* n) {
+    if (!n || cap < 0 || (cap > 0 && (!index || !lock_slot))) { set_error("null argument"); return MCR_ERR_INVALID_ARG; }
+    DevParams d;
+    std::vector<DevStream> extra;
+    std::vector<std::pair<int, int>> kept;
+    const int rc = derive_params(p, working_months, &d, &extra, &kept);
+    if (rc != MCR_OK) return rc;
+    for (size_t i = 0; i < kept.size() && i < (size_t)cap; ++i) { index[i] = kept[i].first; lock_slot[i] = kept[i].second; }
+    *n = (int32_t)kept.size();
     return MCR_OK;
 }
 

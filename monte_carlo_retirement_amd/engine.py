@@ -48,6 +48,28 @@ def growth_form(params: McrParams, working_months: int) -> int:
     return int(mask.value)
 
 
+def month_form(params: McrParams, working_months: int) -> int:
+    """Month form (0 or 1) a whole-path count-only launch of these parameters runs (mcr_k1_month_form; honours
+    MCR_K1_MONTH_FORM); ``ValueError`` if the parameters, or a forced form they do not qualify for, are invalid."""
+    mask = C.c_int32(-1)
+    rc = N.load_library().mcr_k1_month_form(C.byref(params), int(working_months), C.byref(mask))
+    if rc != 0:
+        raise ValueError(N.last_error() or "invalid params / month form")
+    return int(mask.value)
+
+
+def kept_streams(params: McrParams, working_months: int) -> list:
+    """``(index, lock_slot)`` of every ``other_income_streams`` record the path kernel is given, in list order
+    (mcr_k1_kept_streams): records that pay nothing are left out, and the lock slots (-1: an indexed stream has none) are
+    numbered over the kept ones."""
+    cap = max(int(params.n_streams), 1)
+    index, slot, n = (C.c_int32 * cap)(), (C.c_int32 * cap)(), C.c_int32(-1)
+    rc = N.load_library().mcr_k1_kept_streams(C.byref(params), int(working_months), index, slot, cap, C.byref(n))
+    if rc != 0:
+        raise ValueError(N.last_error() or "invalid params")
+    return [(int(index[i]), int(slot[i])) for i in range(n.value)]
+
+
 def stream_start_month_index(current_age: float, working_months: int, start_at_age: float) -> int:
     return int(N.load_library().mcr_stream_start_month_index(current_age, working_months, start_at_age))
 
