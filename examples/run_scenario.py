@@ -9,6 +9,8 @@ switch to the final seed stream, run the final batch, print the response documen
     python examples/run_scenario.py scenarios/config.json --events --full > response.json
     python examples/run_scenario.py scenarios/config.json --working-months 240 --max-expenses
     python examples/run_scenario.py scenarios/config.json --working-months 180 --min-contribution
+    python examples/run_scenario.py scenarios/config.json --min-initial-balance
+    python examples/run_scenario.py scenarios/config.json --min-initial-balance --at-expenses 3000,4000,5000
     python examples/run_scenario.py scenarios/config.json --frontier 180,240,300
     python examples/run_scenario.py scenarios/config.json --grid-months 180,240 --grid-expenses 3000,4000,5000
 
@@ -23,7 +25,11 @@ with its probability and the search curve as one JSON object.  `--frontier` runs
 at once (one grid probe per round) and prints a JSON list of `{working_months, max_monthly_expenses, probability,
 levels_evaluated}`; `--grid-months` with `--grid-expenses` prints the success-probability table of those months x levels.
 `--min-contribution` answers the third one: the smallest monthly contribution (whole cents) that reaches the target when
-retiring after `--working-months` (required), printed with its probability and the search curve as one JSON object."""
+retiring after `--working-months` (required), printed with its probability and the search curve as one JSON object.
+`--min-initial-balance` answers the fourth: the smallest starting balance (whole cents) that reaches the target when retiring
+after `--working-months` (default 0: "retire today"), printed the same way; with `--at-expenses a,b,c` the search runs at each
+of those monthly spending levels in lockstep and the object gains a `frontier` list of `{monthly_expenses,
+min_initial_balance, probability, withdrawal_rate_pct}` — the safe-withdrawal-rate curve, `1200 * expenses / balance`."""
 
 from __future__ import annotations
 
@@ -56,8 +62,12 @@ def main() -> int:
     ap.add_argument("--max-expenses", action="store_true", help="search the maximum monthly expenses instead")
     ap.add_argument("--min-contribution", action="store_true",
                     help="search the minimum monthly contribution at --working-months instead")
+    ap.add_argument("--min-initial-balance", action="store_true",
+                    help="search the minimum initial balance at --working-months (default 0: retire today) instead")
+    ap.add_argument("--at-expenses", default=None,
+                    help="--min-initial-balance: comma-separated monthly expenses, one search each (the withdrawal-rate curve)")
     ap.add_argument("--resolution", type=float, default=1.0,
-                    help="--max-expenses / --min-contribution: stop when the bracket is this narrow")
+                    help="--max-expenses / --min-contribution / --min-initial-balance: stop when the bracket is this narrow")
     ap.add_argument("--frontier", default=None, help="comma-separated working months: maximum monthly expenses at each")
     ap.add_argument("--grid-months", default=None, help="comma-separated working months of a success-probability table")
     ap.add_argument("--grid-expenses", default=None, help="comma-separated monthly expenses of that table")
@@ -66,6 +76,10 @@ def main() -> int:
         ap.error("--min-contribution needs --working-months")
     if args.min_contribution and args.max_expenses:
         ap.error("--min-contribution and --max-expenses are separate questions")
+    if args.min_initial_balance and (args.min_contribution or args.max_expenses):
+        ap.error("--min-initial-balance, --min-contribution and --max-expenses are separate questions")
+    if args.at_expenses and not args.min_initial_balance:
+        ap.error("--at-expenses goes with --min-initial-balance")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank0 = int(os.environ.get("RANK", "0")) == 0
@@ -98,6 +112,8 @@ def main() -> int:
         return max_expenses(args, config, world, rank0)
     if args.min_contribution:
         return min_contribution(args, config, world, rank0)
+    if args.min_initial_balance:
+        return min_initial_balance(args, config, world, rank0)
     if args.frontier or args.grid_months or args.grid_expenses:
         if args.frontier and (args.grid_months or args.grid_expenses):
             ap.error("--frontier and --grid-* are separate questions")
@@ -185,6 +201,45 @@ def min_contribution(args, config: Config, world: int, rank0: bool) -> int:
         "probes": len({e["iteration"] for e in events}), "curve": curve,
         "seconds": round(time.perf_counter() - t0, 3),
     }
+    if rank0:
+        print(json.dumps(out))
+    if world > 1:
+        import torch.distributed as dist
+
+        dist.barrier()
+        dist.destroy_process_group()
+    return 0
+
+
+def min_initial_balance(args, config: Config, world: int, rank0: bool) -> int:
+    from monte_carlo_retirement_amd.simulation import RetirementMonteCarloSimulator
+
+    t0 = time.perf_counter()
+    sim = RetirementMonteCarloSimulator(config, main_seed_override=args.seed, rng=args.rng)
+    wm = 0 if args.working_months is None else int(args.working_months)   # (retire today)
+    events = []
+    if args.at_expenses:
+        levels = _csv(args.at_expenses, float)
+        results = sim.find_minimum_initial_balance_by_expenses(wm, levels, verbose=False, progress_callback=events.append,
+                                                               resolution=args.resolution)
+        # the headline entry: the search at the config's own spending where it is among the levels, else the first
+        head = levels.index(float(config.monthly_expenses)) if float(config.monthly_expenses) in levels else 0
+        balance, prob, curve = results[head]
+        probes = max((e["iteration"] for e in events), default=0)   # (one probe a round, shared by the searches)
+    else:
+        balance, prob, curve = sim.find_minimum_initial_balance(wm, verbose=False, progress_callback=events.append,
+                                                                resolution=args.resolution)
+        probes = len({e["iteration"] for e in events})
+    out = {
+        "scenario": config.Nickname, "rng": args.rng, "working_months": wm,
+        "target_probability": config.target_probability, "min_initial_balance": balance, "probability": prob,
+        "probes": probes, "curve": curve,
+        "seconds": round(time.perf_counter() - t0, 3),
+    }
+    if args.at_expenses:
+        out["frontier"] = [{"monthly_expenses": e, "min_initial_balance": b, "probability": pr,
+                            "withdrawal_rate_pct": 1200.0 * e / b if b > 0 else None}
+                           for e, (b, pr, _) in zip(levels, results)]
     if rank0:
         print(json.dumps(out))
     if world > 1:

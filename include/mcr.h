@@ -344,6 +344,27 @@ int mcr_probe_contributions_rng(const mcr_params* p, const mcr_rng* rng, uint32_
                                 uint64_t* counts, int device, void* hip_stream);
 
 /*
+ * What-if scenarios: success counts of SEVERAL (initial_balance, monthly_contribution, monthly_expenses) records at one
+ * working-month count over the same path range — the probe of the required-starting-balance search and of the
+ * safe-withdrawal-rate curve (balance and spending vary together).  counts[k] equals, bit for bit, the counters of a
+ * count-only mcr_run_batch_rng call with the same arguments and those three fields of *p replaced by scenarios[k].  scenarios
+ * is a HOST array of n_scenarios >= 0 records (0 does nothing; duplicates allowed); every field of every record must be finite
+ * and >= 0 (config.py:56, 57, 59) and everything is validated before anything is enqueued: on an error counts stay untouched
+ * and the message names scenarios[k].<field>.  One scenario: the plain count-only launch.  Philox stream, at most
+ * MCR_INLINE_STREAMS income streams, the tolerance month, n_paths <= 2^31 and at least MCR_SCENARIO_FANOUT_MIN_WAVES
+ * path-wavefronts (environment, default 0): SCENARIO FAN-OUT launches, the contribution fan-out's workgroup (a workgroup per
+ * 64 paths, one wave generating the random numbers of the whole path for up to MCR_MAX_EXPENSE_FANOUT consumer waves) with one
+ * record per consumer wave; the records travel in a stream-ordered device table of 24 B each, released behind the launches.
+ * Otherwise (NumPy stream, longer stream lists, the exact month, allocation refused): one count-only launch per scenario on
+ * internal side streams, joined back onto `hip_stream`.  counts: DEVICE uint64 [n_scenarios][MCR_N_COUNTERS] = {successes,
+ * paths} (zeroed by the call).  Asynchronous like mcr_probe_contributions_rng.
+ */
+typedef struct mcr_scenario { double initial_balance, monthly_contribution, monthly_expenses; } mcr_scenario;
+int mcr_probe_scenarios_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                            uint64_t n_paths, int32_t working_months, const mcr_scenario* scenarios,
+                            int32_t n_scenarios, uint64_t* counts, int device, void* hip_stream);
+
+/*
  * Retirement-month x spending grid: counts[c][k] equals, bit for bit, the counters of a count-only mcr_run_batch_rng call with
  * working_months[c] and p->monthly_expenses = monthly_expenses[c][k], everything else unchanged.  working_months: n_candidates
  * >= 0 months (any order, repeats allowed); monthly_expenses: HOST [n_candidates][n_levels] row-major, each finite and >= 0.

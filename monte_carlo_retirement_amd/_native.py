@@ -184,6 +184,16 @@ def numpy_rng(main_seed: int, child_offset: int = 0, path_seeds_ptr: int = 0) ->
     return r
 
 
+class McrScenario(C.Structure):
+    """One record of a scenario probe (include/mcr.h: mcr_scenario): the three levers success is monotone in."""
+
+    _fields_ = [
+        ("initial_balance", C.c_double),
+        ("monthly_contribution", C.c_double),
+        ("monthly_expenses", C.c_double),
+    ]
+
+
 class McrSizes(C.Structure):
     _fields_ = [
         ("total_months", C.c_int32),
@@ -254,6 +264,7 @@ ABI_SYMBOLS = (
     "mcr_probe_months_rng",
     "mcr_probe_expenses_rng",
     "mcr_probe_contributions_rng",
+    "mcr_probe_scenarios_rng",
     "mcr_probe_grid_rng",
     "mcr_run_batch_multi_host_rng",
     "mcr_run_year_bins_rng",
@@ -341,6 +352,12 @@ def _declare(lib: C.CDLL) -> None:
         P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32, P(C.c_double), C.c_int32,
         C.c_void_p, C.c_int, C.c_void_p,
     ]
+    if hasattr(lib, "mcr_probe_scenarios_rng"):   # (an MCR_HIP_LIBRARY built from an earlier tree, for A/B runs, lacks it)
+        lib.mcr_probe_scenarios_rng.restype = C.c_int
+        lib.mcr_probe_scenarios_rng.argtypes = [
+            P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32, P(McrScenario), C.c_int32,
+            C.c_void_p, C.c_int, C.c_void_p,
+        ]
     lib.mcr_probe_grid_rng.restype = C.c_int
     lib.mcr_probe_grid_rng.argtypes = [
         P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, P(C.c_int32), C.c_int32, P(C.c_double), C.c_int32,

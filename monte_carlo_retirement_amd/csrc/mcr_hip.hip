@@ -69,7 +69,8 @@ struct KernelIO {
     int32_t seg_max_polls;                           // x ~1 us: how long a successor looks for its predecessor's flag before it recomputes the block itself
     // PHASE 5 / 7 (expense / contribution fan-out, mcr_probe_expenses_rng / mcr_probe_contributions_rng): consumer wave j runs
     // level fan_expenses[j] (monthly_expenses / monthly_contribution) and adds its counts to counters + j * MCR_N_COUNTERS;
-    // fan_n = blockDim.x / 64 - 1 levels
+    // fan_n = blockDim.x / 64 - 1 levels.  PHASE 8 (scenario fan-out, mcr_probe_scenarios_rng) reads fan_n only: its records
+    // are a device table (path_kernel's `cand_params`)
     int32_t fan_n;
     // MODE 3 (yearly bins, mcr_run_year_bins_rng) shares the bytes of the fan-out levels: no launch is both, and the layout
     // of the kernel arguments every other variant reads stays what it was
@@ -97,6 +98,9 @@ struct GridCell {
     int32_t snap;                                 // the snapshot column of the row's month
     int32_t pad;
 };
+// PHASE 8 (scenario probe, mcr_probe_scenarios_rng): consumer wave j of a launch runs record j of the launch's device table of
+// mcr_scenario (initial_balance, monthly_contribution, monthly_expenses), through `cand_params` like the grid's records
+static_assert(sizeof(mcr_scenario) == 3 * sizeof(double), "mcr_scenario is three packed doubles");
 constexpr int kSplitVotePairs = 16;   // SPLIT: pairs of months between two stop votes of a workgroup (a power of two)
 constexpr int kSnapFields = 10;   // b1 b2 c1 c2 gacc1 gacc2 infl contrib | pre_fail | Philox carry words
 // Fields per lane of a time-sliced block's hand-over state in front of its lock columns: path_kernel's kSegFixedFields
@@ -235,6 +239,11 @@ __device__ __forceinline__ void year_bins_flush_final(const KernelIO::YearBins& 
 // retirement months with the scenario's own monthly_expenses.  Consumers execute the barriers and votes of PHASE 0's SPLIT
 // consumers over rows 0 .. total_months - 1; lock columns and success counts per level as in PHASE 5.  The month is the
 // issue-bound one (MM): counts are bit-identical to a count-only launch with monthly_contribution = fan_expenses[j].
+// PHASE 8 (SPLIT = true; mcr_probe_scenarios_rng): SCENARIO FAN-OUT = PHASE 7's workgroup, barriers and votes, with three
+// wave-uniform values per consumer wave instead of one: wave j starts from its own initial_balance (the two operations of
+// the plain initial state, in their order), contributes its own monthly_contribution and spends its own monthly_expenses.
+// The launch's records are a device table of mcr_scenario behind `cand_params` (scalar loads, as PHASE 6 reads its GridCell).
+// Counts are bit-identical to a count-only launch with the three fields of the parameter block replaced by record j.
 // EXACT = true: the month in its exact-rounding forms (mcr_device.h) instead of the tolerance form — for configurations whose
 // realized-gains rate lets the reference's denominator clamps bind (DevParams::exact_month), instantiated for the generic XS
 // variants only; -DMCR_K1_EXACT_MONTH builds a library that runs every variant that way (A/B).
@@ -251,7 +260,7 @@ constexpr bool kUniformFixups = false;
 constexpr bool kUniformFixups = true;
 #endif
 template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault, int GF = 0, int MF = 0>
-__global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
+__global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE == 8) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
                                                          const DevParams* __restrict__ cand_params) {
     // MODE 3 (mcr_run_year_bins_rng): YEARLY BINS.  The arithmetic of MODE 2, but wherever that variant stores a yearly sample
     // (nominal balance, real balance, withdrawal rate) the lane bins it instead: cell 0 = below edges[0], cells 1 .. n = the
@@ -270,11 +279,13 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MC
     static_assert(PHASE != 5 || SPLIT, "the expense fan-out is a producer / consumer form");
     static_assert(PHASE != 6 || SPLIT, "the grid fan-out is a producer / consumer form");
     static_assert(PHASE != 7 || SPLIT, "the contribution fan-out is a producer / consumer form");
+    static_assert(PHASE != 8 || SPLIT, "the scenario fan-out is a producer / consumer form");
     // PHASE 4 = PHASE 2 (a candidate's decumulation resumed from its accumulation snapshot) time-sliced like PHASE 3: the
     // 17-month verification window of the search is 17 x 196 workgroups = 2.17 rounds of the resident slots.
     constexpr bool kExpFan = PHASE == 5 || PHASE == 6;    // expense fan-out: the levels are monthly_expenses, resumed at retirement
     constexpr bool kConFan = PHASE == 7;                  // contribution fan-out: the levels are monthly_contribution, the whole path
-    constexpr bool kFan = kExpFan || kConFan;             // fan-out workgroup: one 64-path block, L consumer waves (levels), one producer wave
+    constexpr bool kScnFan = PHASE == 8;                  // scenario fan-out: balance, contribution and spending per wave, the whole path
+    constexpr bool kFan = kExpFan || kConFan || kScnFan;  // fan-out workgroup: one 64-path block, L consumer waves (levels), one producer wave
     constexpr bool kGrid = PHASE == 6;                    // ... of grid row blockIdx.y (GridCell)
     constexpr bool kCand = PHASE == 2 || PHASE == 4 || kExpFan;   // resumes from a PHASE 1 snapshot (PHASE 2 / 4: per-candidate parameter block)
     constexpr bool kSliced = PHASE == 3 || PHASE == 4;    // time-sliced path blocks
@@ -513,6 +524,18 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MC
         return;
     }
     if (kConFan) contrib = io.fan_expenses[fan_j];   // PHASE 7: this consumer wave's contribution level (the producer has returned)
+    // PHASE 8: this consumer wave's record (the producer has returned: fan_j < fan_n, inside the launch's table), three SGPR
+    // pairs; the initial state again, from the record's balance
+    double scn_expenses = 0.0;
+    if constexpr (kScnFan) {
+        const mcr_scenario* const scn = reinterpret_cast<const mcr_scenario*>(cand_params) + fan_j;
+        const double scn_balance = scn->initial_balance;
+        b1 = scn_balance * P.alloc1;             // :499
+        b2 = scn_balance - b1;                   // :500
+        c1 = b1; c2 = b2;                        // :501-502
+        contrib = scn->monthly_contribution;     // :504
+        scn_expenses = scn->monthly_expenses;
+    }
     if (PHASE == 1) while (snap_i < io.n_snap && io.snap_months[snap_i] == 0) save_snapshot();
     // PHASE 3: a later segment of a time-sliced block takes its lanes' state over from its predecessor
     // b1 b2 c1 c2 gacc1 gacc2 infl | flags | Philox carry | (per-path outputs: balance and price level at retirement, the
@@ -647,7 +670,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7) ? 64 * (MC
                 double g1, ginf, g2;
                 if (kStaged) growth(wm + rmi, g1, ginf, g2);           // staged factors: the LDS reads are issued early
                 const double price = infl;                             // :644
-                const double expenses = (kExpFan ? fan_expenses : P.monthly_expenses) * price;   // :645-647
+                const double expenses = (kExpFan ? fan_expenses : kScnFan ? scn_expenses : P.monthly_expenses) * price;   // :645-647
                 // exact form: income accumulates (:649-677) and need = max(0, expenses - income); tolerance form: `income` runs
                 // DOWN from the expenses, one FMA per indexed stream ((amount keep) price), one subtraction per frozen stream
                 // (its slot holds the netted amount): need = max(0, what is left)
@@ -2225,7 +2248,7 @@ static int probe_shared_prefix(const mcr_params* p, const mcr_rng* rng, uint32_t
     return MCR_OK;
 }
 
-// LDS of a level fan-out launch (path_kernel PHASE 5 / 6 / 7): STATIC = the math tables and the double-buffered 64-column stage
+// LDS of a level fan-out launch (path_kernel PHASE 5 / 6 / 7 / 8): STATIC = the math tables and the double-buffered 64-column stage
 // (+ the unused summary / segment words); DYNAMIC = the level counters and [n_lock_slots][64] lock columns per consumer wave.
 // Every lock slot stays in LDS (no overflow block in this form): the levels per launch are lowered until they fit.
 static size_t fanout_static_lds() { return (size_t)kMathTabBytes + (size_t)2 * 6 * 64 * sizeof(double) + 512; }   // (16 640 B compiled)
@@ -2326,6 +2349,44 @@ static int probe_contributions_fanout(const mcr_params* p, const mcr_rng* rng, u
     launch_level_fanout<7>(d, io, levels, LevelGroups(n_levels, lmax), counts, stream);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "contribution fan-out probe");
+    return MCR_OK;
+}
+
+// Several (initial_balance, monthly_contribution, monthly_expenses) records over the same paths, Philox stream: scenario fan-out
+// launches (PHASE 8) over groups of at most fanout_max_levels records, the whole path each, like the contribution fan-out.
+// The records go to ONE stream-ordered device table (SnapshotBlock's records, no snapshot column), filled with one async
+// copy and released behind the launches; group g's launch gets the table at its first record through `cand_params`.
+// Nothing derive_params, the lock-slot plan or the tax variant reads depends on the three fields (they are copied through),
+// so one parameter block serves every record.  Returns MCR_ERR_UNSUPPORTED, having enqueued nothing, for shapes this form
+// does not cover and when the table's allocation is refused.
+static int probe_scenarios_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                                  int32_t wm, const mcr_scenario* scenarios, int32_t n_scenarios, uint64_t* counts, hipStream_t stream) {
+    DevParams d;
+    int lmax = 0;
+    if (int rc = plan_level_fanout(p, rng, n_paths, wm, n_scenarios, fanout_min_waves("MCR_SCENARIO_FANOUT_MIN_WAVES"), &d, &lmax)) return rc;
+    KernelIO io = make_io(rng, nullptr, stream_id, path_begin, n_paths);
+    SnapshotBlock table(stream);
+    hipError_t e = hipSuccess;
+    if (!table.attach(io, 0, scenarios, (size_t)n_scenarios * sizeof(mcr_scenario), &e, SIZE_MAX)) return MCR_ERR_UNSUPPORTED;
+    io.snap = nullptr;   // (no snapshot column: the block is the table alone)
+    if (e == hipSuccess) {
+        const mcr_scenario* d_table = (const mcr_scenario*)table.records;
+        const dim3 grid((unsigned)((n_paths + 63) / 64));
+        const LevelGroups groups(n_scenarios, lmax);
+        for_tax_variant(d, [&](auto T, auto A) {
+            groups.for_each([&](int, int first, int lg) {
+                KernelIO fio = io;
+                fio.out.counters = counts + (size_t)first * MCR_N_COUNTERS;
+                fio.fan_n = lg;
+                hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 8, true>), grid, dim3(64 * (lg + 1)),
+                                   fanout_dynamic_lds(d, lg), stream, d, fio, (const DevParams*)(d_table + first));
+            });
+        });
+        e = hipGetLastError();
+    }
+    const hipError_t ef = table.mem.release();
+    if (e != hipSuccess) return hip_fail(e, "scenario fan-out probe");
+    if (ef != hipSuccess) return hip_fail(ef, "scenario fan-out probe (free)");
     return MCR_OK;
 }
 
@@ -2554,6 +2615,47 @@ int mcr_probe_contributions_rng(const mcr_params* p, const mcr_rng* rng, uint32_
     MCR_ENTER_DEVICE(device);
     return probe_levels<probe_contributions_fanout>(p, rng, stream_id, path_begin, n_paths, working_months, &mcr_params::monthly_contribution,
                                                     "monthly_contribution", 57, monthly_contributions, n_levels, counts, device, (hipStream_t)hip_stream);
+}
+
+int mcr_probe_scenarios_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                            uint64_t n_paths, int32_t working_months, const mcr_scenario* scenarios,
+                            int32_t n_scenarios, uint64_t* counts, int device, void* hip_stream) {
+    MCR_ENTER_DEVICE(device);
+    if (n_scenarios < 0) { set_error("n_scenarios %d must be >= 0", n_scenarios); return MCR_ERR_INVALID_ARG; }
+    if (n_scenarios == 0) return MCR_OK;
+    if (!scenarios || !counts) { set_error("null scenarios / counts"); return MCR_ERR_INVALID_ARG; }
+    // validate every record BEFORE enqueueing anything (counts stay untouched on an error)
+    int rc = validate_months(p, &working_months, 1);
+    if (rc != MCR_OK) return rc;
+    rc = check_rng(rng);
+    if (rc != MCR_OK) return rc;
+    static const struct { double mcr_scenario::*field; const char* name; int config_line; } kFields[3] = {
+        {&mcr_scenario::initial_balance, "initial_balance", 56},
+        {&mcr_scenario::monthly_contribution, "monthly_contribution", 57},
+        {&mcr_scenario::monthly_expenses, "monthly_expenses", 59}};
+    for (int32_t k = 0; k < n_scenarios; ++k)
+        for (const auto& f : kFields) {
+            const double v = scenarios[k].*(f.field);
+            if (!(std::isfinite(v) && v >= 0.0)) {
+                set_error("scenarios[%d].%s = %g: must be finite and >= 0 (config.py:%d)", k, f.name, v, f.config_line);
+                return MCR_ERR_INVALID_ARG;
+            }
+        }
+    hipStream_t main = (hipStream_t)hip_stream;
+    rc = zero_counters(counts, (size_t)n_scenarios, main);
+    if (rc != MCR_OK) return rc;
+    mcr_params q = *p;
+    auto launch_scenario = [&](int k, hipStream_t s) {
+        q.initial_balance = scenarios[k].initial_balance;
+        q.monthly_contribution = scenarios[k].monthly_contribution;
+        q.monthly_expenses = scenarios[k].monthly_expenses;
+        const mcr_outputs o = counters_only(counts + (size_t)k * MCR_N_COUNTERS);
+        return launch_paths(&q, rng, stream_id, path_begin, n_paths, working_months, nullptr, &o, s);
+    };
+    if (n_scenarios == 1) return launch_scenario(0, main);
+    rc = probe_scenarios_fanout(p, rng, stream_id, path_begin, n_paths, working_months, scenarios, n_scenarios, counts, main);
+    if (rc != MCR_ERR_UNSUPPORTED) return rc;     // (unsupported shape / allocation refused: one launch per scenario below)
+    return fork_join(device, main, n_scenarios, launch_scenario);
 }
 
 int mcr_probe_grid_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,

@@ -17,7 +17,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from . import _native as N
-from ._native import McrOutputs, McrParams, McrRng, McrSizes, McrYearBins
+from ._native import McrOutputs, McrParams, McrRng, McrScenario, McrSizes, McrYearBins
 
 SUMMARY_FIELDS = (
     "start_balance",
@@ -574,6 +574,33 @@ def probe_contributions(params: McrParams, seed, stream_id: int, path_begin: int
     ``[len(monthly_contributions), 2]`` = ``{successes, paths}``; asynchronous (reading it synchronises)."""
     return _probe_levels("mcr_probe_contributions_rng", params, seed, stream_id, path_begin, n_paths, working_months,
                          monthly_contributions, device)
+
+
+def probe_scenarios(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
+                    scenarios, device: int = 0):
+    """Success counters of several what-if scenarios at one working-month count over the same path range
+    (``mcr_probe_scenarios_rng``).  ``scenarios`` is a sequence of ``(initial_balance, monthly_contribution,
+    monthly_expenses)`` 3-tuples; scenario k counts exactly what a count-only launch with those three fields of `params`
+    replaced counts.  Up to ``MCR_MAX_EXPENSE_FANOUT`` scenarios share each path's random numbers.  Returns a device int64
+    tensor ``[len(scenarios), 2]`` = ``{successes, paths}``; asynchronous (reading it synchronises)."""
+    import torch
+
+    N.require_device()
+    records = [tuple(float(x) for x in s) for s in scenarios]
+    if any(len(r) != 3 for r in records):
+        raise ValueError("every scenario is (initial_balance, monthly_contribution, monthly_expenses)")
+    arr = (McrScenario * max(1, len(records)))(*[McrScenario(*r) for r in records])
+    counts = torch.empty((len(records), N.MCR_N_COUNTERS), dtype=torch.int64, device=torch.device("cuda", int(device)))
+    if not records:
+        return counts
+    rng = _as_rng(seed)
+    stream = torch.cuda.current_stream(int(device)).cuda_stream
+    rc = N.load_library().mcr_probe_scenarios_rng(
+        C.byref(params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), int(working_months), arr,
+        len(records), counts.data_ptr(), int(device), C.c_void_p(stream),
+    )
+    N.check(rc, "mcr_probe_scenarios_rng")
+    return counts
 
 
 def probe_grid(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months, levels_2d,

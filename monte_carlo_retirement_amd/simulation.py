@@ -909,6 +909,103 @@ class RetirementMonteCarloSimulator:
                             f"({len(curve)} levels evaluated).")
         return contribution, prob, curve
 
+    # ---- what-if scenarios and the required-starting-balance search -----------------------------------
+    def success_probability_by_scenarios(self, working_months: int, scenarios: Sequence[dict],
+                                         num_simulations: Optional[int] = None) -> np.ndarray:
+        """Success % of each what-if scenario at ``working_months``, over the active seed stream's batch of
+        ``num_simulations`` paths (default ``num_simulations_main``), from the scenario probe (``mcr_probe_scenarios_rng``).
+        A scenario is a mapping with any subset of the keys ``initial_balance``, ``monthly_contribution``,
+        ``monthly_expenses``: a missing key takes the config's value, an unknown key raises ``ValueError`` (before any
+        device work).  Aligned with the input; each value equals, bit for bit,
+        ``_success_probability(run_monte_carlo_simulations(working_months, n)[0])`` of a simulator whose config differs in
+        those fields only.  Under a process group the scenarios go through ``distributed.probe_candidates`` (as candidate
+        indices), so every rank returns the same array."""
+        from .nestegg import scenario_records
+
+        p = self.params_model
+        records = scenario_records(scenarios, (p.initial_balance, p.monthly_contribution, p.monthly_expenses))
+        if not records:
+            return np.zeros(0, dtype=np.float64)
+        n = int(p.num_simulations_main if num_simulations is None else num_simulations)
+        wm = int(working_months)
+        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
+
+        def probe(path_begin, count, idx):
+            return E.probe_scenarios(params, rng, self._stream_id, path_begin, count, wm, [records[i] for i in idx], device=dev)
+
+        counts = D.probe_candidates(list(range(len(records))), n, self.shard_min_paths, probe)
+        return np.array([self._count_percent(counts[i, N.MCR_CTR_SUCCESS], n) for i in range(len(records))], dtype=np.float64)
+
+    def find_minimum_initial_balance(
+        self,
+        working_months: int,
+        verbose: bool = True,
+        progress_callback: Optional[Callable[[dict], None]] = None,
+        resolution: float = 1.0,
+    ) -> Tuple[float, float, List[Dict[str, float]]]:
+        """Smallest ``initial_balance`` (whole cents) that reaches ``target_probability`` when retiring after
+        ``working_months``: search stream, ``num_simulations_search`` paths, ``MCR_MAX_EXPENSE_FANOUT`` levels per probe
+        (`nestegg.search_minimum_initial_balance`, starting at ``max(initial_balance, 1)``).  Returns ``(balance,
+        probability, curve)``; ``balance == 0.0`` when nothing is needed up front and ``-1.0`` when even the cap misses the
+        target.  Valid at ``working_months == 0`` ("retire today"), where the starting balance is the only lever.
+        Deterministic for a given seed, and the same on every rank."""
+        return self._minimum_initial_balances(working_months, [float(self.params_model.monthly_expenses)], verbose,
+                                              progress_callback, resolution, tag_events=False)[0]
+
+    def find_minimum_initial_balance_by_expenses(
+        self,
+        working_months: int,
+        monthly_expenses: Sequence[float],
+        verbose: bool = True,
+        progress_callback: Optional[Callable[[dict], None]] = None,
+        resolution: float = 1.0,
+    ) -> List[Tuple[float, float, List[Dict[str, float]]]]:
+        """`find_minimum_initial_balance` at several spending levels at once (the safe-withdrawal-rate curve is ``12 *
+        expenses / balance``): one ``(balance, probability, curve)`` per entry of ``monthly_expenses``, each equal to what
+        ``find_minimum_initial_balance(working_months)`` returns on a config with that ``monthly_expenses``, for the same
+        seed.  The searches run in lockstep (`nestegg.search_minimum_initial_balance_many`): every round is ONE
+        `success_probability_by_scenarios` call over the (balance, expenses) points of all unfinished searches, which the
+        library takes ``MCR_MAX_EXPENSE_FANOUT`` to a launch.  ``progress_callback`` events also carry
+        ``monthly_expenses``."""
+        return self._minimum_initial_balances(working_months, monthly_expenses, verbose, progress_callback, resolution,
+                                              tag_events=True)
+
+    def _minimum_initial_balances(self, working_months: int, monthly_expenses: Sequence[float], verbose: bool,
+                                  progress_callback: Optional[Callable[[dict], None]], resolution: float, tag_events: bool):
+        """The body of `find_minimum_initial_balance` (one spending level, the config's, events untagged) and
+        `find_minimum_initial_balance_by_expenses`."""
+        from .nestegg import INITIAL_BALANCE_CAP, search_minimum_initial_balance_many
+
+        expenses = [float(x) for x in monthly_expenses]
+        self.use_search_seeds()
+        p = self.params_model
+        wm = int(working_months)
+        n_sims, target = int(p.num_simulations_search), float(p.target_probability)
+        if verbose:
+            logger.info(f"Searching the minimum initial balance at {wm} working months for '{p.Nickname}' at "
+                        f"{len(expenses)} spending level(s) (target {target:.2f}%, {n_sims} sims per level, resolution {resolution}).")
+
+        def probe_rows(rows, levels_2d):
+            points = [{"initial_balance": b, "monthly_expenses": expenses[i]} for i, levels in zip(rows, levels_2d) for b in levels]
+            probs = self.success_probability_by_scenarios(wm, points, n_sims).tolist()
+            out, at = [], 0
+            for levels in levels_2d:
+                out.append(probs[at:at + len(levels)])
+                at += len(levels)
+            return out
+
+        start = max(float(p.initial_balance), 1.0)
+        results = search_minimum_initial_balance_many(
+            probe_rows, target, [start] * len(expenses), levels_per_call=N.MCR_MAX_EXPENSE_FANOUT, resolution=resolution,
+            cap=INITIAL_BALANCE_CAP, on_level=progress_callback, monthly_expenses=expenses if tag_events else None)
+        if verbose:
+            for e, (balance, prob, curve) in zip(expenses, results):
+                if balance < 0:
+                    logger.warning(f"Target not met at any initial balance: {prob:.2f}% at {wm} months, {e:.2f} per month.")
+                else:
+                    logger.info(f"  {e:.2f} per month: initial balance {balance:.2f} with prob {prob:.2f}% "
+                                f"({len(curve)} levels evaluated).")
+        return results
 
     def _grid_probabilities(self, working_months: Sequence[int], levels_2d: Sequence[Sequence[float]],
                             num_simulations: int) -> np.ndarray:
