@@ -365,6 +365,37 @@ int mcr_probe_scenarios_rng(const mcr_params* p, const mcr_rng* rng, uint32_t st
                             int32_t n_scenarios, uint64_t* counts, int device, void* hip_stream);
 
 /*
+ * Market-assumption stress: success counts of SEVERAL records of (initial_balance, monthly_contribution, monthly_expenses, the
+ * lognormal parameters of equity, inflation and the premium over inflation, their correlation) at one working-month count over
+ * the same path range — the probe of the stress table and of the break-even assumption search.  counts[k] equals, bit for
+ * bit, the counters of a count-only mcr_run_batch_rng call with the same arguments and those ten fields of *p replaced by
+ * records[k].  records is a HOST array of n_records >= 0 records (0 does nothing; duplicates allowed); every record is held to
+ * mcr_validate_params' rules for the same fields (amounts finite and >= 0; finite mu, sigma >= 0 and |mu|/12 + 40
+ * sigma/sqrt(12) < 700; rho in [-1, 1]) and everything is validated before anything is enqueued: on an error counts stay
+ * untouched and the message names records[k].<field>.  One record: the plain count-only launch.  Philox stream, at most
+ * MCR_INLINE_STREAMS income streams, the tolerance month, n_paths <= 2^31 and at least MCR_ASSUMPTION_FANOUT_MIN_WAVES
+ * path-wavefronts (environment, default 0): ASSUMPTION FAN-OUT launches, the scenario fan-out's workgroup in which the producer
+ * wave stages the path's standard normals (as radius and cosine / sine: they depend on the path alone) and each of up to
+ * MCR_MAX_EXPENSE_FANOUT consumer waves applies its own record's market to them — the operations of the plain launch in
+ * their order; the records travel in a stream-ordered device table of 80 B each, derived by the host code that derives a
+ * parameter block, released behind the launches.  Otherwise (NumPy stream, longer stream lists, the exact month, allocation
+ * refused): one count-only launch per record on internal side streams, joined back onto `hip_stream`.  counts: DEVICE uint64
+ * [n_records][MCR_N_COUNTERS] = {successes, paths} (zeroed by the call).  Asynchronous like mcr_probe_scenarios_rng.
+ * *p itself must pass mcr_validate_params, its own ten fields included, on every route (checked first, with the records).
+ * mcr_probe_assumptions_last_fanout_launches reports, for the calling thread's last call, how many assumption fan-out
+ * launches it enqueued: ceil(n_records / records per launch) on the fan-out route, 0 on the others and after an error.
+ */
+typedef struct mcr_assumptions {
+    double initial_balance, monthly_contribution, monthly_expenses;
+    double inv1_mu_log, inv1_sigma_log, inf_mu_log, inf_sigma_log, prem_mu_log, prem_sigma_log;
+    double equity_inflation_rho;
+} mcr_assumptions;
+int mcr_probe_assumptions_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                              uint64_t n_paths, int32_t working_months, const mcr_assumptions* records,
+                              int32_t n_records, uint64_t* counts, int device, void* hip_stream);
+int mcr_probe_assumptions_last_fanout_launches(void);
+
+/*
  * Retirement-month x spending grid: counts[c][k] equals, bit for bit, the counters of a count-only mcr_run_batch_rng call with
  * working_months[c] and p->monthly_expenses = monthly_expenses[c][k], everything else unchanged.  working_months: n_candidates
  * >= 0 months (any order, repeats allowed); monthly_expenses: HOST [n_candidates][n_levels] row-major, each finite and >= 0.

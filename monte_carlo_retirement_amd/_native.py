@@ -194,6 +194,24 @@ class McrScenario(C.Structure):
     ]
 
 
+class McrAssumptions(C.Structure):
+    """One record of an assumption probe (include/mcr.h: mcr_assumptions): the three scenario levers and the market's seven
+    lognormal parameters, i.e. the ten fields of mcr_params the record replaces."""
+
+    _fields_ = [
+        ("initial_balance", C.c_double),
+        ("monthly_contribution", C.c_double),
+        ("monthly_expenses", C.c_double),
+        ("inv1_mu_log", C.c_double),
+        ("inv1_sigma_log", C.c_double),
+        ("inf_mu_log", C.c_double),
+        ("inf_sigma_log", C.c_double),
+        ("prem_mu_log", C.c_double),
+        ("prem_sigma_log", C.c_double),
+        ("equity_inflation_rho", C.c_double),
+    ]
+
+
 class McrSizes(C.Structure):
     _fields_ = [
         ("total_months", C.c_int32),
@@ -265,6 +283,8 @@ ABI_SYMBOLS = (
     "mcr_probe_expenses_rng",
     "mcr_probe_contributions_rng",
     "mcr_probe_scenarios_rng",
+    "mcr_probe_assumptions_rng",
+    "mcr_probe_assumptions_last_fanout_launches",
     "mcr_probe_grid_rng",
     "mcr_run_batch_multi_host_rng",
     "mcr_run_year_bins_rng",
@@ -358,6 +378,14 @@ def _declare(lib: C.CDLL) -> None:
             P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32, P(McrScenario), C.c_int32,
             C.c_void_p, C.c_int, C.c_void_p,
         ]
+    if hasattr(lib, "mcr_probe_assumptions_rng"):   # (likewise)
+        lib.mcr_probe_assumptions_rng.restype = C.c_int
+        lib.mcr_probe_assumptions_rng.argtypes = [
+            P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32, P(McrAssumptions), C.c_int32,
+            C.c_void_p, C.c_int, C.c_void_p,
+        ]
+        lib.mcr_probe_assumptions_last_fanout_launches.restype = C.c_int
+        lib.mcr_probe_assumptions_last_fanout_launches.argtypes = []
     lib.mcr_probe_grid_rng.restype = C.c_int
     lib.mcr_probe_grid_rng.argtypes = [
         P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, P(C.c_int32), C.c_int32, P(C.c_double), C.c_int32,

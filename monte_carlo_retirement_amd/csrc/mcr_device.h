@@ -294,9 +294,9 @@ struct PairCarry { uint32_t w2, w3; };
 // GEN: how the Philox blocks are drawn.  kGenPlain = philox4x32_10 on the whole counter; kGenUniform = philox_path_rounds
 // with the wave's path_hi (wave-uniform: right only when PhiloxPath::hi_uniform); kGenGeneral = philox_path_rounds with each
 // lane's path_hi.  All three give the same words wherever they are right.
-// Side effects: the six stage slots of the lane and, in HALF 0, the carry — nothing else.  growth_rows2 relies on that (a
-// straddling wave runs the form twice and the second pass overwrites the first); an output added here must be
-// overwritten the same way.
+// Side effects: the lane's stage slots (six factors, growth_rows2_form; nine parts, growth_parts2_stage_form) and, in HALF 0,
+// the carry — nothing else.  growth_rows2 and growth_parts2 rely on that (a straddling wave runs the form twice and the second
+// pass overwrites the first); an output added here must be overwritten the same way.
 enum { kGenPlain = 0, kGenUniform = 1, kGenGeneral = 2 };
 // GF: the launch's GROWTH FORM, a two-bit mask of what its parameters make unnecessary (chosen on the host, mcr_hip.hip:
 // growth_form_of; every value is bit for bit the general form's wherever it may be used).
@@ -304,9 +304,13 @@ enum { kGenPlain = 0, kGenUniform = 1, kGenGeneral = 2 };
 //   kGrowthRhoZero:   rho = 0 -> binf_rho is an exact zero and x_inf's first term, fma(+-0 r0, t0, y) = y, is dropped (only the
 //                     sign of a zero sum can differ, and exp maps both zeros to 1)
 enum { kGrowthNarrowExp = 1, kGrowthRhoZero = 2 };
-template <int HALF, int COLS, int GEN, int GF = 0>
-__device__ __forceinline__ void growth_rows2_form(const DevParams& P, const MathRegs& M, uint64_t seed, uint32_t stream_id, uint64_t path,
-                                                  const PhiloxPath& Q, uint32_t t, const double* tab, double* stage, PairCarry& C) {
+// The form in two steps.  growth_parts2_form: the PARTS of the half's six normals — they depend on the path alone (Philox
+// rounds, Box-Muller radius and angle).  growth_factors_row: a month's three factors (equity, inflation, premium) from the parts and a MARKET, any
+// object with the seven members a1, b1, ainf, binf_rho, binf_rho_c, aprem, bprem (DevParams, or a record of the assumption
+// fan-out, path_kernel PHASE 9, whose consumer waves each apply their own market to the parts the producer staged).
+template <int HALF, int GEN>
+__device__ __forceinline__ void growth_parts2_form(const MathRegs& M, uint64_t seed, uint32_t stream_id, uint64_t path, const PhiloxPath& Q,
+                                                   uint32_t t, const double* tab, double (&rad)[3], double (&trig)[6], PairCarry& C) {
     auto draw = [&](uint32_t block, uint32_t (&x)[4]) {
         if (GEN == kGenPlain)
             philox4x32_10((uint32_t)path, (uint32_t)(path >> 32), block, stream_id, (uint32_t)seed, (uint32_t)(seed >> 32), x);
@@ -314,7 +318,6 @@ __device__ __forceinline__ void growth_rows2_form(const DevParams& P, const Math
             philox_path_rounds<GEN == kGenUniform>(Q, block, (uint32_t)seed, (uint32_t)(seed >> 32), x);
     };
     // pair i: radius rad[i], trig[2 i] = cos, trig[2 i + 1] = sin; normal j of the half = rad[j >> 1] * trig[j]
-    double rad[3], trig[6];
     uint32_t x[4];
     if (HALF == 0) {
         draw(3u * t, x);
@@ -329,34 +332,74 @@ __device__ __forceinline__ void growth_rows2_form(const DevParams& P, const Math
         bm_parts<GEN != kGenPlain>(x[0], x[1], tab, M, rad[1], trig[2], trig[3]);
         bm_parts<GEN != kGenPlain>(x[2], x[3], tab, M, rad[2], trig[4], trig[5]);
     }
-    // The three log-returns of a month, x = a + b z (:473) with z_inf = rho n0 + rho_c n1 (:461-464), written on the
-    // PARTS of the normals: x_eq = (b1 r) t + a1, x_inf = (binf rho r0) t0 + ((binf rho_c r1) t1 + a_inf), x_prem
-    // likewise — the same eight fp64 operations as "normals first", but every FMA now has ONE scalar operand (a VOP3
-    // instruction reads at most one: b z + a with a and b both in SGPRs cost two v_mov_b32 per evaluation, six a month).
-    // The product is associated differently from shock_row_seq's (b (r t) vs (b r) t): the arguments of exp agree to
-    // ~1e-17, a tenth of an ulp of the growth factor.
-    // (v_fma_f64 with the SCALAR addend spelled out: left to itself the compiler picks the two-address v_fmac_f64 and
-    //  copies the scalar into its accumulator first — the very two v_mov_b32 this arrangement is there to avoid)
+}
+// The three log-returns of a month, x = a + b z (:473) with z_inf = rho n0 + rho_c n1 (:461-464), written on the
+// PARTS of the normals: x_eq = (b1 r) t + a1, x_inf = (binf rho r0) t0 + ((binf rho_c r1) t1 + a_inf), x_prem
+// likewise — the same eight fp64 operations as "normals first", but every FMA now has ONE scalar operand (a VOP3
+// instruction reads at most one: b z + a with a and b both in SGPRs cost two v_mov_b32 per evaluation, six a month).
+// The product is associated differently from shock_row_seq's (b (r t) vs (b r) t): the arguments of exp agree to
+// ~1e-17, a tenth of an ulp of the growth factor.
+// (re, te), (ri, ti), (rp, tp): radius and cosine / sine of the month's equity, inflation and premium normals.
+// SADD: the market is wave-uniform in SGPRs and the addend of each FMA is spelled out as the scalar operand (v_fma_f64: left
+// to itself the compiler picks the two-address v_fmac_f64 and copies the scalar into its accumulator first — the very two
+// v_mov_b32 this arrangement is there to avoid).  SADD = false: the same operations on a market held in VGPRs.
+template <int GF, bool SADD, typename MARKET>
+__device__ __forceinline__ void growth_factors_row(const MARKET& K, double re, double te, double ri, double ti, double rp, double tp,
+                                                   const double* tab, const MathRegs& M, double& g1, double& ginf, double& gprem) {
     auto fma_vvs = [](double a, double b, double c_scalar) {
         double d;
-        asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(c_scalar));
+        if constexpr (SADD) asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(c_scalar));
+        else d = __builtin_fma(a, b, c_scalar);
         return d;
     };
+    const double x_eq = fma_vvs(K.b1 * re, te, K.a1);
+    const double x_inf = (GF & kGrowthRhoZero) ? fma_vvs(K.binf_rho_c * ri, ti, K.ainf)
+                                               : __builtin_fma(K.binf_rho * re, te, fma_vvs(K.binf_rho_c * ri, ti, K.ainf));
+    const double x_prem = fma_vvs(K.bprem * rp, tp, K.aprem);
+    constexpr bool kNarrow = (GF & kGrowthNarrowExp) != 0;
+    g1 = fexp<true, kNarrow>(x_eq, tab, M);
+    ginf = fexp<true, kNarrow>(x_inf, tab, M);
+    gprem = fexp<true, kNarrow>(x_prem, tab, M);      // (the caller forms g2 = ginf * gprem, :532, where it uses it)
+}
+template <int HALF, int COLS, int GEN, int GF = 0>
+__device__ __forceinline__ void growth_rows2_form(const DevParams& P, const MathRegs& M, uint64_t seed, uint32_t stream_id, uint64_t path,
+                                                  const PhiloxPath& Q, uint32_t t, const double* tab, double* stage, PairCarry& C) {
+    double rad[3], trig[6];
+    growth_parts2_form<HALF, GEN>(M, seed, stream_id, path, Q, t, tab, rad, trig, C);
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         const int je = 3 * r, ji = 3 * r + 1, jp = 3 * r + 2;
-        const double x_eq = fma_vvs(P.b1 * rad[je >> 1], trig[je], P.a1);
-        const double x_inf = (GF & kGrowthRhoZero) ? fma_vvs(P.binf_rho_c * rad[ji >> 1], trig[ji], P.ainf)
-                                                   : __builtin_fma(P.binf_rho * rad[je >> 1], trig[je], fma_vvs(P.binf_rho_c * rad[ji >> 1], trig[ji], P.ainf));
-        const double x_prem = fma_vvs(P.bprem * rad[jp >> 1], trig[jp], P.aprem);
-        constexpr bool kNarrow = (GF & kGrowthNarrowExp) != 0;
-        const double g1 = fexp<true, kNarrow>(x_eq, tab, M);
-        const double ginf = fexp<true, kNarrow>(x_inf, tab, M);
-        const double gprem = fexp<true, kNarrow>(x_prem, tab, M);
+        double g1, ginf, gprem;
+        growth_factors_row<GF, true>(P, rad[je >> 1], trig[je], rad[ji >> 1], trig[ji], rad[jp >> 1], trig[jp], tab, M, g1, ginf, gprem);
         stage[(3 * r + 0) * COLS] = g1;
         stage[(3 * r + 1) * COLS] = ginf;
         stage[(3 * r + 2) * COLS] = ginf * gprem;                               // :532
     }
+}
+// The assumption fan-out's producer (path_kernel PHASE 9) stages the PARTS of a half instead of its factors: nine doubles per
+// lane, `stage[i * COLS]` = rad[i] for i < 3 and `stage[(3 + j) * COLS]` = trig[j].  Side effects as growth_rows2_form's: the
+// lane's nine slots and, in HALF 0, the carry (a straddling wave's second pass overwrites both).
+constexpr int kPartsPerPair = 9;
+template <int HALF, int COLS, int GEN>
+__device__ __forceinline__ void growth_parts2_stage_form(const MathRegs& M, uint64_t seed, uint32_t stream_id, uint64_t path,
+                                                         const PhiloxPath& Q, uint32_t t, const double* tab, double* stage, PairCarry& C) {
+    double rad[3], trig[6];
+    growth_parts2_form<HALF, GEN>(M, seed, stream_id, path, Q, t, tab, rad, trig, C);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) stage[i * COLS] = rad[i];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) stage[(3 + j) * COLS] = trig[j];
+}
+// ... and a consumer's month `row` of the staged pair (r = row & 1, wave-uniform) under its own market: row 0 of a pair is
+// normals 0, 1, 2 of the half (radii 0, 0, 1), row 1 is normals 3, 4, 5 (radii 1, 2, 2)
+template <int COLS, typename MARKET>
+__device__ __forceinline__ void growth_factors_staged(const MARKET& K, const double* pair, int r, const double* tab, const MathRegs& M,
+                                                      double& g1, double& ginf, double& g2) {
+    const double* rd = pair + (size_t)r * COLS;                 // rad[r], rad[2 r] = rd[r COLS], rad[1 + r] = rd[COLS]
+    const double* tg = pair + (size_t)(3 + 3 * r) * COLS;       // trig[3 r ..]
+    double gprem;
+    growth_factors_row<0, false>(K, rd[0], tg[0], rd[(size_t)r * COLS], tg[COLS], rd[COLS], tg[2 * COLS], tab, M, g1, ginf, gprem);
+    g2 = ginf * gprem;                                                          // :532
 }
 // PER_PATH (the count-only kernels without an annual-gains tax: the issue-bound launches): every wavefront runs the form
 // with a wave-uniform path_hi — one straight-line block, the Philox words interleaved with the fp64 work of the pairs (a
@@ -380,6 +423,22 @@ __device__ __forceinline__ void growth_rows2(const DevParams& P, const MathRegs&
         PairCarry C2 = C;
         asm volatile("" : "+v"(C2.w2), "+v"(C2.w3));
         growth_rows2_form<HALF, COLS, kGenGeneral, GF>(P, M, seed, stream_id, path, Q, t, tab, stage, C2);
+        C = C2;
+    }
+}
+// growth_rows2 for the assumption fan-out's producer: the parts of the pair, staged (growth_parts2_stage_form)
+template <int HALF, int COLS, bool PER_PATH>
+__device__ __forceinline__ void growth_parts2(const MathRegs& M, uint64_t seed, uint32_t stream_id, uint64_t path, const PhiloxPath& Q,
+                                              uint32_t t, const double* tab, double* stage, PairCarry& C) {
+    if (!PER_PATH) {
+        growth_parts2_stage_form<HALF, COLS, kGenPlain>(M, seed, stream_id, path, Q, t, tab, stage, C);
+        return;
+    }
+    growth_parts2_stage_form<HALF, COLS, kGenUniform>(M, seed, stream_id, path, Q, t, tab, stage, C);
+    if (__builtin_expect(!Q.hi_uniform, 0)) {
+        PairCarry C2 = C;
+        asm volatile("" : "+v"(C2.w2), "+v"(C2.w3));
+        growth_parts2_stage_form<HALF, COLS, kGenGeneral>(M, seed, stream_id, path, Q, t, tab, stage, C2);
         C = C2;
     }
 }

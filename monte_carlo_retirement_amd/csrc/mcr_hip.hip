@@ -69,8 +69,8 @@ struct KernelIO {
     int32_t seg_max_polls;                           // x ~1 us: how long a successor looks for its predecessor's flag before it recomputes the block itself
     // PHASE 5 / 7 (expense / contribution fan-out, mcr_probe_expenses_rng / mcr_probe_contributions_rng): consumer wave j runs
     // level fan_expenses[j] (monthly_expenses / monthly_contribution) and adds its counts to counters + j * MCR_N_COUNTERS;
-    // fan_n = blockDim.x / 64 - 1 levels.  PHASE 8 (scenario fan-out, mcr_probe_scenarios_rng) reads fan_n only: its records
-    // are a device table (path_kernel's `cand_params`)
+    // fan_n = blockDim.x / 64 - 1 levels.  PHASE 8 / 9 (scenario / assumption fan-out, mcr_probe_scenarios_rng /
+    // mcr_probe_assumptions_rng) read fan_n only: their records are a device table (path_kernel's `cand_params`)
     int32_t fan_n;
     // MODE 3 (yearly bins, mcr_run_year_bins_rng) shares the bytes of the fan-out levels: no launch is both, and the layout
     // of the kernel arguments every other variant reads stays what it was
@@ -101,6 +101,17 @@ struct GridCell {
 // PHASE 8 (scenario probe, mcr_probe_scenarios_rng): consumer wave j of a launch runs record j of the launch's device table of
 // mcr_scenario (initial_balance, monthly_contribution, monthly_expenses), through `cand_params` like the grid's records
 static_assert(sizeof(mcr_scenario) == 3 * sizeof(double), "mcr_scenario is three packed doubles");
+// PHASE 9 (assumption probe, mcr_probe_assumptions_rng): consumer wave j of a launch runs record j of the launch's device table,
+// through `cand_params` as well: PHASE 8's three values and the market as growth_factors_row reads it (mcr_device.h), derived on
+// the host by the function derive_params uses (derive_market)
+struct AssumptionRecord {
+    double initial_balance, monthly_contribution, monthly_expenses;
+    double a1, b1, ainf, binf_rho, binf_rho_c, aprem, bprem;
+};
+static_assert(sizeof(AssumptionRecord) == 10 * sizeof(double), "AssumptionRecord is ten packed doubles");
+// ... and the market a consumer wave keeps of its record (growth_factors_row's MARKET); NoMarket in every other kernel
+struct Market { double a1, b1, ainf, binf_rho, binf_rho_c, aprem, bprem; };
+struct NoMarket {};
 constexpr int kSplitVotePairs = 16;   // SPLIT: pairs of months between two stop votes of a workgroup (a power of two)
 constexpr int kSnapFields = 10;   // b1 b2 c1 c2 gacc1 gacc2 infl contrib | pre_fail | Philox carry words
 // Fields per lane of a time-sliced block's hand-over state in front of its lock columns: path_kernel's kSegFixedFields
@@ -244,6 +255,14 @@ __device__ __forceinline__ void year_bins_flush_final(const KernelIO::YearBins& 
 // the plain initial state, in their order), contributes its own monthly_contribution and spends its own monthly_expenses.
 // The launch's records are a device table of mcr_scenario behind `cand_params` (scalar loads, as PHASE 6 reads its GridCell).
 // Counts are bit-identical to a count-only launch with the three fields of the parameter block replaced by record j.
+// PHASE 9 (SPLIT = true; mcr_probe_assumptions_rng): ASSUMPTION FAN-OUT = PHASE 8's workgroup, barriers and votes, with the
+// MARKET per consumer wave as well.  The market enters a month only in the last third of growth_rows2 (x = a + b z and the three
+// exps); the Philox rounds and the Box-Muller radius and angle depend on the path alone.  So the producer stages the PARTS of the
+// pair's six normals (growth_parts2: nine doubles per lane instead of six factors; the stage is 2 x 9 x 64 doubles), and consumer
+// wave j computes its own three factors from them with its record's a1, b1, ainf, binf_rho, binf_rho_c, aprem, bprem — the
+// operations of growth_rows2_form in their order (growth_factors_row) — then runs PHASE 8's month.  The seven values sit in
+// VGPRs: the fan-out kernels have no SGPRs to spare.  Counts are bit-identical to a count-only launch with the ten fields of
+// the parameter block replaced by record j.
 // EXACT = true: the month in its exact-rounding forms (mcr_device.h) instead of the tolerance form — for configurations whose
 // realized-gains rate lets the reference's denominator clamps bind (DevParams::exact_month), instantiated for the generic XS
 // variants only; -DMCR_K1_EXACT_MONTH builds a library that runs every variant that way (A/B).
@@ -260,7 +279,7 @@ constexpr bool kUniformFixups = false;
 constexpr bool kUniformFixups = true;
 #endif
 template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault, int GF = 0, int MF = 0>
-__global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE == 8) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
+__global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE == 8 || PHASE == 9) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
                                                          const DevParams* __restrict__ cand_params) {
     // MODE 3 (mcr_run_year_bins_rng): YEARLY BINS.  The arithmetic of MODE 2, but wherever that variant stores a yearly sample
     // (nominal balance, real balance, withdrawal rate) the lane bins it instead: cell 0 = below edges[0], cells 1 .. n = the
@@ -280,11 +299,14 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     static_assert(PHASE != 6 || SPLIT, "the grid fan-out is a producer / consumer form");
     static_assert(PHASE != 7 || SPLIT, "the contribution fan-out is a producer / consumer form");
     static_assert(PHASE != 8 || SPLIT, "the scenario fan-out is a producer / consumer form");
+    static_assert(PHASE != 9 || SPLIT, "the assumption fan-out is a producer / consumer form");
     // PHASE 4 = PHASE 2 (a candidate's decumulation resumed from its accumulation snapshot) time-sliced like PHASE 3: the
     // 17-month verification window of the search is 17 x 196 workgroups = 2.17 rounds of the resident slots.
     constexpr bool kExpFan = PHASE == 5 || PHASE == 6;    // expense fan-out: the levels are monthly_expenses, resumed at retirement
     constexpr bool kConFan = PHASE == 7;                  // contribution fan-out: the levels are monthly_contribution, the whole path
-    constexpr bool kScnFan = PHASE == 8;                  // scenario fan-out: balance, contribution and spending per wave, the whole path
+    constexpr bool kAsmFan = PHASE == 9;                  // assumption fan-out: the scenario fan-out with the market per wave as well
+    constexpr bool kStreamRegs = SPLIT && !kAsmFan;       // the first two income streams stay in SGPRs for the whole launch (S0, S1 below)
+    constexpr bool kScnFan = PHASE == 8 || kAsmFan;       // scenario fan-out: balance, contribution and spending per wave, the whole path
     constexpr bool kFan = kExpFan || kConFan || kScnFan;  // fan-out workgroup: one 64-path block, L consumer waves (levels), one producer wave
     constexpr bool kGrid = PHASE == 6;                    // ... of grid row blockIdx.y (GridCell)
     constexpr bool kCand = PHASE == 2 || PHASE == 4 || kExpFan;   // resumes from a PHASE 1 snapshot (PHASE 2 / 4: per-candidate parameter block)
@@ -342,7 +364,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     // the block counters.
     constexpr bool kStaged = RNG == (int)MCR_RNG_PHILOX && !INJ;
     __shared__ __align__(16) double tab_s[kTabDoubles];
-    constexpr int kStageLen = 6 * kPaths;                // = kStageDoubles for kBlock-path workgroups
+    constexpr int kStageLen = (kAsmFan ? kPartsPerPair : 6) * kPaths;   // = kStageDoubles for kBlock-path workgroups (PHASE 9 stages the normals' parts)
     __shared__ __align__(16) double stage_s[kStaged ? (SPLIT ? 2 : 1) * kStageLen : 1];
     // Per-path values that are written once or twice in a lifetime and read at the very end (first-year withdrawals,
     // YearsToRuin) live in the lane's own LDS column in the variants with per-path outputs: held to 5 waves per SIMD those
@@ -449,7 +471,12 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         }
     };
     // gross factors of month `row` (:522-532)
+    [[maybe_unused]] std::conditional_t<kAsmFan, Market, NoMarket> MK;   // PHASE 9: the consumer wave's market (VGPRs), set below
     auto growth = [&](int row, double& g1, double& ginf, double& g2) {
+        if constexpr (kAsmFan) {    // this wave's factors from the staged parts of the pair
+            growth_factors_staged<kPaths>(MK, stage + (size_t)((row >> 1) & 1) * kStageLen, row & 1, tab, GR, g1, ginf, g2);
+            return;
+        }
         if (kStaged) {
             const double* c = stage + (size_t)(3 * (row & 1)) * kPaths + (SPLIT ? (size_t)((row >> 1) & 1) * kStageLen : 0);
             g1 = c[0]; ginf = c[kPaths]; g2 = c[2 * kPaths];
@@ -515,8 +542,13 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         if (PHASE == 1) while (snap_i < io.n_snap && io.snap_months[snap_i] == 0) put_carry();
         for (int row = first_row; row < last_row; row += 2) {
             double* st = stage + (size_t)((row >> 1) & 1) * kStageLen;
-            if ((row & 2) == 0) growth_rows2<0, kPaths, kPerPathPhilox>(P, GR, io.seed, io.stream_id, path, PQ, (uint32_t)row >> 2, tab, st, carry);
-            else growth_rows2<1, kPaths, kPerPathPhilox>(P, GR, io.seed, io.stream_id, path, PQ, (uint32_t)row >> 2, tab, st, carry);
+            if constexpr (kAsmFan) {
+                if ((row & 2) == 0) growth_parts2<0, kPaths, kPerPathPhilox>(GR, io.seed, io.stream_id, path, PQ, (uint32_t)row >> 2, tab, st, carry);
+                else growth_parts2<1, kPaths, kPerPathPhilox>(GR, io.seed, io.stream_id, path, PQ, (uint32_t)row >> 2, tab, st, carry);
+            } else {
+                if ((row & 2) == 0) growth_rows2<0, kPaths, kPerPathPhilox>(P, GR, io.seed, io.stream_id, path, PQ, (uint32_t)row >> 2, tab, st, carry);
+                else growth_rows2<1, kPaths, kPerPathPhilox>(P, GR, io.seed, io.stream_id, path, PQ, (uint32_t)row >> 2, tab, st, carry);
+            }
             if (PHASE == 1) while (snap_i < io.n_snap && ((io.snap_months[snap_i] - 1) >> 1) == (row >> 1)) put_carry();
             if (((row >> 1) & (kSplitVotePairs - 1)) == 0) { if (__syncthreads_or(0) == 0) return; }   // (the consumers' vote, begin_month)
             else __syncthreads();
@@ -527,7 +559,18 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     // PHASE 8: this consumer wave's record (the producer has returned: fan_j < fan_n, inside the launch's table), three SGPR
     // pairs; the initial state again, from the record's balance
     double scn_expenses = 0.0;
-    if constexpr (kScnFan) {
+    if constexpr (kAsmFan) {                     // PHASE 9: the record's three values likewise, and its market into VGPRs
+        const AssumptionRecord* const rec = reinterpret_cast<const AssumptionRecord*>(cand_params) + fan_j;
+        const double rec_balance = rec->initial_balance;
+        b1 = rec_balance * P.alloc1;             // :499
+        b2 = rec_balance - b1;                   // :500
+        c1 = b1; c2 = b2;                        // :501-502
+        contrib = rec->monthly_contribution;     // :504
+        scn_expenses = rec->monthly_expenses;
+        MK.a1 = rec->a1; MK.b1 = rec->b1; MK.ainf = rec->ainf; MK.binf_rho = rec->binf_rho; MK.binf_rho_c = rec->binf_rho_c;
+        MK.aprem = rec->aprem; MK.bprem = rec->bprem;
+        asm volatile("" : "+v"(MK.a1), "+v"(MK.b1), "+v"(MK.ainf), "+v"(MK.binf_rho), "+v"(MK.binf_rho_c), "+v"(MK.aprem), "+v"(MK.bprem));
+    } else if constexpr (kScnFan) {
         const mcr_scenario* const scn = reinterpret_cast<const mcr_scenario*>(cand_params) + fan_j;
         const double scn_balance = scn->initial_balance;
         b1 = scn_balance * P.alloc1;             // :499
@@ -632,8 +675,12 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     // A launch that cannot fill the chip (SPLIT) is bound by each wave's dependency chain, and re-reading a stream's record
     // from the kernel arguments every month is three dependent scalar loads on it (the compiler loads start, then end, then
     // the rest): the first two records stay in SGPRs there (82 + 16 of them; the unsplit kernel has none to spare).
+    // PHASE 9 does not: its consumers also hold fexp's constants, and the 12 SGPRs of the two records are what the kernel then
+    // lacks (3 to 8 SGPRs spilled with them); its 15 consumer waves a workgroup hide the loads as the unsplit kernel's waves do.
+    // (kStreamRegs is declared with the phase constants above: declared here, the same constant reorders a few scalar
+    // instructions of the time-sliced kernels, which never read it)
     DevStream S0 = {}, S1 = {};
-    if (SPLIT) {
+    if (kStreamRegs) {
         if (P.n_streams > 0) S0 = P.streams[0];
         if (P.n_streams > 1) S1 = P.streams[1];
         // (opaque to the compiler from here on: kernel-argument loads are otherwise rematerialised in the loop)
@@ -694,7 +741,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
                     else income += nominal * S.keep;                   // :675-677
                 };
                 int s = 0;
-                if (SPLIT) {            // the first two streams sit in SGPRs for the whole launch (see S0, S1 above)
+                if (kStreamRegs) {      // the first two streams sit in SGPRs for the whole launch (see S0, S1 above)
                     if (P.n_streams > 0) stream_income(S0);
                     if (P.n_streams > 1) stream_income(S1);
                     s = 2;
@@ -1328,6 +1375,12 @@ static int check_stream_list(const mcr_params* p) {
     return MCR_OK;
 }
 
+// monthly log-growth a + b z with |z| < 40 (Box-Muller of 32-bit uniforms: |z| < 6.8, rho-mix < 9.6; ziggurat tail far
+// below 40) must stay inside fexp's domain: the rule validate_params and the assumption probe's records share
+static bool log_growth_in_domain(double mu, double sg) {
+    return std::isfinite(mu) && std::isfinite(sg) && sg >= 0.0 && std::fabs(mu) / kMPY + 40.0 * sg / std::sqrt((double)kMPY) < 700.0;
+}
+
 static int validate_params(const mcr_params* p) {
     if (!p) { set_error("null params"); return MCR_ERR_INVALID_ARG; }
     auto bad = [](const char* name, double v, const char* want) {
@@ -1347,13 +1400,10 @@ static int validate_params(const mcr_params* p) {
     if (!unit(p->inv2_annual_tax_on_gains_rate)) return bad("inv2_annual_tax_on_gains_rate", p->inv2_annual_tax_on_gains_rate, "in [0, 1] (config.py:79)");
     if (!unit(p->inv2_realized_gains_tax_rate)) return bad("inv2_realized_gains_tax_rate", p->inv2_realized_gains_tax_rate, "in [0, 1] (config.py:80)");
     if (!(p->equity_inflation_rho >= -1.0 && p->equity_inflation_rho <= 1.0)) return bad("equity_inflation_rho", p->equity_inflation_rho, "in [-1, 1] (config.py:85)");
-    // monthly log-growth a + b z with |z| < 40 (Box-Muller of 32-bit uniforms: |z| < 6.8, rho-mix < 9.6; ziggurat tail far
-    // below 40) must stay inside fexp's domain
-    const double sq12 = std::sqrt((double)kMPY);
     const double mu[3] = {p->inv1_mu_log, p->inf_mu_log, p->prem_mu_log}, sg[3] = {p->inv1_sigma_log, p->inf_sigma_log, p->prem_sigma_log};
     const char* nm[3] = {"inv1", "inf", "prem"};
     for (int i = 0; i < 3; ++i) {
-        if (!std::isfinite(mu[i]) || !std::isfinite(sg[i]) || sg[i] < 0.0 || std::fabs(mu[i]) / kMPY + 40.0 * sg[i] / sq12 >= 700.0) {
+        if (!log_growth_in_domain(mu[i], sg[i])) {
             set_error("params.%s_mu_log / %s_sigma_log = %g / %g: need finite values, sigma >= 0 and |mu|/12 + 40 sigma/sqrt(12) < 700",
                       nm[i], nm[i], mu[i], sg[i]);
             return MCR_ERR_INVALID_ARG;
@@ -1399,6 +1449,25 @@ static int32_t start_month_index(double current_age, int32_t wm, double start_at
     return (int32_t)c;
 }
 
+// The market's part of the parameter block, from the seven lognormal parameters alone: derive_params fills DevParams with it,
+// the assumption probe its records (AssumptionRecord).  ONE function, not inlined, so that a record holds the bits a parameter
+// block with the same seven fields holds.
+struct DevMarket { double a1, b1, ainf, binf, aprem, bprem, rho, rho_c, binf_rho, binf_rho_c; };
+__attribute__((noinline)) static DevMarket derive_market(double inv1_mu_log, double inv1_sigma_log, double inf_mu_log, double inf_sigma_log,
+                                                         double prem_mu_log, double prem_sigma_log, double rho) {
+    DevMarket m;
+    const double sqrt12 = std::sqrt((double)kMPY);
+    m.a1 = inv1_mu_log / (double)kMPY;   m.b1 = inv1_sigma_log / sqrt12;     // :473
+    m.ainf = inf_mu_log / (double)kMPY;  m.binf = inf_sigma_log / sqrt12;
+    m.aprem = prem_mu_log / (double)kMPY; m.bprem = prem_sigma_log / sqrt12;
+    m.rho = rho;
+    const double om = 1.0 - m.rho * m.rho;
+    m.rho_c = std::sqrt(om > 0.0 ? om : 0.0);  // :463
+    m.binf_rho = m.binf * m.rho;
+    m.binf_rho_c = m.binf * m.rho_c;
+    return m;
+}
+
 // Host-side derivation of the wave-uniform parameter block (same fp64 expressions as the reference).
 // `extra` receives the records of the streams beyond the by-value block (device-table layout); callers that cannot carry
 // such a table pass nullptr and get MCR_ERR_UNSUPPORTED for longer lists.
@@ -1432,15 +1501,10 @@ static int derive_params(const mcr_params* p, int32_t wm, DevParams* d, std::vec
     // the straight-line month's ballot (path kernel): both balances above this floor -> capacity >= (b1 + b2)(1 - r_max) > 2e-6,
     // outside the dust sub-case.  1e-6 itself without a realized-gains rate.
     d->fast_floor = d->exact_month ? kEps : kEps / (1.0 - std::fmax(d->real_rate1, d->real_rate2));
-    const double sqrt12 = std::sqrt((double)kMPY);
-    d->a1 = p->inv1_mu_log / (double)kMPY;   d->b1 = p->inv1_sigma_log / sqrt12;     // :473
-    d->ainf = p->inf_mu_log / (double)kMPY;  d->binf = p->inf_sigma_log / sqrt12;
-    d->aprem = p->prem_mu_log / (double)kMPY; d->bprem = p->prem_sigma_log / sqrt12;
-    d->rho = p->equity_inflation_rho;
-    const double om = 1.0 - d->rho * d->rho;
-    d->rho_c = std::sqrt(om > 0.0 ? om : 0.0);  // :463
-    d->binf_rho = d->binf * d->rho;
-    d->binf_rho_c = d->binf * d->rho_c;
+    const DevMarket mk = derive_market(p->inv1_mu_log, p->inv1_sigma_log, p->inf_mu_log, p->inf_sigma_log, p->prem_mu_log, p->prem_sigma_log,
+                                       p->equity_inflation_rho);
+    d->a1 = mk.a1; d->b1 = mk.b1; d->ainf = mk.ainf; d->binf = mk.binf; d->aprem = mk.aprem; d->bprem = mk.bprem;
+    d->rho = mk.rho; d->rho_c = mk.rho_c; d->binf_rho = mk.binf_rho; d->binf_rho_c = mk.binf_rho_c;
     d->working_months = wm;
     d->retirement_years = p->retirement_years;
     d->total_months = sz.total_months;
@@ -2251,13 +2315,16 @@ static int probe_shared_prefix(const mcr_params* p, const mcr_rng* rng, uint32_t
 // LDS of a level fan-out launch (path_kernel PHASE 5 / 6 / 7 / 8): STATIC = the math tables and the double-buffered 64-column stage
 // (+ the unused summary / segment words); DYNAMIC = the level counters and [n_lock_slots][64] lock columns per consumer wave.
 // Every lock slot stays in LDS (no overflow block in this form): the levels per launch are lowered until they fit.
-static size_t fanout_static_lds() { return (size_t)kMathTabBytes + (size_t)2 * 6 * 64 * sizeof(double) + 512; }   // (16 640 B compiled)
+// `parts`: PHASE 9, whose stage holds the nine parts of a pair's normals per lane instead of six factors (+3 072 B).
+static size_t fanout_static_lds(bool parts = false) {   // (16 640 B compiled; PHASE 9: 19 712 B)
+    return (size_t)kMathTabBytes + (size_t)2 * (parts ? kPartsPerPair : 6) * 64 * sizeof(double) + 512;
+}
 static size_t fanout_dynamic_lds(const DevParams& d, int levels) {
     return (size_t)MCR_MAX_EXPENSE_FANOUT * sizeof(unsigned int) + (size_t)levels * (size_t)d.n_lock_slots_total * 64 * sizeof(double);
 }
-static int fanout_max_levels(const DevParams& d) {
+static int fanout_max_levels(const DevParams& d, bool parts = false) {
     int l = MCR_MAX_EXPENSE_FANOUT;
-    while (l > 0 && fanout_static_lds() + fanout_dynamic_lds(d, l) > kLdsPerWorkgroup) --l;
+    while (l > 0 && fanout_static_lds(parts) + fanout_dynamic_lds(d, l) > kLdsPerWorkgroup) --l;
     return l;
 }
 // Below this many path-wavefronts per level (n_paths / 64) the per-level route runs instead of a fan-out: the environment
@@ -2281,14 +2348,14 @@ struct LevelGroups {
 // What the expense and the contribution fan-out ask of a probe's shape.  MCR_OK: *d = the parameter block with every lock slot
 // in LDS, *lmax = levels per launch; MCR_ERR_UNSUPPORTED for shapes the form does not cover.
 static int plan_level_fanout(const mcr_params* p, const mcr_rng* rng, uint64_t n_paths, int32_t wm, int32_t n_levels, uint64_t min_waves,
-                             DevParams* d, int* lmax) {
+                             DevParams* d, int* lmax, bool parts = false /* PHASE 9's larger stage */) {
     if (rng->kind != MCR_RNG_PHILOX || n_levels < 2 || n_paths == 0 || n_paths > ((uint64_t)1 << 31)) return MCR_ERR_UNSUPPORTED;
     if ((n_paths + 63) / 64 < min_waves) return MCR_ERR_UNSUPPORTED;
     int rc = derive_params(p, wm, d);
     if (rc != MCR_OK) return rc;
     if (needs_generic_variant(*d)) return MCR_ERR_UNSUPPORTED;
     if ((rc = check_barrier_counts(*d)) != MCR_OK) return rc;
-    *lmax = fanout_max_levels(*d);
+    *lmax = fanout_max_levels(*d, parts);
     if (*lmax < 2) return MCR_ERR_UNSUPPORTED;
     d->n_lock_slots = d->n_lock_slots_total;
     return MCR_OK;
@@ -2387,6 +2454,56 @@ static int probe_scenarios_fanout(const mcr_params* p, const mcr_rng* rng, uint3
     const hipError_t ef = table.mem.release();
     if (e != hipSuccess) return hip_fail(e, "scenario fan-out probe");
     if (ef != hipSuccess) return hip_fail(ef, "scenario fan-out probe (free)");
+    return MCR_OK;
+}
+
+// Several records of (initial_balance, monthly_contribution, monthly_expenses, the market's seven lognormal parameters) over the
+// same paths, Philox stream: assumption fan-out launches (PHASE 9) over groups of at most fanout_max_levels(parts) records, the
+// whole path each.  The records are derived on the host (derive_market: the bits derive_params gives a block with those seven
+// fields) into ONE stream-ordered device table, as the scenario fan-out's.  Of everything the host derives from the parameter
+// block only a1 .. binf_rho_c, rho and rho_c depend on the seven fields, and the kernel reads them in growth_rows2 alone —
+// which PHASE 9's consumers replace by their record's; the tax variant, needs_generic_variant, the lock-slot plan, the kept
+// streams and the barrier counts read none of the ten fields, so one parameter block serves every record.  Returns
+// MCR_ERR_UNSUPPORTED, having enqueued nothing, for shapes this form does not cover and when the table's allocation is refused.
+static thread_local int g_last_assumption_fanout_launches = 0;   // (mcr_probe_assumptions_last_fanout_launches)
+static int probe_assumptions_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                                    int32_t wm, const mcr_assumptions* records, int32_t n_records, uint64_t* counts, hipStream_t stream) {
+    DevParams d;
+    int lmax = 0;
+    if (int rc = plan_level_fanout(p, rng, n_paths, wm, n_records, fanout_min_waves("MCR_ASSUMPTION_FANOUT_MIN_WAVES"), &d, &lmax, true)) return rc;
+    std::vector<AssumptionRecord> host((size_t)n_records);
+    for (int32_t k = 0; k < n_records; ++k) {
+        const mcr_assumptions& r = records[k];
+        const DevMarket mk = derive_market(r.inv1_mu_log, r.inv1_sigma_log, r.inf_mu_log, r.inf_sigma_log, r.prem_mu_log, r.prem_sigma_log,
+                                           r.equity_inflation_rho);
+        host[(size_t)k] = AssumptionRecord{r.initial_balance, r.monthly_contribution, r.monthly_expenses,
+                                           mk.a1, mk.b1, mk.ainf, mk.binf_rho, mk.binf_rho_c, mk.aprem, mk.bprem};
+    }
+    KernelIO io = make_io(rng, nullptr, stream_id, path_begin, n_paths);
+    SnapshotBlock table(stream);
+    hipError_t e = hipSuccess;
+    if (!table.attach(io, 0, host.data(), host.size() * sizeof(AssumptionRecord), &e, SIZE_MAX)) return MCR_ERR_UNSUPPORTED;
+    io.snap = nullptr;   // (no snapshot column: the block is the table alone)
+    if (e == hipSuccess) {
+        const AssumptionRecord* d_table = (const AssumptionRecord*)table.records;
+        const dim3 grid((unsigned)((n_paths + 63) / 64));
+        const LevelGroups groups(n_records, lmax);
+        for_tax_variant(d, [&](auto T, auto A) {
+            groups.for_each([&](int, int first, int lg) {
+                KernelIO fio = io;
+                fio.out.counters = counts + (size_t)first * MCR_N_COUNTERS;
+                fio.fan_n = lg;
+                hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 9, true>), grid, dim3(64 * (lg + 1)),
+                                   fanout_dynamic_lds(d, lg), stream, d, fio, (const DevParams*)(d_table + first));
+                ++g_last_assumption_fanout_launches;
+            });
+        });
+        e = hipGetLastError();
+    }
+    const hipError_t ef = table.mem.release();
+    if (e != hipSuccess) g_last_assumption_fanout_launches = 0;
+    if (e != hipSuccess) return hip_fail(e, "assumption fan-out probe");
+    if (ef != hipSuccess) return hip_fail(ef, "assumption fan-out probe (free)");
     return MCR_OK;
 }
 
@@ -2657,6 +2774,73 @@ int mcr_probe_scenarios_rng(const mcr_params* p, const mcr_rng* rng, uint32_t st
     if (rc != MCR_ERR_UNSUPPORTED) return rc;     // (unsupported shape / allocation refused: one launch per scenario below)
     return fork_join(device, main, n_scenarios, launch_scenario);
 }
+
+int mcr_probe_assumptions_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                              uint64_t n_paths, int32_t working_months, const mcr_assumptions* records,
+                              int32_t n_records, uint64_t* counts, int device, void* hip_stream) {
+    MCR_ENTER_DEVICE(device);
+    g_last_assumption_fanout_launches = 0;
+    if (n_records < 0) { set_error("n_records %d must be >= 0", n_records); return MCR_ERR_INVALID_ARG; }
+    if (n_records == 0) return MCR_OK;
+    if (!records || !counts) { set_error("null records / counts"); return MCR_ERR_INVALID_ARG; }
+    // validate the block itself (validate_months derives it, its own ten fields included: *p must be valid on every route,
+    // whatever the records replace) and every record BEFORE enqueueing anything (counts stay untouched on an error):
+    // validate_params' rules
+    int rc = validate_months(p, &working_months, 1);
+    if (rc != MCR_OK) return rc;
+    rc = check_rng(rng);
+    if (rc != MCR_OK) return rc;
+    static const struct { double mcr_assumptions::*field; const char* name; int config_line; } kAmounts[3] = {
+        {&mcr_assumptions::initial_balance, "initial_balance", 56},
+        {&mcr_assumptions::monthly_contribution, "monthly_contribution", 57},
+        {&mcr_assumptions::monthly_expenses, "monthly_expenses", 59}};
+    static const struct { double mcr_assumptions::*mu; double mcr_assumptions::*sigma; const char* name; } kSeries[3] = {
+        {&mcr_assumptions::inv1_mu_log, &mcr_assumptions::inv1_sigma_log, "inv1"},
+        {&mcr_assumptions::inf_mu_log, &mcr_assumptions::inf_sigma_log, "inf"},
+        {&mcr_assumptions::prem_mu_log, &mcr_assumptions::prem_sigma_log, "prem"}};
+    for (int32_t k = 0; k < n_records; ++k) {
+        const mcr_assumptions& r = records[k];
+        for (const auto& f : kAmounts) {
+            const double v = r.*(f.field);
+            if (!(std::isfinite(v) && v >= 0.0)) {
+                set_error("records[%d].%s = %g: must be finite and >= 0 (config.py:%d)", k, f.name, v, f.config_line);
+                return MCR_ERR_INVALID_ARG;
+            }
+        }
+        for (const auto& f : kSeries) {
+            const double mu = r.*(f.mu), sg = r.*(f.sigma);
+            if (!log_growth_in_domain(mu, sg)) {
+                set_error("records[%d].%s_mu_log / records[%d].%s_sigma_log = %g / %g: need finite values, sigma >= 0 and |mu|/12 + 40 sigma/sqrt(12) < 700",
+                          k, f.name, k, f.name, mu, sg);
+                return MCR_ERR_INVALID_ARG;
+            }
+        }
+        if (!(r.equity_inflation_rho >= -1.0 && r.equity_inflation_rho <= 1.0)) {
+            set_error("records[%d].equity_inflation_rho = %g: must be in [-1, 1] (config.py:85)", k, r.equity_inflation_rho);
+            return MCR_ERR_INVALID_ARG;
+        }
+    }
+    hipStream_t main = (hipStream_t)hip_stream;
+    rc = zero_counters(counts, (size_t)n_records, main);
+    if (rc != MCR_OK) return rc;
+    mcr_params q = *p;
+    auto launch_record = [&](int k, hipStream_t s) {
+        const mcr_assumptions& r = records[k];
+        q.initial_balance = r.initial_balance; q.monthly_contribution = r.monthly_contribution; q.monthly_expenses = r.monthly_expenses;
+        q.inv1_mu_log = r.inv1_mu_log; q.inv1_sigma_log = r.inv1_sigma_log;
+        q.inf_mu_log = r.inf_mu_log; q.inf_sigma_log = r.inf_sigma_log;
+        q.prem_mu_log = r.prem_mu_log; q.prem_sigma_log = r.prem_sigma_log;
+        q.equity_inflation_rho = r.equity_inflation_rho;
+        const mcr_outputs o = counters_only(counts + (size_t)k * MCR_N_COUNTERS);
+        return launch_paths(&q, rng, stream_id, path_begin, n_paths, working_months, nullptr, &o, s);
+    };
+    if (n_records == 1) return launch_record(0, main);
+    rc = probe_assumptions_fanout(p, rng, stream_id, path_begin, n_paths, working_months, records, n_records, counts, main);
+    if (rc != MCR_ERR_UNSUPPORTED) return rc;     // (unsupported shape / allocation refused: one launch per record below)
+    return fork_join(device, main, n_records, launch_record);
+}
+
+int mcr_probe_assumptions_last_fanout_launches(void) { return g_last_assumption_fanout_launches; }
 
 int mcr_probe_grid_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
                        uint64_t n_paths, const int32_t* working_months, int32_t n_candidates,

@@ -17,7 +17,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from . import _native as N
-from ._native import McrOutputs, McrParams, McrRng, McrScenario, McrSizes, McrYearBins
+from ._native import McrAssumptions, McrOutputs, McrParams, McrRng, McrScenario, McrSizes, McrYearBins
 
 SUMMARY_FIELDS = (
     "start_balance",
@@ -600,6 +600,34 @@ def probe_scenarios(params: McrParams, seed, stream_id: int, path_begin: int, n_
         len(records), counts.data_ptr(), int(device), C.c_void_p(stream),
     )
     N.check(rc, "mcr_probe_scenarios_rng")
+    return counts
+
+
+def probe_assumptions(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
+                      records, device: int = 0):
+    """Success counters of several market-assumption records at one working-month count over the same path range
+    (``mcr_probe_assumptions_rng``).  ``records`` is a sequence of 10-tuples in the order of ``mcr_assumptions``:
+    ``(initial_balance, monthly_contribution, monthly_expenses, inv1_mu_log, inv1_sigma_log, inf_mu_log, inf_sigma_log,
+    prem_mu_log, prem_sigma_log, equity_inflation_rho)``; record k counts exactly what a count-only launch with those ten
+    fields of `params` replaced counts.  Up to ``MCR_MAX_EXPENSE_FANOUT`` records share each path's normals.  Returns a
+    device int64 tensor ``[len(records), 2]`` = ``{successes, paths}``; asynchronous (reading it synchronises)."""
+    import torch
+
+    N.require_device()
+    records = [tuple(float(x) for x in r) for r in records]
+    if any(len(r) != 10 for r in records):
+        raise ValueError("every record holds the ten fields of mcr_assumptions")
+    arr = (McrAssumptions * max(1, len(records)))(*[McrAssumptions(*r) for r in records])
+    counts = torch.empty((len(records), N.MCR_N_COUNTERS), dtype=torch.int64, device=torch.device("cuda", int(device)))
+    if not records:
+        return counts
+    rng = _as_rng(seed)
+    stream = torch.cuda.current_stream(int(device)).cuda_stream
+    rc = N.load_library().mcr_probe_assumptions_rng(
+        C.byref(params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), int(working_months), arr,
+        len(records), counts.data_ptr(), int(device), C.c_void_p(stream),
+    )
+    N.check(rc, "mcr_probe_assumptions_rng")
     return counts
 
 

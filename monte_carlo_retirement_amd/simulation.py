@@ -1007,6 +1007,88 @@ class RetirementMonteCarloSimulator:
                                 f"({len(curve)} levels evaluated).")
         return results
 
+    # ---- market-assumption stress and the break-even assumption search ---------------------------------
+    def success_probability_by_assumptions(self, working_months: int, scenarios: Sequence[dict],
+                                           num_simulations: Optional[int] = None) -> np.ndarray:
+        """Success % of each record of market assumptions at ``working_months``, over the active seed stream's batch of
+        ``num_simulations`` paths (default ``num_simulations_main``), from the assumption probe
+        (``mcr_probe_assumptions_rng``).  A record is a mapping with any subset of `stress.ASSUMPTION_FIELDS` (the seven
+        market names of `Config` and the three scenario levers): a missing key takes the config's value; an unknown key or
+        a value outside `Config`'s bounds raises ``ValueError`` naming ``scenarios[k]`` (before any device work).  Aligned
+        with the input; each value equals, bit for bit, ``_success_probability(run_monte_carlo_simulations(working_months,
+        n)[0])`` of a simulator whose config differs in those fields only.  Under a process group the records go through
+        ``distributed.probe_candidates`` (as candidate indices), so every rank returns the same array."""
+        from .stress import assumption_records
+
+        p = self.params_model
+        records = assumption_records(p, scenarios)
+        if not records:
+            return np.zeros(0, dtype=np.float64)
+        n = int(p.num_simulations_main if num_simulations is None else num_simulations)
+        wm = int(working_months)
+        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
+
+        def probe(path_begin, count, idx):
+            return E.probe_assumptions(params, rng, self._stream_id, path_begin, count, wm, [records[i] for i in idx], device=dev)
+
+        counts = D.probe_candidates(list(range(len(records))), n, self.shard_min_paths, probe)
+        return np.array([self._count_percent(counts[i, N.MCR_CTR_SUCCESS], n) for i in range(len(records))], dtype=np.float64)
+
+    def stress_test(self, working_months: int, shifts: Optional[Sequence[Tuple[str, dict]]] = None,
+                    num_simulations: Optional[int] = None) -> List[Dict[str, object]]:
+        """The stress table at ``working_months``: ONE `success_probability_by_assumptions` call over the base case and one
+        row per shift (default `stress.DEFAULT_SHIFTS`: 14 one-at-a-time additive shifts of the market's means,
+        volatilities and correlation, i.e. 15 records, one launch).  ``shifts`` replaces the table with ``[(label, {field:
+        delta, ...}), ...]``; several fields in one entry make a combined scenario.  Each shifted value is clipped to
+        `Config`'s bounds.  Returns ``{"label", "overrides", "probability", "delta"}`` per row, base first: ``overrides``
+        holds the applied values, ``delta`` the row's probability minus the base row's, in points."""
+        from .stress import stress_scenarios
+
+        rows = stress_scenarios(self.params_model, shifts)
+        probs = self.success_probability_by_assumptions(working_months, [o for _, o in rows], num_simulations)
+        base = float(probs[0])
+        return [{"label": label, "overrides": dict(o), "probability": float(pr), "delta": float(pr) - base}
+                for (label, o), pr in zip(rows, probs)]
+
+    def find_breakeven_assumption(
+        self,
+        working_months: int,
+        field: str,
+        window: float = 0.25,
+        resolution: float = 1e-4,
+        verbose: bool = True,
+        progress_callback: Optional[Callable[[dict], None]] = None,
+    ) -> Tuple[Optional[float], float, List[Dict[str, float]], str]:
+        """The most adverse value of one mean or volatility of the market (`stress.ADVERSE_DIRECTION`: lower for the two
+        return means, higher for the inflation mean and every volatility) at which ``target_probability`` is still met when
+        retiring after ``working_months``: search stream, ``num_simulations_search`` paths, ``MCR_MAX_EXPENSE_FANOUT``
+        levels per probe (`stress.search_breakeven`).  Levels are multiples of ``resolution`` inside ``[config value -
+        window, config value + window]`` clipped to `Config`'s bounds.  Returns ``(value, probability, curve, status)``
+        with ``status`` ``"found"``, ``"holds_at_window_end"`` (the value is the window's adverse end) or ``"not_reached"``
+        (``None``).  Deterministic for a given seed, and the same on every rank."""
+        from .stress import search_breakeven
+
+        self.use_search_seeds()
+        p = self.params_model
+        wm = int(working_months)
+        n_sims, target = int(p.num_simulations_search), float(p.target_probability)
+        if verbose:
+            logger.info(f"Searching the break-even {field} at {wm} working months for '{p.Nickname}' "
+                        f"(target {target:.2f}%, {n_sims} sims per level, window {window}, resolution {resolution}).")
+
+        def probe_levels(values):
+            return list(self.success_probability_by_assumptions(wm, [{field: v} for v in values], n_sims))
+
+        value, prob, curve, status = search_breakeven(probe_levels, target, field, float(getattr(p, field)), window=window,
+                                                      resolution=resolution, levels_per_call=N.MCR_MAX_EXPENSE_FANOUT, on_level=progress_callback)
+        if verbose:
+            if status == "not_reached":
+                logger.warning(f"Target not met at any {field} of the window: {prob:.2f}% at its favourable end.")
+            else:
+                logger.info(f"  Break-even search complete ({status}): {field} = {value:.4f} with prob {prob:.2f}% "
+                            f"({len(curve)} levels evaluated).")
+        return value, prob, curve, status
+
     def _grid_probabilities(self, working_months: Sequence[int], levels_2d: Sequence[Sequence[float]],
                             num_simulations: int) -> np.ndarray:
         """Success % ``[len(working_months), n_levels]`` of month ``c`` at the levels of row ``c`` (rectangular), over the
