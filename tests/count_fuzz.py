@@ -1,0 +1,276 @@
+"""Stratified random plans for the count-only routes of the path kernel, with the CPU oracle's answer to each.
+
+tests/test_gpu_differential.py draws its plans from one distribution, which never yields a block that qualifies for the
+equal-rates month form and almost never one inside the narrow exp window.  Here every plan is drawn for a named CLASS, so that
+each compiled count-only variant (tax masks 0-3, the annual-gains kernels, the generic extended-stream / exact-month ones) gets
+parameter blocks of its own, and the growth-form ingredients (rho, the volatilities) are strata of the plan's index within its
+class rather than left to chance:
+
+    index % 5 in (0, 4): rho = 0          index % 5 in (1, 3): rho uniform in (-1, 1)          index % 5 == 2: rho = +-1
+    index % 4 == 1:      equity volatility 0.2-0.6 (outside the narrow exp window: growth mask 0)
+
+A count on a plan where every path succeeds (or fails) proves little, so `monthly_expenses` is calibrated after the draw, with
+the oracle alone: ten bisection steps on log-expenses in [20, 200 000] at 128 paths towards half the paths failing.  A plan that
+is still all-or-nothing at the test's path count (no wealth at all, income that covers everything) is drawn again, at most
+MAX_ATTEMPTS times.  A plan one of whose paths reaches a money scale (max |trajectory|) of 2^33 is DROPPED and counted: from
+there on the reference's absolute 1e-6 comparisons are below one ulp of their operands and its own flags hang on the last bit
+of exp (tests/test_gpu_differential.py), so only below it are identical counts demanded.
+
+MCR_COUNT_FUZZ_SEED: other plans (soaks by hand); the default is the suite's.  Everything is deterministic in it, class by
+class: a class's plans do not depend on which other classes were generated before."""
+
+from __future__ import annotations
+
+import math
+import os
+from concurrent.futures import ThreadPoolExecutor
+from dataclasses import dataclass
+
+import numpy as np
+
+from monte_carlo_retirement_amd import Config, params_from_config
+
+CLASSES = ("equal_rates", "unequal_rates", "mask1", "mask2", "mask0", "annual", "generic")
+KEPT = {"equal_rates": 10, "unequal_rates": 10, "mask1": 10, "mask2": 10, "mask0": 10, "annual": 10, "generic": 8}
+SLICED_CLASSES = ("equal_rates", "mask1", "annual")
+PATHS = (512, 321)                      # even / odd index: two whole workgroups; a ragged last wavefront and workgroup
+SCALE_LIMIT = 2.0 ** 33
+RATE_BELOW_EXACT = 1.0 - 2e-6           # the last rate class below the exact-month switch (rate > 1 - 1e-6)
+MAX_ATTEMPTS = 8
+CAL_PATHS, CAL_STEPS, CAL_LO, CAL_HI = 128, 10, 20.0, 200_000.0
+MIXED = (0.05, 0.95)
+SAMPLE = 4096                           # trajectory sample of a time-sliced plan (its money scale, its failure share)
+
+
+def seed() -> int:
+    return int(os.environ.get("MCR_COUNT_FUZZ_SEED", "20261018"))
+
+
+@dataclass
+class Scenario:
+    cls: str
+    index: int
+    cfgd: dict
+    wm: int
+    seed: int
+    stream: int
+    begin: int
+    n: int
+
+    def config(self, **over) -> Config:
+        return Config(**dict(self.cfgd, **over))
+
+    def params(self, **over):
+        return params_from_config(self.config(**over))
+
+    def frozen_streams(self) -> int:
+        """Paying non-indexed income streams: the lock columns the kernel keeps."""
+        return sum(1 for s in self.cfgd["other_income_streams"] if not s["inflation_indexed"] and s["monthly_amount_today"] != 0.0)
+
+    def context(self, route: str = "", env=None) -> str:
+        return (f"class {self.cls} scenario {self.index} route {route!r} env {dict(env or {})}: seed={self.seed} stream={self.stream} "
+                f"path_begin={self.begin} n={self.n} wm={self.wm} cfg={self.cfgd}")
+
+
+# ---- the draw ---------------------------------------------------------------------------------------------------------------
+def _streams(rng, pick, age, count):
+    out = []
+    for s in range(count):
+        out.append({
+            "name": f"s{s}", "monthly_amount_today": float(pick(0.0, rng.uniform(50, 4000), rng.uniform(50, 4000))),
+            "start_at_age": float(age + rng.uniform(-3, 25)), "duration_years": pick(None, int(rng.integers(0, 12))),
+            "inflation_indexed": bool(rng.integers(2)), "tax_rate": float(pick(0.0, 1.0, rng.uniform(0, 0.6))),
+        })
+    return out
+
+
+def _tax(cls, rng, pick, i):
+    """The twelve tax fields' six values of class `cls`: (use1, real1, annual1, use2, real2, annual2)."""
+    rate = lambda: float(pick(rng.uniform(0.01, 0.6), rng.uniform(0.01, 0.6), 0.1, RATE_BELOW_EXACT))  # noqa: E731
+    ignored = lambda: float(pick(0.0, rng.uniform(0, 0.5)))    # noqa: E731  (an annual rate on an asset of the realized system is not applied)
+    untaxed = lambda: pick((False, float(pick(0.0, rng.uniform(0, 0.6))), 0.0), (True, 0.0, ignored()))  # noqa: E731  annual system at rate 0 | realized at rate 0
+    if cls == "equal_rates":
+        r = float((rng.uniform(0.01, 0.6), 0.1, RATE_BELOW_EXACT)[i % 3])
+        return (True, r, ignored(), True, r, ignored())
+    if cls == "unequal_rates":
+        r1, r2 = rate(), rate()
+        while r2 == r1:
+            r2 = float(rng.uniform(0.01, 0.6))
+        return (True, r1, ignored(), True, r2, ignored())
+    if cls == "mask1":
+        return (True, rate(), ignored()) + untaxed()
+    if cls == "mask2":
+        return untaxed() + (True, rate(), ignored())
+    if cls == "mask0":
+        return untaxed() + untaxed()
+    if cls == "annual":
+        annual = lambda: (False, float(pick(0.0, rng.uniform(0, 0.6))), float(pick(1.0, rng.uniform(0.05, 0.5), rng.uniform(0.05, 0.5))))  # noqa: E731
+        other = lambda: pick((True, rate(), ignored()), untaxed())  # noqa: E731
+        return (annual() + other(), other() + annual(), annual() + annual())[i % 3]
+    raise ValueError(cls)
+
+
+def _draw(cls, rng, i, n):
+    pick = lambda *xs: xs[int(rng.integers(len(xs)))]  # noqa: E731
+    age = float(pick(25.0, 40.5, 58.25, 66.0))
+    wm = int(pick(0, 1, 11, 12, 13, 25, int(rng.integers(0, 200))))
+    outside = i % 4 == 1
+    rho = (0.0, float(rng.uniform(-1, 1)), float(pick(-1.0, 1.0)), float(rng.uniform(-1, 1)), 0.0)[i % 5]
+    n_streams = int(rng.integers(0, 7))
+    base = cls
+    if cls == "generic":   # even: 17-20 paying streams on a lean class's taxes; odd: a realized rate the exact month is for
+        base = pick("equal_rates", "unequal_rates", "mask1", "mask2", "mask0") if i % 2 == 0 else pick("equal_rates", "mask1", "mask2")
+    use1, real1, ann1, use2, real2, ann2 = _tax(base, rng, pick, i)
+    if cls == "generic" and i % 2 == 1:
+        exact = float(pick(1.0, 1.0 - 5e-7))     # mask1 / mask2: on the taxed asset; else on asset 1, and on both for i % 4 == 1
+        if base != "mask2":
+            real1 = exact
+        if base == "mask2" or (base == "equal_rates" and i % 4 == 1):
+            real2 = exact
+    streams = _streams(rng, pick, age, n_streams)
+    if cls == "generic" and i % 2 == 0:
+        streams = _streams(rng, pick, age, int(rng.integers(20, 26)))
+        for s in streams[:int(rng.integers(17, 21))]:       # at least 17 of them pay: one beyond the by-value block of 16
+            s["monthly_amount_today"] = float(rng.uniform(20, 400))
+    cfgd = dict(
+        scenario=f"{cls}-{i}", initial_balance=float(pick(0.0, rng.uniform(1e3, 5e4), rng.uniform(1e5, 1e6))),
+        monthly_contribution=float(pick(0.0, rng.uniform(0, 5000), rng.uniform(0, 5000))),
+        contribution_growth_rate_annual=float(rng.uniform(0, 0.06)) if i % 2 else 0.0,
+        monthly_expenses=1000.0, current_age=age, retirement_years=int(rng.integers(4, 41)),
+        allocation_inv1_pct=float(pick(0.0, 1.0, rng.uniform(0, 1), rng.uniform(0, 1))),
+        inv1_returns_mean=float(rng.uniform(-0.02, 0.12)),
+        inv1_returns_volatility=float(rng.uniform(0.2, 0.6)) if outside else float(pick(0.0, rng.uniform(0.02, 0.17), rng.uniform(0.02, 0.17))),
+        inv1_annual_tax_on_gains_rate=ann1, inv1_realized_gains_tax_rate=real1, inv1_use_realized_gains_tax_system=use1,
+        inv2_premium_over_inflation_mean=float(rng.uniform(-0.02, 0.05)),
+        inv2_premium_over_inflation_volatility=float(pick(0.0, rng.uniform(0, 0.12), rng.uniform(0, 0.12))),
+        inv2_annual_tax_on_gains_rate=ann2, inv2_realized_gains_tax_rate=real2, inv2_use_realized_gains_tax_system=use2,
+        inflation_rate_mean=float(rng.uniform(-0.01, 0.08)), inflation_rate_volatility=float(pick(0.0, rng.uniform(0, 0.04), rng.uniform(0, 0.04))),
+        equity_inflation_correlation=rho,
+        num_simulations_main=1, num_simulations_search=1, target_probability=50.0, starting_working_months_search=0,
+        seed=None, num_processes=1, other_income_streams=streams,
+    )
+    if cls == "annual" and i % 5 == 4:
+        # the family of test_gpu_differential.py prone to PRE-RETIREMENT annual-tax failure: inv1 booms and is taxed annually at
+        # 100 %, its gains are swept into inv2, which crashes
+        cfgd.update(allocation_inv1_pct=0.5, inv1_returns_mean=1.5, inv1_returns_volatility=0.5,
+                    inv1_use_realized_gains_tax_system=False, inv1_annual_tax_on_gains_rate=1.0,
+                    inv2_premium_over_inflation_mean=-0.9, inv2_premium_over_inflation_volatility=0.3,
+                    inv2_use_realized_gains_tax_system=True, inv2_realized_gains_tax_rate=0.5,
+                    inflation_rate_mean=0.0, inflation_rate_volatility=0.0, initial_balance=100_000.0)
+        wm = int(pick(12, 14, 25, 37))
+    return Scenario(cls, i, cfgd, wm, int(rng.integers(0, 2 ** 63)), int(rng.integers(2)),
+                    int(pick(0, 2 ** 32 - 100, 2 ** 40)), n)
+
+
+# ---- the oracle's answers, computed once and shared ---------------------------------------------------------------------------
+_RUNS = {}
+
+
+def oracle_run(O, scn: Scenario, wm=None, n=None, trajectories=False, **over):
+    """The oracle's `run_batch` of `scn` (with `Config` fields replaced by `over`, at `wm` months, over `n` paths): cached."""
+    wm = scn.wm if wm is None else int(wm)
+    n = scn.n if n is None else int(n)
+    key = (scn.cls, scn.index, scn.seed, scn.begin, scn.cfgd["monthly_expenses"], n, wm, tuple(sorted(over.items())))
+    hit = _RUNS.get(key)
+    if hit is None or (trajectories and "trajectory" not in hit):
+        hit = O.run_batch(scn.params(**over), scn.seed, scn.stream, scn.begin, n, wm, want_trajectories=trajectories)
+        _RUNS[key] = hit
+    return hit
+
+
+def oracle_runs(O, jobs, threads: int = 8):
+    """`oracle_run(O, *args, **kwargs)` for every `(args, kwargs)` of `jobs`, on host threads (the oracle is a C call)."""
+    with ThreadPoolExecutor(max_workers=threads) as pool:
+        return list(pool.map(lambda j: oracle_run(O, *j[0], **j[1]), jobs))
+
+
+def oracle_run_threaded(O, scn: Scenario, threads: int = 16):
+    """The integers and summary fields of all of `scn.n` paths without trajectories, the path range cut over host threads."""
+    per = (scn.n + threads - 1) // threads
+    p = scn.params()
+
+    def work(t):
+        b = t * per
+        return O.run_batch(p, scn.seed, scn.stream, scn.begin + b, max(0, min(per, scn.n - b)), scn.wm, want_trajectories=False)
+
+    with ThreadPoolExecutor(max_workers=threads) as pool:
+        parts = list(pool.map(work, range(threads)))
+    return {k: (sum(q[k] for q in parts) if k in ("counters", "ruin_year_bins", "wr_obs_counts") else np.concatenate([q[k] for q in parts]))
+            for k in parts[0]}
+
+
+def money_scale(run) -> float:
+    return float(np.abs(run["trajectory"]).max()) if run["trajectory"].size else 0.0
+
+
+def failure_share(run) -> float:
+    return 1.0 - float(run["counters"][0]) / float(run["counters"][1])
+
+
+def _calibrate(O, scn: Scenario) -> float:
+    lo, hi = math.log(CAL_LO), math.log(CAL_HI)
+    for _ in range(CAL_STEPS):
+        mid = 0.5 * (lo + hi)
+        c = O.run_batch(scn.params(monthly_expenses=math.exp(mid)), scn.seed, scn.stream, scn.begin, CAL_PATHS, scn.wm, want_trajectories=False)
+        if 2 * int(c["counters"][0]) < CAL_PATHS:
+            hi = mid        # more than half fail: spend less
+        else:
+            lo = mid
+    return round(math.exp(0.5 * (lo + hi)), 2)
+
+
+def _fits_a_sliced_launch(scn: Scenario) -> bool:
+    frozen = sum(1 for s in scn.cfgd["other_income_streams"] if not s["inflation_indexed"])
+    return scn.wm <= 25 and 4 <= scn.cfgd["retirement_years"] <= 8 and frozen <= 2
+
+
+STATS = {}          # class -> {"drawn", "kept", "dropped_scale", "redrawn_unmixed", "kept_unmixed"}
+_KEPT = {}
+
+
+def _generate(O, cls: str, count: int, sliced_n=None):
+    rng = np.random.default_rng([seed(), CLASSES.index(cls), 0 if sliced_n is None else 1])
+    stats = {"drawn": 0, "kept": 0, "dropped_scale": 0, "redrawn_unmixed": 0, "kept_unmixed": 0}
+    kept = []
+    while len(kept) < count:
+        i = len(kept)
+        fallback = None
+        for _ in range(MAX_ATTEMPTS):
+            scn = _draw(cls, rng, i, PATHS[i % 2] if sliced_n is None else sliced_n)
+            while sliced_n is not None and not _fits_a_sliced_launch(scn):
+                scn = _draw(cls, rng, i, sliced_n)
+            stats["drawn"] += 1
+            if stats["drawn"] > 40 * count:
+                raise RuntimeError(f"count_fuzz: class {cls} does not yield {count} plans in {40 * count} draws: {stats}")
+            scn.cfgd["monthly_expenses"] = _calibrate(O, scn)
+            run = oracle_run(O, scn, n=None if sliced_n is None else SAMPLE, trajectories=True)
+            if money_scale(run) >= SCALE_LIMIT:
+                stats["dropped_scale"] += 1
+                continue
+            fallback = scn
+            if MIXED[0] <= failure_share(run) <= MIXED[1]:
+                break
+            stats["redrawn_unmixed"] += 1
+        else:
+            if fallback is None:
+                continue            # (every attempt was dropped for its scale: draw on, under the cap above)
+            scn = fallback          # all-or-nothing after MAX_ATTEMPTS: kept, and counted against the 90 % of the CPU test
+            stats["redrawn_unmixed"] -= 1
+            stats["kept_unmixed"] += 1
+        kept.append(scn)
+        stats["kept"] += 1
+    return kept, stats
+
+
+def scenarios(O, cls: str):
+    """The kept plans of class `cls` (KEPT[cls] of them), generated once; STATS[cls] says what it took."""
+    if cls not in _KEPT:
+        _KEPT[cls], STATS[cls] = _generate(O, cls, KEPT[cls])
+    return _KEPT[cls]
+
+
+def sliced_scenario(O, cls: str, n: int):
+    """A plan of class `cls` (one of SLICED_CLASSES) that a time-sliced launch of `n` paths takes: working_months <= 25, 4-8
+    retirement years, at most two frozen streams (redrawn within the class until that holds); calibrated, and its money scale
+    and failure share checked, on a SAMPLE-path trajectory run."""
+    return _generate(O, cls, 1, sliced_n=n)[0][0]
