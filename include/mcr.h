@@ -199,6 +199,11 @@ int mcr_k1_growth_form(const mcr_params* p, int32_t working_months, int32_t* mas
  * rate, with no annual-gains tax; masks 0 and 1.  MCR_K1_MONTH_FORM in the environment forces a lower mask, as at a launch; a
  * mask the parameters do not qualify for returns MCR_ERR_INVALID_ARG. */
 int mcr_k1_month_form(const mcr_params* p, int32_t working_months, int32_t* mask);
+/* The stream form of the same launch ("stream form"): bit 0 = the records the kernel is given (mcr_k1_kept_streams)
+ * are at most two, all inflation-indexed, with no annual-gains tax: they stay in registers for the whole launch; masks 0 and 1.
+ * MCR_K1_STREAM_FORM in the environment forces a lower mask, as at a launch; a mask the parameters do not qualify for returns
+ * MCR_ERR_INVALID_ARG. */
+int mcr_k1_stream_form(const mcr_params* p, int32_t working_months, int32_t* mask);
 /* The other_income_streams records the path kernel is given for (params, working_months), in list order: a record with
  * monthly_amount_today == 0 pays an exact zero every month and is left out; lock slots (non-indexed streams; -1 for an indexed
  * one) are numbered over the kept records.  Writes min(*n, cap) entries of index[] (position in the caller's list) and

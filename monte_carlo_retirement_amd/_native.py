@@ -272,6 +272,7 @@ ABI_SYMBOLS = (
     "mcr_stream_start_month_index",
     "mcr_k1_growth_form",
     "mcr_k1_month_form",
+    "mcr_k1_stream_form",
     "mcr_k1_kept_streams",
     "mcr_run_batch",
     "mcr_run_batch_host",
@@ -337,6 +338,9 @@ def _declare(lib: C.CDLL) -> None:
         lib.mcr_k1_month_form.argtypes = [P(McrParams), C.c_int32, P(C.c_int32)]
         lib.mcr_k1_kept_streams.restype = C.c_int
         lib.mcr_k1_kept_streams.argtypes = [P(McrParams), C.c_int32, P(C.c_int32), P(C.c_int32), C.c_int32, P(C.c_int32)]
+    if hasattr(lib, "mcr_k1_stream_form"):  # (likewise)
+        lib.mcr_k1_stream_form.restype = C.c_int
+        lib.mcr_k1_stream_form.argtypes = [P(McrParams), C.c_int32, P(C.c_int32)]
     lib.mcr_run_batch.restype = C.c_int
     lib.mcr_run_batch.argtypes = [
         P(McrParams), C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32,

@@ -694,6 +694,13 @@ __device__ __forceinline__ void rebalance_path(const LaneParams& P, double& b1, 
 //   kMonthEqualRates: both assets are taxed on realized gains at the SAME rate -> rebalance_tol<..., EQR>
 enum { kMonthEqualRates = 1 };
 
+// SF: the launch's STREAM FORM, likewise for what its income-stream list makes unnecessary (host: stream_form_of; the same
+// kernels, in the tolerance form of the month).
+//   kStreamsInRegs: at most two records reach the kernel (the zero-amount ones are dropped on the host), none in the extra
+//   table, and every one is inflation-indexed -> the records sit in SGPRs for the whole launch and the month issues their
+//   FMAs in list order behind two window tests: no loop over the list, no record re-read, no lock column.
+enum { kStreamsInRegs = 1 };
+
 // ---------------------------------------------------------------------------------------------
 // TOLERANCE FORM of the month (what the path kernel runs since round 4; the forms above stay the unit API, the corner
 // configurations below and the A/B build -DMCR_K1_EXACT_MONTH).  The forms above mirror the reference's roundings operation

@@ -278,7 +278,29 @@ constexpr bool kUniformFixups = false;
 #else
 constexpr bool kUniformFixups = true;
 #endif
-template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault, int GF = 0, int MF = 0>
+// Scalar month counters of the kernels that have growth, month and stream forms (kScalarCounters in path_kernel): the month's
+// wave-uniform bookkeeping in running scalars instead of a multiply, a modulo and a compare chain a month.  Every other kernel
+// holds the empty object and the expressions it always had (the overloads below), so that its code is what it was.
+//   row: the row of the retirement month that comes up next; moy: the accumulation month of the year, 1 .. 12;
+//   ye_mi: the month mi of a retirement year in which a year of the plan ends, (wm + mi + 1) % 12 == 0;
+//   prio_next: the next row at which the wave's priority falls (rows come up in order, so one compare a month is enough).
+struct MonthCounters { int prio_next, row, moy, ye_mi; };
+struct NoMonthCounters {};
+// (each call site passes the one value its variant reads, chosen by a constant condition: the other is not even evaluated)
+__device__ __forceinline__ bool year_opens(const MonthCounters& c, int) { return c.moy == 1; }
+__device__ __forceinline__ bool year_opens(const NoMonthCounters&, int months_done) { return months_done % kMPY == 0; }
+__device__ __forceinline__ bool year_closes(const MonthCounters& c, int) { return c.moy == kMPY; }
+__device__ __forceinline__ bool year_closes(const NoMonthCounters&, int m) { return m % kMPY == 0; }
+__device__ __forceinline__ int month_row(const MonthCounters& c, int) { return c.row; }
+__device__ __forceinline__ int month_row(const NoMonthCounters&, int row) { return row; }
+// the first of the ascending thresholds t1 <= t2 <= t3 that is >= r
+__device__ __forceinline__ int prio_from(int t1, int t2, int t3, int r) { return t1 >= r ? t1 : t2 >= r ? t2 : t3 >= r ? t3 : INT32_MAX; }
+// Stream form kStreamsInRegs: the netted amounts of the launch's (at most two) indexed records, and each window as its first
+// ROW (start + wm, saturated) and its length in months — the month tests (unsigned)(row - first) < length
+struct StreamRegs { double a0, a1; int s0, s1; unsigned n0, n1; };
+struct NoStreamRegs {};
+
+template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault, int GF = 0, int MF = 0, int SF = 0>
 __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE == 8 || PHASE == 9) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
                                                          const DevParams* __restrict__ cand_params) {
     // MODE 3 (mcr_run_year_bins_rng): YEARLY BINS.  The arithmetic of MODE 2, but wherever that variant stores a yearly sample
@@ -311,6 +333,17 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     constexpr bool kGrid = PHASE == 6;                    // ... of grid row blockIdx.y (GridCell)
     constexpr bool kCand = PHASE == 2 || PHASE == 4 || kExpFan;   // resumes from a PHASE 1 snapshot (PHASE 2 / 4: per-candidate parameter block)
     constexpr bool kSliced = PHASE == 3 || PHASE == 4;    // time-sliced path blocks
+    // the kernels that have growth, month and stream forms (kHasGrowthForms on the host) keep the month's wave-uniform counters
+    // in running scalars: the row, the month of the year, the next priority threshold ("Scalar month counters" below)
+    // (not the GF 3, MF 0 kernels at SF 0: with the counters they spill one to four SGPRs more than they did — LABNOTES R15 —
+    // so they keep the month's old bookkeeping; their SF 1 forms read the running row and have it)
+    constexpr bool kSIR = (SF & kStreamsInRegs) != 0;     // stream form (mcr_device.h): at most two records, all indexed, held in SGPRs
+    constexpr bool kScalarCounters = MODE == 0 && RNG == 0 && !ANNUAL && !INJ && (PHASE == 0 || PHASE == 3) && !SPLIT && !XS &&
+                                     (kSIR || !(GF == (kGrowthNarrowExp | kGrowthRhoZero) && MF == 0));
+    // (both objects are declared HERE, with the phase constants: declared where they are first used, further down, the empty
+    // objects reorder scalar instructions of eight time-sliced kernels that never read them — LABNOTES R15)
+    [[maybe_unused]] std::conditional_t<kScalarCounters, MonthCounters, NoMonthCounters> SC;    // (an empty object in every other variant)
+    [[maybe_unused]] std::conditional_t<kSIR, StreamRegs, NoStreamRegs> SR;    // (an empty object in every other variant)
     static_assert(!kSliced || (RNG == 0 && !INJ && !SPLIT && !XS), "time-sliced blocks exist for the plain Philox variants");
     static_assert(PHASE != 4 || MODE == 0, "the search probes count only");
     // TAXED: which assets carry an effective realized-gains rate (bit 0: inv1, bit 1: inv2; DevParams::tax_mask)
@@ -330,6 +363,10 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
                   "month forms exist for the kernels that have growth forms, in the tolerance form of the month");
     static_assert(!(MF & kMonthEqualRates) || TAXED == 3, "equal realized-gains rates: both assets are taxed");
     constexpr bool EQR = (MF & kMonthEqualRates) != 0;
+    // SF: the launch's stream form (mcr_device.h: kStreamsInRegs; masks 0 and 1), for the same kernels.  Behind MF, with a default.
+    static_assert(SF == 0 || SF == kStreamsInRegs, "stream forms: masks 0 and 1");
+    static_assert(SF == 0 || (MODE == 0 && RNG == (int)MCR_RNG_PHILOX && !ANNUAL && !INJ && (PHASE == 0 || PHASE == 3) && !SPLIT && !XS && !EXACT),
+                  "stream forms exist for the kernels that have growth forms, in the tolerance form of the month");
     constexpr bool TOL = !EXACT;         // the month in its tolerance form (mcr_device.h: "TOLERANCE FORM of the month")
     constexpr bool MM = !SPLIT || kFan;  // exec-masked moves (issue-bound launches) vs the compiler's selects (latency-bound SPLIT launches): MCR_MASKED_MOVE, mcr_device.h
     // the tolerance month's dust / empty fix-ups tested once per wave (mcr_device.h: WAVE-UNIFORM fix-ups), issue-bound launches only
@@ -452,10 +489,22 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     __builtin_amdgcn_s_setprio(3);
     bool wg_dead = false;      // SPLIT: no consumer lane of the workgroup is alive any more (wave-uniform, agreed at a barrier)
     bool lane_alive = true;    // SPLIT: this consumer lane still has months to simulate
+    // Scalar month counters (MonthCounters above): a month compares its row with the NEXT threshold only; the chain, and the
+    // threshold after it, run in the three months a path hits one
+    if constexpr (kScalarCounters) { SC.prio_next = prio_t1; SC.row = 0; SC.moy = 0; SC.ye_mi = kMPY - 1 - P.working_months % kMPY; }   // (prio_t1 = prio_from(.., 0))
     auto begin_month = [&](int row) {
+        if constexpr (kScalarCounters) {
+            if (row == SC.prio_next) {
+                if (row == prio_t1) __builtin_amdgcn_s_setprio(2);
+                else if (row == prio_t2) __builtin_amdgcn_s_setprio(1);
+                else if (row == prio_t3) __builtin_amdgcn_s_setprio(0);
+                SC.prio_next = prio_from(prio_t1, prio_t2, prio_t3, row + 1);
+            }
+        } else {
         if (row == prio_t1) __builtin_amdgcn_s_setprio(2);
         else if (row == prio_t2) __builtin_amdgcn_s_setprio(1);
         else if (row == prio_t3) __builtin_amdgcn_s_setprio(0);
+        }
         if (kStaged && (row & 1) == 0) {
             if (SPLIT) {
                 // the producers have staged the pair (row, row + 1) in buffer (row >> 1) & 1.  Every kSplitVotePairs-th pair the barrier
@@ -624,7 +673,8 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
                 if (r0 >= prio_t3) __builtin_amdgcn_s_setprio(0);
                 else if (r0 >= prio_t2) __builtin_amdgcn_s_setprio(1);
                 else if (r0 >= prio_t1) __builtin_amdgcn_s_setprio(2);
-                if (r0 & 1) begin_month(r0 - 1);   // the pair of rows (r0 - 1, r0) was staged by the predecessor: stage it again
+                if constexpr (kScalarCounters) { SC.prio_next = prio_from(prio_t1, prio_t2, prio_t3, r0 - (r0 & 1)); SC.row = r0; }
+                if (r0 & 1) begin_month(r0 - 1);  // the pair of rows (r0 - 1, r0) was staged by the predecessor: stage it again
             }
         }
     }
@@ -639,8 +689,10 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         if (wm & 1) begin_month(wm - 1);   // the pair of rows (wm - 1, wm) was staged during the accumulation: stage it again
     }
     // ---- accumulation (:513-579): no lane leaves this loop early ----
+    // (kScalarCounters: moy = m mod 12 in 1 .. 12, a running month of the year instead of the two % kMPY tests)
     for (int m = 1; m <= ((kCand || (kSliced && seg_resumed)) ? 0 : wm); ++m) {
-        if (P.contrib_grows && (m - 1) % kMPY == 0 && m > 1) {  // :514-517 (wave-uniform: a scalar branch, not a select)
+        if constexpr (kScalarCounters) ++SC.moy;
+        if (P.contrib_grows && year_opens(SC, m - 1) && m > 1) {  // :514-517 (wave-uniform: a scalar branch, not a select)
             asm volatile("");
             contrib *= P.contrib_growth_factor;
         }
@@ -653,7 +705,8 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         b1 += k1; c1 += k1; b2 += k2; c2 += k2;                        // :544-547
         if (TOL) rebalance_tol<TANY, MM, kFastMonth, EQR>(P, L, b1, c1, b2, c2);  // :549-553
         else rebalance_path<TANY, MM>(L, b1, c1, b2, c2);
-        if (m % kMPY == 0) {                                           // :557
+        if (year_closes(SC, m)) {                                      // :557
+            if constexpr (kScalarCounters) SC.moy = 0;
             pre_fail |= annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, TOL, EQR>(P, L, b1, c1, b2, c2, gacc1, gacc2);  // :558-573
             put_sample(t_idx++, b1 + b2, infl);                        // :574-576
             gacc1 = 0.0; gacc2 = 0.0;                                  // :578-579
@@ -661,6 +714,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         if (PHASE == 1 && snap_i < io.n_snap && m == io.snap_months[snap_i]) save_snapshot();
     }
     if (PHASE == 1) return;   // (every thread of the workgroup: nothing below is needed)
+    if constexpr (kScalarCounters) { if (!(kSliced && seg_resumed)) SC.row = wm; }   // (a resumed segment starts at its own row)
     double start_balance = b1 + b2;        // :581
     double infl_ret = infl;                // :582
     if (kSliced && seg_resumed) { start_balance = seg_start_balance; infl_ret = seg_infl_ret; t_idx = P.trajectory_len - ry + y_begin; }
@@ -692,6 +746,19 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
             asm volatile("" : "+s"(S1.amount), "+s"(S1.keep), "+s"(S1.start_month), "+s"(S1.end_month), "+s"(S1.indexed), "+s"(S1.lock_slot));
         }
     }
+    // Stream form kStreamsInRegs (the host gives it to a launch whose kept records are at most two, all inflation-indexed):
+    // the records are read once and pinned in SGPRs like S0 / S1 above — 8 SGPRs, against the 8 that the list's pointer,
+    // counter and temporaries held.  An absent record has length 0.
+    if constexpr (kSIR) {
+        auto to_row = [&](int32_t m) { return m > INT32_MAX - wm ? INT32_MAX : m + wm; };
+        // (the host gives 0 <= start <= end; a record with end < start has the empty window the loop form's two tests give it)
+        auto window_months = [](int first, int end) { return end > first ? (unsigned)(end - first) : 0u; };
+        SR = StreamRegs{0.0, 0.0, 0, 0, 0u, 0u};
+        if (P.n_streams > 0) { SR.a0 = P.streams[0].amount_keep; SR.s0 = to_row(P.streams[0].start_month); SR.n0 = window_months(SR.s0, to_row(P.streams[0].end_month)); }
+        if (P.n_streams > 1) { SR.a1 = P.streams[1].amount_keep; SR.s1 = to_row(P.streams[1].start_month); SR.n1 = window_months(SR.s1, to_row(P.streams[1].end_month)); }
+        asm volatile("" : "+s"(SR.a0), "+s"(SR.s0), "+s"(SR.n0));
+        asm volatile("" : "+s"(SR.a1), "+s"(SR.s1), "+s"(SR.n1));
+    }
     // PHASE 5: this wave's spending level, an SGPR (kernel-argument array, wave-uniform index)
     const double fan_expenses = kGrid ? cell->levels[fan_j] : kExpFan ? io.fan_expenses[fan_j] : 0.0;
     int ruin_bin = pre_fail ? 0 : -1;
@@ -712,10 +779,10 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         int fail_rmi = 0;
         for (int mi = 0; mi < kMPY; ++mi) {
             const int rmi = year * kMPY + mi;  // :641-643
-            begin_month(wm + rmi);
+            begin_month(month_row(SC, wm + rmi));
             if (alive && !yfail) {
                 double g1, ginf, g2;
-                if (kStaged) growth(wm + rmi, g1, ginf, g2);           // staged factors: the LDS reads are issued early
+                if (kStaged) growth(month_row(SC, wm + rmi), g1, ginf, g2);    // staged factors: the LDS reads are issued early
                 const double price = infl;                             // :644
                 const double expenses = (kExpFan ? fan_expenses : kScnFan ? scn_expenses : P.monthly_expenses) * price;   // :645-647
                 // exact form: income accumulates (:649-677) and need = max(0, expenses - income); tolerance form: `income` runs
@@ -746,7 +813,11 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
                     if (P.n_streams > 1) stream_income(S1);
                     s = 2;
                 }
-                for (; s < P.n_streams; ++s) stream_income(P.streams[s]);    // :650 (wave-uniform; the record is re-read from the kernel arguments)
+                if constexpr (kSIR) {   // the whole list: two indexed records in SGPRs, the same FMAs in list order
+                    // (wave-uniform: scalar branches, not selects; one unsigned compare tests both ends of a window)
+                    if ((unsigned)(SC.row - SR.s0) < SR.n0) { asm volatile(""); income = __builtin_fma(-SR.a0, price, income); }
+                    if ((unsigned)(SC.row - SR.s1) < SR.n1) { asm volatile(""); income = __builtin_fma(-SR.a1, price, income); }
+                } else for (; s < P.n_streams; ++s) stream_income(P.streams[s]);    // :650 (wave-uniform; the record is re-read from the kernel arguments)
                 if (XS && P.n_extra_streams > 0) {                                 // the rest of the list (config.py:99 has no length limit): scalar loads from the device table
                     const DevStreamTable xs = (DevStreamTable)P.extra_streams;
                     for (int x = 0; x < P.n_extra_streams; ++x) {
@@ -795,6 +866,15 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
                     }
                     sell_fraction_tol<MM, FAST>(phi, b1, c1, b2, c2);                 // :757-776
                     rebalance_tol<TANY, MM, kFastMonth, EQR>(P, L, b1, c1, b2, c2);   // :792-796
+                    // (the counters' form in a branch of its own: named in the other kernels' month, SC would be one more capture of
+                    // this lambda, which is enough to reorder their code)
+                    if constexpr (kScalarCounters) {
+                        if (!yfail && mi == SC.ye_mi) {                               // :798-804
+                            const bool tf = annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, true, EQR>(P, L, b1, c1, b2, c2, gacc1, gacc2);  // :805-818
+                            gacc1 = 0.0; gacc2 = 0.0;                                 // :819-820
+                            yfail = yfail || tf;                                      // :821-822
+                        }
+                    } else
                     if (!yfail && (wm + rmi + 1) % kMPY == 0) {                       // :798-804
                         const bool tf = annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, true, EQR>(P, L, b1, c1, b2, c2, gacc1, gacc2);  // :805-818
                         gacc1 = 0.0; gacc2 = 0.0;                                     // :819-820
@@ -802,7 +882,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
                     }
                 };
                 if (!stop) {
-                    if (!kStaged) growth(wm + rmi, g1, ginf, g2);      // :692-705 (sequential generators draw here)
+                    if (!kStaged) growth(month_row(SC, wm + rmi), g1, ginf, g2);      // :692-705 (sequential generators draw here)
                     market_step<ANNUAL, TOL>(g1, ginf, g2, b1, b2, gacc1, gacc2, infl);  // :706-714
                     // Both balances > fast_floor >= 1e-6 in every active lane: FAIL-2 cannot fire (b1 + b2 > 1e-6), no capacity is
                     // zeroed, each is > 0 (cap_i >= b_i (1 - r_i), r_i <= 1 - 1e-6 in the tolerance form), no asset is left alone,
@@ -843,6 +923,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
                 }
                 if (yfail) fail_rmi = rmi;  // :825-828, :844-847
             }
+            if constexpr (kScalarCounters) ++SC.row;
         }
         // ---- year end (:830-868); lanes that were already dead pad with 0 / NaN (:902-916,:934-935) ----
         double sample = 0.0;
@@ -1626,6 +1707,40 @@ static int month_form_of(const DevParams& d, bool has_variants, int* mask) {
     return MCR_OK;
 }
 
+// The STREAM FORM of a launch (mcr_device.h: kStreamsInRegs), from its parameter block alone: the records handed to the
+// kernel (derive_params has dropped the ones that pay nothing) are at most two, none sits in the extra table, and every one
+// is inflation-indexed — in the tolerance form of the month, with no annual-gains tax (the kernels that have the variants).
+// An empty list qualifies.  MCR_K1_STREAM_FORM=0|1 forces a LOWER mask, under the rules of MCR_K1_MONTH_FORM.  A library built
+// with -DMCR_K1_EXACT_MONTH has no stream forms: no launch qualifies there.
+static int stream_form_qualified(const DevParams& d) {
+    if (kExactMonthDefault) return 0;
+    if (d.any_annual_tax || d.exact_month || d.n_extra_streams > 0 || d.n_streams > 2) return 0;
+    for (int s = 0; s < d.n_streams; ++s) if (!d.streams[s].indexed) return 0;
+    return kStreamsInRegs;
+}
+static int stream_form_of(const DevParams& d, bool has_variants, int* mask) {
+    const int q = stream_form_qualified(d);
+    *mask = has_variants ? q : 0;
+    const char* e = std::getenv("MCR_K1_STREAM_FORM");
+    if (!e || !*e) return MCR_OK;
+    char* end = nullptr;
+    const long want = std::strtol(e, &end, 10);
+    if (*end != '\0' || (want != 0 && want != kStreamsInRegs)) {
+        set_error("MCR_K1_STREAM_FORM=%s: the stream forms are 0 and 1", e);
+        return MCR_ERR_INVALID_ARG;
+    }
+    if (want != 0 && !has_variants) {
+        set_error("MCR_K1_STREAM_FORM=%s set on a launch whose kernel has no stream variants", e);
+        return MCR_ERR_INVALID_ARG;
+    }
+    if (((int)want & ~q) != 0) {
+        set_error("MCR_K1_STREAM_FORM=%s: the parameters qualify for mask %d only (at most two paying income streams, all inflation-indexed, no annual-gains tax)", e, q);
+        return MCR_ERR_INVALID_ARG;
+    }
+    *mask = (int)want;
+    return MCR_OK;
+}
+
 // LDS of one path_kernel launch.  STATIC part of the variant — it mirrors the __shared__ declarations at the top of the
 // kernel: the math tables, the stage of growth factors (Philox stream without injection; twice for the producer / consumer
 // form) and the three per-path summary columns (those variants with per-path outputs) — plus the launch's DYNAMIC part: the
@@ -1850,6 +1965,11 @@ template <int T, typename F> static inline void for_month_form(int mf, F&& f) {
     if constexpr (T == 3 && !kExactMonthDefault) { if (mf == kMonthEqualRates) { f(int_c<kMonthEqualRates>{}); return; } }
     f(int_c<0>{});
 }
+// f(S): S = the launch's stream form (stream_form_of); the exact-month build has none
+template <typename F> static inline void for_stream_form(int sf, F&& f) {
+    if constexpr (!kExactMonthDefault) { if (sf == kStreamsInRegs) { f(int_c<kStreamsInRegs>{}); return; } }
+    f(int_c<0>{});
+}
 // whether path_kernel<MODE, RNG, ., ANNUAL, ...> of a whole-path or time-sliced launch has growth variants (kPerPathPhilox)
 template <int MODE, int RNG, bool ANNUAL, bool XS> constexpr bool kHasGrowthForms = MODE == 0 && RNG == 0 && !ANNUAL && !XS;
 template <typename F> static inline void for_output_mode(int mode, F&& f) {
@@ -1991,6 +2111,9 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
     int mf = 0;     // ... and its month form: the same kernels
     rc = month_form_of(d, !np_rng && !injected && !xs && !split && mode == 0 && !d.any_annual_tax, &mf);
     if (rc != MCR_OK) return rc;
+    int sf = 0;     // ... and its stream form
+    rc = stream_form_of(d, !np_rng && !injected && !xs && !split && mode == 0 && !d.any_annual_tax, &sf);
+    if (rc != MCR_OK) return rc;
     StreamSideBlock side;
     rc = side.attach(d, extra, grid.x, stream);
     if (rc != MCR_OK) { (void)side.release(stream); return rc; }
@@ -2002,8 +2125,10 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
                 if constexpr (kHasGrowthForms<decltype(M)::value, decltype(R)::value, decltype(A)::value, decltype(X)::value>) {
                     for_growth_form(gf, [&](auto G) {
                         for_month_form<decltype(T)::value>(mf, [&](auto F) {
-                            hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, false, false, 0, false, false, kExactMonthDefault, decltype(G)::value, decltype(F)::value>),
-                                               grid, block, lds, stream, d, io, no_cand);
+                            for_stream_form(sf, [&](auto S) {
+                                hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, false, false, 0, false, false, kExactMonthDefault, decltype(G)::value, decltype(F)::value, decltype(S)::value>),
+                                                   grid, block, lds, stream, d, io, no_cand);
+                            });
                         });
                     });
                 } else {
@@ -2045,8 +2170,10 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
                         if constexpr (kHasGrowthForms<decltype(M)::value, 0, decltype(A)::value, false>) {
                             for_growth_form(gf, [&](auto G) {
                                 for_month_form<decltype(T)::value>(mf, [&](auto F) {
-                                    launch_sliced(&path_kernel<0, 0, decltype(T)::value, false, false, 3, false, false, kExactMonthDefault, decltype(G)::value, decltype(F)::value>, plan,
-                                                  seg_order ? order : nullptr, block, lds, stream, d, io, no_cand);
+                                    for_stream_form(sf, [&](auto S) {
+                                        launch_sliced(&path_kernel<0, 0, decltype(T)::value, false, false, 3, false, false, kExactMonthDefault, decltype(G)::value, decltype(F)::value, decltype(S)::value>, plan,
+                                                      seg_order ? order : nullptr, block, lds, stream, d, io, no_cand);
+                                    });
                                 });
                             });
                         } else {
@@ -2656,6 +2783,19 @@ int mcr_k1_month_form(const mcr_params* p, int32_t working_months, int32_t* mask
     if (rc != MCR_OK) return rc;
     int m = 0;
     rc = month_form_of(d, true, &m);
+    if (rc != MCR_OK) return rc;
+    *mask = m;
+    return MCR_OK;
+}
+
+int mcr_k1_stream_form(const mcr_params* p, int32_t working_months, int32_t* mask) {
+    if (!mask) { set_error("null mask"); return MCR_ERR_INVALID_ARG; }
+    DevParams d;
+    std::vector<DevStream> extra;
+    int rc = derive_params(p, working_months, &d, &extra);
+    if (rc != MCR_OK) return rc;
+    int m = 0;
+    rc = stream_form_of(d, true, &m);
     if (rc != MCR_OK) return rc;
     *mask = m;
     return MCR_OK;

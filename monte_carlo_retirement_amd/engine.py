@@ -58,6 +58,16 @@ def month_form(params: McrParams, working_months: int) -> int:
     return int(mask.value)
 
 
+def stream_form(params: McrParams, working_months: int) -> int:
+    """Stream form (0 or 1) a whole-path count-only launch of these parameters runs (mcr_k1_stream_form; honours
+    MCR_K1_STREAM_FORM); ``ValueError`` if the parameters, or a forced form they do not qualify for, are invalid."""
+    mask = C.c_int32(-1)
+    rc = N.load_library().mcr_k1_stream_form(C.byref(params), int(working_months), C.byref(mask))
+    if rc != 0:
+        raise ValueError(N.last_error() or "invalid params / stream form")
+    return int(mask.value)
+
+
 def kept_streams(params: McrParams, working_months: int) -> list:
     """``(index, lock_slot)`` of every ``other_income_streams`` record the path kernel is given, in list order
     (mcr_k1_kept_streams): records that pay nothing are left out, and the lock slots (-1: an indexed stream has none) are
