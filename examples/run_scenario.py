@@ -11,6 +11,9 @@ switch to the final seed stream, run the final batch, print the response documen
     python examples/run_scenario.py scenarios/config.json --working-months 180 --min-contribution
     python examples/run_scenario.py scenarios/config.json --min-initial-balance
     python examples/run_scenario.py scenarios/config.json --min-initial-balance --at-expenses 3000,4000,5000
+    python examples/run_scenario.py scenarios/config.json --working-months 240 --income-options "State Pension" \
+        --claim-ages 62,67,70 --claim-amounts 2800,4000,4960
+    python examples/run_scenario.py scenarios/config.json --working-months 240 --min-income "State Pension" --claim-age 67
     python examples/run_scenario.py scenarios/config.json --working-months 240 --stress
     python examples/run_scenario.py scenarios/config.json --working-months 240 --breakeven inv1_returns_mean,inflation_rate_mean
     python examples/run_scenario.py scenarios/config.json --frontier 180,240,300
@@ -35,7 +38,12 @@ min_initial_balance, probability, withdrawal_rate_pct}` — the safe-withdrawal-
 `--stress` prints the market-assumption stress table at `--working-months` (or the searched minimum): the success probability
 under the config's market and under one-at-a-time shifts of its means, volatilities and correlation, one probe over the same
 random numbers.  `--breakeven FIELD[,FIELD...]` runs the break-even search for each listed mean or volatility: the most adverse
-value at which the target is still met (`--window`, `--breakeven-resolution`).  Both may be given together."""
+value at which the target is still met (`--window`, `--breakeven-resolution`).  Both may be given together.
+`--income-options STREAM` (a list index into `other_income_streams`, or a unique name) with `--claim-ages` and / or
+`--claim-amounts` prints the claiming-option table of that stream at `--working-months` (default 0): `{stream, options:
+[{the six fields, probability}], best}` over the same random numbers; lists of unequal length are an error.  `--min-income
+STREAM [--claim-age A]` answers "how large does this income have to be": the smallest monthly amount (whole cents) of that
+stream, started at age A (default: its own), that reaches the target, printed like `--min-initial-balance`."""
 
 from __future__ import annotations
 
@@ -79,6 +87,13 @@ def main() -> int:
                     help="comma-separated Config names of market means / volatilities: the break-even search for each")
     ap.add_argument("--window", type=float, default=0.25, help="--breakeven: half-width of the searched window")
     ap.add_argument("--breakeven-resolution", type=float, default=1e-4, help="--breakeven: the level grid (default one basis point)")
+    ap.add_argument("--income-options", default=None, metavar="STREAM",
+                    help="index or name of an income stream: the table of --claim-ages / --claim-amounts options instead")
+    ap.add_argument("--claim-ages", default=None, help="--income-options: comma-separated start_at_age, one per option")
+    ap.add_argument("--claim-amounts", default=None, help="--income-options: comma-separated monthly_amount_today, one per option")
+    ap.add_argument("--min-income", default=None, metavar="STREAM",
+                    help="index or name of an income stream: search its minimum monthly amount at --working-months (default 0) instead")
+    ap.add_argument("--claim-age", type=float, default=None, help="--min-income: the stream's start_at_age (default: its own)")
     ap.add_argument("--frontier", default=None, help="comma-separated working months: maximum monthly expenses at each")
     ap.add_argument("--grid-months", default=None, help="comma-separated working months of a success-probability table")
     ap.add_argument("--grid-expenses", default=None, help="comma-separated monthly expenses of that table")
@@ -91,6 +106,19 @@ def main() -> int:
         ap.error("--min-initial-balance, --min-contribution and --max-expenses are separate questions")
     if args.at_expenses and not args.min_initial_balance:
         ap.error("--at-expenses goes with --min-initial-balance")
+    if (args.income_options is not None or args.min_income is not None) and (args.min_initial_balance or args.min_contribution or args.max_expenses):
+        ap.error("--income-options / --min-income and the other searches are separate questions")
+    if args.income_options is not None and args.min_income is not None:
+        ap.error("--income-options and --min-income are separate questions")
+    if (args.claim_ages or args.claim_amounts) and args.income_options is None:
+        ap.error("--claim-ages / --claim-amounts go with --income-options")
+    if args.claim_age is not None and args.min_income is None:
+        ap.error("--claim-age goes with --min-income")
+    if args.income_options is not None:
+        if not (args.claim_ages or args.claim_amounts):
+            ap.error("--income-options needs --claim-ages and / or --claim-amounts")
+        if args.claim_ages and args.claim_amounts and len(_csv(args.claim_ages, float)) != len(_csv(args.claim_amounts, float)):
+            ap.error("--claim-ages and --claim-amounts must list one value per option each (equal lengths)")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank0 = int(os.environ.get("RANK", "0")) == 0
@@ -125,6 +153,10 @@ def main() -> int:
         return min_contribution(args, config, world, rank0)
     if args.min_initial_balance:
         return min_initial_balance(args, config, world, rank0)
+    if args.income_options is not None:
+        return income_table(args, config, world, rank0)
+    if args.min_income is not None:
+        return min_income(args, config, world, rank0)
     if args.stress or args.breakeven:
         return stress(args, config, world, rank0)
     if args.frontier or args.grid_months or args.grid_expenses:
@@ -292,6 +324,67 @@ def min_initial_balance(args, config: Config, world: int, rank0: bool) -> int:
         out["frontier"] = [{"monthly_expenses": e, "min_initial_balance": b, "probability": pr,
                             "withdrawal_rate_pct": 1200.0 * e / b if b > 0 else None}
                            for e, (b, pr, _) in zip(levels, results)]
+    if rank0:
+        print(json.dumps(out))
+    if world > 1:
+        import torch.distributed as dist
+
+        dist.barrier()
+        dist.destroy_process_group()
+    return 0
+
+
+def _stream_arg(text: str):
+    """STREAM of --income-options / --min-income: a list index where it reads as one, else a name"""
+    return int(text) if text.strip().lstrip("+").isdigit() else text
+
+
+def income_table(args, config: Config, world: int, rank0: bool) -> int:
+    from monte_carlo_retirement_amd.simulation import RetirementMonteCarloSimulator
+
+    t0 = time.perf_counter()
+    sim = RetirementMonteCarloSimulator(config, main_seed_override=args.seed, rng=args.rng)
+    wm = 0 if args.working_months is None else int(args.working_months)
+    ages = _csv(args.claim_ages, float) if args.claim_ages else None
+    amounts = _csv(args.claim_amounts, float) if args.claim_amounts else None
+    options = [{} for _ in (ages or amounts)]
+    for k, o in enumerate(options):
+        if ages:
+            o["start_at_age"] = ages[k]
+        if amounts:
+            o["monthly_amount_today"] = amounts[k]
+    sim.use_final_seeds()
+    table = sim.compare_claiming_options(wm, _stream_arg(args.income_options), options)
+    out = {"scenario": config.Nickname, "rng": args.rng, "working_months": wm, "num_simulations": int(config.num_simulations_main),
+           "target_probability": config.target_probability, **table, "seconds": round(time.perf_counter() - t0, 3)}
+    if rank0:
+        print(json.dumps(out))
+    if world > 1:
+        import torch.distributed as dist
+
+        dist.barrier()
+        dist.destroy_process_group()
+    return 0
+
+
+def min_income(args, config: Config, world: int, rank0: bool) -> int:
+    from monte_carlo_retirement_amd.income import stream_index
+    from monte_carlo_retirement_amd.simulation import RetirementMonteCarloSimulator
+
+    t0 = time.perf_counter()
+    sim = RetirementMonteCarloSimulator(config, main_seed_override=args.seed, rng=args.rng)
+    wm = 0 if args.working_months is None else int(args.working_months)
+    index = stream_index(config, _stream_arg(args.min_income))
+    events = []
+    amount, prob, curve = sim.find_minimum_income_amount(wm, index, start_at_age=args.claim_age, verbose=False,
+                                                         progress_callback=events.append, resolution=args.resolution)
+    out = {
+        "scenario": config.Nickname, "rng": args.rng, "working_months": wm, "stream": index,
+        "start_at_age": float(config.other_income_streams[index].start_at_age if args.claim_age is None else args.claim_age),
+        "target_probability": config.target_probability, "min_income_amount": amount, "probability": prob,
+        "probes": len({e["iteration"] for e in events}), "curve": curve,
+        "seconds": round(time.perf_counter() - t0, 3),
+    }
     if rank0:
         print(json.dumps(out))
     if world > 1:

@@ -401,6 +401,40 @@ int mcr_probe_assumptions_rng(const mcr_params* p, const mcr_rng* rng, uint32_t 
 int mcr_probe_assumptions_last_fanout_launches(void);
 
 /*
+ * Income options: success counts of SEVERAL versions of ONE income stream (claim at 62, 67 or 70; a larger or smaller
+ * annuity; a bridge job of three years or five) at one working-month count over the same path range — the probe of the
+ * claiming-option table and of the required-income search.  counts[k] equals, bit for bit, the counters of a count-only
+ * mcr_run_batch_rng call with the same arguments and six fields of *p replaced by options[k]: initial_balance,
+ * monthly_contribution, monthly_expenses, and monthly_amount_today, start_at_age and duration_years (-1 = None) of entry
+ * stream_index of the stream list (the index counts the whole list, extra_streams included).  The stream's tax_rate and
+ * inflation_indexed stay the list's own.  options is a HOST array of n_options >= 0 records (0 does nothing; duplicates
+ * allowed).  0 <= stream_index < n_streams; the three amounts and monthly_amount_today finite and >= 0 (config.py:56, 57, 59,
+ * 18), start_at_age finite and in [0, 120] (config.py `Age`), duration_years >= -1, reserved == 0; everything is validated
+ * before anything is enqueued: on an error counts stay untouched and the message names options[k].<field>.  One option: the
+ * plain count-only launch.  Philox stream, at most MCR_INLINE_STREAMS kept income streams (the probed one always counts), the
+ * tolerance month, n_paths <= 2^31 and at least MCR_INCOME_FANOUT_MIN_WAVES path-wavefronts (environment, default 0): INCOME
+ * FAN-OUT launches, the scenario fan-out's workgroup in which each of up to MCR_MAX_EXPENSE_FANOUT consumer waves also carries
+ * its own record of the one stream (netted amount, first and last month), derived by the host code that derives a parameter
+ * block's stream records; the records travel in a stream-ordered device table of 48 B each, released behind the launches.
+ * Otherwise (NumPy stream, longer stream lists, the exact month, allocation refused): one count-only launch per option on
+ * internal side streams, joined back onto `hip_stream`.  counts: DEVICE uint64 [n_options][MCR_N_COUNTERS] = {successes,
+ * paths} (zeroed by the call).  Asynchronous like mcr_probe_scenarios_rng.
+ * mcr_probe_income_last_fanout_launches reports, for the calling thread's last call, how many income fan-out launches it
+ * enqueued: ceil(n_options / options per launch) on the fan-out route, 0 on the others and after an error.
+ */
+typedef struct mcr_income_option {
+    double initial_balance, monthly_contribution, monthly_expenses;   /* as mcr_scenario */
+    double monthly_amount_today, start_at_age;                        /* of stream `stream_index` */
+    int32_t duration_years;                                           /* -1 = None */
+    int32_t reserved;                                                 /* 0 */
+} mcr_income_option;
+int mcr_probe_income_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                         uint64_t n_paths, int32_t working_months, int32_t stream_index,
+                         const mcr_income_option* options, int32_t n_options,
+                         uint64_t* counts, int device, void* hip_stream);
+int mcr_probe_income_last_fanout_launches(void);
+
+/*
  * Retirement-month x spending grid: counts[c][k] equals, bit for bit, the counters of a count-only mcr_run_batch_rng call with
  * working_months[c] and p->monthly_expenses = monthly_expenses[c][k], everything else unchanged.  working_months: n_candidates
  * >= 0 months (any order, repeats allowed); monthly_expenses: HOST [n_candidates][n_levels] row-major, each finite and >= 0.

@@ -212,6 +212,21 @@ class McrAssumptions(C.Structure):
     ]
 
 
+class McrIncomeOption(C.Structure):
+    """One record of an income probe (include/mcr.h: mcr_income_option): the three scenario levers and the amount, start age
+    and duration (-1 = None) of the one income stream the probe varies."""
+
+    _fields_ = [
+        ("initial_balance", C.c_double),
+        ("monthly_contribution", C.c_double),
+        ("monthly_expenses", C.c_double),
+        ("monthly_amount_today", C.c_double),
+        ("start_at_age", C.c_double),
+        ("duration_years", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 class McrSizes(C.Structure):
     _fields_ = [
         ("total_months", C.c_int32),
@@ -286,6 +301,8 @@ ABI_SYMBOLS = (
     "mcr_probe_scenarios_rng",
     "mcr_probe_assumptions_rng",
     "mcr_probe_assumptions_last_fanout_launches",
+    "mcr_probe_income_rng",
+    "mcr_probe_income_last_fanout_launches",
     "mcr_probe_grid_rng",
     "mcr_run_batch_multi_host_rng",
     "mcr_run_year_bins_rng",
@@ -390,6 +407,14 @@ def _declare(lib: C.CDLL) -> None:
         ]
         lib.mcr_probe_assumptions_last_fanout_launches.restype = C.c_int
         lib.mcr_probe_assumptions_last_fanout_launches.argtypes = []
+    if hasattr(lib, "mcr_probe_income_rng"):   # (likewise)
+        lib.mcr_probe_income_rng.restype = C.c_int
+        lib.mcr_probe_income_rng.argtypes = [
+            P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, P(McrIncomeOption), C.c_int32,
+            C.c_void_p, C.c_int, C.c_void_p,
+        ]
+        lib.mcr_probe_income_last_fanout_launches.restype = C.c_int
+        lib.mcr_probe_income_last_fanout_launches.argtypes = []
     lib.mcr_probe_grid_rng.restype = C.c_int
     lib.mcr_probe_grid_rng.argtypes = [
         P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, P(C.c_int32), C.c_int32, P(C.c_double), C.c_int32,

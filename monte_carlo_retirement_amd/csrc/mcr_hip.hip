@@ -70,7 +70,8 @@ struct KernelIO {
     // PHASE 5 / 7 (expense / contribution fan-out, mcr_probe_expenses_rng / mcr_probe_contributions_rng): consumer wave j runs
     // level fan_expenses[j] (monthly_expenses / monthly_contribution) and adds its counts to counters + j * MCR_N_COUNTERS;
     // fan_n = blockDim.x / 64 - 1 levels.  PHASE 8 / 9 (scenario / assumption fan-out, mcr_probe_scenarios_rng /
-    // mcr_probe_assumptions_rng) read fan_n only: their records are a device table (path_kernel's `cand_params`)
+    // mcr_probe_assumptions_rng) read fan_n only: their records are a device table (path_kernel's `cand_params`).  PHASE 10
+    // (income fan-out, mcr_probe_income_rng) likewise, and fan_stream below
     int32_t fan_n;
     // MODE 3 (yearly bins, mcr_run_year_bins_rng) shares the bytes of the fan-out levels: no launch is both, and the layout
     // of the kernel arguments every other variant reads stays what it was
@@ -86,6 +87,7 @@ struct KernelIO {
     union {
         double fan_expenses[MCR_MAX_EXPENSE_FANOUT];   // the fan-out levels
         YearBins yb;
+        int32_t fan_stream;                            // PHASE 10: which of the kept records (DevParams::streams) the consumer waves replace
     };
 };
 static_assert(sizeof(KernelIO::YearBins) <= sizeof(double) * MCR_MAX_EXPENSE_FANOUT, "the yearly-bins block must fit the bytes it overlays");
@@ -104,6 +106,15 @@ static_assert(sizeof(mcr_scenario) == 3 * sizeof(double), "mcr_scenario is three
 // PHASE 9 (assumption probe, mcr_probe_assumptions_rng): consumer wave j of a launch runs record j of the launch's device table,
 // through `cand_params` as well: PHASE 8's three values and the market as growth_factors_row reads it (mcr_device.h), derived on
 // the host by the function derive_params uses (derive_market)
+// PHASE 10 (income probe, mcr_probe_income_rng): consumer wave j of a launch runs record j of the launch's device table, through
+// `cand_params` as well: PHASE 8's three values and ONE income stream's amount and window, derived on the host by the function
+// derive_params uses for a stream (derive_stream).  The stream's keep, indexed and lock_slot are the parameter block's own.
+struct IncomeRecord {
+    double initial_balance, monthly_contribution, monthly_expenses;
+    double amount, amount_keep;
+    int32_t start_month, end_month;
+};
+static_assert(sizeof(IncomeRecord) == 6 * sizeof(double), "IncomeRecord is five packed doubles and two months");
 struct AssumptionRecord {
     double initial_balance, monthly_contribution, monthly_expenses;
     double a1, b1, ainf, binf_rho, binf_rho_c, aprem, bprem;
@@ -263,6 +274,17 @@ __device__ __forceinline__ void year_bins_flush_final(const KernelIO::YearBins& 
 // operations of growth_rows2_form in their order (growth_factors_row) — then runs PHASE 8's month.  The seven values sit in
 // VGPRs: the fan-out kernels have no SGPRs to spare.  Counts are bit-identical to a count-only launch with the ten fields of
 // the parameter block replaced by record j.
+// PHASE 10 (SPLIT = true; mcr_probe_income_rng): INCOME FAN-OUT = PHASE 8's workgroup, barriers and votes, with ONE INCOME STREAM
+// per consumer wave as well: claim ages, annuity sizes, bridge-job lengths over the same random numbers.  The launch's records are
+// a device table of IncomeRecord behind `cand_params` (scalar loads): PHASE 8's three values, and the netted amount and the window
+// [start_month, end_month) of kept record io.fan_stream of the parameter block, derived on the host by the code derive_params
+// runs for a stream.  The record keeps its LIST POSITION (the tolerance month subtracts the streams in list order, one FMA or one
+// subtraction each: the order is part of the bits): kept record 0 or 1 lives in S0 / S1, which the wave sets from its record
+// once; a later one is substituted at its wave-uniform index of the stream loop (four scalar moves under a scalar compare).  Its keep, indexed
+// and lock_slot stay the block's own, so every consumer wave has the same lock-column layout, and each wave has its own columns:
+// the first-active-month store works per wave unchanged.  The host always hands the kernel the probed stream, also when the
+// list's own amount is 0; a record with amount 0 then subtracts an exact zero, as the plain launch that drops it.  Counts are
+// bit-identical to a count-only launch with the six fields replaced by record j.
 // EXACT = true: the month in its exact-rounding forms (mcr_device.h) instead of the tolerance form — for configurations whose
 // realized-gains rate lets the reference's denominator clamps bind (DevParams::exact_month), instantiated for the generic XS
 // variants only; -DMCR_K1_EXACT_MONTH builds a library that runs every variant that way (A/B).
@@ -299,9 +321,15 @@ __device__ __forceinline__ int prio_from(int t1, int t2, int t3, int r) { return
 // ROW (start + wm, saturated) and its length in months — the month tests (unsigned)(row - first) < length
 struct StreamRegs { double a0, a1; int s0, s1; unsigned n0, n1; };
 struct NoStreamRegs {};
+// PHASE 10: what a consumer wave keeps of its record's stream, and which of the kept records (DevParams::streams) it replaces
+struct IncomeRegs { double amount, amount_keep; int32_t start_month, end_month; int k; };
+struct NoIncomeRegs {};
+__device__ __forceinline__ void income_put(DevStream& S, const IncomeRegs& R) {
+    S.amount = R.amount; S.amount_keep = R.amount_keep; S.start_month = R.start_month; S.end_month = R.end_month;
+}
 
 template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault, int GF = 0, int MF = 0, int SF = 0>
-__global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE == 8 || PHASE == 9) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
+__global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE == 8 || PHASE == 9 || PHASE == 10) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
                                                          const DevParams* __restrict__ cand_params) {
     // MODE 3 (mcr_run_year_bins_rng): YEARLY BINS.  The arithmetic of MODE 2, but wherever that variant stores a yearly sample
     // (nominal balance, real balance, withdrawal rate) the lane bins it instead: cell 0 = below edges[0], cells 1 .. n = the
@@ -322,13 +350,15 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     static_assert(PHASE != 7 || SPLIT, "the contribution fan-out is a producer / consumer form");
     static_assert(PHASE != 8 || SPLIT, "the scenario fan-out is a producer / consumer form");
     static_assert(PHASE != 9 || SPLIT, "the assumption fan-out is a producer / consumer form");
+    static_assert(PHASE != 10 || SPLIT, "the income fan-out is a producer / consumer form");
     // PHASE 4 = PHASE 2 (a candidate's decumulation resumed from its accumulation snapshot) time-sliced like PHASE 3: the
     // 17-month verification window of the search is 17 x 196 workgroups = 2.17 rounds of the resident slots.
     constexpr bool kExpFan = PHASE == 5 || PHASE == 6;    // expense fan-out: the levels are monthly_expenses, resumed at retirement
     constexpr bool kConFan = PHASE == 7;                  // contribution fan-out: the levels are monthly_contribution, the whole path
     constexpr bool kAsmFan = PHASE == 9;                  // assumption fan-out: the scenario fan-out with the market per wave as well
     constexpr bool kStreamRegs = SPLIT && !kAsmFan;       // the first two income streams stay in SGPRs for the whole launch (S0, S1 below)
-    constexpr bool kScnFan = PHASE == 8 || kAsmFan;       // scenario fan-out: balance, contribution and spending per wave, the whole path
+    constexpr bool kIncFan = PHASE == 10;                 // income fan-out: the scenario fan-out with one income stream per wave as well
+    constexpr bool kScnFan = PHASE == 8 || kAsmFan || kIncFan;   // scenario fan-out: balance, contribution and spending per wave, the whole path
     constexpr bool kFan = kExpFan || kConFan || kScnFan;  // fan-out workgroup: one 64-path block, L consumer waves (levels), one producer wave
     constexpr bool kGrid = PHASE == 6;                    // ... of grid row blockIdx.y (GridCell)
     constexpr bool kCand = PHASE == 2 || PHASE == 4 || kExpFan;   // resumes from a PHASE 1 snapshot (PHASE 2 / 4: per-candidate parameter block)
@@ -344,6 +374,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     // objects reorder scalar instructions of eight time-sliced kernels that never read them — LABNOTES R15)
     [[maybe_unused]] std::conditional_t<kScalarCounters, MonthCounters, NoMonthCounters> SC;    // (an empty object in every other variant)
     [[maybe_unused]] std::conditional_t<kSIR, StreamRegs, NoStreamRegs> SR;    // (an empty object in every other variant)
+    [[maybe_unused]] std::conditional_t<kIncFan, IncomeRegs, NoIncomeRegs> IR;   // (likewise)
     static_assert(!kSliced || (RNG == 0 && !INJ && !SPLIT && !XS), "time-sliced blocks exist for the plain Philox variants");
     static_assert(PHASE != 4 || MODE == 0, "the search probes count only");
     // TAXED: which assets carry an effective realized-gains rate (bit 0: inv1, bit 1: inv2; DevParams::tax_mask)
@@ -619,6 +650,14 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         MK.a1 = rec->a1; MK.b1 = rec->b1; MK.ainf = rec->ainf; MK.binf_rho = rec->binf_rho; MK.binf_rho_c = rec->binf_rho_c;
         MK.aprem = rec->aprem; MK.bprem = rec->bprem;
         asm volatile("" : "+v"(MK.a1), "+v"(MK.b1), "+v"(MK.ainf), "+v"(MK.binf_rho), "+v"(MK.binf_rho_c), "+v"(MK.aprem), "+v"(MK.bprem));
+    } else if constexpr (kIncFan) {              // PHASE 10: the record's three values likewise (its stream: at S0 / S1 below)
+        const IncomeRecord* const rec = reinterpret_cast<const IncomeRecord*>(cand_params) + fan_j;
+        const double rec_balance = rec->initial_balance;
+        b1 = rec_balance * P.alloc1;             // :499
+        b2 = rec_balance - b1;                   // :500
+        c1 = b1; c2 = b2;                        // :501-502
+        contrib = rec->monthly_contribution;     // :504
+        scn_expenses = rec->monthly_expenses;
     } else if constexpr (kScnFan) {
         const mcr_scenario* const scn = reinterpret_cast<const mcr_scenario*>(cand_params) + fan_j;
         const double scn_balance = scn->initial_balance;
@@ -734,9 +773,19 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     // (kStreamRegs is declared with the phase constants above: declared here, the same constant reorders a few scalar
     // instructions of the time-sliced kernels, which never read it)
     DevStream S0 = {}, S1 = {};
+    // PHASE 10: the wave's version of kept record IR.k (wave-uniform values: SGPRs)
+    if constexpr (kIncFan) {
+        const IncomeRecord* const rec = reinterpret_cast<const IncomeRecord*>(cand_params) + fan_j;
+        IR.k = io.fan_stream;
+        IR.amount = rec->amount; IR.amount_keep = rec->amount_keep; IR.start_month = rec->start_month; IR.end_month = rec->end_month;
+    }
     if (kStreamRegs) {
         if (P.n_streams > 0) S0 = P.streams[0];
         if (P.n_streams > 1) S1 = P.streams[1];
+        if constexpr (kIncFan) {   // kept record 0 or 1 is the probed one: this wave's version of it, for the whole launch
+            if (IR.k == 0) income_put(S0, IR);
+            if (IR.k == 1) income_put(S1, IR);
+        }
         // (opaque to the compiler from here on: kernel-argument loads are otherwise rematerialised in the loop)
         if (TOL) {   // (the tolerance form of the month reads the netted amount only)
             asm volatile("" : "+s"(S0.amount_keep), "+s"(S0.start_month), "+s"(S0.end_month), "+s"(S0.indexed), "+s"(S0.lock_slot));
@@ -817,6 +866,12 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
                     // (wave-uniform: scalar branches, not selects; one unsigned compare tests both ends of a window)
                     if ((unsigned)(SC.row - SR.s0) < SR.n0) { asm volatile(""); income = __builtin_fma(-SR.a0, price, income); }
                     if ((unsigned)(SC.row - SR.s1) < SR.n1) { asm volatile(""); income = __builtin_fma(-SR.a1, price, income); }
+                } else if constexpr (kIncFan) {   // the list in its order, this wave's version of record IR.k in its place
+                    for (; s < P.n_streams; ++s) {
+                        DevStream S = P.streams[s];
+                        if (s == IR.k) income_put(S, IR);
+                        stream_income(S);
+                    }
                 } else for (; s < P.n_streams; ++s) stream_income(P.streams[s]);    // :650 (wave-uniform; the record is re-read from the kernel arguments)
                 if (XS && P.n_extra_streams > 0) {                                 // the rest of the list (config.py:99 has no length limit): scalar loads from the device table
                     const DevStreamTable xs = (DevStreamTable)P.extra_streams;
@@ -1549,11 +1604,31 @@ __attribute__((noinline)) static DevMarket derive_market(double inv1_mu_log, dou
     return m;
 }
 
+// One income stream's amount and window: derive_params fills a DevStream with it, the income probe its records (IncomeRecord).
+// ONE function, not inlined, so that a record holds the bits a parameter block with the same stream holds.
+struct DevStreamWindow { double amount, keep, amount_keep; int32_t start_month, end_month; };
+__attribute__((noinline)) static DevStreamWindow derive_stream(double current_age, int32_t wm, double monthly_amount_today, double tax_rate,
+                                                               double start_at_age, int32_t duration_years) {
+    DevStreamWindow o;
+    o.amount = monthly_amount_today;
+    o.keep = 1.0 - tax_rate;  // :676
+    o.amount_keep = o.amount * o.keep;
+    o.start_month = start_month_index(current_age, wm, start_at_age);  // :603-608
+    if (duration_years < 0) {
+        o.end_month = INT32_MAX;  // None: forever (:654)
+    } else {
+        const int64_t e = (int64_t)o.start_month + (int64_t)duration_years * kMPY;  // :609-613,:655
+        o.end_month = e > INT32_MAX ? INT32_MAX : (int32_t)e;
+    }
+    return o;
+}
+
 // Host-side derivation of the wave-uniform parameter block (same fp64 expressions as the reference).
 // `extra` receives the records of the streams beyond the by-value block (device-table layout); callers that cannot carry
 // such a table pass nullptr and get MCR_ERR_UNSUPPORTED for longer lists.
 static int derive_params(const mcr_params* p, int32_t wm, DevParams* d, std::vector<DevStream>* extra = nullptr,
-                         std::vector<std::pair<int, int>>* kept = nullptr /* (list index, lock slot) of the records the kernel gets */) {
+                         std::vector<std::pair<int, int>>* kept = nullptr /* (list index, lock slot) of the records the kernel gets */,
+                         int keep_index = -1 /* a list index whose record the kernel gets even if it pays nothing (the income probe's) */) {
     mcr_sizes sz;
     int rc = query_sizes(p, wm, &sz);
     if (rc != MCR_OK) return rc;
@@ -1595,9 +1670,10 @@ static int derive_params(const mcr_params* p, int32_t wm, DevParams* d, std::vec
     // A record that pays nothing (monthly_amount_today == 0) contributes an exact zero to every month's income, frozen or
     // indexed: income - 0 and fma(-0, price, income) are `income` (the price level is finite), and the exact form adds 0 keep
     // = +0 to a non-negative sum.  The kernel is not given it: no record to test every month, no lock column, no field in a
-    // time-sliced block's hand-over.  The kept records keep their list order; lock slots are numbered over them.
+    // time-sliced block's hand-over.  The kept records keep their list order; lock slots are numbered over them.  (keep_index:
+    // the income probe's stream is kept whatever it pays, with its lock slot if it is frozen — its consumer waves pay their own.)
     int kept_n = 0;
-    for (int s = 0; s < p->n_streams; ++s) kept_n += stream_at(p, s).monthly_amount_today != 0.0;
+    for (int s = 0; s < p->n_streams; ++s) kept_n += stream_at(p, s).monthly_amount_today != 0.0 || s == keep_index;
     d->n_streams = kept_n < MCR_INLINE_STREAMS ? kept_n : MCR_INLINE_STREAMS;
     d->n_extra_streams = kept_n - d->n_streams;
     if (extra) extra->assign((size_t)d->n_extra_streams, DevStream{});
@@ -1605,20 +1681,12 @@ static int derive_params(const mcr_params* p, int32_t wm, DevParams* d, std::vec
     int slots = 0, k = 0;
     for (int s = 0; s < p->n_streams; ++s) {
         const mcr_stream& in = stream_at(p, s);
-        if (in.monthly_amount_today == 0.0) continue;
+        if (in.monthly_amount_today == 0.0 && s != keep_index) continue;
         DevStream scratch;
         DevStream& o = k < MCR_INLINE_STREAMS ? d->streams[k] : (extra ? (*extra)[(size_t)(k - MCR_INLINE_STREAMS)] : scratch);
         ++k;
-        o.amount = in.monthly_amount_today;
-        o.keep = 1.0 - in.tax_rate;  // :676
-        o.amount_keep = o.amount * o.keep;
-        o.start_month = start_month_index(p->current_age, wm, in.start_at_age);  // :603-608
-        if (in.duration_years < 0) {
-            o.end_month = INT32_MAX;  // None: forever (:654)
-        } else {
-            const int64_t e = (int64_t)o.start_month + (int64_t)in.duration_years * kMPY;  // :609-613,:655
-            o.end_month = e > INT32_MAX ? INT32_MAX : (int32_t)e;
-        }
+        const DevStreamWindow w = derive_stream(p->current_age, wm, in.monthly_amount_today, in.tax_rate, in.start_at_age, in.duration_years);
+        o.amount = w.amount; o.keep = w.keep; o.amount_keep = w.amount_keep; o.start_month = w.start_month; o.end_month = w.end_month;
         o.indexed = in.inflation_indexed ? 1 : 0;
         o.lock_slot = o.indexed ? -1 : slots++;
         if (kept) kept->push_back({s, o.lock_slot});
@@ -2475,10 +2543,11 @@ struct LevelGroups {
 // What the expense and the contribution fan-out ask of a probe's shape.  MCR_OK: *d = the parameter block with every lock slot
 // in LDS, *lmax = levels per launch; MCR_ERR_UNSUPPORTED for shapes the form does not cover.
 static int plan_level_fanout(const mcr_params* p, const mcr_rng* rng, uint64_t n_paths, int32_t wm, int32_t n_levels, uint64_t min_waves,
-                             DevParams* d, int* lmax, bool parts = false /* PHASE 9's larger stage */) {
+                             DevParams* d, int* lmax, bool parts = false /* PHASE 9's larger stage */,
+                             int keep_index = -1, std::vector<std::pair<int, int>>* kept = nullptr /* PHASE 10: derive_params' */) {
     if (rng->kind != MCR_RNG_PHILOX || n_levels < 2 || n_paths == 0 || n_paths > ((uint64_t)1 << 31)) return MCR_ERR_UNSUPPORTED;
     if ((n_paths + 63) / 64 < min_waves) return MCR_ERR_UNSUPPORTED;
-    int rc = derive_params(p, wm, d);
+    int rc = derive_params(p, wm, d, nullptr, kept, keep_index);
     if (rc != MCR_OK) return rc;
     if (needs_generic_variant(*d)) return MCR_ERR_UNSUPPORTED;
     if ((rc = check_barrier_counts(*d)) != MCR_OK) return rc;
@@ -2631,6 +2700,63 @@ static int probe_assumptions_fanout(const mcr_params* p, const mcr_rng* rng, uin
     if (e != hipSuccess) g_last_assumption_fanout_launches = 0;
     if (e != hipSuccess) return hip_fail(e, "assumption fan-out probe");
     if (ef != hipSuccess) return hip_fail(ef, "assumption fan-out probe (free)");
+    return MCR_OK;
+}
+
+// Several versions of ONE income stream (and of the scenario fan-out's three fields) over the same paths, Philox stream: income
+// fan-out launches (PHASE 10) over groups of at most fanout_max_levels records, the whole path each.  The records are derived on
+// the host (derive_stream: the bits derive_params gives a block whose stream has those fields) into ONE stream-ordered device
+// table, as the scenario fan-out's.  The parameter block is derived with the probed stream KEPT whatever its own amount
+// (derive_params' keep_index), so the kernel has a record to replace at the stream's list position and, for a frozen stream, a
+// lock column per consumer wave; the stream's keep, indexed and lock_slot are the list's own for every record, and nothing else
+// derive_params, the lock-slot plan or the tax variant reads depends on the six fields: one parameter block serves every record.
+// Returns MCR_ERR_UNSUPPORTED, having enqueued nothing, for shapes this form does not cover and when the table's allocation is
+// refused.
+static thread_local int g_last_income_fanout_launches = 0;   // (mcr_probe_income_last_fanout_launches)
+static int probe_income_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                               int32_t wm, int32_t stream_index, const mcr_income_option* options, int32_t n_options, uint64_t* counts,
+                               hipStream_t stream) {
+    DevParams d;
+    int lmax = 0;
+    std::vector<std::pair<int, int>> kept;
+    if (int rc = plan_level_fanout(p, rng, n_paths, wm, n_options, fanout_min_waves("MCR_INCOME_FANOUT_MIN_WAVES"), &d, &lmax, false,
+                                   stream_index, &kept)) return rc;
+    int kept_k = -1;   // the probed stream's position among the kept records (all of them in the by-value block here)
+    for (size_t i = 0; i < kept.size(); ++i) if (kept[i].first == stream_index) kept_k = (int)i;
+    if (kept_k < 0 || kept_k >= d.n_streams) return MCR_ERR_UNSUPPORTED;
+    const mcr_stream& own = stream_at(p, stream_index);
+    std::vector<IncomeRecord> host((size_t)n_options);
+    for (int32_t k = 0; k < n_options; ++k) {
+        const mcr_income_option& r = options[k];
+        const DevStreamWindow w = derive_stream(p->current_age, wm, r.monthly_amount_today, own.tax_rate, r.start_at_age, r.duration_years);
+        host[(size_t)k] = IncomeRecord{r.initial_balance, r.monthly_contribution, r.monthly_expenses, w.amount, w.amount_keep, w.start_month, w.end_month};
+    }
+    KernelIO io = make_io(rng, nullptr, stream_id, path_begin, n_paths);
+    SnapshotBlock table(stream);
+    hipError_t e = hipSuccess;
+    if (!table.attach(io, 0, host.data(), host.size() * sizeof(IncomeRecord), &e, SIZE_MAX)) return MCR_ERR_UNSUPPORTED;
+    io.snap = nullptr;   // (no snapshot column: the block is the table alone)
+    if (e == hipSuccess) {
+        const IncomeRecord* d_table = (const IncomeRecord*)table.records;
+        const dim3 grid((unsigned)((n_paths + 63) / 64));
+        const LevelGroups groups(n_options, lmax);
+        for_tax_variant(d, [&](auto T, auto A) {
+            groups.for_each([&](int, int first, int lg) {
+                KernelIO fio = io;
+                fio.out.counters = counts + (size_t)first * MCR_N_COUNTERS;
+                fio.fan_n = lg;
+                fio.fan_stream = kept_k;
+                hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 10, true>), grid, dim3(64 * (lg + 1)),
+                                   fanout_dynamic_lds(d, lg), stream, d, fio, (const DevParams*)(d_table + first));
+                ++g_last_income_fanout_launches;
+            });
+        });
+        e = hipGetLastError();
+    }
+    const hipError_t ef = table.mem.release();
+    if (e != hipSuccess) g_last_income_fanout_launches = 0;
+    if (e != hipSuccess) return hip_fail(e, "income fan-out probe");
+    if (ef != hipSuccess) return hip_fail(ef, "income fan-out probe (free)");
     return MCR_OK;
 }
 
@@ -2981,6 +3107,78 @@ int mcr_probe_assumptions_rng(const mcr_params* p, const mcr_rng* rng, uint32_t 
 }
 
 int mcr_probe_assumptions_last_fanout_launches(void) { return g_last_assumption_fanout_launches; }
+
+int mcr_probe_income_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                         uint64_t n_paths, int32_t working_months, int32_t stream_index,
+                         const mcr_income_option* options, int32_t n_options,
+                         uint64_t* counts, int device, void* hip_stream) {
+    MCR_ENTER_DEVICE(device);
+    g_last_income_fanout_launches = 0;
+    if (n_options < 0) { set_error("n_options %d must be >= 0", n_options); return MCR_ERR_INVALID_ARG; }
+    if (n_options == 0) return MCR_OK;
+    if (!options || !counts) { set_error("null options / counts"); return MCR_ERR_INVALID_ARG; }
+    // validate the block, the index and every record BEFORE enqueueing anything (counts stay untouched on an error)
+    int rc = validate_months(p, &working_months, 1);
+    if (rc != MCR_OK) return rc;
+    rc = check_rng(rng);
+    if (rc != MCR_OK) return rc;
+    if (stream_index < 0 || stream_index >= p->n_streams) {
+        set_error("stream_index = %d: must be in [0, n_streams = %d)", stream_index, p->n_streams);
+        return MCR_ERR_INVALID_ARG;
+    }
+    static const struct { double mcr_income_option::*field; const char* name; int config_line; } kAmounts[4] = {
+        {&mcr_income_option::initial_balance, "initial_balance", 56},
+        {&mcr_income_option::monthly_contribution, "monthly_contribution", 57},
+        {&mcr_income_option::monthly_expenses, "monthly_expenses", 59},
+        {&mcr_income_option::monthly_amount_today, "monthly_amount_today", 18}};
+    for (int32_t k = 0; k < n_options; ++k) {
+        const mcr_income_option& r = options[k];
+        for (const auto& f : kAmounts) {
+            const double v = r.*(f.field);
+            if (!(std::isfinite(v) && v >= 0.0)) {
+                set_error("options[%d].%s = %g: must be finite and >= 0 (config.py:%d)", k, f.name, v, f.config_line);
+                return MCR_ERR_INVALID_ARG;
+            }
+        }
+        if (!(std::isfinite(r.start_at_age) && r.start_at_age >= 0.0 && r.start_at_age <= 120.0)) {
+            set_error("options[%d].start_at_age = %g: must be finite and in [0, 120] (config.py:23)", k, r.start_at_age);
+            return MCR_ERR_INVALID_ARG;
+        }
+        if (r.duration_years < -1) {
+            set_error("options[%d].duration_years = %d: must be >= 0, or -1 for None (config.py:33)", k, r.duration_years);
+            return MCR_ERR_INVALID_ARG;
+        }
+        if (r.reserved != 0) {
+            set_error("options[%d].reserved = %d: must be 0", k, r.reserved);
+            return MCR_ERR_INVALID_ARG;
+        }
+    }
+    hipStream_t main = (hipStream_t)hip_stream;
+    rc = zero_counters(counts, (size_t)n_options, main);
+    if (rc != MCR_OK) return rc;
+    // the per-option route's parameter block: a copy whose stream `stream_index` is rewritten per launch (launch_paths derives
+    // its records, the extra table's included, before it returns)
+    mcr_params q = *p;
+    std::vector<mcr_stream> q_extra;
+    if (p->n_streams > MCR_INLINE_STREAMS) {
+        q_extra.assign(p->extra_streams, p->extra_streams + (p->n_streams - MCR_INLINE_STREAMS));
+        q.extra_streams = q_extra.data();
+    }
+    mcr_stream& qs = stream_index < MCR_INLINE_STREAMS ? q.streams[stream_index] : q_extra[(size_t)(stream_index - MCR_INLINE_STREAMS)];
+    auto launch_option = [&](int k, hipStream_t s) {
+        const mcr_income_option& r = options[k];
+        q.initial_balance = r.initial_balance; q.monthly_contribution = r.monthly_contribution; q.monthly_expenses = r.monthly_expenses;
+        qs.monthly_amount_today = r.monthly_amount_today; qs.start_at_age = r.start_at_age; qs.duration_years = r.duration_years;
+        const mcr_outputs o = counters_only(counts + (size_t)k * MCR_N_COUNTERS);
+        return launch_paths(&q, rng, stream_id, path_begin, n_paths, working_months, nullptr, &o, s);
+    };
+    if (n_options == 1) return launch_option(0, main);
+    rc = probe_income_fanout(p, rng, stream_id, path_begin, n_paths, working_months, stream_index, options, n_options, counts, main);
+    if (rc != MCR_ERR_UNSUPPORTED) return rc;     // (unsupported shape / allocation refused: one launch per option below)
+    return fork_join(device, main, n_options, launch_option);
+}
+
+int mcr_probe_income_last_fanout_launches(void) { return g_last_income_fanout_launches; }
 
 int mcr_probe_grid_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
                        uint64_t n_paths, const int32_t* working_months, int32_t n_candidates,

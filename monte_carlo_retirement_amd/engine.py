@@ -17,7 +17,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from . import _native as N
-from ._native import McrAssumptions, McrOutputs, McrParams, McrRng, McrScenario, McrSizes, McrYearBins
+from ._native import McrAssumptions, McrIncomeOption, McrOutputs, McrParams, McrRng, McrScenario, McrSizes, McrYearBins
 
 SUMMARY_FIELDS = (
     "start_balance",
@@ -610,6 +610,37 @@ def probe_scenarios(params: McrParams, seed, stream_id: int, path_begin: int, n_
         len(records), counts.data_ptr(), int(device), C.c_void_p(stream),
     )
     N.check(rc, "mcr_probe_scenarios_rng")
+    return counts
+
+
+def probe_income(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
+                 stream_index: int, options, device: int = 0):
+    """Success counters of several versions of one income stream at one working-month count over the same path range
+    (``mcr_probe_income_rng``).  ``options`` is a sequence of 6-tuples in the order of ``mcr_income_option``:
+    ``(initial_balance, monthly_contribution, monthly_expenses, monthly_amount_today, start_at_age, duration_years)`` with
+    ``duration_years`` an int or ``None`` (paid for life); option k counts exactly what a count-only launch counts with the
+    three money fields of `params` and those three fields of entry ``stream_index`` of its stream list replaced.  Up to
+    ``MCR_MAX_EXPENSE_FANOUT`` options share each path's random numbers.  Returns a device int64 tensor ``[len(options), 2]``
+    = ``{successes, paths}``; asynchronous (reading it synchronises)."""
+    import torch
+
+    N.require_device()
+    options = [tuple(o) for o in options]
+    if any(len(o) != 6 for o in options):
+        raise ValueError("every option is (initial_balance, monthly_contribution, monthly_expenses, monthly_amount_today, "
+                         "start_at_age, duration_years)")
+    records = [McrIncomeOption(*(float(x) for x in o[:5]), -1 if o[5] is None else int(o[5]), 0) for o in options]
+    arr = (McrIncomeOption * max(1, len(records)))(*records)
+    counts = torch.empty((len(records), N.MCR_N_COUNTERS), dtype=torch.int64, device=torch.device("cuda", int(device)))
+    if not records:
+        return counts
+    rng = _as_rng(seed)
+    stream = torch.cuda.current_stream(int(device)).cuda_stream
+    rc = N.load_library().mcr_probe_income_rng(
+        C.byref(params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), int(working_months), int(stream_index),
+        arr, len(records), counts.data_ptr(), int(device), C.c_void_p(stream),
+    )
+    N.check(rc, "mcr_probe_income_rng")
     return counts
 
 

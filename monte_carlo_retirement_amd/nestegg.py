@@ -54,9 +54,11 @@ def scenario_records(scenarios: Sequence[dict], defaults: Sequence[float]) -> Li
 
 
 def _search(target: float, start: float, L: int, resolution: float, cap: float,
-            on_level: Optional[Callable[[dict], None]]) -> Generator[List[float], Sequence[float], SearchResult]:
+            on_level: Optional[Callable[[dict], None]], key: str = "initial_balance", event: str = "initial_balance_search_iter",
+            what: str = "required-starting-balance") -> Generator[List[float], Sequence[float], SearchResult]:
     """One search: yields the levels of a call (1 .. L distinct whole-cent values), receives their probabilities, and
-    returns ``(initial_balance, probability, curve)``."""
+    returns ``(level, probability, curve)``.  ``key`` names the level in the curve and the events, ``event`` is the events'
+    type and ``what`` names the search in the cap warning (`income.search_minimum_income_amount` passes its own)."""
     res_c = float(resolution) * 100.0
     cap_c = _cents(cap)
     memo: Dict[int, float] = {}
@@ -74,9 +76,9 @@ def _search(target: float, start: float, L: int, resolution: float, cap: float,
         for c, pr in zip(levels_c, probs):
             pr = float(pr)
             memo[c] = pr
-            curve.append({"initial_balance": c / 100.0, "probability": pr})
+            curve.append({key: c / 100.0, "probability": pr})
             if on_level:
-                on_level({"type": "initial_balance_search_iter", "iteration": state["call"], "initial_balance": c / 100.0,
+                on_level({"type": event, "iteration": state["call"], key: c / 100.0,
                           "probability": round(pr, 2), "target": target,
                           "lo": None if state["lo"] is None else state["lo"] / 100.0,
                           "hi": None if state["hi"] is None else state["hi"] / 100.0})
@@ -105,7 +107,7 @@ def _search(target: float, start: float, L: int, resolution: float, cap: float,
             break
         k = next((i for i, c in enumerate(ladder) if c not in memo), None)
         if k is None:   # every rung up to the cap missed
-            warnings.warn(f"required-starting-balance search reached the cap of {cap:g} without reaching the target",
+            warnings.warn(f"{what} search reached the cap of {cap:g} without reaching the target",
                           RuntimeWarning, stacklevel=3)
             return -1.0, memo[cap_c], curve
         yield from evaluate(ladder[k: k + L])

@@ -1007,6 +1007,100 @@ class RetirementMonteCarloSimulator:
                                 f"({len(curve)} levels evaluated).")
         return results
 
+    # ---- income-stream options and the required-income search ------------------------------------------
+    def success_probability_by_income_options(self, working_months: int, stream, options: Sequence[dict],
+                                              num_simulations: Optional[int] = None) -> np.ndarray:
+        """Success % of each option for ONE income stream at ``working_months``, over the active seed stream's batch of
+        ``num_simulations`` paths (default ``num_simulations_main``), from the income probe (``mcr_probe_income_rng``).
+        ``stream`` is a list index into ``other_income_streams`` or a unique ``name``; an option is a mapping with any subset
+        of the keys ``initial_balance``, ``monthly_contribution``, ``monthly_expenses`` and the stream's
+        ``monthly_amount_today``, ``start_at_age``, ``duration_years``: a missing key takes the config's value, an unknown
+        key or stream raises ``ValueError`` (before any device work).  Aligned with the input; each value equals, bit for
+        bit, ``_success_probability(run_monte_carlo_simulations(working_months, n)[0])`` of a simulator whose config differs
+        in those fields only.  Under a process group the options go through ``distributed.probe_candidates`` (as candidate
+        indices), so every rank returns the same array."""
+        from .income import income_options, stream_index
+
+        p = self.params_model
+        index = stream_index(p, stream)
+        records = income_options(p, index, options)
+        if not records:
+            return np.zeros(0, dtype=np.float64)
+        n = int(p.num_simulations_main if num_simulations is None else num_simulations)
+        wm = int(working_months)
+        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
+
+        def probe(path_begin, count, idx):
+            return E.probe_income(params, rng, self._stream_id, path_begin, count, wm, index, [records[i] for i in idx], device=dev)
+
+        counts = D.probe_candidates(list(range(len(records))), n, self.shard_min_paths, probe)
+        return np.array([self._count_percent(counts[i, N.MCR_CTR_SUCCESS], n) for i in range(len(records))], dtype=np.float64)
+
+    def compare_claiming_options(self, working_months: int, stream, options: Sequence[dict],
+                                 num_simulations: Optional[int] = None) -> dict:
+        """The claim-age table and the annuity comparison: `success_probability_by_income_options` of ``options`` as
+        ``{"stream": list index, "options": [{the six fields, "probability"}, ...], "best": index}``, ``best`` being the
+        option with the highest probability (the first of equals)."""
+        from .income import INCOME_OPTION_FIELDS, income_options, stream_index
+
+        index = stream_index(self.params_model, stream)
+        records = income_options(self.params_model, index, options)
+        probs = self.success_probability_by_income_options(working_months, index, options, num_simulations)
+        rows = [dict(zip(INCOME_OPTION_FIELDS, r), probability=float(pr)) for r, pr in zip(records, probs)]
+        best = max(range(len(rows)), key=lambda i: (rows[i]["probability"], -i)) if rows else None
+        return {"stream": index, "options": rows, "best": best}
+
+    _UNCHANGED = object()   # (find_minimum_income_amount: "the stream's own duration_years", which may itself be None)
+
+    def find_minimum_income_amount(
+        self,
+        working_months: int,
+        stream,
+        start_at_age: Optional[float] = None,
+        duration_years=_UNCHANGED,
+        verbose: bool = True,
+        progress_callback: Optional[Callable[[dict], None]] = None,
+        resolution: float = 1.0,
+    ) -> Tuple[float, float, List[Dict[str, float]]]:
+        """Smallest ``monthly_amount_today`` (whole cents) of income stream ``stream`` that reaches ``target_probability``
+        when retiring after ``working_months``: search stream, ``num_simulations_search`` paths, ``MCR_MAX_EXPENSE_FANOUT``
+        levels per probe (`income.search_minimum_income_amount`, starting at ``max(the stream's amount, 1)``).
+        ``start_at_age`` / ``duration_years`` replace the stream's own for every level (default: unchanged; ``None`` as
+        ``duration_years`` = for life).  Returns ``(amount, probability, curve)``; ``amount == 0.0`` when the plan needs no
+        such income and ``-1.0`` when even the cap misses the target.  Deterministic for a given seed, and the same on every
+        rank."""
+        from .income import INCOME_AMOUNT_CAP, search_minimum_income_amount, stream_index
+
+        self.use_search_seeds()
+        p = self.params_model
+        wm = int(working_months)
+        index = stream_index(p, stream)
+        fixed = {}
+        if start_at_age is not None:
+            fixed["start_at_age"] = float(start_at_age)
+        if duration_years is not self._UNCHANGED:
+            fixed["duration_years"] = duration_years
+        n_sims, target = int(p.num_simulations_search), float(p.target_probability)
+        if verbose:
+            logger.info(f"Searching the minimum monthly amount of income stream {index} at {wm} working months for "
+                        f"'{p.Nickname}' (target {target:.2f}%, {n_sims} sims per level, resolution {resolution}).")
+
+        def probe_levels(levels):
+            return list(self.success_probability_by_income_options(
+                wm, index, [dict(fixed, monthly_amount_today=x) for x in levels], n_sims))
+
+        start = max(float(p.other_income_streams[index].monthly_amount_today), 1.0)
+        amount, prob, curve = search_minimum_income_amount(
+            probe_levels, target, start, levels_per_call=N.MCR_MAX_EXPENSE_FANOUT, resolution=resolution,
+            cap=INCOME_AMOUNT_CAP, on_level=progress_callback)
+        if verbose:
+            if amount < 0:
+                logger.warning(f"Target not met at any amount of income stream {index}: {prob:.2f}% at {wm} months.")
+            else:
+                logger.info(f"  Income search complete: {amount:.2f} per month with prob {prob:.2f}% "
+                            f"({len(curve)} levels evaluated).")
+        return amount, prob, curve
+
     # ---- market-assumption stress and the break-even assumption search ---------------------------------
     def success_probability_by_assumptions(self, working_months: int, scenarios: Sequence[dict],
                                            num_simulations: Optional[int] = None) -> np.ndarray:
