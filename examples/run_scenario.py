@@ -43,7 +43,11 @@ value at which the target is still met (`--window`, `--breakeven-resolution`).  
 `--claim-amounts` prints the claiming-option table of that stream at `--working-months` (default 0): `{stream, options:
 [{the six fields, probability}], best}` over the same random numbers; lists of unequal length are an error.  `--min-income
 STREAM [--claim-age A]` answers "how large does this income have to be": the smallest monthly amount (whole cents) of that
-stream, started at age A (default: its own), that reaches the target, printed like `--min-initial-balance`."""
+stream, started at age A (default: its own), that reaches the target, printed like `--min-initial-balance`.
+`--paired` (with `--income-options` and / or `--stress`) says whether the table's gaps are real: the options run over the same
+paths, so every row also gets the paired difference against the best option (`vs_best`) or the base market (`vs_base`: also
+`hurt` / `helped` path counts) with its standard error and the exact McNemar p-value, and the claiming table gains
+`tied_with_best`, `all_succeed` and `none_succeed`."""
 
 from __future__ import annotations
 
@@ -91,6 +95,9 @@ def main() -> int:
                     help="index or name of an income stream: the table of --claim-ages / --claim-amounts options instead")
     ap.add_argument("--claim-ages", default=None, help="--income-options: comma-separated start_at_age, one per option")
     ap.add_argument("--claim-amounts", default=None, help="--income-options: comma-separated monthly_amount_today, one per option")
+    ap.add_argument("--paired", action="store_true",
+                    help="--income-options / --stress: add the paired comparison over the shared paths (difference, its standard "
+                         "error, the exact McNemar p-value, paths helped and hurt)")
     ap.add_argument("--min-income", default=None, metavar="STREAM",
                     help="index or name of an income stream: search its minimum monthly amount at --working-months (default 0) instead")
     ap.add_argument("--claim-age", type=float, default=None, help="--min-income: the stream's start_at_age (default: its own)")
@@ -110,6 +117,8 @@ def main() -> int:
         ap.error("--income-options / --min-income and the other searches are separate questions")
     if args.income_options is not None and args.min_income is not None:
         ap.error("--income-options and --min-income are separate questions")
+    if args.paired and args.income_options is None and not args.stress:
+        ap.error("--paired goes with --income-options or --stress")
     if (args.claim_ages or args.claim_amounts) and args.income_options is None:
         ap.error("--claim-ages / --claim-amounts go with --income-options")
     if args.claim_age is not None and args.min_income is None:
@@ -249,7 +258,7 @@ def stress(args, config: Config, world: int, rank0: bool) -> int:
                "target_probability": config.target_probability}
         if args.stress:
             sim.use_final_seeds()
-            out["stress"] = sim.stress_test(wm)
+            out["stress"] = sim.stress_test(wm, paired=True) if args.paired else sim.stress_test(wm)
         if args.breakeven:
             out["breakeven"] = []
             for field in [f.strip() for f in args.breakeven.split(",") if f.strip()]:
@@ -354,7 +363,7 @@ def income_table(args, config: Config, world: int, rank0: bool) -> int:
         if amounts:
             o["monthly_amount_today"] = amounts[k]
     sim.use_final_seeds()
-    table = sim.compare_claiming_options(wm, _stream_arg(args.income_options), options)
+    table = sim.compare_claiming_options(wm, _stream_arg(args.income_options), options, **({"paired": True} if args.paired else {}))
     out = {"scenario": config.Nickname, "rng": args.rng, "working_months": wm, "num_simulations": int(config.num_simulations_main),
            "target_probability": config.target_probability, **table, "seconds": round(time.perf_counter() - t0, 3)}
     if rank0:

@@ -29,6 +29,7 @@ extern "C" {
                                    backend/config.py:99) follows through mcr_params.extra_streams */
 #define MCR_MAX_PROBE_CANDIDATES 32 /* candidates of one mcr_probe_months_rng call that can share their accumulation sweep */
 #define MCR_MAX_EXPENSE_FANOUT 15  /* spending levels one expense fan-out workgroup evaluates (mcr_probe_expenses_rng) */
+#define MCR_MAX_JOINT_OPTIONS 32    /* options of one joint probe / mcr_joint_counts call (the co-occurrence matrix is n x n) */
 #define MCR_MAX_HIST_BINS 4096  /* bins of the in-kernel final-balance histogram (mcr_outputs.hist_bins) */
 #define MCR_MAX_YEAR_BINS 512   /* bins per row of the yearly-bins tables (mcr_year_bins); each balance bin costs 28 bytes of a
                                    workgroup's LDS and each withdrawal-rate bin 16: 2.9 KB at 64 + 64 bins, 11.4 KB at 256 + 256,
@@ -433,6 +434,45 @@ int mcr_probe_income_rng(const mcr_params* p, const mcr_rng* rng, uint32_t strea
                          const mcr_income_option* options, int32_t n_options,
                          uint64_t* counts, int device, void* hip_stream);
 int mcr_probe_income_last_fanout_launches(void);
+
+/*
+ * JOINT OUTCOMES: what the scenario, assumption and income probes know beyond their counts.  Every option of such a probe runs
+ * over the SAME paths, so the per-path outcomes of two options are paired: the difference between their success
+ * probabilities is known far better than either probability.  The *_joint_rng calls take the arguments of their plain probe
+ * (same validation, same routes, `counts` bit for bit the plain probe's) plus
+ *   masks:    DEVICE uint64 [n][mcr_joint_mask_words(n_paths)] or NULL.  Row k is option k's success mask: bit b of word w is 1
+ *             iff path path_begin + 64 w + b succeeds under option k; bits of paths at or beyond n_paths are 0.  Every word is
+ *             written.  NULL: the call keeps the masks in stream-ordered scratch of its own, released behind the work.
+ *   joint:    DEVICE uint64 [n][n], required: joint[i][j] = paths on which options i AND j both succeed (symmetric, both
+ *             triangles filled; the diagonal is each option's success count = counts[k][MCR_CTR_SUCCESS]).
+ *   extremes: DEVICE uint64 [2] or NULL: {paths on which EVERY option succeeds, paths on which NONE does}.
+ * n > MCR_MAX_JOINT_OPTIONS or < 0 and a null `joint` are MCR_ERR_INVALID_ARG (the message names the cap), checked first, before
+ * the device is touched; n == 0 does nothing.  All outputs are zeroed or overwritten by the call; asynchronous on hip_stream
+ * like the plain probes.  On the fan-out route (the plain probe's conditions) the fan-out kernel's consumer waves store their
+ * success ballots as the mask words -- no extra launch but the reduction; option lists longer than one launch's share need
+ * nothing special, the matrix is counted from the rows afterwards.  Where the plain probe would run one launch per option
+ * (NumPy stream, more than MCR_INLINE_STREAMS kept streams, the exact month, one option, the MCR_*_FANOUT_MIN_WAVES knobs) each
+ * option's launch also writes its uint8 success column to scratch and a pack kernel turns the column into the mask row.
+ * mcr_probe_*_last_fanout_launches report the route as for the plain probes.
+ * mcr_joint_counts is the reduction alone, for callers that combine mask rows kept from several probes: joint / extremes as
+ * above from n_options rows of mcr_joint_mask_words(n_paths) words.  The kernel clears the bits beyond n_paths of the last
+ * word as it reads, so rows need not be tail-clean.  n_paths == 0: zeroes.
+ */
+uint64_t mcr_joint_mask_words(uint64_t n_paths);   /* (n_paths + 63) / 64 */
+int mcr_probe_scenarios_joint_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                  uint64_t n_paths, int32_t working_months, const mcr_scenario* scenarios,
+                                  int32_t n_scenarios, uint64_t* counts, uint64_t* masks, uint64_t* joint, uint64_t* extremes,
+                                  int device, void* hip_stream);
+int mcr_probe_assumptions_joint_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                    uint64_t n_paths, int32_t working_months, const mcr_assumptions* records,
+                                    int32_t n_records, uint64_t* counts, uint64_t* masks, uint64_t* joint, uint64_t* extremes,
+                                    int device, void* hip_stream);
+int mcr_probe_income_joint_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                               uint64_t n_paths, int32_t working_months, int32_t stream_index,
+                               const mcr_income_option* options, int32_t n_options,
+                               uint64_t* counts, uint64_t* masks, uint64_t* joint, uint64_t* extremes, int device, void* hip_stream);
+int mcr_joint_counts(const uint64_t* masks, int32_t n_options, uint64_t n_paths, uint64_t* joint, uint64_t* extremes,
+                     int device, void* hip_stream);
 
 /*
  * Retirement-month x spending grid: counts[c][k] equals, bit for bit, the counters of a count-only mcr_run_batch_rng call with

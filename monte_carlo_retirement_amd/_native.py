@@ -27,6 +27,7 @@ MCR_DEVICE_ALL = -2
 MCR_MAX_HIST_BINS = 4096
 MCR_MAX_YEAR_BINS = 512  # bins per row of the yearly-bins tables (mcr_year_bins)
 MCR_ERR_INVALID_ARG = -1
+MCR_MAX_JOINT_OPTIONS = 32  # options of one joint probe / mcr_joint_counts call
 MCR_MAX_EXPENSE_FANOUT = 15  # spending levels one expense fan-out workgroup evaluates (mcr_probe_expenses_rng)
 
 MCR_HELPER_WITHDRAW = 0
@@ -303,6 +304,11 @@ ABI_SYMBOLS = (
     "mcr_probe_assumptions_last_fanout_launches",
     "mcr_probe_income_rng",
     "mcr_probe_income_last_fanout_launches",
+    "mcr_joint_mask_words",
+    "mcr_probe_scenarios_joint_rng",
+    "mcr_probe_assumptions_joint_rng",
+    "mcr_probe_income_joint_rng",
+    "mcr_joint_counts",
     "mcr_probe_grid_rng",
     "mcr_run_batch_multi_host_rng",
     "mcr_run_year_bins_rng",
@@ -415,6 +421,19 @@ def _declare(lib: C.CDLL) -> None:
         ]
         lib.mcr_probe_income_last_fanout_launches.restype = C.c_int
         lib.mcr_probe_income_last_fanout_launches.argtypes = []
+    if hasattr(lib, "mcr_joint_counts"):   # (likewise)
+        lib.mcr_joint_mask_words.restype = C.c_uint64
+        lib.mcr_joint_mask_words.argtypes = [C.c_uint64]
+        joint_out = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]   # counts, masks, joint, extremes, device, stream
+        head = [P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32]
+        lib.mcr_probe_scenarios_joint_rng.restype = C.c_int
+        lib.mcr_probe_scenarios_joint_rng.argtypes = head + [P(McrScenario), C.c_int32] + joint_out
+        lib.mcr_probe_assumptions_joint_rng.restype = C.c_int
+        lib.mcr_probe_assumptions_joint_rng.argtypes = head + [P(McrAssumptions), C.c_int32] + joint_out
+        lib.mcr_probe_income_joint_rng.restype = C.c_int
+        lib.mcr_probe_income_joint_rng.argtypes = head + [C.c_int32, P(McrIncomeOption), C.c_int32] + joint_out
+        lib.mcr_joint_counts.restype = C.c_int
+        lib.mcr_joint_counts.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.mcr_probe_grid_rng.restype = C.c_int
     lib.mcr_probe_grid_rng.argtypes = [
         P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, P(C.c_int32), C.c_int32, P(C.c_double), C.c_int32,

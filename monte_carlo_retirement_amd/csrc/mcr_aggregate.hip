@@ -1698,6 +1698,102 @@ static void rq_count_pass(hipStream_t s, const double* rows, int64_t row_stride,
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Joint outcomes: success masks -> option x option co-occurrence counts (mcr_joint_counts, mcr_probe_*_joint_rng)
+// ---------------------------------------------------------------------------------------------
+// One mask row per option, one bit per path (mcr_host.h: joint_mask_words).  A workgroup takes tiles of kJointTile words:
+// it stages the tile's n rows in LDS (32 rows x 128 words x 8 B = 32 KiB, + the 8 KiB matrix: 40 of the 64 KiB a workgroup
+// plans with), with the bits beyond n_paths cleared on the way in, so callers' tail bits never count.  The pairs i <= j
+// are dealt round-robin to the four waves; a wave's lanes run over the tile's words, __popcll(a & b), a shuffle reduction,
+// and lane 0 adds the sum to the pair's LDS cell -- a pair belongs to ONE wave, so the cell needs no atomic.  Threads
+// 0 .. kJointTile - 1 also AND / OR the n rows of their word for `all` / `none`.  At the end the workgroup adds each
+// non-zero cell to both triangles of the global matrix with one 64-bit atomic each.
+constexpr int kJointTile = 128;     // words per tile (8 192 paths)
+constexpr int kJointBlock = 256;
+constexpr int kJointMaxGrid = 2048;
+__global__ __launch_bounds__(kJointBlock) void joint_counts_kernel(const unsigned long long* __restrict__ masks, int n, unsigned long long words,
+                                                                   unsigned long long n_paths, unsigned long long* __restrict__ joint,
+                                                                   unsigned long long* __restrict__ extremes) {
+    __shared__ unsigned long long rows[MCR_MAX_JOINT_OPTIONS * kJointTile];
+    __shared__ unsigned long long cell[MCR_MAX_JOINT_OPTIONS * MCR_MAX_JOINT_OPTIONS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int k = threadIdx.x; k < n * n; k += kJointBlock) cell[k] = 0ull;
+    unsigned int n_all = 0, n_none = 0;
+    const unsigned long long n_tiles = (words + kJointTile - 1) / kJointTile;
+    for (unsigned long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const unsigned long long w0 = tile * kJointTile;
+        __syncthreads();   // (the cells are zeroed; the previous tile's rows are read)
+        for (int k = threadIdx.x; k < n * kJointTile; k += kJointBlock) {
+            const unsigned long long w = w0 + (unsigned)(k % kJointTile);
+            unsigned long long m = 0ull;
+            if (w < words) {
+                m = masks[(size_t)(k / kJointTile) * words + w];
+                if (w == words - 1 && (n_paths & 63ull)) m &= (1ull << (n_paths & 63ull)) - 1ull;
+            }
+            rows[k] = m;
+        }
+        __syncthreads();
+        for (int k = wave; k < n * n; k += kJointBlock / 64) {   // cell k = (i, j) is wave k % 4's; the upper triangle is computed
+            const int i = k / n, j = k % n;
+            if (j < i) continue;
+            unsigned int c = 0;
+            for (int t = lane; t < kJointTile; t += 64) c += (unsigned int)__popcll(rows[i * kJointTile + t] & rows[j * kJointTile + t]);
+            for (int off = 32; off > 0; off >>= 1) c += (unsigned int)__shfl_down((int)c, off, 64);
+            if (lane == 0 && c) cell[k] += c;
+        }
+        if (threadIdx.x < kJointTile) {
+            const unsigned long long w = w0 + threadIdx.x;
+            if (w < words) {
+                unsigned long long a = ~0ull, o = 0ull;
+                for (int i = 0; i < n; ++i) { const unsigned long long m = rows[i * kJointTile + threadIdx.x]; a &= m; o |= m; }
+                const unsigned long long valid = (w == words - 1 && (n_paths & 63ull)) ? (1ull << (n_paths & 63ull)) - 1ull : ~0ull;
+                n_all += (unsigned int)__popcll(a & valid);
+                n_none += (unsigned int)__popcll(~o & valid);
+            }
+        }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < n * n; k += kJointBlock) {
+        const int i = k / n, j = k % n;
+        const unsigned long long c = cell[i <= j ? k : j * n + i];
+        if (c) atomicAdd(&joint[k], c);
+    }
+    if (extremes && threadIdx.x < kJointTile) {   // (two whole waves)
+        for (int off = 32; off > 0; off >>= 1) {
+            n_all += (unsigned int)__shfl_down((int)n_all, off, 64);
+            n_none += (unsigned int)__shfl_down((int)n_none, off, 64);
+        }
+        if (lane == 0 && n_all) atomicAdd(&extremes[0], (unsigned long long)n_all);
+        if (lane == 0 && n_none) atomicAdd(&extremes[1], (unsigned long long)n_none);
+    }
+}
+// A uint8 [n_paths] success column -> its mask row: one thread per path, the wave's ballot, lane 0 stores the word
+__global__ __launch_bounds__(256) void pack_success_kernel(const uint8_t* __restrict__ success, unsigned long long n_paths,
+                                                           unsigned long long* __restrict__ row) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(i < n_paths && success[i] != 0);
+    if ((threadIdx.x & 63) == 0 && (i >> 6) < (n_paths + 63) >> 6) row[i >> 6] = m;   // (i < 2^32 * 256: no overflow)
+}
+int launch_pack_success(const uint8_t* success, uint64_t n_paths, uint64_t* row, hipStream_t stream) {
+    if (n_paths == 0) return MCR_OK;
+    hipLaunchKernelGGL(pack_success_kernel, dim3((unsigned)((n_paths + 255) / 256)), dim3(256), 0, stream, success,
+                       (unsigned long long)n_paths, (unsigned long long*)row);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MCR_OK : hip_fail(e, "pack_success_kernel");
+}
+int launch_joint_counts(const uint64_t* masks, int n, uint64_t n_paths, uint64_t* joint, uint64_t* extremes, hipStream_t stream) {
+    hipError_t e = hipMemsetAsync(joint, 0, sizeof(uint64_t) * (size_t)n * (size_t)n, stream);
+    if (e == hipSuccess && extremes) e = hipMemsetAsync(extremes, 0, sizeof(uint64_t) * 2, stream);
+    if (e != hipSuccess) return hip_fail(e, "joint counts memset");
+    if (n_paths == 0) return MCR_OK;
+    const uint64_t words = joint_mask_words(n_paths), n_tiles = (words + kJointTile - 1) / kJointTile;
+    hipLaunchKernelGGL(joint_counts_kernel, dim3((unsigned)(n_tiles < (uint64_t)kJointMaxGrid ? n_tiles : (uint64_t)kJointMaxGrid)), dim3(kJointBlock), 0, stream,
+                       (const unsigned long long*)masks, n, (unsigned long long)words, (unsigned long long)n_paths,
+                       (unsigned long long*)joint, (unsigned long long*)extremes);
+    e = hipGetLastError();
+    return e == hipSuccess ? MCR_OK : hip_fail(e, "joint_counts_kernel");
+}
+
 }  // namespace mcr
 using namespace mcr;
 extern "C" {
@@ -2080,6 +2176,19 @@ int mcr_summary_stat_rows(const double* start_balance, const double* final_balan
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "stat_rows_kernel");
     return MCR_OK;
+}
+
+uint64_t mcr_joint_mask_words(uint64_t n_paths) { return joint_mask_words(n_paths); }
+
+int mcr_joint_counts(const uint64_t* masks, int32_t n_options, uint64_t n_paths, uint64_t* joint, uint64_t* extremes, int device, void* hip_stream) {
+    if (n_options < 0 || n_options > MCR_MAX_JOINT_OPTIONS) {
+        set_error("n_options %d: joint counts take 0 .. MCR_MAX_JOINT_OPTIONS = %d options", n_options, MCR_MAX_JOINT_OPTIONS);
+        return MCR_ERR_INVALID_ARG;
+    }
+    if (n_options == 0) return MCR_OK;
+    if (!joint || (!masks && n_paths > 0)) { set_error("null joint / masks"); return MCR_ERR_INVALID_ARG; }
+    MCR_ENTER_DEVICE(device);
+    return launch_joint_counts(masks, n_options, n_paths, joint, extremes, (hipStream_t)hip_stream);
 }
 
 }  // extern "C"

@@ -89,8 +89,18 @@ struct KernelIO {
         YearBins yb;
         int32_t fan_stream;                            // PHASE 10: which of the kept records (DevParams::streams) the consumer waves replace
     };
+    // PHASE 8 / 9 / 10, joint probes (mcr_probe_*_joint_rng): [fan_n][(n_paths + 63) / 64] success masks or nullptr; consumer wave j
+    // stores its 64 paths' ballot to word blockIdx.x of row j.  Last, so every other field keeps its place in the kernel arguments
+    uint64_t* fan_masks;
 };
 static_assert(sizeof(KernelIO::YearBins) <= sizeof(double) * MCR_MAX_EXPENSE_FANOUT, "the yearly-bins block must fit the bytes it overlays");
+// path_kernel(DevParams, KernelIO, const DevParams*): a field of the second argument read from the kernel-argument segment at
+// the point of use (the arguments lie there in order, each at its natural alignment).  Wave-uniform: a scalar load.
+constexpr size_t kKernelIOArgOffset = (sizeof(DevParams) + alignof(KernelIO) - 1) / alignof(KernelIO) * alignof(KernelIO);
+template <typename T> __device__ __forceinline__ T late_arg(size_t offset_in_io) {
+    typedef const char __attribute__((address_space(4)))* KernArg;
+    return *(const T __attribute__((address_space(4)))*)((KernArg)__builtin_amdgcn_kernarg_segment_ptr() + kKernelIOArgOffset + offset_in_io);
+}
 // PHASE 6 (grid probe, mcr_probe_grid_rng): one record per grid row (blockIdx.y) of a launch, in device memory; path_kernel's
 // `cand_params` points at the launch's records.  Everything a row needs is wave-uniform there: scalar loads.
 struct GridCell {
@@ -1088,6 +1098,26 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     const unsigned long long ok = __builtin_amdgcn_ballot_w64(valid && succeeded);
     if (kFan) {   // one count per level: consumer wave j -> blk[j] -> counters of level j (the producer has returned)
         if ((threadIdx.x & 63) == 0) blk[fan_j] = (unsigned int)__popcll(ok);
+        if constexpr (kScnFan) {
+            // PHASE 8 / 9 / 10 read the launch constants of this epilogue from the kernel-argument segment HERE (late_arg) instead
+            // of through `io`, whose fields are loaded at kernel entry and held in SGPRs through the month loop: the mask pointer
+            // of the joint probes then costs no register there, and the three other values stop costing theirs
+            const int fan_n = late_arg<int32_t>(offsetof(KernelIO, fan_n));
+            const uint64_t n_paths = late_arg<uint64_t>(offsetof(KernelIO, n_paths));
+            uint64_t* const fan_ctr = late_arg<uint64_t*>(offsetof(KernelIO, out) + offsetof(mcr_outputs, counters));
+            // joint probes keep the ballot: bit b of word path_block of row j = path 64 path_block + b under option j
+            uint64_t* const fan_masks = late_arg<uint64_t*>(offsetof(KernelIO, fan_masks));
+            if (fan_masks && (threadIdx.x & 63) == 0) fan_masks[(size_t)fan_j * ((n_paths + 63) >> 6) + path_block] = ok;
+            __syncthreads();
+            if (threadIdx.x < (unsigned)fan_n && fan_ctr) {
+                uint64_t* c = fan_ctr + (size_t)threadIdx.x * MCR_N_COUNTERS;
+                const uint64_t first = (uint64_t)path_block * kPaths;
+                const uint64_t cnt = n_paths - first < (uint64_t)kPaths ? n_paths - first : (uint64_t)kPaths;
+                atomicAdd((unsigned long long*)&c[MCR_CTR_SUCCESS], (unsigned long long)blk[threadIdx.x]);
+                atomicAdd((unsigned long long*)&c[MCR_CTR_PATHS], (unsigned long long)cnt);
+            }
+            return;
+        }
         __syncthreads();
         uint64_t* const fan_ctr = kGrid ? cell->counters : io.out.counters;
         if (threadIdx.x < (unsigned)io.fan_n && fan_ctr) {
@@ -2623,7 +2653,8 @@ static int probe_contributions_fanout(const mcr_params* p, const mcr_rng* rng, u
 // so one parameter block serves every record.  Returns MCR_ERR_UNSUPPORTED, having enqueued nothing, for shapes this form
 // does not cover and when the table's allocation is refused.
 static int probe_scenarios_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
-                                  int32_t wm, const mcr_scenario* scenarios, int32_t n_scenarios, uint64_t* counts, hipStream_t stream) {
+                                  int32_t wm, const mcr_scenario* scenarios, int32_t n_scenarios, uint64_t* counts, hipStream_t stream,
+                                  uint64_t* masks = nullptr /* joint probes: KernelIO::fan_masks of the whole option list */) {
     DevParams d;
     int lmax = 0;
     if (int rc = plan_level_fanout(p, rng, n_paths, wm, n_scenarios, fanout_min_waves("MCR_SCENARIO_FANOUT_MIN_WAVES"), &d, &lmax)) return rc;
@@ -2641,6 +2672,7 @@ static int probe_scenarios_fanout(const mcr_params* p, const mcr_rng* rng, uint3
                 KernelIO fio = io;
                 fio.out.counters = counts + (size_t)first * MCR_N_COUNTERS;
                 fio.fan_n = lg;
+                fio.fan_masks = masks ? masks + (size_t)first * ((n_paths + 63) / 64) : nullptr;
                 hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 8, true>), grid, dim3(64 * (lg + 1)),
                                    fanout_dynamic_lds(d, lg), stream, d, fio, (const DevParams*)(d_table + first));
             });
@@ -2663,7 +2695,8 @@ static int probe_scenarios_fanout(const mcr_params* p, const mcr_rng* rng, uint3
 // MCR_ERR_UNSUPPORTED, having enqueued nothing, for shapes this form does not cover and when the table's allocation is refused.
 static thread_local int g_last_assumption_fanout_launches = 0;   // (mcr_probe_assumptions_last_fanout_launches)
 static int probe_assumptions_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
-                                    int32_t wm, const mcr_assumptions* records, int32_t n_records, uint64_t* counts, hipStream_t stream) {
+                                    int32_t wm, const mcr_assumptions* records, int32_t n_records, uint64_t* counts, hipStream_t stream,
+                                  uint64_t* masks = nullptr /* joint probes: KernelIO::fan_masks of the whole option list */) {
     DevParams d;
     int lmax = 0;
     if (int rc = plan_level_fanout(p, rng, n_paths, wm, n_records, fanout_min_waves("MCR_ASSUMPTION_FANOUT_MIN_WAVES"), &d, &lmax, true)) return rc;
@@ -2689,6 +2722,7 @@ static int probe_assumptions_fanout(const mcr_params* p, const mcr_rng* rng, uin
                 KernelIO fio = io;
                 fio.out.counters = counts + (size_t)first * MCR_N_COUNTERS;
                 fio.fan_n = lg;
+                fio.fan_masks = masks ? masks + (size_t)first * ((n_paths + 63) / 64) : nullptr;
                 hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 9, true>), grid, dim3(64 * (lg + 1)),
                                    fanout_dynamic_lds(d, lg), stream, d, fio, (const DevParams*)(d_table + first));
                 ++g_last_assumption_fanout_launches;
@@ -2715,7 +2749,7 @@ static int probe_assumptions_fanout(const mcr_params* p, const mcr_rng* rng, uin
 static thread_local int g_last_income_fanout_launches = 0;   // (mcr_probe_income_last_fanout_launches)
 static int probe_income_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
                                int32_t wm, int32_t stream_index, const mcr_income_option* options, int32_t n_options, uint64_t* counts,
-                               hipStream_t stream) {
+                               hipStream_t stream, uint64_t* masks = nullptr /* joint probes: KernelIO::fan_masks of the whole option list */) {
     DevParams d;
     int lmax = 0;
     std::vector<std::pair<int, int>> kept;
@@ -2745,6 +2779,7 @@ static int probe_income_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t
                 KernelIO fio = io;
                 fio.out.counters = counts + (size_t)first * MCR_N_COUNTERS;
                 fio.fan_n = lg;
+                fio.fan_masks = masks ? masks + (size_t)first * ((n_paths + 63) / 64) : nullptr;
                 fio.fan_stream = kept_k;
                 hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 10, true>), grid, dim3(64 * (lg + 1)),
                                    fanout_dynamic_lds(d, lg), stream, d, fio, (const DevParams*)(d_table + first));
@@ -2865,6 +2900,68 @@ static int probe_grid_shared(const mcr_params* p, const mcr_rng* rng, uint32_t s
     if (e != hipSuccess) return hip_fail(e, "grid probe");
     if (ef != hipSuccess) return hip_fail(ef, "grid probe (free)");
     return MCR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Joint probes (mcr_probe_*_joint_rng): the per-path success bits of every option and their co-occurrence matrix
+// ---------------------------------------------------------------------------------------------
+struct JointOut { uint64_t* masks; uint64_t* joint; uint64_t* extremes; };   // (the *_joint_rng arguments; null = a plain probe)
+// What a joint entry point checks before it touches the device or its outputs
+static int check_joint_args(int32_t n_options, const uint64_t* joint) {
+    if (n_options < 0 || n_options > MCR_MAX_JOINT_OPTIONS) {
+        set_error("n_options %d: a joint probe takes 0 .. MCR_MAX_JOINT_OPTIONS = %d options", n_options, MCR_MAX_JOINT_OPTIONS);
+        return MCR_ERR_INVALID_ARG;
+    }
+    if (n_options > 0 && !joint) { set_error("null joint"); return MCR_ERR_INVALID_ARG; }
+    return MCR_OK;
+}
+// The routes of a scenario / assumption / income probe once its arguments are validated and `counts` zeroed.
+//   fanout(masks): the probe's probe_*_fanout (MCR_ERR_UNSUPPORTED, nothing enqueued, for shapes it does not cover);
+//   launch(k, stream, success): option k's whole-path launch into its counter block and, if non-null, a uint8 [n_paths] column.
+// Plain (jo == nullptr): one option -> its launch; else the fan-out; else one count-only launch per option (fork_join).
+// Joint: the fan-out stores its ballots to the mask rows; where it does not run, one launch per option with `success` and
+// `counters` set fills a scratch uint8 [n][n_paths] and pack_success_kernel turns each column into its row on the option's side
+// stream.  Either way joint_counts_kernel then reduces the rows.  Masks the caller does not keep and the flag columns are
+// stream-ordered scratch, released behind the work.
+template <typename Fanout, typename Launch>
+static int run_probe_routes(int device, hipStream_t main, int n, uint64_t n_paths, const JointOut* jo, Fanout&& fanout, Launch&& launch) {
+    auto per_option = [&](uint8_t* flags, uint64_t* masks) {
+        return fork_join(device, main, n, [&](int k, hipStream_t s) {
+            uint8_t* const col = flags ? flags + (size_t)k * n_paths : nullptr;
+            const int rc = launch(k, s, col);
+            return rc == MCR_OK && col ? launch_pack_success(col, n_paths, masks + (size_t)k * joint_mask_words(n_paths), s) : rc;
+        });
+    };
+    if (!jo || n_paths == 0) {
+        int rc = MCR_OK;
+        if (n == 1) rc = launch(0, main, nullptr);
+        else if ((rc = fanout(nullptr)) == MCR_ERR_UNSUPPORTED) rc = per_option(nullptr, nullptr);   // (unsupported shape / allocation refused)
+        return rc == MCR_OK && jo ? launch_joint_counts(nullptr, n, 0, jo->joint, jo->extremes, main) : rc;
+    }
+    const size_t words = (size_t)joint_mask_words(n_paths);
+    StreamAlloc own_masks(main), flags(main);
+    uint64_t* masks = jo->masks;
+    if (!masks) {
+        if (!own_masks.alloc((size_t)n * words * sizeof(uint64_t))) { set_error("joint probe: could not allocate %d mask rows", n); return MCR_ERR_HIP; }
+        masks = (uint64_t*)own_masks.p;
+    }
+    int rc = n == 1 ? MCR_ERR_UNSUPPORTED : fanout(masks);
+    if (rc == MCR_ERR_UNSUPPORTED) {
+        if (!flags.alloc((size_t)n * n_paths)) { set_error("joint probe: could not allocate %d success columns", n); return MCR_ERR_HIP; }
+        rc = per_option((uint8_t*)flags.p, masks);
+        const hipError_t ef = flags.release();
+        if (rc == MCR_OK && ef != hipSuccess) rc = hip_fail(ef, "joint probe (free)");
+    }
+    if (rc == MCR_OK) rc = launch_joint_counts(masks, n, n_paths, jo->joint, jo->extremes, main);
+    const hipError_t ef = own_masks.release();
+    if (rc == MCR_OK && ef != hipSuccess) rc = hip_fail(ef, "joint probe (free)");
+    return rc;
+}
+// counters_only plus the per-path success column of the joint probes' per-option route (null: counters alone)
+static mcr_outputs counters_and_success(uint64_t* counters, uint8_t* success) {
+    mcr_outputs o = counters_only(counters);
+    o.success = success;
+    return o;
 }
 
 }  // namespace mcr
@@ -3000,10 +3097,10 @@ int mcr_probe_contributions_rng(const mcr_params* p, const mcr_rng* rng, uint32_
                                                     "monthly_contribution", 57, monthly_contributions, n_levels, counts, device, (hipStream_t)hip_stream);
 }
 
-int mcr_probe_scenarios_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
-                            uint64_t n_paths, int32_t working_months, const mcr_scenario* scenarios,
-                            int32_t n_scenarios, uint64_t* counts, int device, void* hip_stream) {
-    MCR_ENTER_DEVICE(device);
+// mcr_probe_scenarios_rng (jo == nullptr) and mcr_probe_scenarios_joint_rng, on the entered device
+static int probe_scenarios(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                           int32_t working_months, const mcr_scenario* scenarios, int32_t n_scenarios, uint64_t* counts,
+                           const JointOut* jo, int device, hipStream_t main) {
     if (n_scenarios < 0) { set_error("n_scenarios %d must be >= 0", n_scenarios); return MCR_ERR_INVALID_ARG; }
     if (n_scenarios == 0) return MCR_OK;
     if (!scenarios || !counts) { set_error("null scenarios / counts"); return MCR_ERR_INVALID_ARG; }
@@ -3024,27 +3121,45 @@ int mcr_probe_scenarios_rng(const mcr_params* p, const mcr_rng* rng, uint32_t st
                 return MCR_ERR_INVALID_ARG;
             }
         }
-    hipStream_t main = (hipStream_t)hip_stream;
     rc = zero_counters(counts, (size_t)n_scenarios, main);
     if (rc != MCR_OK) return rc;
     mcr_params q = *p;
-    auto launch_scenario = [&](int k, hipStream_t s) {
+    auto launch_scenario = [&](int k, hipStream_t s, uint8_t* success) {
         q.initial_balance = scenarios[k].initial_balance;
         q.monthly_contribution = scenarios[k].monthly_contribution;
         q.monthly_expenses = scenarios[k].monthly_expenses;
-        const mcr_outputs o = counters_only(counts + (size_t)k * MCR_N_COUNTERS);
+        const mcr_outputs o = counters_and_success(counts + (size_t)k * MCR_N_COUNTERS, success);
         return launch_paths(&q, rng, stream_id, path_begin, n_paths, working_months, nullptr, &o, s);
     };
-    if (n_scenarios == 1) return launch_scenario(0, main);
-    rc = probe_scenarios_fanout(p, rng, stream_id, path_begin, n_paths, working_months, scenarios, n_scenarios, counts, main);
-    if (rc != MCR_ERR_UNSUPPORTED) return rc;     // (unsupported shape / allocation refused: one launch per scenario below)
-    return fork_join(device, main, n_scenarios, launch_scenario);
+    auto fanout = [&](uint64_t* masks) {
+        return probe_scenarios_fanout(p, rng, stream_id, path_begin, n_paths, working_months, scenarios, n_scenarios, counts, main, masks);
+    };
+    return run_probe_routes(device, main, n_scenarios, n_paths, jo, fanout, launch_scenario);
 }
 
-int mcr_probe_assumptions_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
-                              uint64_t n_paths, int32_t working_months, const mcr_assumptions* records,
-                              int32_t n_records, uint64_t* counts, int device, void* hip_stream) {
+int mcr_probe_scenarios_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                            uint64_t n_paths, int32_t working_months, const mcr_scenario* scenarios,
+                            int32_t n_scenarios, uint64_t* counts, int device, void* hip_stream) {
     MCR_ENTER_DEVICE(device);
+    return probe_scenarios(p, rng, stream_id, path_begin, n_paths, working_months, scenarios, n_scenarios, counts, nullptr, device,
+                           (hipStream_t)hip_stream);
+}
+
+int mcr_probe_scenarios_joint_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                  uint64_t n_paths, int32_t working_months, const mcr_scenario* scenarios,
+                                  int32_t n_scenarios, uint64_t* counts, uint64_t* masks, uint64_t* joint, uint64_t* extremes,
+                                  int device, void* hip_stream) {
+    if (int rc = check_joint_args(n_scenarios, joint)) return rc;
+    MCR_ENTER_DEVICE(device);
+    const JointOut jo{masks, joint, extremes};
+    return probe_scenarios(p, rng, stream_id, path_begin, n_paths, working_months, scenarios, n_scenarios, counts, &jo, device,
+                           (hipStream_t)hip_stream);
+}
+
+// mcr_probe_assumptions_rng (jo == nullptr) and mcr_probe_assumptions_joint_rng, on the entered device
+static int probe_assumptions(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                             int32_t working_months, const mcr_assumptions* records, int32_t n_records, uint64_t* counts,
+                             const JointOut* jo, int device, hipStream_t main) {
     g_last_assumption_fanout_launches = 0;
     if (n_records < 0) { set_error("n_records %d must be >= 0", n_records); return MCR_ERR_INVALID_ARG; }
     if (n_records == 0) return MCR_OK;
@@ -3086,33 +3201,50 @@ int mcr_probe_assumptions_rng(const mcr_params* p, const mcr_rng* rng, uint32_t 
             return MCR_ERR_INVALID_ARG;
         }
     }
-    hipStream_t main = (hipStream_t)hip_stream;
     rc = zero_counters(counts, (size_t)n_records, main);
     if (rc != MCR_OK) return rc;
     mcr_params q = *p;
-    auto launch_record = [&](int k, hipStream_t s) {
+    auto launch_record = [&](int k, hipStream_t s, uint8_t* success) {
         const mcr_assumptions& r = records[k];
         q.initial_balance = r.initial_balance; q.monthly_contribution = r.monthly_contribution; q.monthly_expenses = r.monthly_expenses;
         q.inv1_mu_log = r.inv1_mu_log; q.inv1_sigma_log = r.inv1_sigma_log;
         q.inf_mu_log = r.inf_mu_log; q.inf_sigma_log = r.inf_sigma_log;
         q.prem_mu_log = r.prem_mu_log; q.prem_sigma_log = r.prem_sigma_log;
         q.equity_inflation_rho = r.equity_inflation_rho;
-        const mcr_outputs o = counters_only(counts + (size_t)k * MCR_N_COUNTERS);
+        const mcr_outputs o = counters_and_success(counts + (size_t)k * MCR_N_COUNTERS, success);
         return launch_paths(&q, rng, stream_id, path_begin, n_paths, working_months, nullptr, &o, s);
     };
-    if (n_records == 1) return launch_record(0, main);
-    rc = probe_assumptions_fanout(p, rng, stream_id, path_begin, n_paths, working_months, records, n_records, counts, main);
-    if (rc != MCR_ERR_UNSUPPORTED) return rc;     // (unsupported shape / allocation refused: one launch per record below)
-    return fork_join(device, main, n_records, launch_record);
+    auto fanout = [&](uint64_t* masks) {
+        return probe_assumptions_fanout(p, rng, stream_id, path_begin, n_paths, working_months, records, n_records, counts, main, masks);
+    };
+    return run_probe_routes(device, main, n_records, n_paths, jo, fanout, launch_record);
+}
+
+int mcr_probe_assumptions_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                              uint64_t n_paths, int32_t working_months, const mcr_assumptions* records,
+                              int32_t n_records, uint64_t* counts, int device, void* hip_stream) {
+    MCR_ENTER_DEVICE(device);
+    return probe_assumptions(p, rng, stream_id, path_begin, n_paths, working_months, records, n_records, counts, nullptr, device,
+                             (hipStream_t)hip_stream);
+}
+
+int mcr_probe_assumptions_joint_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                    uint64_t n_paths, int32_t working_months, const mcr_assumptions* records,
+                                    int32_t n_records, uint64_t* counts, uint64_t* masks, uint64_t* joint, uint64_t* extremes,
+                                    int device, void* hip_stream) {
+    if (int rc = check_joint_args(n_records, joint)) return rc;
+    MCR_ENTER_DEVICE(device);
+    const JointOut jo{masks, joint, extremes};
+    return probe_assumptions(p, rng, stream_id, path_begin, n_paths, working_months, records, n_records, counts, &jo, device,
+                             (hipStream_t)hip_stream);
 }
 
 int mcr_probe_assumptions_last_fanout_launches(void) { return g_last_assumption_fanout_launches; }
 
-int mcr_probe_income_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
-                         uint64_t n_paths, int32_t working_months, int32_t stream_index,
-                         const mcr_income_option* options, int32_t n_options,
-                         uint64_t* counts, int device, void* hip_stream) {
-    MCR_ENTER_DEVICE(device);
+// mcr_probe_income_rng (jo == nullptr) and mcr_probe_income_joint_rng, on the entered device
+static int probe_income(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                        int32_t working_months, int32_t stream_index, const mcr_income_option* options, int32_t n_options,
+                        uint64_t* counts, const JointOut* jo, int device, hipStream_t main) {
     g_last_income_fanout_launches = 0;
     if (n_options < 0) { set_error("n_options %d must be >= 0", n_options); return MCR_ERR_INVALID_ARG; }
     if (n_options == 0) return MCR_OK;
@@ -3153,7 +3285,6 @@ int mcr_probe_income_rng(const mcr_params* p, const mcr_rng* rng, uint32_t strea
             return MCR_ERR_INVALID_ARG;
         }
     }
-    hipStream_t main = (hipStream_t)hip_stream;
     rc = zero_counters(counts, (size_t)n_options, main);
     if (rc != MCR_OK) return rc;
     // the per-option route's parameter block: a copy whose stream `stream_index` is rewritten per launch (launch_paths derives
@@ -3165,17 +3296,37 @@ int mcr_probe_income_rng(const mcr_params* p, const mcr_rng* rng, uint32_t strea
         q.extra_streams = q_extra.data();
     }
     mcr_stream& qs = stream_index < MCR_INLINE_STREAMS ? q.streams[stream_index] : q_extra[(size_t)(stream_index - MCR_INLINE_STREAMS)];
-    auto launch_option = [&](int k, hipStream_t s) {
+    auto launch_option = [&](int k, hipStream_t s, uint8_t* success) {
         const mcr_income_option& r = options[k];
         q.initial_balance = r.initial_balance; q.monthly_contribution = r.monthly_contribution; q.monthly_expenses = r.monthly_expenses;
         qs.monthly_amount_today = r.monthly_amount_today; qs.start_at_age = r.start_at_age; qs.duration_years = r.duration_years;
-        const mcr_outputs o = counters_only(counts + (size_t)k * MCR_N_COUNTERS);
+        const mcr_outputs o = counters_and_success(counts + (size_t)k * MCR_N_COUNTERS, success);
         return launch_paths(&q, rng, stream_id, path_begin, n_paths, working_months, nullptr, &o, s);
     };
-    if (n_options == 1) return launch_option(0, main);
-    rc = probe_income_fanout(p, rng, stream_id, path_begin, n_paths, working_months, stream_index, options, n_options, counts, main);
-    if (rc != MCR_ERR_UNSUPPORTED) return rc;     // (unsupported shape / allocation refused: one launch per option below)
-    return fork_join(device, main, n_options, launch_option);
+    auto fanout = [&](uint64_t* masks) {
+        return probe_income_fanout(p, rng, stream_id, path_begin, n_paths, working_months, stream_index, options, n_options, counts, main, masks);
+    };
+    return run_probe_routes(device, main, n_options, n_paths, jo, fanout, launch_option);
+}
+
+int mcr_probe_income_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                         uint64_t n_paths, int32_t working_months, int32_t stream_index,
+                         const mcr_income_option* options, int32_t n_options,
+                         uint64_t* counts, int device, void* hip_stream) {
+    MCR_ENTER_DEVICE(device);
+    return probe_income(p, rng, stream_id, path_begin, n_paths, working_months, stream_index, options, n_options, counts, nullptr, device,
+                        (hipStream_t)hip_stream);
+}
+
+int mcr_probe_income_joint_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                               uint64_t n_paths, int32_t working_months, int32_t stream_index,
+                               const mcr_income_option* options, int32_t n_options,
+                               uint64_t* counts, uint64_t* masks, uint64_t* joint, uint64_t* extremes, int device, void* hip_stream) {
+    if (int rc = check_joint_args(n_options, joint)) return rc;
+    MCR_ENTER_DEVICE(device);
+    const JointOut jo{masks, joint, extremes};
+    return probe_income(p, rng, stream_id, path_begin, n_paths, working_months, stream_index, options, n_options, counts, &jo, device,
+                        (hipStream_t)hip_stream);
 }
 
 int mcr_probe_income_last_fanout_launches(void) { return g_last_income_fanout_launches; }

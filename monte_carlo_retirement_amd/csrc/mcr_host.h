@@ -109,4 +109,12 @@ public:
     StreamFork* f;
 };
 
+// Joint outcomes (mcr_aggregate.hip): option k's success mask is a row of joint_mask_words(n_paths) 64-bit words, bit b of
+// word w = path 64 w + b of the range.
+inline uint64_t joint_mask_words(uint64_t n_paths) { return n_paths / 64 + (n_paths % 64 ? 1 : 0); }
+// pack_success_kernel: a uint8 [n_paths] success column -> its mask row (every word written, tail bits 0)
+int launch_pack_success(const uint8_t* success, uint64_t n_paths, uint64_t* row, hipStream_t stream);
+// joint_counts_kernel: zeroes joint [n][n] and extremes [2] (may be null), then counts the rows (n_paths == 0: zeroes alone)
+int launch_joint_counts(const uint64_t* masks, int n, uint64_t n_paths, uint64_t* joint, uint64_t* extremes, hipStream_t stream);
+
 }  // namespace mcr

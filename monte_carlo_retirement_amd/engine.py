@@ -586,6 +586,64 @@ def probe_contributions(params: McrParams, seed, stream_id: int, path_begin: int
                          monthly_contributions, device)
 
 
+def _scenario_records(scenarios):
+    records = [tuple(float(x) for x in s) for s in scenarios]
+    if any(len(r) != 3 for r in records):
+        raise ValueError("every scenario is (initial_balance, monthly_contribution, monthly_expenses)")
+    return (McrScenario * max(1, len(records)))(*[McrScenario(*r) for r in records]), len(records)
+
+
+def _income_records(options):
+    options = [tuple(o) for o in options]
+    if any(len(o) != 6 for o in options):
+        raise ValueError("every option is (initial_balance, monthly_contribution, monthly_expenses, monthly_amount_today, "
+                         "start_at_age, duration_years)")
+    records = [McrIncomeOption(*(float(x) for x in o[:5]), -1 if o[5] is None else int(o[5]), 0) for o in options]
+    return (McrIncomeOption * max(1, len(records)))(*records), len(records)
+
+
+def _assumption_records(records):
+    records = [tuple(float(x) for x in r) for r in records]
+    if any(len(r) != 10 for r in records):
+        raise ValueError("every record holds the ten fields of mcr_assumptions")
+    return (McrAssumptions * max(1, len(records)))(*[McrAssumptions(*r) for r in records]), len(records)
+
+
+def _probe_records(symbol: str, params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
+                   record_args, n: int, device: int, joint: bool = False, masks=True):
+    """The body of the record probes: `symbol` is the library entry, `record_args` what it takes between `working_months` and
+    the record count.  Plain: returns `counts`.  `joint`: the ``*_joint_rng`` entry; returns ``(counts, joint, extremes,
+    masks)`` (`masks` falsy: the library keeps them in scratch of its own and None is returned in their place)."""
+    import torch
+
+    N.require_device()
+    dev = torch.device("cuda", int(device))
+    counts = torch.empty((n, N.MCR_N_COUNTERS), dtype=torch.int64, device=dev)
+    outs = []
+    if joint:
+        if n > N.MCR_MAX_JOINT_OPTIONS:
+            raise ValueError(f"a joint probe takes at most MCR_MAX_JOINT_OPTIONS = {N.MCR_MAX_JOINT_OPTIONS} options, got {n}")
+        alloc = torch.empty if n else torch.zeros       # (the call zeroes or overwrites all three; no options: no call)
+        jm = alloc((n, n), dtype=torch.int64, device=dev)
+        ex = alloc((2,), dtype=torch.int64, device=dev)
+        mk = alloc((n, joint_mask_words(n_paths)), dtype=torch.int64, device=dev) if masks else None
+        outs = [mk.data_ptr() if mk is not None and mk.numel() else None, jm.data_ptr() if n else None, ex.data_ptr()]
+    if n:
+        rng = _as_rng(seed)
+        stream = torch.cuda.current_stream(int(device)).cuda_stream
+        rc = getattr(N.load_library(), symbol)(
+            C.byref(params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), int(working_months), *record_args,
+            n, counts.data_ptr(), *outs, int(device), C.c_void_p(stream),
+        )
+        N.check(rc, symbol)
+    return (counts, jm, ex, mk) if joint else counts
+
+
+def joint_mask_words(n_paths: int) -> int:
+    """Words of one option's success mask over `n_paths` paths (``mcr_joint_mask_words``)."""
+    return (int(n_paths) + 63) // 64
+
+
 def probe_scenarios(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
                     scenarios, device: int = 0):
     """Success counters of several what-if scenarios at one working-month count over the same path range
@@ -593,24 +651,8 @@ def probe_scenarios(params: McrParams, seed, stream_id: int, path_begin: int, n_
     monthly_expenses)`` 3-tuples; scenario k counts exactly what a count-only launch with those three fields of `params`
     replaced counts.  Up to ``MCR_MAX_EXPENSE_FANOUT`` scenarios share each path's random numbers.  Returns a device int64
     tensor ``[len(scenarios), 2]`` = ``{successes, paths}``; asynchronous (reading it synchronises)."""
-    import torch
-
-    N.require_device()
-    records = [tuple(float(x) for x in s) for s in scenarios]
-    if any(len(r) != 3 for r in records):
-        raise ValueError("every scenario is (initial_balance, monthly_contribution, monthly_expenses)")
-    arr = (McrScenario * max(1, len(records)))(*[McrScenario(*r) for r in records])
-    counts = torch.empty((len(records), N.MCR_N_COUNTERS), dtype=torch.int64, device=torch.device("cuda", int(device)))
-    if not records:
-        return counts
-    rng = _as_rng(seed)
-    stream = torch.cuda.current_stream(int(device)).cuda_stream
-    rc = N.load_library().mcr_probe_scenarios_rng(
-        C.byref(params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), int(working_months), arr,
-        len(records), counts.data_ptr(), int(device), C.c_void_p(stream),
-    )
-    N.check(rc, "mcr_probe_scenarios_rng")
-    return counts
+    arr, n = _scenario_records(scenarios)
+    return _probe_records("mcr_probe_scenarios_rng", params, seed, stream_id, path_begin, n_paths, working_months, (arr,), n, device)
 
 
 def probe_income(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
@@ -622,26 +664,9 @@ def probe_income(params: McrParams, seed, stream_id: int, path_begin: int, n_pat
     three money fields of `params` and those three fields of entry ``stream_index`` of its stream list replaced.  Up to
     ``MCR_MAX_EXPENSE_FANOUT`` options share each path's random numbers.  Returns a device int64 tensor ``[len(options), 2]``
     = ``{successes, paths}``; asynchronous (reading it synchronises)."""
-    import torch
-
-    N.require_device()
-    options = [tuple(o) for o in options]
-    if any(len(o) != 6 for o in options):
-        raise ValueError("every option is (initial_balance, monthly_contribution, monthly_expenses, monthly_amount_today, "
-                         "start_at_age, duration_years)")
-    records = [McrIncomeOption(*(float(x) for x in o[:5]), -1 if o[5] is None else int(o[5]), 0) for o in options]
-    arr = (McrIncomeOption * max(1, len(records)))(*records)
-    counts = torch.empty((len(records), N.MCR_N_COUNTERS), dtype=torch.int64, device=torch.device("cuda", int(device)))
-    if not records:
-        return counts
-    rng = _as_rng(seed)
-    stream = torch.cuda.current_stream(int(device)).cuda_stream
-    rc = N.load_library().mcr_probe_income_rng(
-        C.byref(params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), int(working_months), int(stream_index),
-        arr, len(records), counts.data_ptr(), int(device), C.c_void_p(stream),
-    )
-    N.check(rc, "mcr_probe_income_rng")
-    return counts
+    arr, n = _income_records(options)
+    return _probe_records("mcr_probe_income_rng", params, seed, stream_id, path_begin, n_paths, working_months,
+                          (int(stream_index), arr), n, device)
 
 
 def probe_assumptions(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
@@ -652,24 +677,66 @@ def probe_assumptions(params: McrParams, seed, stream_id: int, path_begin: int, 
     prem_mu_log, prem_sigma_log, equity_inflation_rho)``; record k counts exactly what a count-only launch with those ten
     fields of `params` replaced counts.  Up to ``MCR_MAX_EXPENSE_FANOUT`` records share each path's normals.  Returns a
     device int64 tensor ``[len(records), 2]`` = ``{successes, paths}``; asynchronous (reading it synchronises)."""
+    arr, n = _assumption_records(records)
+    return _probe_records("mcr_probe_assumptions_rng", params, seed, stream_id, path_begin, n_paths, working_months, (arr,), n, device)
+
+
+def probe_scenarios_joint(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
+                          scenarios, device: int = 0, masks=True):
+    """`probe_scenarios` plus the joint outcomes of its scenarios over the shared paths (``mcr_probe_scenarios_joint_rng``).
+    Returns device int64 tensors ``(counts, joint, extremes, masks)``: `counts` as the plain probe's; ``joint[i, j]`` = paths on
+    which scenarios i and j both succeed (the diagonal is ``counts[:, 0]``); ``extremes`` = ``{paths on which all succeed,
+    paths on which none does}``; ``masks[k]`` = scenario k's success bits, bit b of word w = path ``path_begin + 64 w + b``
+    (int64 words: bit 63 is the sign).  At most ``MCR_MAX_JOINT_OPTIONS`` scenarios.  ``masks=None``: the library keeps the
+    masks in scratch of its own and None comes back in their place.  Asynchronous (reading a tensor synchronises)."""
+    arr, n = _scenario_records(scenarios)
+    return _probe_records("mcr_probe_scenarios_joint_rng", params, seed, stream_id, path_begin, n_paths, working_months, (arr,), n,
+                          device, joint=True, masks=masks)
+
+
+def probe_income_joint(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
+                       stream_index: int, options, device: int = 0, masks=True):
+    """`probe_income` plus the joint outcomes of its options (``mcr_probe_income_joint_rng``); returns ``(counts, joint,
+    extremes, masks)`` as `probe_scenarios_joint`."""
+    arr, n = _income_records(options)
+    return _probe_records("mcr_probe_income_joint_rng", params, seed, stream_id, path_begin, n_paths, working_months,
+                          (int(stream_index), arr), n, device, joint=True, masks=masks)
+
+
+def probe_assumptions_joint(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
+                            records, device: int = 0, masks=True):
+    """`probe_assumptions` plus the joint outcomes of its records (``mcr_probe_assumptions_joint_rng``); returns ``(counts,
+    joint, extremes, masks)`` as `probe_scenarios_joint`."""
+    arr, n = _assumption_records(records)
+    return _probe_records("mcr_probe_assumptions_joint_rng", params, seed, stream_id, path_begin, n_paths, working_months, (arr,), n,
+                          device, joint=True, masks=masks)
+
+
+def joint_counts(masks, n_paths: int, device: Optional[int] = None):
+    """The co-occurrence reduction alone (``mcr_joint_counts``): `masks` is a device int64 tensor ``[n, joint_mask_words(n_paths)]``
+    of success-mask rows, e.g. rows kept from several joint probes over the same path range.  Returns device int64 tensors
+    ``(joint [n, n], extremes [2])``.  Bits beyond `n_paths` in the last word are ignored.  Asynchronous."""
     import torch
 
     N.require_device()
-    records = [tuple(float(x) for x in r) for r in records]
-    if any(len(r) != 10 for r in records):
-        raise ValueError("every record holds the ten fields of mcr_assumptions")
-    arr = (McrAssumptions * max(1, len(records)))(*[McrAssumptions(*r) for r in records])
-    counts = torch.empty((len(records), N.MCR_N_COUNTERS), dtype=torch.int64, device=torch.device("cuda", int(device)))
-    if not records:
-        return counts
-    rng = _as_rng(seed)
-    stream = torch.cuda.current_stream(int(device)).cuda_stream
-    rc = N.load_library().mcr_probe_assumptions_rng(
-        C.byref(params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), int(working_months), arr,
-        len(records), counts.data_ptr(), int(device), C.c_void_p(stream),
-    )
-    N.check(rc, "mcr_probe_assumptions_rng")
-    return counts
+    if masks.dtype != torch.int64 or masks.dim() != 2 or not masks.is_cuda:
+        raise ValueError("masks must be a 2-d int64 device tensor")
+    n, words = int(masks.shape[0]), joint_mask_words(n_paths)
+    if int(masks.shape[1]) != words:
+        raise ValueError(f"masks has {int(masks.shape[1])} words per row; {int(n_paths)} paths take {words}")
+    if n > N.MCR_MAX_JOINT_OPTIONS:
+        raise ValueError(f"joint counts take at most MCR_MAX_JOINT_OPTIONS = {N.MCR_MAX_JOINT_OPTIONS} rows, got {n}")
+    device = masks.device.index if device is None else int(device)
+    masks = masks.contiguous()
+    alloc = torch.empty if n else torch.zeros           # (the call zeroes both)
+    jm = alloc((n, n), dtype=torch.int64, device=masks.device)
+    ex = alloc((2,), dtype=torch.int64, device=masks.device)
+    if n:
+        stream = torch.cuda.current_stream(device).cuda_stream
+        rc = N.load_library().mcr_joint_counts(masks.data_ptr() if words else None, n, int(n_paths), jm.data_ptr(), ex.data_ptr(),
+                                               device, C.c_void_p(stream))
+        N.check(rc, "mcr_joint_counts")
+    return jm, ex
 
 
 def probe_grid(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months, levels_2d,

@@ -809,6 +809,27 @@ class RetirementMonteCarloSimulator:
         counts = D.probe_candidates(list(range(len(levels))), n, self.shard_min_paths, probe)
         return np.array([self._count_percent(counts[i, N.MCR_CTR_SUCCESS], n) for i in range(len(levels))], dtype=np.float64)
 
+    def _joint_outcomes(self, joint_probe, n_records: int, num_simulations: Optional[int]):
+        """The body of the `joint_outcomes_by_*` methods: ``joint_probe(path_begin, count) -> (counts, joint, extremes, masks)``
+        is an `engine.probe_*_joint` call over ALL the records.  A pair table needs both options on the same path, so under
+        a process group the batch is always sharded by PATH RANGE (never by option) and the ``n^2 + 2`` integers are summed
+        in one all-reduce: every rank returns the same `paired.JointOutcomes`; masks stay on their rank."""
+        import torch
+
+        from .paired import JointOutcomes
+
+        k = int(n_records)
+        n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
+        if k == 0:
+            return JointOutcomes(np.zeros((0, 0), dtype=np.int64), n, (0, 0))
+
+        def probe(path_begin, count, _):
+            _, joint, extremes, _ = joint_probe(path_begin, count)
+            return torch.cat([joint.reshape(-1), extremes.reshape(-1)])
+
+        flat = D.probe_candidates([0], n, 0, probe, width=k * k + 2)[0]
+        return JointOutcomes(flat[:k * k].reshape(k, k), n, (int(flat[k * k]), int(flat[k * k + 1])))
+
     def success_probability_by_expenses(self, working_months: int, monthly_expenses: Sequence[float],
                                         num_simulations: Optional[int] = None) -> np.ndarray:
         """Success % of each ``monthly_expenses`` level at ``working_months``, over the active seed stream's batch of
@@ -936,6 +957,24 @@ class RetirementMonteCarloSimulator:
         counts = D.probe_candidates(list(range(len(records))), n, self.shard_min_paths, probe)
         return np.array([self._count_percent(counts[i, N.MCR_CTR_SUCCESS], n) for i in range(len(records))], dtype=np.float64)
 
+    def joint_outcomes_by_scenarios(self, working_months: int, scenarios: Sequence[dict],
+                                    num_simulations: Optional[int] = None):
+        """The joint outcomes of the scenarios of `success_probability_by_scenarios` (same arguments) over their shared
+        paths, from the joint scenario probe (``mcr_probe_scenarios_joint_rng``): a `paired.JointOutcomes` whose
+        ``.probabilities`` equal that method's array bit for bit.  At most ``MCR_MAX_JOINT_OPTIONS`` scenarios."""
+        from .nestegg import scenario_records
+
+        p = self.params_model
+        records = scenario_records(scenarios, (p.initial_balance, p.monthly_contribution, p.monthly_expenses))
+        n = int(p.num_simulations_main if num_simulations is None else num_simulations)
+        wm = int(working_months)
+        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
+
+        def probe(path_begin, count):
+            return E.probe_scenarios_joint(params, rng, self._stream_id, path_begin, count, wm, records, device=dev, masks=None)
+
+        return self._joint_outcomes(probe, len(records), n)
+
     def find_minimum_initial_balance(
         self,
         working_months: int,
@@ -1036,19 +1075,52 @@ class RetirementMonteCarloSimulator:
         counts = D.probe_candidates(list(range(len(records))), n, self.shard_min_paths, probe)
         return np.array([self._count_percent(counts[i, N.MCR_CTR_SUCCESS], n) for i in range(len(records))], dtype=np.float64)
 
+    def joint_outcomes_by_income_options(self, working_months: int, stream, options: Sequence[dict],
+                                         num_simulations: Optional[int] = None):
+        """The joint outcomes of the options of `success_probability_by_income_options` (same arguments) over their shared
+        paths, from the joint income probe (``mcr_probe_income_joint_rng``): a `paired.JointOutcomes` whose
+        ``.probabilities`` equal that method's array bit for bit.  At most ``MCR_MAX_JOINT_OPTIONS`` options."""
+        from .income import income_options, stream_index
+
+        p = self.params_model
+        index = stream_index(p, stream)
+        records = income_options(p, index, options)
+        n = int(p.num_simulations_main if num_simulations is None else num_simulations)
+        wm = int(working_months)
+        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
+
+        def probe(path_begin, count):
+            return E.probe_income_joint(params, rng, self._stream_id, path_begin, count, wm, index, records, device=dev, masks=None)
+
+        return self._joint_outcomes(probe, len(records), n)
+
     def compare_claiming_options(self, working_months: int, stream, options: Sequence[dict],
-                                 num_simulations: Optional[int] = None) -> dict:
+                                 num_simulations: Optional[int] = None, paired: bool = False) -> dict:
         """The claim-age table and the annuity comparison: `success_probability_by_income_options` of ``options`` as
         ``{"stream": list index, "options": [{the six fields, "probability"}, ...], "best": index}``, ``best`` being the
-        option with the highest probability (the first of equals)."""
+        option with the highest probability (the first of equals).
+
+        ``paired=True`` says whether the gaps are real: the table comes from `joint_outcomes_by_income_options` (the same
+        probabilities), every row gains ``"vs_best"`` = `JointOutcomes.difference` of the best option against the row
+        (``delta``, paired ``se``, ``se_unpaired``, McNemar ``p_value``, ``rescued``), and the document gains
+        ``"tied_with_best"`` (the rows the paired test cannot tell from the best at 5 %) and ``"all_succeed"`` /
+        ``"none_succeed"``, the paths on which every option works and on which none does."""
         from .income import INCOME_OPTION_FIELDS, income_options, stream_index
 
         index = stream_index(self.params_model, stream)
         records = income_options(self.params_model, index, options)
-        probs = self.success_probability_by_income_options(working_months, index, options, num_simulations)
+        outcomes = self.joint_outcomes_by_income_options(working_months, index, options, num_simulations) if paired else None
+        probs = (outcomes.probabilities if paired else
+                 self.success_probability_by_income_options(working_months, index, options, num_simulations))
         rows = [dict(zip(INCOME_OPTION_FIELDS, r), probability=float(pr)) for r, pr in zip(records, probs)]
         best = max(range(len(rows)), key=lambda i: (rows[i]["probability"], -i)) if rows else None
-        return {"stream": index, "options": rows, "best": best}
+        doc = {"stream": index, "options": rows, "best": best}
+        if paired:
+            for i, row in enumerate(rows):
+                row["vs_best"] = outcomes.difference(best, i)
+            doc["tied_with_best"] = outcomes.indistinguishable_from(best) if rows else []
+            doc["all_succeed"], doc["none_succeed"] = outcomes.all_succeed, outcomes.none_succeed
+        return doc
 
     _UNCHANGED = object()   # (find_minimum_income_amount: "the stream's own duration_years", which may itself be None)
 
@@ -1128,21 +1200,50 @@ class RetirementMonteCarloSimulator:
         counts = D.probe_candidates(list(range(len(records))), n, self.shard_min_paths, probe)
         return np.array([self._count_percent(counts[i, N.MCR_CTR_SUCCESS], n) for i in range(len(records))], dtype=np.float64)
 
+    def joint_outcomes_by_assumptions(self, working_months: int, scenarios: Sequence[dict],
+                                      num_simulations: Optional[int] = None):
+        """The joint outcomes of the records of `success_probability_by_assumptions` (same arguments) over their shared
+        paths, from the joint assumption probe (``mcr_probe_assumptions_joint_rng``): a `paired.JointOutcomes` whose
+        ``.probabilities`` equal that method's array bit for bit.  At most ``MCR_MAX_JOINT_OPTIONS`` records."""
+        from .stress import assumption_records
+
+        p = self.params_model
+        records = assumption_records(p, scenarios)
+        n = int(p.num_simulations_main if num_simulations is None else num_simulations)
+        wm = int(working_months)
+        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
+
+        def probe(path_begin, count):
+            return E.probe_assumptions_joint(params, rng, self._stream_id, path_begin, count, wm, records, device=dev, masks=None)
+
+        return self._joint_outcomes(probe, len(records), n)
+
     def stress_test(self, working_months: int, shifts: Optional[Sequence[Tuple[str, dict]]] = None,
-                    num_simulations: Optional[int] = None) -> List[Dict[str, object]]:
+                    num_simulations: Optional[int] = None, paired: bool = False) -> List[Dict[str, object]]:
         """The stress table at ``working_months``: ONE `success_probability_by_assumptions` call over the base case and one
         row per shift (default `stress.DEFAULT_SHIFTS`: 14 one-at-a-time additive shifts of the market's means,
         volatilities and correlation, i.e. 15 records, one launch).  ``shifts`` replaces the table with ``[(label, {field:
         delta, ...}), ...]``; several fields in one entry make a combined scenario.  Each shifted value is clipped to
         `Config`'s bounds.  Returns ``{"label", "overrides", "probability", "delta"}`` per row, base first: ``overrides``
-        holds the applied values, ``delta`` the row's probability minus the base row's, in points."""
+        holds the applied values, ``delta`` the row's probability minus the base row's, in points.
+
+        ``paired=True``: the table comes from `joint_outcomes_by_assumptions` (the same probabilities) and every row gains
+        ``"vs_base"`` = `JointOutcomes.difference` of the base row against it plus ``hurt`` (paths that succeed under the
+        base and fail under the shift) and ``helped`` (the reverse)."""
         from .stress import stress_scenarios
 
         rows = stress_scenarios(self.params_model, shifts)
-        probs = self.success_probability_by_assumptions(working_months, [o for _, o in rows], num_simulations)
+        records = [o for _, o in rows]
+        outcomes = self.joint_outcomes_by_assumptions(working_months, records, num_simulations) if paired else None
+        probs = outcomes.probabilities if paired else self.success_probability_by_assumptions(working_months, records, num_simulations)
         base = float(probs[0])
-        return [{"label": label, "overrides": dict(o), "probability": float(pr), "delta": float(pr) - base}
-                for (label, o), pr in zip(rows, probs)]
+        table = [{"label": label, "overrides": dict(o), "probability": float(pr), "delta": float(pr) - base}
+                 for (label, o), pr in zip(rows, probs)]
+        if paired:
+            for i, row in enumerate(table):
+                t = outcomes.pair(0, i)
+                row["vs_base"] = dict(outcomes.difference(0, i), hurt=t["only_a"], helped=t["only_b"])
+        return table
 
     def find_breakeven_assumption(
         self,
