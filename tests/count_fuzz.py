@@ -16,6 +16,10 @@ MAX_ATTEMPTS times.  A plan one of whose paths reaches a money scale (max |traje
 there on the reference's absolute 1e-6 comparisons are below one ulp of their operands and its own flags hang on the last bit
 of exp (tests/test_gpu_differential.py), so only below it are identical counts demanded.
 
+Every plan also has a NumPy leg (`numpy_leg`, `numpy_shocks`, `oracle_run_numpy` at the end of the file): the same plan on the
+reference's own random stream, its shocks drawn by NumPy and injected into the oracle, for the rng="numpy" kernels; and
+`numpy_extra` adds the one variant family of that stream the classes leave out.  The classes' plans do not depend on it.
+
 MCR_COUNT_FUZZ_SEED: other plans (soaks by hand); the default is the suite's.  Everything is deterministic in it, class by
 class: a class's plans do not depend on which other classes were generated before."""
 
@@ -228,22 +232,26 @@ STATS = {}          # class -> {"drawn", "kept", "dropped_scale", "redrawn_unmix
 _KEPT = {}
 
 
-def _generate(O, cls: str, count: int, sliced_n=None):
-    rng = np.random.default_rng([seed(), CLASSES.index(cls), 0 if sliced_n is None else 1])
+def _generate(O, cls: str, count: int, sliced_n=None, rng=None, draw=_draw, run_of=None):
+    """`rng`, `draw`, `run_of`: the generator, the draw and the run a plan is judged by, for plans outside CLASSES (numpy_extra)."""
+    if rng is None:
+        rng = np.random.default_rng([seed(), CLASSES.index(cls), 0 if sliced_n is None else 1])
+    if run_of is None:
+        run_of = lambda scn: oracle_run(O, scn, n=None if sliced_n is None else SAMPLE, trajectories=True)  # noqa: E731
     stats = {"drawn": 0, "kept": 0, "dropped_scale": 0, "redrawn_unmixed": 0, "kept_unmixed": 0}
     kept = []
     while len(kept) < count:
         i = len(kept)
         fallback = None
         for _ in range(MAX_ATTEMPTS):
-            scn = _draw(cls, rng, i, PATHS[i % 2] if sliced_n is None else sliced_n)
+            scn = draw(cls, rng, i, PATHS[i % 2] if sliced_n is None else sliced_n)
             while sliced_n is not None and not _fits_a_sliced_launch(scn):
-                scn = _draw(cls, rng, i, sliced_n)
+                scn = draw(cls, rng, i, sliced_n)
             stats["drawn"] += 1
             if stats["drawn"] > 40 * count:
                 raise RuntimeError(f"count_fuzz: class {cls} does not yield {count} plans in {40 * count} draws: {stats}")
             scn.cfgd["monthly_expenses"] = _calibrate(O, scn)
-            run = oracle_run(O, scn, n=None if sliced_n is None else SAMPLE, trajectories=True)
+            run = run_of(scn)
             if money_scale(run) >= SCALE_LIMIT:
                 stats["dropped_scale"] += 1
                 continue
@@ -274,3 +282,91 @@ def sliced_scenario(O, cls: str, n: int):
     retirement years, at most two frozen streams (redrawn within the class until that holds); calibrated, and its money scale
     and failure share checked, on a SAMPLE-path trajectory run."""
     return _generate(O, cls, 1, sliced_n=n)[0][0]
+
+
+# ---- the NumPy leg of a plan: the reference's own random stream, drawn by NumPy itself and injected into the oracle ------------
+# rng="numpy" runs path_kernel<MODE, 1, ...> instantiations of its own, and `O.run_batch` has no NumPy generator.  NumPy has: path
+# i of a launch at (main_seed, child_offset, stream, path_begin) draws from default_rng(s) with s the first state word of
+# SeedSequence(main_seed).spawn(2)[stream].spawn(..)[child_offset + path_begin + i], exactly as the reference's _path_seeds /
+# _draw_shock_path do, and the oracle takes the rows through `injected_shocks`.
+NUMPY_OFFSETS = (0, 7, 100_000)         # index % 3: the spawn offset an earlier batch of another size leaves behind
+NUMPY_BEGINS = (0, 1000)                # (index // 3) % 2
+EXTRA = "extra"                         # the class name of numpy_extra's plans
+EXTRA_KEPT = 2
+
+
+def numpy_leg(scn: Scenario):
+    """(main_seed, child_offset, path_begin) of plan `scn` on the NumPy stream: the child index of path i is their sum + i."""
+    return scn.seed, NUMPY_OFFSETS[scn.index % 3], NUMPY_BEGINS[(scn.index // 3) % 2]
+
+
+def numpy_path_seeds(scn: Scenario, n=None) -> np.ndarray:
+    """The uint32 seed of each of the plan's paths (SeedSequence.spawn appends the child's index to the spawn key)."""
+    main, off, begin = numpy_leg(scn)
+    n = scn.n if n is None else int(n)
+    return np.array([np.random.SeedSequence(main, spawn_key=(scn.stream, off + begin + i)).generate_state(1)[0] for i in range(n)],
+                    dtype=np.uint32)
+
+
+def numpy_shocks(scn: Scenario, wm=None, n=None, rho=None) -> np.ndarray:
+    """[n, shock_rows, 3] float64 (equity, inflation, premium): per path default_rng(seed32).standard_normal((shock_rows, 3)),
+    then inflation = rho equity + sqrt(max(0, 1 - rho^2)) independent (the reference's _draw_shock_path).  `shock_rows` is the
+    oracle's for `wm` months; `rho` is the plan's unless given (an assumption record may move it)."""
+    from oracle import oracle as O
+
+    wm = scn.wm if wm is None else int(wm)
+    rho = float(scn.cfgd["equity_inflation_correlation"] if rho is None else rho)
+    rows = int(O.query_sizes(scn.params(), wm).shock_rows)
+    ind = np.stack([np.random.default_rng(int(s)).standard_normal((rows, 3)) for s in numpy_path_seeds(scn, n)])
+    out = ind.copy()
+    out[:, :, 1] = rho * ind[:, :, 0] + math.sqrt(max(0.0, 1.0 - rho * rho)) * ind[:, :, 1]
+    return out
+
+
+_NUMPY_RUNS = {}
+
+
+def oracle_run_numpy(O, scn: Scenario, wm=None, n=None, trajectories=False, **over):
+    """`oracle_run` on the NumPy stream: the oracle's `run_batch` with `numpy_shocks` injected (cached, apart from the Philox
+    runs).  A moved `equity_inflation_correlation` in `over` moves the mix of the shocks with it."""
+    wm = scn.wm if wm is None else int(wm)
+    n = scn.n if n is None else int(n)
+    key = (scn.cls, scn.index, numpy_leg(scn), scn.stream, scn.cfgd["monthly_expenses"], n, wm,
+           tuple(sorted((k, repr(v)) for k, v in over.items())))
+    hit = _NUMPY_RUNS.get(key)
+    if hit is None or (trajectories and "trajectory" not in hit):
+        shocks = numpy_shocks(scn, wm, n, over.get("equity_inflation_correlation"))
+        hit = O.run_batch(scn.params(**over), 0, scn.stream, 0, n, wm, injected_shocks=shocks, want_trajectories=trajectories)
+        _NUMPY_RUNS[key] = hit
+    return hit
+
+
+def oracle_runs_numpy(O, jobs, threads: int = 8):
+    """`oracle_run_numpy(O, *args, **kwargs)` for every `(args, kwargs)` of `jobs`, on host threads."""
+    with ThreadPoolExecutor(max_workers=threads) as pool:
+        return list(pool.map(lambda j: oracle_run_numpy(O, *j[0], **j[1]), jobs))
+
+
+def _draw_extra(cls, rng, i, n):
+    """The one family CLASSES leave out: the generic variant for its 17-20 paying streams WITH an annual-gains tax on one asset
+    (asset 1 for even i, asset 2 for odd i).  The rest is a `generic` plan of even index 2 i: rho = 0, then rho = +-1."""
+    scn = _draw("generic", rng, 2 * i, n)
+    a = ("inv1", "inv2")[i % 2]
+    scn.cfgd.update({"scenario": f"{cls}-{i}", f"{a}_use_realized_gains_tax_system": False,
+                     f"{a}_annual_tax_on_gains_rate": float(rng.uniform(0.05, 0.5))})
+    scn.cls, scn.index = cls, i
+    return scn
+
+
+def numpy_extra(O):
+    """EXTRA_KEPT plans of class EXTRA, from a generator of their own (no plan of CLASSES moves); calibrated as the classes'
+    plans are, and judged (money scale, mixed outcomes) by their run on the NumPy stream, the one they are for."""
+    if EXTRA not in _KEPT:
+        _KEPT[EXTRA], STATS[EXTRA] = _generate(O, EXTRA, EXTRA_KEPT, rng=np.random.default_rng([seed(), len(CLASSES), 2]),
+                                               draw=_draw_extra, run_of=lambda scn: oracle_run_numpy(O, scn, trajectories=True))
+    return _KEPT[EXTRA]
+
+
+def numpy_plans(O, cls: str):
+    """The plans of `cls` on the NumPy stream: a class of CLASSES, or EXTRA."""
+    return numpy_extra(O) if cls == EXTRA else scenarios(O, cls)
