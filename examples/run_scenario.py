@@ -47,7 +47,10 @@ stream, started at age A (default: its own), that reaches the target, printed li
 `--paired` (with `--income-options` and / or `--stress`) says whether the table's gaps are real: the options run over the same
 paths, so every row also gets the paired difference against the best option (`vs_best`) or the base market (`vs_base`: also
 `hurt` / `helped` path counts) with its standard error and the exact McNemar p-value, and the claiming table gains
-`tied_with_best`, `all_succeed` and `none_succeed`."""
+`tied_with_best`, `all_succeed` and `none_succeed`.
+`--outcomes` (with `--income-options` and / or `--stress`, alone or with `--paired`) says when it goes wrong and what is left:
+every row also gets `lasts_until_age` (the age the money lasts to with 90 / 95 / 99 % confidence; null = the whole horizon),
+`median_ruin_age` (among the failing paths) and `final_balance` (p5 .. p95 of the successful paths' nominal final balance)."""
 
 from __future__ import annotations
 
@@ -98,6 +101,9 @@ def main() -> int:
     ap.add_argument("--paired", action="store_true",
                     help="--income-options / --stress: add the paired comparison over the shared paths (difference, its standard "
                          "error, the exact McNemar p-value, paths helped and hurt)")
+    ap.add_argument("--outcomes", action="store_true",
+                    help="--income-options / --stress: add when each option fails and what it leaves (lasts_until_age, "
+                         "median_ruin_age, final_balance percentiles of the successful paths)")
     ap.add_argument("--min-income", default=None, metavar="STREAM",
                     help="index or name of an income stream: search its minimum monthly amount at --working-months (default 0) instead")
     ap.add_argument("--claim-age", type=float, default=None, help="--min-income: the stream's start_at_age (default: its own)")
@@ -119,6 +125,8 @@ def main() -> int:
         ap.error("--income-options and --min-income are separate questions")
     if args.paired and args.income_options is None and not args.stress:
         ap.error("--paired goes with --income-options or --stress")
+    if args.outcomes and args.income_options is None and not args.stress:
+        ap.error("--outcomes goes with --income-options or --stress")
     if (args.claim_ages or args.claim_amounts) and args.income_options is None:
         ap.error("--claim-ages / --claim-amounts go with --income-options")
     if args.claim_age is not None and args.min_income is None:
@@ -258,7 +266,7 @@ def stress(args, config: Config, world: int, rank0: bool) -> int:
                "target_probability": config.target_probability}
         if args.stress:
             sim.use_final_seeds()
-            out["stress"] = sim.stress_test(wm, paired=True) if args.paired else sim.stress_test(wm)
+            out["stress"] = sim.stress_test(wm, **_table_flags(args))
         if args.breakeven:
             out["breakeven"] = []
             for field in [f.strip() for f in args.breakeven.split(",") if f.strip()]:
@@ -343,6 +351,11 @@ def min_initial_balance(args, config: Config, world: int, rank0: bool) -> int:
     return 0
 
 
+def _table_flags(args) -> dict:
+    """--paired / --outcomes as keyword arguments of `compare_claiming_options` / `stress_test` (neither: none at all)"""
+    return {k: True for k in ("paired", "outcomes") if getattr(args, k)}
+
+
 def _stream_arg(text: str):
     """STREAM of --income-options / --min-income: a list index where it reads as one, else a name"""
     return int(text) if text.strip().lstrip("+").isdigit() else text
@@ -363,7 +376,7 @@ def income_table(args, config: Config, world: int, rank0: bool) -> int:
         if amounts:
             o["monthly_amount_today"] = amounts[k]
     sim.use_final_seeds()
-    table = sim.compare_claiming_options(wm, _stream_arg(args.income_options), options, **({"paired": True} if args.paired else {}))
+    table = sim.compare_claiming_options(wm, _stream_arg(args.income_options), options, **_table_flags(args))
     out = {"scenario": config.Nickname, "rng": args.rng, "working_months": wm, "num_simulations": int(config.num_simulations_main),
            "target_probability": config.target_probability, **table, "seconds": round(time.perf_counter() - t0, 3)}
     if rank0:

@@ -475,6 +475,48 @@ int mcr_joint_counts(const uint64_t* masks, int32_t n_options, uint64_t n_paths,
                      int device, void* hip_stream);
 
 /*
+ * PER-OPTION OUTCOMES: when a path fails, and what a path that succeeds has left.  The *_outcomes_rng calls take the arguments
+ * of their plain probe (same validation, same routes, `counts` bit for bit the plain probe's,
+ * mcr_probe_*_last_fanout_launches report as before) plus `rows`, two DEVICE slabs of doubles, [n][path_stride] each:
+ *   row k of final_balance = where(success, final_balance, NaN), and row k of years_to_ruin = years_to_ruin (NaN on success),
+ *   of a summary mcr_run_batch_rng call with option k's fields replaced -- bit for bit, on every route.
+ * years_to_ruin is 0.0 for a pre-retirement tax failure, (month of retirement + 1) / 12 for a failure inside retirement and
+ * (double)retirement_years for a failure at the terminal settlement.  Elements of a row at or beyond n_paths are never
+ * written.  rows == NULL, or both pointers NULL, is the plain probe.  path_stride < n_paths is MCR_ERR_INVALID_ARG, checked
+ * before the device is touched; on any error `counts` and the rows stay untouched.  On the fan-out route the consumer waves of
+ * the fan-out kernel store their 64 paths' outcomes in their epilogue (one 512-byte store per wave and row; an option list
+ * longer than one launch's share needs nothing special).  Where the plain probe runs one launch per option (NumPy stream, more
+ * than MCR_INLINE_STREAMS kept streams, the exact month, one option, the MCR_*_FANOUT_MIN_WAVES knobs) each option's launch is
+ * a summary launch into the caller's rows (years_to_ruin into scratch where it is not requested) and a small kernel NaNs the
+ * failed paths' final balances.  The final_balance rows are mcr_row_quantiles input as they stand (NaNs are skipped there: the
+ * quantiles are those of the successful cohort, and the counts it returns are the success counts).
+ * mcr_ruin_month_counts reduces years_to_ruin rows: counts is DEVICE uint64 [n_rows][12 retirement_years + 1], ACCUMULATED
+ * into (the caller zeroes it); counts[r][m] += the non-NaN entries y of row r with rint(12 y) == m.  Entries whose month falls
+ * outside [0, 12 retirement_years] are dropped (the kernels write none).  One read of the slab; rows of up to 4096 cells
+ * (retirement_years <= 341) are counted in an LDS histogram per workgroup and flushed with one 64-bit atomic per non-empty
+ * cell, longer rows go straight to global atomics.  n == 0 or n_rows == 0 does nothing; row_stride >= n, retirement_years >= 1.
+ */
+typedef struct mcr_option_outcomes {
+    double* final_balance;   /* DEVICE [n][path_stride] or NULL = not requested */
+    double* years_to_ruin;   /* DEVICE [n][path_stride] or NULL = not requested */
+    int64_t path_stride;     /* >= n_paths */
+} mcr_option_outcomes;
+int mcr_probe_scenarios_outcomes_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                     uint64_t n_paths, int32_t working_months, const mcr_scenario* scenarios,
+                                     int32_t n_scenarios, uint64_t* counts, const mcr_option_outcomes* rows,
+                                     int device, void* hip_stream);
+int mcr_probe_assumptions_outcomes_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                       uint64_t n_paths, int32_t working_months, const mcr_assumptions* records,
+                                       int32_t n_records, uint64_t* counts, const mcr_option_outcomes* rows,
+                                       int device, void* hip_stream);
+int mcr_probe_income_outcomes_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                  uint64_t n_paths, int32_t working_months, int32_t stream_index,
+                                  const mcr_income_option* options, int32_t n_options,
+                                  uint64_t* counts, const mcr_option_outcomes* rows, int device, void* hip_stream);
+int mcr_ruin_month_counts(const double* years_to_ruin, int64_t row_stride, int32_t n_rows, int64_t n,
+                          int32_t retirement_years, uint64_t* counts, int device, void* hip_stream);
+
+/*
  * Retirement-month x spending grid: counts[c][k] equals, bit for bit, the counters of a count-only mcr_run_batch_rng call with
  * working_months[c] and p->monthly_expenses = monthly_expenses[c][k], everything else unchanged.  working_months: n_candidates
  * >= 0 months (any order, repeats allowed); monthly_expenses: HOST [n_candidates][n_levels] row-major, each finite and >= 0.

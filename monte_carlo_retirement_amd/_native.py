@@ -228,6 +228,16 @@ class McrIncomeOption(C.Structure):
     ]
 
 
+class McrOptionOutcomes(C.Structure):
+    """mcr_option_outcomes: the row slabs of the ``*_outcomes_rng`` probes (device pointers; None = not requested)."""
+
+    _fields_ = [
+        ("final_balance", C.c_void_p),
+        ("years_to_ruin", C.c_void_p),
+        ("path_stride", C.c_int64),
+    ]
+
+
 class McrSizes(C.Structure):
     _fields_ = [
         ("total_months", C.c_int32),
@@ -309,6 +319,10 @@ ABI_SYMBOLS = (
     "mcr_probe_assumptions_joint_rng",
     "mcr_probe_income_joint_rng",
     "mcr_joint_counts",
+    "mcr_probe_scenarios_outcomes_rng",
+    "mcr_probe_assumptions_outcomes_rng",
+    "mcr_probe_income_outcomes_rng",
+    "mcr_ruin_month_counts",
     "mcr_probe_grid_rng",
     "mcr_run_batch_multi_host_rng",
     "mcr_run_year_bins_rng",
@@ -434,6 +448,17 @@ def _declare(lib: C.CDLL) -> None:
         lib.mcr_probe_income_joint_rng.argtypes = head + [C.c_int32, P(McrIncomeOption), C.c_int32] + joint_out
         lib.mcr_joint_counts.restype = C.c_int
         lib.mcr_joint_counts.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    if hasattr(lib, "mcr_ruin_month_counts"):   # (likewise)
+        out = [C.c_void_p, P(McrOptionOutcomes), C.c_int, C.c_void_p]   # counts, rows, device, stream
+        head = [P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32]
+        lib.mcr_probe_scenarios_outcomes_rng.restype = C.c_int
+        lib.mcr_probe_scenarios_outcomes_rng.argtypes = head + [P(McrScenario), C.c_int32] + out
+        lib.mcr_probe_assumptions_outcomes_rng.restype = C.c_int
+        lib.mcr_probe_assumptions_outcomes_rng.argtypes = head + [P(McrAssumptions), C.c_int32] + out
+        lib.mcr_probe_income_outcomes_rng.restype = C.c_int
+        lib.mcr_probe_income_outcomes_rng.argtypes = head + [C.c_int32, P(McrIncomeOption), C.c_int32] + out
+        lib.mcr_ruin_month_counts.restype = C.c_int
+        lib.mcr_ruin_month_counts.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_int, C.c_void_p]
     lib.mcr_probe_grid_rng.restype = C.c_int
     lib.mcr_probe_grid_rng.argtypes = [
         P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, P(C.c_int32), C.c_int32, P(C.c_double), C.c_int32,

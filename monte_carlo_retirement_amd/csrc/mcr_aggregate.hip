@@ -1794,6 +1794,52 @@ int launch_joint_counts(const uint64_t* masks, int n, uint64_t n_paths, uint64_t
     return e == hipSuccess ? MCR_OK : hip_fail(e, "joint_counts_kernel");
 }
 
+// ---------------------------------------------------------------------------------------------
+// Per-option outcomes: years_to_ruin rows -> ruin-month counts (mcr_ruin_month_counts, mcr_probe_*_outcomes_rng)
+// ---------------------------------------------------------------------------------------------
+// grid = (column blocks, rows).  A workgroup strides over its row's columns, one contiguous 8-byte load per lane (a wave reads
+// 512 contiguous bytes), and counts month rint(12 y) of every non-NaN entry in an LDS histogram of 32-bit cells (ds atomics:
+// lanes collide only where paths fail in the same month, which the data decides).  Then one 64-bit global atomic per non-empty
+// cell, as the hist_bins flush.  LDS budget: kRuinLdsCells 32-bit cells = 16 KiB (12 ry + 1 <= 4096: retirement_years <= 341);
+// a longer row (LDS = false) adds straight to the global table.  A workgroup sees at most n / gridDim.x + 256 entries, far
+// below 2^32 for the n < 2^40 the host accepts.
+constexpr int kRuinLdsCells = 4096;
+constexpr int kRuinBlock = 256;
+template <bool LDS>
+__global__ __launch_bounds__(kRuinBlock) void ruin_month_counts_kernel(const double* __restrict__ rows, int64_t row_stride, int64_t n, int cells,
+                                                                       unsigned long long* __restrict__ counts) {
+    __shared__ unsigned int h[LDS ? kRuinLdsCells : 1];
+    if (LDS) {
+        for (int k = threadIdx.x; k < cells; k += kRuinBlock) h[k] = 0u;
+        __syncthreads();
+    }
+    const double* __restrict__ row = rows + (size_t)blockIdx.y * (size_t)row_stride;
+    unsigned long long* const out = counts + (size_t)blockIdx.y * (size_t)cells;
+    const double top = (double)(cells - 1);
+    for (int64_t i = (int64_t)blockIdx.x * kRuinBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kRuinBlock) {
+        const double m = rint(12.0 * row[i]);
+        if (!(m >= 0.0 && m <= top)) continue;    // NaN (a path that succeeded) or a month outside the table
+        if (LDS) atomicAdd(&h[(int)m], 1u); else atomicAdd(&out[(int)m], 1ull);
+    }
+    if (LDS) {
+        __syncthreads();
+        for (int k = threadIdx.x; k < cells; k += kRuinBlock)
+            if (h[k]) atomicAdd(&out[k], (unsigned long long)h[k]);
+    }
+}
+// final_balance[i] = NaN where years_to_ruin[i] is a number: row 2 of stat_rows_kernel, from the summary launch's own column
+__global__ __launch_bounds__(256) void nan_failed_kernel(double* __restrict__ fin, const double* __restrict__ ytr, unsigned long long n) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n && ytr[i] == ytr[i]) fin[i] = __longlong_as_double(0x7ff8000000000000LL);
+}
+int launch_nan_failed(double* final_balance, const double* years_to_ruin, uint64_t n_paths, hipStream_t stream) {
+    if (n_paths == 0) return MCR_OK;
+    hipLaunchKernelGGL(nan_failed_kernel, dim3((unsigned)((n_paths + 255) / 256)), dim3(256), 0, stream, final_balance, years_to_ruin,
+                       (unsigned long long)n_paths);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MCR_OK : hip_fail(e, "nan_failed_kernel");
+}
+
 }  // namespace mcr
 using namespace mcr;
 extern "C" {
@@ -2189,6 +2235,31 @@ int mcr_joint_counts(const uint64_t* masks, int32_t n_options, uint64_t n_paths,
     if (!joint || (!masks && n_paths > 0)) { set_error("null joint / masks"); return MCR_ERR_INVALID_ARG; }
     MCR_ENTER_DEVICE(device);
     return launch_joint_counts(masks, n_options, n_paths, joint, extremes, (hipStream_t)hip_stream);
+}
+
+int mcr_ruin_month_counts(const double* years_to_ruin, int64_t row_stride, int32_t n_rows, int64_t n, int32_t retirement_years,
+                          uint64_t* counts, int device, void* hip_stream) {
+    if (n_rows < 0 || n < 0 || n >= ((int64_t)1 << 40) || retirement_years < 1 || retirement_years > (INT32_MAX - 1) / 12 || row_stride < n) {
+        set_error("bad arguments: n_rows %d, n %lld, row_stride %lld, retirement_years %d", n_rows, (long long)n, (long long)row_stride, retirement_years);
+        return MCR_ERR_INVALID_ARG;
+    }
+    if (n_rows == 0 || n == 0) return MCR_OK;
+    if (!years_to_ruin || !counts) { set_error("null years_to_ruin / counts"); return MCR_ERR_INVALID_ARG; }
+    MCR_ENTER_DEVICE(device);
+    const int cells = 12 * retirement_years + 1;
+    // 8 columns a thread; the column blocks of all rows together stay near the 2 048 workgroups of the other slab passes
+    int gx = grid_for(n, kRuinBlock * 8, 2048 / (n_rows < 2048 ? n_rows : 2048));
+    for (int r0 = 0; r0 < n_rows; r0 += 65535) {    // (grid.y <= 65 535)
+        const int nr = n_rows - r0 < 65535 ? n_rows - r0 : 65535;
+        const double* rows = years_to_ruin + (size_t)r0 * (size_t)row_stride;
+        unsigned long long* out = (unsigned long long*)counts + (size_t)r0 * (size_t)cells;
+        if (cells <= kRuinLdsCells)
+            hipLaunchKernelGGL(ruin_month_counts_kernel<true>, dim3(gx, nr), dim3(kRuinBlock), 0, (hipStream_t)hip_stream, rows, row_stride, n, cells, out);
+        else
+            hipLaunchKernelGGL(ruin_month_counts_kernel<false>, dim3(gx, nr), dim3(kRuinBlock), 0, (hipStream_t)hip_stream, rows, row_stride, n, cells, out);
+    }
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MCR_OK : hip_fail(e, "ruin_month_counts_kernel");
 }
 
 }  // extern "C"

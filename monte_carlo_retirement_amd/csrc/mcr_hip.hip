@@ -84,16 +84,27 @@ struct KernelIO {
         unsigned long long* final_success;    // [n_bins + 2] or nullptr
         int32_t n_bins, n_wr_bins;            // (0: the group is not requested)
     };
+    // PHASE 8 / 9 / 10, outcome probes (mcr_probe_*_outcomes_rng; path_kernel's OUT): [fan_n][row_stride] rows or nullptr; lane l of
+    // consumer wave j stores its path's outcome to element 64 blockIdx.x + l of row j.  These launches read no fan-out level, so
+    // the rows share those bytes too (behind the word of PHASE 10's fan_stream): the kernel arguments keep their size and layout
+    struct FanRows {
+        int64_t fan_stream_word;
+        double* final_balance;
+        double* years_to_ruin;
+        int64_t row_stride;
+    };
     union {
         double fan_expenses[MCR_MAX_EXPENSE_FANOUT];   // the fan-out levels
         YearBins yb;
         int32_t fan_stream;                            // PHASE 10: which of the kept records (DevParams::streams) the consumer waves replace
+        FanRows fan_rows;                              // PHASE 8 / 9 / 10, outcome probes (behind fan_stream's word)
     };
     // PHASE 8 / 9 / 10, joint probes (mcr_probe_*_joint_rng): [fan_n][(n_paths + 63) / 64] success masks or nullptr; consumer wave j
     // stores its 64 paths' ballot to word blockIdx.x of row j.  Last, so every other field keeps its place in the kernel arguments
     uint64_t* fan_masks;
 };
 static_assert(sizeof(KernelIO::YearBins) <= sizeof(double) * MCR_MAX_EXPENSE_FANOUT, "the yearly-bins block must fit the bytes it overlays");
+static_assert(sizeof(KernelIO::FanRows) <= sizeof(double) * MCR_MAX_EXPENSE_FANOUT, "the outcome rows must fit the bytes they overlay");
 // path_kernel(DevParams, KernelIO, const DevParams*): a field of the second argument read from the kernel-argument segment at
 // the point of use (the arguments lie there in order, each at its natural alignment).  Wave-uniform: a scalar load.
 constexpr size_t kKernelIOArgOffset = (sizeof(DevParams) + alignof(KernelIO) - 1) / alignof(KernelIO) * alignof(KernelIO);
@@ -331,6 +342,9 @@ __device__ __forceinline__ int prio_from(int t1, int t2, int t3, int r) { return
 // ROW (start + wm, saturated) and its length in months — the month tests (unsigned)(row - first) < length
 struct StreamRegs { double a0, a1; int s0, s1; unsigned n0, n1; };
 struct NoStreamRegs {};
+// OUT (outcome probes): the lane's month of failure, for the years_to_ruin row
+struct RuinMonth { int month; };
+struct NoRuinMonth {};
 // PHASE 10: what a consumer wave keeps of its record's stream, and which of the kept records (DevParams::streams) it replaces
 struct IncomeRegs { double amount, amount_keep; int32_t start_month, end_month; int k; };
 struct NoIncomeRegs {};
@@ -338,7 +352,7 @@ __device__ __forceinline__ void income_put(DevStream& S, const IncomeRegs& R) {
     S.amount = R.amount; S.amount_keep = R.amount_keep; S.start_month = R.start_month; S.end_month = R.end_month;
 }
 
-template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault, int GF = 0, int MF = 0, int SF = 0>
+template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault, int GF = 0, int MF = 0, int SF = 0, bool OUT = false>
 __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE == 8 || PHASE == 9 || PHASE == 10) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
                                                          const DevParams* __restrict__ cand_params) {
     // MODE 3 (mcr_run_year_bins_rng): YEARLY BINS.  The arithmetic of MODE 2, but wherever that variant stores a yearly sample
@@ -361,6 +375,10 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     static_assert(PHASE != 8 || SPLIT, "the scenario fan-out is a producer / consumer form");
     static_assert(PHASE != 9 || SPLIT, "the assumption fan-out is a producer / consumer form");
     static_assert(PHASE != 10 || SPLIT, "the income fan-out is a producer / consumer form");
+    // OUT (mcr_probe_*_outcomes_rng): the PHASE 8 / 9 / 10 consumer waves also store their paths' outcome rows (KernelIO::fan_final,
+    // fan_ruin) in the epilogue.  A template flag, not a null check: the month of failure is one more VGPR through the month loop,
+    // which the plain and the joint probes' kernels do not pay.
+    static_assert(!OUT || PHASE == 8 || PHASE == 9 || PHASE == 10, "outcome rows exist for the scenario, assumption and income fan-outs");
     // PHASE 4 = PHASE 2 (a candidate's decumulation resumed from its accumulation snapshot) time-sliced like PHASE 3: the
     // 17-month verification window of the search is 17 x 196 workgroups = 2.17 rounds of the resident slots.
     constexpr bool kExpFan = PHASE == 5 || PHASE == 6;    // expense fan-out: the levels are monthly_expenses, resumed at retirement
@@ -385,6 +403,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     [[maybe_unused]] std::conditional_t<kScalarCounters, MonthCounters, NoMonthCounters> SC;    // (an empty object in every other variant)
     [[maybe_unused]] std::conditional_t<kSIR, StreamRegs, NoStreamRegs> SR;    // (an empty object in every other variant)
     [[maybe_unused]] std::conditional_t<kIncFan, IncomeRegs, NoIncomeRegs> IR;   // (likewise)
+    [[maybe_unused]] std::conditional_t<OUT, RuinMonth, NoRuinMonth> RM;         // (likewise: the outcome probes' month of failure)
     static_assert(!kSliced || (RNG == 0 && !INJ && !SPLIT && !XS), "time-sliced blocks exist for the plain Philox variants");
     static_assert(PHASE != 4 || MODE == 0, "the search probes count only");
     // TAXED: which assets carry an effective realized-gains rate (bit 0: inv1, bit 1: inv2; DevParams::tax_mask)
@@ -821,6 +840,10 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     // PHASE 5: this wave's spending level, an SGPR (kernel-argument array, wave-uniform index)
     const double fan_expenses = kGrid ? cell->levels[fan_j] : kExpFan ? io.fan_expenses[fan_j] : 0.0;
     int ruin_bin = pre_fail ? 0 : -1;
+    // OUT: YearsToRuin as an integer, 12 x the column's value (-1: none).  0 = a pre-retirement tax failure, fail_rmi + 1 = a
+    // failure inside retirement, 12 ry = a terminal-settlement failure: one conversion and one IEEE division in the epilogue
+    // give the bits a summary launch stores (12 ry / 12 is exact)
+    if constexpr (OUT) RM.month = pre_fail ? 0 : -1;
     int done_years = 0;  // completed (observed) retirement years = non-NaN WR entries
     int year = 0;
     if (kSliced && seg_resumed) {   // flags of the hand-over state: alive | succeeded << 1 | (ruin_bin + 1) << 8 | done_years << 24
@@ -1004,6 +1027,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
                 succeeded = false;                                                     // :843
                 if (kSumLds) sum_col[2 * kBlock] = (double)(fail_rmi + 1) / (double)kMPY;  // :825-827, :844-847
                 else ytr_bits = f64_bits((double)(fail_rmi + 1) / (double)kMPY);
+                if constexpr (OUT) RM.month = fail_rmi + 1;
                 ruin_bin = 1 + year;
                 sample = fmax(0.0, b1 + b2);                                           // :848
                 alive = false;                                                         // :857
@@ -1067,6 +1091,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
             if (tf) {                                                            // :894-896
                 succeeded = false; ruin_bin = ry + 1;
                 if (kSumLds) sum_col[2 * kBlock] = (double)ry; else ytr_bits = f64_bits((double)ry);
+                if constexpr (OUT) RM.month = kMPY * ry;
             }
             if constexpr (kBins) YB.last = b1 + b2;                              // (binned below: no barrier under a lane mask)
             else put_sample(P.trajectory_len - 1, b1 + b2, infl);                // :897-898
@@ -1108,6 +1133,20 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
             // joint probes keep the ballot: bit b of word path_block of row j = path 64 path_block + b under option j
             uint64_t* const fan_masks = late_arg<uint64_t*>(offsetof(KernelIO, fan_masks));
             if (fan_masks && (threadIdx.x & 63) == 0) fan_masks[(size_t)fan_j * ((n_paths + 63) >> 6) + path_block] = ok;
+            // outcome probes keep the path's outcome: one 512-byte wave store per requested row, lanes beyond n_paths store nothing.
+            // final_balance = "Final Balance" where the path succeeds, else NaN (row 2 of mcr_summary_stat_rows); years_to_ruin =
+            // the summary launch's column.  NaNs go out as bit patterns (the device code is built without NaN semantics).
+            if constexpr (OUT) {
+                double* const fan_final = late_arg<double*>(offsetof(KernelIO, fan_rows) + offsetof(KernelIO::FanRows, final_balance));
+                double* const fan_ruin = late_arg<double*>(offsetof(KernelIO, fan_rows) + offsetof(KernelIO::FanRows, years_to_ruin));
+                const int64_t row_stride = late_arg<int64_t>(offsetof(KernelIO, fan_rows) + offsetof(KernelIO::FanRows, row_stride));
+                const uint64_t col = (uint64_t)path_block * kPaths + (threadIdx.x & 63);
+                if (col < n_paths) {
+                    const size_t at = (size_t)fan_j * (size_t)row_stride + (size_t)col;
+                    if (fan_final) store_bits(&fan_final[at], succeeded ? f64_bits(final_balance) : kNanBits);
+                    if (fan_ruin) store_bits(&fan_ruin[at], RM.month < 0 ? kNanBits : f64_bits((double)RM.month / (double)kMPY));
+                }
+            }
             __syncthreads();
             if (threadIdx.x < (unsigned)fan_n && fan_ctr) {
                 uint64_t* c = fan_ctr + (size_t)threadIdx.x * MCR_N_COUNTERS;
@@ -2645,6 +2684,14 @@ static int probe_contributions_fanout(const mcr_params* p, const mcr_rng* rng, u
     return MCR_OK;
 }
 
+// Outcome probes (mcr_probe_*_outcomes_rng): a fan-out launch over options [first, first + lg) gets the rows at option `first`
+static void set_fan_rows(KernelIO& fio, const mcr_option_outcomes* rows, int first) {
+    if (!rows) return;
+    fio.fan_rows.row_stride = rows->path_stride;
+    fio.fan_rows.final_balance = rows->final_balance ? rows->final_balance + (size_t)first * (size_t)rows->path_stride : nullptr;
+    fio.fan_rows.years_to_ruin = rows->years_to_ruin ? rows->years_to_ruin + (size_t)first * (size_t)rows->path_stride : nullptr;
+}
+
 // Several (initial_balance, monthly_contribution, monthly_expenses) records over the same paths, Philox stream: scenario fan-out
 // launches (PHASE 8) over groups of at most fanout_max_levels records, the whole path each, like the contribution fan-out.
 // The records go to ONE stream-ordered device table (SnapshotBlock's records, no snapshot column), filled with one async
@@ -2654,7 +2701,8 @@ static int probe_contributions_fanout(const mcr_params* p, const mcr_rng* rng, u
 // does not cover and when the table's allocation is refused.
 static int probe_scenarios_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
                                   int32_t wm, const mcr_scenario* scenarios, int32_t n_scenarios, uint64_t* counts, hipStream_t stream,
-                                  uint64_t* masks = nullptr /* joint probes: KernelIO::fan_masks of the whole option list */) {
+                                  uint64_t* masks = nullptr /* joint probes: KernelIO::fan_masks of the whole option list */,
+                                  const mcr_option_outcomes* rows = nullptr /* outcome probes: the rows of the whole option list */) {
     DevParams d;
     int lmax = 0;
     if (int rc = plan_level_fanout(p, rng, n_paths, wm, n_scenarios, fanout_min_waves("MCR_SCENARIO_FANOUT_MIN_WAVES"), &d, &lmax)) return rc;
@@ -2673,8 +2721,11 @@ static int probe_scenarios_fanout(const mcr_params* p, const mcr_rng* rng, uint3
                 fio.out.counters = counts + (size_t)first * MCR_N_COUNTERS;
                 fio.fan_n = lg;
                 fio.fan_masks = masks ? masks + (size_t)first * ((n_paths + 63) / 64) : nullptr;
-                hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 8, true>), grid, dim3(64 * (lg + 1)),
-                                   fanout_dynamic_lds(d, lg), stream, d, fio, (const DevParams*)(d_table + first));
+                set_fan_rows(fio, rows, first);
+                for_bool(rows != nullptr, [&](auto O) {
+                    hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 8, true, false, kExactMonthDefault, 0, 0, 0, decltype(O)::value>),
+                                       grid, dim3(64 * (lg + 1)), fanout_dynamic_lds(d, lg), stream, d, fio, (const DevParams*)(d_table + first));
+                });
             });
         });
         e = hipGetLastError();
@@ -2696,7 +2747,8 @@ static int probe_scenarios_fanout(const mcr_params* p, const mcr_rng* rng, uint3
 static thread_local int g_last_assumption_fanout_launches = 0;   // (mcr_probe_assumptions_last_fanout_launches)
 static int probe_assumptions_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
                                     int32_t wm, const mcr_assumptions* records, int32_t n_records, uint64_t* counts, hipStream_t stream,
-                                  uint64_t* masks = nullptr /* joint probes: KernelIO::fan_masks of the whole option list */) {
+                                  uint64_t* masks = nullptr /* joint probes: KernelIO::fan_masks of the whole option list */,
+                                  const mcr_option_outcomes* rows = nullptr /* outcome probes: the rows of the whole option list */) {
     DevParams d;
     int lmax = 0;
     if (int rc = plan_level_fanout(p, rng, n_paths, wm, n_records, fanout_min_waves("MCR_ASSUMPTION_FANOUT_MIN_WAVES"), &d, &lmax, true)) return rc;
@@ -2723,8 +2775,11 @@ static int probe_assumptions_fanout(const mcr_params* p, const mcr_rng* rng, uin
                 fio.out.counters = counts + (size_t)first * MCR_N_COUNTERS;
                 fio.fan_n = lg;
                 fio.fan_masks = masks ? masks + (size_t)first * ((n_paths + 63) / 64) : nullptr;
-                hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 9, true>), grid, dim3(64 * (lg + 1)),
-                                   fanout_dynamic_lds(d, lg), stream, d, fio, (const DevParams*)(d_table + first));
+                set_fan_rows(fio, rows, first);
+                for_bool(rows != nullptr, [&](auto O) {
+                    hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 9, true, false, kExactMonthDefault, 0, 0, 0, decltype(O)::value>),
+                                       grid, dim3(64 * (lg + 1)), fanout_dynamic_lds(d, lg), stream, d, fio, (const DevParams*)(d_table + first));
+                });
                 ++g_last_assumption_fanout_launches;
             });
         });
@@ -2749,7 +2804,8 @@ static int probe_assumptions_fanout(const mcr_params* p, const mcr_rng* rng, uin
 static thread_local int g_last_income_fanout_launches = 0;   // (mcr_probe_income_last_fanout_launches)
 static int probe_income_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
                                int32_t wm, int32_t stream_index, const mcr_income_option* options, int32_t n_options, uint64_t* counts,
-                               hipStream_t stream, uint64_t* masks = nullptr /* joint probes: KernelIO::fan_masks of the whole option list */) {
+                               hipStream_t stream, uint64_t* masks = nullptr /* joint probes: KernelIO::fan_masks of the whole option list */,
+                               const mcr_option_outcomes* rows = nullptr /* outcome probes: the rows of the whole option list */) {
     DevParams d;
     int lmax = 0;
     std::vector<std::pair<int, int>> kept;
@@ -2781,8 +2837,11 @@ static int probe_income_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t
                 fio.fan_n = lg;
                 fio.fan_masks = masks ? masks + (size_t)first * ((n_paths + 63) / 64) : nullptr;
                 fio.fan_stream = kept_k;
-                hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 10, true>), grid, dim3(64 * (lg + 1)),
-                                   fanout_dynamic_lds(d, lg), stream, d, fio, (const DevParams*)(d_table + first));
+                set_fan_rows(fio, rows, first);
+                for_bool(rows != nullptr, [&](auto O) {
+                    hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 10, true, false, kExactMonthDefault, 0, 0, 0, decltype(O)::value>),
+                                       grid, dim3(64 * (lg + 1)), fanout_dynamic_lds(d, lg), stream, d, fio, (const DevParams*)(d_table + first));
+                });
                 ++g_last_income_fanout_launches;
             });
         });
@@ -2917,25 +2976,51 @@ static int check_joint_args(int32_t n_options, const uint64_t* joint) {
 }
 // The routes of a scenario / assumption / income probe once its arguments are validated and `counts` zeroed.
 //   fanout(masks): the probe's probe_*_fanout (MCR_ERR_UNSUPPORTED, nothing enqueued, for shapes it does not cover);
-//   launch(k, stream, success): option k's whole-path launch into its counter block and, if non-null, a uint8 [n_paths] column.
+//   launch(k, stream, success, final_balance, years_to_ruin): option k's whole-path launch into its counter block and, where
+//   non-null, a uint8 [n_paths] column and the two summary columns.
 // Plain (jo == nullptr): one option -> its launch; else the fan-out; else one count-only launch per option (fork_join).
 // Joint: the fan-out stores its ballots to the mask rows; where it does not run, one launch per option with `success` and
 // `counters` set fills a scratch uint8 [n][n_paths] and pack_success_kernel turns each column into its row on the option's side
 // stream.  Either way joint_counts_kernel then reduces the rows.  Masks the caller does not keep and the flag columns are
 // stream-ordered scratch, released behind the work.
+// Outcomes (rows != nullptr, never with jo): the fan-out's OUT kernels store the rows; where it does not run, option k's launch
+// is a summary launch whose final_balance / years_to_ruin columns ARE its rows (years_to_ruin in scratch where the caller does
+// not ask for it), and nan_failed_kernel then NaNs the final balances of the failed paths on the option's side stream.
 template <typename Fanout, typename Launch>
-static int run_probe_routes(int device, hipStream_t main, int n, uint64_t n_paths, const JointOut* jo, Fanout&& fanout, Launch&& launch) {
+static int run_probe_routes(int device, hipStream_t main, int n, uint64_t n_paths, const JointOut* jo, const mcr_option_outcomes* rows,
+                            Fanout&& fanout, Launch&& launch) {
+    if (rows && n_paths > 0) {
+        int rc = n == 1 ? MCR_ERR_UNSUPPORTED : fanout(nullptr, rows);
+        if (rc != MCR_ERR_UNSUPPORTED) return rc;
+        StreamAlloc own_ruin(main);
+        double* ruin = rows->years_to_ruin;
+        size_t ruin_stride = (size_t)rows->path_stride;
+        if (!ruin) {
+            if (!own_ruin.alloc((size_t)n * n_paths * sizeof(double))) { set_error("outcome probe: could not allocate %d ruin columns", n); return MCR_ERR_HIP; }
+            ruin = (double*)own_ruin.p;
+            ruin_stride = (size_t)n_paths;
+        }
+        rc = fork_join(device, main, n, [&](int k, hipStream_t s) {
+            double* const fin = rows->final_balance ? rows->final_balance + (size_t)k * (size_t)rows->path_stride : nullptr;
+            double* const ytr = ruin + (size_t)k * ruin_stride;
+            const int rck = launch(k, s, nullptr, fin, ytr);
+            return rck == MCR_OK && fin ? launch_nan_failed(fin, ytr, n_paths, s) : rck;
+        });
+        const hipError_t ef = own_ruin.release();
+        if (rc == MCR_OK && ef != hipSuccess) rc = hip_fail(ef, "outcome probe (free)");
+        return rc;
+    }
     auto per_option = [&](uint8_t* flags, uint64_t* masks) {
         return fork_join(device, main, n, [&](int k, hipStream_t s) {
             uint8_t* const col = flags ? flags + (size_t)k * n_paths : nullptr;
-            const int rc = launch(k, s, col);
+            const int rc = launch(k, s, col, nullptr, nullptr);
             return rc == MCR_OK && col ? launch_pack_success(col, n_paths, masks + (size_t)k * joint_mask_words(n_paths), s) : rc;
         });
     };
     if (!jo || n_paths == 0) {
         int rc = MCR_OK;
-        if (n == 1) rc = launch(0, main, nullptr);
-        else if ((rc = fanout(nullptr)) == MCR_ERR_UNSUPPORTED) rc = per_option(nullptr, nullptr);   // (unsupported shape / allocation refused)
+        if (n == 1) rc = launch(0, main, nullptr, nullptr, nullptr);
+        else if ((rc = fanout(nullptr, nullptr)) == MCR_ERR_UNSUPPORTED) rc = per_option(nullptr, nullptr);   // (unsupported shape / allocation refused)
         return rc == MCR_OK && jo ? launch_joint_counts(nullptr, n, 0, jo->joint, jo->extremes, main) : rc;
     }
     const size_t words = (size_t)joint_mask_words(n_paths);
@@ -2945,7 +3030,7 @@ static int run_probe_routes(int device, hipStream_t main, int n, uint64_t n_path
         if (!own_masks.alloc((size_t)n * words * sizeof(uint64_t))) { set_error("joint probe: could not allocate %d mask rows", n); return MCR_ERR_HIP; }
         masks = (uint64_t*)own_masks.p;
     }
-    int rc = n == 1 ? MCR_ERR_UNSUPPORTED : fanout(masks);
+    int rc = n == 1 ? MCR_ERR_UNSUPPORTED : fanout(masks, nullptr);
     if (rc == MCR_ERR_UNSUPPORTED) {
         if (!flags.alloc((size_t)n * n_paths)) { set_error("joint probe: could not allocate %d success columns", n); return MCR_ERR_HIP; }
         rc = per_option((uint8_t*)flags.p, masks);
@@ -2957,11 +3042,22 @@ static int run_probe_routes(int device, hipStream_t main, int n, uint64_t n_path
     if (rc == MCR_OK && ef != hipSuccess) rc = hip_fail(ef, "joint probe (free)");
     return rc;
 }
-// counters_only plus the per-path success column of the joint probes' per-option route (null: counters alone)
-static mcr_outputs counters_and_success(uint64_t* counters, uint8_t* success) {
+// counters_only plus the per-path columns of the joint and the outcome probes' per-option route (all null: counters alone)
+static mcr_outputs counters_and_columns(uint64_t* counters, uint8_t* success, double* final_balance, double* years_to_ruin) {
     mcr_outputs o = counters_only(counters);
     o.success = success;
+    o.final_balance = final_balance;
+    o.years_to_ruin = years_to_ruin;
     return o;
+}
+// What an outcomes entry point checks before it touches the device or its outputs; *rows = nullptr where no row is requested
+static int check_outcome_args(const mcr_option_outcomes** rows, uint64_t n_paths) {
+    if (*rows && !(*rows)->final_balance && !(*rows)->years_to_ruin) *rows = nullptr;
+    if (*rows && ((*rows)->path_stride < 0 || (uint64_t)(*rows)->path_stride < n_paths)) {
+        set_error("rows->path_stride %lld < n_paths %llu", (long long)(*rows)->path_stride, (unsigned long long)n_paths);
+        return MCR_ERR_INVALID_ARG;
+    }
+    return MCR_OK;
 }
 
 }  // namespace mcr
@@ -3097,10 +3193,11 @@ int mcr_probe_contributions_rng(const mcr_params* p, const mcr_rng* rng, uint32_
                                                     "monthly_contribution", 57, monthly_contributions, n_levels, counts, device, (hipStream_t)hip_stream);
 }
 
-// mcr_probe_scenarios_rng (jo == nullptr) and mcr_probe_scenarios_joint_rng, on the entered device
+// mcr_probe_scenarios_rng (jo == nullptr, rows == nullptr), mcr_probe_scenarios_joint_rng and mcr_probe_scenarios_outcomes_rng,
+// on the entered device
 static int probe_scenarios(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
                            int32_t working_months, const mcr_scenario* scenarios, int32_t n_scenarios, uint64_t* counts,
-                           const JointOut* jo, int device, hipStream_t main) {
+                           const JointOut* jo, const mcr_option_outcomes* rows, int device, hipStream_t main) {
     if (n_scenarios < 0) { set_error("n_scenarios %d must be >= 0", n_scenarios); return MCR_ERR_INVALID_ARG; }
     if (n_scenarios == 0) return MCR_OK;
     if (!scenarios || !counts) { set_error("null scenarios / counts"); return MCR_ERR_INVALID_ARG; }
@@ -3124,24 +3221,24 @@ static int probe_scenarios(const mcr_params* p, const mcr_rng* rng, uint32_t str
     rc = zero_counters(counts, (size_t)n_scenarios, main);
     if (rc != MCR_OK) return rc;
     mcr_params q = *p;
-    auto launch_scenario = [&](int k, hipStream_t s, uint8_t* success) {
+    auto launch_scenario = [&](int k, hipStream_t s, uint8_t* success, double* final_balance, double* years_to_ruin) {
         q.initial_balance = scenarios[k].initial_balance;
         q.monthly_contribution = scenarios[k].monthly_contribution;
         q.monthly_expenses = scenarios[k].monthly_expenses;
-        const mcr_outputs o = counters_and_success(counts + (size_t)k * MCR_N_COUNTERS, success);
+        const mcr_outputs o = counters_and_columns(counts + (size_t)k * MCR_N_COUNTERS, success, final_balance, years_to_ruin);
         return launch_paths(&q, rng, stream_id, path_begin, n_paths, working_months, nullptr, &o, s);
     };
-    auto fanout = [&](uint64_t* masks) {
-        return probe_scenarios_fanout(p, rng, stream_id, path_begin, n_paths, working_months, scenarios, n_scenarios, counts, main, masks);
+    auto fanout = [&](uint64_t* masks, const mcr_option_outcomes* fan_rows) {
+        return probe_scenarios_fanout(p, rng, stream_id, path_begin, n_paths, working_months, scenarios, n_scenarios, counts, main, masks, fan_rows);
     };
-    return run_probe_routes(device, main, n_scenarios, n_paths, jo, fanout, launch_scenario);
+    return run_probe_routes(device, main, n_scenarios, n_paths, jo, rows, fanout, launch_scenario);
 }
 
 int mcr_probe_scenarios_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
                             uint64_t n_paths, int32_t working_months, const mcr_scenario* scenarios,
                             int32_t n_scenarios, uint64_t* counts, int device, void* hip_stream) {
     MCR_ENTER_DEVICE(device);
-    return probe_scenarios(p, rng, stream_id, path_begin, n_paths, working_months, scenarios, n_scenarios, counts, nullptr, device,
+    return probe_scenarios(p, rng, stream_id, path_begin, n_paths, working_months, scenarios, n_scenarios, counts, nullptr, nullptr, device,
                            (hipStream_t)hip_stream);
 }
 
@@ -3152,14 +3249,24 @@ int mcr_probe_scenarios_joint_rng(const mcr_params* p, const mcr_rng* rng, uint3
     if (int rc = check_joint_args(n_scenarios, joint)) return rc;
     MCR_ENTER_DEVICE(device);
     const JointOut jo{masks, joint, extremes};
-    return probe_scenarios(p, rng, stream_id, path_begin, n_paths, working_months, scenarios, n_scenarios, counts, &jo, device,
+    return probe_scenarios(p, rng, stream_id, path_begin, n_paths, working_months, scenarios, n_scenarios, counts, &jo, nullptr, device,
                            (hipStream_t)hip_stream);
 }
 
-// mcr_probe_assumptions_rng (jo == nullptr) and mcr_probe_assumptions_joint_rng, on the entered device
+int mcr_probe_scenarios_outcomes_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                     uint64_t n_paths, int32_t working_months, const mcr_scenario* scenarios,
+                                     int32_t n_scenarios, uint64_t* counts, const mcr_option_outcomes* rows, int device, void* hip_stream) {
+    if (int rc = check_outcome_args(&rows, n_paths)) return rc;
+    MCR_ENTER_DEVICE(device);
+    return probe_scenarios(p, rng, stream_id, path_begin, n_paths, working_months, scenarios, n_scenarios, counts, nullptr, rows, device,
+                           (hipStream_t)hip_stream);
+}
+
+// mcr_probe_assumptions_rng (jo == nullptr, rows == nullptr), mcr_probe_assumptions_joint_rng and
+// mcr_probe_assumptions_outcomes_rng, on the entered device
 static int probe_assumptions(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
                              int32_t working_months, const mcr_assumptions* records, int32_t n_records, uint64_t* counts,
-                             const JointOut* jo, int device, hipStream_t main) {
+                             const JointOut* jo, const mcr_option_outcomes* rows, int device, hipStream_t main) {
     g_last_assumption_fanout_launches = 0;
     if (n_records < 0) { set_error("n_records %d must be >= 0", n_records); return MCR_ERR_INVALID_ARG; }
     if (n_records == 0) return MCR_OK;
@@ -3204,27 +3311,27 @@ static int probe_assumptions(const mcr_params* p, const mcr_rng* rng, uint32_t s
     rc = zero_counters(counts, (size_t)n_records, main);
     if (rc != MCR_OK) return rc;
     mcr_params q = *p;
-    auto launch_record = [&](int k, hipStream_t s, uint8_t* success) {
+    auto launch_record = [&](int k, hipStream_t s, uint8_t* success, double* final_balance, double* years_to_ruin) {
         const mcr_assumptions& r = records[k];
         q.initial_balance = r.initial_balance; q.monthly_contribution = r.monthly_contribution; q.monthly_expenses = r.monthly_expenses;
         q.inv1_mu_log = r.inv1_mu_log; q.inv1_sigma_log = r.inv1_sigma_log;
         q.inf_mu_log = r.inf_mu_log; q.inf_sigma_log = r.inf_sigma_log;
         q.prem_mu_log = r.prem_mu_log; q.prem_sigma_log = r.prem_sigma_log;
         q.equity_inflation_rho = r.equity_inflation_rho;
-        const mcr_outputs o = counters_and_success(counts + (size_t)k * MCR_N_COUNTERS, success);
+        const mcr_outputs o = counters_and_columns(counts + (size_t)k * MCR_N_COUNTERS, success, final_balance, years_to_ruin);
         return launch_paths(&q, rng, stream_id, path_begin, n_paths, working_months, nullptr, &o, s);
     };
-    auto fanout = [&](uint64_t* masks) {
-        return probe_assumptions_fanout(p, rng, stream_id, path_begin, n_paths, working_months, records, n_records, counts, main, masks);
+    auto fanout = [&](uint64_t* masks, const mcr_option_outcomes* fan_rows) {
+        return probe_assumptions_fanout(p, rng, stream_id, path_begin, n_paths, working_months, records, n_records, counts, main, masks, fan_rows);
     };
-    return run_probe_routes(device, main, n_records, n_paths, jo, fanout, launch_record);
+    return run_probe_routes(device, main, n_records, n_paths, jo, rows, fanout, launch_record);
 }
 
 int mcr_probe_assumptions_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
                               uint64_t n_paths, int32_t working_months, const mcr_assumptions* records,
                               int32_t n_records, uint64_t* counts, int device, void* hip_stream) {
     MCR_ENTER_DEVICE(device);
-    return probe_assumptions(p, rng, stream_id, path_begin, n_paths, working_months, records, n_records, counts, nullptr, device,
+    return probe_assumptions(p, rng, stream_id, path_begin, n_paths, working_months, records, n_records, counts, nullptr, nullptr, device,
                              (hipStream_t)hip_stream);
 }
 
@@ -3235,16 +3342,26 @@ int mcr_probe_assumptions_joint_rng(const mcr_params* p, const mcr_rng* rng, uin
     if (int rc = check_joint_args(n_records, joint)) return rc;
     MCR_ENTER_DEVICE(device);
     const JointOut jo{masks, joint, extremes};
-    return probe_assumptions(p, rng, stream_id, path_begin, n_paths, working_months, records, n_records, counts, &jo, device,
+    return probe_assumptions(p, rng, stream_id, path_begin, n_paths, working_months, records, n_records, counts, &jo, nullptr, device,
+                             (hipStream_t)hip_stream);
+}
+
+int mcr_probe_assumptions_outcomes_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                       uint64_t n_paths, int32_t working_months, const mcr_assumptions* records,
+                                       int32_t n_records, uint64_t* counts, const mcr_option_outcomes* rows, int device, void* hip_stream) {
+    if (int rc = check_outcome_args(&rows, n_paths)) return rc;
+    MCR_ENTER_DEVICE(device);
+    return probe_assumptions(p, rng, stream_id, path_begin, n_paths, working_months, records, n_records, counts, nullptr, rows, device,
                              (hipStream_t)hip_stream);
 }
 
 int mcr_probe_assumptions_last_fanout_launches(void) { return g_last_assumption_fanout_launches; }
 
-// mcr_probe_income_rng (jo == nullptr) and mcr_probe_income_joint_rng, on the entered device
+// mcr_probe_income_rng (jo == nullptr, rows == nullptr), mcr_probe_income_joint_rng and mcr_probe_income_outcomes_rng, on the
+// entered device
 static int probe_income(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
                         int32_t working_months, int32_t stream_index, const mcr_income_option* options, int32_t n_options,
-                        uint64_t* counts, const JointOut* jo, int device, hipStream_t main) {
+                        uint64_t* counts, const JointOut* jo, const mcr_option_outcomes* rows, int device, hipStream_t main) {
     g_last_income_fanout_launches = 0;
     if (n_options < 0) { set_error("n_options %d must be >= 0", n_options); return MCR_ERR_INVALID_ARG; }
     if (n_options == 0) return MCR_OK;
@@ -3296,17 +3413,17 @@ static int probe_income(const mcr_params* p, const mcr_rng* rng, uint32_t stream
         q.extra_streams = q_extra.data();
     }
     mcr_stream& qs = stream_index < MCR_INLINE_STREAMS ? q.streams[stream_index] : q_extra[(size_t)(stream_index - MCR_INLINE_STREAMS)];
-    auto launch_option = [&](int k, hipStream_t s, uint8_t* success) {
+    auto launch_option = [&](int k, hipStream_t s, uint8_t* success, double* final_balance, double* years_to_ruin) {
         const mcr_income_option& r = options[k];
         q.initial_balance = r.initial_balance; q.monthly_contribution = r.monthly_contribution; q.monthly_expenses = r.monthly_expenses;
         qs.monthly_amount_today = r.monthly_amount_today; qs.start_at_age = r.start_at_age; qs.duration_years = r.duration_years;
-        const mcr_outputs o = counters_and_success(counts + (size_t)k * MCR_N_COUNTERS, success);
+        const mcr_outputs o = counters_and_columns(counts + (size_t)k * MCR_N_COUNTERS, success, final_balance, years_to_ruin);
         return launch_paths(&q, rng, stream_id, path_begin, n_paths, working_months, nullptr, &o, s);
     };
-    auto fanout = [&](uint64_t* masks) {
-        return probe_income_fanout(p, rng, stream_id, path_begin, n_paths, working_months, stream_index, options, n_options, counts, main, masks);
+    auto fanout = [&](uint64_t* masks, const mcr_option_outcomes* fan_rows) {
+        return probe_income_fanout(p, rng, stream_id, path_begin, n_paths, working_months, stream_index, options, n_options, counts, main, masks, fan_rows);
     };
-    return run_probe_routes(device, main, n_options, n_paths, jo, fanout, launch_option);
+    return run_probe_routes(device, main, n_options, n_paths, jo, rows, fanout, launch_option);
 }
 
 int mcr_probe_income_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
@@ -3314,7 +3431,7 @@ int mcr_probe_income_rng(const mcr_params* p, const mcr_rng* rng, uint32_t strea
                          const mcr_income_option* options, int32_t n_options,
                          uint64_t* counts, int device, void* hip_stream) {
     MCR_ENTER_DEVICE(device);
-    return probe_income(p, rng, stream_id, path_begin, n_paths, working_months, stream_index, options, n_options, counts, nullptr, device,
+    return probe_income(p, rng, stream_id, path_begin, n_paths, working_months, stream_index, options, n_options, counts, nullptr, nullptr, device,
                         (hipStream_t)hip_stream);
 }
 
@@ -3325,8 +3442,18 @@ int mcr_probe_income_joint_rng(const mcr_params* p, const mcr_rng* rng, uint32_t
     if (int rc = check_joint_args(n_options, joint)) return rc;
     MCR_ENTER_DEVICE(device);
     const JointOut jo{masks, joint, extremes};
-    return probe_income(p, rng, stream_id, path_begin, n_paths, working_months, stream_index, options, n_options, counts, &jo, device,
+    return probe_income(p, rng, stream_id, path_begin, n_paths, working_months, stream_index, options, n_options, counts, &jo, nullptr, device,
                         (hipStream_t)hip_stream);
+}
+
+int mcr_probe_income_outcomes_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                  uint64_t n_paths, int32_t working_months, int32_t stream_index,
+                                  const mcr_income_option* options, int32_t n_options,
+                                  uint64_t* counts, const mcr_option_outcomes* rows, int device, void* hip_stream) {
+    if (int rc = check_outcome_args(&rows, n_paths)) return rc;
+    MCR_ENTER_DEVICE(device);
+    return probe_income(p, rng, stream_id, path_begin, n_paths, working_months, stream_index, options, n_options, counts, nullptr, rows,
+                        device, (hipStream_t)hip_stream);
 }
 
 int mcr_probe_income_last_fanout_launches(void) { return g_last_income_fanout_launches; }

@@ -117,4 +117,7 @@ int launch_pack_success(const uint8_t* success, uint64_t n_paths, uint64_t* row,
 // joint_counts_kernel: zeroes joint [n][n] and extremes [2] (may be null), then counts the rows (n_paths == 0: zeroes alone)
 int launch_joint_counts(const uint64_t* masks, int n, uint64_t n_paths, uint64_t* joint, uint64_t* extremes, hipStream_t stream);
 
+// Outcome probes (mcr_aggregate.hip), per-option route: final_balance[i] = NaN where years_to_ruin[i] is a number (the path failed)
+int launch_nan_failed(double* final_balance, const double* years_to_ruin, uint64_t n_paths, hipStream_t stream);
+
 }  // namespace mcr

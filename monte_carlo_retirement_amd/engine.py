@@ -17,7 +17,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from . import _native as N
-from ._native import McrAssumptions, McrIncomeOption, McrOutputs, McrParams, McrRng, McrScenario, McrSizes, McrYearBins
+from ._native import McrAssumptions, McrIncomeOption, McrOptionOutcomes, McrOutputs, McrParams, McrRng, McrScenario, McrSizes, McrYearBins
 
 SUMMARY_FIELDS = (
     "start_balance",
@@ -610,16 +610,37 @@ def _assumption_records(records):
 
 
 def _probe_records(symbol: str, params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
-                   record_args, n: int, device: int, joint: bool = False, masks=True):
+                   record_args, n: int, device: int, joint: bool = False, masks=True, outcomes=None):
     """The body of the record probes: `symbol` is the library entry, `record_args` what it takes between `working_months` and
     the record count.  Plain: returns `counts`.  `joint`: the ``*_joint_rng`` entry; returns ``(counts, joint, extremes,
-    masks)`` (`masks` falsy: the library keeps them in scratch of its own and None is returned in their place)."""
+    masks)`` (`masks` falsy: the library keeps them in scratch of its own and None is returned in their place).  `outcomes`:
+    the ``*_outcomes_rng`` entry; ``(final_balance, years_to_ruin, path_stride)`` with each row argument True (allocate),
+    falsy (not requested) or a float64 device tensor ``[n, path_stride]`` to write into; returns ``(counts, final_rows,
+    ruin_rows)``."""
     import torch
 
     N.require_device()
     dev = torch.device("cuda", int(device))
     counts = torch.empty((n, N.MCR_N_COUNTERS), dtype=torch.int64, device=dev)
     outs = []
+    if outcomes is not None:
+        want_final, want_ruin, stride = outcomes
+        stride = (int(n_paths) + 63) // 64 * 64 if stride is None else int(stride)
+
+        def row_slab(want):
+            if want is None or want is False:
+                return None
+            if want is True:
+                return torch.empty((n, stride), dtype=torch.float64, device=dev)
+            if not (torch.is_tensor(want) and want.is_cuda and want.dtype == torch.float64 and want.is_contiguous()
+                    and tuple(want.shape) == (n, stride)):
+                raise ValueError(f"a row slab must be a contiguous float64 device tensor of shape ({n}, {stride})")
+            return want
+
+        fin, ruin = row_slab(want_final), row_slab(want_ruin)
+        rows = McrOptionOutcomes(fin.data_ptr() if fin is not None and fin.numel() else None,
+                                 ruin.data_ptr() if ruin is not None and ruin.numel() else None, stride)
+        outs = [C.byref(rows)]
     if joint:
         if n > N.MCR_MAX_JOINT_OPTIONS:
             raise ValueError(f"a joint probe takes at most MCR_MAX_JOINT_OPTIONS = {N.MCR_MAX_JOINT_OPTIONS} options, got {n}")
@@ -636,6 +657,8 @@ def _probe_records(symbol: str, params: McrParams, seed, stream_id: int, path_be
             n, counts.data_ptr(), *outs, int(device), C.c_void_p(stream),
         )
         N.check(rc, symbol)
+    if outcomes is not None:
+        return counts, fin, ruin
     return (counts, jm, ex, mk) if joint else counts
 
 
@@ -710,6 +733,69 @@ def probe_assumptions_joint(params: McrParams, seed, stream_id: int, path_begin:
     arr, n = _assumption_records(records)
     return _probe_records("mcr_probe_assumptions_joint_rng", params, seed, stream_id, path_begin, n_paths, working_months, (arr,), n,
                           device, joint=True, masks=masks)
+
+
+def probe_scenarios_outcomes(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
+                             scenarios, device: int = 0, final_balance=True, years_to_ruin=True, path_stride: Optional[int] = None):
+    """`probe_scenarios` plus the per-path outcomes of its scenarios (``mcr_probe_scenarios_outcomes_rng``).  Returns device
+    tensors ``(counts, final_rows, ruin_rows)``: `counts` as the plain probe's; the rows are float64 ``[n, path_stride]``
+    (default stride: `n_paths` rounded up to 64; columns at or beyond `n_paths` are never written): ``final_rows[k]`` = the final
+    balance of the paths that succeed under scenario k, NaN elsewhere; ``ruin_rows[k]`` = YearsToRuin, NaN on success -- bit
+    for bit the columns of a summary batch with scenario k's fields.  ``final_balance`` / ``years_to_ruin``: True, falsy (not
+    requested: None comes back) or a tensor to write into.  Asynchronous (reading a tensor synchronises)."""
+    arr, n = _scenario_records(scenarios)
+    return _probe_records("mcr_probe_scenarios_outcomes_rng", params, seed, stream_id, path_begin, n_paths, working_months, (arr,), n,
+                          device, outcomes=(final_balance, years_to_ruin, path_stride))
+
+
+def probe_income_outcomes(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
+                          stream_index: int, options, device: int = 0, final_balance=True, years_to_ruin=True,
+                          path_stride: Optional[int] = None):
+    """`probe_income` plus the per-path outcomes of its options (``mcr_probe_income_outcomes_rng``); returns ``(counts,
+    final_rows, ruin_rows)`` as `probe_scenarios_outcomes`."""
+    arr, n = _income_records(options)
+    return _probe_records("mcr_probe_income_outcomes_rng", params, seed, stream_id, path_begin, n_paths, working_months,
+                          (int(stream_index), arr), n, device, outcomes=(final_balance, years_to_ruin, path_stride))
+
+
+def probe_assumptions_outcomes(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
+                               records, device: int = 0, final_balance=True, years_to_ruin=True, path_stride: Optional[int] = None):
+    """`probe_assumptions` plus the per-path outcomes of its records (``mcr_probe_assumptions_outcomes_rng``); returns
+    ``(counts, final_rows, ruin_rows)`` as `probe_scenarios_outcomes`."""
+    arr, n = _assumption_records(records)
+    return _probe_records("mcr_probe_assumptions_outcomes_rng", params, seed, stream_id, path_begin, n_paths, working_months, (arr,), n,
+                          device, outcomes=(final_balance, years_to_ruin, path_stride))
+
+
+def ruin_month_counts(ruin_rows, n_paths: int, retirement_years: int, into=None, device: Optional[int] = None):
+    """Ruin-month counts of YearsToRuin rows (``mcr_ruin_month_counts``): `ruin_rows` is a float64 device tensor ``[n, stride]``
+    with ``stride >= n_paths`` (the ``ruin_rows`` of an outcomes probe).  Returns a device int64 tensor ``[n, 12 *
+    retirement_years + 1]``: cell ``[k, m]`` = the paths of row k ruined in month m (``rint(12 * years_to_ruin) == m``; NaN =
+    never).  `into`: a table of that shape to accumulate into (several path ranges, one table).  Asynchronous."""
+    import torch
+
+    N.require_device()
+    if not (torch.is_tensor(ruin_rows) and ruin_rows.is_cuda and ruin_rows.dtype == torch.float64 and ruin_rows.dim() == 2):
+        raise ValueError("ruin_rows must be a 2-d float64 device tensor")
+    if ruin_rows.stride(1) != 1 and ruin_rows.numel():
+        raise ValueError("the columns of ruin_rows must be contiguous")
+    n, cells = int(ruin_rows.shape[0]), 12 * int(retirement_years) + 1
+    if int(retirement_years) < 1:
+        raise ValueError("retirement_years must be >= 1")
+    if int(ruin_rows.shape[1]) < int(n_paths):
+        raise ValueError(f"ruin_rows has {int(ruin_rows.shape[1])} columns for {int(n_paths)} paths")
+    device = ruin_rows.device.index if device is None else int(device)
+    if into is None:
+        into = torch.zeros((n, cells), dtype=torch.int64, device=ruin_rows.device)
+    elif not (into.is_cuda and into.dtype == torch.int64 and into.is_contiguous() and tuple(into.shape) == (n, cells)):
+        raise ValueError(f"`into` must be a contiguous int64 device tensor of shape ({n}, {cells})")
+    if n and int(n_paths):
+        stream = torch.cuda.current_stream(device).cuda_stream
+        row_stride = int(ruin_rows.stride(0)) if n > 1 else max(int(ruin_rows.shape[1]), int(n_paths))
+        rc = N.load_library().mcr_ruin_month_counts(ruin_rows.data_ptr(), row_stride, n, int(n_paths), int(retirement_years),
+                                                    into.data_ptr(), device, C.c_void_p(stream))
+        N.check(rc, "mcr_ruin_month_counts")
+    return into
 
 
 def joint_counts(masks, n_paths: int, device: Optional[int] = None):

@@ -830,6 +830,47 @@ class RetirementMonteCarloSimulator:
         flat = D.probe_candidates([0], n, 0, probe, width=k * k + 2)[0]
         return JointOutcomes(flat[:k * k].reshape(k, k), n, (int(flat[k * k]), int(flat[k * k + 1])))
 
+    def _option_outcomes(self, outcomes_probe, n_records: int, working_months: int, num_simulations: Optional[int], quantiles):
+        """The body of the `option_outcomes_by_*` methods: ``outcomes_probe(path_begin, count) -> (counts, final_rows,
+        ruin_rows)`` is an `engine.probe_*_outcomes` call over ALL the records.  Under a process group the batch is sharded
+        by PATH RANGE as `_joint_outcomes` shards it: the success counts and the ruin-month counts (``k (12 ry + 2)``
+        integers) are summed in one all-reduce, the final-balance quantiles of the successful cohorts come from the
+        distributed radix select (`distributed.sharded_row_quantiles`); the rows stay on their rank and every rank returns
+        the same `outcomes.OptionOutcomes`."""
+        import torch
+
+        from .outcomes import OptionOutcomes
+
+        k = int(n_records)
+        n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
+        ry = int(self.params_model.retirement_years)
+        cells = 12 * ry + 1
+        qs = tuple(float(q) for q in quantiles)
+        if any(not (0.0 <= q <= 1.0) for q in qs):
+            raise ValueError(f"quantiles must lie in [0, 1], got {qs}")
+        age = retirement_age(self.params_model.current_age, int(working_months))
+        if k == 0:
+            return OptionOutcomes(np.zeros(0, dtype=np.int64), n, np.zeros((0, cells), dtype=np.int64), qs,
+                                  np.zeros((0, len(qs))), np.zeros(0, dtype=np.int64), age)
+        local = {}
+
+        def probe(path_begin, count, _):
+            counts, final_rows, ruin_rows = outcomes_probe(path_begin, count)
+            local["rows"], local["n"] = final_rows, int(count)
+            months = E.ruin_month_counts(ruin_rows, count, ry)
+            return torch.cat([counts[:, N.MCR_CTR_SUCCESS].reshape(-1), months.reshape(-1)])
+
+        flat = D.probe_candidates([0], n, 0, probe, width=k + k * cells)[0]
+        successes, months = flat[:k], flat[k:].reshape(k, cells)
+        final_q, cohort = np.full((k, len(qs)), np.nan), successes.copy()
+        if qs and n > 0:
+            rows = local.get("rows")
+            if rows is None or local["n"] == 0:      # (a rank whose shard of the path range is empty still takes part in the selection)
+                dev = torch.device("cuda", self._local_device())
+                rows, local["n"] = torch.full((k, 64), float("nan"), dtype=torch.float64, device=dev), 0
+            final_q, cohort = D.sharded_row_quantiles(rows, local["n"], qs)
+        return OptionOutcomes(successes, n, months, qs, final_q, cohort, age)
+
     def success_probability_by_expenses(self, working_months: int, monthly_expenses: Sequence[float],
                                         num_simulations: Optional[int] = None) -> np.ndarray:
         """Success % of each ``monthly_expenses`` level at ``working_months``, over the active seed stream's batch of
@@ -975,6 +1016,25 @@ class RetirementMonteCarloSimulator:
 
         return self._joint_outcomes(probe, len(records), n)
 
+    def option_outcomes_by_scenarios(self, working_months: int, scenarios: Sequence[dict], num_simulations: Optional[int] = None,
+                                     quantiles: Sequence[float] = (0.05, 0.25, 0.5, 0.75, 0.95)):
+        """The per-option outcomes of the scenarios of `success_probability_by_scenarios` (same arguments and validation)
+        over their shared paths, from the scenario outcomes probe (``mcr_probe_scenarios_outcomes_rng``): an
+        `outcomes.OptionOutcomes` -- ruin-month counts, the `quantiles` of the successful cohort's final balance --
+        whose ``.probabilities`` equal that method's array bit for bit."""
+        from .nestegg import scenario_records
+
+        p = self.params_model
+        records = scenario_records(scenarios, (p.initial_balance, p.monthly_contribution, p.monthly_expenses))
+        n = int(p.num_simulations_main if num_simulations is None else num_simulations)
+        wm = int(working_months)
+        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
+
+        def probe(path_begin, count):
+            return E.probe_scenarios_outcomes(params, rng, self._stream_id, path_begin, count, wm, records, device=dev)
+
+        return self._option_outcomes(probe, len(records), wm, n, quantiles)
+
     def find_minimum_initial_balance(
         self,
         working_months: int,
@@ -1094,8 +1154,28 @@ class RetirementMonteCarloSimulator:
 
         return self._joint_outcomes(probe, len(records), n)
 
+    def option_outcomes_by_income_options(self, working_months: int, stream, options: Sequence[dict],
+                                          num_simulations: Optional[int] = None,
+                                          quantiles: Sequence[float] = (0.05, 0.25, 0.5, 0.75, 0.95)):
+        """The per-option outcomes of the options of `success_probability_by_income_options` (same arguments and
+        validation) over their shared paths, from the income outcomes probe (``mcr_probe_income_outcomes_rng``): an
+        `outcomes.OptionOutcomes` whose ``.probabilities`` equal that method's array bit for bit."""
+        from .income import income_options, stream_index
+
+        p = self.params_model
+        index = stream_index(p, stream)
+        records = income_options(p, index, options)
+        n = int(p.num_simulations_main if num_simulations is None else num_simulations)
+        wm = int(working_months)
+        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
+
+        def probe(path_begin, count):
+            return E.probe_income_outcomes(params, rng, self._stream_id, path_begin, count, wm, index, records, device=dev)
+
+        return self._option_outcomes(probe, len(records), wm, n, quantiles)
+
     def compare_claiming_options(self, working_months: int, stream, options: Sequence[dict],
-                                 num_simulations: Optional[int] = None, paired: bool = False) -> dict:
+                                 num_simulations: Optional[int] = None, paired: bool = False, outcomes: bool = False) -> dict:
         """The claim-age table and the annuity comparison: `success_probability_by_income_options` of ``options`` as
         ``{"stream": list index, "options": [{the six fields, "probability"}, ...], "best": index}``, ``best`` being the
         option with the highest probability (the first of equals).
@@ -1104,22 +1184,32 @@ class RetirementMonteCarloSimulator:
         probabilities), every row gains ``"vs_best"`` = `JointOutcomes.difference` of the best option against the row
         (``delta``, paired ``se``, ``se_unpaired``, McNemar ``p_value``, ``rescued``), and the document gains
         ``"tied_with_best"`` (the rows the paired test cannot tell from the best at 5 %) and ``"all_succeed"`` /
-        ``"none_succeed"``, the paths on which every option works and on which none does."""
+        ``"none_succeed"``, the paths on which every option works and on which none does.
+
+        ``outcomes=True`` says when it goes wrong and what is left: `option_outcomes_by_income_options` over the same paths
+        (the same probabilities) adds to every row ``"lasts_until_age"`` = ``{"90", "95", "99"}`` (the age the money lasts
+        to with that confidence; None = the whole horizon), ``"median_ruin_age"`` (among the failing paths; None without
+        any) and ``"final_balance"`` = ``{"p5", "p25", "p50", "p75", "p95"}`` of the successful paths' nominal final
+        balance (None values for an empty cohort).  Composes with ``paired``."""
         from .income import INCOME_OPTION_FIELDS, income_options, stream_index
 
         index = stream_index(self.params_model, stream)
         records = income_options(self.params_model, index, options)
-        outcomes = self.joint_outcomes_by_income_options(working_months, index, options, num_simulations) if paired else None
-        probs = (outcomes.probabilities if paired else
+        joint = self.joint_outcomes_by_income_options(working_months, index, options, num_simulations) if paired else None
+        per_option = self.option_outcomes_by_income_options(working_months, index, options, num_simulations) if outcomes else None
+        probs = (joint.probabilities if paired else per_option.probabilities if outcomes else
                  self.success_probability_by_income_options(working_months, index, options, num_simulations))
         rows = [dict(zip(INCOME_OPTION_FIELDS, r), probability=float(pr)) for r, pr in zip(records, probs)]
         best = max(range(len(rows)), key=lambda i: (rows[i]["probability"], -i)) if rows else None
         doc = {"stream": index, "options": rows, "best": best}
         if paired:
             for i, row in enumerate(rows):
-                row["vs_best"] = outcomes.difference(best, i)
-            doc["tied_with_best"] = outcomes.indistinguishable_from(best) if rows else []
-            doc["all_succeed"], doc["none_succeed"] = outcomes.all_succeed, outcomes.none_succeed
+                row["vs_best"] = joint.difference(best, i)
+            doc["tied_with_best"] = joint.indistinguishable_from(best) if rows else []
+            doc["all_succeed"], doc["none_succeed"] = joint.all_succeed, joint.none_succeed
+        if outcomes:
+            for i, row in enumerate(rows):
+                row.update(per_option.row(i))
         return doc
 
     _UNCHANGED = object()   # (find_minimum_income_amount: "the stream's own duration_years", which may itself be None)
@@ -1218,8 +1308,26 @@ class RetirementMonteCarloSimulator:
 
         return self._joint_outcomes(probe, len(records), n)
 
+    def option_outcomes_by_assumptions(self, working_months: int, scenarios: Sequence[dict], num_simulations: Optional[int] = None,
+                                       quantiles: Sequence[float] = (0.05, 0.25, 0.5, 0.75, 0.95)):
+        """The per-option outcomes of the records of `success_probability_by_assumptions` (same arguments and validation)
+        over their shared paths, from the assumption outcomes probe (``mcr_probe_assumptions_outcomes_rng``): an
+        `outcomes.OptionOutcomes` whose ``.probabilities`` equal that method's array bit for bit."""
+        from .stress import assumption_records
+
+        p = self.params_model
+        records = assumption_records(p, scenarios)
+        n = int(p.num_simulations_main if num_simulations is None else num_simulations)
+        wm = int(working_months)
+        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
+
+        def probe(path_begin, count):
+            return E.probe_assumptions_outcomes(params, rng, self._stream_id, path_begin, count, wm, records, device=dev)
+
+        return self._option_outcomes(probe, len(records), wm, n, quantiles)
+
     def stress_test(self, working_months: int, shifts: Optional[Sequence[Tuple[str, dict]]] = None,
-                    num_simulations: Optional[int] = None, paired: bool = False) -> List[Dict[str, object]]:
+                    num_simulations: Optional[int] = None, paired: bool = False, outcomes: bool = False) -> List[Dict[str, object]]:
         """The stress table at ``working_months``: ONE `success_probability_by_assumptions` call over the base case and one
         row per shift (default `stress.DEFAULT_SHIFTS`: 14 one-at-a-time additive shifts of the market's means,
         volatilities and correlation, i.e. 15 records, one launch).  ``shifts`` replaces the table with ``[(label, {field:
@@ -1229,20 +1337,29 @@ class RetirementMonteCarloSimulator:
 
         ``paired=True``: the table comes from `joint_outcomes_by_assumptions` (the same probabilities) and every row gains
         ``"vs_base"`` = `JointOutcomes.difference` of the base row against it plus ``hurt`` (paths that succeed under the
-        base and fail under the shift) and ``helped`` (the reverse)."""
+        base and fail under the shift) and ``helped`` (the reverse).
+
+        ``outcomes=True``: `option_outcomes_by_assumptions` over the same paths (the same probabilities) adds
+        ``"lasts_until_age"``, ``"median_ruin_age"`` and ``"final_balance"`` to every row, as in
+        `compare_claiming_options`.  Composes with ``paired``."""
         from .stress import stress_scenarios
 
         rows = stress_scenarios(self.params_model, shifts)
         records = [o for _, o in rows]
-        outcomes = self.joint_outcomes_by_assumptions(working_months, records, num_simulations) if paired else None
-        probs = outcomes.probabilities if paired else self.success_probability_by_assumptions(working_months, records, num_simulations)
+        joint = self.joint_outcomes_by_assumptions(working_months, records, num_simulations) if paired else None
+        per_option = self.option_outcomes_by_assumptions(working_months, records, num_simulations) if outcomes else None
+        probs = (joint.probabilities if paired else per_option.probabilities if outcomes else
+                 self.success_probability_by_assumptions(working_months, records, num_simulations))
         base = float(probs[0])
         table = [{"label": label, "overrides": dict(o), "probability": float(pr), "delta": float(pr) - base}
                  for (label, o), pr in zip(rows, probs)]
         if paired:
             for i, row in enumerate(table):
-                t = outcomes.pair(0, i)
-                row["vs_base"] = dict(outcomes.difference(0, i), hurt=t["only_a"], helped=t["only_b"])
+                t = joint.pair(0, i)
+                row["vs_base"] = dict(joint.difference(0, i), hurt=t["only_a"], helped=t["only_b"])
+        if outcomes:
+            for i, row in enumerate(table):
+                row.update(per_option.row(i))
         return table
 
     def find_breakeven_assumption(
