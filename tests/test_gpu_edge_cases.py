@@ -272,6 +272,21 @@ def test_very_large_batches_use_64bit_addressing(oracle):
     assert tq.shape == (b.sizes.trajectory_len, 7) and np.all(np.diff(tq, axis=1) >= 0)
     assert wc[0] == n and np.all(np.diff(wc) <= 0)
     assert tq[0].tolist() == [cfgd["initial_balance"]] * 7
+    # three rows of that slab against pandas, bit for bit: real data at n > 2^24 (10-bit sub-histograms), with the giant
+    # tie at 0 that ruined paths leave in the last trajectory row and the NaNs of the last withdrawal-rate row.  (Each
+    # row goes to the host as ONE contiguous 1-D copy of n elements: LABNOTES.md, rounds 1-3 section 11.)
+    import pandas as pd
+
+    for what, row, band, qs, count in (
+            ("trajectory row 0", b.trajectory[0], tq[0], A.TRAJECTORY_QUANTILES, None),
+            ("last trajectory row", b.trajectory[b.sizes.trajectory_len - 1], tq[-1], A.TRAJECTORY_QUANTILES, None),
+            ("last withdrawal-rate row", b.withdrawal_rate_trajectory[b.withdrawal_rate_trajectory.shape[0] - 1], wq[-1], A.WR_QUANTILES, wc[-1])):
+        host = row[:n].cpu().numpy()
+        exp = pd.DataFrame(host[:, None]).quantile(list(qs), axis=0).to_numpy()[:, 0]
+        assert np.array_equal(band, exp, equal_nan=True), (what, band.tolist(), exp.tolist())
+        if count is not None:
+            assert int(count) == int((~np.isnan(host)).sum()), what
+        del host
     # the 100-bin histogram of successful final balances accounts for every successful path
     bins, edges = A.success_histogram(b.summary["final_balance"], b.success, 100)
     assert int(bins.sum()) == int(b.counters[0].item()) and len(edges) == 101 and np.all(np.diff(edges) > 0)
