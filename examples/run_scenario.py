@@ -18,9 +18,15 @@ switch to the final seed stream, run the final batch, print the response documen
     python examples/run_scenario.py scenarios/config.json --working-months 240 --breakeven inv1_returns_mean,inflation_rate_mean
     python examples/run_scenario.py scenarios/config.json --frontier 180,240,300
     python examples/run_scenario.py scenarios/config.json --grid-months 180,240 --grid-expenses 3000,4000,5000
+    python examples/run_scenario.py scenarios/config.json --history record.csv --history-block 12 [--history-as-recorded]
 
 `--rng numpy` uses the reference's own NumPy stream (same seed -> the reference's numbers); `--rng philox`
-(default) the engine's counter-based stream.  `--compact` assembles the document from device-side aggregates
+(default) the engine's counter-based stream.  `--history FILE.csv` asks every question of a recorded market instead: months
+resampled in blocks of `--history-block` (default 12) from the file's columns `equity`, `inflation` and `inv2` (simple monthly
+returns, one row per month, oldest first; `premium` instead of `inv2` when the file holds the premium over inflation) — the
+record's sequence of surprises around the config's own means and volatilities, or, with `--history-as-recorded`, around the
+record's own fitted ones: the history as it was.  The response document then carries a `market` key (months, block_months,
+as_recorded, the fitted values), and so does every other object this script prints.  `--compact` assembles the document from device-side aggregates
 only (no per-path lists: for batches far beyond the UI's); `--streamed` from yearly bins taken inside the path kernel (no
 memory per path at all: any number of paths, under `torchrun` too; bands are known to within one bin).  `--events` writes the progress events the SSE
 endpoint would stream to stderr, one JSON per line.  Without `--full` only the `summary` block (plus timings
@@ -72,6 +78,11 @@ def main() -> int:
     ap.add_argument("config")
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--rng", choices=["philox", "numpy"], default="philox")
+    ap.add_argument("--history", default=None, metavar="FILE.csv",
+                    help="resample months from this record (columns equity, inflation, inv2 | premium) instead of drawing them")
+    ap.add_argument("--history-block", type=int, default=12, help="--history: months per resampled block")
+    ap.add_argument("--history-as-recorded", action="store_true",
+                    help="--history: use the record's own fitted means and volatilities instead of the config's")
     ap.add_argument("--paths", type=int, default=None, help="override num_simulations_main")
     ap.add_argument("--search-paths", type=int, default=None, help="override num_simulations_search")
     ap.add_argument("--working-months", type=int, default=None, help="skip the search")
@@ -153,6 +164,21 @@ def main() -> int:
     if args.search_paths:
         raw["num_simulations_search"] = args.search_paths
     config = Config(**raw)
+    args.market_history = None
+    if args.history_as_recorded and not args.history:
+        ap.error("--history-as-recorded goes with --history")
+    if args.history:
+        if args.rng != "philox":
+            ap.error("--history is a random stream of its own: leave --rng out")
+        from monte_carlo_retirement_amd.history import MarketHistory, with_fitted_market
+
+        with open(args.history, "r", encoding="utf-8") as fh:
+            columns = [c.strip() for c in fh.readline().split(",")]
+        over = {"inv2": None, "premium": "premium"} if "premium" in columns and "inv2" not in columns else {}
+        args.market_history = MarketHistory.from_csv(args.history, block_months=args.history_block, **over)
+        args.rng = "history"
+        if args.history_as_recorded:
+            config = with_fitted_market(config, args.market_history)
 
     marks = {"t0": time.perf_counter()}
     seen = []
@@ -186,7 +212,8 @@ def main() -> int:
         ap.error("--compact and --streamed are two ways to build the document")
     builder = R.streamed_result if args.streamed else R.compact_result if args.compact else R.build_result
     doc = R.run_scenario(config, args.working_months, emit=emit, result_builder=builder,
-                         main_seed_override=args.seed, rng=args.rng)
+                         main_seed_override=args.seed, rng=args.rng,
+                         **({"market_history": args.market_history, "market_as_recorded": args.history_as_recorded} if args.market_history else {}))
     t_end = time.perf_counter()
     rc = 0
     if doc is None:
@@ -196,7 +223,7 @@ def main() -> int:
         out = doc
     else:
         out = {
-            "scenario": doc["scenario"], "rng": args.rng, "summary": doc["summary"],
+            "scenario": doc["scenario"], "rng": args.rng, "summary": doc["summary"], **({"market": doc["market"]} if "market" in doc else {}),
             "search_probes": seen.count("search_iter"),
             "trajectory_points": len(doc["trajectory"]["years"]),
             "sample_paths": len(doc["trajectory"]["sample_paths"]),
@@ -206,7 +233,7 @@ def main() -> int:
                         "final_run_and_document": round(t_end - marks.get("search_done", t_end), 3)},
         }
     if rank0:
-        print(json.dumps(out))
+        print(json.dumps(_with_market(args, out)))
     if world > 1:
         import torch.distributed as dist
 
@@ -216,10 +243,8 @@ def main() -> int:
 
 
 def max_expenses(args, config: Config, world: int, rank0: bool) -> int:
-    from monte_carlo_retirement_amd.simulation import RetirementMonteCarloSimulator
-
     t0 = time.perf_counter()
-    sim = RetirementMonteCarloSimulator(config, main_seed_override=args.seed, rng=args.rng)
+    sim = _simulator(args, config)
     wm = args.working_months
     searched = wm is None
     if searched:
@@ -239,7 +264,7 @@ def max_expenses(args, config: Config, world: int, rank0: bool) -> int:
             "seconds": round(time.perf_counter() - t0, 3),
         }
     if rank0:
-        print(json.dumps(out))
+        print(json.dumps(_with_market(args, out)))
     if world > 1:
         import torch.distributed as dist
 
@@ -249,10 +274,8 @@ def max_expenses(args, config: Config, world: int, rank0: bool) -> int:
 
 
 def stress(args, config: Config, world: int, rank0: bool) -> int:
-    from monte_carlo_retirement_amd.simulation import RetirementMonteCarloSimulator
-
     t0 = time.perf_counter()
-    sim = RetirementMonteCarloSimulator(config, main_seed_override=args.seed, rng=args.rng)
+    sim = _simulator(args, config)
     wm = args.working_months
     searched = wm is None
     if searched:
@@ -278,7 +301,7 @@ def stress(args, config: Config, world: int, rank0: bool) -> int:
                                          "levels_evaluated": len(curve)})
         out["seconds"] = round(time.perf_counter() - t0, 3)
     if rank0:
-        print(json.dumps(out))
+        print(json.dumps(_with_market(args, out)))
     if world > 1:
         import torch.distributed as dist
 
@@ -288,10 +311,8 @@ def stress(args, config: Config, world: int, rank0: bool) -> int:
 
 
 def min_contribution(args, config: Config, world: int, rank0: bool) -> int:
-    from monte_carlo_retirement_amd.simulation import RetirementMonteCarloSimulator
-
     t0 = time.perf_counter()
-    sim = RetirementMonteCarloSimulator(config, main_seed_override=args.seed, rng=args.rng)
+    sim = _simulator(args, config)
     events = []
     contribution, prob, curve = sim.find_minimum_monthly_contribution(args.working_months, verbose=False,
                                                                       progress_callback=events.append,
@@ -303,7 +324,7 @@ def min_contribution(args, config: Config, world: int, rank0: bool) -> int:
         "seconds": round(time.perf_counter() - t0, 3),
     }
     if rank0:
-        print(json.dumps(out))
+        print(json.dumps(_with_market(args, out)))
     if world > 1:
         import torch.distributed as dist
 
@@ -313,10 +334,8 @@ def min_contribution(args, config: Config, world: int, rank0: bool) -> int:
 
 
 def min_initial_balance(args, config: Config, world: int, rank0: bool) -> int:
-    from monte_carlo_retirement_amd.simulation import RetirementMonteCarloSimulator
-
     t0 = time.perf_counter()
-    sim = RetirementMonteCarloSimulator(config, main_seed_override=args.seed, rng=args.rng)
+    sim = _simulator(args, config)
     wm = 0 if args.working_months is None else int(args.working_months)   # (retire today)
     events = []
     if args.at_expenses:
@@ -342,7 +361,7 @@ def min_initial_balance(args, config: Config, world: int, rank0: bool) -> int:
                             "withdrawal_rate_pct": 1200.0 * e / b if b > 0 else None}
                            for e, (b, pr, _) in zip(levels, results)]
     if rank0:
-        print(json.dumps(out))
+        print(json.dumps(_with_market(args, out)))
     if world > 1:
         import torch.distributed as dist
 
@@ -362,10 +381,8 @@ def _stream_arg(text: str):
 
 
 def income_table(args, config: Config, world: int, rank0: bool) -> int:
-    from monte_carlo_retirement_amd.simulation import RetirementMonteCarloSimulator
-
     t0 = time.perf_counter()
-    sim = RetirementMonteCarloSimulator(config, main_seed_override=args.seed, rng=args.rng)
+    sim = _simulator(args, config)
     wm = 0 if args.working_months is None else int(args.working_months)
     ages = _csv(args.claim_ages, float) if args.claim_ages else None
     amounts = _csv(args.claim_amounts, float) if args.claim_amounts else None
@@ -380,7 +397,7 @@ def income_table(args, config: Config, world: int, rank0: bool) -> int:
     out = {"scenario": config.Nickname, "rng": args.rng, "working_months": wm, "num_simulations": int(config.num_simulations_main),
            "target_probability": config.target_probability, **table, "seconds": round(time.perf_counter() - t0, 3)}
     if rank0:
-        print(json.dumps(out))
+        print(json.dumps(_with_market(args, out)))
     if world > 1:
         import torch.distributed as dist
 
@@ -391,10 +408,8 @@ def income_table(args, config: Config, world: int, rank0: bool) -> int:
 
 def min_income(args, config: Config, world: int, rank0: bool) -> int:
     from monte_carlo_retirement_amd.income import stream_index
-    from monte_carlo_retirement_amd.simulation import RetirementMonteCarloSimulator
-
     t0 = time.perf_counter()
-    sim = RetirementMonteCarloSimulator(config, main_seed_override=args.seed, rng=args.rng)
+    sim = _simulator(args, config)
     wm = 0 if args.working_months is None else int(args.working_months)
     index = stream_index(config, _stream_arg(args.min_income))
     events = []
@@ -408,7 +423,7 @@ def min_income(args, config: Config, world: int, rank0: bool) -> int:
         "seconds": round(time.perf_counter() - t0, 3),
     }
     if rank0:
-        print(json.dumps(out))
+        print(json.dumps(_with_market(args, out)))
     if world > 1:
         import torch.distributed as dist
 
@@ -417,14 +432,27 @@ def min_income(args, config: Config, world: int, rank0: bool) -> int:
     return 0
 
 
+def _simulator(args, config: Config):
+    from monte_carlo_retirement_amd.simulation import RetirementMonteCarloSimulator
+
+    return RetirementMonteCarloSimulator(config, main_seed_override=args.seed, rng=args.rng, market_history=args.market_history)
+
+
+def _with_market(args, out):
+    """The printed object with the `market` key of a --history run (the response document carries its own)"""
+    if args.market_history is None or not isinstance(out, dict) or "market" in out or "error" in out:
+        return out
+    from monte_carlo_retirement_amd.history import market_document
+
+    return dict(out, market=market_document(args.market_history, args.history_as_recorded))
+
+
 def _csv(text: str, kind):
     return [kind(x) for x in text.split(",") if x.strip()]
 
 
 def frontier_or_grid(args, config: Config, world: int, rank0: bool) -> int:
-    from monte_carlo_retirement_amd.simulation import RetirementMonteCarloSimulator
-
-    sim = RetirementMonteCarloSimulator(config, main_seed_override=args.seed, rng=args.rng)
+    sim = _simulator(args, config)
     if args.frontier:
         months = _csv(args.frontier, int)
         results = sim.find_maximum_monthly_expenses_by_months(months, verbose=False, resolution=args.resolution)
@@ -436,7 +464,7 @@ def frontier_or_grid(args, config: Config, world: int, rank0: bool) -> int:
         out = {"scenario": config.Nickname, "rng": args.rng, "num_simulations": int(config.num_simulations_main),
                "working_months": months, "monthly_expenses": levels, "probability": table.tolist()}
     if rank0:
-        print(json.dumps(out))
+        print(json.dumps(_with_market(args, out)))
     if world > 1:
         import torch.distributed as dist
 

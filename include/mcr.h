@@ -60,17 +60,44 @@ extern "C" {
  *                  SeedSequence.n_children_spawned when the reference would spawn this batch's seeds;
  *                  `path_seeds` (optional) = explicit uint32 seed per path instead of the derivation
  *                  (what _run_single_simulation_path(working_months, path_seed) receives).
+ *  MCR_RNG_HISTORY a BLOCK BOOTSTRAP of a recorded market: `history` = Z[history_months][3], the record's monthly
+ *                  (equity, inflation, premium) standard shocks; a path reads them in blocks of `history_block`
+ *                  consecutive months that start at uniformly drawn months of the record and wrap around its end.
+ *                  Shock row r of global path `path` (r = the row an injected launch would read, clamped to
+ *                  shock_rows - 1 like it):
+ *                      k = r / B, j = r % B                                  (B = history_block, H = history_months)
+ *                      x = word (k & 3) of Philox4x32-10(counter = (path_lo, path_hi, k >> 2, stream_id),
+ *                                                        key = (seed_lo, seed_hi))        (seed = philox_seed)
+ *                      s = ((uint64_t)x * H) >> 32       block start; each start is drawn with probability within
+ *                                                        H / 2^32 (< 5e-7) of 1 / H
+ *                      row = (s + j) mod H               circular
+ *                      (z_equity, z_inflation, z_premium) = Z[row]
+ *                  The triple is used exactly as an injected row: equity_inflation_correlation is NOT applied (the
+ *                  record carries its own co-movement).  Row r is a pure function of (seed, stream_id, path, r):
+ *                  common random numbers across working-month candidates, probe levels and any sharding, like the
+ *                  Philox stream.  B = 1 is an i.i.d. month bootstrap; B >= total_months draws one start per path
+ *                  and runs the record forward.  A record of standardised log returns replays "the history as it
+ *                  was" under its own fitted parameters, and "the history's shape around other means" under any
+ *                  other mcr_params: the growth factors are made from Z with the launch's parameters.
+ *                  Whole-path launches only: the fan-out probe forms answer MCR_ERR_UNSUPPORTED inside the probe
+ *                  entry points, which then run one launch per level.  Kinds 0 and 1 never read the three fields.
  */
 #define MCR_RNG_PHILOX 0u
 #define MCR_RNG_NUMPY 1u
+#define MCR_RNG_HISTORY 2u
 #define MCR_MAX_ENTROPY_WORDS 8
+#define MCR_MAX_HISTORY_MONTHS 2048 /* 170 years: 48 KB of growth factors in a workgroup's LDS */
 typedef struct mcr_rng {
     uint32_t kind;
     uint32_t n_entropy_words;                /* 1..MCR_MAX_ENTROPY_WORDS (numpy) */
     uint32_t entropy[MCR_MAX_ENTROPY_WORDS]; /* numpy: main_seed words, least significant first */
-    uint64_t philox_seed;                    /* philox key */
+    uint64_t philox_seed;                    /* philox key; history: the key of the block starts */
     uint64_t child_offset;                   /* numpy */
     const uint32_t* path_seeds;              /* numpy, optional; DEVICE ptr for mcr_run_batch_rng, HOST ptr for *_host_rng */
+    const double* history;                   /* history: Z[history_months][3], finite; DEVICE ptr for the hip_stream entry
+                                                points, HOST ptr for *_host_rng (uploaded like path_seeds) */
+    uint32_t history_months;                 /* history: 1..MCR_MAX_HISTORY_MONTHS */
+    uint32_t history_block;                  /* history: block length in months, 1..2^31 - 1 */
 } mcr_rng;
 
 /* One `OtherIncomeStreamConfig` (backend/config.py:12-47), raw field values. */

@@ -9,6 +9,7 @@ of include/mcr.h.
 
 from .config import Config, ConfigurationError, OtherIncomeStreamConfig, load_config_from_json
 from .constants import MONTHS_PER_YEAR, SMALL_EPSILON
+from .history import MarketHistory, with_fitted_market
 from .params import arithmetic_to_log_params, params_from_config
 
 __all__ = [
@@ -16,6 +17,8 @@ __all__ = [
     "ConfigurationError",
     "OtherIncomeStreamConfig",
     "load_config_from_json",
+    "MarketHistory",
+    "with_fitted_market",
     "MONTHS_PER_YEAR",
     "SMALL_EPSILON",
     "arithmetic_to_log_params",

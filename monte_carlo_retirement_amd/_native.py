@@ -22,7 +22,9 @@ MCR_STREAM_SEARCH = 0
 MCR_STREAM_FINAL = 1
 MCR_RNG_PHILOX = 0
 MCR_RNG_NUMPY = 1
+MCR_RNG_HISTORY = 2
 MCR_MAX_ENTROPY_WORDS = 8
+MCR_MAX_HISTORY_MONTHS = 2048
 MCR_DEVICE_ALL = -2
 MCR_MAX_HIST_BINS = 4096
 MCR_MAX_YEAR_BINS = 512  # bins per row of the yearly-bins tables (mcr_year_bins)
@@ -153,6 +155,9 @@ class McrRng(C.Structure):
         ("philox_seed", C.c_uint64),
         ("child_offset", C.c_uint64),
         ("path_seeds", C.c_void_p),
+        ("history", C.c_void_p),
+        ("history_months", C.c_uint32),
+        ("history_block", C.c_uint32),
     ]
 
 
@@ -182,6 +187,32 @@ def numpy_rng(main_seed: int, child_offset: int = 0, path_seeds_ptr: int = 0) ->
         r.entropy[i] = w
     r.child_offset = int(child_offset)
     r.path_seeds = path_seeds_ptr or None
+    return r
+
+
+def history_rng(seed: int, table, block: int) -> McrRng:
+    """The block bootstrap of a recorded market (include/mcr.h: MCR_RNG_HISTORY): ``table`` = Z[months][3] standard shocks
+    (equity, inflation, premium), ``block`` = months per block, ``seed`` = the Philox key of the block starts.  The
+    descriptor points at HOST memory — what the ``*_host_rng`` entry points take — and keeps the array alive as
+    ``_history_table``; ``engine`` swaps in a device copy for the entry points that want one."""
+    import numpy as np
+
+    z = np.ascontiguousarray(table, dtype=np.float64)
+    if z.ndim != 2 or z.shape[1] != 3:
+        raise ValueError(f"history table: shape {z.shape} is not (months, 3)")
+    if not 1 <= z.shape[0] <= MCR_MAX_HISTORY_MONTHS:
+        raise ValueError(f"history table: {z.shape[0]} months (1..{MCR_MAX_HISTORY_MONTHS})")
+    if not 1 <= int(block) <= 2**31 - 1:
+        raise ValueError(f"history block: {block} months (1..2^31 - 1)")
+    if not np.all(np.isfinite(z)):
+        raise ValueError("history table: every entry must be finite")
+    r = McrRng()
+    r.kind = MCR_RNG_HISTORY
+    r.philox_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    r.history = z.ctypes.data
+    r.history_months = z.shape[0]
+    r.history_block = int(block)
+    r._history_table = z
     return r
 
 

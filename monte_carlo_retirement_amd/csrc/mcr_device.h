@@ -137,6 +137,45 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
+// MCR_RNG_HISTORY (include/mcr.h): a lane's place in the recorded market.  Shock row r = k B + j of a path reads row
+// (s_k + j) mod H of the record, s_k = hi32(x_k H) with x_k = word k & 3 of Philox block k >> 2 of the path.  Rows come in
+// order, so the cursor steps: the row of the record goes up by one and wraps, and every B-th month a new start is taken
+// (every 4 B-th a new Philox block).  r, j and k are wave-uniform (the month index is): scalar registers and scalar
+// branches; per lane the cursor is the row and the block's four words.  Any other row (the first one, or a caller that
+// skips) is reached from its definition, by division.
+struct HistoryCursor {
+    uint32_t w[4];   // Philox block k >> 2 of the path
+    uint32_t cur;    // the row of the record at shock row r
+    int r;           // the shock row the cursor stands at (-2: none yet)
+    uint32_t j, k;   // r = k B + j, j < B
+};
+__device__ __forceinline__ HistoryCursor history_cursor() { return HistoryCursor{{0u, 0u, 0u, 0u}, 0u, -2, 0u, 0u}; }
+__device__ __forceinline__ uint32_t history_block_start(const HistoryCursor& C, uint32_t H) {
+    const uint32_t q = C.k & 3u;
+    const uint32_t x = q == 0u ? C.w[0] : q == 1u ? C.w[1] : q == 2u ? C.w[2] : C.w[3];
+    return __umulhi(x, H);     // ((uint64_t)x * H) >> 32 < H
+}
+__device__ __forceinline__ void history_seek(HistoryCursor& C, int r, uint32_t H, uint32_t B, uint64_t seed, uint32_t stream_id, uint64_t path) {
+    if (r == C.r) return;      // (the reference's clamp repeats the last row)
+    if (r == C.r + 1) {
+        if (++C.j == B) {
+            C.j = 0u;
+            if ((++C.k & 3u) == 0u)
+                philox4x32_10((uint32_t)path, (uint32_t)(path >> 32), C.k >> 2, stream_id, (uint32_t)seed, (uint32_t)(seed >> 32), C.w);
+            C.cur = history_block_start(C, H);
+        } else if (++C.cur == H) {
+            C.cur = 0u;
+        }
+    } else {
+        C.k = (uint32_t)r / B;
+        C.j = (uint32_t)r % B;
+        philox4x32_10((uint32_t)path, (uint32_t)(path >> 32), C.k >> 2, stream_id, (uint32_t)seed, (uint32_t)(seed >> 32), C.w);
+        const uint32_t t = history_block_start(C, H) + C.j % H;      // both terms < H <= MCR_MAX_HISTORY_MONTHS
+        C.cur = t >= H ? t - H : t;
+    }
+    C.r = r;
+}
+
 // The same generator for the path kernel's blocks, counter = (path_lo, path_hi, block, stream_id) with the parts of rounds
 // 0 and 1 that do not depend on the block computed once per path (philox_path, at a point where the whole wave is
 // active): round 0's M0 path_lo, and round 1's M1 c2 — c2 = hi(M0 path_lo) ^ stream_id ^ key_hi is block-free.  path_hi is

@@ -6,7 +6,8 @@
 //       MODE 2: + yearly trajectories       (time-major [T][N]: 512 contiguous bytes per wave store)
 //       MODE 3: yearly bins                 (every lane bins its yearly samples on the caller's edges: no per-path HBM traffic)
 //       RNG 0: Philox4x32-10 + Box-Muller (mcr_device.h);  RNG 1: NumPy's SeedSequence -> PCG64 ->
-//              ziggurat stream (mcr_numpy_rng.h), for literal seed parity with the reference
+//              ziggurat stream (mcr_numpy_rng.h), for literal seed parity with the reference;  RNG 2: block bootstrap of a
+//              recorded market (include/mcr.h: MCR_RNG_HISTORY), the months' growth factors read from a table in LDS
 //     reductions: wave ballot+popcount -> LDS -> one global atomic per workgroup.
 // Helpers: helper_kernel (device unit functions + the specialised math of mcr_math.h),
 //          shocks_kernel / np_shocks_kernel (_draw_shock_path).
@@ -46,11 +47,15 @@ struct KernelIO {
     const double* injected;  // [n_paths][shock_rows][3] or nullptr
     mcr_outputs out;
     uint32_t stream_id;
-    // MCR_RNG_NUMPY (mcr_numpy_rng.h)
-    uint32_t n_entropy;
-    uint32_t entropy[MCR_MAX_ENTROPY_WORDS];
+    // MCR_RNG_NUMPY (mcr_numpy_rng.h).  MCR_RNG_HISTORY reads none of it: its table, length and block length share the bytes
+    // of the seed-word count, the first seed word and the explicit seeds, so the kernel arguments keep their size and layout
+    union { uint32_t n_entropy; uint32_t history_months; };
+    union { uint32_t entropy[MCR_MAX_ENTROPY_WORDS]; uint32_t history_block; };
     uint64_t child_offset;
-    const uint32_t* path_seeds;  // [n_paths] explicit seeds or nullptr
+    union {
+        const uint32_t* path_seeds;  // [n_paths] explicit seeds or nullptr
+        const double* history;       // MCR_RNG_HISTORY: Z[history_months][3]
+    };
     // search probes that share their accumulation phase (PHASE 1 / 2 of path_kernel; mcr_probe_months_rng)
     double* snap;                    // [n_snap][kSnapFields][snap_stride] state at the end of month snap_months[c]
     int64_t snap_stride;
@@ -329,6 +334,7 @@ constexpr bool kUniformFixups = true;
 //   prio_next: the next row at which the wave's priority falls (rows come up in order, so one compare a month is enough).
 struct MonthCounters { int prio_next, row, moy, ye_mi; };
 struct NoMonthCounters {};
+struct NoHistoryCursor {};
 // (each call site passes the one value its variant reads, chosen by a constant condition: the other is not even evaluated)
 __device__ __forceinline__ bool year_opens(const MonthCounters& c, int) { return c.moy == 1; }
 __device__ __forceinline__ bool year_opens(const NoMonthCounters&, int months_done) { return months_done % kMPY == 0; }
@@ -458,9 +464,10 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     // ds_read with an immediate offset; against the dynamic region every address is `base + ...` with a base it only learns
     // to be 0 after instruction selection: v_lshl_add_u32 x, 3, 0 (a 3-operand op, 4.6 cycles instead of 2.7) or a literal
     // v_add_u32 0.  DYNAMIC: the NumPy ziggurat tables, [n_lock_slots][kBlock] doubles (frozen nominal stream amounts),
-    // the block counters.
+    // the block counters.  (The history stream's factor table stands where the ziggurat tables do.)
     constexpr bool kStaged = RNG == (int)MCR_RNG_PHILOX && !INJ;
-    __shared__ __align__(16) double tab_s[kTabDoubles];
+    constexpr bool kHistory = RNG == (int)MCR_RNG_HISTORY && !INJ;   // (its math tables are needed before the first month only: dynamic LDS, below)
+    __shared__ __align__(16) double tab_s[kHistory ? 1 : kTabDoubles];
     constexpr int kStageLen = (kAsmFan ? kPartsPerPair : 6) * kPaths;   // = kStageDoubles for kBlock-path workgroups (PHASE 9 stages the normals' parts)
     __shared__ __align__(16) double stage_s[kStaged ? (SPLIT ? 2 : 1) * kStageLen : 1];
     // Per-path values that are written once or twice in a lifetime and read at the very end (first-year withdrawals,
@@ -477,15 +484,51 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
 #ifdef MCR_K1_TIMELINE   // diagnostic build only (tools/k1_timeline.py): per-wave start / end stamps and placement
     const unsigned long long tl_t0 = wall_clock64();
 #endif
-    double* tab = tab_s;
+    double* tab = kHistory ? reinterpret_cast<double*>(smem_raw) : tab_s;
     load_math_tables<(GF & kGrowthNarrowExp) != 0>(tab, threadIdx.x, kThreads);
     ZigTables zig{nullptr, nullptr, nullptr, nullptr};
     if (RNG == (int)MCR_RNG_NUMPY) { zig = load_zig_tables(smem_raw, threadIdx.x, kThreads); zig.math_tab = tab; }
+    // History stream: G[H][3] = (g1, ginf, g2 = ginf gprem) of every month of the record under THIS launch's market, made by the
+    // workgroup from Z with the injected route's operations in its order (growth(), below): the two routes agree bit for bit.  Rows
+    // of three doubles: a lane's month is one address and three reads at immediate offsets (the lanes of a wave stand at 64
+    // unrelated rows either way).  H x 3 exp per workgroup against 256 x total_months x 3 on the engine's own stream.  The math
+    // tables serve these exps and nothing after them, so the table takes their place: every thread makes its (at most 8) rows in
+    // registers, and stores them once the whole workgroup has read the tables for the last time.  A 2048-month record is then
+    // 48 KB a workgroup, three to a CU, where table + math tables were two.
+    [[maybe_unused]] const double* const hist_tab = reinterpret_cast<const double*>(smem_raw);
+    [[maybe_unused]] std::conditional_t<kHistory, HistoryCursor, NoHistoryCursor> HC;    // (an empty object in every other variant)
+    if constexpr (kHistory) {
+        constexpr int kRowsPerThread = MCR_MAX_HISTORY_MONTHS / kBlock;
+        static_assert(kRowsPerThread * kBlock == MCR_MAX_HISTORY_MONTHS, "every row of the longest record has a thread");
+        HC = history_cursor();
+        __syncthreads();     // the math tables are in place
+        const int H = (int)io.history_months;
+        double g[kRowsPerThread][3];
+#pragma unroll
+        for (int i = 0; i < kRowsPerThread; ++i) {
+            const int k = (int)threadIdx.x + i * kBlock;
+            g[i][0] = g[i][1] = g[i][2] = 0.0;
+            if (k < H) {
+                const double ze = io.history[3 * k + 0], zi = io.history[3 * k + 1], zp = io.history[3 * k + 2];
+                g[i][0] = monthly_gross(P.a1, P.b1, ze, tab);
+                g[i][1] = monthly_gross(P.ainf, P.binf, zi, tab);
+                g[i][2] = g[i][1] * monthly_gross(P.aprem, P.bprem, zp, tab);  // :532
+            }
+        }
+        __syncthreads();     // nobody reads the math tables any more
+        double* const G = reinterpret_cast<double*>(smem_raw);
+#pragma unroll
+        for (int i = 0; i < kRowsPerThread; ++i) {
+            const int k = (int)threadIdx.x + i * kBlock;
+            if (k < H) { G[3 * k + 0] = g[i][0]; G[3 * k + 1] = g[i][1]; G[3 * k + 2] = g[i][2]; }
+        }
+    }
     // Philox stream: the gross factors of two months at a time, staged per lane (growth_rows2)
     double* stage = stage_s + (kStaged ? tid : 0);
     double* sum_col = sum_s + (kSumLds ? tid : 0);     // [0] first-year gross, [kBlock] first-year real gross, [2 kBlock] YearsToRuin bits
     // lock columns: [n_lock_slots][kPaths] doubles; PHASE 5: one such block per consumer wave
-    double* lock_lds = reinterpret_cast<double*>(smem_raw + (RNG == (int)MCR_RNG_NUMPY ? kZigLdsBytes : 0));
+    double* lock_lds = reinterpret_cast<double*>(smem_raw + (RNG == (int)MCR_RNG_NUMPY ? (size_t)kZigLdsBytes
+                                                             : kHistory ? (size_t)io.history_months * 3u * sizeof(double) : (size_t)0));
     unsigned int* blk = reinterpret_cast<unsigned int*>(lock_lds + (size_t)P.n_lock_slots * kPaths * (kFan ? io.fan_n : 1));
     if (kFan && !producer) lock_lds += (size_t)fan_j * P.n_lock_slots * kPaths;
     // blk[0] = success count; blk[1 .. 1+ry+2) = ruin bins; then [ry+1] done-years histogram; then the
@@ -589,6 +632,13 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         if (kStaged) {
             const double* c = stage + (size_t)(3 * (row & 1)) * kPaths + (SPLIT ? (size_t)((row >> 1) & 1) * kStageLen : 0);
             g1 = c[0]; ginf = c[kPaths]; g2 = c[2 * kPaths];
+            return;
+        }
+        if constexpr (kHistory) {
+            const int r = row < P.shock_rows - 1 ? row : P.shock_rows - 1;  // :692, like an injected row
+            history_seek(HC, r, io.history_months, io.history_block, io.seed, io.stream_id, path);
+            const double* const c = hist_tab + 3u * HC.cur;
+            g1 = c[0]; ginf = c[1]; g2 = c[2];
             return;
         }
         double ze, zi, zp;
@@ -1430,6 +1480,21 @@ __global__ void np_shocks_kernel(const KernelIO io, int32_t n_months, double rho
     }
 }
 
+// The history stream's rows (include/mcr.h: MCR_RNG_HISTORY): out[n_paths][n_months][3] = Z[row]; one thread per path, rows in
+// order through the path kernel's cursor
+__global__ void history_shocks_kernel(uint64_t seed, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths, int32_t n_months,
+                                      const double* __restrict__ z, uint32_t history_months, uint32_t history_block, double* out) {
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool valid = p < n_paths;
+    const uint64_t q = valid ? p : n_paths - 1;       // (tail lanes shadow the last path: the cursor's branches stay wave-uniform)
+    HistoryCursor C = history_cursor();
+    double* o = out + (size_t)q * 3u * (size_t)n_months;
+    for (int32_t m = 0; m < n_months; ++m) {
+        history_seek(C, m, history_months, history_block, seed, stream_id, path_begin + q);
+        if (valid) { o[3 * m + 0] = z[3u * C.cur + 0]; o[3 * m + 1] = z[3u * C.cur + 1]; o[3 * m + 2] = z[3u * C.cur + 2]; }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
@@ -1890,9 +1955,10 @@ static int stream_form_of(const DevParams& d, bool has_variants, int* mask) {
 // slots in LDS (A/B, tests).
 constexpr size_t kLdsPerWorkgroup = 64 * 1024;
 constexpr size_t kLdsForFourResident = 40 * 1024;
-static size_t path_kernel_static_lds(int mode, bool numpy_rng, bool injected, bool split) {
-    const bool staged = !numpy_rng && !injected;
-    return (size_t)kMathTabBytes + (staged ? (size_t)(split ? 2 : 1) * kStageDoubles * sizeof(double) : 16) +
+static size_t path_kernel_static_lds(int mode, uint32_t rng_kind, bool injected, bool split) {
+    const bool staged = rng_kind == MCR_RNG_PHILOX && !injected;
+    const bool history = rng_kind == MCR_RNG_HISTORY && !injected;     // (its math tables lie in the dynamic part, under its factor table)
+    return (history ? (size_t)16 : (size_t)kMathTabBytes) + (staged ? (size_t)(split ? 2 : 1) * kStageDoubles * sizeof(double) : 16) +
            (((mode == 1 || mode == 2) && staged) ? (size_t)3 * kBlock * sizeof(double) : 16);
 }
 // LDS of the yearly-bins form (MODE 3 of path_kernel) behind the block counters: both edge arrays as doubles, two row buffers
@@ -1902,18 +1968,28 @@ static size_t year_bins_lds(int n_bins, int n_wr_bins) {
     const size_t cells = (size_t)n_bins + 2, wcells = (size_t)n_wr_bins + 2;
     return 8 + ((size_t)n_bins + 1 + (size_t)n_wr_bins + 1) * sizeof(double) + (2 * (2 * cells + wcells) + cells) * sizeof(unsigned int);
 }
-static int plan_path_kernel_lds(DevParams& d, int mode, bool numpy_rng, bool injected, bool split, int n_hist_bins, size_t* dynamic_bytes,
-                                size_t year_bins_bytes = 0) {
-    const size_t fixed = path_kernel_static_lds(mode, numpy_rng, injected, split) + (numpy_rng ? (size_t)kZigLdsBytes : (size_t)0) +
+// The history stream (rng_kind MCR_RNG_HISTORY, not injected) holds its factor table, history_months x 3 doubles, in the
+// dynamic part — where the math tables stand until the table is made, so the part is never smaller than they are — and has
+// no stage.  A long record alone costs resident workgroups (2048 months: 48 KB = three on a CU); its lock columns then get
+// what is left of the budget of THAT number of workgroups, not of four.
+constexpr size_t kLdsPerCu = 160 * 1024;
+static int plan_path_kernel_lds(DevParams& d, int mode, uint32_t rng_kind, bool injected, bool split, int n_hist_bins, size_t* dynamic_bytes,
+                                size_t year_bins_bytes = 0, uint32_t history_months = 0) {
+    const size_t table_bytes = injected ? (size_t)0 : rng_kind == MCR_RNG_NUMPY ? (size_t)kZigLdsBytes
+                               : rng_kind == MCR_RNG_HISTORY ? (size_t)history_months * 3u * sizeof(double) : (size_t)0;
+    size_t fixed = path_kernel_static_lds(mode, rng_kind, injected, split) + table_bytes +
                          (size_t)(1 + (d.retirement_years + 2) + (d.retirement_years + 1) + n_hist_bins) * sizeof(unsigned int) + year_bins_bytes;
+    if (rng_kind == MCR_RNG_HISTORY && !injected) fixed = std::max(fixed, path_kernel_static_lds(mode, rng_kind, injected, split) + (size_t)kMathTabBytes);
     if (fixed > kLdsPerWorkgroup) { set_error("too many retirement years / histogram bins for the LDS of a workgroup"); return MCR_ERR_UNSUPPORTED; }
     constexpr size_t kSlotBytes = (size_t)kBlock * sizeof(double);
     long slots = (long)((kLdsPerWorkgroup - fixed) / kSlotBytes);
+    size_t budget = kLdsForFourResident;
+    if (rng_kind == MCR_RNG_HISTORY && !injected && fixed >= kLdsForFourResident) budget = std::min(kLdsPerWorkgroup, kLdsPerCu / (kLdsPerCu / fixed));
     const char* e = std::getenv("MCR_K1_LDS_LOCK_SLOTS");
     if (e && *e) slots = std::min(slots, std::max(0l, std::strtol(e, nullptr, 10)));
-    else slots = std::min(slots, fixed < kLdsForFourResident ? (long)((kLdsForFourResident - fixed) / kSlotBytes) : 0l);
+    else slots = std::min(slots, fixed < budget ? (long)((budget - fixed) / kSlotBytes) : 0l);
     d.n_lock_slots = (int32_t)std::min<long>(slots, d.n_lock_slots_total);
-    *dynamic_bytes = fixed - path_kernel_static_lds(mode, numpy_rng, injected, split) + (size_t)d.n_lock_slots * kBlock * sizeof(double);
+    *dynamic_bytes = fixed - path_kernel_static_lds(mode, rng_kind, injected, split) + (size_t)d.n_lock_slots * kBlock * sizeof(double);
     return MCR_OK;
 }
 
@@ -2045,9 +2121,27 @@ static void launch_sliced(Kernel kernel, const SegmentPlan& plan, const int* ord
     }
 }
 
-static int check_rng(const mcr_rng* rng) {
+// host_table: rng->history is host memory (the *_host_rng entry points), so its entries can be checked too
+static int check_rng(const mcr_rng* rng, bool host_table = false) {
     if (!rng) { set_error("null rng"); return MCR_ERR_INVALID_ARG; }
-    if (rng->kind != MCR_RNG_PHILOX && rng->kind != MCR_RNG_NUMPY) { set_error("unknown rng kind %u", rng->kind); return MCR_ERR_INVALID_ARG; }
+    if (rng->kind != MCR_RNG_PHILOX && rng->kind != MCR_RNG_NUMPY && rng->kind != MCR_RNG_HISTORY) { set_error("unknown rng kind %u", rng->kind); return MCR_ERR_INVALID_ARG; }
+    if (rng->kind == MCR_RNG_HISTORY) {
+        if (!rng->history) { set_error("history rng: null history table"); return MCR_ERR_INVALID_ARG; }
+        if (rng->history_months < 1 || rng->history_months > MCR_MAX_HISTORY_MONTHS) {
+            set_error("history rng: history_months = %u (1..%d)", rng->history_months, MCR_MAX_HISTORY_MONTHS);
+            return MCR_ERR_INVALID_ARG;
+        }
+        if (rng->history_block < 1 || rng->history_block > (uint32_t)INT32_MAX) {
+            set_error("history rng: history_block = %u (1..%d)", rng->history_block, INT32_MAX);
+            return MCR_ERR_INVALID_ARG;
+        }
+        if (host_table)
+            for (uint32_t k = 0; k < 3u * rng->history_months; ++k)
+                if (!std::isfinite(rng->history[k])) {
+                    set_error("history rng: history[%u][%u] = %g: the table must be finite", k / 3u, k % 3u, rng->history[k]);
+                    return MCR_ERR_INVALID_ARG;
+                }
+    }
     if (rng->kind == MCR_RNG_NUMPY && !rng->path_seeds &&
         (rng->n_entropy_words < 1 || rng->n_entropy_words > MCR_MAX_ENTROPY_WORDS)) {
         set_error("numpy rng: main seed must have 1..%d uint32 words (got %u)", MCR_MAX_ENTROPY_WORDS, rng->n_entropy_words);
@@ -2056,12 +2150,19 @@ static int check_rng(const mcr_rng* rng) {
     return MCR_OK;
 }
 
+// A history descriptor of a *_host_rng call is judged before the device is entered: a bad table is the caller's error with or
+// without a GPU (the other kinds keep their order: device first)
+static int check_history_host(const mcr_rng* rng) { return rng && rng->kind == MCR_RNG_HISTORY ? check_rng(rng, true) : MCR_OK; }
+
 static void fill_io_rng(KernelIO& io, const mcr_rng* rng, const uint32_t* device_path_seeds) {
     io.seed = rng->philox_seed;
     io.n_entropy = rng->n_entropy_words;
     for (int i = 0; i < MCR_MAX_ENTROPY_WORDS; ++i) io.entropy[i] = rng->entropy[i];
     io.child_offset = rng->child_offset;
     io.path_seeds = device_path_seeds;
+    if (rng->kind == MCR_RNG_HISTORY) {      // (a DEVICE table here: the fields lie over the NumPy stream's, KernelIO)
+        io.history = rng->history; io.history_months = rng->history_months; io.history_block = rng->history_block;
+    }
 }
 
 static KernelIO make_io(const mcr_rng* rng, const uint32_t* device_path_seeds, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths) {
@@ -2115,9 +2216,9 @@ template <typename F> static inline void for_output_mode(int mode, F&& f) {
 
 // f(R, T, A, X, E) = (stream, tax mask, annual-gains tax, extended streams, exact month) of a whole-path launch (PHASE 0, not
 // split, no injection) — the one place that says which variants such a launch has: the generic form (mask 3, annual) for
-// extended streams / the exact month; the engine's own stream per tax mask; the NumPy stream taxed / untaxed only (mask 3
-// computes a zero-rate asset's tax arithmetic as exact zeros)
-template <typename F> static inline void for_whole_path_variant(const DevParams& d, bool np_rng, bool xs, bool exact, F&& f) {
+// extended streams / the exact month; the engine's own stream per tax mask; the NumPy and history streams taxed / untaxed
+// only (mask 3 computes a zero-rate asset's tax arithmetic as exact zeros)
+template <typename F> static inline void for_whole_path_variant(const DevParams& d, uint32_t rng_kind, bool xs, bool exact, F&& f) {
     auto with_stream = [&](auto R) {
         if (xs) {
             if (exact) f(R, int_c<3>{}, std::true_type{}, std::true_type{}, std::true_type{});
@@ -2131,7 +2232,9 @@ template <typename F> static inline void for_whole_path_variant(const DevParams&
             });
         }
     };
-    if (np_rng) with_stream(int_c<1>{}); else with_stream(int_c<0>{});
+    if (rng_kind == MCR_RNG_HISTORY) with_stream(int_c<(int)MCR_RNG_HISTORY>{});
+    else if (rng_kind == MCR_RNG_NUMPY) with_stream(int_c<(int)MCR_RNG_NUMPY>{});
+    else with_stream(int_c<0>{});
 }
 // The generic variants (XS) carry what the lean ones leave out: records beyond the by-value block and both forms of the month
 static bool needs_exact_month(const DevParams& d) { return d.exact_month && !kExactMonthDefault; }
@@ -2210,7 +2313,8 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
         set_error("path_stride %lld < n_paths %llu", (long long)io.out.path_stride, (unsigned long long)n_paths);
         return MCR_ERR_INVALID_ARG;
     }
-    const bool np_rng = rng->kind == MCR_RNG_NUMPY;
+    const uint32_t rng_kind = rng->kind;
+    const bool np_rng = rng_kind != MCR_RNG_PHILOX;      // the NumPy or the history stream: whole-path launches only
     if (io.out.hist_bins == nullptr || io.out.hist_n_bins == 0) { io.out.hist_bins = nullptr; io.out.hist_edges = nullptr; io.out.hist_n_bins = 0; }
     if (io.out.hist_bins && (io.out.hist_n_bins < 0 || io.out.hist_n_bins > MCR_MAX_HIST_BINS || !io.out.hist_edges)) {
         set_error("hist_bins requested with hist_n_bins = %d (1..%d) / hist_edges = %p", io.out.hist_n_bins, MCR_MAX_HIST_BINS, (const void*)io.out.hist_edges);
@@ -2223,12 +2327,12 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
     bool split = !injected && !np_rng && mode == 0 && (uint64_t)grid.x * (kBlock / 64) <= split_max_waves();
     if (split && (rc = check_barrier_counts(d)) != MCR_OK) return rc;
     size_t lds = 0;
-    rc = plan_path_kernel_lds(d, mode, np_rng, injected != nullptr, split, io.out.hist_n_bins, &lds);
+    rc = plan_path_kernel_lds(d, mode, rng_kind, injected != nullptr, split, io.out.hist_n_bins, &lds, 0, rng->history_months);
     if (rc != MCR_OK) return rc;
     if (split && (d.n_lock_slots < d.n_lock_slots_total || needs_generic_variant(d))) {
         // the producer / consumer form doubles the stage: where only IT cannot hold every lock column, the unsplit kernel runs
         split = false;
-        rc = plan_path_kernel_lds(d, mode, np_rng, false, false, io.out.hist_n_bins, &lds);
+        rc = plan_path_kernel_lds(d, mode, rng_kind, false, false, io.out.hist_n_bins, &lds);
         if (rc != MCR_OK) return rc;
     }
     // XS: records beyond the by-value block and / or lock slots beyond the LDS budget -> the extended-stream variants
@@ -2238,7 +2342,7 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
     const char* seg_order = segment_order_env();
     if (seg_order && (np_rng || injected || xs || split)) {
         set_error("MCR_K1_SEGMENT_ORDER=%s set on a launch that is not time-sliced (%s)", seg_order,
-                  np_rng ? "NumPy stream" : injected ? "injected shocks" : xs ? "extended streams / exact month" : "producer / consumer split");
+                  rng_kind == MCR_RNG_HISTORY ? "history stream" : np_rng ? "NumPy stream" : injected ? "injected shocks" : xs ? "extended streams / exact month" : "producer / consumer split");
         return MCR_ERR_INVALID_ARG;
     }
     // growth form of the launch: the whole-path and time-sliced count-only kernels of the engine's own stream have the variants
@@ -2258,7 +2362,7 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
     // the whole-path variants of the engine's streams (for_whole_path_variant), output mode M
     auto launch_whole_path = [&]() {
         for_output_mode(mode, [&](auto M) {
-            for_whole_path_variant(d, np_rng, xs, exact, [&](auto R, auto T, auto A, auto X, auto EX) {
+            for_whole_path_variant(d, rng_kind, xs, exact, [&](auto R, auto T, auto A, auto X, auto EX) {
                 if constexpr (kHasGrowthForms<decltype(M)::value, decltype(R)::value, decltype(A)::value, decltype(X)::value>) {
                     for_growth_form(gf, [&](auto G) {
                         for_month_form<decltype(T)::value>(mf, [&](auto F) {
@@ -2404,10 +2508,10 @@ static int launch_year_bins(const mcr_params* p, const mcr_rng* rng, uint32_t st
     io.yb.real_trajectory = (unsigned long long*)yb->real_trajectory_bins;
     io.yb.wr = (unsigned long long*)yb->wr_bins;
     io.yb.final_success = (unsigned long long*)yb->final_success_bins;
-    const bool np_rng = rng->kind == MCR_RNG_NUMPY;
+    const uint32_t rng_kind = rng->kind;
     const dim3 grid((unsigned)((n_paths + kBlock - 1) / kBlock)), block(kBlock);
     size_t lds = 0;
-    rc = plan_path_kernel_lds(d, 3, np_rng, false, false, io.out.hist_n_bins, &lds, year_bins_lds(io.yb.n_bins, io.yb.n_wr_bins));
+    rc = plan_path_kernel_lds(d, 3, rng_kind, false, false, io.out.hist_n_bins, &lds, year_bins_lds(io.yb.n_bins, io.yb.n_wr_bins), rng->history_months);
     if (rc != MCR_OK) return rc;
     const bool exact = needs_exact_month(d);
     const bool xs = d.n_lock_slots < d.n_lock_slots_total || needs_generic_variant(d);
@@ -2415,7 +2519,7 @@ static int launch_year_bins(const mcr_params* p, const mcr_rng* rng, uint32_t st
     rc = side.attach(d, extra, grid.x, stream);
     if (rc != MCR_OK) { (void)side.release(stream); return rc; }
     const DevParams* const no_cand = nullptr;
-    for_whole_path_variant(d, np_rng, xs, exact, [&](auto R, auto T, auto A, auto X, auto EX) {
+    for_whole_path_variant(d, rng_kind, xs, exact, [&](auto R, auto T, auto A, auto X, auto EX) {
         hipLaunchKernelGGL((path_kernel<3, decltype(R)::value, decltype(T)::value, decltype(A)::value, false, 0, false, decltype(X)::value,
                                         (decltype(X)::value && decltype(EX)::value) || kExactMonthDefault>),
                            grid, block, lds, stream, d, io, no_cand);
@@ -2526,7 +2630,7 @@ static int probe_shared_prefix(const mcr_params* p, const mcr_rng* rng, uint32_t
     //  each then carries its own device table / overflow block)
     if (needs_generic_variant(top)) return MCR_ERR_UNSUPPORTED;
     size_t lds = 0;
-    if (plan_path_kernel_lds(top, 0, false, false, true, 0, &lds) != MCR_OK || top.n_lock_slots < top.n_lock_slots_total) return MCR_ERR_UNSUPPORTED;
+    if (plan_path_kernel_lds(top, 0, MCR_RNG_PHILOX, false, true, 0, &lds) != MCR_OK || top.n_lock_slots < top.n_lock_slots_total) return MCR_ERR_UNSUPPORTED;
     for (DevParams& b : blocks) b.n_lock_slots = top.n_lock_slots;
     KernelIO io = make_io(rng, nullptr, stream_id, path_begin, n_paths);
     io.out.counters = counts;
@@ -2653,7 +2757,7 @@ static int probe_expenses_fanout(const mcr_params* p, const mcr_rng* rng, uint32
     if (int rc = plan_level_fanout(p, rng, n_paths, wm, n_levels, fanout_min_waves(), &d, &lmax)) return rc;
     DevParams d1 = d;    // (PHASE 1 never reads a lock column: its plan may lower the LDS slots)
     size_t lds1 = 0;
-    if (plan_path_kernel_lds(d1, 0, false, false, true, 0, &lds1) != MCR_OK) { (void)hipGetLastError(); return MCR_ERR_UNSUPPORTED; }
+    if (plan_path_kernel_lds(d1, 0, MCR_RNG_PHILOX, false, true, 0, &lds1) != MCR_OK) { (void)hipGetLastError(); return MCR_ERR_UNSUPPORTED; }
     KernelIO io = make_io(rng, nullptr, stream_id, path_begin, n_paths);
     io.snap_months[0] = wm;
     SnapshotBlock snap(stream);
@@ -2922,7 +3026,7 @@ static int probe_grid_shared(const mcr_params* p, const mcr_rng* rng, uint32_t s
     if (lmax < 1) return MCR_ERR_UNSUPPORTED;
     DevParams d1 = top;    // (PHASE 1 never reads a lock column: its plan may lower the LDS slots)
     size_t lds1 = 0;
-    if (plan_path_kernel_lds(d1, 0, false, false, true, 0, &lds1) != MCR_OK) { (void)hipGetLastError(); return MCR_ERR_UNSUPPORTED; }
+    if (plan_path_kernel_lds(d1, 0, MCR_RNG_PHILOX, false, true, 0, &lds1) != MCR_OK) { (void)hipGetLastError(); return MCR_ERR_UNSUPPORTED; }
     KernelIO io = make_io(rng, nullptr, stream_id, path_begin, n_paths);
     for (int c = 0; c < n_cand; ++c) io.snap_months[c] = months[(size_t)c];
     // the rows' records, level group by level group: group g covers levels [first, first + lg) of every row
@@ -3513,7 +3617,7 @@ int mcr_run_batch_host(const mcr_params* p, uint64_t seed, uint32_t stream_id, u
 static int run_batch_host_on(int device, const mcr_params* p, const mcr_rng* rng_in, uint32_t stream_id, uint64_t path_begin,
                              uint64_t n_paths, int32_t working_months, const double* injected_shocks, const mcr_outputs* out) {
     MCR_ENTER_DEVICE(device);
-    int rc = check_rng(rng_in);
+    int rc = check_rng(rng_in, true);
     if (rc != MCR_OK) return rc;
     mcr_sizes sz;
     rc = query_sizes(p, working_months, &sz);
@@ -3569,6 +3673,9 @@ static int run_batch_host_on(int device, const mcr_params* p, const mcr_rng* rng
     mcr_rng rng = *rng_in;
     uint32_t* d_seeds = nullptr;   // explicit per-path seeds: upload
     plan((void**)&d_seeds, rng.path_seeds, 1, n * sizeof(uint32_t), 0, 0, true, false);
+    const bool history = rng.kind == MCR_RNG_HISTORY;
+    double* d_history = nullptr;   // the history stream's table: upload
+    if (history) plan((void**)&d_history, rng.history, 1, (size_t)rng.history_months * 3 * sizeof(double), 0, 0, true, false);
 
     HostCtxLease lease(device);
     HostCtx* ctx = lease.ctx;
@@ -3581,6 +3688,7 @@ static int run_batch_host_on(int device, const mcr_params* p, const mcr_rng* rng
     }
     if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return hip_fail(e, "upload"); }
     if (rng.path_seeds) rng.path_seeds = d_seeds;
+    if (history) rng.history = d_history;
     rc = launch_paths(p, &rng, stream_id, path_begin, n_paths, working_months, d_inj, &d, ctx->stream);
     if (rc == MCR_OK) {
         for (const Buf& b : bufs) {
@@ -3670,6 +3778,8 @@ static int run_batch_host_multi(const int32_t* devices, int32_t n_devices, const
 int mcr_run_batch_host_rng(const mcr_params* p, const mcr_rng* rng_in, uint32_t stream_id, uint64_t path_begin,
                            uint64_t n_paths, int32_t working_months, const double* injected_shocks,
                            const mcr_outputs* out, int device) {
+    const int rc = check_history_host(rng_in);
+    if (rc != MCR_OK) return rc;
     if (device == MCR_DEVICE_ALL)
         return run_batch_host_multi(nullptr, 0, p, rng_in, stream_id, path_begin, n_paths, working_months, injected_shocks, out);
     return run_batch_host_on(device, p, rng_in, stream_id, path_begin, n_paths, working_months, injected_shocks, out);
@@ -3678,6 +3788,8 @@ int mcr_run_batch_host_rng(const mcr_params* p, const mcr_rng* rng_in, uint32_t 
 int mcr_run_batch_multi_host_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
                                  uint64_t n_paths, int32_t working_months, const double* injected_shocks,
                                  const mcr_outputs* out, const int32_t* devices, int32_t n_devices) {
+    const int rc = check_history_host(rng);
+    if (rc != MCR_OK) return rc;
     return run_batch_host_multi(devices, n_devices, p, rng, stream_id, path_begin, n_paths, working_months, injected_shocks, out);
 }
 
@@ -3704,7 +3816,7 @@ static std::vector<YearBinsBlock> year_bins_blocks(const mcr_sizes& sz, const mc
 // Everything that can be checked on the host, before any device work
 static int check_year_bins_host(const mcr_params* p, const mcr_rng* rng, int32_t working_months, const mcr_outputs* out,
                                 const mcr_year_bins* yb, mcr_sizes* sz) {
-    int rc = check_rng(rng);
+    int rc = check_rng(rng, true);
     if (rc != MCR_OK) return rc;
     if ((rc = query_sizes(p, working_months, sz)) != MCR_OK) return rc;
     if ((rc = validate_params(p)) != MCR_OK) return rc;
@@ -3741,6 +3853,9 @@ static int run_year_bins_host_on(int device, const mcr_params* p, const mcr_rng*
     mcr_rng rng = *rng_in;
     uint32_t* d_seeds = nullptr;
     plan((void**)&d_seeds, rng.path_seeds, (size_t)n_paths * sizeof(uint32_t), false);
+    const bool history = rng.kind == MCR_RNG_HISTORY;
+    double* d_history = nullptr;   // the history stream's table: upload
+    if (history) plan((void**)&d_history, rng.history, (size_t)rng.history_months * 3 * sizeof(double), false);
 
     HostCtxLease lease(device);
     HostCtx* ctx = lease.ctx;
@@ -3753,6 +3868,7 @@ static int run_year_bins_host_on(int device, const mcr_params* p, const mcr_rng*
     }
     if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return hip_fail(e, "upload"); }
     if (rng.path_seeds) rng.path_seeds = d_seeds;
+    if (history) rng.history = d_history;
     rc = launch_year_bins(p, &rng, stream_id, path_begin, n_paths, working_months, &d, &dy, ctx->stream);
     // the tables come back through a staging copy: the caller's stay untouched unless the whole call succeeds
     std::vector<std::vector<unsigned char>> staged(bufs.size());
@@ -3983,7 +4099,7 @@ int mcr_draw_shocks_host_rng(const mcr_rng* rng, uint32_t stream_id, uint64_t pa
                              int32_t n_months, double rho, double* out, int device) {
     MCR_ENTER_DEVICE(device);
     int rc = MCR_OK;
-    rc = check_rng(rng);
+    rc = check_rng(rng, true);
     if (rc != MCR_OK) return rc;
     const uint64_t seed = rng->philox_seed;
     if (!out || n_months < 0) { set_error("bad arguments"); return MCR_ERR_INVALID_ARG; }
@@ -3996,7 +4112,15 @@ int mcr_draw_shocks_host_rng(const mcr_rng* rng, uint32_t stream_id, uint64_t pa
     if (e != hipSuccess) return hip_fail(e, "hipMalloc");
     const double om = 1.0 - rho * rho;
     const double rho_c = std::sqrt(om > 0.0 ? om : 0.0);
-    if (rng->kind == MCR_RNG_NUMPY) {
+    if (rng->kind == MCR_RNG_HISTORY) {      // the gathered rows of the record (rho is not applied)
+        double* d_z = nullptr;
+        const size_t z_bytes = (size_t)rng->history_months * 3 * sizeof(double);
+        e = arena.alloc((void**)&d_z, z_bytes);
+        if (e == hipSuccess) e = hipMemcpy(d_z, rng->history, z_bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return hip_fail(e, "history table upload");
+        hipLaunchKernelGGL(history_shocks_kernel, dim3((unsigned)((n_paths + 63) / 64)), dim3(64), 0, nullptr, seed, stream_id, path_begin,
+                           n_paths, n_months, d_z, rng->history_months, rng->history_block, d);
+    } else if (rng->kind == MCR_RNG_NUMPY) {
         KernelIO io;
         std::memset(&io, 0, sizeof(io));
         uint32_t* d_seeds = nullptr;

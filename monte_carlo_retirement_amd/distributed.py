@@ -106,6 +106,23 @@ def broadcast_int(value: int, src: int = 0) -> int:
     return int(t.item())
 
 
+def broadcast_array(value: np.ndarray, src: int = 0) -> np.ndarray:
+    """The float64 matrix ``value`` of rank ``src`` on every rank (no-op without a process group); the ranks' own matrices
+    may differ in their number of rows."""
+    arr = np.ascontiguousarray(value, dtype=np.float64)
+    if not is_active():
+        return arr
+    import torch
+    import torch.distributed as dist
+
+    rows, cols = broadcast_int(arr.shape[0], src), broadcast_int(arr.shape[1], src)
+    t = torch.zeros((rows, cols), dtype=torch.float64, device=_comm_device())
+    if dist.get_rank() == src:
+        t.copy_(torch.from_numpy(arr))
+    dist.broadcast(t, src=src)
+    return t.cpu().numpy()
+
+
 def all_reduce_sum_(tensor) -> None:
     """In-place sum over ranks (the path's single exchange step)."""
     import torch.distributed as dist

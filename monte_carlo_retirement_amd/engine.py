@@ -84,11 +84,27 @@ def stream_start_month_index(current_age: float, working_months: int, start_at_a
     return int(N.load_library().mcr_stream_start_month_index(current_age, working_months, start_at_age))
 
 
-def _as_rng(seed) -> McrRng:
-    """`seed` may be an int (Philox key) or a ready McrRng descriptor (copied: callers' objects are never mutated)."""
+def _as_rng(seed, device: Optional[int] = None) -> McrRng:
+    """`seed` may be an int (Philox key) or a ready McrRng descriptor (copied: callers' objects are never mutated).
+
+    ``device``: the HIP ordinal of an entry point that takes DEVICE pointers.  A history descriptor
+    (``_native.history_rng``) points at host memory; its copy then points at a device copy of the table, made once per
+    device and kept with the caller's descriptor."""
     if isinstance(seed, McrRng):
         dup = McrRng()
         C.memmove(C.byref(dup), C.byref(seed), C.sizeof(McrRng))
+        table = getattr(seed, "_history_table", None)
+        dup._history_table = table          # (the copy keeps what it points at alive)
+        if device is not None and seed.kind == N.MCR_RNG_HISTORY:
+            if table is None:
+                raise ValueError("history rng: build the descriptor with _native.history_rng (it owns the table)")
+            import torch
+
+            cache = seed.__dict__.setdefault("_history_device", {})
+            if int(device) not in cache:
+                cache[int(device)] = torch.as_tensor(np.array(table), device=torch.device("cuda", int(device)))   # (a copy: the table is read-only)
+            dup._history_device = cache[int(device)]
+            dup.history = dup._history_device.data_ptr()
         return dup
     return N.philox_rng(int(seed))
 
@@ -351,7 +367,7 @@ class YearBinsBatch:
         """Enqueue one launch over global paths ``[path_begin, path_begin + n_paths)`` on the current stream; the tables
         accumulate.  ``seed``: int (Philox key) or an ``McrRng`` descriptor."""
         stream = self.torch.cuda.current_stream(self.device).cuda_stream
-        rng = _as_rng(seed)
+        rng = _as_rng(seed, self.device)
         rc = self._lib.mcr_run_year_bins_rng(
             C.byref(self.params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), self.working_months,
             C.byref(self._out), C.byref(self._yb), self.device, C.c_void_p(stream),
@@ -511,7 +527,7 @@ class DeviceBatch:
         if n > self.n_paths:
             raise ValueError("launch larger than the batch buffers")
         stream = self.torch.cuda.current_stream(self.device).cuda_stream
-        rng = _as_rng(seed)
+        rng = _as_rng(seed, self.device)
         rc = self._lib.mcr_run_batch_rng(
             C.byref(self.params), C.byref(rng), int(stream_id), int(path_begin), n,
             self.working_months, None, C.byref(self._out), self.device, C.c_void_p(stream),
@@ -533,7 +549,7 @@ def probe_months(params: McrParams, seed, stream_id: int, path_begin: int, n_pat
                          device=torch.device("cuda", int(device)))
     if len(working_months) == 0:
         return counts
-    rng = _as_rng(seed)
+    rng = _as_rng(seed, int(device))
     stream = torch.cuda.current_stream(int(device)).cuda_stream
     rc = N.load_library().mcr_probe_months_rng(
         C.byref(params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), months,
@@ -554,7 +570,7 @@ def _probe_levels(symbol: str, params: McrParams, seed, stream_id: int, path_beg
     counts = torch.empty((len(levels), N.MCR_N_COUNTERS), dtype=torch.int64, device=torch.device("cuda", int(device)))
     if not levels:
         return counts
-    rng = _as_rng(seed)
+    rng = _as_rng(seed, int(device))
     stream = torch.cuda.current_stream(int(device)).cuda_stream
     rc = getattr(N.load_library(), symbol)(
         C.byref(params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), int(working_months), arr,
@@ -650,7 +666,7 @@ def _probe_records(symbol: str, params: McrParams, seed, stream_id: int, path_be
         mk = alloc((n, joint_mask_words(n_paths)), dtype=torch.int64, device=dev) if masks else None
         outs = [mk.data_ptr() if mk is not None and mk.numel() else None, jm.data_ptr() if n else None, ex.data_ptr()]
     if n:
-        rng = _as_rng(seed)
+        rng = _as_rng(seed, int(device))
         stream = torch.cuda.current_stream(int(device)).cuda_stream
         rc = getattr(N.load_library(), symbol)(
             C.byref(params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), int(working_months), *record_args,
@@ -849,7 +865,7 @@ def probe_grid(params: McrParams, seed, stream_id: int, path_begin: int, n_paths
     marr = (C.c_int32 * len(months))(*months)
     flat = [x for r in rows for x in r]
     larr = (C.c_double * len(flat))(*flat)
-    rng = _as_rng(seed)
+    rng = _as_rng(seed, int(device))
     stream = torch.cuda.current_stream(int(device)).cuda_stream
     rc = N.load_library().mcr_probe_grid_rng(
         C.byref(params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), marr, len(months), larr, n_levels,

@@ -396,24 +396,29 @@ def streamed_result(config: Config, simulator: RetirementMonteCarloSimulator, re
 # ---------------------------------------------------------------------------------------------------
 def run_scenario(config: Config, working_months_override: Optional[int] = None,
                  emit: Optional[Callable[[dict], None]] = None, result_builder: Callable[..., dict] = build_result,
-                 **simulator_kwargs: Any) -> Optional[dict]:
+                 market_as_recorded: bool = False, **simulator_kwargs: Any) -> Optional[dict]:
     """Search (unless overridden), final run, document.
 
     Without ``emit`` this is ``_run_simulation`` (server.py:231-266): returns the document, raises
     ``ValueError`` when the target cannot be met.  With ``emit`` it is the body of the SSE endpoint
     (server.py:341-394): the same ``phase`` / ``search_iter`` / ``search_refining`` / ``search_complete`` /
     ``result`` / ``error`` events, in the same order, go to ``emit`` (called on this thread), and an
-    unreachable target is reported as an ``error`` event (returns None) instead of raised."""
+    unreachable target is reported as an ``error`` event (returns None) instead of raised.
+
+    With ``rng="history", market_history=h`` among the simulator's arguments the document gains one key, ``market``
+    (``history.market_document``: the record's months, the block length, its fitted market and ``market_as_recorded`` — whether
+    ``config`` is ``history.with_fitted_market(...)``, the record as it was, rather than the record's shape around the config's
+    own means).  Without a history the document is unchanged key for key."""
     if emit is None:
-        return _run_flow(config, working_months_override, None, result_builder, simulator_kwargs)
+        return _run_flow(config, working_months_override, None, result_builder, simulator_kwargs, market_as_recorded)
     try:
-        return _run_flow(config, working_months_override, emit, result_builder, simulator_kwargs)
+        return _run_flow(config, working_months_override, emit, result_builder, simulator_kwargs, market_as_recorded)
     except Exception as exc:  # the SSE body reports every failure as an event (server.py:395-396)
         emit({"type": "error", "message": str(exc)})
         return None
 
 
-def _run_flow(config, working_months_override, emit, result_builder, simulator_kwargs) -> Optional[dict]:
+def _run_flow(config, working_months_override, emit, result_builder, simulator_kwargs, market_as_recorded=False) -> Optional[dict]:
     simulator = RetirementMonteCarloSimulator(config, **simulator_kwargs)
     curve: List[dict] = []
     if working_months_override is not None:
@@ -446,6 +451,11 @@ def _run_flow(config, working_months_override, emit, result_builder, simulator_k
                     f"({config.num_simulations_main} sims, {wm} working months)")
     simulator.use_final_seeds()
     doc = result_builder(config, simulator, wm, search_curve=curve)
+    history = getattr(simulator, "market_history", None)      # (a stand-in simulator of a caller's own may not have one)
+    if history is not None:
+        from .history import market_document
+
+        doc["market"] = market_document(history, market_as_recorded)
     if emit:
         emit({"type": "result", "data": doc})
     return doc

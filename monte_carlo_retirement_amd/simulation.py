@@ -242,13 +242,23 @@ class RetirementMonteCarloSimulator:
     """Monte Carlo retirement simulator whose paths run on an MI355X (see module docstring)."""
 
     def __init__(self, params_model: Config, main_seed_override: Optional[int] = None, device: int = 0,
-                 rng: str = "philox"):
+                 rng: str = "philox", market_history=None):
         """``rng="philox"`` (default): the engine's counter-based stream; ``path_seed`` = global path
         index.  ``rng="numpy"``: the reference's OWN stream reproduced on the device (SeedSequence ->
         PCG64 -> ziggurat): the same ``seed`` then yields the reference's numbers, ``path_seed`` is the
-        reference's uint32 path seed and `_path_seeds` follows its spawn-and-cache rule (:187-199)."""
-        if rng not in ("philox", "numpy"):
-            raise ValueError("rng must be 'philox' or 'numpy'")
+        reference's uint32 path seed and `_path_seeds` follows its spawn-and-cache rule (:187-199).
+        ``rng="history"`` with ``market_history`` = a :class:`history.MarketHistory`: months resampled in
+        blocks from a recorded market (``include/mcr.h``: MCR_RNG_HISTORY); ``path_seed`` = global path
+        index, the block starts are keyed by the seed, and ``equity_inflation_correlation`` is NOT applied
+        (the record carries its own co-movement).  The record's shocks run around the config's own means
+        and volatilities; ``history.with_fitted_market(config, h)`` gives the config that replays the
+        record as it was.  Probes run one launch per level on this stream."""
+        if rng not in ("philox", "numpy", "history"):
+            raise ValueError("rng must be 'philox', 'numpy' or 'history'")
+        if rng == "history" and market_history is None:
+            raise ValueError("rng='history' needs market_history (a MarketHistory)")
+        if rng != "history" and market_history is not None:
+            raise ValueError(f"market_history is given but rng is {rng!r}: pass rng='history'")
         self.rng = rng
         self.params_model = params_model.model_copy(deep=True)  # simulation.py:136
 
@@ -268,6 +278,16 @@ class RetirementMonteCarloSimulator:
         # Philox counter, so the streams never overlap.
         self._stream_name = "final"
         self._engine_seed = _fold_seed_u64(self.main_seed)
+        self.market_history = None
+        self._history_rng = None
+        if rng == "history":
+            from .history import MarketHistory, as_history
+
+            h = as_history(market_history)
+            if D.is_active():     # every rank must resample the same record: rank 0's, like its seed
+                h = MarketHistory(D.broadcast_array(h.z), D.broadcast_int(h.block_months), h.fitted)
+            self.market_history = h
+            self._history_rng = N.history_rng(self._engine_seed, h.z, h.block_months)   # (owns its copy of the table)
         self.device = int(device)
         #: under torch.distributed, batches smaller than this are computed in full on EVERY rank (identical
         #: results, no communication): a 50 000-path probe is latency-bound (~1 ms) and sharding it would add
@@ -317,7 +337,7 @@ class RetirementMonteCarloSimulator:
         active stream.  NumPy stream: the reference's uint32 seeds, spawned once per (stream, n) and
         cached (:187-199).  Either way the list is the same for every working-month candidate."""
         n = int(num_simulations)
-        if self.rng == "philox":
+        if self.rng != "numpy":
             return list(range(n))
         off = self._np_offset(n)  # children (stream, off .. off+n-1) of SeedSequence(main_seed)
         return [
@@ -346,6 +366,8 @@ class RetirementMonteCarloSimulator:
         """RNG descriptor of an n-path batch on the active stream (int = Philox key)."""
         if self.rng == "philox":
             return self._engine_seed
+        if self.rng == "history":
+            return self._history_rng
         return N.numpy_rng(self.main_seed, child_offset=self._np_offset(n))
 
     # ---- scalar helpers: evaluated by the SAME device functions the path kernel inlines -----------
@@ -404,7 +426,7 @@ class RetirementMonteCarloSimulator:
                 self._local_device(), path_seeds=np.array([int(path_seed)], dtype=np.uint32),
             )[0]
         return E.draw_shocks_host(
-            self._engine_seed, self._stream_id, int(path_seed), 1, int(n_months), self._equity_inflation_rho,
+            self._batch_rng(1), self._stream_id, int(path_seed), 1, int(n_months), self._equity_inflation_rho,
             self._local_device(),
         )[0]
 
@@ -427,7 +449,7 @@ class RetirementMonteCarloSimulator:
             )
         else:
             r = E.run_batch_host(
-                self._current_params(), self._engine_seed, self._stream_id, int(path_seed), 1,
+                self._current_params(), self._batch_rng(1), self._stream_id, int(path_seed), 1,
                 int(working_months), want_bins=False, device=self._local_device(),
             )
         return {
