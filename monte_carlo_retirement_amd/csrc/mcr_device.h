@@ -339,7 +339,8 @@ struct PairCarry { uint32_t w2, w3; };
 enum { kGenPlain = 0, kGenUniform = 1, kGenGeneral = 2 };
 // GF: the launch's GROWTH FORM, a two-bit mask of what its parameters make unnecessary (chosen on the host, mcr_hip.hip:
 // growth_form_of; every value is bit for bit the general form's wherever it may be used).
-//   kGrowthNarrowExp: every argument of exp has k in fexp's narrow window -> fexp<., NARROW> on a CENTRED table (mcr_math.h)
+//   kGrowthNarrowExp: every argument of exp has k in fexp's narrow window -> fexp<., NARROW> on a ROTATED table: the biased shifter's low word is the
+//                     table position, no mask (mcr_math.h)
 //   kGrowthRhoZero:   rho = 0 -> binf_rho is an exact zero and x_inf's first term, fma(+-0 r0, t0, y) = y, is dropped (only the
 //                     sign of a zero sum can differ, and exp maps both zeros to 1)
 enum { kGrowthNarrowExp = 1, kGrowthRhoZero = 2 };

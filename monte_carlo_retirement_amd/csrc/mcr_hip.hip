@@ -418,7 +418,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     static_assert(!EXACT || XS || kExactMonthDefault, "the exact month is instantiated for the generic variants only");
     // GF: the launch's growth form (mcr_device.h: kGrowthNarrowExp | kGrowthRhoZero; masks 0, 1 and 3), for the issue-bound
     // whole-path count-only launches, plain or time-sliced.  Last, with a default: the names of the mask-0 variants are a prefix
-    // of the others'.  A kernel with kGrowthNarrowExp loads the exp2 table CENTRED: growth_rows2 is its only reader there.
+    // of the others'.  A kernel with kGrowthNarrowExp loads the exp2 table ROTATED: growth_rows2 is its only reader there.
     static_assert(GF == 0 || GF == kGrowthNarrowExp || GF == (kGrowthNarrowExp | kGrowthRhoZero), "growth forms: masks 0, 1 and 3");
     static_assert(GF == 0 || (MODE == 0 && RNG == (int)MCR_RNG_PHILOX && !ANNUAL && !INJ && (PHASE == 0 || PHASE == 3) && !SPLIT && !XS),
                   "growth forms exist for the per-path Philox count-only launches (kPerPathPhilox), whole path or time-sliced");
@@ -1269,7 +1269,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
 // Device unit functions exposed for the reference's helper-level tests
 // ---------------------------------------------------------------------------------------------
 // MCR_HELPER_MATH_EXP_FORMS: the path form of exp as the general kernels run it and as the narrow-window growth form runs it
-// (fexp<true, true> on a CENTRED table), side by side: out = (general, narrow).  A kernel of its own: the two forms read
+// (fexp<true, true> on a ROTATED table), side by side: out = (general, narrow).  A kernel of its own: the two forms read
 // different tables.
 __global__ void exp_forms_kernel(const double* in, double* out, int64_t n) {
     __shared__ double tab[kTabDoubles], tab_c[kTabDoubles];

@@ -38,14 +38,17 @@ namespace mcr {
 constexpr int kMathTabBytes = kTabDoubles * (int)sizeof(double);  // 10 240 B of LDS
 
 // every thread of a kBlockThreads-wide workgroup calls this once; caller syncs afterwards
-// CENTRED (the narrow-window exp, fexp<., true>): entries 256 .. 511 of the exp2 part are stored HALVED, 2^(j/512) / 2 — exact,
-// they lie in [sqrt 2, 2) — so that entry k & 511 is 2^(k/512) itself for every k in [-256, 255].  Such a table serves the
-// narrow form only; the other parts (logarithm, sine / cosine) are the same.
-template <bool CENTRED = false>
+// ROTATED (the narrow-window exp, fexp<., true>): position p of the exp2 part holds 2^((p - 256)/512), i.e. entry p - 256 for
+// p >= 256 and HALF of entry p + 256 for p < 256 — exact, those entries lie in [sqrt 2, 2) — so that position k + 256 is
+// 2^(k/512) itself for every k in [-256, 255].  Such a table serves the narrow form only; the other parts (logarithm,
+// sine / cosine) are the same.
+template <bool ROTATED = false>
 __device__ __forceinline__ void load_math_tables(double* lds_tab, int tid, int nthreads) {
+    constexpr int kHalf = 1 << (kExp2Bits - 1);
     for (int i = tid; i < kTabDoubles; i += nthreads) {
-        const double v = kMathTab[i];
-        lds_tab[i] = (CENTRED && i >= kTabExp2 + (1 << (kExp2Bits - 1)) && i < kTabExp2 + (1 << kExp2Bits)) ? 0.5 * v : v;
+        const bool rot = ROTATED && i >= kTabExp2 && i < kTabExp2 + 2 * kHalf;
+        const double v = kMathTab[rot ? kTabExp2 + ((i - kTabExp2) ^ kHalf) : i];
+        lds_tab[i] = (rot && i < kTabExp2 + kHalf) ? 0.5 * v : v;
     }
 }
 
@@ -93,24 +96,35 @@ constexpr double kExpStep = 0x1.62e42fefa39efp-10;   // ln 2 / 512, correctly ro
 constexpr double kExpPathHalf = 0.5 + (0x1.62e42fefa39efp-11 * 0x1.62e42fefa39efp-11) / 40.0;   // 1/2 + a^2/40, a = ln 2 / 1024
 constexpr double kM2Ln2 = -0x1.62e42fefa39efp+0;     // -2 ln 2, correctly rounded
 
-// NARROW (with a table loaded CENTRED, load_math_tables): the form for launches whose every argument has
+// NARROW (with a table loaded ROTATED, load_math_tables): the form for launches whose every argument has
 // k = rint(x 512 / ln 2) in [-256, 255] (kExpNarrowMaxK; the host proves it from the launch's parameters, mcr_hip.hip:
-// growth_form_of).  k >> 9 is then 0 or -1, and the table holds that factor: entry k & 511 is 2^(j/512) for j < 256 and
-// 2^(j/512) / 2 for j >= 256.  fma(t/2, p, t/2) is fma(t, p, t) / 2 exactly (a power-of-two scale of a normal result), so the
-// value is the general form's bit for bit, without the two 32-bit instructions of the exponent insertion.
+// growth_form_of).  k >> 9 is then 0 or -1, and the table holds that factor: position k + 256 is 2^(k/512), stored as
+// 2^(j/512) for k = j >= 0 and as 2^(j/512) / 2 for k = j - 512 < 0.  fma(t/2, p, t/2) is fma(t, p, t) / 2 exactly (a
+// power-of-two scale of a normal result), so the value is the general form's bit for bit, without the two 32-bit
+// instructions of the exponent insertion.
+// The position comes straight from the shifter: the narrow form adds 1.5 2^52 + 256 (kExpNarrowShift).  Both shifters are
+// even integers and both sums lie on the unit grid of [2^52, 2^53), so fma(x, c, S + 256) = fma(x, c, S) + 256 exactly: the
+// same fraction is discarded and a tie sees the same parity.  kf, r and the polynomial are therefore unchanged, and the low
+// word of the sum is k + 256 in [0, 511]: a table position as it stands, with no mask (one v_lshlrev_b32 per exp).
+// (The shifter is left to the compiler, which copies it from an SGPR pair once per half-block of growth_rows2, one v_mov_b64.
+// Pinned in a VGPR pair beside MathRegs' constants it saved 0.7 VALU per path-month more and no time that could be measured,
+// for four VGPRs of the time-sliced headline kernel — LABNOTES R22.)
 constexpr int kExpNarrowMaxK = (1 << (kExp2Bits - 1)) - 1;   // 255: the window is [-256, 255]
+constexpr double kExpShift = 6755399441055744.0;             // 1.5 * 2^52
+constexpr double kExpNarrowShift = kExpShift + (double)(1 << (kExp2Bits - 1));   // exact
 template <bool PATH = false, bool NARROW = false>
 __device__ __forceinline__ double fexp(double x, const double* tab, const MathRegs& R) {
     // k = rint(x 512/ln2) by the shifter trick: the sum lands on the unit grid of [2^52, 2^53), so its low word IS k
     // (two's complement) and subtracting the shifter gives k as a double: no v_rndne / v_cvt_i32.
-    const double shifted = __builtin_fma(x, kExpScale, 6755399441055744.0);   // 1.5 * 2^52
+    constexpr double shift = NARROW ? kExpNarrowShift : kExpShift;    // (NARROW: low word = k + 256, the rotated table's position)
+    const double shifted = __builtin_fma(x, kExpScale, shift);
     const int k = (int)(uint32_t)(uint64_t)__double_as_longlong(shifted);
-    const double kf = shifted - 6755399441055744.0;
+    const double kf = shifted - shift;
     // one-constant reduction: the step's representation error (1.1e-16 relative) times |k| step ~ |x| adds 1.1e-16 |x| to
     // r, i.e. half an ulp of the result per unit of |x| — monthly log-returns are |x| < 2 (a two-constant Cody-Waite
     // reduction only pays for arguments this kernel never sees)
     const double r = __builtin_fma(-kf, kExpStep, x);
-    const double t = tab[kTabExp2 + (k & ((1 << kExp2Bits) - 1))];
+    const double t = NARROW ? tab[kTabExp2 + (uint32_t)k] : tab[kTabExp2 + (k & ((1 << kExp2Bits) - 1))];
     // e^r - 1 = r + r^2 (1/2 + r/6 + r^2/24), |r| <= ln2/1024: the next term r^5/120 < 1.2e-18
     double p;
     if (PATH) {
@@ -127,7 +141,7 @@ __device__ __forceinline__ double fexp(double x, const double* tab, const MathRe
     // t (1 + p) 2^(k >> 9): the scale goes straight into the exponent field of the high word (v_ashr + v_lshl_add_u32,
     // both 32-bit) instead of v_ashr + v_ldexp_f64.  Exact while the result is a normal number (|x| < 700).
     const double v = __builtin_fma(t, p, t);
-    if (NARROW) return v;                                 // (the centred table's t already carries 2^(k >> 9))
+    if (NARROW) return v;                                 // (the rotated table's t already carries 2^(k >> 9))
     const uint64_t vb = (uint64_t)__double_as_longlong(v);
     uint32_t hi;
     asm("v_lshl_add_u32 %0, %1, 20, %2" : "=v"(hi) : "v"(k >> kExp2Bits), "v"((uint32_t)(vb >> 32)));  // (the compiler splits it in three)
