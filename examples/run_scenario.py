@@ -19,6 +19,9 @@ switch to the final seed stream, run the final batch, print the response documen
     python examples/run_scenario.py scenarios/config.json --frontier 180,240,300
     python examples/run_scenario.py scenarios/config.json --grid-months 180,240 --grid-expenses 3000,4000,5000
     python examples/run_scenario.py scenarios/config.json --history record.csv --history-block 12 [--history-as-recorded]
+    python examples/run_scenario.py scenarios/config.json --history record.csv --history-scheme stationary
+    python examples/run_scenario.py scenarios/config.json --history record.csv --history-scheme cohorts \
+        --history-first-month 1926-01 --working-months 240 --cohorts
 
 `--rng numpy` uses the reference's own NumPy stream (same seed -> the reference's numbers); `--rng philox`
 (default) the engine's counter-based stream.  `--history FILE.csv` asks every question of a recorded market instead: months
@@ -26,7 +29,12 @@ resampled in blocks of `--history-block` (default 12) from the file's columns `e
 returns, one row per month, oldest first; `premium` instead of `inv2` when the file holds the premium over inflation) — the
 record's sequence of surprises around the config's own means and volatilities, or, with `--history-as-recorded`, around the
 record's own fitted ones: the history as it was.  The response document then carries a `market` key (months, block_months,
-as_recorded, the fitted values), and so does every other object this script prints.  `--compact` assembles the document from device-side aggregates
+as_recorded, the fitted values), and so does every other object this script prints.  `--history-scheme stationary` makes the
+block lengths geometric with mean `--history-block` (the stationary bootstrap) and `--history-scheme cohorts` draws nothing:
+path i starts at month i of the record (mod its length) and runs it forward, so `--paths` should be a multiple of the
+record's length.  `--cohorts` (with `--history-scheme cohorts` and `--working-months`) prints the historical backtest instead:
+one path per start month, which starts failed, which were the worst, the success share over all starts and over those whose
+horizon fits inside the record; `--history-first-month YYYY-MM` labels the starts.  `--compact` assembles the document from device-side aggregates
 only (no per-path lists: for batches far beyond the UI's); `--streamed` from yearly bins taken inside the path kernel (no
 memory per path at all: any number of paths, under `torchrun` too; bands are known to within one bin).  `--events` writes the progress events the SSE
 endpoint would stream to stderr, one JSON per line.  Without `--full` only the `summary` block (plus timings
@@ -81,6 +89,11 @@ def main() -> int:
     ap.add_argument("--history", default=None, metavar="FILE.csv",
                     help="resample months from this record (columns equity, inflation, inv2 | premium) instead of drawing them")
     ap.add_argument("--history-block", type=int, default=12, help="--history: months per resampled block")
+    ap.add_argument("--history-scheme", choices=["block", "stationary", "cohorts"], default="block",
+                    help="--history: fixed blocks, geometric block lengths of mean --history-block, or path i from month i of the record")
+    ap.add_argument("--history-first-month", default=None, metavar="YYYY-MM", help="--history: the month of the record's first row (labels cohorts)")
+    ap.add_argument("--cohorts", action="store_true",
+                    help="--history-scheme cohorts: print the historical backtest at --working-months, one path per start month, instead")
     ap.add_argument("--history-as-recorded", action="store_true",
                     help="--history: use the record's own fitted means and volatilities instead of the config's")
     ap.add_argument("--paths", type=int, default=None, help="override num_simulations_main")
@@ -167,6 +180,12 @@ def main() -> int:
     args.market_history = None
     if args.history_as_recorded and not args.history:
         ap.error("--history-as-recorded goes with --history")
+    if (args.history_scheme != "block" or args.history_first_month is not None) and not args.history:
+        ap.error("--history-scheme / --history-first-month go with --history")
+    if args.cohorts and not (args.history and args.history_scheme == "cohorts"):
+        ap.error("--cohorts needs --history with --history-scheme cohorts")
+    if args.cohorts and args.working_months is None:
+        ap.error("--cohorts needs --working-months")
     if args.history:
         if args.rng != "philox":
             ap.error("--history is a random stream of its own: leave --rng out")
@@ -175,7 +194,11 @@ def main() -> int:
         with open(args.history, "r", encoding="utf-8") as fh:
             columns = [c.strip() for c in fh.readline().split(",")]
         over = {"inv2": None, "premium": "premium"} if "premium" in columns and "inv2" not in columns else {}
-        args.market_history = MarketHistory.from_csv(args.history, block_months=args.history_block, **over)
+        try:
+            args.market_history = MarketHistory.from_csv(args.history, block_months=args.history_block, scheme=args.history_scheme,
+                                                         first_month=args.history_first_month, **over)
+        except ValueError as e:
+            ap.error(str(e))
         args.rng = "history"
         if args.history_as_recorded:
             config = with_fitted_market(config, args.market_history)
@@ -190,6 +213,8 @@ def main() -> int:
         if args.events and rank0 and event["type"] != "result":
             print(json.dumps(event), file=sys.stderr)
 
+    if args.cohorts:
+        return cohorts(args, config, world, rank0)
     if args.max_expenses:
         return max_expenses(args, config, world, rank0)
     if args.min_contribution:
@@ -240,6 +265,19 @@ def main() -> int:
         dist.barrier()
         dist.destroy_process_group()
     return rc
+
+
+def cohorts(args, config: Config, world: int, rank0: bool) -> int:
+    """Every rank replays the (small) record's cohorts in full; rank 0 prints."""
+    out = _simulator(args, config).historical_cohorts(args.working_months).to_document()
+    if rank0:
+        print(json.dumps(_with_market(args, out)))
+    if world > 1:
+        import torch.distributed as dist
+
+        dist.barrier()
+        dist.destroy_process_group()
+    return 0
 
 
 def max_expenses(args, config: Config, world: int, rank0: bool) -> int:

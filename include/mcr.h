@@ -80,13 +80,40 @@ extern "C" {
  *                  was" under its own fitted parameters, and "the history's shape around other means" under any
  *                  other mcr_params: the growth factors are made from Z with the launch's parameters.
  *                  Whole-path launches only: the fan-out probe forms answer MCR_ERR_UNSUPPORTED inside the probe
- *                  entry points, which then run one launch per level.  Kinds 0 and 1 never read the three fields.
+ *                  entry points, which then run one launch per level.  Kinds 0 and 1 never read the history fields.
+ *
+ *                  `history_scheme` chooses which row of the record shock row r reads; the rule above is
+ *                  MCR_HISTORY_BLOCK (0, what a zeroed descriptor asks for).  The other two, with the same H, B and r:
+ *
+ *                  MCR_HISTORY_STATIONARY  the stationary bootstrap (Politis & Romano 1994): block lengths geometric
+ *                  with mean B instead of all equal, so no month of a path is a seam in every path and the resampled
+ *                  series is stationary.
+ *                      q = r >> 1, a = 2 (r & 1)
+ *                      (w0..w3) = Philox4x32-10(counter = (path_lo, path_hi, q, stream_id), key = (seed_lo, seed_hi))
+ *                      u = w[a], v = w[a + 1]                               one Philox block serves two months
+ *                      restart = (r == 0) || (((uint64_t)u * B) >> 32) == 0  probability ceil(2^32 / B) / 2^32: mean
+ *                                                                            block length B to within B / 2^32
+ *                      row_r   = restart ? ((uint64_t)v * H) >> 32 : (row_{r-1} + 1) mod H
+ *                  B = 1 restarts every month (an i.i.d. month bootstrap); B = 2^31 - 1 practically never restarts
+ *                  after row 0.  Row r is reached by walking from row 0, which always restarts, so it is still a pure
+ *                  function of (seed, stream_id, path, r).  The counters coincide with some of the block rule's at the
+ *                  same seed; that does not matter, because one launch has one scheme.
+ *
+ *                  MCR_HISTORY_COHORTS  the every-start replay, the historical backtest itself: path i starts at month
+ *                  i mod H of the record and runs it forward.
+ *                      row_r = ((path mod H) + r) mod H                      path = the 64-bit global path index
+ *                  No random numbers: philox_seed and history_block are not read (but validated as before).  Paths i
+ *                  and i + H are the same path; a count over n paths weighs the starts equally when n is a multiple
+ *                  of H.
  */
 #define MCR_RNG_PHILOX 0u
 #define MCR_RNG_NUMPY 1u
 #define MCR_RNG_HISTORY 2u
 #define MCR_MAX_ENTROPY_WORDS 8
 #define MCR_MAX_HISTORY_MONTHS 2048 /* 170 years: 48 KB of growth factors in a workgroup's LDS */
+#define MCR_HISTORY_BLOCK      0u   /* fixed block length */
+#define MCR_HISTORY_STATIONARY 1u   /* geometric block lengths of mean history_block */
+#define MCR_HISTORY_COHORTS    2u   /* path i starts at month i mod history_months */
 typedef struct mcr_rng {
     uint32_t kind;
     uint32_t n_entropy_words;                /* 1..MCR_MAX_ENTROPY_WORDS (numpy) */
@@ -97,7 +124,9 @@ typedef struct mcr_rng {
     const double* history;                   /* history: Z[history_months][3], finite; DEVICE ptr for the hip_stream entry
                                                 points, HOST ptr for *_host_rng (uploaded like path_seeds) */
     uint32_t history_months;                 /* history: 1..MCR_MAX_HISTORY_MONTHS */
-    uint32_t history_block;                  /* history: block length in months, 1..2^31 - 1 */
+    uint32_t history_block;                  /* history: block length in months (stationary: its mean), 1..2^31 - 1 */
+    uint32_t history_scheme;                 /* history: MCR_HISTORY_BLOCK / _STATIONARY / _COHORTS */
+    uint32_t history_reserved;               /* 0 */
 } mcr_rng;
 
 /* One `OtherIncomeStreamConfig` (backend/config.py:12-47), raw field values. */

@@ -25,6 +25,9 @@ MCR_RNG_NUMPY = 1
 MCR_RNG_HISTORY = 2
 MCR_MAX_ENTROPY_WORDS = 8
 MCR_MAX_HISTORY_MONTHS = 2048
+MCR_HISTORY_BLOCK = 0
+MCR_HISTORY_STATIONARY = 1
+MCR_HISTORY_COHORTS = 2
 MCR_DEVICE_ALL = -2
 MCR_MAX_HIST_BINS = 4096
 MCR_MAX_YEAR_BINS = 512  # bins per row of the yearly-bins tables (mcr_year_bins)
@@ -158,6 +161,8 @@ class McrRng(C.Structure):
         ("history", C.c_void_p),
         ("history_months", C.c_uint32),
         ("history_block", C.c_uint32),
+        ("history_scheme", C.c_uint32),
+        ("history_reserved", C.c_uint32),
     ]
 
 
@@ -190,9 +195,11 @@ def numpy_rng(main_seed: int, child_offset: int = 0, path_seeds_ptr: int = 0) ->
     return r
 
 
-def history_rng(seed: int, table, block: int) -> McrRng:
+def history_rng(seed: int, table, block: int, scheme: int = 0) -> McrRng:
     """The block bootstrap of a recorded market (include/mcr.h: MCR_RNG_HISTORY): ``table`` = Z[months][3] standard shocks
-    (equity, inflation, premium), ``block`` = months per block, ``seed`` = the Philox key of the block starts.  The
+    (equity, inflation, premium), ``block`` = months per block, ``seed`` = the Philox key of the block starts, ``scheme`` =
+    MCR_HISTORY_BLOCK (fixed blocks), MCR_HISTORY_STATIONARY (geometric block lengths of mean ``block``) or
+    MCR_HISTORY_COHORTS (path i starts at month i mod months; neither ``seed`` nor ``block`` is read).  The
     descriptor points at HOST memory — what the ``*_host_rng`` entry points take — and keeps the array alive as
     ``_history_table``; ``engine`` swaps in a device copy for the entry points that want one."""
     import numpy as np
@@ -206,12 +213,15 @@ def history_rng(seed: int, table, block: int) -> McrRng:
         raise ValueError(f"history block: {block} months (1..2^31 - 1)")
     if not np.all(np.isfinite(z)):
         raise ValueError("history table: every entry must be finite")
+    if isinstance(scheme, bool) or scheme not in (MCR_HISTORY_BLOCK, MCR_HISTORY_STATIONARY, MCR_HISTORY_COHORTS):
+        raise ValueError(f"history scheme: {scheme!r} (0 block, 1 stationary, 2 cohorts)")
     r = McrRng()
     r.kind = MCR_RNG_HISTORY
     r.philox_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     r.history = z.ctypes.data
     r.history_months = z.shape[0]
     r.history_block = int(block)
+    r.history_scheme = int(scheme)
     r._history_table = z
     return r
 

@@ -142,9 +142,10 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
 // order, so the cursor steps: the row of the record goes up by one and wraps, and every B-th month a new start is taken
 // (every 4 B-th a new Philox block).  r, j and k are wave-uniform (the month index is): scalar registers and scalar
 // branches; per lane the cursor is the row and the block's four words.  Any other row (the first one, or a caller that
-// skips) is reached from its definition, by division.
+// skips) is reached from its definition, by division.  The other two schemes of the header use the same cursor: the stationary
+// bootstrap its row and the words of Philox block r >> 1, the cohort replay its row alone.
 struct HistoryCursor {
-    uint32_t w[4];   // Philox block k >> 2 of the path
+    uint32_t w[4];   // Philox block k >> 2 of the path (stationary: block r >> 1)
     uint32_t cur;    // the row of the record at shock row r
     int r;           // the shock row the cursor stands at (-2: none yet)
     uint32_t j, k;   // r = k B + j, j < B
@@ -155,9 +156,36 @@ __device__ __forceinline__ uint32_t history_block_start(const HistoryCursor& C, 
     const uint32_t x = q == 0u ? C.w[0] : q == 1u ? C.w[1] : q == 2u ? C.w[2] : C.w[3];
     return __umulhi(x, H);     // ((uint64_t)x * H) >> 32 < H
 }
-__device__ __forceinline__ void history_seek(HistoryCursor& C, int r, uint32_t H, uint32_t B, uint64_t seed, uint32_t stream_id, uint64_t path) {
+// MCR_HISTORY_STATIONARY: row rr, the cursor standing at row rr - 1 (or anywhere, for rr = 0).  Every even row a new Philox
+// block (wave-uniform timing); per lane a compare and a select, no branch: umulhi(u, B) == 0 restarts at umulhi(v, H).
+__device__ __forceinline__ void history_step_stationary(HistoryCursor& C, int rr, uint32_t H, uint32_t B, uint64_t seed, uint32_t stream_id, uint64_t path) {
+    uint32_t u = C.w[2], v = C.w[3];      // an odd row: the second half of the block its predecessor made
+    if ((rr & 1) == 0) {
+        uint32_t w[4];
+        philox4x32_10((uint32_t)path, (uint32_t)(path >> 32), (uint32_t)rr >> 1, stream_id, (uint32_t)seed, (uint32_t)(seed >> 32), w);
+        u = w[0]; v = w[1]; C.w[2] = w[2]; C.w[3] = w[3];
+    }
+    const uint32_t next = C.cur + 1u == H ? 0u : C.cur + 1u;
+    C.cur = (rr == 0 || __umulhi(u, B) == 0u) ? __umulhi(v, H) : next;
+}
+// SCHEMES = false: the block rule alone, the code it always was (the kernels of MCR_HISTORY_BLOCK launches keep their
+// instructions and registers).  SCHEMES = true: the other two rules; `scheme` (include/mcr.h: MCR_HISTORY_STATIONARY or
+// MCR_HISTORY_COHORTS) is launch-constant, a scalar branch.
+template <bool SCHEMES = false>
+__device__ __forceinline__ void history_seek(HistoryCursor& C, int r, uint32_t H, uint32_t B, uint32_t scheme, uint64_t seed, uint32_t stream_id, uint64_t path) {
     if (r == C.r) return;      // (the reference's clamp repeats the last row)
-    if (r == C.r + 1) {
+    if constexpr (SCHEMES) {
+        if (scheme == MCR_HISTORY_STATIONARY) {
+            if (r != C.r + 1)      // (no launch does this: whole-path launches start at row 0) walk from row 0, which restarts
+                for (int rr = 0; rr < r; ++rr) history_step_stationary(C, rr, H, B, seed, stream_id, path);
+            history_step_stationary(C, r, H, B, seed, stream_id, path);
+        } else if (r == C.r + 1 && C.r >= 0) {      // MCR_HISTORY_COHORTS: the record run forward
+            if (++C.cur == H) C.cur = 0u;
+        } else {               // once per path: path mod H in 32-bit pieces, 2^32 mod H = (2^32 - 1) mod H + 1 (or H itself: the same class)
+            const uint32_t t = 0xFFFFFFFFu % H + 1u;
+            C.cur = (((uint32_t)(path >> 32) % H) * t + (uint32_t)path % H + (uint32_t)r % H) % H;      // < 2^23: H <= MCR_MAX_HISTORY_MONTHS
+        }
+    } else if (r == C.r + 1) {
         if (++C.j == B) {
             C.j = 0u;
             if ((++C.k & 3u) == 0u)

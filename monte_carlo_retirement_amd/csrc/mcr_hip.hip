@@ -40,6 +40,9 @@ namespace mcr {
 // K1: the per-path state machine (_run_single_simulation_path, simulation.py:476-950)
 // ---------------------------------------------------------------------------------------------
 constexpr int kMaxSegments = 8;
+// path_kernel's RNG parameter is mcr_rng.kind, and for a history launch of a scheme other than MCR_HISTORY_BLOCK this value:
+// kernels of their own (history_seek<true>, mcr_device.h), so that the block rule's kernels stay the instructions they were
+constexpr int kRngHistorySchemes = 3;
 struct KernelIO {
     uint64_t seed;           // Philox key
     uint64_t path_begin;
@@ -50,7 +53,7 @@ struct KernelIO {
     // MCR_RNG_NUMPY (mcr_numpy_rng.h).  MCR_RNG_HISTORY reads none of it: its table, length and block length share the bytes
     // of the seed-word count, the first seed word and the explicit seeds, so the kernel arguments keep their size and layout
     union { uint32_t n_entropy; uint32_t history_months; };
-    union { uint32_t entropy[MCR_MAX_ENTROPY_WORDS]; uint32_t history_block; };
+    union { uint32_t entropy[MCR_MAX_ENTROPY_WORDS]; struct { uint32_t history_block, history_scheme; }; };   // (the scheme over entropy[1])
     uint64_t child_offset;
     union {
         const uint32_t* path_seeds;  // [n_paths] explicit seeds or nullptr
@@ -466,7 +469,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     // v_add_u32 0.  DYNAMIC: the NumPy ziggurat tables, [n_lock_slots][kBlock] doubles (frozen nominal stream amounts),
     // the block counters.  (The history stream's factor table stands where the ziggurat tables do.)
     constexpr bool kStaged = RNG == (int)MCR_RNG_PHILOX && !INJ;
-    constexpr bool kHistory = RNG == (int)MCR_RNG_HISTORY && !INJ;   // (its math tables are needed before the first month only: dynamic LDS, below)
+    constexpr bool kHistory = (RNG == (int)MCR_RNG_HISTORY || RNG == kRngHistorySchemes) && !INJ;   // (its math tables are needed before the first month only: dynamic LDS, below)
     __shared__ __align__(16) double tab_s[kHistory ? 1 : kTabDoubles];
     constexpr int kStageLen = (kAsmFan ? kPartsPerPair : 6) * kPaths;   // = kStageDoubles for kBlock-path workgroups (PHASE 9 stages the normals' parts)
     __shared__ __align__(16) double stage_s[kStaged ? (SPLIT ? 2 : 1) * kStageLen : 1];
@@ -636,7 +639,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         }
         if constexpr (kHistory) {
             const int r = row < P.shock_rows - 1 ? row : P.shock_rows - 1;  // :692, like an injected row
-            history_seek(HC, r, io.history_months, io.history_block, io.seed, io.stream_id, path);
+            history_seek<RNG == kRngHistorySchemes>(HC, r, io.history_months, io.history_block, io.history_scheme, io.seed, io.stream_id, path);
             const double* const c = hist_tab + 3u * HC.cur;
             g1 = c[0]; ginf = c[1]; g2 = c[2];
             return;
@@ -1483,14 +1486,16 @@ __global__ void np_shocks_kernel(const KernelIO io, int32_t n_months, double rho
 // The history stream's rows (include/mcr.h: MCR_RNG_HISTORY): out[n_paths][n_months][3] = Z[row]; one thread per path, rows in
 // order through the path kernel's cursor
 __global__ void history_shocks_kernel(uint64_t seed, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths, int32_t n_months,
-                                      const double* __restrict__ z, uint32_t history_months, uint32_t history_block, double* out) {
+                                      const double* __restrict__ z, uint32_t history_months, uint32_t history_block, uint32_t history_scheme,
+                                      double* out) {
     const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = p < n_paths;
     const uint64_t q = valid ? p : n_paths - 1;       // (tail lanes shadow the last path: the cursor's branches stay wave-uniform)
     HistoryCursor C = history_cursor();
     double* o = out + (size_t)q * 3u * (size_t)n_months;
     for (int32_t m = 0; m < n_months; ++m) {
-        history_seek(C, m, history_months, history_block, seed, stream_id, path_begin + q);
+        if (history_scheme == MCR_HISTORY_BLOCK) history_seek<false>(C, m, history_months, history_block, history_scheme, seed, stream_id, path_begin + q);
+        else history_seek<true>(C, m, history_months, history_block, history_scheme, seed, stream_id, path_begin + q);
         if (valid) { o[3 * m + 0] = z[3u * C.cur + 0]; o[3 * m + 1] = z[3u * C.cur + 1]; o[3 * m + 2] = z[3u * C.cur + 2]; }
     }
 }
@@ -2135,6 +2140,14 @@ static int check_rng(const mcr_rng* rng, bool host_table = false) {
             set_error("history rng: history_block = %u (1..%d)", rng->history_block, INT32_MAX);
             return MCR_ERR_INVALID_ARG;
         }
+        if (rng->history_scheme > MCR_HISTORY_COHORTS) {
+            set_error("history rng: history_scheme = %u (0..%u)", rng->history_scheme, MCR_HISTORY_COHORTS);
+            return MCR_ERR_INVALID_ARG;
+        }
+        if (rng->history_reserved != 0u) {
+            set_error("history rng: history_reserved = %u (must be 0)", rng->history_reserved);
+            return MCR_ERR_INVALID_ARG;
+        }
         if (host_table)
             for (uint32_t k = 0; k < 3u * rng->history_months; ++k)
                 if (!std::isfinite(rng->history[k])) {
@@ -2154,6 +2167,11 @@ static int check_rng(const mcr_rng* rng, bool host_table = false) {
 // without a GPU (the other kinds keep their order: device first)
 static int check_history_host(const mcr_rng* rng) { return rng && rng->kind == MCR_RNG_HISTORY ? check_rng(rng, true) : MCR_OK; }
 
+// path_kernel's RNG template argument for a launch on this descriptor
+static uint32_t kernel_rng_kind(const mcr_rng* rng) {
+    return rng->kind == MCR_RNG_HISTORY && rng->history_scheme != MCR_HISTORY_BLOCK ? (uint32_t)kRngHistorySchemes : rng->kind;
+}
+
 static void fill_io_rng(KernelIO& io, const mcr_rng* rng, const uint32_t* device_path_seeds) {
     io.seed = rng->philox_seed;
     io.n_entropy = rng->n_entropy_words;
@@ -2162,6 +2180,7 @@ static void fill_io_rng(KernelIO& io, const mcr_rng* rng, const uint32_t* device
     io.path_seeds = device_path_seeds;
     if (rng->kind == MCR_RNG_HISTORY) {      // (a DEVICE table here: the fields lie over the NumPy stream's, KernelIO)
         io.history = rng->history; io.history_months = rng->history_months; io.history_block = rng->history_block;
+        io.history_scheme = rng->history_scheme;
     }
 }
 
@@ -2214,6 +2233,7 @@ template <typename F> static inline void for_output_mode(int mode, F&& f) {
     if (mode == 2) f(int_c<2>{}); else if (mode == 1) f(int_c<1>{}); else f(int_c<0>{});
 }
 
+// rng_kind: mcr_rng.kind, or kernel_rng_kind() of the descriptor (a history launch's scheme chooses between two sets of kernels).
 // f(R, T, A, X, E) = (stream, tax mask, annual-gains tax, extended streams, exact month) of a whole-path launch (PHASE 0, not
 // split, no injection) — the one place that says which variants such a launch has: the generic form (mask 3, annual) for
 // extended streams / the exact month; the engine's own stream per tax mask; the NumPy and history streams taxed / untaxed
@@ -2232,7 +2252,8 @@ template <typename F> static inline void for_whole_path_variant(const DevParams&
             });
         }
     };
-    if (rng_kind == MCR_RNG_HISTORY) with_stream(int_c<(int)MCR_RNG_HISTORY>{});
+    if (rng_kind == (uint32_t)kRngHistorySchemes) with_stream(int_c<kRngHistorySchemes>{});
+    else if (rng_kind == MCR_RNG_HISTORY) with_stream(int_c<(int)MCR_RNG_HISTORY>{});
     else if (rng_kind == MCR_RNG_NUMPY) with_stream(int_c<(int)MCR_RNG_NUMPY>{});
     else with_stream(int_c<0>{});
 }
@@ -2362,7 +2383,7 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
     // the whole-path variants of the engine's streams (for_whole_path_variant), output mode M
     auto launch_whole_path = [&]() {
         for_output_mode(mode, [&](auto M) {
-            for_whole_path_variant(d, rng_kind, xs, exact, [&](auto R, auto T, auto A, auto X, auto EX) {
+            for_whole_path_variant(d, kernel_rng_kind(rng), xs, exact, [&](auto R, auto T, auto A, auto X, auto EX) {
                 if constexpr (kHasGrowthForms<decltype(M)::value, decltype(R)::value, decltype(A)::value, decltype(X)::value>) {
                     for_growth_form(gf, [&](auto G) {
                         for_month_form<decltype(T)::value>(mf, [&](auto F) {
@@ -2519,7 +2540,7 @@ static int launch_year_bins(const mcr_params* p, const mcr_rng* rng, uint32_t st
     rc = side.attach(d, extra, grid.x, stream);
     if (rc != MCR_OK) { (void)side.release(stream); return rc; }
     const DevParams* const no_cand = nullptr;
-    for_whole_path_variant(d, rng_kind, xs, exact, [&](auto R, auto T, auto A, auto X, auto EX) {
+    for_whole_path_variant(d, kernel_rng_kind(rng), xs, exact, [&](auto R, auto T, auto A, auto X, auto EX) {
         hipLaunchKernelGGL((path_kernel<3, decltype(R)::value, decltype(T)::value, decltype(A)::value, false, 0, false, decltype(X)::value,
                                         (decltype(X)::value && decltype(EX)::value) || kExactMonthDefault>),
                            grid, block, lds, stream, d, io, no_cand);
@@ -4119,7 +4140,7 @@ int mcr_draw_shocks_host_rng(const mcr_rng* rng, uint32_t stream_id, uint64_t pa
         if (e == hipSuccess) e = hipMemcpy(d_z, rng->history, z_bytes, hipMemcpyHostToDevice);
         if (e != hipSuccess) return hip_fail(e, "history table upload");
         hipLaunchKernelGGL(history_shocks_kernel, dim3((unsigned)((n_paths + 63) / 64)), dim3(64), 0, nullptr, seed, stream_id, path_begin,
-                           n_paths, n_months, d_z, rng->history_months, rng->history_block, d);
+                           n_paths, n_months, d_z, rng->history_months, rng->history_block, rng->history_scheme, d);
     } else if (rng->kind == MCR_RNG_NUMPY) {
         KernelIO io;
         std::memset(&io, 0, sizeof(io));

@@ -6,6 +6,17 @@ from a record in blocks of ``block_months`` consecutive months, each block start
 around the record's end (``include/mcr.h``: ``MCR_RNG_HISTORY`` states the rule).  Inside a block the record's fat tails,
 its volatility clustering and the co-movement of its series are kept as they were.
 
+``scheme`` chooses the resampling rule (``include/mcr.h`` states all three as integer recipes):
+
+* ``"block"`` (the default): every block ``block_months`` long;
+* ``"stationary"``: the stationary bootstrap of Politis & Romano — block lengths geometric with MEAN ``block_months``, so
+  no month of a path is a seam in every path and the resampled series is stationary;
+* ``"cohorts"``: no resampling at all — path ``i`` starts at month ``i mod months`` of the record and runs it forward, the
+  historical backtest itself ("would this plan have survived retiring into 1929?").  ``block_months`` is not used.  A
+  success probability over ``n`` paths is the share over the starts ``0 .. n - 1 mod months``: ``n`` should be a multiple
+  of the record's length, or some starts count once more than others
+  (``RetirementMonteCarloSimulator.historical_cohorts`` runs exactly one path per start and says which start did what).
+
 The table holds STANDARD shocks ``z`` — what ``exp(mu_log / 12 + sigma_log / sqrt(12) z)`` turns into a month's growth
 factor — so one record has two readings:
 
@@ -23,6 +34,7 @@ from __future__ import annotations
 
 import csv
 import math
+import re
 from typing import Dict, Optional, Sequence
 
 import numpy as np
@@ -32,6 +44,14 @@ from .config import Config
 MAX_HISTORY_MONTHS = 2048      # include/mcr.h: MCR_MAX_HISTORY_MONTHS
 MAX_BLOCK_MONTHS = 2**31 - 1
 _SERIES = ("inv1", "inflation", "inv2_premium")
+SCHEMES = ("block", "stationary", "cohorts")      # include/mcr.h: MCR_HISTORY_BLOCK / _STATIONARY / _COHORTS, in this order
+
+
+def month_label(first_month: str, offset: int) -> str:
+    """``"YYYY-MM"`` of the month ``offset`` months after ``first_month``."""
+    year, month = int(first_month[:4]), int(first_month[5:7])
+    t = year * 12 + (month - 1) + int(offset)
+    return f"{t // 12:04d}-{t % 12 + 1:02d}"
 
 
 def _log_to_arithmetic(mu_log: float, sigma_log: float):
@@ -45,9 +65,12 @@ class MarketHistory:
     finite.  ``block_months``: the block length of the bootstrap (1 = i.i.d. months; at least the horizon = one start per
     path, the record run forward from it).  ``fitted``: the annual log parameters the table was standardised with
     (``{"inv1" | "inflation" | "inv2_premium": (mu_log, sigma_log)}``) and the sample correlation, when it was built from
-    returns; a table given directly has none."""
+    returns; a table given directly has none.  ``scheme``: ``"block"``, ``"stationary"`` (``block_months`` is then the MEAN
+    block length) or ``"cohorts"`` (``block_months`` is not used), see the module's text.  ``first_month``: an optional
+    ``"YYYY-MM"`` label of row 0, used only to label cohorts."""
 
-    def __init__(self, z, block_months: int = 12, fitted: Optional[Dict[str, object]] = None):
+    def __init__(self, z, block_months: int = 12, fitted: Optional[Dict[str, object]] = None, *, scheme: str = "block",
+                 first_month: Optional[str] = None):
         arr = np.array(z, dtype=np.float64, order="C")
         if arr.ndim != 2 or arr.shape[1] != 3:
             raise ValueError(f"z: shape {arr.shape} is not (months, 3)")
@@ -57,17 +80,24 @@ class MarketHistory:
             raise ValueError("z: every entry must be finite")
         if isinstance(block_months, bool) or int(block_months) != block_months or not 1 <= int(block_months) <= MAX_BLOCK_MONTHS:
             raise ValueError(f"block_months: {block_months!r} is not an integer in 1..2^31 - 1")
+        if not isinstance(scheme, str) or scheme not in SCHEMES:
+            raise ValueError(f"scheme: {scheme!r} is not one of {', '.join(repr(s) for s in SCHEMES)}")
+        if first_month is not None and (not isinstance(first_month, str) or not re.fullmatch(r"\d{4}-(0[1-9]|1[0-2])", first_month)):
+            raise ValueError(f"first_month: {first_month!r} is not a 'YYYY-MM' month")
         arr.setflags(write=False)
         self.z = arr
         self.block_months = int(block_months)
         self.fitted = dict(fitted) if fitted is not None else None
+        self.scheme = scheme
+        self.first_month = first_month
 
     @property
     def months(self) -> int:
         return int(self.z.shape[0])
 
     @classmethod
-    def from_monthly_returns(cls, equity, inflation, inv2=None, premium=None, block_months: int = 12) -> "MarketHistory":
+    def from_monthly_returns(cls, equity, inflation, inv2=None, premium=None, block_months: int = 12, *, scheme: str = "block",
+                             first_month: Optional[str] = None) -> "MarketHistory":
         """From SIMPLE monthly returns (0.01 = +1 %): the equity series, the inflation series, and exactly one of ``inv2``
         (the second asset's nominal return; its premium gross is its gross over inflation's) or ``premium`` (already over
         inflation).  Per series: ``z = (ln g - m) / s`` with the sample mean and standard deviation (ddof = 0) of the log
@@ -105,11 +135,12 @@ class MarketHistory:
             fitted[key] = (12.0 * m, math.sqrt(12.0) * s)
         moving = fitted["inv1"][1] > 0.0 and fitted["inflation"][1] > 0.0      # (a constant series correlates with nothing)
         fitted["equity_inflation_correlation"] = float(np.corrcoef(logs[0], logs[1])[0, 1]) if moving else 0.0
-        return cls(z, block_months, fitted)
+        return cls(z, block_months, fitted, scheme=scheme, first_month=first_month)
 
     @classmethod
     def from_csv(cls, path: str, equity: str = "equity", inflation: str = "inflation", inv2: Optional[str] = "inv2",
-                 premium: Optional[str] = None, block_months: int = 12) -> "MarketHistory":
+                 premium: Optional[str] = None, block_months: int = 12, *, scheme: str = "block",
+                 first_month: Optional[str] = None) -> "MarketHistory":
         """From a CSV file with a header line and one row per month, oldest first; the arguments name its columns of simple
         monthly returns.  Give ``premium`` (and ``inv2=None``) when the file holds the premium over inflation."""
         if (inv2 is None) == (premium is None):
@@ -128,7 +159,7 @@ class MarketHistory:
                     except (TypeError, ValueError):
                         raise ValueError(f"{k}: column {name!r}, line {line} of {path}: {row[name]!r} is not a number") from None
         return cls.from_monthly_returns(cols["equity"], cols["inflation"], inv2=cols.get("inv2"), premium=cols.get("premium"),
-                                        block_months=block_months)
+                                        block_months=block_months, scheme=scheme, first_month=first_month)
 
     def fitted_assumptions(self) -> Dict[str, float]:
         """The ``Config`` fields that replay the record as it was: arithmetic annual means and volatilities (the inverse of
@@ -154,8 +185,13 @@ def with_fitted_market(config: Config, history: MarketHistory) -> Config:
 
 
 def market_document(history: MarketHistory, as_recorded: bool) -> Dict[str, object]:
-    """What a response document says about the history it was computed with (``examples/run_scenario.py``: key ``market``)."""
+    """What a response document says about the history it was computed with (``examples/run_scenario.py``: key ``market``).
+    ``scheme`` appears for the schemes other than ``"block"``, ``first_month`` when it was given."""
     doc: Dict[str, object] = {"months": history.months, "block_months": history.block_months, "as_recorded": bool(as_recorded)}
+    if history.scheme != "block":
+        doc["scheme"] = history.scheme
+    if history.first_month is not None:
+        doc["first_month"] = history.first_month
     if history.fitted is not None:
         doc["fitted"] = history.fitted_assumptions()
     return doc
@@ -167,4 +203,4 @@ def as_history(value) -> MarketHistory:
     return value
 
 
-__all__: Sequence[str] = ("MarketHistory", "with_fitted_market", "market_document", "MAX_HISTORY_MONTHS")
+__all__: Sequence[str] = ("MarketHistory", "with_fitted_market", "market_document", "MAX_HISTORY_MONTHS", "SCHEMES")

@@ -406,7 +406,7 @@ def run_scenario(config: Config, working_months_override: Optional[int] = None,
     unreachable target is reported as an ``error`` event (returns None) instead of raised.
 
     With ``rng="history", market_history=h`` among the simulator's arguments the document gains one key, ``market``
-    (``history.market_document``: the record's months, the block length, its fitted market and ``market_as_recorded`` — whether
+    (``history.market_document``: the record's months, the block length, the scheme when it is not ``"block"``, its fitted market and ``market_as_recorded`` — whether
     ``config`` is ``history.with_fitted_market(...)``, the record as it was, rather than the record's shape around the config's
     own means).  Without a history the document is unchanged key for key."""
     if emit is None:

@@ -252,7 +252,10 @@ class RetirementMonteCarloSimulator:
         index, the block starts are keyed by the seed, and ``equity_inflation_correlation`` is NOT applied
         (the record carries its own co-movement).  The record's shocks run around the config's own means
         and volatilities; ``history.with_fitted_market(config, h)`` gives the config that replays the
-        record as it was.  Probes run one launch per level on this stream."""
+        record as it was.  Probes run one launch per level on this stream.  The history's ``scheme`` chooses
+        the rule: fixed blocks, the stationary bootstrap, or ``"cohorts"`` — path i starts at month
+        i mod H of the H-month record, so a success probability over n paths is the share over the
+        starts 0 .. n - 1 mod H and n should be a multiple of H (`historical_cohorts` runs exactly H)."""
         if rng not in ("philox", "numpy", "history"):
             raise ValueError("rng must be 'philox', 'numpy' or 'history'")
         if rng == "history" and market_history is None:
@@ -281,13 +284,14 @@ class RetirementMonteCarloSimulator:
         self.market_history = None
         self._history_rng = None
         if rng == "history":
-            from .history import MarketHistory, as_history
+            from .history import SCHEMES, MarketHistory, as_history
 
             h = as_history(market_history)
-            if D.is_active():     # every rank must resample the same record: rank 0's, like its seed
-                h = MarketHistory(D.broadcast_array(h.z), D.broadcast_int(h.block_months), h.fitted)
+            if D.is_active():     # every rank must resample the same record by the same rule: rank 0's, like its seed
+                h = MarketHistory(D.broadcast_array(h.z), D.broadcast_int(h.block_months), h.fitted,
+                                  scheme=SCHEMES[D.broadcast_int(SCHEMES.index(h.scheme))], first_month=h.first_month)
             self.market_history = h
-            self._history_rng = N.history_rng(self._engine_seed, h.z, h.block_months)   # (owns its copy of the table)
+            self._history_rng = N.history_rng(self._engine_seed, h.z, h.block_months, SCHEMES.index(h.scheme))   # (owns its copy of the table)
         self.device = int(device)
         #: under torch.distributed, batches smaller than this are computed in full on EVERY rank (identical
         #: results, no communication): a 50 000-path probe is latency-bound (~1 ms) and sharding it would add
@@ -464,6 +468,22 @@ class RetirementMonteCarloSimulator:
             "WithdrawalRateTrajectory": r["withdrawal_rate_trajectory"][:, 0].tolist(),
             "Inflation At Retirement": float(r["inflation_at_retirement"][0]),
         }
+
+    # ---- the historical backtest: one path per start month of the record ------------------------
+    def historical_cohorts(self, working_months: int):
+        """On a ``"cohorts"`` history of H months: ONE summary launch of exactly the H paths 0 .. H - 1 of the
+        final stream — cohort i lives its first month in month i of the record — as a :class:`cohorts.CohortReplay`
+        (per start: success, final balance, YearsToRuin, whether it wrapped around the record's end)."""
+        from .cohorts import CohortReplay
+
+        h = self.market_history
+        if h is None or h.scheme != "cohorts":
+            raise ValueError("historical_cohorts needs rng='history' with a market_history of scheme='cohorts'")
+        wm = int(working_months)
+        params = self._current_params()
+        r = E.run_batch_host(params, self._history_rng, N.MCR_STREAM_FINAL, 0, h.months, wm, want_trajectories=False,
+                             want_bins=False, device=self._local_device())
+        return CohortReplay(r["success"], r["final_balance"], r["years_to_ruin"], int(E.query_sizes(params, wm).total_months), h.first_month)
 
     # ---- batch driver (:952-1128) --------------------------------------------------------------
     def run_monte_carlo_simulations(
