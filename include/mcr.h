@@ -261,6 +261,23 @@ int mcr_k1_month_form(const mcr_params* p, int32_t working_months, int32_t* mask
  * MCR_K1_STREAM_FORM in the environment forces a lower mask, as at a launch; a mask the parameters do not qualify for returns
  * MCR_ERR_INVALID_ARG. */
 int mcr_k1_stream_form(const mcr_params* p, int32_t working_months, int32_t* mask);
+/* Whether a count-only launch of n_paths paths of (params, working_months) on `rng` (NULL: the engine's own stream), with
+ * hist_n_bins bins of the in-kernel histogram (0: none), takes the SCREENED route ("screened count-only launches"):
+ * every path is first classified in fp32, and only the doubtful ones run the fp64 state machine.  *screened = 1 when the
+ * parameters qualify (no annual-gains tax, the tolerance month, at most two paying income records, all inflation-indexed),
+ * the stream is MCR_RNG_PHILOX, no histogram is requested, n_paths < 2^32 and n_paths >= MCR_K1_SCREEN_MIN_PATHS (default
+ * 500 000).  MCR_K1_SCREEN=0 in the environment turns the route off, =1 takes it at any size; a launch under any knob that
+ * addresses the classic kernels (MCR_K1_SEGMENTS, _SEGMENTS_ALWAYS, _SEGMENT_ORDER, _SEGMENT_POLLS, _GROWTH_FORM, _MONTH_FORM,
+ * _STREAM_FORM) takes the classic route.  Same counters, wr_obs_counts and ruin_year_bins either way, bit for bit. */
+int mcr_k1_screen(const mcr_params* p, const mcr_rng* rng, int32_t working_months, uint64_t n_paths, int32_t hist_n_bins, int32_t* screened);
+/* Test hook (tests and tools only): runs the screening kernel of that route ALONE over global paths [path_begin, path_begin +
+ * n_paths) and returns per path, in HOST arrays (any may be NULL): its class, the lowest capacity / need of the retirement months
+ * it ran (+inf: no month with a need) and b1 + b2 where it stopped (a SAFE path: at the end of the horizon).
+ * MCR_ERR_UNSUPPORTED when the parameters or the stream do not qualify.  Synchronous. */
+#define MCR_SCREEN_SAFE 0      /* succeeds with every retirement year observed: counted by the screening kernel */
+#define MCR_SCREEN_DOUBTFUL 1  /* decided by the fp64 state machine */
+int mcr_screen_paths_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                         int32_t working_months, uint8_t* cls, float* min_ratio, float* final_total, int device);
 /* The other_income_streams records the path kernel is given for (params, working_months), in list order: a record with
  * monthly_amount_today == 0 pays an exact zero every month and is left out; lock slots (non-indexed streams; -1 for an indexed
  * one) are numbered over the kept records.  Writes min(*n, cap) entries of index[] (position in the caller's list) and

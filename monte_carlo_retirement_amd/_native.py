@@ -340,6 +340,8 @@ ABI_SYMBOLS = (
     "mcr_k1_growth_form",
     "mcr_k1_month_form",
     "mcr_k1_stream_form",
+    "mcr_k1_screen",
+    "mcr_screen_paths_rng",
     "mcr_k1_kept_streams",
     "mcr_run_batch",
     "mcr_run_batch_host",
@@ -419,6 +421,12 @@ def _declare(lib: C.CDLL) -> None:
     if hasattr(lib, "mcr_k1_stream_form"):  # (likewise)
         lib.mcr_k1_stream_form.restype = C.c_int
         lib.mcr_k1_stream_form.argtypes = [P(McrParams), C.c_int32, P(C.c_int32)]
+    if hasattr(lib, "mcr_k1_screen"):       # (likewise)
+        lib.mcr_k1_screen.restype = C.c_int
+        lib.mcr_k1_screen.argtypes = [P(McrParams), P(McrRng), C.c_int32, C.c_uint64, C.c_int32, P(C.c_int32)]
+        lib.mcr_screen_paths_rng.restype = C.c_int
+        lib.mcr_screen_paths_rng.argtypes = [P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.mcr_run_batch.restype = C.c_int
     lib.mcr_run_batch.argtypes = [
         P(McrParams), C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32,

@@ -32,6 +32,7 @@
 
 #include "mcr_device.h"
 #include "mcr_numpy_rng.h"
+#include "mcr_screen.h"
 #include "mcr_host.h"
 
 namespace mcr {
@@ -106,6 +107,9 @@ struct KernelIO {
         YearBins yb;
         int32_t fan_stream;                            // PHASE 10: which of the kept records (DevParams::streams) the consumer waves replace
         FanRows fan_rows;                              // PHASE 8 / 9 / 10, outcome probes (behind fan_stream's word)
+        // LIST (the re-run of a screened launch, path_kernel's LIST): lane i of the launch runs local path path_list[i] for
+        // i < *path_list_count, both written by screen_kernel earlier on the stream.  Such a launch reads no fan-out level.
+        struct { const uint32_t* path_list; const uint32_t* path_list_count; };
     };
     // PHASE 8 / 9 / 10, joint probes (mcr_probe_*_joint_rng): [fan_n][(n_paths + 63) / 64] success masks or nullptr; consumer wave j
     // stores its 64 paths' ballot to word blockIdx.x of row j.  Last, so every other field keeps its place in the kernel arguments
@@ -361,7 +365,7 @@ __device__ __forceinline__ void income_put(DevStream& S, const IncomeRegs& R) {
     S.amount = R.amount; S.amount_keep = R.amount_keep; S.start_month = R.start_month; S.end_month = R.end_month;
 }
 
-template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault, int GF = 0, int MF = 0, int SF = 0, bool OUT = false>
+template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault, int GF = 0, int MF = 0, int SF = 0, bool OUT = false, bool LIST = false>
 __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE == 8 || PHASE == 9 || PHASE == 10) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
                                                          const DevParams* __restrict__ cand_params) {
     // MODE 3 (mcr_run_year_bins_rng): YEARLY BINS.  The arithmetic of MODE 2, but wherever that variant stores a yearly sample
@@ -388,6 +392,12 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     // fan_ruin) in the epilogue.  A template flag, not a null check: the month of failure is one more VGPR through the month loop,
     // which the plain and the joint probes' kernels do not pay.
     static_assert(!OUT || PHASE == 8 || PHASE == 9 || PHASE == 10, "outcome rows exist for the scenario, assumption and income fan-outs");
+    // LIST (the re-run of a screened launch; launch_screened): the lanes' local path indices come from a device list that
+    // screen_kernel filled earlier on the stream, io.path_list[i] for i < *io.path_list_count; lanes beyond the count behave
+    // like tail lanes, and a workgroup whose first index is at or beyond the count returns at once (the host sizes the grid
+    // from a bound: it cannot read the count without a synchronisation).  Last, with a default: every other instantiation
+    // keeps its instruction stream.
+    static_assert(!LIST || (MODE == 0 && RNG == (int)MCR_RNG_PHILOX && !ANNUAL && !INJ && PHASE == 0 && !XS), "path lists exist for the whole-path count-only Philox launches, split or not");
     // PHASE 4 = PHASE 2 (a candidate's decumulation resumed from its accumulation snapshot) time-sliced like PHASE 3: the
     // 17-month verification window of the search is 17 x 196 workgroups = 2.17 rounds of the resident slots.
     constexpr bool kExpFan = PHASE == 5 || PHASE == 6;    // expense fan-out: the levels are monthly_expenses, resumed at retirement
@@ -458,6 +468,9 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         else if (bid >= S + F) { const int k = bid - S - F; seg = 1 + k / S; seg_block = k % S; lb = (unsigned)seg_block; }
         if (PHASE == 4) { cand = lb / (unsigned)io.seg_blocks_per_cand; path_block = lb % (unsigned)io.seg_blocks_per_cand; }
         else path_block = lb;
+    }
+    if constexpr (LIST) {
+        if ((uint64_t)blockIdx.x * kBlock >= (uint64_t)*io.path_list_count) return;     // (wave-uniform; every thread of the workgroup, before any barrier)
     }
     const GridCell* cell = kGrid ? reinterpret_cast<const GridCell*>(cand_params) + cand : nullptr;   // PHASE 6: the row's record
     const DevParams& P = kGrid ? cell->p : (kCand && !kFan) ? cand_params[cand] : P_arg;
@@ -552,8 +565,13 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     }
     __syncthreads();
 
-    const uint64_t local = (uint64_t)path_block * kPaths + (unsigned)tid;
-    const bool valid = local < io.n_paths;
+    uint64_t local = (uint64_t)path_block * kPaths + (unsigned)tid;
+    bool valid = local < io.n_paths;
+    if constexpr (LIST) {     // the lane's position in the list, then the entry there (a local path index below n_paths)
+        const uint64_t list_n = *io.path_list_count;
+        valid = local < list_n;
+        if (valid) local = io.path_list[local];
+    }
     const uint64_t li = valid ? local : (io.n_paths - 1);  // tail lanes shadow the last path, write nothing
     const uint64_t path = io.path_begin + li;
     // growth_rows2's per-path Philox rounds (mcr_device.h), in the count-only kernels without an annual-gains tax
@@ -1249,6 +1267,10 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         atomicAdd((unsigned long long*)&ctr[MCR_CTR_SUCCESS], (unsigned long long)blk[0]);
         const uint64_t first = (uint64_t)path_block * kBlock;
         const uint64_t cnt = io.n_paths - first < (uint64_t)kBlock ? io.n_paths - first : (uint64_t)kBlock;
+        if constexpr (LIST) {     // the list's entries in this workgroup's range
+            const uint64_t list_n = *io.path_list_count;
+            atomicAdd((unsigned long long*)&ctr[MCR_CTR_PATHS], (unsigned long long)(list_n - first < (uint64_t)kBlock ? list_n - first : (uint64_t)kBlock));
+        } else
         atomicAdd((unsigned long long*)&ctr[MCR_CTR_PATHS], (unsigned long long)cnt);
     }
     if (want_bins) {
@@ -1266,6 +1288,123 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     }
     for (int k = threadIdx.x; k < n_hist; k += kBlock)   // one global atomic per non-empty bin per workgroup
         if (blk[n_blk + k]) atomicAdd((unsigned long long*)&io.out.hist_bins[k], (unsigned long long)blk[n_blk + k]);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Screening kernel of a count-only launch (mcr_screen.h; launch_screened): one path per lane, the whole path in fp32 on the
+// hardware's transcendentals, no LDS tables and no stage.  The month is the closed tolerance form of path_kernel
+// (capacity_tol, sell_fraction_tol, rebalance_tol, the income FMAs of the stream form) restated in fp32: selects stay selects,
+// and instead of the dust fix-ups a lane becomes DOUBTFUL when a balance falls to one dollar.  (The rebalance that closes a
+// tax year without an annual-gains tax comes right behind the month's own and moves a rounding's worth: it is left out.)
+// A lane is SAFE only if in every retirement month cap >= kScreenNeedMargin need and cap >= peak / kScreenPeakDiv, `need` and
+// `cap` the month's own values and `peak` the running maximum of b1 + b2 (need <= 0: the second test alone decides, as the
+// first then holds for any positive cap).  SAFE lanes are counted as path_kernel's epilogue counts a successful path whose
+// every year was observed; DOUBTFUL lanes append their local index to io.list, one atomic per wave; tail lanes do neither.
+// HOOK (mcr_screen_paths_rng, tests and tools): per path the class, the lowest cap / need seen and the final b1 + b2.
+// Held to 8 waves per SIMD (<= 64 VGPRs), no scratch.
+struct ScreenIO {
+    uint64_t seed, path_begin, n_paths;
+    uint32_t stream_id, reserved;
+    uint64_t* counters;          // [MCR_N_COUNTERS] or nullptr
+    uint64_t* wr_obs_counts;     // [ry] or nullptr
+    uint32_t* list;              // [n_paths] local indices of the doubtful paths, or nullptr (HOOK)
+    uint32_t* list_count;        // zeroed before the launch
+    uint8_t* cls;                // HOOK: [n_paths] MCR_SCREEN_SAFE / MCR_SCREEN_DOUBTFUL
+    float* min_ratio;            // HOOK: [n_paths] lowest cap / need of the months the lane ran (+inf: no month with a need)
+    float* final_total;          // HOOK: [n_paths] b1 + b2 where the lane stopped
+};
+template <int TAXED, bool EQR, bool HOOK = false>
+__global__ __launch_bounds__(kBlock, 8) void screen_kernel(const ScreenParams S, const ScreenIO io) {
+    static_assert(TAXED >= 0 && TAXED <= 3 && (!EQR || TAXED == 3), "TAXED is path_kernel's mask; equal rates need both assets taxed");
+    constexpr bool T1 = (TAXED & 1) != 0, T2 = (TAXED & 2) != 0;
+    __shared__ unsigned int safe_s;
+    if (threadIdx.x == 0) safe_s = 0u;
+    __syncthreads();
+    const uint64_t local = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const bool valid = local < io.n_paths;
+    const uint64_t path = io.path_begin + (valid ? local : io.n_paths - 1);   // tail lanes shadow the last path
+    const PhiloxPath PQ = philox_path(path, io.stream_id, io.seed);           // (the whole wave is here: philox_path's ballot)
+    float b1 = S.b1_0, b2 = S.b2_0, c1 = b1, c2 = b2, infl = 1.0f;
+    float peak = b1 + b2;
+    float contrib = S.contrib, k1 = contrib * S.alloc1, k2 = contrib - k1;
+    bool ok = __builtin_fminf(b1, b2) > kScreenMinBalance;
+    [[maybe_unused]] float min_ratio = __builtin_inff();
+    PairCarry carry{0u, 0u};
+    const int wm = S.working_months, total = S.total_months;
+    int moy = 0;                                                     // accumulation month of the year, 0 .. 11
+    for (int row = 0; row < total; row += 2) {
+        if (__builtin_amdgcn_ballot_w64(ok) == 0ull) break;          // every lane of the wave is doubtful: nothing left to decide
+        float g[6];
+        if (PQ.hi_uniform) {
+            if ((row & 2) == 0) screen_factors2<0, true>(S, PQ, io.seed, (uint32_t)row >> 2, carry, g);
+            else screen_factors2<1, true>(S, PQ, io.seed, (uint32_t)row >> 2, carry, g);
+        } else {                                                     // a wave that straddles a multiple of 2^32 paths
+            if ((row & 2) == 0) screen_factors2<0, false>(S, PQ, io.seed, (uint32_t)row >> 2, carry, g);
+            else screen_factors2<1, false>(S, PQ, io.seed, (uint32_t)row >> 2, carry, g);
+        }
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int m = row + r;                                   // wave-uniform
+            if (m >= total) break;
+            const float g1 = g[3 * r], ginf = g[3 * r + 1], g2 = g[3 * r + 2];
+            if (m < wm) {                                            // accumulation (:513-553)
+                if (moy == kMPY) {
+                    moy = 0;
+                    if (S.contrib_grows) { contrib *= S.contrib_growth_factor; k1 = contrib * S.alloc1; k2 = contrib - k1; }
+                }
+                ++moy;
+                b1 *= g1; b2 *= g2; infl *= ginf;
+                b1 += k1; c1 += k1; b2 += k2; c2 += k2;
+            } else {                                                 // decumulation (:644-796)
+                const float price = infl;
+                float income = S.expenses * price;
+                if ((unsigned)(m - S.s0) < S.n0) income = __builtin_fmaf(-S.sa0, price, income);
+                if ((unsigned)(m - S.s1) < S.n1) income = __builtin_fmaf(-S.sa1, price, income);
+                const float need = __builtin_fmaxf(0.0f, income);
+                b1 *= g1; b2 *= g2; infl *= ginf;
+                const float v1 = T1 ? __builtin_fmaf(-__builtin_fmaxf(0.0f, b1 - c1), S.rate1, b1) : b1;
+                const float v2 = T2 ? __builtin_fmaf(-__builtin_fmaxf(0.0f, b2 - c2), EQR ? S.rate1 : S.rate2, b2) : b2;
+                const float cap = v1 + v2;
+                ok = ok && cap >= kScreenNeedMargin * need && cap >= peak * (1.0f / kScreenPeakDiv);
+                const float inv_cap = __builtin_amdgcn_rcpf(cap);
+                const float phi = __builtin_fminf(need, cap) * inv_cap;
+                if constexpr (HOOK) { if (need > 0.0f) min_ratio = __builtin_fminf(min_ratio, cap * __builtin_amdgcn_rcpf(need)); }
+                b1 = __builtin_fmaf(-b1, phi, b1); c1 = __builtin_fmaf(-c1, phi, c1);
+                b2 = __builtin_fmaf(-b2, phi, b2); c2 = __builtin_fmaf(-c2, phi, c2);
+            }
+            peak = __builtin_fmaxf(peak, screen_rebalance<TAXED, EQR>(S, b1, c1, b2, c2));
+            ok = ok && __builtin_fminf(b1, b2) > kScreenMinBalance;
+        }
+    }
+    ok = ok && peak < kScreenMaxTotal;
+    const bool safe = valid && ok, doubt = valid && !ok;
+    const unsigned long long safe_mask = __builtin_amdgcn_ballot_w64(safe), doubt_mask = __builtin_amdgcn_ballot_w64(doubt);
+    const unsigned int lane = threadIdx.x & 63u;
+    if (lane == 0u && safe_mask) atomicAdd(&safe_s, (unsigned int)__popcll(safe_mask));
+    if (io.list && doubt_mask) {                                     // wave-uniform
+        unsigned int base = 0u;
+        if (lane == 0u) base = atomicAdd(io.list_count, (unsigned int)__popcll(doubt_mask));
+        base = (unsigned int)__builtin_amdgcn_readfirstlane((int)base);
+        const unsigned int before = __builtin_amdgcn_mbcnt_hi((unsigned int)(doubt_mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)doubt_mask, 0u));
+        if (doubt) io.list[base + before] = (uint32_t)local;         // (at most n_paths entries in all: one per valid lane)
+    }
+    if constexpr (HOOK) {
+        if (valid) {
+            if (io.cls) io.cls[local] = ok ? MCR_SCREEN_SAFE : MCR_SCREEN_DOUBTFUL;
+            if (io.min_ratio) io.min_ratio[local] = min_ratio;
+            if (io.final_total) io.final_total[local] = b1 + b2;
+        }
+    }
+    __syncthreads();
+    const unsigned int n_safe = safe_s;
+    if (n_safe == 0u) return;
+    if (threadIdx.x == 0 && io.counters) {
+        atomicAdd((unsigned long long*)&io.counters[MCR_CTR_SUCCESS], (unsigned long long)n_safe);
+        atomicAdd((unsigned long long*)&io.counters[MCR_CTR_PATHS], (unsigned long long)n_safe);
+    }
+    // wr_obs_counts[y] = #paths with done_years > y: a SAFE path has done_years = ry, and no ruin bin
+    if (io.wr_obs_counts)
+        for (int y = threadIdx.x; y < S.retirement_years; y += kBlock) atomicAdd((unsigned long long*)&io.wr_obs_counts[y], (unsigned long long)n_safe);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2310,6 +2449,135 @@ struct SegmentHandOver {
     hipError_t release() { return mem.release(); }
 };
 
+// ---------------------------------------------------------------------------------------------
+// The SCREENED route of a count-only launch (mcr_screen.h): screen_kernel classifies every path in fp32 and counts the SAFE
+// ones; path_kernel's LIST form re-runs the DOUBTFUL ones in fp64 and adds its counts to the same vectors.
+// ---------------------------------------------------------------------------------------------
+// Which parameter blocks can be screened: the launches that have growth, month and stream forms (no annual-gains tax, the
+// tolerance month, no extended streams) whose kept income records are at most two, all indexed (kStreamsInRegs).
+static bool screen_qualified(const DevParams& d) {
+    return !kExactMonthDefault && !d.any_annual_tax && !d.exact_month && d.n_extra_streams == 0 && stream_form_qualified(d) == kStreamsInRegs;
+}
+// Smallest launch that takes the route by default: the measured crossover (LABNOTES R24); MCR_K1_SCREEN_MIN_PATHS moves it.
+constexpr uint64_t kScreenMinPathsDefault = 500000;
+// The knobs that address the classic kernels: a launch under any of them takes the classic route
+static const char* const kClassicKnobs[] = {"MCR_K1_SEGMENTS", "MCR_K1_SEGMENTS_ALWAYS", "MCR_K1_SEGMENT_ORDER", "MCR_K1_SEGMENT_POLLS",
+                                            "MCR_K1_GROWTH_FORM", "MCR_K1_MONTH_FORM", "MCR_K1_STREAM_FORM"};
+// *screened = whether a count-only launch (no per-path output, no injected shocks, `hist_n_bins` histogram bins) of n_paths
+// paths of `d` on `rng` takes the screened route.  MCR_K1_SCREEN=0 turns the route off, =1 forces it on at any size.
+static int screen_route_of(const DevParams& d, const mcr_rng* rng, uint64_t n_paths, int hist_n_bins, bool* screened) {
+    *screened = false;
+    int force = -1;
+    if (const char* e = std::getenv("MCR_K1_SCREEN"); e && *e) {
+        if ((e[0] != '0' && e[0] != '1') || e[1] != '\0') { set_error("MCR_K1_SCREEN=%s: 0 (never) or 1 (whenever the launch qualifies)", e); return MCR_ERR_INVALID_ARG; }
+        force = e[0] - '0';
+    }
+    if (force == 0 || !screen_qualified(d) || (rng && rng->kind != MCR_RNG_PHILOX) || hist_n_bins != 0) return MCR_OK;
+    if (n_paths == 0 || n_paths > (uint64_t)UINT32_MAX) return MCR_OK;     // (the list holds 32-bit local indices)
+    for (const char* knob : kClassicKnobs) { const char* e = std::getenv(knob); if (e && *e) return MCR_OK; }
+    uint64_t min_paths = kScreenMinPathsDefault;
+    if (const char* e = std::getenv("MCR_K1_SCREEN_MIN_PATHS"); e && *e) {
+        char* end = nullptr;
+        min_paths = std::strtoull(e, &end, 10);
+        if (*end != '\0') { set_error("MCR_K1_SCREEN_MIN_PATHS=%s: a path count", e); return MCR_ERR_INVALID_ARG; }
+    }
+    *screened = force == 1 || n_paths >= min_paths;
+    return MCR_OK;
+}
+// Share of a screened launch's paths expected on the list: sizes the choice between the two forms of the re-run
+static double screen_expected() {
+    const char* e = std::getenv("MCR_K1_SCREEN_EXPECTED");
+    const double v = (e && *e) ? std::strtod(e, nullptr) : 0.08;
+    return v > 0.0 ? v : 0.08;
+}
+// The screening kernel's parameter block: every value derived in double, rounded once
+static ScreenParams screen_params(const DevParams& d) {
+    const double log2e = 1.4426950408889634074;
+    ScreenParams s;
+    std::memset(&s, 0, sizeof(s));
+    s.a1 = (float)(d.a1 * log2e); s.b1 = (float)(d.b1 * log2e);
+    s.ainf = (float)(d.ainf * log2e); s.binf_rho = (float)(d.binf_rho * log2e); s.binf_rho_c = (float)(d.binf_rho_c * log2e);
+    s.aprem = (float)(d.aprem * log2e); s.bprem = (float)(d.bprem * log2e);
+    const double b1 = d.initial_balance * d.alloc1;
+    s.b1_0 = (float)b1; s.b2_0 = (float)(d.initial_balance - b1);
+    s.contrib = (float)d.monthly_contribution; s.contrib_growth_factor = (float)d.contrib_growth_factor;
+    s.expenses = (float)d.monthly_expenses; s.alloc1 = (float)d.alloc1;
+    s.rate1 = (float)d.real_rate1; s.rate2 = (float)d.real_rate2;
+    s.ar1 = (float)(d.alloc1 * d.real_rate1); s.ar2 = (float)(d.alloc2 * d.real_rate2);
+    const int wm = d.working_months;
+    auto to_row = [&](int32_t m) { return m > INT32_MAX - wm ? INT32_MAX : m + wm; };      // (path_kernel's StreamRegs)
+    auto window_months = [](int first, int end) { return end > first ? (uint32_t)(end - first) : 0u; };
+    if (d.n_streams > 0) { s.sa0 = (float)d.streams[0].amount_keep; s.s0 = to_row(d.streams[0].start_month); s.n0 = window_months(s.s0, to_row(d.streams[0].end_month)); }
+    if (d.n_streams > 1) { s.sa1 = (float)d.streams[1].amount_keep; s.s1 = to_row(d.streams[1].start_month); s.n1 = window_months(s.s1, to_row(d.streams[1].end_month)); }
+    s.working_months = wm; s.retirement_years = d.retirement_years; s.total_months = d.total_months; s.contrib_grows = d.contrib_grows;
+    return s;
+}
+template <bool HOOK>
+static void launch_screen_kernel(const DevParams& d, const ScreenParams& sp, const ScreenIO& sio, dim3 grid, hipStream_t stream) {
+    const bool eqr = month_form_qualified(d) == kMonthEqualRates;
+    switch (d.tax_mask) {
+        case 0: hipLaunchKernelGGL((screen_kernel<0, false, HOOK>), grid, dim3(kBlock), 0, stream, sp, sio); break;
+        case 1: hipLaunchKernelGGL((screen_kernel<1, false, HOOK>), grid, dim3(kBlock), 0, stream, sp, sio); break;
+        case 2: hipLaunchKernelGGL((screen_kernel<2, false, HOOK>), grid, dim3(kBlock), 0, stream, sp, sio); break;
+        default:
+            if (eqr) hipLaunchKernelGGL((screen_kernel<3, true, HOOK>), grid, dim3(kBlock), 0, stream, sp, sio);
+            else hipLaunchKernelGGL((screen_kernel<3, false, HOOK>), grid, dim3(kBlock), 0, stream, sp, sio);
+    }
+}
+// One screened launch.  `d` is the launch's parameter block (screen_qualified), `io` its kernel arguments (count-only).  The
+// list and its count are one stream-ordered allocation, 4 n + 8 bytes, the count zeroed on the stream and the block freed
+// behind the re-run.  The host never reads the count: the re-run's grid is sized from the bound ceil(n / 256), and its
+// workgroups beyond the count return at once.  The re-run takes the producer / consumer form when the EXPECTED list
+// (n x MCR_K1_SCREEN_EXPECTED) is a latency-bound launch.  MCR_ERR_UNSUPPORTED: the allocation was refused, nothing enqueued.
+static int launch_screened(DevParams d, KernelIO io, hipStream_t stream) {
+    const uint64_t n = io.n_paths;
+    StreamAlloc mem(stream);
+    if (!mem.alloc(4 * (size_t)n + 8)) return MCR_ERR_UNSUPPORTED;
+    uint32_t* const count = (uint32_t*)mem.p;
+    uint32_t* const list = (uint32_t*)((char*)mem.p + 8);
+    hipError_t e = hipMemsetAsync(count, 0, 8, stream);
+    if (e != hipSuccess) return hip_fail(e, "screened launch: zeroing the list's count");
+    const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
+    ScreenIO sio;
+    std::memset(&sio, 0, sizeof(sio));
+    sio.seed = io.seed; sio.path_begin = io.path_begin; sio.n_paths = n; sio.stream_id = io.stream_id;
+    sio.counters = io.out.counters; sio.wr_obs_counts = io.out.wr_obs_counts; sio.list = list; sio.list_count = count;
+    launch_screen_kernel<false>(d, screen_params(d), sio, grid, stream);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "screen_kernel launch");
+    bool split = (double)n * screen_expected() / 64.0 <= (double)split_max_waves();
+    int rc = split ? check_barrier_counts(d) : MCR_OK;
+    if (rc != MCR_OK) return rc;
+    size_t lds = 0;
+    rc = plan_path_kernel_lds(d, 0, MCR_RNG_PHILOX, false, split, 0, &lds);
+    if (rc != MCR_OK) return rc;
+    io.path_list = list; io.path_list_count = count;
+    const DevParams* const no_cand = nullptr;
+    if (split) {
+        for_tax_variant(d, [&](auto T, auto A) {
+            if constexpr (!decltype(A)::value)
+                hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, false, false, 0, true, false, kExactMonthDefault, 0, 0, 0, false, true>),
+                                   grid, dim3(2 * kBlock), lds, stream, d, io, no_cand);
+        });
+    } else {
+        const int gf = growth_form_qualified(d), mf = month_form_qualified(d);
+        for_tax_variant(d, [&](auto T, auto A) {
+            if constexpr (!decltype(A)::value && !kExactMonthDefault)
+                for_growth_form(gf, [&](auto G) {
+                    for_month_form<decltype(T)::value>(mf, [&](auto F) {
+                        hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, false, false, 0, false, false, false, decltype(G)::value, decltype(F)::value, kStreamsInRegs, false, true>),
+                                           grid, block, lds, stream, d, io, no_cand);
+                    });
+                });
+        });
+    }
+    e = hipGetLastError();
+    const hipError_t ef = mem.release();
+    if (e != hipSuccess) return hip_fail(e, "path_kernel launch (screened re-run)");
+    if (ef != hipSuccess) return hip_fail(ef, "screened launch: list release");
+    return MCR_OK;
+}
+
 static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
                         uint64_t n_paths, int32_t wm, const double* injected, const mcr_outputs* out,
                         hipStream_t stream) {
@@ -2376,6 +2644,16 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
     int sf = 0;     // ... and its stream form
     rc = stream_form_of(d, !np_rng && !injected && !xs && !split && mode == 0 && !d.any_annual_tax, &sf);
     if (rc != MCR_OK) return rc;
+    // the screened route (launch_screened): count-only launches of the engine's own stream whose parameters qualify
+    if (!injected && !np_rng && mode == 0 && !xs) {
+        bool screened = false;
+        rc = screen_route_of(d, rng, n_paths, io.out.hist_n_bins, &screened);
+        if (rc != MCR_OK) return rc;
+        if (screened) {
+            rc = launch_screened(d, io, stream);
+            if (rc != MCR_ERR_UNSUPPORTED) return rc;      // (allocation refused: the classic route below)
+        }
+    }
     StreamSideBlock side;
     rc = side.attach(d, extra, grid.x, stream);
     if (rc != MCR_OK) { (void)side.release(stream); return rc; }
@@ -3242,6 +3520,52 @@ int mcr_k1_stream_form(const mcr_params* p, int32_t working_months, int32_t* mas
     rc = stream_form_of(d, true, &m);
     if (rc != MCR_OK) return rc;
     *mask = m;
+    return MCR_OK;
+}
+
+int mcr_k1_screen(const mcr_params* p, const mcr_rng* rng, int32_t working_months, uint64_t n_paths, int32_t hist_n_bins, int32_t* screened) {
+    if (!screened) { set_error("null screened"); return MCR_ERR_INVALID_ARG; }
+    DevParams d;
+    std::vector<DevStream> extra;
+    int rc = derive_params(p, working_months, &d, &extra);
+    if (rc != MCR_OK) return rc;
+    if (rng && (rc = check_rng(rng)) != MCR_OK) return rc;
+    bool s = false;
+    rc = screen_route_of(d, rng, n_paths, hist_n_bins, &s);
+    if (rc != MCR_OK) return rc;
+    *screened = s ? 1 : 0;
+    return MCR_OK;
+}
+
+int mcr_screen_paths_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                         int32_t working_months, uint8_t* cls, float* min_ratio, float* final_total, int device) {
+    MCR_ENTER_DEVICE(device);
+    DevParams d;
+    std::vector<DevStream> extra;
+    int rc = derive_params(p, working_months, &d, &extra);
+    if (rc != MCR_OK) return rc;
+    rc = check_rng(rng);
+    if (rc != MCR_OK) return rc;
+    if (rng->kind != MCR_RNG_PHILOX || !screen_qualified(d)) { set_error("the launch does not qualify for screening (mcr_k1_screen)"); return MCR_ERR_UNSUPPORTED; }
+    if (n_paths == 0) return MCR_OK;
+    if (n_paths > (uint64_t)UINT32_MAX) { set_error("n_paths too large for one screening launch"); return MCR_ERR_INVALID_ARG; }
+    if (path_begin + n_paths < path_begin) { set_error("path range overflows 64 bits"); return MCR_ERR_INVALID_ARG; }
+    DeviceArena arena;
+    ScreenIO sio;
+    std::memset(&sio, 0, sizeof(sio));
+    sio.seed = rng->philox_seed; sio.path_begin = path_begin; sio.n_paths = n_paths; sio.stream_id = stream_id;
+    hipError_t e = hipSuccess;
+    if (cls) e = arena.alloc((void**)&sio.cls, (size_t)n_paths);
+    if (e == hipSuccess && min_ratio) e = arena.alloc((void**)&sio.min_ratio, (size_t)n_paths * sizeof(float));
+    if (e == hipSuccess && final_total) e = arena.alloc((void**)&sio.final_total, (size_t)n_paths * sizeof(float));
+    if (e != hipSuccess) return hip_fail(e, "hipMalloc");
+    launch_screen_kernel<true>(d, screen_params(d), sio, dim3((unsigned)((n_paths + kBlock - 1) / kBlock)), nullptr);
+    e = hipGetLastError();
+    if (e == hipSuccess && cls) e = hipMemcpy(cls, sio.cls, (size_t)n_paths, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && min_ratio) e = hipMemcpy(min_ratio, sio.min_ratio, (size_t)n_paths * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && final_total) e = hipMemcpy(final_total, sio.final_total, (size_t)n_paths * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) return hip_fail(e, "screen_kernel");
     return MCR_OK;
 }
 

@@ -1,0 +1,106 @@
+// mcr_screen.h — device-side building blocks of the SCREENING kernel (screen_kernel, mcr_hip.hip).
+//
+// A count-only launch returns integers: how many paths succeed, in which retirement year the others fail, how many years
+// each was observed.  For almost every path the classification is never in doubt, so the launch first runs the whole path in
+// fp32 on the hardware's transcendentals (v_log_f32, v_sqrt_f32, v_sin_f32 / v_cos_f32, v_exp_f32) and asks one question per
+// retirement month: is the liquidation value still at least kScreenNeedMargin times the month's net need, and at least
+// 1 / kScreenPeakDiv of the largest total the path has held?  A path that answers yes every month is SAFE: it succeeds with
+// every year observed, and is counted here.  Every other path is DOUBTFUL: its index goes to a list, and the fp64 state
+// machine (path_kernel's LIST form) alone decides its flags, ruin year and observed years.
+//
+// Soundness: the fp64 month fails a path only when capacity < need - 1e-6.  A SAFE path could be misclassified only if the fp32
+// capacity were off by a factor of kScreenNeedMargin (a relative deviation of 0.95) where the expected deviation of the fp32
+// path from the fp64 one is 1e-5 to 1e-4 (833 months of fp32 roundings and ~1e-6 absolute on each normal variate).
+//
+// Random numbers: the Philox words of growth_parts2_form (mcr_device.h), the same word-to-pair assignment and row order, so
+// normal j of month k is the fp64 kernel's variate to fp32 accuracy.  No LDS tables, no stage.
+#pragma once
+
+#include "mcr_device.h"
+
+namespace mcr {
+
+constexpr float kScreenNeedMargin = 24.0f;       // SAFE needs capacity >= 24 x the month's net need ...
+constexpr float kScreenPeakDiv = 64.0f;          // ... and capacity >= (running maximum of b1 + b2) / 64
+constexpr float kScreenMinBalance = 1.0f;        // a balance at or below one dollar: doubtful (the fp64 month's dust fix-ups are not restated)
+constexpr float kScreenMaxTotal = 1e30f;         // a total beyond this: doubtful (every fp32 intermediate of a SAFE path is finite)
+
+// Wave-uniform parameter block of the screening kernel, derived on the host in double and rounded once (screen_params,
+// mcr_hip.hip).  The growth coefficients are pre-scaled by log2(e): a factor is exp2(fma(b', r t, a')).
+struct ScreenParams {
+    float a1, b1, ainf, binf_rho, binf_rho_c, aprem, bprem;
+    float b1_0, b2_0;                  // initial balances (initial_balance alloc1, initial_balance - that)
+    float contrib, contrib_growth_factor, expenses, alloc1;
+    float rate1, rate2, ar1, ar2;      // realized-gains rates, and weight x rate (lane_params_tol)
+    float sa0, sa1;                    // netted amounts of the (at most two) indexed income records
+    int32_t s0, s1;                    // their first ROW (start + wm, saturated) ...
+    uint32_t n0, n1;                   // ... and length in months (StreamRegs of path_kernel)
+    int32_t working_months, retirement_years, total_months, contrib_grows;
+};
+
+// The three gross factors (equity, inflation, inv2 = inflation x premium) of the two months of a HALF (growth_parts2_form's
+// halves, words and carry), in registers.  UNIFORM: philox_path_rounds with the wave's path_hi (PhiloxPath::hi_uniform).
+template <int HALF, bool UNIFORM>
+__device__ __forceinline__ void screen_factors2(const ScreenParams& S, const PhiloxPath& Q, uint64_t seed, uint32_t t, PairCarry& C, float (&g)[6]) {
+    float rad[3], trig[6];
+    auto parts = [&](uint32_t xr, uint32_t xa, int i) {
+        // u = (w + 0.5) 2^-32 in (0, 1]; radius = sqrt(-2 ln u) = sqrt(-2 ln 2 log2 u); angle in revolutions
+        const float u = __builtin_fmaf((float)xr, 0x1p-32f, 0x1p-33f);
+        rad[i] = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u));
+        const float rev = (float)xa * 0x1p-32f;
+        trig[2 * i] = __builtin_amdgcn_cosf(rev);
+        trig[2 * i + 1] = __builtin_amdgcn_sinf(rev);
+    };
+    uint32_t x[4];
+    if (HALF == 0) {
+        philox_path_rounds<UNIFORM>(Q, 3u * t, (uint32_t)seed, (uint32_t)(seed >> 32), x);
+        parts(x[0], x[1], 0);
+        parts(x[2], x[3], 1);
+        philox_path_rounds<UNIFORM>(Q, 3u * t + 1u, (uint32_t)seed, (uint32_t)(seed >> 32), x);
+        parts(x[0], x[1], 2);
+        C.w2 = x[2]; C.w3 = x[3];
+    } else {
+        parts(C.w2, C.w3, 0);
+        philox_path_rounds<UNIFORM>(Q, 3u * t + 2u, (uint32_t)seed, (uint32_t)(seed >> 32), x);
+        parts(x[0], x[1], 1);
+        parts(x[2], x[3], 2);
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {      // growth_factors_row on normals 3 r, 3 r + 1, 3 r + 2 of the half
+        const int je = 3 * r, ji = 3 * r + 1, jp = 3 * r + 2;
+        const float ne = rad[je >> 1] * trig[je], ni = rad[ji >> 1] * trig[ji], np = rad[jp >> 1] * trig[jp];
+        const float g1 = __builtin_amdgcn_exp2f(__builtin_fmaf(S.b1, ne, S.a1));
+        const float ginf = __builtin_amdgcn_exp2f(__builtin_fmaf(S.binf_rho, ne, __builtin_fmaf(S.binf_rho_c, ni, S.ainf)));
+        const float gprem = __builtin_amdgcn_exp2f(__builtin_fmaf(S.bprem, np, S.aprem));
+        g[3 * r + 0] = g1; g[3 * r + 1] = ginf; g[3 * r + 2] = ginf * gprem;
+    }
+}
+
+// rebalance_tol (mcr_device.h) in fp32: selects stay selects, no guard and no dust fix-ups (a lane whose balance falls to
+// kScreenMinBalance is doubtful; with both balances above it every denominator is positive).  Returns b1 + b2 before the trade.
+template <int TAXED, bool EQR>
+__device__ __forceinline__ float screen_rebalance(const ScreenParams& S, float& b1, float& c1, float& b2, float& c2) {
+    const float total = b1 + b2;
+    const float drift1 = __builtin_fmaf(-total, S.alloc1, b1);
+    const bool sell1 = drift1 > 0.0f;
+    const float bs = sell1 ? b1 : b2, cs = sell1 ? c1 : c2;
+    const float drift = __builtin_fabsf(drift1);
+    float fraction_sold, net_purchase;
+    if (TAXED != 0) {
+        const float rate_s = EQR ? S.rate1 : sell1 ? S.rate1 : S.rate2;
+        const float ar_s = sell1 ? S.ar1 : S.ar2;
+        const float G = __builtin_fmaxf(0.0f, bs - cs);
+        fraction_sold = __builtin_fminf(1.0f, drift * __builtin_amdgcn_rcpf(__builtin_fmaf(-ar_s, G, bs)));
+        net_purchase = fraction_sold * __builtin_fmaf(-G, rate_s, bs);
+    } else {
+        fraction_sold = __builtin_fminf(1.0f, drift * __builtin_amdgcn_rcpf(bs));
+        net_purchase = fraction_sold * bs;
+    }
+    const float nbs = __builtin_fmaf(-bs, fraction_sold, bs), ncs = __builtin_fmaf(-cs, fraction_sold, cs);
+    const float r1b = b1 + net_purchase, r1c = c1 + net_purchase, r2b = b2 + net_purchase, r2c = c2 + net_purchase;
+    b1 = sell1 ? nbs : r1b; c1 = sell1 ? ncs : r1c;
+    b2 = sell1 ? r2b : nbs; c2 = sell1 ? r2c : ncs;
+    return total;
+}
+
+}  // namespace mcr

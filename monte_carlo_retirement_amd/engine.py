@@ -68,6 +68,33 @@ def stream_form(params: McrParams, working_months: int) -> int:
     return int(mask.value)
 
 
+def screen(params: McrParams, working_months: int, n_paths: int, rng: Optional[McrRng] = None, hist_n_bins: int = 0) -> bool:
+    """Whether a count-only launch of ``n_paths`` paths takes the screened route (mcr_k1_screen; honours MCR_K1_SCREEN,
+    MCR_K1_SCREEN_MIN_PATHS and the knobs that address the classic kernels).  ``rng``: a descriptor, or None for the
+    engine's own stream; ``ValueError`` if the parameters or a knob's value are invalid."""
+    out = C.c_int32(-1)
+    rc = N.load_library().mcr_k1_screen(C.byref(params), C.byref(rng) if rng is not None else None, int(working_months),
+                                        int(n_paths), int(hist_n_bins), C.byref(out))
+    if rc != 0:
+        raise ValueError(N.last_error() or "invalid params / screen knob")
+    return bool(out.value)
+
+
+def screen_paths(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
+                 device: int = 0) -> Dict[str, np.ndarray]:
+    """The screening kernel alone (mcr_screen_paths_rng; tests and tools): per path ``cls`` (0 safe, 1 doubtful), ``min_ratio``
+    (lowest capacity / need seen) and ``final_total`` (b1 + b2 where the lane stopped), all in the kernel's fp32."""
+    N.require_device()
+    n = int(n_paths)
+    res = {"cls": np.empty(n, dtype=np.uint8), "min_ratio": np.empty(n, dtype=np.float32), "final_total": np.empty(n, dtype=np.float32)}
+    rng = _as_rng(seed)
+    rc = N.load_library().mcr_screen_paths_rng(C.byref(params), C.byref(rng), int(stream_id), int(path_begin), n, int(working_months),
+                                               res["cls"].ctypes.data, res["min_ratio"].ctypes.data, res["final_total"].ctypes.data, int(device))
+    if rc != 0:
+        raise RuntimeError(N.last_error() or f"mcr_screen_paths_rng failed ({rc})")
+    return res
+
+
 def kept_streams(params: McrParams, working_months: int) -> list:
     """``(index, lock_slot)`` of every ``other_income_streams`` record the path kernel is given, in list order
     (mcr_k1_kept_streams): records that pay nothing are left out, and the lock slots (-1: an indexed stream has none) are
