@@ -429,11 +429,10 @@ __device__ __forceinline__ void growth_factors_row(const MARKET& K, double re, d
     ginf = fexp<true, kNarrow>(x_inf, tab, M);
     gprem = fexp<true, kNarrow>(x_prem, tab, M);      // (the caller forms g2 = ginf * gprem, :532, where it uses it)
 }
-template <int HALF, int COLS, int GEN, int GF = 0>
-__device__ __forceinline__ void growth_rows2_form(const DevParams& P, const MathRegs& M, uint64_t seed, uint32_t stream_id, uint64_t path,
-                                                  const PhiloxPath& Q, uint32_t t, const double* tab, double* stage, PairCarry& C) {
-    double rad[3], trig[6];
-    growth_parts2_form<HALF, GEN>(M, seed, stream_id, path, Q, t, tab, rad, trig, C);
+// ... and the second step: the two months' factors from the parts of a half, staged
+template <int COLS, int GF = 0>
+__device__ __forceinline__ void growth_stage_rows(const DevParams& P, const MathRegs& M, const double (&rad)[3], const double (&trig)[6],
+                                                  const double* tab, double* stage) {
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
         const int je = 3 * r, ji = 3 * r + 1, jp = 3 * r + 2;
@@ -443,6 +442,40 @@ __device__ __forceinline__ void growth_rows2_form(const DevParams& P, const Math
         stage[(3 * r + 1) * COLS] = ginf;
         stage[(3 * r + 2) * COLS] = ginf * gprem;                               // :532
     }
+}
+template <int HALF, int COLS, int GEN, int GF = 0>
+__device__ __forceinline__ void growth_rows2_form(const DevParams& P, const MathRegs& M, uint64_t seed, uint32_t stream_id, uint64_t path,
+                                                  const PhiloxPath& Q, uint32_t t, const double* tab, double* stage, PairCarry& C) {
+    double rad[3], trig[6];
+    growth_parts2_form<HALF, GEN>(M, seed, stream_id, path, Q, t, tab, rad, trig, C);
+    growth_stage_rows<COLS, GF>(P, M, rad, trig, tab, stage);
+}
+// growth_rows2 (PER_PATH) for a producer wave that stages only the pairs of ITS half (path_kernel NPROD = 2: one wave runs every
+// HALF 0, another every HALF 1), with a hook between the two steps of the form.  Such a wave has no carry from the half before:
+// a HALF 1 draws block 3t + 1 again for its words 2 and 3 (one more block of integer work against the pair's fp64 work).
+// `mid()` runs once, at a wave-uniform point behind the parts (a straddling wave has made both passes by then) and in front of
+// the factors and every store to the stage: the caller's workgroup barrier, which therefore also orders the stores.
+template <int HALF, int COLS, typename MID>
+__device__ __forceinline__ void growth_rows2_own_half(const DevParams& P, const MathRegs& M, uint64_t seed, uint32_t stream_id, uint64_t path,
+                                                      const PhiloxPath& Q, uint32_t t, const double* tab, double* stage, MID&& mid) {
+    double rad[3], trig[6];
+    PairCarry C{0u, 0u};
+    uint32_t x[4];
+    if (HALF == 1) {
+        philox_path_rounds<true>(Q, 3u * t + 1u, (uint32_t)seed, (uint32_t)(seed >> 32), x);
+        C.w2 = x[2]; C.w3 = x[3];
+    }
+    growth_parts2_form<HALF, kGenUniform>(M, seed, stream_id, path, Q, t, tab, rad, trig, C);
+    if (__builtin_expect(!Q.hi_uniform, 0)) {
+        if (HALF == 1) {
+            philox_path_rounds<false>(Q, 3u * t + 1u, (uint32_t)seed, (uint32_t)(seed >> 32), x);
+            C.w2 = x[2]; C.w3 = x[3];
+        }
+        asm volatile("" : "+v"(C.w2), "+v"(C.w3));      // (growth_rows2: keeps the general form a branch)
+        growth_parts2_form<HALF, kGenGeneral>(M, seed, stream_id, path, Q, t, tab, rad, trig, C);
+    }
+    mid();
+    growth_stage_rows<COLS>(P, M, rad, trig, tab, stage);
 }
 // The assumption fan-out's producer (path_kernel PHASE 9) stages the PARTS of a half instead of its factors: nine doubles per
 // lane, `stage[i * COLS]` = rad[i] for i < 3 and `stage[(3 + j) * COLS]` = trig[j].  Side effects as growth_rows2_form's: the

@@ -365,8 +365,8 @@ __device__ __forceinline__ void income_put(DevStream& S, const IncomeRegs& R) {
     S.amount = R.amount; S.amount_keep = R.amount_keep; S.start_month = R.start_month; S.end_month = R.end_month;
 }
 
-template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault, int GF = 0, int MF = 0, int SF = 0, bool OUT = false, bool LIST = false>
-__global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE == 8 || PHASE == 9 || PHASE == 10) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
+template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault, int GF = 0, int MF = 0, int SF = 0, bool OUT = false, bool LIST = false, int NPROD = 1>
+__global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE == 8 || PHASE == 9 || PHASE == 10) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : NPROD == 2 ? 3 * 64 : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
                                                          const DevParams* __restrict__ cand_params) {
     // MODE 3 (mcr_run_year_bins_rng): YEARLY BINS.  The arithmetic of MODE 2, but wherever that variant stores a yearly sample
     // (nominal balance, real balance, withdrawal rate) the lane bins it instead: cell 0 = below edges[0], cells 1 .. n = the
@@ -398,6 +398,18 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     // from a bound: it cannot read the count without a synchronisation).  Last, with a default: every other instantiation
     // keeps its instruction stream.
     static_assert(!LIST || (MODE == 0 && RNG == (int)MCR_RNG_PHILOX && !ANNUAL && !INJ && PHASE == 0 && !XS), "path lists exist for the whole-path count-only Philox launches, split or not");
+    // NPROD = 2 (the re-run of a screened launch whose expected list is latency-bound, under MCR_K1_RERUN_PRODUCERS=2): the SPLIT form
+    // on ONE 64-path block per workgroup, one consumer wave and TWO producer waves (192 threads).  A short list then spreads
+    // over every CU, about a wave to a SIMD, and the consumer no longer waits for its producer: producer 0 stages every HALF 0
+    // of the path, producer 1 every HALF 1 (growth_rows2_own_half), each with two barrier intervals for its pair.  The stage
+    // is the SPLIT form's two pair buffers (6 KB at 64 columns: a producer keeps its pair in registers until barrier p - 1
+    // and stores behind it, so one buffer is being read and one written at any time).  Barriers: pair p is handed over at barrier p, which every wave of
+    // the workgroup executes — the consumer in begin_month of row 2 p, the producer of pair p behind its stores, the other
+    // producer in the middle of pair p + 1 (between the parts and the factors).  The votes are PHASE 0's.  Every staged
+    // factor is the SPLIT form's.  The chain that is left is the consumer's own, so its month is the fan-out consumers' one
+    // (MM, WAVE-UNIFORM fix-ups: straight-line code where the SPLIT month branches on lane masks; re-run of 10^6 config.json
+    // paths 0.548 -> 0.503 ms on a development tree, LABNOTES R25), bit for bit the same counts.  Last, with a default, like LIST.
+    static_assert(NPROD == 1 || (NPROD == 2 && SPLIT && LIST), "two producers exist for the split re-run of a screened launch");
     // PHASE 4 = PHASE 2 (a candidate's decumulation resumed from its accumulation snapshot) time-sliced like PHASE 3: the
     // 17-month verification window of the search is 17 x 196 workgroups = 2.17 rounds of the resident slots.
     constexpr bool kExpFan = PHASE == 5 || PHASE == 6;    // expense fan-out: the levels are monthly_expenses, resumed at retirement
@@ -447,15 +459,15 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     static_assert(SF == 0 || (MODE == 0 && RNG == (int)MCR_RNG_PHILOX && !ANNUAL && !INJ && (PHASE == 0 || PHASE == 3) && !SPLIT && !XS && !EXACT),
                   "stream forms exist for the kernels that have growth forms, in the tolerance form of the month");
     constexpr bool TOL = !EXACT;         // the month in its tolerance form (mcr_device.h: "TOLERANCE FORM of the month")
-    constexpr bool MM = !SPLIT || kFan;  // exec-masked moves (issue-bound launches) vs the compiler's selects (latency-bound SPLIT launches): MCR_MASKED_MOVE, mcr_device.h
+    constexpr bool MM = !SPLIT || kFan || NPROD == 2;  // exec-masked moves (issue-bound launches, and the lone consumer wave of NPROD = 2) vs the compiler's selects (latency-bound SPLIT launches): MCR_MASKED_MOVE, mcr_device.h
     // the tolerance month's dust / empty fix-ups tested once per wave (mcr_device.h: WAVE-UNIFORM fix-ups), issue-bound launches only
     constexpr bool kFastMonth = TOL && MM && kUniformFixups;
-    constexpr int kPaths = kFan ? 64 : kBlock;           // paths of a workgroup = columns of every per-path LDS array
-    const int kThreads = kFan ? (int)blockDim.x : SPLIT ? 2 * kBlock : kBlock;
+    constexpr int kPaths = (kFan || NPROD == 2) ? 64 : kBlock;   // paths of a workgroup = columns of every per-path LDS array
+    const int kThreads = kFan ? (int)blockDim.x : NPROD == 2 ? 3 * 64 : SPLIT ? 2 * kBlock : kBlock;
     const int tid = SPLIT ? (int)(threadIdx.x & (kPaths - 1)) : (int)threadIdx.x;    // the path's lane column in every per-path LDS array
     // PHASE 5 / 7: the wave's level (wave-uniform: an SGPR); the producer is wave fan_n
     const int fan_j = kFan ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
-    const bool producer = kFan ? fan_j == io.fan_n : (SPLIT && threadIdx.x >= (unsigned)kBlock);   // wave-uniform (kBlock = 4 wavefronts)
+    const bool producer = kFan ? fan_j == io.fan_n : (SPLIT && threadIdx.x >= (unsigned)kPaths);   // wave-uniform (kPaths = 4 wavefronts, or 1)
     // PHASE 2: the parameter block of candidate blockIdx.y, in device memory (a separate const __restrict__ kernel
     // argument so that its loads are provably invariant and uniform: scalar loads, like the by-value block)
     // time-sliced launches (1-D grid): which path block (of which candidate) and which segment of it this workgroup runs (seg < 0: a whole block)
@@ -470,7 +482,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         else path_block = lb;
     }
     if constexpr (LIST) {
-        if ((uint64_t)blockIdx.x * kBlock >= (uint64_t)*io.path_list_count) return;     // (wave-uniform; every thread of the workgroup, before any barrier)
+        if ((uint64_t)blockIdx.x * kPaths >= (uint64_t)*io.path_list_count) return;     // (wave-uniform; every thread of the workgroup, before any barrier)
     }
     const GridCell* cell = kGrid ? reinterpret_cast<const GridCell*>(cand_params) + cand : nullptr;   // PHASE 6: the row's record
     const DevParams& P = kGrid ? cell->p : (kCand && !kFan) ? cand_params[cand] : P_arg;
@@ -485,7 +497,8 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     constexpr bool kHistory = (RNG == (int)MCR_RNG_HISTORY || RNG == kRngHistorySchemes) && !INJ;   // (its math tables are needed before the first month only: dynamic LDS, below)
     __shared__ __align__(16) double tab_s[kHistory ? 1 : kTabDoubles];
     constexpr int kStageLen = (kAsmFan ? kPartsPerPair : 6) * kPaths;   // = kStageDoubles for kBlock-path workgroups (PHASE 9 stages the normals' parts)
-    __shared__ __align__(16) double stage_s[kStaged ? (SPLIT ? 2 : 1) * kStageLen : 1];
+    constexpr int kStageRing = SPLIT ? 2 : 1;   // pair buffers of the stage (a power of two)
+    __shared__ __align__(16) double stage_s[kStaged ? kStageRing * kStageLen : 1];
     // Per-path values that are written once or twice in a lifetime and read at the very end (first-year withdrawals,
     // YearsToRuin) live in the lane's own LDS column in the variants with per-path outputs: held to 5 waves per SIMD those
     // variants had no registers for them (round 2: 12 / 36 bytes of scratch per lane, 4-12 VGPRs spilled).
@@ -651,7 +664,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
             return;
         }
         if (kStaged) {
-            const double* c = stage + (size_t)(3 * (row & 1)) * kPaths + (SPLIT ? (size_t)((row >> 1) & 1) * kStageLen : 0);
+            const double* c = stage + (size_t)(3 * (row & 1)) * kPaths + (SPLIT ? (size_t)((row >> 1) & (kStageRing - 1)) * kStageLen : 0);
             g1 = c[0]; ginf = c[kPaths]; g2 = c[2 * kPaths];
             return;
         }
@@ -704,6 +717,37 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         }
         ++snap_i;
     };
+    if constexpr (NPROD == 2) {
+        if (producer) {
+            // Producer h = 0 / 1 stages the pairs p = h, h + 2, ... below n_pairs, pair p in buffer p & 1.  Barriers 0 .. n_pairs - 1
+            // in order, each exactly once unless a vote ends the workgroup first (then no wave executes another): barrier p - 1 in
+            // the middle of pair p (not for p = 0: there is none), barrier p behind it, and behind the loop the last barrier where
+            // it belongs to the other producer's pair.  The consumer executes barrier p at row 2 p (begin_month), p < n_pairs.
+            // Buffer p & 1 is read between barriers p and p + 1 and written again for pair p + 2 behind barrier p + 1: every store of
+            // growth_rows2_own_half comes behind its hook, i.e. behind barrier (p + 2) - 1.
+            const int n_pairs = (P.total_months + 1) >> 1;
+            bool stop = false;
+            auto handover = [&](int q) {      // barrier q, a vote at the consumer's vote rows (producers vote 0)
+                if ((q & (kSplitVotePairs - 1)) == 0) { if (__syncthreads_or(0) == 0) stop = true; }
+                else __syncthreads();
+            };
+            auto run = [&](auto half) {
+                constexpr int H = decltype(half)::value;
+                int p = H;
+                for (; p < n_pairs; p += 2) {
+                    growth_rows2_own_half<H, kPaths>(P, GR, io.seed, io.stream_id, path, PQ, (uint32_t)p >> 1, tab, stage + (size_t)(p & (kStageRing - 1)) * kStageLen,
+                                                     [&]() { if (p > 0) handover(p - 1); });
+                    if (stop) return;
+                    handover(p);
+                    if (stop) return;
+                }
+                if (p == n_pairs && p > 0) handover(p - 1);
+            };
+            if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 1) run(std::integral_constant<int, 0>{});
+            else run(std::integral_constant<int, 1>{});
+            return;
+        }
+    }
     if (SPLIT && producer) {
         // Rows [first_row, last_row), a pair per iteration, one barrier per pair: exactly the barriers the consumers execute
         // in begin_month at every even row they visit (they visit every row of this range, in order, and never leave early).
@@ -1265,28 +1309,28 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     uint64_t* ctr = io.out.counters ? io.out.counters + (kCand ? (size_t)io.cand_out[cand] * MCR_N_COUNTERS : 0) : nullptr;
     if (threadIdx.x == 0 && ctr) {
         atomicAdd((unsigned long long*)&ctr[MCR_CTR_SUCCESS], (unsigned long long)blk[0]);
-        const uint64_t first = (uint64_t)path_block * kBlock;
-        const uint64_t cnt = io.n_paths - first < (uint64_t)kBlock ? io.n_paths - first : (uint64_t)kBlock;
+        const uint64_t first = (uint64_t)path_block * kPaths;
+        const uint64_t cnt = io.n_paths - first < (uint64_t)kPaths ? io.n_paths - first : (uint64_t)kPaths;
         if constexpr (LIST) {     // the list's entries in this workgroup's range
             const uint64_t list_n = *io.path_list_count;
-            atomicAdd((unsigned long long*)&ctr[MCR_CTR_PATHS], (unsigned long long)(list_n - first < (uint64_t)kBlock ? list_n - first : (uint64_t)kBlock));
+            atomicAdd((unsigned long long*)&ctr[MCR_CTR_PATHS], (unsigned long long)(list_n - first < (uint64_t)kPaths ? list_n - first : (uint64_t)kPaths));
         } else
         atomicAdd((unsigned long long*)&ctr[MCR_CTR_PATHS], (unsigned long long)cnt);
     }
     if (want_bins) {
-        for (int k = threadIdx.x; k < ry + 2; k += kBlock) {
+        for (int k = threadIdx.x; k < ry + 2; k += kPaths) {
             if (io.out.ruin_year_bins && blk[1 + k])
                 atomicAdd((unsigned long long*)&io.out.ruin_year_bins[k], (unsigned long long)blk[1 + k]);
         }
         // wr_obs_counts[y] = #paths with done_years > y   (wr_df.count(axis=1), :1111-1113)
-        for (int y = threadIdx.x; y < ry; y += kBlock) {
+        for (int y = threadIdx.x; y < ry; y += kPaths) {
             unsigned int c = 0;
             for (int d = y + 1; d <= ry; ++d) c += blk[1 + (ry + 2) + d];
             if (io.out.wr_obs_counts && c)
                 atomicAdd((unsigned long long*)&io.out.wr_obs_counts[y], (unsigned long long)c);
         }
     }
-    for (int k = threadIdx.x; k < n_hist; k += kBlock)   // one global atomic per non-empty bin per workgroup
+    for (int k = threadIdx.x; k < n_hist; k += kPaths)   // one global atomic per non-empty bin per workgroup (the fan-outs have returned: kPaths consumer threads)
         if (blk[n_blk + k]) atomicAdd((unsigned long long*)&io.out.hist_bins[k], (unsigned long long)blk[n_blk + k]);
 }
 
@@ -1301,7 +1345,8 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
 // first then holds for any positive cap).  SAFE lanes are counted as path_kernel's epilogue counts a successful path whose
 // every year was observed; DOUBTFUL lanes append their local index to io.list, one atomic per wave; tail lanes do neither.
 // HOOK (mcr_screen_paths_rng, tests and tools): per path the class, the lowest cap / need seen and the final b1 + b2.
-// Held to 8 waves per SIMD (<= 64 VGPRs), no scratch.
+// Held to 8 waves per SIMD (<= 64 VGPRs), no scratch.  Wave priority falls as the path advances, as in path_kernel (laggards
+// first: 8 waves a SIMD over 1.9 rounds otherwise leave the youngest to finish alone; median 2.22-2.25 -> 2.14-2.17 ms at 10^6 paths, LABNOTES R25).
 struct ScreenIO {
     uint64_t seed, path_begin, n_paths;
     uint32_t stream_id, reserved;
@@ -1332,8 +1377,18 @@ __global__ __launch_bounds__(kBlock, 8) void screen_kernel(const ScreenParams S,
     PairCarry carry{0u, 0u};
     const int wm = S.working_months, total = S.total_months;
     int moy = 0;                                                     // accumulation month of the year, 0 .. 11
+    // laggards first, as in path_kernel: the wave's priority falls at half, three quarters and nine tenths of the path (even rows)
+    const int prio_t1 = (total / 2) & ~1, prio_t2 = ((total * 3) / 4) & ~1, prio_t3 = ((total * 9) / 10) & ~1;
+    int prio_next = prio_t1;
+    __builtin_amdgcn_s_setprio(3);
     for (int row = 0; row < total; row += 2) {
         if (__builtin_amdgcn_ballot_w64(ok) == 0ull) break;          // every lane of the wave is doubtful: nothing left to decide
+        if (row == prio_next) {
+            if (row == prio_t1) __builtin_amdgcn_s_setprio(2);
+            else if (row == prio_t2) __builtin_amdgcn_s_setprio(1);
+            else if (row == prio_t3) __builtin_amdgcn_s_setprio(0);
+            prio_next = prio_from(prio_t1, prio_t2, prio_t3, row + 2);
+        }
         float g[6];
         if (PQ.hi_uniform) {
             if ((row & 2) == 0) screen_factors2<0, true>(S, PQ, io.seed, (uint32_t)row >> 2, carry, g);
@@ -2402,8 +2457,11 @@ static bool needs_generic_variant(const DevParams& d) { return d.n_extra_streams
 // The producer / consumer forms count on both halves of a workgroup executing the same number of barriers: producers run
 // rows [first, total_months), consumers the accumulation months + 12 months per retirement year.  (They also count on gfx9's
 // s_barrier not waiting for waves that have ended — producers return while consumers still reduce their counts.)
-static int check_barrier_counts(const DevParams& d) {
-    if (d.total_months == d.working_months + kMPY * d.retirement_years) return MCR_OK;
+// Two producers (path_kernel's NPROD = 2): barrier p hands pair p over, p < ceil(total_months / 2) — the consumer executes it
+// at row 2 p, which it visits for exactly those p when its months add up to total_months; each producer executes it behind
+// its own pair p or in the middle of (or, at the end, instead of) its pair p + 1.  The same identity, and at least one month.
+static int check_barrier_counts(const DevParams& d, int producers = 1) {
+    if (d.total_months == d.working_months + kMPY * d.retirement_years && (producers == 1 || d.total_months >= 1)) return MCR_OK;
     set_error("internal: total_months != working_months + 12 retirement_years");
     return MCR_ERR_INVALID_ARG;
 }
@@ -2463,6 +2521,18 @@ constexpr uint64_t kScreenMinPathsDefault = 500000;
 // The knobs that address the classic kernels: a launch under any of them takes the classic route
 static const char* const kClassicKnobs[] = {"MCR_K1_SEGMENTS", "MCR_K1_SEGMENTS_ALWAYS", "MCR_K1_SEGMENT_ORDER", "MCR_K1_SEGMENT_POLLS",
                                             "MCR_K1_GROWTH_FORM", "MCR_K1_MONTH_FORM", "MCR_K1_STREAM_FORM"};
+// Producer waves per consumer wave of the re-run's producer / consumer form: 1 = the 256-path workgroup of the lone probes
+// (four consumer and four producer waves), 2 = one 64-path block per workgroup with one consumer and two producer waves
+// (path_kernel's NPROD).  MCR_K1_RERUN_PRODUCERS, read at every launch.
+constexpr int kRerunProducersDefault = 1;     // (the 64-path form gains 0.085 ms of a 10^6-path step: under the bar set for a new default, LABNOTES R25)
+static int rerun_producers_of(int* producers) {
+    *producers = kRerunProducersDefault;
+    if (const char* e = std::getenv("MCR_K1_RERUN_PRODUCERS"); e && *e) {
+        if ((e[0] != '1' && e[0] != '2') || e[1] != '\0') { set_error("MCR_K1_RERUN_PRODUCERS=%s: 1 (the 256-path form) or 2 (64 paths, two producer waves)", e); return MCR_ERR_INVALID_ARG; }
+        *producers = e[0] - '0';
+    }
+    return MCR_OK;
+}
 // *screened = whether a count-only launch (no per-path output, no injected shocks, `hist_n_bins` histogram bins) of n_paths
 // paths of `d` on `rng` takes the screened route.  MCR_K1_SCREEN=0 turns the route off, =1 forces it on at any size.
 static int screen_route_of(const DevParams& d, const mcr_rng* rng, uint64_t n_paths, int hist_n_bins, bool* screened) {
@@ -2472,6 +2542,8 @@ static int screen_route_of(const DevParams& d, const mcr_rng* rng, uint64_t n_pa
         if ((e[0] != '0' && e[0] != '1') || e[1] != '\0') { set_error("MCR_K1_SCREEN=%s: 0 (never) or 1 (whenever the launch qualifies)", e); return MCR_ERR_INVALID_ARG; }
         force = e[0] - '0';
     }
+    int producers = 0;
+    if (int rc = rerun_producers_of(&producers)) return rc;      // (junk in the re-run's knob is an error wherever the route is asked about)
     if (force == 0 || !screen_qualified(d) || (rng && rng->kind != MCR_RNG_PHILOX) || hist_n_bins != 0) return MCR_OK;
     if (n_paths == 0 || n_paths > (uint64_t)UINT32_MAX) return MCR_OK;     // (the list holds 32-bit local indices)
     for (const char* knob : kClassicKnobs) { const char* e = std::getenv(knob); if (e && *e) return MCR_OK; }
@@ -2526,11 +2598,15 @@ static void launch_screen_kernel(const DevParams& d, const ScreenParams& sp, con
 }
 // One screened launch.  `d` is the launch's parameter block (screen_qualified), `io` its kernel arguments (count-only).  The
 // list and its count are one stream-ordered allocation, 4 n + 8 bytes, the count zeroed on the stream and the block freed
-// behind the re-run.  The host never reads the count: the re-run's grid is sized from the bound ceil(n / 256), and its
-// workgroups beyond the count return at once.  The re-run takes the producer / consumer form when the EXPECTED list
-// (n x MCR_K1_SCREEN_EXPECTED) is a latency-bound launch.  MCR_ERR_UNSUPPORTED: the allocation was refused, nothing enqueued.
+// behind the re-run.  The host never reads the count: the re-run's grid is sized from the bound ceil(n / 256) (ceil(n / 64)
+// for the 64-path form), and its workgroups beyond the count return at once.  The re-run takes a producer / consumer form
+// when the EXPECTED list (n x MCR_K1_SCREEN_EXPECTED) is a latency-bound launch: the 64-path form with two producer waves, or
+// the 256-path one (MCR_K1_RERUN_PRODUCERS).  MCR_ERR_UNSUPPORTED: the allocation was refused, nothing enqueued.
 static int launch_screened(DevParams d, KernelIO io, hipStream_t stream) {
     const uint64_t n = io.n_paths;
+    int producers = 1;
+    int rc = rerun_producers_of(&producers);
+    if (rc != MCR_OK) return rc;
     StreamAlloc mem(stream);
     if (!mem.alloc(4 * (size_t)n + 8)) return MCR_ERR_UNSUPPORTED;
     uint32_t* const count = (uint32_t*)mem.p;
@@ -2546,14 +2622,22 @@ static int launch_screened(DevParams d, KernelIO io, hipStream_t stream) {
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "screen_kernel launch");
     bool split = (double)n * screen_expected() / 64.0 <= (double)split_max_waves();
-    int rc = split ? check_barrier_counts(d) : MCR_OK;
+    rc = split ? check_barrier_counts(d, producers) : MCR_OK;
     if (rc != MCR_OK) return rc;
     size_t lds = 0;
-    rc = plan_path_kernel_lds(d, 0, MCR_RNG_PHILOX, false, split, 0, &lds);
+    rc = plan_path_kernel_lds(d, 0, MCR_RNG_PHILOX, false, split, 0, &lds);     // (the plan counts the 256-path form's 24 KB stage and 256 columns: a bound for the 64-path form's 6 KB and 64)
     if (rc != MCR_OK) return rc;
     io.path_list = list; io.path_list_count = count;
     const DevParams* const no_cand = nullptr;
-    if (split) {
+    if (split && producers == 2) {
+        // the grid's bound is ceil(n / 64) workgroups of one 64-path block; those beyond the count return at once
+        const dim3 grid64((unsigned)((n + 63) / 64));
+        for_tax_variant(d, [&](auto T, auto A) {
+            if constexpr (!decltype(A)::value)
+                hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, false, false, 0, true, false, kExactMonthDefault, 0, 0, 0, false, true, 2>),
+                                   grid64, dim3(3 * 64), lds, stream, d, io, no_cand);
+        });
+    } else if (split) {
         for_tax_variant(d, [&](auto T, auto A) {
             if constexpr (!decltype(A)::value)
                 hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, false, false, 0, true, false, kExactMonthDefault, 0, 0, 0, false, true>),
