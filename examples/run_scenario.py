@@ -22,6 +22,7 @@ switch to the final seed stream, run the final batch, print the response documen
     python examples/run_scenario.py scenarios/config.json --history record.csv --history-scheme stationary
     python examples/run_scenario.py scenarios/config.json --history record.csv --history-scheme cohorts \
         --history-first-month 1926-01 --working-months 240 --cohorts
+    python examples/run_scenario.py scenarios/config.json --working-months 240 --spending-rule 1.2,0.8,0.1,0.1,0.5,1.5 [--max-expenses]
 
 `--rng numpy` uses the reference's own NumPy stream (same seed -> the reference's numbers); `--rng philox`
 (default) the engine's counter-based stream.  `--history FILE.csv` asks every question of a recorded market instead: months
@@ -134,7 +135,21 @@ def main() -> int:
     ap.add_argument("--frontier", default=None, help="comma-separated working months: maximum monthly expenses at each")
     ap.add_argument("--grid-months", default=None, help="comma-separated working months of a success-probability table")
     ap.add_argument("--grid-expenses", default=None, help="comma-separated monthly expenses of that table")
+    ap.add_argument("--spending-rule", default=None, metavar="UPPER,LOWER,CUT,RAISE,FLOOR,CEILING",
+                    help="a guardrail spending rule: alone, what it does to the plan year by year; with --max-expenses, the "
+                         "maximum spending to begin with under the rule beside the fixed-spending answer (needs --working-months)")
     args = ap.parse_args()
+    if args.spending_rule is not None:
+        from monte_carlo_retirement_amd.spending_rules import SpendingRule
+
+        if args.working_months is None:
+            ap.error("--spending-rule needs --working-months")
+        if args.rng != "philox" or args.history:
+            ap.error("--spending-rule runs on the engine's own stream")
+        try:
+            args.spending_rule = SpendingRule.parse(args.spending_rule)
+        except ValueError as e:
+            ap.error(str(e))
     if args.min_contribution and args.working_months is None:
         ap.error("--min-contribution needs --working-months")
     if args.min_contribution and args.max_expenses:
@@ -215,6 +230,8 @@ def main() -> int:
 
     if args.cohorts:
         return cohorts(args, config, world, rank0)
+    if args.spending_rule is not None and not args.max_expenses:
+        return spending_rule(args, config, world, rank0)
     if args.max_expenses:
         return max_expenses(args, config, world, rank0)
     if args.min_contribution:
@@ -301,6 +318,11 @@ def max_expenses(args, config: Config, world: int, rank0: bool) -> int:
             "probes": len({e["iteration"] for e in events}), "curve": curve,
             "seconds": round(time.perf_counter() - t0, 3),
         }
+        if args.spending_rule is not None:    # both answers side by side: fixed spending, and spending that follows the rule
+            t1 = time.perf_counter()
+            r_expenses, r_prob, r_curve = sim.find_maximum_initial_expenses(wm, args.spending_rule, resolution=args.resolution, verbose=False)
+            out["with_spending_rule"] = {"rule": args.spending_rule.as_dict(), "max_initial_monthly_expenses": r_expenses,
+                                         "probability": r_prob, "levels": len(r_curve), "seconds": round(time.perf_counter() - t1, 3)}
     if rank0:
         print(json.dumps(_with_market(args, out)))
     if world > 1:
@@ -309,6 +331,29 @@ def max_expenses(args, config: Config, world: int, rank0: bool) -> int:
         dist.barrier()
         dist.destroy_process_group()
     return rc
+
+
+def spending_rule(args, config: Config, world: int, rank0: bool) -> int:
+    """What the rule does to the plan at --working-months: success % and, per retirement year, the shares alive / cut / at
+    the floor / raised."""
+    sim = _simulator(args, config)
+    outcomes = sim.spending_rule_outcomes(args.working_months, args.spending_rule)
+    out = {"scenario": config.Nickname, "rng": args.rng, "working_months": int(args.working_months),
+           "rule": args.spending_rule.as_dict(), **outcomes.row()}
+    if rank0:
+        if args.full:
+            print(json.dumps(out))
+        else:
+            print(f"{config.Nickname}: success {outcomes.probability:.2f}% over {outcomes.n_paths} paths under {args.spending_rule.as_dict()}")
+            print(f"{'year':>4} {'age':>6} {'alive':>7} {'cut':>7} {'floor':>7} {'raised':>7}")
+            for y in out["years"]:
+                print(f"{y['year']:>4} {y['age']:>6.1f} {100 * y['alive']:>6.1f}% {100 * y['cut']:>6.1f}% {100 * y['at_floor']:>6.1f}% {100 * y['raised']:>6.1f}%")
+    if world > 1:
+        import torch.distributed as dist
+
+        dist.barrier()
+        dist.destroy_process_group()
+    return 0
 
 
 def stress(args, config: Config, world: int, rank0: bool) -> int:

@@ -646,6 +646,62 @@ int mcr_run_year_bins_multi_host_rng(const mcr_params* p, const mcr_rng* rng, ui
                                      uint64_t n_paths, int32_t working_months, const mcr_outputs* out, const mcr_year_bins* yb,
                                      const int32_t* devices, int32_t n_devices);
 
+/*
+ * SPENDING RULE: a withdrawal-rate guardrail in the style of Guyton-Klinger.  The reference spends the same real amount every
+ * month of retirement whatever the portfolio does; under a rule the household cuts back when it is drawing too fast and loosens
+ * up when it is drawing slowly.  Every path carries a spending multiplier m, 1.0 in retirement year 0, and the month's base
+ * expenses (simulation.py:645-647) become
+ *     expenses = (monthly_expenses * m) * price             in this order: m == 1.0 leaves every bit of the month unchanged
+ * Income streams are not scaled.  With
+ *     B0 = the path's "Start Balance", P0 = its "inflation_at_retirement" (mcr_outputs),
+ *     B, P = the total balance and the price level at the start of retirement year y: the yearly trajectory sample of the end
+ *            of year y - 1 (mcr_outputs.trajectory row T - ry + y - 1) and the price level real_trajectory divides it by,
+ * the path's real withdrawal rate relative to its initial one is q = m (B0 / P0) / (B / P).  At the start of every retirement
+ * year y >= 1 that the path begins alive (it has not failed in an earlier year), in fp64, each operation rounded once:
+ *     r0  = B0 / P0                       one IEEE division per path, before the year loop
+ *     lhs = (m * r0) * P
+ *     if      lhs > upper * B:  m = max(floor,   m * (1.0 - cut))          "q > upper": cut
+ *     else if lhs < lower * B:  m = min(ceiling, m * (1.0 + raise))        "q < lower": raise
+ *     else                      m unchanged
+ * (products, no division in the year loop; upper >= 1 >= lower and B >= 0, so the two tests never both hold; B == 0 with
+ * lhs > 0 cuts.)  The rule is inert, m stays 1.0, for a path with B0 <= MCR_SMALL_EPSILON and for a path that failed before
+ * retirement (it begins no year).  cut = 0 and raise = 0 give the neutral rule: every result equals the plain launch's.
+ * Ranges (mcr_validate_spending_rule; every value finite): upper >= 1, 0 <= lower <= 1, 0 <= cut < 1, raise >= 0,
+ * 0 <= floor <= 1 <= ceiling.
+ */
+typedef struct mcr_spending_rule { double upper, lower, cut, raise, floor, ceiling; } mcr_spending_rule;
+/* columns of mcr_rule_outputs.year_counts: per retirement year, over the paths that BEGIN the year alive, after its decision */
+#define MCR_RULE_ALIVE 0   /* paths that begin the year */
+#define MCR_RULE_CUT 1     /* ... with m < 1 */
+#define MCR_RULE_FLOOR 2   /* ... with m <= floor, where floor < 1 */
+#define MCR_RULE_RAISED 3  /* ... with m > 1 */
+#define MCR_RULE_N_COUNTS 4
+typedef struct mcr_rule_outputs {
+    uint64_t* year_counts;   /* DEVICE [retirement_years][MCR_RULE_N_COUNTS], ACCUMULATED into like the counters (the caller
+                                zeroes it); NULL = not requested */
+    double* multipliers;     /* DEVICE [retirement_years][path_stride], time-major like the trajectory slab: m of local path i in
+                                year y at [y * path_stride + i], NaN for a year the path does not begin; NULL = not requested */
+    int64_t path_stride;     /* >= n_paths (elements); <= 0: n_paths */
+} mcr_rule_outputs;
+/* Host only (no device needed): MCR_ERR_INVALID_ARG with the offending field named in mcr_last_error(). */
+int mcr_validate_spending_rule(const mcr_spending_rule* rule);
+/*
+ * mcr_run_batch_rng under a spending rule: global paths [path_begin, path_begin + n_paths), DEVICE pointers in `out` and
+ * `rule_out`, asynchronous on hip_stream like mcr_run_batch_rng.  `out` carries the counters, wr_obs_counts, ruin_year_bins and
+ * the per-path summary columns (start_balance .. success): a count-only launch without them, a summary launch with any of them.
+ * rule_out may be NULL.  One plain whole-path launch on the generic tax variant (both assets' tax arithmetic; a zero-rate
+ * asset's is exact zeros): under the neutral rule the counters and every summary column equal mcr_run_batch_rng's bit for bit.
+ * A path's multipliers are a pure function of (params, seed, stream_id, path): any partition of the path range gives the same
+ * rows and year_counts that sum to the whole range's.
+ * MCR_ERR_UNSUPPORTED, with a message that names what was asked and nothing computed, for: trajectory pointers in `out`; the
+ * in-kernel histogram (hist_bins); the NumPy and history streams; a parameter block that needs the generic variant (more than
+ * MCR_INLINE_STREAMS kept income streams, frozen streams beyond the LDS budget, or the exact month of a realized-gains rate
+ * above 1 - 1e-6).  There are no yearly bins, injected shocks, fan-out, time-sliced, split or screened forms of this launch.
+ */
+int mcr_run_rule_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                     int32_t working_months, const mcr_spending_rule* rule, mcr_outputs* out, mcr_rule_outputs* rule_out,
+                     int device, void* hip_stream);
+
 /* _draw_shock_path (simulation.py:452-466) for n_paths paths: host out [n_paths][n_months][3]. */
 int mcr_draw_shocks_host(uint64_t seed, uint32_t stream_id, uint64_t path_begin,
                          uint64_t n_paths, int32_t n_months, double rho, double* out,

@@ -32,6 +32,10 @@ MCR_DEVICE_ALL = -2
 MCR_MAX_HIST_BINS = 4096
 MCR_MAX_YEAR_BINS = 512  # bins per row of the yearly-bins tables (mcr_year_bins)
 MCR_ERR_INVALID_ARG = -1
+MCR_ERR_NO_DEVICE = -2
+MCR_ERR_UNSUPPORTED = -4
+MCR_RULE_ALIVE, MCR_RULE_CUT, MCR_RULE_FLOOR, MCR_RULE_RAISED = 0, 1, 2, 3   # columns of mcr_rule_outputs.year_counts
+MCR_RULE_N_COUNTS = 4
 MCR_MAX_JOINT_OPTIONS = 32  # options of one joint probe / mcr_joint_counts call
 MCR_MAX_EXPENSE_FANOUT = 15  # spending levels one expense fan-out workgroup evaluates (mcr_probe_expenses_rng)
 
@@ -279,6 +283,29 @@ class McrOptionOutcomes(C.Structure):
     ]
 
 
+class McrSpendingRule(C.Structure):
+    """mcr_spending_rule: the withdrawal-rate guardrail of include/mcr.h."""
+
+    _fields_ = [
+        ("upper", C.c_double),
+        ("lower", C.c_double),
+        ("cut", C.c_double),
+        ("raise", C.c_double),
+        ("floor", C.c_double),
+        ("ceiling", C.c_double),
+    ]
+
+
+class McrRuleOutputs(C.Structure):
+    """mcr_rule_outputs: the per-year counts and the optional multiplier rows of mcr_run_rule_rng (device pointers)."""
+
+    _fields_ = [
+        ("year_counts", C.c_void_p),
+        ("multipliers", C.c_void_p),
+        ("path_stride", C.c_int64),
+    ]
+
+
 class McrSizes(C.Structure):
     _fields_ = [
         ("total_months", C.c_int32),
@@ -372,6 +399,8 @@ ABI_SYMBOLS = (
     "mcr_run_year_bins_host_rng",
     "mcr_run_year_bins_multi_host_rng",
     "mcr_validate_params",
+    "mcr_validate_spending_rule",
+    "mcr_run_rule_rng",
     "mcr_release_cached",
     "mcr_sample_columns",
     "mcr_eval_helper_host",
@@ -537,6 +566,14 @@ def _declare(lib: C.CDLL) -> None:
     ]
     lib.mcr_validate_params.restype = C.c_int
     lib.mcr_validate_params.argtypes = [P(McrParams)]
+    if hasattr(lib, "mcr_run_rule_rng"):   # (an MCR_HIP_LIBRARY built from an earlier tree, for A/B runs, lacks it)
+        lib.mcr_validate_spending_rule.restype = C.c_int
+        lib.mcr_validate_spending_rule.argtypes = [P(McrSpendingRule)]
+        lib.mcr_run_rule_rng.restype = C.c_int
+        lib.mcr_run_rule_rng.argtypes = [
+            P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32, P(McrSpendingRule), P(McrOutputs),
+            P(McrRuleOutputs), C.c_int, C.c_void_p,
+        ]
     lib.mcr_release_cached.restype = C.c_int
     lib.mcr_release_cached.argtypes = [C.c_int]
     lib.mcr_sample_columns.restype = C.c_int

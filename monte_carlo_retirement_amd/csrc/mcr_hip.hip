@@ -102,6 +102,13 @@ struct KernelIO {
         double* years_to_ruin;
         int64_t row_stride;
     };
+    // keep = 1 - cut and grow = 1 + raise, formed once on the host (the same two fp64 operations include/mcr.h states)
+    struct RuleIO {
+        double upper, lower, keep, grow, floor, ceiling;
+        unsigned long long* year_counts;      // [ry][MCR_RULE_N_COUNTS] or nullptr, accumulated into
+        double* multipliers;                  // [ry][stride] or nullptr
+        int64_t stride;
+    };
     union {
         double fan_expenses[MCR_MAX_EXPENSE_FANOUT];   // the fan-out levels
         YearBins yb;
@@ -110,6 +117,9 @@ struct KernelIO {
         // LIST (the re-run of a screened launch, path_kernel's LIST): lane i of the launch runs local path path_list[i] for
         // i < *path_list_count, both written by screen_kernel earlier on the stream.  Such a launch reads no fan-out level.
         struct { const uint32_t* path_list; const uint32_t* path_list_count; };
+        // RULE (mcr_run_rule_rng, path_kernel's RULE): the spending rule as the year's decision reads it and the rule outputs.
+        // Such a launch is a plain whole-path one: it reads no fan-out level, so the block shares those bytes as well.
+        RuleIO rule;
     };
     // PHASE 8 / 9 / 10, joint probes (mcr_probe_*_joint_rng): [fan_n][(n_paths + 63) / 64] success masks or nullptr; consumer wave j
     // stores its 64 paths' ballot to word blockIdx.x of row j.  Last, so every other field keeps its place in the kernel arguments
@@ -117,6 +127,7 @@ struct KernelIO {
 };
 static_assert(sizeof(KernelIO::YearBins) <= sizeof(double) * MCR_MAX_EXPENSE_FANOUT, "the yearly-bins block must fit the bytes it overlays");
 static_assert(sizeof(KernelIO::FanRows) <= sizeof(double) * MCR_MAX_EXPENSE_FANOUT, "the outcome rows must fit the bytes they overlay");
+static_assert(sizeof(KernelIO::RuleIO) <= sizeof(double) * MCR_MAX_EXPENSE_FANOUT, "the spending rule must fit the bytes it overlays");
 // path_kernel(DevParams, KernelIO, const DevParams*): a field of the second argument read from the kernel-argument segment at
 // the point of use (the arguments lie there in order, each at its natural alignment).  Wave-uniform: a scalar load.
 constexpr size_t kKernelIOArgOffset = (sizeof(DevParams) + alignof(KernelIO) - 1) / alignof(KernelIO) * alignof(KernelIO);
@@ -361,11 +372,65 @@ struct NoRuinMonth {};
 // PHASE 10: what a consumer wave keeps of its record's stream, and which of the kept records (DevParams::streams) it replaces
 struct IncomeRegs { double amount, amount_keep; int32_t start_month, end_month; int k; };
 struct NoIncomeRegs {};
+// RULE (mcr_run_rule_rng): the lane's spending multiplier m, r0 = B0 / P0 and whether the rule applies to the path at all
+struct RuleState { double m, r0; bool on; };
+struct NoRuleState {};
+// (the one value the month reads of it, chosen by overload like the month counters': every other kernel's expression is what it was)
+__device__ __forceinline__ double rule_scaled(const RuleState& r, double e) { return e * r.m; }
+__device__ __forceinline__ double rule_scaled(const NoRuleState&, double e) { return e; }
+// At retirement: m = 1; the rule is inert (m stays 1) for a path that starts retirement with B0 <= 1e-6.  One IEEE division a
+// path, none in the year loop.
+__device__ __forceinline__ void rule_begin(RuleState& r, double start_balance, double infl_ret) {
+    r.m = 1.0; r.on = start_balance > kEps; r.r0 = r.on ? start_balance / infl_ret : 0.0;
+}
+__device__ __forceinline__ void rule_begin(NoRuleState&, double, double) {}
+// Top of retirement year `year` (the whole wave is here).  The year's decision (include/mcr.h, mcr_spending_rule): B = b1 + b2
+// and P = infl are the yearly sample and its price level at the end of the year before.  q > upper  <=>  (m r0) P > upper B,
+// q < lower  <=>  (m r0) P < lower B (B >= 0; upper >= lower, so at most one holds): multiplies, two compares and selects, no
+// lane-divergent branch.  Lanes that do not begin the year keep their m: it is never read again.  Then the year's four counts,
+// wave ballots whose popcounts one lane adds with 64-bit vector atomics (zero counts skipped), and the multiplier row: the
+// lane's m, NaN (as a bit pattern) for a year the path does not begin.
+template <typename IO>
+__device__ __forceinline__ void rule_year(RuleState& r, const IO& io, int year, bool valid, bool alive, double b1, double b2, double infl, uint64_t li) {
+    if (year >= 1) {                                             // (wave-uniform)
+        const double B = b1 + b2;
+        const double lhs = (r.m * r.r0) * infl;
+        const bool go = alive && r.on;
+        const bool cut = go && lhs > io.rule.upper * B;
+        const bool up = go && lhs < io.rule.lower * B;
+        const double m_cut = fmax(io.rule.floor, r.m * io.rule.keep);
+        const double m_up = fmin(io.rule.ceiling, r.m * io.rule.grow);
+        r.m = cut ? m_cut : up ? m_up : r.m;
+    }
+    const bool begun = valid && alive;
+    const unsigned long long n_alive = __builtin_amdgcn_ballot_w64(begun);
+    const unsigned long long n_cut = __builtin_amdgcn_ballot_w64(begun && r.m < 1.0);
+    const unsigned long long n_floor = __builtin_amdgcn_ballot_w64(begun && io.rule.floor < 1.0 && r.m <= io.rule.floor);
+    const unsigned long long n_up = __builtin_amdgcn_ballot_w64(begun && r.m > 1.0);
+    unsigned long long* const yc = io.rule.year_counts;
+    if (yc && (threadIdx.x & 63) == 0) {
+        unsigned long long* const c = yc + (size_t)year * MCR_RULE_N_COUNTS;
+        if (n_alive) atomicAdd(&c[MCR_RULE_ALIVE], (unsigned long long)__popcll(n_alive));
+        if (n_cut) atomicAdd(&c[MCR_RULE_CUT], (unsigned long long)__popcll(n_cut));
+        if (n_floor) atomicAdd(&c[MCR_RULE_FLOOR], (unsigned long long)__popcll(n_floor));
+        if (n_up) atomicAdd(&c[MCR_RULE_RAISED], (unsigned long long)__popcll(n_up));
+    }
+    if (io.rule.multipliers && valid) store_bits(&io.rule.multipliers[(int64_t)year * io.rule.stride + (int64_t)li], alive ? f64_bits(r.m) : kNanBits);
+}
+template <typename IO>
+__device__ __forceinline__ void rule_year(NoRuleState&, const IO&, int, bool, bool, double, double, double, uint64_t) {}
+// a year the whole wave does not begin (the pad loop): NaN in the multiplier row
+template <typename IO>
+__device__ __forceinline__ void rule_pad(const RuleState&, const IO& io, int year, bool valid, uint64_t li) {
+    if (io.rule.multipliers && valid) store_bits(&io.rule.multipliers[(int64_t)year * io.rule.stride + (int64_t)li], kNanBits);
+}
+template <typename IO>
+__device__ __forceinline__ void rule_pad(const NoRuleState&, const IO&, int, bool, uint64_t) {}
 __device__ __forceinline__ void income_put(DevStream& S, const IncomeRegs& R) {
     S.amount = R.amount; S.amount_keep = R.amount_keep; S.start_month = R.start_month; S.end_month = R.end_month;
 }
 
-template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault, int GF = 0, int MF = 0, int SF = 0, bool OUT = false, bool LIST = false, int NPROD = 1>
+template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault, int GF = 0, int MF = 0, int SF = 0, bool OUT = false, bool LIST = false, int NPROD = 1, bool RULE = false>
 __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE == 8 || PHASE == 9 || PHASE == 10) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : NPROD == 2 ? 3 * 64 : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
                                                          const DevParams* __restrict__ cand_params) {
     // MODE 3 (mcr_run_year_bins_rng): YEARLY BINS.  The arithmetic of MODE 2, but wherever that variant stores a yearly sample
@@ -410,6 +475,18 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     // (MM, WAVE-UNIFORM fix-ups: straight-line code where the SPLIT month branches on lane masks; re-run of 10^6 config.json
     // paths 0.548 -> 0.503 ms on a development tree, LABNOTES R25), bit for bit the same counts.  Last, with a default, like LIST.
     static_assert(NPROD == 1 || (NPROD == 2 && SPLIT && LIST), "two producers exist for the split re-run of a screened launch");
+    // RULE (mcr_run_rule_rng; the guardrail spending rule of include/mcr.h): every lane carries a spending multiplier m (1 in
+    // retirement year 0) that scales the month's base expenses, (monthly_expenses m) price, and is decided again at the top of
+    // every retirement year y >= 1 from the balance and the price level the year starts with.  The decision is a handful of
+    // fp64 multiplies, two compares and selects: no lane-divergent branch.  The year's four counts are wave ballots, added by
+    // one lane; the optional multiplier row is one 512-byte wave store a year.  Last, with a default: everything it adds stands
+    // in overloads on the state object RS (rule_begin, rule_year, rule_pad, rule_scaled: empty for every other kernel's empty
+    // object, like the month counters' helpers), and every other instantiation keeps its registers.  (The same statements
+    // written in place under `if constexpr (RULE)` cost the time-sliced trajectory kernels, which never run them, one or two
+    // spilled SGPRs each.)
+    static_assert(!RULE || ((MODE == 0 || MODE == 1) && RNG == (int)MCR_RNG_PHILOX && TAXED == 3 && !INJ && PHASE == 0 && !SPLIT && !XS && EXACT == kExactMonthDefault &&
+                            GF == 0 && MF == 0 && SF == 0 && !OUT && !LIST && NPROD == 1),
+                  "the spending rule exists for the plain whole-path Philox launches, count-only and summary, on the generic tax mask");
     // PHASE 4 = PHASE 2 (a candidate's decumulation resumed from its accumulation snapshot) time-sliced like PHASE 3: the
     // 17-month verification window of the search is 17 x 196 workgroups = 2.17 rounds of the resident slots.
     constexpr bool kExpFan = PHASE == 5 || PHASE == 6;    // expense fan-out: the levels are monthly_expenses, resumed at retirement
@@ -435,6 +512,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     [[maybe_unused]] std::conditional_t<kSIR, StreamRegs, NoStreamRegs> SR;    // (an empty object in every other variant)
     [[maybe_unused]] std::conditional_t<kIncFan, IncomeRegs, NoIncomeRegs> IR;   // (likewise)
     [[maybe_unused]] std::conditional_t<OUT, RuinMonth, NoRuinMonth> RM;         // (likewise: the outcome probes' month of failure)
+    [[maybe_unused]] std::conditional_t<RULE, RuleState, NoRuleState> RS;        // (likewise: the spending rule's multiplier)
     static_assert(!kSliced || (RNG == 0 && !INJ && !SPLIT && !XS), "time-sliced blocks exist for the plain Philox variants");
     static_assert(PHASE != 4 || MODE == 0, "the search probes count only");
     // TAXED: which assets carry an effective realized-gains rate (bit 0: inv1, bit 1: inv2; DevParams::tax_mask)
@@ -902,6 +980,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     double infl_ret = infl;                // :582
     if (kSliced && seg_resumed) { start_balance = seg_start_balance; infl_ret = seg_infl_ret; t_idx = P.trajectory_len - ry + y_begin; }
     else if (wm > 0 && wm % kMPY != 0) put_sample(t_idx++, start_balance, infl_ret);  // :590-594
+    rule_begin(RS, start_balance, infl_ret);         // (RULE: m = 1 at retirement; nothing in every other kernel)
 
     // ---- decumulation (:632-868) ----
     double fy_gross = 0.0, fy_real = 0.0;            // :623-624
@@ -971,6 +1050,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     for (; year < (kSliced ? y_end : ry); ++year) {
         if (!SPLIT && __builtin_amdgcn_ballot_w64(alive) == 0ull) break;  // every lane of this wave has failed: nothing left to simulate
         if (SPLIT) { lane_alive = alive; if (wg_dead) break; }           // (SPLIT: the wave keeps pace with its producers' barriers until the workgroup votes to stop)
+        rule_year(RS, io, year, valid, alive, b1, b2, infl, li);      // (RULE: the year's decision, counts and multiplier row; nothing in every other kernel)
         double tg1 = 0.0, tg2 = 0.0, treal = 0.0;  // :635-637
         bool yfail = false;                        // :638
         int fail_rmi = 0;
@@ -981,7 +1061,8 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
                 double g1, ginf, g2;
                 if (kStaged) growth(month_row(SC, wm + rmi), g1, ginf, g2);    // staged factors: the LDS reads are issued early
                 const double price = infl;                             // :644
-                const double expenses = (kExpFan ? fan_expenses : kScnFan ? scn_expenses : P.monthly_expenses) * price;   // :645-647
+                // (RULE: the multiplier comes in HERE, not inside tol_month: (monthly_expenses m) price, so that m == 1.0 leaves every bit alone)
+                const double expenses = (kExpFan ? fan_expenses : kScnFan ? scn_expenses : rule_scaled(RS, P.monthly_expenses)) * price;   // :645-647
                 // exact form: income accumulates (:649-677) and need = max(0, expenses - income); tolerance form: `income` runs
                 // DOWN from the expenses, one FMA per indexed stream ((amount keep) price), one subtraction per frozen stream
                 // (its slot holds the netted amount): need = max(0, what is left)
@@ -1166,6 +1247,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         if constexpr (kBins) year_bins_row(io.yb, YB.L, YB.k++, valid, t_idx++, !(P.total_months % kMPY != 0 && year == ry - 1), 0.0, infl, year, kNanBits);
         else put_sample(t_idx++, 0.0, infl);
         if (kTraj && valid && wrt) store_bits(&wrt[(int64_t)year * stride + (int64_t)li], kNanBits);
+        rule_pad(RS, io, year, valid, li);
     }
     if (kSliced && seg >= 0 && seg < io.seg_q - 1) {
         // Not the block's last segment: raise the flag, to 1 with the lanes' state handed over, or to 2 (every wave gets here:
@@ -2836,6 +2918,87 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
     return MCR_OK;
 }
 
+// Spending rule (RULE of path_kernel; mcr_run_rule_rng).  The ranges of include/mcr.h; no device is needed.
+static int validate_spending_rule(const mcr_spending_rule* r) {
+    if (!r) { set_error("null spending rule"); return MCR_ERR_INVALID_ARG; }
+    const struct { const char* name; double v; } fields[] = {{"upper", r->upper}, {"lower", r->lower}, {"cut", r->cut},
+                                                             {"raise", r->raise}, {"floor", r->floor}, {"ceiling", r->ceiling}};
+    for (const auto& f : fields)
+        if (!std::isfinite(f.v)) { set_error("spending rule: %s = %g must be finite", f.name, f.v); return MCR_ERR_INVALID_ARG; }
+    if (!(r->upper >= 1.0)) { set_error("spending rule: upper = %g must be >= 1", r->upper); return MCR_ERR_INVALID_ARG; }
+    if (!(r->lower >= 0.0 && r->lower <= 1.0)) { set_error("spending rule: lower = %g must be in [0, 1]", r->lower); return MCR_ERR_INVALID_ARG; }
+    if (!(r->cut >= 0.0 && r->cut < 1.0)) { set_error("spending rule: cut = %g must be in [0, 1)", r->cut); return MCR_ERR_INVALID_ARG; }
+    if (!(r->raise >= 0.0)) { set_error("spending rule: raise = %g must be >= 0", r->raise); return MCR_ERR_INVALID_ARG; }
+    if (!(r->floor >= 0.0 && r->floor <= 1.0)) { set_error("spending rule: floor = %g must be in [0, 1]", r->floor); return MCR_ERR_INVALID_ARG; }
+    if (!(r->ceiling >= 1.0)) { set_error("spending rule: ceiling = %g must be >= 1", r->ceiling); return MCR_ERR_INVALID_ARG; }
+    return MCR_OK;
+}
+
+// One plain whole-path launch of the rule kernels: path_kernel<MODE 0 | 1, Philox, mask 3, annual-gains tax or not, ..., RULE>,
+// four instantiations.  Everything else a caller can ask for is refused by name before anything is enqueued.
+static int launch_rule(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths, int32_t wm,
+                       const mcr_spending_rule* rule, const mcr_outputs* out, const mcr_rule_outputs* rule_out, hipStream_t stream) {
+    DevParams d;
+    std::vector<DevStream> extra;
+    int rc = derive_params(p, wm, &d, &extra);
+    if (rc != MCR_OK) return rc;
+    rc = check_rng(rng);
+    if (rc != MCR_OK) return rc;
+    rc = validate_spending_rule(rule);
+    if (rc != MCR_OK) return rc;
+    if (!out) { set_error("null outputs"); return MCR_ERR_INVALID_ARG; }
+    if (n_paths > (uint64_t)INT32_MAX * kBlock) { set_error("n_paths too large for one launch"); return MCR_ERR_INVALID_ARG; }
+    if (path_begin + n_paths < path_begin) { set_error("path range overflows 64 bits"); return MCR_ERR_INVALID_ARG; }
+    if (rng->kind == MCR_RNG_NUMPY) { set_error("spending rule: the NumPy stream is not supported (the engine's own stream only)"); return MCR_ERR_UNSUPPORTED; }
+    if (rng->kind == MCR_RNG_HISTORY) { set_error("spending rule: the history stream is not supported (the engine's own stream only)"); return MCR_ERR_UNSUPPORTED; }
+    if (out->trajectory || out->real_trajectory || out->withdrawal_rate_trajectory) {
+        set_error("spending rule: trajectories are not supported (counters and per-path summary columns only)");
+        return MCR_ERR_UNSUPPORTED;
+    }
+    if (out->hist_bins && out->hist_n_bins != 0) { set_error("spending rule: the in-kernel histogram (hist_bins) is not supported"); return MCR_ERR_UNSUPPORTED; }
+    if (p->n_streams > MCR_INLINE_STREAMS && d.n_extra_streams > 0) {
+        set_error("spending rule: %d income streams need the generic variant (at most %d are supported)", (int)p->n_streams, MCR_INLINE_STREAMS);
+        return MCR_ERR_UNSUPPORTED;
+    }
+    if (needs_generic_variant(d)) { set_error("spending rule: the exact month (a realized-gains rate above 1 - 1e-6) needs the generic variant, which is not supported"); return MCR_ERR_UNSUPPORTED; }
+    KernelIO io = make_io(rng, nullptr, stream_id, path_begin, n_paths);
+    io.out = *out;
+    io.out.hist_bins = nullptr; io.out.hist_edges = nullptr; io.out.hist_n_bins = 0;
+    if (io.out.path_stride <= 0) io.out.path_stride = (int64_t)n_paths;
+    io.rule.upper = rule->upper; io.rule.lower = rule->lower; io.rule.keep = 1.0 - rule->cut; io.rule.grow = 1.0 + rule->raise;
+    io.rule.floor = rule->floor; io.rule.ceiling = rule->ceiling;
+    if (rule_out) {
+        io.rule.year_counts = (unsigned long long*)rule_out->year_counts; io.rule.multipliers = rule_out->multipliers;
+        io.rule.stride = rule_out->path_stride > 0 ? rule_out->path_stride : (int64_t)n_paths;
+        if (io.rule.multipliers && (uint64_t)io.rule.stride < n_paths) {
+            set_error("rule_out->path_stride %lld < n_paths %llu", (long long)io.rule.stride, (unsigned long long)n_paths);
+            return MCR_ERR_INVALID_ARG;
+        }
+    }
+    if (n_paths == 0) return MCR_OK;
+    const bool want_summary = out->start_balance || out->final_balance || out->years_to_ruin || out->first_year_gross_withdrawal ||
+                              out->first_year_real_gross_withdrawal || out->inflation_at_retirement || out->success;
+    const int mode = want_summary ? 1 : 0;
+    size_t lds = 0;
+    rc = plan_path_kernel_lds(d, mode, MCR_RNG_PHILOX, false, false, 0, &lds);
+    if (rc != MCR_OK) return rc;
+    if (d.n_lock_slots < d.n_lock_slots_total) {
+        set_error("spending rule: %d frozen income streams exceed the LDS budget and need the generic variant, which is not supported", (int)d.n_lock_slots_total);
+        return MCR_ERR_UNSUPPORTED;
+    }
+    const dim3 grid((unsigned)((n_paths + kBlock - 1) / kBlock)), block(kBlock);
+    const DevParams* const no_cand = nullptr;
+    for_bool(d.any_annual_tax, [&](auto A) {
+        for_bool(mode == 1, [&](auto S) {
+            hipLaunchKernelGGL((path_kernel<decltype(S)::value ? 1 : 0, 0, 3, decltype(A)::value, false, 0, false, false, kExactMonthDefault, 0, 0, 0, false, false, 1, true>),
+                               grid, block, lds, stream, d, io, no_cand);
+        });
+    });
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "path_kernel launch (spending rule)");
+    return MCR_OK;
+}
+
 // Yearly bins (MODE 3 of path_kernel; mcr_run_year_bins_rng).  Checks of the arguments both entry points share: nothing is
 // enqueued, and no table touched, unless they all pass.
 static int check_year_bins(const mcr_outputs* out, const mcr_year_bins* yb) {
@@ -3683,6 +3846,15 @@ int mcr_run_batch_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_i
     MCR_ENTER_DEVICE(device);
     return launch_paths(p, rng, stream_id, path_begin, n_paths, working_months, injected_shocks, out,
                         (hipStream_t)hip_stream);
+}
+
+int mcr_validate_spending_rule(const mcr_spending_rule* rule) { return validate_spending_rule(rule); }
+
+int mcr_run_rule_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                     int32_t working_months, const mcr_spending_rule* rule, mcr_outputs* out, mcr_rule_outputs* rule_out,
+                     int device, void* hip_stream) {
+    MCR_ENTER_DEVICE(device);
+    return launch_rule(p, rng, stream_id, path_begin, n_paths, working_months, rule, out, rule_out, (hipStream_t)hip_stream);
 }
 
 int mcr_probe_months_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,

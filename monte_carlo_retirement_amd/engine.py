@@ -900,3 +900,68 @@ def probe_grid(params: McrParams, seed, stream_id: int, path_begin: int, n_paths
     )
     N.check(rc, "mcr_probe_grid_rng")
     return counts
+
+
+def _rule_record(rule):
+    """`rule`: a `spending_rules.SpendingRule` or a ready ``McrSpendingRule``."""
+    return rule if isinstance(rule, N.McrSpendingRule) else rule.record()
+
+
+def run_rule(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int, rule,
+             want: str = "count", multipliers: bool = False, device: int = 0, out_extra: Optional[dict] = None):
+    """One launch under a spending rule (``mcr_run_rule_rng``) into device tensors, asynchronous on torch's current stream
+    (reading a tensor synchronises).  Returns a dict: ``counts`` = one int64 vector ``[2 + 4 ry]``, the counters followed by
+    ``year_counts`` row-major (one all-reduce sums it across ranks); with ``want="summary"`` the six float summary fields
+    and ``success`` (uint8); with ``multipliers`` the rows ``[ry, n_paths]`` (NaN for a year the path does not begin).
+    ``out_extra``: further ``McrOutputs`` fields by name (device addresses), for callers that test what the entry point
+    refuses."""
+    import torch
+
+    if want not in ("count", "summary"):
+        raise ValueError(want)
+    N.require_device()
+    n = int(n_paths)
+    sz = query_sizes(params, working_months)
+    ry = int(sz.retirement_years)
+    dev = torch.device("cuda", int(device))
+    res = {"counts": torch.zeros(N.MCR_N_COUNTERS + N.MCR_RULE_N_COUNTS * ry, dtype=torch.int64, device=dev)}
+    o = McrOutputs()
+    o.path_stride = n
+    o.counters = res["counts"].data_ptr()
+    if want == "summary":
+        for k in SUMMARY_FIELDS:
+            res[k] = torch.empty(n, dtype=torch.float64, device=dev)
+            setattr(o, k, res[k].data_ptr())
+        res["success"] = torch.empty(n, dtype=torch.uint8, device=dev)
+        o.success = res["success"].data_ptr()
+    for k, v in (out_extra or {}).items():
+        setattr(o, k, v)
+    ro = N.McrRuleOutputs()
+    ro.year_counts = res["counts"][N.MCR_N_COUNTERS:].data_ptr()
+    ro.path_stride = n
+    if multipliers:
+        res["multipliers"] = torch.empty((ry, n), dtype=torch.float64, device=dev)
+        ro.multipliers = res["multipliers"].data_ptr()
+    rec = _rule_record(rule)
+    rng = _as_rng(seed, int(device))
+    stream = torch.cuda.current_stream(int(device)).cuda_stream
+    rc = N.load_library().mcr_run_rule_rng(
+        C.byref(params), C.byref(rng), int(stream_id), int(path_begin), n, int(working_months), C.byref(rec), C.byref(o),
+        C.byref(ro), int(device), C.c_void_p(stream),
+    )
+    N.check(rc, "mcr_run_rule_rng")
+    return res
+
+
+def run_rule_host(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int, rule,
+                  want: str = "count", multipliers: bool = False, device: int = 0) -> Dict[str, np.ndarray]:
+    """`run_rule` with numpy arrays out: ``counters`` ``[2]``, ``year_counts`` ``[ry, 4]`` (columns ``MCR_RULE_ALIVE``,
+    ``_CUT``, ``_FLOOR``, ``_RAISED``), with ``want="summary"`` the summary fields and ``success`` as `run_batch_host`
+    returns them, with ``multipliers`` the rows ``[ry, n_paths]``."""
+    res = run_rule(params, seed, stream_id, path_begin, n_paths, working_months, rule, want=want, multipliers=multipliers,
+                   device=device)
+    out = {k: v.cpu().numpy() for k, v in res.items() if k != "counts"}
+    counts = res["counts"].cpu().numpy()
+    out["counters"] = counts[:N.MCR_N_COUNTERS].astype(np.uint64)
+    out["year_counts"] = counts[N.MCR_N_COUNTERS:].reshape(-1, N.MCR_RULE_N_COUNTS).astype(np.uint64)
+    return out

@@ -957,6 +957,96 @@ class RetirementMonteCarloSimulator:
                             f"({len(curve)} levels evaluated).")
         return expenses, prob, curve
 
+    # ---- spending rules ------------------------------------------------------------------------------
+    def _rule_counts(self, working_months: int, rule, params, n: int, multipliers: bool = False) -> np.ndarray:
+        """The integers of one launch under `rule` over the active stream's batch of ``n`` paths: the two counters, the
+        ``4 ry`` year counts and, with ``multipliers``, the number of paths that were ever cut.  Sharded by PATH RANGE through
+        `distributed.probe_candidates` (one all-reduce; every rank returns the same vector)."""
+        wm, ry = int(working_months), int(self.params_model.retirement_years)
+        rng, dev = self._batch_rng(n), self._local_device()
+        width = N.MCR_N_COUNTERS + N.MCR_RULE_N_COUNTS * ry + (1 if multipliers else 0)
+
+        def probe(path_begin, count, _):
+            if not multipliers:
+                return E.run_rule(params, rng, self._stream_id, path_begin, count, wm, rule, device=dev)["counts"]
+            res = E.run_rule_host(params, rng, self._stream_id, path_begin, count, wm, rule, multipliers=True, device=dev)
+            with np.errstate(invalid="ignore"):
+                ever = int(np.count_nonzero(np.any(res["multipliers"] < 1.0, axis=0)))
+            return np.concatenate([res["counters"].astype(np.int64), res["year_counts"].astype(np.int64).reshape(-1), [ever]])
+
+        return D.probe_candidates([0], n, self.shard_min_paths, probe, width=width)[0]
+
+    def success_probability_with_rule(self, working_months: int, rule, monthly_expenses=None,
+                                      num_simulations: Optional[int] = None):
+        """Success % at ``working_months`` when spending follows `rule` (a `spending_rules.SpendingRule`), over the active
+        seed stream's batch of ``num_simulations`` paths (default ``num_simulations_main``).  ``monthly_expenses``: None (the
+        config's own level; returns a float), one level (a float) or a sequence of levels (an array aligned with it): the
+        spending the path STARTS with.  One launch per level (``mcr_run_rule_rng``), as the history stream's probes run.
+        Under the neutral rule each value equals `success_probability_by_expenses` at the same level, bit for bit."""
+        n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
+        scalar = monthly_expenses is None or np.ndim(monthly_expenses) == 0
+        levels = [None] if monthly_expenses is None else [float(x) for x in np.atleast_1d(np.asarray(monthly_expenses, dtype=np.float64))]
+        out = []
+        for level in levels:
+            params = params_from_config(self.params_model)     # (a block of this call's own: the level goes into it)
+            if level is not None:
+                params.monthly_expenses = level
+            counts = self._rule_counts(working_months, rule, params, n)
+            out.append(self._count_percent(counts[N.MCR_CTR_SUCCESS], n))
+        return float(out[0]) if scalar else np.array(out, dtype=np.float64)
+
+    def spending_rule_outcomes(self, working_months: int, rule, num_simulations: Optional[int] = None, multipliers: bool = False):
+        """What `rule` does to the plan at ``working_months``: one count-only launch over the active stream's batch returns
+        the ``2 + 4 ry`` integers of a `spending_rules.SpendingRuleOutcomes` (success count; per retirement year the paths
+        alive, cut, at the floor and raised).  ``multipliers=True`` also downloads the multiplier rows and counts the paths
+        that were ever cut (``ever_cut_share``).  Under a process group the integers are summed in one all-reduce and every
+        rank returns the same object."""
+        from .spending_rules import SpendingRuleOutcomes
+
+        n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
+        ry = int(self.params_model.retirement_years)
+        flat = self._rule_counts(working_months, rule, self._current_params(), n, multipliers=bool(multipliers))
+        k = N.MCR_N_COUNTERS + N.MCR_RULE_N_COUNTS * ry
+        return SpendingRuleOutcomes(int(flat[N.MCR_CTR_SUCCESS]), n, flat[N.MCR_N_COUNTERS:k].reshape(ry, N.MCR_RULE_N_COUNTS),
+                                    retirement_age(self.params_model.current_age, int(working_months)),
+                                    ever_cut=int(flat[k]) if multipliers else None)
+
+    def find_maximum_initial_expenses(
+        self,
+        working_months: int,
+        rule,
+        resolution: float = 1.0,
+        verbose: bool = True,
+        progress_callback: Optional[Callable[[dict], None]] = None,
+    ) -> Tuple[float, float, List[Dict[str, float]]]:
+        """`find_maximum_monthly_expenses` for a household that follows `rule`: the largest ``monthly_expenses`` to START
+        retirement with (whole cents) that still reaches ``target_probability``.  The same search
+        (`spending.search_maximum_expenses`), stream, path count and return shape, ``-1.0`` when even zero spending misses
+        the target; its probe is `success_probability_with_rule`.  With the neutral rule the result is exactly
+        `find_maximum_monthly_expenses`'."""
+        from .spending import EXPENSE_CAP, search_maximum_expenses
+
+        self.use_search_seeds()
+        p = self.params_model
+        n_sims, target = int(p.num_simulations_search), float(p.target_probability)
+        if verbose:
+            logger.info(f"Searching the maximum initial monthly expenses under a spending rule at {int(working_months)} working "
+                        f"months for '{p.Nickname}' (target {target:.2f}%, {n_sims} sims per level, resolution {resolution}).")
+
+        def probe_levels(levels):
+            return list(self.success_probability_with_rule(working_months, rule, list(levels), n_sims))
+
+        expenses, prob, curve = search_maximum_expenses(
+            probe_levels, target, max(float(p.monthly_expenses), 1.0), levels_per_call=N.MCR_MAX_EXPENSE_FANOUT,
+            resolution=resolution, cap=EXPENSE_CAP, on_level=progress_callback)
+        if verbose:
+            if expenses < 0:
+                logger.warning(f"Target not met even without spending: {prob:.2f}% at {int(working_months)} months.")
+            else:
+                logger.info(f"  Rule expense search complete: {expenses:.2f} per month to begin with, prob {prob:.2f}% "
+                            f"({len(curve)} levels evaluated).")
+        return expenses, prob, curve
+
     # ---- minimum-contribution search ---------------------------------------------------------------
     def success_probability_by_contributions(self, working_months: int, monthly_contributions: Sequence[float],
                                              num_simulations: Optional[int] = None) -> np.ndarray:
