@@ -138,7 +138,25 @@ def main() -> int:
     ap.add_argument("--spending-rule", default=None, metavar="UPPER,LOWER,CUT,RAISE,FLOOR,CEILING",
                     help="a guardrail spending rule: alone, what it does to the plan year by year; with --max-expenses, the "
                          "maximum spending to begin with under the rule beside the fixed-spending answer (needs --working-months)")
+    ap.add_argument("--compare-rules", default=None, metavar="RULE;RULE;...",
+                    help="spending rules compared over the same paths at --working-months: each UPPER,LOWER,CUT,RAISE,FLOOR,CEILING "
+                         "or 'none' (fixed spending), separated by ';'; composes with --paired and --outcomes")
     args = ap.parse_args()
+    if args.compare_rules is not None:
+        from monte_carlo_retirement_amd.spending_rules import SpendingRule
+
+        if args.working_months is None:
+            ap.error("--compare-rules needs --working-months")
+        if args.rng != "philox" or args.history:
+            ap.error("--compare-rules runs on the engine's own stream")
+        if args.spending_rule is not None:
+            ap.error("--compare-rules and --spending-rule are separate questions")
+        try:
+            args.compare_rules = [None if t.strip().lower() == "none" else SpendingRule.parse(t) for t in args.compare_rules.split(";") if t.strip()]
+        except ValueError as e:
+            ap.error(str(e))
+        if not args.compare_rules:
+            ap.error("--compare-rules needs at least one rule")
     if args.spending_rule is not None:
         from monte_carlo_retirement_amd.spending_rules import SpendingRule
 
@@ -162,10 +180,10 @@ def main() -> int:
         ap.error("--income-options / --min-income and the other searches are separate questions")
     if args.income_options is not None and args.min_income is not None:
         ap.error("--income-options and --min-income are separate questions")
-    if args.paired and args.income_options is None and not args.stress:
-        ap.error("--paired goes with --income-options or --stress")
-    if args.outcomes and args.income_options is None and not args.stress:
-        ap.error("--outcomes goes with --income-options or --stress")
+    if args.paired and args.income_options is None and not args.stress and args.compare_rules is None:
+        ap.error("--paired goes with --income-options, --stress or --compare-rules")
+    if args.outcomes and args.income_options is None and not args.stress and args.compare_rules is None:
+        ap.error("--outcomes goes with --income-options, --stress or --compare-rules")
     if (args.claim_ages or args.claim_amounts) and args.income_options is None:
         ap.error("--claim-ages / --claim-amounts go with --income-options")
     if args.claim_age is not None and args.min_income is None:
@@ -230,6 +248,8 @@ def main() -> int:
 
     if args.cohorts:
         return cohorts(args, config, world, rank0)
+    if args.compare_rules is not None:
+        return compare_rules(args, config, world, rank0)
     if args.spending_rule is not None and not args.max_expenses:
         return spending_rule(args, config, world, rank0)
     if args.max_expenses:
@@ -348,6 +368,42 @@ def spending_rule(args, config: Config, world: int, rank0: bool) -> int:
             print(f"{'year':>4} {'age':>6} {'alive':>7} {'cut':>7} {'floor':>7} {'raised':>7}")
             for y in out["years"]:
                 print(f"{y['year']:>4} {y['age']:>6.1f} {100 * y['alive']:>6.1f}% {100 * y['cut']:>6.1f}% {100 * y['at_floor']:>6.1f}% {100 * y['raised']:>6.1f}%")
+    if world > 1:
+        import torch.distributed as dist
+
+        dist.barrier()
+        dist.destroy_process_group()
+    return 0
+
+
+def compare_rules(args, config: Config, world: int, rank0: bool) -> int:
+    """--compare-rules: which guardrail to choose.  One row per rule over the same paths: success %, the shares of all paths
+    that are cut / at the floor in the last retirement year, and with --paired the gap to the best rule and whether it is real."""
+    t0 = time.perf_counter()
+    sim = _simulator(args, config)
+    sim.use_final_seeds()
+    table = sim.compare_spending_rules(int(args.working_months), [{"rule": r} for r in args.compare_rules], **_table_flags(args))
+    out = {"scenario": config.Nickname, "rng": args.rng, "working_months": int(args.working_months),
+           "num_simulations": int(config.num_simulations_main), "target_probability": config.target_probability, **table,
+           "seconds": round(time.perf_counter() - t0, 3)}
+    if rank0:
+        if args.full:
+            print(json.dumps(out))
+        else:
+            print(f"{config.Nickname}: {len(table['options'])} spending rules over {out['num_simulations']} shared paths, best = #{table['best']}")
+            print(f"{'#':>2} {'rule':<32} {'success':>8} {'cut@end':>8} {'floor@end':>9}" + (f" {'vs best':>8} {'se':>6} {'p':>7}" if args.paired else "")
+                  + (f" {'lasts 95%':>9} {'median left':>12}" if args.outcomes else ""))
+            for i, row in enumerate(table["options"]):
+                r, last = row["rule"], row["years"][-1]
+                name = "fixed spending" if r is None else ",".join(f"{r[k]:g}" for k in ("upper", "lower", "cut", "raise", "floor", "ceiling"))
+                line = f"{i:>2} {name:<32} {row['probability']:>7.2f}% {100 * last['cut']:>7.1f}% {100 * last['at_floor']:>8.1f}%"
+                if args.paired:
+                    d = row["vs_best"]
+                    line += f" {d['delta']:>8.2f} {d['se']:>6.2f} {d['p_value']:>7.4f}"
+                if args.outcomes:
+                    age, med = row["lasts_until_age"]["95"], row["final_balance"]["p50"]
+                    line += f" {'horizon' if age is None else format(age, '.1f'):>9} {'-' if med is None else format(med, ',.0f'):>12}"
+                print(line)
     if world > 1:
         import torch.distributed as dist
 

@@ -696,11 +696,59 @@ int mcr_validate_spending_rule(const mcr_spending_rule* rule);
  * MCR_ERR_UNSUPPORTED, with a message that names what was asked and nothing computed, for: trajectory pointers in `out`; the
  * in-kernel histogram (hist_bins); the NumPy and history streams; a parameter block that needs the generic variant (more than
  * MCR_INLINE_STREAMS kept income streams, frozen streams beyond the LDS budget, or the exact month of a realized-gains rate
- * above 1 - 1e-6).  There are no yearly bins, injected shocks, fan-out, time-sliced, split or screened forms of this launch.
+ * above 1 - 1e-6).  There are no yearly bins, injected shocks, time-sliced, split or screened forms of this launch; several rules
+ * over the same paths are mcr_probe_rules_rng's, below.
  */
 int mcr_run_rule_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
                      int32_t working_months, const mcr_spending_rule* rule, mcr_outputs* out, mcr_rule_outputs* rule_out,
                      int device, void* hip_stream);
+
+/*
+ * Rule options: SEVERAL spending rules (and versions of the scenario probe's three fields) at one working-month count over the
+ * same path range -- a tight band with small cuts against a wide band with large ones, cut-only, fixed spending -- the probe of
+ * the rule comparison table and of the rule's spending search.  Row k of counts and of year_counts equals, bit for bit, the
+ * counters and the year_counts of a count-only mcr_run_rule_rng call with the same arguments, initial_balance,
+ * monthly_contribution and monthly_expenses of *p replaced by options[k]'s, and rule = options[k].rule.
+ *   counts:      DEVICE uint64 [n_options][MCR_N_COUNTERS] = {successes, paths};
+ *   year_counts: DEVICE uint64 [n_options][retirement_years][MCR_RULE_N_COUNTS] or NULL = not requested.
+ * Both are ZEROED by the call (like every probe's counts; mcr_run_rule_rng accumulates).  options is a HOST array of
+ * n_options >= 0 records (0 does nothing; duplicates allowed).  The three amounts finite and >= 0 (config.py:56, 57, 59), every
+ * rule in mcr_validate_spending_rule's ranges; everything is validated on the host before the device is touched and before
+ * anything is enqueued: on any error every output stays untouched and the message names options[k].<field> or
+ * options[k].rule.<field>.
+ * What mcr_run_rule_rng refuses is refused here, MCR_ERR_UNSUPPORTED with nothing computed: the NumPy and history streams, more
+ * than MCR_INLINE_STREAMS kept income streams, frozen streams beyond the LDS budget, the exact month.  There is no route for
+ * them to fall back to.  One option: the plain rule launch.  Otherwise, with n_paths <= 2^31 and at least
+ * MCR_RULE_FANOUT_MIN_WAVES path-wavefronts (environment, default 0, read per call): RULE FAN-OUT launches, the scenario
+ * fan-out's workgroup in which each of up to MCR_MAX_EXPENSE_FANOUT consumer waves also carries its own rule and multiplier;
+ * the records (the three amounts, upper, lower, 1 - cut, 1 + raise, floor, ceiling) travel in a stream-ordered device table of
+ * 72 B each, released behind the launches.  Where the knob rules the fan-out out: one mcr_run_rule_rng launch per option on
+ * internal side streams, joined back onto `hip_stream`.  No multiplier rows in this form.  Asynchronous like
+ * mcr_probe_scenarios_rng.
+ * mcr_probe_rules_joint_rng and mcr_probe_rules_outcomes_rng add the arguments of mcr_probe_scenarios_joint_rng and
+ * mcr_probe_scenarios_outcomes_rng with their contracts (JOINT OUTCOMES and PER-OPTION OUTCOMES above; the cap
+ * MCR_MAX_JOINT_OPTIONS and a null `joint`, and rows->path_stride < n_paths, are checked first): the mask rows are the success
+ * columns, and the rows are where(success, final_balance, NaN) and years_to_ruin, of summary mcr_run_rule_rng launches of the
+ * options, bit for bit on both routes; elements of a row at or beyond n_paths are never written.
+ * mcr_probe_rules_last_fanout_launches reports, for the calling thread's last call, how many rule fan-out launches it
+ * enqueued: ceil(n_options / options per launch) on the fan-out route, 0 on the others and after an error.
+ */
+typedef struct mcr_rule_option {
+    double initial_balance, monthly_contribution, monthly_expenses;   /* as mcr_scenario */
+    mcr_spending_rule rule;
+} mcr_rule_option;                                                     /* 72 bytes */
+int mcr_probe_rules_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                        uint64_t n_paths, int32_t working_months, const mcr_rule_option* options, int32_t n_options,
+                        uint64_t* counts, uint64_t* year_counts, int device, void* hip_stream);
+int mcr_probe_rules_joint_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                              uint64_t n_paths, int32_t working_months, const mcr_rule_option* options, int32_t n_options,
+                              uint64_t* counts, uint64_t* year_counts, uint64_t* masks, uint64_t* joint, uint64_t* extremes,
+                              int device, void* hip_stream);
+int mcr_probe_rules_outcomes_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                 uint64_t n_paths, int32_t working_months, const mcr_rule_option* options, int32_t n_options,
+                                 uint64_t* counts, uint64_t* year_counts, const mcr_option_outcomes* rows,
+                                 int device, void* hip_stream);
+int mcr_probe_rules_last_fanout_launches(void);
 
 /* _draw_shock_path (simulation.py:452-466) for n_paths paths: host out [n_paths][n_months][3]. */
 int mcr_draw_shocks_host(uint64_t seed, uint32_t stream_id, uint64_t path_begin,

@@ -306,6 +306,17 @@ class McrRuleOutputs(C.Structure):
     ]
 
 
+class McrRuleOption(C.Structure):
+    """One record of a rule probe (include/mcr.h: mcr_rule_option): the three scenario levers and the option's spending rule."""
+
+    _fields_ = [
+        ("initial_balance", C.c_double),
+        ("monthly_contribution", C.c_double),
+        ("monthly_expenses", C.c_double),
+        ("rule", McrSpendingRule),
+    ]
+
+
 class McrSizes(C.Structure):
     _fields_ = [
         ("total_months", C.c_int32),
@@ -401,6 +412,10 @@ ABI_SYMBOLS = (
     "mcr_validate_params",
     "mcr_validate_spending_rule",
     "mcr_run_rule_rng",
+    "mcr_probe_rules_rng",
+    "mcr_probe_rules_joint_rng",
+    "mcr_probe_rules_outcomes_rng",
+    "mcr_probe_rules_last_fanout_launches",
     "mcr_release_cached",
     "mcr_sample_columns",
     "mcr_eval_helper_host",
@@ -574,6 +589,17 @@ def _declare(lib: C.CDLL) -> None:
             P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32, P(McrSpendingRule), P(McrOutputs),
             P(McrRuleOutputs), C.c_int, C.c_void_p,
         ]
+    if hasattr(lib, "mcr_probe_rules_rng"):   # (likewise)
+        head = [P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32, P(McrRuleOption), C.c_int32,
+                C.c_void_p, C.c_void_p]   # ..., options, n_options, counts, year_counts
+        lib.mcr_probe_rules_rng.restype = C.c_int
+        lib.mcr_probe_rules_rng.argtypes = head + [C.c_int, C.c_void_p]
+        lib.mcr_probe_rules_joint_rng.restype = C.c_int
+        lib.mcr_probe_rules_joint_rng.argtypes = head + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]   # masks, joint, extremes
+        lib.mcr_probe_rules_outcomes_rng.restype = C.c_int
+        lib.mcr_probe_rules_outcomes_rng.argtypes = head + [P(McrOptionOutcomes), C.c_int, C.c_void_p]
+        lib.mcr_probe_rules_last_fanout_launches.restype = C.c_int
+        lib.mcr_probe_rules_last_fanout_launches.argtypes = []
     lib.mcr_release_cached.restype = C.c_int
     lib.mcr_release_cached.argtypes = [C.c_int]
     lib.mcr_sample_columns.restype = C.c_int

@@ -109,6 +109,10 @@ struct KernelIO {
         double* multipliers;                  // [ry][stride] or nullptr
         int64_t stride;
     };
+    struct FanRuleRows {
+        FanRows rows;
+        unsigned long long* year_counts;
+    };
     union {
         double fan_expenses[MCR_MAX_EXPENSE_FANOUT];   // the fan-out levels
         YearBins yb;
@@ -120,6 +124,9 @@ struct KernelIO {
         // RULE (mcr_run_rule_rng, path_kernel's RULE): the spending rule as the year's decision reads it and the rule outputs.
         // Such a launch is a plain whole-path one: it reads no fan-out level, so the block shares those bytes as well.
         RuleIO rule;
+        // PHASE 11 (rule fan-out, mcr_probe_rules_rng): the outcome rows where the other outcome probes keep them, and behind them
+        // the options' year counts, [fan_n][ry][MCR_RULE_N_COUNTS] or nullptr.  The rules themselves travel in the device table.
+        FanRuleRows fan_rule;
     };
     // PHASE 8 / 9 / 10, joint probes (mcr_probe_*_joint_rng): [fan_n][(n_paths + 63) / 64] success masks or nullptr; consumer wave j
     // stores its 64 paths' ballot to word blockIdx.x of row j.  Last, so every other field keeps its place in the kernel arguments
@@ -128,6 +135,8 @@ struct KernelIO {
 static_assert(sizeof(KernelIO::YearBins) <= sizeof(double) * MCR_MAX_EXPENSE_FANOUT, "the yearly-bins block must fit the bytes it overlays");
 static_assert(sizeof(KernelIO::FanRows) <= sizeof(double) * MCR_MAX_EXPENSE_FANOUT, "the outcome rows must fit the bytes they overlay");
 static_assert(sizeof(KernelIO::RuleIO) <= sizeof(double) * MCR_MAX_EXPENSE_FANOUT, "the spending rule must fit the bytes it overlays");
+static_assert(sizeof(KernelIO::FanRuleRows) <= sizeof(double) * MCR_MAX_EXPENSE_FANOUT && offsetof(KernelIO::FanRuleRows, rows) == 0,
+              "the rule fan-out's rows must fit the bytes they overlay, the outcome rows where every outcome probe reads them");
 // path_kernel(DevParams, KernelIO, const DevParams*): a field of the second argument read from the kernel-argument segment at
 // the point of use (the arguments lie there in order, each at its natural alignment).  Wave-uniform: a scalar load.
 constexpr size_t kKernelIOArgOffset = (sizeof(DevParams) + alignof(KernelIO) - 1) / alignof(KernelIO) * alignof(KernelIO);
@@ -159,6 +168,14 @@ struct IncomeRecord {
     int32_t start_month, end_month;
 };
 static_assert(sizeof(IncomeRecord) == 6 * sizeof(double), "IncomeRecord is five packed doubles and two months");
+// PHASE 11 (rule probe, mcr_probe_rules_rng): consumer wave j of a launch runs record j of the launch's device table, through
+// `cand_params` as well: PHASE 8's three values and the option's spending rule as the year's decision reads it (KernelIO::RuleIO's
+// six values: keep = 1 - cut and grow = 1 + raise formed on the host by the two operations launch_rule performs)
+struct RuleRecord {
+    double initial_balance, monthly_contribution, monthly_expenses;
+    double upper, lower, keep, grow, floor, ceiling;
+};
+static_assert(sizeof(RuleRecord) == 9 * sizeof(double), "RuleRecord is nine packed doubles");
 struct AssumptionRecord {
     double initial_balance, monthly_contribution, monthly_expenses;
     double a1, b1, ainf, binf_rho, binf_rho_c, aprem, bprem;
@@ -329,6 +346,13 @@ __device__ __forceinline__ void year_bins_flush_final(const KernelIO::YearBins& 
 // the first-active-month store works per wave unchanged.  The host always hands the kernel the probed stream, also when the
 // list's own amount is 0; a record with amount 0 then subtracts an exact zero, as the plain launch that drops it.  Counts are
 // bit-identical to a count-only launch with the six fields replaced by record j.
+// PHASE 11 (SPLIT = true, RULE = true; mcr_probe_rules_rng): RULE FAN-OUT = PHASE 8's workgroup, barriers and votes, with a SPENDING
+// RULE per consumer wave as well: which guardrail, over the same random numbers.  The launch's records are a device table of
+// RuleRecord behind `cand_params` (scalar loads): PHASE 8's three values and the rule as the year's decision reads it.  The lanes
+// carry the rule launch's RuleState through its overloads; the year's decision and ballots are rule_year_from on the wave's own
+// FanRule (its six values and option j's table of the launch's year counts), the month spends (scn_expenses m) price.  No
+// multiplier rows.  Mask 3 only, like the rule launch.  Counts and year counts are bit-identical to a count-only rule launch
+// with the three fields replaced by record j under record j's rule.
 // EXACT = true: the month in its exact-rounding forms (mcr_device.h) instead of the tolerance form — for configurations whose
 // realized-gains rate lets the reference's denominator clamps bind (DevParams::exact_month), instantiated for the generic XS
 // variants only; -DMCR_K1_EXACT_MONTH builds a library that runs every variant that way (A/B).
@@ -390,24 +414,26 @@ __device__ __forceinline__ void rule_begin(NoRuleState&, double, double) {}
 // lane-divergent branch.  Lanes that do not begin the year keep their m: it is never read again.  Then the year's four counts,
 // wave ballots whose popcounts one lane adds with 64-bit vector atomics (zero counts skipped), and the multiplier row: the
 // lane's m, NaN (as a bit pattern) for a year the path does not begin.
-template <typename IO>
-__device__ __forceinline__ void rule_year(RuleState& r, const IO& io, int year, bool valid, bool alive, double b1, double b2, double infl, uint64_t li) {
+// The rule and its outputs come from a SOURCE R: KernelIO::RuleIO, the launch's one rule in the kernel arguments (the plain rule
+// launch, rule_year below), or FanRule, a consumer wave's own rule and year counts (the rule fan-out, PHASE 11).
+template <typename SRC>
+__device__ __forceinline__ void rule_year_from(RuleState& r, const SRC& R, int year, bool valid, bool alive, double b1, double b2, double infl, uint64_t li) {
     if (year >= 1) {                                             // (wave-uniform)
         const double B = b1 + b2;
         const double lhs = (r.m * r.r0) * infl;
         const bool go = alive && r.on;
-        const bool cut = go && lhs > io.rule.upper * B;
-        const bool up = go && lhs < io.rule.lower * B;
-        const double m_cut = fmax(io.rule.floor, r.m * io.rule.keep);
-        const double m_up = fmin(io.rule.ceiling, r.m * io.rule.grow);
+        const bool cut = go && lhs > R.upper * B;
+        const bool up = go && lhs < R.lower * B;
+        const double m_cut = fmax(R.floor, r.m * R.keep);
+        const double m_up = fmin(R.ceiling, r.m * R.grow);
         r.m = cut ? m_cut : up ? m_up : r.m;
     }
     const bool begun = valid && alive;
     const unsigned long long n_alive = __builtin_amdgcn_ballot_w64(begun);
     const unsigned long long n_cut = __builtin_amdgcn_ballot_w64(begun && r.m < 1.0);
-    const unsigned long long n_floor = __builtin_amdgcn_ballot_w64(begun && io.rule.floor < 1.0 && r.m <= io.rule.floor);
+    const unsigned long long n_floor = __builtin_amdgcn_ballot_w64(begun && R.floor < 1.0 && r.m <= R.floor);
     const unsigned long long n_up = __builtin_amdgcn_ballot_w64(begun && r.m > 1.0);
-    unsigned long long* const yc = io.rule.year_counts;
+    unsigned long long* const yc = R.year_counts;
     if (yc && (threadIdx.x & 63) == 0) {
         unsigned long long* const c = yc + (size_t)year * MCR_RULE_N_COUNTS;
         if (n_alive) atomicAdd(&c[MCR_RULE_ALIVE], (unsigned long long)__popcll(n_alive));
@@ -415,8 +441,21 @@ __device__ __forceinline__ void rule_year(RuleState& r, const IO& io, int year, 
         if (n_floor) atomicAdd(&c[MCR_RULE_FLOOR], (unsigned long long)__popcll(n_floor));
         if (n_up) atomicAdd(&c[MCR_RULE_RAISED], (unsigned long long)__popcll(n_up));
     }
-    if (io.rule.multipliers && valid) store_bits(&io.rule.multipliers[(int64_t)year * io.rule.stride + (int64_t)li], alive ? f64_bits(r.m) : kNanBits);
+    if (R.multipliers && valid) store_bits(&R.multipliers[(int64_t)year * R.stride + (int64_t)li], alive ? f64_bits(r.m) : kNanBits);
 }
+template <typename IO>
+__device__ __forceinline__ void rule_year(RuleState& r, const IO& io, int year, bool valid, bool alive, double b1, double b2, double infl, uint64_t li) {
+    rule_year_from(r, io.rule, year, valid, alive, b1, b2, infl, li);
+}
+// PHASE 11: what a consumer wave keeps of its record's rule (wave-uniform values), and its option's year counts.  The form
+// writes no multiplier rows: the null pointer is a constant, and rule_year_from's store is not compiled.
+struct FanRule {
+    double upper, lower, keep, grow, floor, ceiling;
+    unsigned long long* year_counts;
+    static constexpr double* multipliers = nullptr;
+    static constexpr int64_t stride = 0;
+};
+struct NoFanRule {};
 template <typename IO>
 __device__ __forceinline__ void rule_year(NoRuleState&, const IO&, int, bool, bool, double, double, double, uint64_t) {}
 // a year the whole wave does not begin (the pad loop): NaN in the multiplier row
@@ -431,7 +470,7 @@ __device__ __forceinline__ void income_put(DevStream& S, const IncomeRegs& R) {
 }
 
 template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault, int GF = 0, int MF = 0, int SF = 0, bool OUT = false, bool LIST = false, int NPROD = 1, bool RULE = false>
-__global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE == 8 || PHASE == 9 || PHASE == 10) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : NPROD == 2 ? 3 * 64 : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
+__global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE == 8 || PHASE == 9 || PHASE == 10 || PHASE == 11) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : NPROD == 2 ? 3 * 64 : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
                                                          const DevParams* __restrict__ cand_params) {
     // MODE 3 (mcr_run_year_bins_rng): YEARLY BINS.  The arithmetic of MODE 2, but wherever that variant stores a yearly sample
     // (nominal balance, real balance, withdrawal rate) the lane bins it instead: cell 0 = below edges[0], cells 1 .. n = the
@@ -453,10 +492,11 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     static_assert(PHASE != 8 || SPLIT, "the scenario fan-out is a producer / consumer form");
     static_assert(PHASE != 9 || SPLIT, "the assumption fan-out is a producer / consumer form");
     static_assert(PHASE != 10 || SPLIT, "the income fan-out is a producer / consumer form");
+    static_assert(PHASE != 11 || (SPLIT && RULE), "the rule fan-out is a producer / consumer form of the rule kernels");
     // OUT (mcr_probe_*_outcomes_rng): the PHASE 8 / 9 / 10 consumer waves also store their paths' outcome rows (KernelIO::fan_final,
     // fan_ruin) in the epilogue.  A template flag, not a null check: the month of failure is one more VGPR through the month loop,
     // which the plain and the joint probes' kernels do not pay.
-    static_assert(!OUT || PHASE == 8 || PHASE == 9 || PHASE == 10, "outcome rows exist for the scenario, assumption and income fan-outs");
+    static_assert(!OUT || PHASE == 8 || PHASE == 9 || PHASE == 10 || PHASE == 11, "outcome rows exist for the scenario, assumption, income and rule fan-outs");
     // LIST (the re-run of a screened launch; launch_screened): the lanes' local path indices come from a device list that
     // screen_kernel filled earlier on the stream, io.path_list[i] for i < *io.path_list_count; lanes beyond the count behave
     // like tail lanes, and a workgroup whose first index is at or beyond the count returns at once (the host sizes the grid
@@ -484,9 +524,9 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     // object, like the month counters' helpers), and every other instantiation keeps its registers.  (The same statements
     // written in place under `if constexpr (RULE)` cost the time-sliced trajectory kernels, which never run them, one or two
     // spilled SGPRs each.)
-    static_assert(!RULE || ((MODE == 0 || MODE == 1) && RNG == (int)MCR_RNG_PHILOX && TAXED == 3 && !INJ && PHASE == 0 && !SPLIT && !XS && EXACT == kExactMonthDefault &&
-                            GF == 0 && MF == 0 && SF == 0 && !OUT && !LIST && NPROD == 1),
-                  "the spending rule exists for the plain whole-path Philox launches, count-only and summary, on the generic tax mask");
+    static_assert(!RULE || (RNG == (int)MCR_RNG_PHILOX && TAXED == 3 && !INJ && !XS && EXACT == kExactMonthDefault && GF == 0 && MF == 0 && SF == 0 && !LIST && NPROD == 1 &&
+                            (((MODE == 0 || MODE == 1) && PHASE == 0 && !SPLIT && !OUT) || (MODE == 0 && PHASE == 11 && SPLIT))),
+                  "the spending rule exists for the plain whole-path Philox launches, count-only and summary, and for the rule fan-out, on the generic tax mask");
     // PHASE 4 = PHASE 2 (a candidate's decumulation resumed from its accumulation snapshot) time-sliced like PHASE 3: the
     // 17-month verification window of the search is 17 x 196 workgroups = 2.17 rounds of the resident slots.
     constexpr bool kExpFan = PHASE == 5 || PHASE == 6;    // expense fan-out: the levels are monthly_expenses, resumed at retirement
@@ -494,7 +534,8 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     constexpr bool kAsmFan = PHASE == 9;                  // assumption fan-out: the scenario fan-out with the market per wave as well
     constexpr bool kStreamRegs = SPLIT && !kAsmFan;       // the first two income streams stay in SGPRs for the whole launch (S0, S1 below)
     constexpr bool kIncFan = PHASE == 10;                 // income fan-out: the scenario fan-out with one income stream per wave as well
-    constexpr bool kScnFan = PHASE == 8 || kAsmFan || kIncFan;   // scenario fan-out: balance, contribution and spending per wave, the whole path
+    constexpr bool kRuleFan = PHASE == 11;                // rule fan-out: the scenario fan-out with a spending rule per wave as well
+    constexpr bool kScnFan = PHASE == 8 || kAsmFan || kIncFan || kRuleFan;   // scenario fan-out: balance, contribution and spending per wave, the whole path
     constexpr bool kFan = kExpFan || kConFan || kScnFan;  // fan-out workgroup: one 64-path block, L consumer waves (levels), one producer wave
     constexpr bool kGrid = PHASE == 6;                    // ... of grid row blockIdx.y (GridCell)
     constexpr bool kCand = PHASE == 2 || PHASE == 4 || kExpFan;   // resumes from a PHASE 1 snapshot (PHASE 2 / 4: per-candidate parameter block)
@@ -513,6 +554,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     [[maybe_unused]] std::conditional_t<kIncFan, IncomeRegs, NoIncomeRegs> IR;   // (likewise)
     [[maybe_unused]] std::conditional_t<OUT, RuinMonth, NoRuinMonth> RM;         // (likewise: the outcome probes' month of failure)
     [[maybe_unused]] std::conditional_t<RULE, RuleState, NoRuleState> RS;        // (likewise: the spending rule's multiplier)
+    [[maybe_unused]] std::conditional_t<kRuleFan, FanRule, NoFanRule> FR;        // (likewise: PHASE 11, the consumer wave's own rule)
     static_assert(!kSliced || (RNG == 0 && !INJ && !SPLIT && !XS), "time-sliced blocks exist for the plain Philox variants");
     static_assert(PHASE != 4 || MODE == 0, "the search probes count only");
     // TAXED: which assets carry an effective realized-gains rate (bit 0: inv1, bit 1: inv2; DevParams::tax_mask)
@@ -880,6 +922,18 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         c1 = b1; c2 = b2;                        // :501-502
         contrib = rec->monthly_contribution;     // :504
         scn_expenses = rec->monthly_expenses;
+    } else if constexpr (kRuleFan) {             // PHASE 11: the record's three values likewise, and its rule (wave-uniform: scalar loads)
+        const RuleRecord* const rec = reinterpret_cast<const RuleRecord*>(cand_params) + fan_j;
+        const double rec_balance = rec->initial_balance;
+        b1 = rec_balance * P.alloc1;             // :499
+        b2 = rec_balance - b1;                   // :500
+        c1 = b1; c2 = b2;                        // :501-502
+        contrib = rec->monthly_contribution;     // :504
+        scn_expenses = rec->monthly_expenses;
+        FR.upper = rec->upper; FR.lower = rec->lower; FR.keep = rec->keep; FR.grow = rec->grow; FR.floor = rec->floor; FR.ceiling = rec->ceiling;
+        // option j's own table of the launch's year counts (the pointer is a launch constant read late, like the epilogue's)
+        unsigned long long* const yc = late_arg<unsigned long long*>(offsetof(KernelIO, fan_rule) + offsetof(KernelIO::FanRuleRows, year_counts));
+        FR.year_counts = yc ? yc + (size_t)fan_j * (size_t)P.retirement_years * MCR_RULE_N_COUNTS : nullptr;
     } else if constexpr (kScnFan) {
         const mcr_scenario* const scn = reinterpret_cast<const mcr_scenario*>(cand_params) + fan_j;
         const double scn_balance = scn->initial_balance;
@@ -1050,6 +1104,8 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     for (; year < (kSliced ? y_end : ry); ++year) {
         if (!SPLIT && __builtin_amdgcn_ballot_w64(alive) == 0ull) break;  // every lane of this wave has failed: nothing left to simulate
         if (SPLIT) { lane_alive = alive; if (wg_dead) break; }           // (SPLIT: the wave keeps pace with its producers' barriers until the workgroup votes to stop)
+        if constexpr (kRuleFan) rule_year_from(RS, FR, year, valid, alive, b1, b2, infl, li);   // (PHASE 11: the wave's own rule and year counts, no multiplier row)
+        else
         rule_year(RS, io, year, valid, alive, b1, b2, infl, li);      // (RULE: the year's decision, counts and multiplier row; nothing in every other kernel)
         double tg1 = 0.0, tg2 = 0.0, treal = 0.0;  // :635-637
         bool yfail = false;                        // :638
@@ -1062,7 +1118,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
                 if (kStaged) growth(month_row(SC, wm + rmi), g1, ginf, g2);    // staged factors: the LDS reads are issued early
                 const double price = infl;                             // :644
                 // (RULE: the multiplier comes in HERE, not inside tol_month: (monthly_expenses m) price, so that m == 1.0 leaves every bit alone)
-                const double expenses = (kExpFan ? fan_expenses : kScnFan ? scn_expenses : rule_scaled(RS, P.monthly_expenses)) * price;   // :645-647
+                const double expenses = (kExpFan ? fan_expenses : kScnFan ? rule_scaled(RS, scn_expenses) : rule_scaled(RS, P.monthly_expenses)) * price;   // :645-647
                 // exact form: income accumulates (:649-677) and need = max(0, expenses - income); tolerance form: `income` runs
                 // DOWN from the expenses, one FMA per indexed stream ((amount keep) price), one subtraction per frozen stream
                 // (its slot holds the netted amount): need = max(0, what is left)
@@ -1247,7 +1303,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         if constexpr (kBins) year_bins_row(io.yb, YB.L, YB.k++, valid, t_idx++, !(P.total_months % kMPY != 0 && year == ry - 1), 0.0, infl, year, kNanBits);
         else put_sample(t_idx++, 0.0, infl);
         if (kTraj && valid && wrt) store_bits(&wrt[(int64_t)year * stride + (int64_t)li], kNanBits);
-        rule_pad(RS, io, year, valid, li);
+        if constexpr (!kRuleFan) rule_pad(RS, io, year, valid, li);   // (PHASE 11 writes no multiplier row)
     }
     if (kSliced && seg >= 0 && seg < io.seg_q - 1) {
         // Not the block's last segment: raise the flag, to 1 with the lanes' state handed over, or to 2 (every wave gets here:
@@ -3504,6 +3560,61 @@ static int probe_income_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t
     return MCR_OK;
 }
 
+// Several (initial_balance, monthly_contribution, monthly_expenses, spending rule) options over the same paths, Philox stream:
+// rule fan-out launches (PHASE 11) over groups of at most fanout_max_levels records, the whole path each.  The records are made
+// on the host (keep = 1 - cut, grow = 1 + raise: launch_rule's two operations) into ONE stream-ordered device table, as the
+// scenario fan-out's.  The kernels are the generic tax mask's (TAXED = 3), like the plain rule launch's: a zero-rate asset's
+// arithmetic is exact zeros there.  Group g's launch counts the years of its options into year_counts at its first option.
+// Returns MCR_ERR_UNSUPPORTED, having enqueued nothing, for shapes this form does not cover and when the table's allocation
+// is refused.
+static thread_local int g_last_rule_fanout_launches = 0;   // (mcr_probe_rules_last_fanout_launches)
+static int probe_rules_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                              int32_t wm, const mcr_rule_option* options, int32_t n_options, uint64_t* counts, uint64_t* year_counts,
+                              hipStream_t stream, uint64_t* masks = nullptr /* joint probes: KernelIO::fan_masks of the whole option list */,
+                              const mcr_option_outcomes* rows = nullptr /* outcome probes: the rows of the whole option list */) {
+    DevParams d;
+    int lmax = 0;
+    if (int rc = plan_level_fanout(p, rng, n_paths, wm, n_options, fanout_min_waves("MCR_RULE_FANOUT_MIN_WAVES"), &d, &lmax)) return rc;
+    std::vector<RuleRecord> host((size_t)n_options);
+    for (int32_t k = 0; k < n_options; ++k) {
+        const mcr_rule_option& r = options[k];
+        host[(size_t)k] = RuleRecord{r.initial_balance, r.monthly_contribution, r.monthly_expenses,
+                                     r.rule.upper, r.rule.lower, 1.0 - r.rule.cut, 1.0 + r.rule.raise, r.rule.floor, r.rule.ceiling};
+    }
+    KernelIO io = make_io(rng, nullptr, stream_id, path_begin, n_paths);
+    SnapshotBlock table(stream);
+    hipError_t e = hipSuccess;
+    if (!table.attach(io, 0, host.data(), host.size() * sizeof(RuleRecord), &e, SIZE_MAX)) return MCR_ERR_UNSUPPORTED;
+    io.snap = nullptr;   // (no snapshot column: the block is the table alone)
+    if (e == hipSuccess) {
+        const RuleRecord* d_table = (const RuleRecord*)table.records;
+        const dim3 grid((unsigned)((n_paths + 63) / 64));
+        const LevelGroups groups(n_options, lmax);
+        for_bool(d.any_annual_tax, [&](auto A) {
+            groups.for_each([&](int, int first, int lg) {
+                KernelIO fio = io;
+                fio.out.counters = counts + (size_t)first * MCR_N_COUNTERS;
+                fio.fan_n = lg;
+                fio.fan_masks = masks ? masks + (size_t)first * ((n_paths + 63) / 64) : nullptr;
+                fio.fan_rule = KernelIO::FanRuleRows{};
+                set_fan_rows(fio, rows, first);
+                fio.fan_rule.year_counts = year_counts ? (unsigned long long*)year_counts + (size_t)first * (size_t)d.retirement_years * MCR_RULE_N_COUNTS : nullptr;
+                for_bool(rows != nullptr, [&](auto O) {
+                    hipLaunchKernelGGL((path_kernel<0, 0, 3, decltype(A)::value, false, 11, true, false, kExactMonthDefault, 0, 0, 0, decltype(O)::value, false, 1, true>),
+                                       grid, dim3(64 * (lg + 1)), fanout_dynamic_lds(d, lg), stream, d, fio, (const DevParams*)(d_table + first));
+                });
+                ++g_last_rule_fanout_launches;
+            });
+        });
+        e = hipGetLastError();
+    }
+    const hipError_t ef = table.mem.release();
+    if (e != hipSuccess) g_last_rule_fanout_launches = 0;
+    if (e != hipSuccess) return hip_fail(e, "rule fan-out probe");
+    if (ef != hipSuccess) return hip_fail(ef, "rule fan-out probe (free)");
+    return MCR_OK;
+}
+
 // A level probe (mcr_probe_expenses_rng / mcr_probe_contributions_rng): n_levels values of one field of the parameter block,
 // `name` (config.py:`config_line`) in messages.  kFanout, the shared-work route, is tried first; where it answers
 // MCR_ERR_UNSUPPORTED (unsupported shape / allocation refused) one launch per level runs instead.
@@ -4162,6 +4273,123 @@ int mcr_probe_income_outcomes_rng(const mcr_params* p, const mcr_rng* rng, uint3
 }
 
 int mcr_probe_income_last_fanout_launches(void) { return g_last_income_fanout_launches; }
+
+// What the rule probes check on the host, before the device and their outputs are touched: the block and the month, the stream,
+// every record (the message names options[k].<field> / options[k].rule.<field>), and everything launch_rule refuses -- there is
+// no route behind the rule kernels.  `summary`: the per-option route's launches are summary launches (joint, outcomes).
+static int check_rule_probe(const mcr_params* p, const mcr_rng* rng, uint64_t path_begin, uint64_t n_paths, int32_t working_months,
+                            const mcr_rule_option* options, int32_t n_options, const uint64_t* counts, bool summary) {
+    if (n_options < 0) { set_error("n_options %d must be >= 0", n_options); return MCR_ERR_INVALID_ARG; }
+    if (n_options == 0) return MCR_OK;
+    if (!options || !counts) { set_error("null options / counts"); return MCR_ERR_INVALID_ARG; }
+    DevParams d;
+    std::vector<DevStream> extra;
+    int rc = derive_params(p, working_months, &d, &extra);
+    if (rc != MCR_OK) return rc;
+    rc = check_rng(rng);
+    if (rc != MCR_OK) return rc;
+    static const struct { double mcr_rule_option::*field; const char* name; int config_line; } kAmounts[3] = {
+        {&mcr_rule_option::initial_balance, "initial_balance", 56},
+        {&mcr_rule_option::monthly_contribution, "monthly_contribution", 57},
+        {&mcr_rule_option::monthly_expenses, "monthly_expenses", 59}};
+    for (int32_t k = 0; k < n_options; ++k) {
+        for (const auto& f : kAmounts) {
+            const double v = options[k].*(f.field);
+            if (!(std::isfinite(v) && v >= 0.0)) {
+                set_error("options[%d].%s = %g: must be finite and >= 0 (config.py:%d)", k, f.name, v, f.config_line);
+                return MCR_ERR_INVALID_ARG;
+            }
+        }
+        if (validate_spending_rule(&options[k].rule) != MCR_OK) {
+            // "spending rule: <field> = ..." -> "options[k].rule.<field> = ..."
+            const std::string msg = g_err;
+            const size_t at = msg.find(": ");
+            set_error("options[%d].rule.%s", k, at == std::string::npos ? msg.c_str() : msg.c_str() + at + 2);
+            return MCR_ERR_INVALID_ARG;
+        }
+    }
+    if (n_paths > (uint64_t)INT32_MAX * kBlock) { set_error("n_paths too large for one launch"); return MCR_ERR_INVALID_ARG; }
+    if (path_begin + n_paths < path_begin) { set_error("path range overflows 64 bits"); return MCR_ERR_INVALID_ARG; }
+    if (rng->kind == MCR_RNG_NUMPY) { set_error("rule probe: the NumPy stream is not supported (the engine's own stream only)"); return MCR_ERR_UNSUPPORTED; }
+    if (rng->kind == MCR_RNG_HISTORY) { set_error("rule probe: the history stream is not supported (the engine's own stream only)"); return MCR_ERR_UNSUPPORTED; }
+    if (p->n_streams > MCR_INLINE_STREAMS && d.n_extra_streams > 0) {
+        set_error("rule probe: %d income streams need the generic variant (at most %d are supported)", (int)p->n_streams, MCR_INLINE_STREAMS);
+        return MCR_ERR_UNSUPPORTED;
+    }
+    if (needs_generic_variant(d)) { set_error("rule probe: the exact month (a realized-gains rate above 1 - 1e-6) needs the generic variant, which is not supported"); return MCR_ERR_UNSUPPORTED; }
+    size_t lds = 0;
+    rc = plan_path_kernel_lds(d, summary ? 1 : 0, MCR_RNG_PHILOX, false, false, 0, &lds);
+    if (rc != MCR_OK) return rc;
+    if (d.n_lock_slots < d.n_lock_slots_total) {
+        set_error("rule probe: %d frozen income streams exceed the LDS budget and need the generic variant, which is not supported", (int)d.n_lock_slots_total);
+        return MCR_ERR_UNSUPPORTED;
+    }
+    return MCR_OK;
+}
+
+// mcr_probe_rules_rng (jo == nullptr, rows == nullptr), mcr_probe_rules_joint_rng and mcr_probe_rules_outcomes_rng, on the entered
+// device, their arguments checked (check_rule_probe)
+static int probe_rules(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                       int32_t working_months, const mcr_rule_option* options, int32_t n_options, uint64_t* counts, uint64_t* year_counts,
+                       const JointOut* jo, const mcr_option_outcomes* rows, int device, hipStream_t main) {
+    if (n_options == 0) return MCR_OK;
+    int rc = zero_counters(counts, (size_t)n_options, main);
+    if (rc != MCR_OK) return rc;
+    const size_t year_block = (size_t)p->retirement_years * MCR_RULE_N_COUNTS;   // one option's year counts
+    if (year_counts) {
+        const hipError_t e = hipMemsetAsync(year_counts, 0, sizeof(uint64_t) * year_block * (size_t)n_options, main);
+        if (e != hipSuccess) return hip_fail(e, "rule probe year counts memset");
+    }
+    mcr_params q = *p;
+    auto launch_option = [&](int k, hipStream_t s, uint8_t* success, double* final_balance, double* years_to_ruin) {
+        const mcr_rule_option& r = options[k];
+        q.initial_balance = r.initial_balance; q.monthly_contribution = r.monthly_contribution; q.monthly_expenses = r.monthly_expenses;
+        const mcr_outputs o = counters_and_columns(counts + (size_t)k * MCR_N_COUNTERS, success, final_balance, years_to_ruin);
+        const mcr_rule_outputs ro{year_counts ? year_counts + (size_t)k * year_block : nullptr, nullptr, 0};
+        return launch_rule(&q, rng, stream_id, path_begin, n_paths, working_months, &r.rule, &o, &ro, s);
+    };
+    auto fanout = [&](uint64_t* masks, const mcr_option_outcomes* fan_rows) {
+        return probe_rules_fanout(p, rng, stream_id, path_begin, n_paths, working_months, options, n_options, counts, year_counts, main, masks, fan_rows);
+    };
+    return run_probe_routes(device, main, n_options, n_paths, jo, rows, fanout, launch_option);
+}
+
+int mcr_probe_rules_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                        uint64_t n_paths, int32_t working_months, const mcr_rule_option* options, int32_t n_options,
+                        uint64_t* counts, uint64_t* year_counts, int device, void* hip_stream) {
+    g_last_rule_fanout_launches = 0;
+    if (int rc = check_rule_probe(p, rng, path_begin, n_paths, working_months, options, n_options, counts, false)) return rc;
+    MCR_ENTER_DEVICE(device);
+    return probe_rules(p, rng, stream_id, path_begin, n_paths, working_months, options, n_options, counts, year_counts, nullptr, nullptr, device,
+                       (hipStream_t)hip_stream);
+}
+
+int mcr_probe_rules_joint_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                              uint64_t n_paths, int32_t working_months, const mcr_rule_option* options, int32_t n_options,
+                              uint64_t* counts, uint64_t* year_counts, uint64_t* masks, uint64_t* joint, uint64_t* extremes,
+                              int device, void* hip_stream) {
+    g_last_rule_fanout_launches = 0;
+    if (int rc = check_joint_args(n_options, joint)) return rc;
+    if (int rc = check_rule_probe(p, rng, path_begin, n_paths, working_months, options, n_options, counts, true)) return rc;
+    MCR_ENTER_DEVICE(device);
+    const JointOut jo{masks, joint, extremes};
+    return probe_rules(p, rng, stream_id, path_begin, n_paths, working_months, options, n_options, counts, year_counts, &jo, nullptr, device,
+                       (hipStream_t)hip_stream);
+}
+
+int mcr_probe_rules_outcomes_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                 uint64_t n_paths, int32_t working_months, const mcr_rule_option* options, int32_t n_options,
+                                 uint64_t* counts, uint64_t* year_counts, const mcr_option_outcomes* rows,
+                                 int device, void* hip_stream) {
+    g_last_rule_fanout_launches = 0;
+    if (int rc = check_outcome_args(&rows, n_paths)) return rc;
+    if (int rc = check_rule_probe(p, rng, path_begin, n_paths, working_months, options, n_options, counts, rows != nullptr)) return rc;
+    MCR_ENTER_DEVICE(device);
+    return probe_rules(p, rng, stream_id, path_begin, n_paths, working_months, options, n_options, counts, year_counts, nullptr, rows, device,
+                       (hipStream_t)hip_stream);
+}
+
+int mcr_probe_rules_last_fanout_launches(void) { return g_last_rule_fanout_launches; }
 
 int mcr_probe_grid_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
                        uint64_t n_paths, const int32_t* working_months, int32_t n_candidates,

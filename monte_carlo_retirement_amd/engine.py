@@ -653,13 +653,13 @@ def _assumption_records(records):
 
 
 def _probe_records(symbol: str, params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
-                   record_args, n: int, device: int, joint: bool = False, masks=True, outcomes=None):
+                   record_args, n: int, device: int, joint: bool = False, masks=True, outcomes=None, after_counts=()):
     """The body of the record probes: `symbol` is the library entry, `record_args` what it takes between `working_months` and
     the record count.  Plain: returns `counts`.  `joint`: the ``*_joint_rng`` entry; returns ``(counts, joint, extremes,
     masks)`` (`masks` falsy: the library keeps them in scratch of its own and None is returned in their place).  `outcomes`:
     the ``*_outcomes_rng`` entry; ``(final_balance, years_to_ruin, path_stride)`` with each row argument True (allocate),
     falsy (not requested) or a float64 device tensor ``[n, path_stride]`` to write into; returns ``(counts, final_rows,
-    ruin_rows)``."""
+    ruin_rows)``.  `after_counts`: what the entry takes right behind `counts` (the rule probes' year counts)."""
     import torch
 
     N.require_device()
@@ -697,7 +697,7 @@ def _probe_records(symbol: str, params: McrParams, seed, stream_id: int, path_be
         stream = torch.cuda.current_stream(int(device)).cuda_stream
         rc = getattr(N.load_library(), symbol)(
             C.byref(params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), int(working_months), *record_args,
-            n, counts.data_ptr(), *outs, int(device), C.c_void_p(stream),
+            n, counts.data_ptr(), *after_counts, *outs, int(device), C.c_void_p(stream),
         )
         N.check(rc, symbol)
     if outcomes is not None:
@@ -808,6 +808,64 @@ def probe_assumptions_outcomes(params: McrParams, seed, stream_id: int, path_beg
     arr, n = _assumption_records(records)
     return _probe_records("mcr_probe_assumptions_outcomes_rng", params, seed, stream_id, path_begin, n_paths, working_months, (arr,), n,
                           device, outcomes=(final_balance, years_to_ruin, path_stride))
+
+
+def _rule_option_records(options):
+    """`options`: ``(initial_balance, monthly_contribution, monthly_expenses, rule)`` 4-tuples, `rule` a
+    `spending_rules.SpendingRule`, a ready ``McrSpendingRule`` or None (the neutral rule: fixed spending)."""
+    records = []
+    for o in options:
+        o = tuple(o)
+        if len(o) != 4:
+            raise ValueError("every option is (initial_balance, monthly_contribution, monthly_expenses, rule)")
+        rule = N.McrSpendingRule(1.0, 1.0, 0.0, 0.0, 1.0, 1.0) if o[3] is None else _rule_record(o[3])
+        records.append(N.McrRuleOption(float(o[0]), float(o[1]), float(o[2]), rule))
+    return (N.McrRuleOption * max(1, len(records)))(*records), len(records)
+
+
+def _probe_rules(symbol: str, params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
+                 options, device: int, year_counts: bool, **kw):
+    import torch
+
+    arr, n = _rule_option_records(options)
+    yc = None
+    if year_counts:
+        N.require_device()
+        ry = int(query_sizes(params, working_months).retirement_years)
+        alloc = torch.empty if n else torch.zeros       # (the call zeroes it; no options: no call)
+        yc = alloc((n, ry, N.MCR_RULE_N_COUNTS), dtype=torch.int64, device=torch.device("cuda", int(device)))
+    res = _probe_records(symbol, params, seed, stream_id, path_begin, n_paths, working_months, (arr,), n, device,
+                         after_counts=(yc.data_ptr() if yc is not None and yc.numel() else None,), **kw)
+    return (res, yc) if torch.is_tensor(res) else (res[0], yc) + tuple(res[1:])
+
+
+def probe_rules(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int, options,
+                device: int = 0, year_counts: bool = True):
+    """Success counters and year counts of several spending rules (and versions of the three scenario fields) at one
+    working-month count over the same path range (``mcr_probe_rules_rng``).  ``options`` is a sequence of ``(initial_balance,
+    monthly_contribution, monthly_expenses, rule)`` 4-tuples, `rule` a `spending_rules.SpendingRule` or None (fixed spending);
+    option k counts exactly what a count-only `run_rule` with those three fields of `params` replaced counts under its rule.
+    Up to ``MCR_MAX_EXPENSE_FANOUT`` options share each path's random numbers.  Returns device int64 tensors ``(counts,
+    year_counts)``: ``[len(options), 2]`` = ``{successes, paths}`` and ``[len(options), ry, MCR_RULE_N_COUNTS]`` (None with
+    ``year_counts=False``); asynchronous (reading a tensor synchronises)."""
+    return _probe_rules("mcr_probe_rules_rng", params, seed, stream_id, path_begin, n_paths, working_months, options, device, year_counts)
+
+
+def probe_rules_joint(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int, options,
+                      device: int = 0, masks=True, year_counts: bool = True):
+    """`probe_rules` plus the joint outcomes of its options (``mcr_probe_rules_joint_rng``); returns ``(counts, year_counts,
+    joint, extremes, masks)``, the last three as `probe_scenarios_joint`."""
+    return _probe_rules("mcr_probe_rules_joint_rng", params, seed, stream_id, path_begin, n_paths, working_months, options, device,
+                        year_counts, joint=True, masks=masks)
+
+
+def probe_rules_outcomes(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int, options,
+                         device: int = 0, final_balance=True, years_to_ruin=True, path_stride: Optional[int] = None,
+                         year_counts: bool = True):
+    """`probe_rules` plus the per-path outcomes of its options (``mcr_probe_rules_outcomes_rng``); returns ``(counts,
+    year_counts, final_rows, ruin_rows)``, the last two as `probe_scenarios_outcomes`."""
+    return _probe_rules("mcr_probe_rules_outcomes_rng", params, seed, stream_id, path_begin, n_paths, working_months, options, device,
+                        year_counts, outcomes=(final_balance, years_to_ruin, path_stride))
 
 
 def ruin_month_counts(ruin_rows, n_paths: int, retirement_years: int, into=None, device: Optional[int] = None):

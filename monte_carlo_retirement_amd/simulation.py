@@ -981,11 +981,17 @@ class RetirementMonteCarloSimulator:
         """Success % at ``working_months`` when spending follows `rule` (a `spending_rules.SpendingRule`), over the active
         seed stream's batch of ``num_simulations`` paths (default ``num_simulations_main``).  ``monthly_expenses``: None (the
         config's own level; returns a float), one level (a float) or a sequence of levels (an array aligned with it): the
-        spending the path STARTS with.  One launch per level (``mcr_run_rule_rng``), as the history stream's probes run.
-        Under the neutral rule each value equals `success_probability_by_expenses` at the same level, bit for bit."""
+        spending the path STARTS with.  One level is one launch (``mcr_run_rule_rng``); two or more go through the rule
+        probe (``mcr_probe_rules_rng``), up to ``MCR_MAX_EXPENSE_FANOUT`` of them sharing each path's random numbers, and
+        count the same integers.  Under the neutral rule each value equals `success_probability_by_expenses` at the same
+        level, bit for bit."""
         n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
         scalar = monthly_expenses is None or np.ndim(monthly_expenses) == 0
         levels = [None] if monthly_expenses is None else [float(x) for x in np.atleast_1d(np.asarray(monthly_expenses, dtype=np.float64))]
+        if len(levels) >= 2:
+            p = self.params_model
+            counts = self._rule_probe_counts(working_months, [(p.initial_balance, p.monthly_contribution, x, rule) for x in levels], n)
+            return np.array([self._count_percent(c[N.MCR_CTR_SUCCESS], n) for c in counts], dtype=np.float64)
         out = []
         for level in levels:
             params = params_from_config(self.params_model)     # (a block of this call's own: the level goes into it)
@@ -1046,6 +1052,114 @@ class RetirementMonteCarloSimulator:
                 logger.info(f"  Rule expense search complete: {expenses:.2f} per month to begin with, prob {prob:.2f}% "
                             f"({len(curve)} levels evaluated).")
         return expenses, prob, curve
+
+    # ---- spending rules compared on shared paths ----------------------------------------------------
+    def _rule_probe_counts(self, working_months: int, records, n: int) -> np.ndarray:
+        """``[len(records), 2 + 4 ry]`` integers of the rule probe (``mcr_probe_rules_rng``) over the active stream's batch
+        of ``n`` paths: per record of `spending_rules.rule_options` its two counters and its year counts, row-major.  The
+        records go through ``distributed.probe_candidates`` as candidate indices; every rank returns the same array."""
+        import torch
+
+        wm, ry = int(working_months), int(self.params_model.retirement_years)
+        width = N.MCR_N_COUNTERS + N.MCR_RULE_N_COUNTS * ry
+        if not records:
+            return np.zeros((0, width), dtype=np.int64)
+        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
+
+        def probe(path_begin, count, idx):
+            counts, years = E.probe_rules(params, rng, self._stream_id, path_begin, count, wm, [records[i] for i in idx], device=dev)
+            return torch.cat([counts, years.reshape(len(idx), -1)], dim=1)
+
+        return D.probe_candidates(list(range(len(records))), n, self.shard_min_paths, probe, width=width)
+
+    def success_probability_by_rules(self, working_months: int, options: Sequence[dict],
+                                     num_simulations: Optional[int] = None) -> np.ndarray:
+        """Success % of each spending-rule option at ``working_months``, over the active seed stream's batch of
+        ``num_simulations`` paths (default ``num_simulations_main``), from the rule probe (``mcr_probe_rules_rng``).  An
+        option is a mapping ``{"rule": SpendingRule | six numbers | None, "initial_balance"?, "monthly_contribution"?,
+        "monthly_expenses"?}`` (`spending_rules.rule_options`): None is fixed spending, a missing amount takes the config's
+        value, an unknown key raises ``ValueError`` (before any device work).  Aligned with the input; each value equals,
+        bit for bit, `success_probability_with_rule` of a simulator whose config differs in those amounts only.  Under a
+        process group the options go through ``distributed.probe_candidates`` (as candidate indices), so every rank returns
+        the same array."""
+        from .spending_rules import rule_options
+
+        n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
+        counts = self._rule_probe_counts(working_months, rule_options(self.params_model, options), n)
+        return np.array([self._count_percent(c[N.MCR_CTR_SUCCESS], n) for c in counts], dtype=np.float64)
+
+    def joint_outcomes_by_rules(self, working_months: int, options: Sequence[dict], num_simulations: Optional[int] = None):
+        """The joint outcomes of the options of `success_probability_by_rules` (same arguments) over their shared paths,
+        from the joint rule probe (``mcr_probe_rules_joint_rng``): a `paired.JointOutcomes` whose ``.probabilities`` equal
+        that method's array bit for bit.  At most ``MCR_MAX_JOINT_OPTIONS`` options."""
+        from .spending_rules import rule_options
+
+        records = rule_options(self.params_model, options)
+        n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
+        wm = int(working_months)
+        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
+
+        def probe(path_begin, count):
+            counts, _, joint, extremes, masks = E.probe_rules_joint(params, rng, self._stream_id, path_begin, count, wm, records,
+                                                                    device=dev, masks=None, year_counts=False)
+            return counts, joint, extremes, masks
+
+        return self._joint_outcomes(probe, len(records), n)
+
+    def option_outcomes_by_rules(self, working_months: int, options: Sequence[dict], num_simulations: Optional[int] = None,
+                                 quantiles: Sequence[float] = (0.05, 0.25, 0.5, 0.75, 0.95)):
+        """The per-option outcomes of the options of `success_probability_by_rules` (same arguments and validation) over
+        their shared paths, from the rule outcomes probe (``mcr_probe_rules_outcomes_rng``): an `outcomes.OptionOutcomes`
+        whose ``.probabilities`` equal that method's array bit for bit."""
+        from .spending_rules import rule_options
+
+        records = rule_options(self.params_model, options)
+        n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
+        wm = int(working_months)
+        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
+
+        def probe(path_begin, count):
+            counts, _, final_rows, ruin_rows = E.probe_rules_outcomes(params, rng, self._stream_id, path_begin, count, wm, records,
+                                                                      device=dev, year_counts=False)
+            return counts, final_rows, ruin_rows
+
+        return self._option_outcomes(probe, len(records), wm, n, quantiles)
+
+    def compare_spending_rules(self, working_months: int, options: Sequence[dict], num_simulations: Optional[int] = None,
+                               paired: bool = False, outcomes: bool = False) -> dict:
+        """Which guardrail to choose: the options of `success_probability_by_rules` over the same paths as ``{"options":
+        [{"initial_balance", "monthly_contribution", "monthly_expenses", "rule": `SpendingRule.as_dict` or None,
+        "probability", "years": `SpendingRuleOutcomes.years` of the option}, ...], "best": index}``, ``best`` being the option
+        with the highest probability (the first of equals).  ``paired=True`` adds ``"vs_best"`` to every row and
+        ``"tied_with_best"``, ``"all_succeed"`` and ``"none_succeed"`` to the document (`joint_outcomes_by_rules`);
+        ``outcomes=True`` adds ``"lasts_until_age"``, ``"median_ruin_age"`` and ``"final_balance"`` to every row
+        (`option_outcomes_by_rules`) -- both exactly as `compare_claiming_options` adds them, and they compose."""
+        from .nestegg import SCENARIO_FIELDS
+        from .spending_rules import SpendingRuleOutcomes, rule_options
+
+        records = rule_options(self.params_model, options)
+        n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
+        ry = int(self.params_model.retirement_years)
+        age = retirement_age(self.params_model.current_age, int(working_months))
+        counts = self._rule_probe_counts(working_months, records, n)
+        rows = []
+        for r, c in zip(records, counts):
+            o = SpendingRuleOutcomes(int(c[N.MCR_CTR_SUCCESS]), n, c[N.MCR_N_COUNTERS:].reshape(ry, N.MCR_RULE_N_COUNTS), age)
+            rows.append(dict(zip(SCENARIO_FIELDS, r[:3]), rule=None if r[3] is None else r[3].as_dict(),
+                             probability=self._count_percent(c[N.MCR_CTR_SUCCESS], n), years=o.years()))
+        best = max(range(len(rows)), key=lambda i: (rows[i]["probability"], -i)) if rows else None
+        doc = {"options": rows, "best": best}
+        if paired:
+            joint = self.joint_outcomes_by_rules(working_months, options, num_simulations)
+            for i, row in enumerate(rows):
+                row["vs_best"] = joint.difference(best, i)
+            doc["tied_with_best"] = joint.indistinguishable_from(best) if rows else []
+            doc["all_succeed"], doc["none_succeed"] = joint.all_succeed, joint.none_succeed
+        if outcomes:
+            per_option = self.option_outcomes_by_rules(working_months, options, num_simulations)
+            for i, row in enumerate(rows):
+                row.update(per_option.row(i))
+        return doc
 
     # ---- minimum-contribution search ---------------------------------------------------------------
     def success_probability_by_contributions(self, working_months: int, monthly_contributions: Sequence[float],

@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
@@ -69,6 +69,30 @@ class SpendingRule:
     def as_dict(self) -> Dict[str, float]:
         return {"upper": self.upper, "lower": self.lower, "cut": self.cut, "raise": self.raise_, "floor": self.floor,
                 "ceiling": self.ceiling}
+
+
+RULE_OPTION_AMOUNTS = ("initial_balance", "monthly_contribution", "monthly_expenses")
+
+
+def rule_options(params_model, options: Sequence[dict]) -> List[tuple]:
+    """The records of a rule probe (``engine.probe_rules``): ``(initial_balance, monthly_contribution, monthly_expenses, rule)``
+    per mapping of ``options``.  ``"rule"`` is a `SpendingRule`, six numbers in its field order, or None / missing: the neutral
+    rule, i.e. fixed spending (None in the record).  A missing amount takes the value of ``params_model`` (the config), an
+    unknown key raises ``ValueError``; so does a rule outside its ranges, naming ``options[k].rule`` and the field."""
+    defaults = tuple(float(getattr(params_model, f)) for f in RULE_OPTION_AMOUNTS)
+    records = []
+    for k, o in enumerate(options):
+        unknown = sorted(set(o) - set(RULE_OPTION_AMOUNTS) - {"rule"})
+        if unknown:
+            raise ValueError(f"options[{k}]: unknown key(s) {unknown}; a rule option may set {['rule', *RULE_OPTION_AMOUNTS]}")
+        rule = o.get("rule")
+        if rule is not None and not isinstance(rule, SpendingRule):
+            try:
+                rule = SpendingRule(*[float(x) for x in rule])
+            except (TypeError, ValueError) as exc:
+                raise ValueError(f"options[{k}].rule: {exc}") from None
+        records.append(tuple(float(o.get(f, d)) for f, d in zip(RULE_OPTION_AMOUNTS, defaults)) + (rule,))
+    return records
 
 
 class SpendingRuleOutcomes:
