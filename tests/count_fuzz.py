@@ -20,6 +20,9 @@ Every plan also has a NumPy leg (`numpy_leg`, `numpy_shocks`, `oracle_run_numpy`
 reference's own random stream, its shocks drawn by NumPy and injected into the oracle, for the rng="numpy" kernels; and
 `numpy_extra` adds the one variant family of that stream the classes leave out.  The classes' plans do not depend on it.
 
+The SCREENED family (`screened_scenarios`, at the end of the file) is drawn for the one count-only route the classes' plans do
+not reach, the fp32 screening kernel and its fp64 re-run; it has generators of its own, and no other plan depends on it.
+
 MCR_COUNT_FUZZ_SEED: other plans (soaks by hand); the default is the suite's.  Everything is deterministic in it, class by
 class: a class's plans do not depend on which other classes were generated before."""
 
@@ -211,13 +214,14 @@ def failure_share(run) -> float:
     return 1.0 - float(run["counters"][0]) / float(run["counters"][1])
 
 
-def _calibrate(O, scn: Scenario) -> float:
+def _calibrate(O, scn: Scenario, target: float = 0.5) -> float:
+    """Expenses at which about `target` of the paths fail (CAL_STEPS bisection steps at CAL_PATHS paths)."""
     lo, hi = math.log(CAL_LO), math.log(CAL_HI)
     for _ in range(CAL_STEPS):
         mid = 0.5 * (lo + hi)
         c = O.run_batch(scn.params(monthly_expenses=math.exp(mid)), scn.seed, scn.stream, scn.begin, CAL_PATHS, scn.wm, want_trajectories=False)
-        if 2 * int(c["counters"][0]) < CAL_PATHS:
-            hi = mid        # more than half fail: spend less
+        if CAL_PATHS - int(c["counters"][0]) > target * CAL_PATHS:
+            hi = mid        # more than the target share fail: spend less
         else:
             lo = mid
     return round(math.exp(0.5 * (lo + hi)), 2)
@@ -232,19 +236,22 @@ STATS = {}          # class -> {"drawn", "kept", "dropped_scale", "redrawn_unmix
 _KEPT = {}
 
 
-def _generate(O, cls: str, count: int, sliced_n=None, rng=None, draw=_draw, run_of=None):
-    """`rng`, `draw`, `run_of`: the generator, the draw and the run a plan is judged by, for plans outside CLASSES (numpy_extra)."""
+def _generate(O, cls: str, count: int, sliced_n=None, rng=None, draw=_draw, run_of=None, paths=PATHS, refuse=None):
+    """`rng`, `draw`, `run_of`: the generator, the draw and the run a plan is judged by, for plans outside CLASSES (numpy_extra).
+    `paths`: the path counts of even / odd indices.  `refuse(scn)`: a further condition on a plan below the money scale, judged
+    after its calibration; it returns None, or the name of the STATS counter the plan is redrawn under (never kept)."""
     if rng is None:
         rng = np.random.default_rng([seed(), CLASSES.index(cls), 0 if sliced_n is None else 1])
     if run_of is None:
         run_of = lambda scn: oracle_run(O, scn, n=None if sliced_n is None else SAMPLE, trajectories=True)  # noqa: E731
     stats = {"drawn": 0, "kept": 0, "dropped_scale": 0, "redrawn_unmixed": 0, "kept_unmixed": 0}
     kept = []
+    n_of = lambda i: paths[i % 2] if sliced_n is None else sliced_n  # noqa: E731
     while len(kept) < count:
         i = len(kept)
         fallback = None
         for _ in range(MAX_ATTEMPTS):
-            scn = draw(cls, rng, i, PATHS[i % 2] if sliced_n is None else sliced_n)
+            scn = draw(cls, rng, i, n_of(i))
             while sliced_n is not None and not _fits_a_sliced_launch(scn):
                 scn = draw(cls, rng, i, sliced_n)
             stats["drawn"] += 1
@@ -254,6 +261,10 @@ def _generate(O, cls: str, count: int, sliced_n=None, rng=None, draw=_draw, run_
             run = run_of(scn)
             if money_scale(run) >= SCALE_LIMIT:
                 stats["dropped_scale"] += 1
+                continue
+            why = refuse(scn) if refuse is not None else None
+            if why is not None:
+                stats[why] = stats.get(why, 0) + 1
                 continue
             fallback = scn
             if MIXED[0] <= failure_share(run) <= MIXED[1]:
@@ -370,3 +381,156 @@ def numpy_extra(O):
 def numpy_plans(O, cls: str):
     """The plans of `cls` on the NumPy stream: a class of CLASSES, or EXTRA."""
     return numpy_extra(O) if cls == EXTRA else scenarios(O, cls)
+
+
+# ---- the SCREENED family: plans a count-only launch screens in fp32 (csrc/mcr_screen.h) ---------------------------------------
+# The classes' plans rarely qualify for the screened route (half their income records are frozen-nominal), and the tests that
+# run them address the classic kernels.  These plans are drawn for that route: `_draw` of one of five tax BASES supplies the
+# market (rho strata, volatilities outside the narrow exp window, the last rate below the exact month), the months, the seed
+# and the path range (2^32 - 100 and 2^40 among them); the income records, the allocation and the initial balance are drawn
+# here, as strata of the plan's index within its base:
+#
+#     index % 3:       0, 1 or 2 paying, inflation-indexed income records (SCREENED_FEATURES: what their draw must reach)
+#     index odd:       a record that pays nothing, frozen-nominal allowed, at a random list position (the kernel is not given it)
+#     index % 4 == 3:  an EDGE plan: allocation 0, allocation 1 or initial balance 0 in turn: every path is DOUBTFUL by
+#                      construction (a balance at or below one dollar), so the fp64 re-run gets the whole, ragged range
+#     otherwise:       INTERIOR: allocation uniform in (0.05, 0.95), initial balance log-uniform in [1e3, 1e6]
+#     index even:      15-40 retirement years (odd: `_draw`'s 4-40; the short ones have few SAFE paths, or none)
+#
+# Each plan has two expense LEVELS, calibrated with the oracle alone: "half" (half the paths fail: a long list of doubtful
+# paths) and "comfortable" (5 % fail: most paths SAFE, a short list).  A plan is dropped for its money scale and redrawn for
+# all-or-nothing outcomes as the classes' plans are, both judged at the "half" level; it is also redrawn unless it takes the
+# screened route at a million paths with no knob set, and unless its tolerance (`screen_reference`) is at most SCREENED_TOL_MAX
+# at both levels.  A generator of its own per base: no plan of CLASSES or of numpy_extra moves.
+SCREENED_BASES = ("equal_rates", "unequal_rates", "mask1", "mask2", "mask0")
+SCREENED_KEPT = 8
+SCREENED_PATHS = (1025, 705)            # even / odd index: four screening workgroups and one lane; two, three wavefronts and one lane
+SCREENED_LEVELS = {"half": 0.5, "comfortable": 0.05}
+SCREENED_EDGES = ("allocation 0", "allocation 1", "initial balance 0")
+SCREENED_FEATURES = ("starts before retirement", "duration 0", "no duration", "tax rate 1")
+SCREENED_TOL_FLOOR, SCREENED_TOL_FACTOR, SCREENED_TOL_MAX = 2e-4, 8.0, 1e-2
+SCREEN_KNOBS = ("MCR_K1_SCREEN", "MCR_K1_SCREEN_MIN_PATHS", "MCR_K1_SCREEN_EXPECTED", "MCR_K1_RERUN_PRODUCERS", "MCR_K1_SPLIT_MAX_WAVES",
+                "MCR_K1_SEGMENTS", "MCR_K1_SEGMENTS_ALWAYS", "MCR_K1_SEGMENT_POLLS", "MCR_K1_SEGMENT_ORDER", "MCR_K1_GROWTH_FORM",
+                "MCR_K1_MONTH_FORM", "MCR_K1_STREAM_FORM")
+
+
+def screened_class(base: str) -> str:
+    return f"screened-{base}"
+
+
+def screened_edge(scn: Scenario):
+    """The edge of an edge plan (one of SCREENED_EDGES), None for an interior plan."""
+    if scn.index % 4 != 3:
+        return None
+    return SCREENED_EDGES[(2 * SCREENED_BASES.index(scn.cls[len("screened-"):]) + scn.index // 4) % 3]
+
+
+def screened_features(scn: Scenario):
+    """Which of SCREENED_FEATURES the plan's PAYING income records show."""
+    retirement = scn.cfgd["current_age"] + scn.wm / 12.0
+    out = set()
+    for s in scn.cfgd["other_income_streams"]:
+        if s["monthly_amount_today"] == 0.0:
+            continue
+        out |= {f for f, holds in zip(SCREENED_FEATURES, (s["start_at_age"] < retirement, s["duration_years"] == 0,
+                                                          s["duration_years"] is None, s["tax_rate"] == 1.0)) if holds}
+    return out
+
+
+def _draw_screened(cls, rng, i, n):
+    base = cls[len("screened-"):]
+    scn = _draw(base, rng, i, n)
+    pick = lambda *xs: xs[int(rng.integers(len(xs)))]  # noqa: E731
+    retirement = scn.cfgd["current_age"] + scn.wm / 12.0
+    records = []
+    for s in range(i % 3):
+        rec = {"name": f"s{s}", "monthly_amount_today": float(rng.uniform(50, 4000)),
+               "start_at_age": float(retirement + pick(-rng.uniform(0.1, 10), rng.uniform(0, 25), rng.uniform(0, 10))),
+               "duration_years": pick(None, 0, int(rng.integers(1, 12)), int(rng.integers(1, 12))), "inflation_indexed": True,
+               "tax_rate": float(pick(0.0, 1.0, rng.uniform(0, 0.6), rng.uniform(0, 0.6)))}
+        if s == 0:      # the first record shows one feature for certain, in turn over the base's plans and over the bases
+            forced = SCREENED_FEATURES[(i // 3 + SCREENED_BASES.index(base)) % 4]
+            rec.update({"starts before retirement": {"start_at_age": float(retirement - rng.uniform(0.1, 10))}, "duration 0": {"duration_years": 0},
+                        "no duration": {"duration_years": None}, "tax rate 1": {"tax_rate": 1.0}}[forced])
+        records.append(rec)
+    if i % 2 == 1:
+        records.insert(int(rng.integers(len(records) + 1)),
+                       {"name": "nothing", "monthly_amount_today": 0.0, "start_at_age": float(retirement + rng.uniform(-3, 25)),
+                        "duration_years": pick(None, int(rng.integers(0, 12))), "inflation_indexed": bool(rng.integers(2)),
+                        "tax_rate": float(rng.uniform(0, 0.6))})
+    alloc, balance = float(rng.uniform(0.05, 0.95)), float(math.exp(rng.uniform(math.log(1e3), math.log(1e6))))
+    scn.cls = cls
+    scn.cfgd.update(scenario=f"{cls}-{i}", other_income_streams=records, allocation_inv1_pct=alloc, initial_balance=balance)
+    if i % 2 == 0:      # (a retirement of 4-8 years has no SAFE path at the "half" level: 24 months of need are a large part of it)
+        scn.cfgd["retirement_years"] = int(rng.integers(15, 41))
+    edge = screened_edge(scn)
+    if edge is not None:
+        scn.cfgd.update({"allocation 0": {"allocation_inv1_pct": 0.0}, "allocation 1": {"allocation_inv1_pct": 1.0},
+                         "initial balance 0": {"initial_balance": 0.0}}[edge])
+    return scn
+
+
+def at_level(scn: Scenario, level: str) -> Scenario:
+    """The plan at one of its two expense levels (a copy: `scn` itself stands at "half")."""
+    out = Scenario(scn.cls, scn.index, dict(scn.cfgd, monthly_expenses=scn.levels[level]), scn.wm, scn.seed, scn.stream, scn.begin, scn.n)
+    out.levels = scn.levels
+    return out
+
+
+_SCREEN_REFERENCES = {}
+
+
+def screen_reference(scn: Scenario, level: str):
+    """The reference of plan `scn` at `level` (tests/screen_model.py: the screening kernel's loop in plain NumPy), cached:
+    `fp64` and `fp32`, the model's run in either precision; `dev`, the largest relative deviation of the fp32 run from the fp64
+    one over `min_ratio` and `final_total` of the paths SAFE in both (0.0 without such a path); and the plan's tolerance
+    `tol` = max(SCREENED_TOL_FLOOR, SCREENED_TOL_FACTOR dev), measured from the reference and never from the kernel.  The
+    factor: NumPy's single-precision exp and log are within an ulp, while the kernel adds about 1e-6 absolute on each normal
+    (csrc/mcr_screen.h) and a few ulp on each hardware exp, log and reciprocal."""
+    import screen_model
+
+    key = (scn.cls, scn.index, scn.seed, scn.begin, scn.n, scn.wm, scn.levels[level])
+    if key not in _SCREEN_REFERENCES:
+        s = at_level(scn, level)
+        fp64, fp32 = (screen_model.model(s.params(), s.cfgd, s.wm, s.seed, s.stream, s.begin, s.n, dtype=t) for t in (np.float64, np.float32))
+        both = fp64["safe"] & fp32["safe"]
+        dev = 0.0
+        for k in ("min_ratio", "final_total"):
+            a, b = fp64[k][both], fp32[k][both].astype(np.float64)
+            finite = np.isfinite(a)
+            if not np.array_equal(finite, np.isfinite(b)):      # (a month has a need in one precision only: no tolerance covers that)
+                dev = math.inf
+            elif finite.any():
+                dev = max(dev, float(np.abs(b[finite] / a[finite] - 1.0).max()))
+        _SCREEN_REFERENCES[key] = {"fp64": fp64, "fp32": fp32, "dev": dev, "tol": max(SCREENED_TOL_FLOOR, SCREENED_TOL_FACTOR * dev)}
+    return _SCREEN_REFERENCES[key]
+
+
+def _takes_the_screened_route(scn: Scenario) -> bool:
+    from monte_carlo_retirement_amd import engine as E
+
+    old = {k: os.environ.pop(k, None) for k in SCREEN_KNOBS}
+    try:
+        return E.screen(scn.params(), scn.wm, 10 ** 6)
+    finally:
+        os.environ.update({k: v for k, v in old.items() if v is not None})
+
+
+def screened_scenarios(O, base: str):
+    """The SCREENED_KEPT kept plans of base `base` (one of SCREENED_BASES), generated once: each stands at its "half" level,
+    and `scn.levels` holds both.  STATS[screened_class(base)] says what it took."""
+    cls = screened_class(base)
+    if cls not in _KEPT:
+        def refuse(scn):
+            if not _takes_the_screened_route(scn):
+                return "redrawn_unqualified"
+            scn.levels = {"half": scn.cfgd["monthly_expenses"], "comfortable": _calibrate(O, scn, SCREENED_LEVELS["comfortable"])}
+            if max(screen_reference(scn, level)["tol"] for level in SCREENED_LEVELS) > SCREENED_TOL_MAX:
+                return "redrawn_tolerance"
+            return None
+
+        _KEPT[cls], STATS[cls] = _generate(O, cls, SCREENED_KEPT, rng=np.random.default_rng([seed(), len(CLASSES) + 1, SCREENED_BASES.index(base)]),
+                                           draw=_draw_screened, paths=SCREENED_PATHS, refuse=refuse)
+        for k in ("redrawn_unqualified", "redrawn_tolerance"):
+            STATS[cls].setdefault(k, 0)
+    return _KEPT[cls]

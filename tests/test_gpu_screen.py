@@ -8,7 +8,11 @@ bit, and equal to the CPU oracle's.
 Classification: the screening kernel alone (mcr_screen_paths_rng) over 4096 paths of three plans.  (a) every path it calls
 SAFE succeeds in the oracle with no ruin year; (b) its fp32 final total is within 1e-2 of the oracle's final balance (the design
 tolerates 0.95, a factor of 24 on the capacity; the expected deviation is about 1e-5); (c) it calls at most 8 % of config.json's
-paths doubtful, so the test cannot pass on an empty SAFE set.  Observed on MI355X (LABNOTES R24): see the table there."""
+paths doubtful, so the test cannot pass on an empty SAFE set.  Observed on MI355X (LABNOTES R24): see the table there.
+
+Plans with income records and random markets (20-60 % volatility, rho = +-1, rates near 1, contribution growth, odd month
+counts), and the kernel's per-path `min_ratio` and `final_total` held to an fp64 restatement of its month rather than to the
+oracle's final balance alone: tests/test_gpu_screen_vs_oracle.py."""
 
 from __future__ import annotations
 
