@@ -23,6 +23,7 @@ switch to the final seed stream, run the final batch, print the response documen
     python examples/run_scenario.py scenarios/config.json --history record.csv --history-scheme cohorts \
         --history-first-month 1926-01 --working-months 240 --cohorts
     python examples/run_scenario.py scenarios/config.json --working-months 240 --spending-rule 1.2,0.8,0.1,0.1,0.5,1.5 [--max-expenses]
+    python examples/run_scenario.py scenarios/config.json --working-months 240 --spending-rule 1.2,0.8,0.1,0.1,0.5,1.5 --streamed
 
 `--rng numpy` uses the reference's own NumPy stream (same seed -> the reference's numbers); `--rng philox`
 (default) the engine's counter-based stream.  `--history FILE.csv` asks every question of a recorded market instead: months
@@ -137,7 +138,9 @@ def main() -> int:
     ap.add_argument("--grid-expenses", default=None, help="comma-separated monthly expenses of that table")
     ap.add_argument("--spending-rule", default=None, metavar="UPPER,LOWER,CUT,RAISE,FLOOR,CEILING",
                     help="a guardrail spending rule: alone, what it does to the plan year by year; with --max-expenses, the "
-                         "maximum spending to begin with under the rule beside the fixed-spending answer (needs --working-months)")
+                         "maximum spending to begin with under the rule beside the fixed-spending answer; with --streamed, the "
+                         "response document under the rule from in-kernel yearly bins: balance and spending fan charts "
+                         "(needs --working-months)")
     ap.add_argument("--compare-rules", default=None, metavar="RULE;RULE;...",
                     help="spending rules compared over the same paths at --working-months: each UPPER,LOWER,CUT,RAISE,FLOOR,CEILING "
                          "or 'none' (fixed spending), separated by ';'; composes with --paired and --outcomes")
@@ -357,6 +360,17 @@ def spending_rule(args, config: Config, world: int, rank0: bool) -> int:
     """What the rule does to the plan at --working-months: success % and, per retirement year, the shares alive / cut / at
     the floor / raised."""
     sim = _simulator(args, config)
+    if args.streamed:    # the whole document from yearly bins under the rule: balance and spending fan charts, no per-path memory
+        sim.use_final_seeds()
+        doc = R.streamed_result(config, sim, int(args.working_months), rule=args.spending_rule)
+        if rank0:
+            print(json.dumps(doc))
+        if world > 1:
+            import torch.distributed as dist
+
+            dist.barrier()
+            dist.destroy_process_group()
+        return 0
     outcomes = sim.spending_rule_outcomes(args.working_months, args.spending_rule)
     out = {"scenario": config.Nickname, "rng": args.rng, "working_months": int(args.working_months),
            "rule": args.spending_rule.as_dict(), **outcomes.row()}

@@ -696,12 +696,46 @@ int mcr_validate_spending_rule(const mcr_spending_rule* rule);
  * MCR_ERR_UNSUPPORTED, with a message that names what was asked and nothing computed, for: trajectory pointers in `out`; the
  * in-kernel histogram (hist_bins); the NumPy and history streams; a parameter block that needs the generic variant (more than
  * MCR_INLINE_STREAMS kept income streams, frozen streams beyond the LDS budget, or the exact month of a realized-gains rate
- * above 1 - 1e-6).  There are no yearly bins, injected shocks, time-sliced, split or screened forms of this launch; several rules
- * over the same paths are mcr_probe_rules_rng's, below.
+ * above 1 - 1e-6).  There are no injected shocks, time-sliced, split or screened forms of this launch; its yearly-bins form, the
+ * fan charts of balance and spending under a rule, is mcr_run_rule_year_bins_rng, and several rules over the same paths are
+ * mcr_probe_rules_rng's, both below.
  */
 int mcr_run_rule_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
                      int32_t working_months, const mcr_spending_rule* rule, mcr_outputs* out, mcr_rule_outputs* rule_out,
                      int device, void* hip_stream);
+
+/*
+ * YEARLY BINS UNDER A SPENDING RULE: mcr_run_year_bins_rng's tables for paths that spend (monthly_expenses * m) * price, the fan
+ * chart of the balance under a guardrail, and with them the rule's own yearly outputs, still with nothing allocated per path:
+ *   year_counts[y]      exactly mcr_run_rule_rng's mcr_rule_outputs.year_counts
+ *   multiplier_bins[y]  <- the multiplier m of every path that BEGINS retirement year y alive (the non-NaN entries of row y of
+ *                          mcr_rule_outputs.multipliers, bit for bit), on the caller's m_edges, in the cell convention of
+ *                          mcr_year_bins (n_m_bins + 2 cells a row): row y sums to year_counts[y][MCR_RULE_ALIVE].  The spending
+ *                          fan chart: monthly_expenses * m is the real monthly spending of the year.
+ * Both are accumulated into like the other tables; either may be NULL.  trajectory_bins, real_trajectory_bins, wr_bins,
+ * final_success_bins, counters, wr_obs_counts and ruin_year_bins mean what they mean in mcr_run_year_bins_rng; under the neutral
+ * rule they equal that launch's cell for cell.  Each multiplier bin costs 16 bytes of a workgroup's LDS, like a withdrawal-rate bin.
+ */
+typedef struct mcr_rule_year_bins {
+    const double* m_edges;  int32_t n_m_bins;   /* [n_m_bins+1] ascending finite, n_m_bins in 1..MCR_MAX_YEAR_BINS; required under multiplier_bins */
+    uint64_t* multiplier_bins;                  /* [ry][n_m_bins+2], accumulated into; NULL = not requested */
+    uint64_t* year_counts;                      /* [ry][MCR_RULE_N_COUNTS], accumulated into; NULL = not requested */
+} mcr_rule_year_bins;
+/* `out` / `yb` as mcr_run_year_bins_rng takes them, `rule` as mcr_validate_spending_rule checks it.  Everything is validated,
+ * on the host and before a device is looked for, before anything is enqueued: on any error every table is untouched.
+ * MCR_ERR_UNSUPPORTED, by name and with nothing computed, for what mcr_run_rule_rng refuses: the NumPy and history streams, the
+ * in-kernel histogram (hist_bins), more than MCR_INLINE_STREAMS kept income streams, frozen streams beyond the LDS budget and the
+ * exact month.  One launch of the generic tax variant, like mcr_run_rule_rng.
+ * mcr_run_rule_year_bins_rng: DEVICE pointers in `out` / `yb` / `rule_yb`, asynchronous on hip_stream (the rule travels in a small
+ * stream-ordered device record, released behind the launch).
+ * mcr_run_rule_year_bins_host_rng: HOST pointers; leases a pooled context on ONE device (a HIP ordinal; there is no multi-device
+ * host form: several GPUs sum their tables with one all-reduce); also checks the three edge arrays finite and ascending. */
+int mcr_run_rule_year_bins_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                               int32_t working_months, const mcr_spending_rule* rule, const mcr_outputs* out, const mcr_year_bins* yb,
+                               const mcr_rule_year_bins* rule_yb, int device, void* hip_stream);
+int mcr_run_rule_year_bins_host_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                                    int32_t working_months, const mcr_spending_rule* rule, const mcr_outputs* out, const mcr_year_bins* yb,
+                                    const mcr_rule_year_bins* rule_yb, int device);
 
 /*
  * Rule options: SEVERAL spending rules (and versions of the scenario probe's three fields) at one working-month count over the

@@ -368,6 +368,17 @@ class McrYearBins(C.Structure):
     ]
 
 
+class McrRuleYearBins(C.Structure):
+    """The rule's tables of a yearly-bins launch under a spending rule (include/mcr.h: mcr_rule_year_bins); addresses like McrOutputs."""
+
+    _fields_ = [
+        ("m_edges", C.c_void_p),
+        ("n_m_bins", C.c_int32),
+        ("multiplier_bins", C.c_void_p),
+        ("year_counts", C.c_void_p),
+    ]
+
+
 #: The symbols include/mcr.h declares; tests check that the built library exports them all.
 ABI_SYMBOLS = (
     "mcr_abi_version",
@@ -412,6 +423,8 @@ ABI_SYMBOLS = (
     "mcr_validate_params",
     "mcr_validate_spending_rule",
     "mcr_run_rule_rng",
+    "mcr_run_rule_year_bins_rng",
+    "mcr_run_rule_year_bins_host_rng",
     "mcr_probe_rules_rng",
     "mcr_probe_rules_joint_rng",
     "mcr_probe_rules_outcomes_rng",
@@ -589,6 +602,13 @@ def _declare(lib: C.CDLL) -> None:
             P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32, P(McrSpendingRule), P(McrOutputs),
             P(McrRuleOutputs), C.c_int, C.c_void_p,
         ]
+    if hasattr(lib, "mcr_run_rule_year_bins_rng"):   # (likewise)
+        head = [P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32, P(McrSpendingRule), P(McrOutputs),
+                P(McrYearBins), P(McrRuleYearBins)]
+        lib.mcr_run_rule_year_bins_rng.restype = C.c_int
+        lib.mcr_run_rule_year_bins_rng.argtypes = head + [C.c_int, C.c_void_p]
+        lib.mcr_run_rule_year_bins_host_rng.restype = C.c_int
+        lib.mcr_run_rule_year_bins_host_rng.argtypes = head + [C.c_int]
     if hasattr(lib, "mcr_probe_rules_rng"):   # (likewise)
         head = [P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32, P(McrRuleOption), C.c_int32,
                 C.c_void_p, C.c_void_p]   # ..., options, n_options, counts, year_counts

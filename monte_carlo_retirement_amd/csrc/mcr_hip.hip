@@ -176,6 +176,17 @@ struct RuleRecord {
     double upper, lower, keep, grow, floor, ceiling;
 };
 static_assert(sizeof(RuleRecord) == 9 * sizeof(double), "RuleRecord is nine packed doubles");
+// MODE 3 with RULE (rule yearly bins, mcr_run_rule_year_bins_rng): a whole-path launch, whose `cand_params` is otherwise null, reads
+// ONE record there: the rule as the year's decision reads it (RuleIO's six values), the year counts, and the multiplier table with
+// its edges.  KernelIO::yb stays where it is: the rule block it overlays does not exist in this launch.  Scalar loads, once.
+struct RuleBinsRecord {
+    double upper, lower, keep, grow, floor, ceiling;
+    unsigned long long* year_counts;      // [ry][MCR_RULE_N_COUNTS] or nullptr, accumulated into
+    unsigned long long* multiplier_bins;  // [ry][n_m_bins + 2] or nullptr, accumulated into
+    const double* m_edges;                // [n_m_bins + 1]
+    int32_t n_m_bins, pad;                // (0: the table is not requested)
+};
+static_assert(sizeof(RuleBinsRecord) == 10 * sizeof(double), "RuleBinsRecord is six packed doubles, three pointers and a count");
 struct AssumptionRecord {
     double initial_balance, monthly_contribution, monthly_expenses;
     double a1, b1, ainf, binf_rho, binf_rho_c, aprem, bprem;
@@ -208,6 +219,13 @@ struct YearBinsLds {
 // terminal partial period writes that row a second time (the row is binned once, after it)
 struct YearBinsState { YearBinsLds L; int k; double last; };
 struct NoYearBins {};
+// ... under a spending rule (RULE): a fourth segment of the row, [trajectory | real | wr | multiplier], with its edges behind the
+// withdrawal-rate ones, and the launch's rule (FanRule, below: the year's decision is rule_year_from's statements)
+struct YearBinsLdsRule : YearBinsLds {
+    double* medges;                      // [mn + 1]
+    unsigned long long* mbins;           // the global table, [ry][mcells], or nullptr
+    int mn, mcells;
+};
 __device__ __forceinline__ YearBinsLds year_bins_lds(const KernelIO::YearBins& yb, unsigned int* after_blk) {
     YearBinsLds L;
     L.n = yb.n_bins; L.wn = yb.n_wr_bins;
@@ -217,6 +235,28 @@ __device__ __forceinline__ YearBinsLds year_bins_lds(const KernelIO::YearBins& y
     L.buf = reinterpret_cast<unsigned int*>(L.wedges + (L.wn + 1));
     L.fin = L.buf + 2 * L.row;
     return L;
+}
+// (the plan by the type of the state's L: the plain form's is the function above, and its code is what it was)
+__device__ __forceinline__ void year_bins_plan(YearBinsLds& L, const KernelIO::YearBins& yb, const void*, unsigned int* after_blk) { L = year_bins_lds(yb, after_blk); }
+__device__ __forceinline__ void year_bins_plan(YearBinsLdsRule& L, const KernelIO::YearBins& yb, const void* record, unsigned int* after_blk) {
+    const RuleBinsRecord* const rec = static_cast<const RuleBinsRecord*>(record);
+    static_cast<YearBinsLds&>(L) = year_bins_lds(yb, after_blk);
+    L.mn = rec->n_m_bins; L.mcells = L.mn + 2; L.mbins = rec->multiplier_bins;
+    L.medges = L.wedges + (L.wn + 1);
+    L.buf = reinterpret_cast<unsigned int*>(L.medges + (L.mn + 1));
+    L.row = 2 * L.cells + L.wcells + L.mcells;
+    L.fin = L.buf + 2 * L.row;
+}
+__device__ __forceinline__ void year_bins_load_m_edges(const YearBinsLds&, const void*, int, int) {}
+__device__ __forceinline__ void year_bins_load_m_edges(const YearBinsLdsRule& L, const void* record, int thread, int n_threads) {
+    const double* const e = static_cast<const RuleBinsRecord*>(record)->m_edges;
+    if (L.mn > 0) for (int k = thread; k <= L.mn; k += n_threads) L.medges[k] = e[k];
+}
+// where cell c of a flushed row goes when it lies in the multiplier segment (nothing in the plain form: its row ends before it)
+__device__ __forceinline__ void year_bins_m_dst(const YearBinsLds&, int, int, unsigned long long*&) {}
+__device__ __forceinline__ void year_bins_m_dst(const YearBinsLdsRule& L, int y, int c, unsigned long long*& dst) {
+    const int c0 = 2 * L.cells + L.wcells;
+    if (c >= c0) dst = (y >= 0 && L.mbins) ? L.mbins + (size_t)y * L.mcells + (c - c0) : nullptr;
 }
 // the cell of x in a row of n bins: 0 below e[0], n + 1 above e[n], else 1 + np.histogram's bin (the last one closed)
 __device__ __forceinline__ int year_bins_cell(const double* e, int n, double x) {
@@ -231,7 +271,8 @@ __device__ __forceinline__ int year_bins_cell(const double* e, int n, double x) 
 }
 // One row of the tables; call k of the workgroup (every thread makes the same calls: one barrier each).  nominal / px go to row t
 // of trajectory_bins / real_trajectory_bins (has_sample), wr_bits (NaN: not counted) to row y of wr_bins (y < 0: none).
-__device__ __forceinline__ void year_bins_row(const KernelIO::YearBins& yb, const YearBinsLds& L, int k, bool valid, int t, bool has_sample,
+template <typename LDS>
+__device__ __forceinline__ void year_bins_row(const KernelIO::YearBins& yb, const LDS& L, int k, bool valid, int t, bool has_sample,
                                               double nominal, double px, int y, unsigned long long wr_bits) {
     unsigned int* const b = L.buf + (k & 1) * L.row;
     if (valid) {
@@ -253,6 +294,7 @@ __device__ __forceinline__ void year_bins_row(const KernelIO::YearBins& yb, cons
         if (c < L.cells) dst = yb.trajectory ? yb.trajectory + (size_t)t * L.cells + c : nullptr;
         else if (c < 2 * L.cells) dst = yb.real_trajectory ? yb.real_trajectory + (size_t)t * L.cells + (c - L.cells) : nullptr;
         else if (y >= 0 && yb.wr) dst = yb.wr + (size_t)y * L.wcells + (c - 2 * L.cells);
+        year_bins_m_dst(L, y, c, dst);
         // every lane of the group adds, zeros included: consecutive cells, contiguous 8-byte atomics.  Adding only the non-zero
         // cells measured the same (LABNOTES R10: 6.33 / 6.47 ms against 6.30 / 6.51 at 64 / 256 bins)
         if (dst) atomicAdd(dst, (unsigned long long)v);
@@ -456,6 +498,22 @@ struct FanRule {
     static constexpr int64_t stride = 0;
 };
 struct NoFanRule {};
+// MODE 3 with RULE: the yearly-bins state with the launch's rule, and the top of a retirement year: rule_year_from's decision and
+// counts on that rule, then the lane's m into the multiplier segment of the row buffer the year's own year_bins_row call (call
+// B.k, at the end of this year or in the pad loop) flushes behind its barrier.  The thread has passed barrier B.k - 1, behind
+// which every wave had flushed that buffer's row B.k - 2: the binning needs no barrier of its own.
+struct YearBinsRuleState { YearBinsLdsRule L; int k; double last; FanRule R; };
+__device__ __forceinline__ void rule_year_binned(RuleState& r, const YearBinsRuleState& B, int year, bool valid, bool alive, double b1, double b2, double infl, uint64_t li) {
+    rule_year_from(r, B.R, year, valid, alive, b1, b2, infl, li);
+    if (B.L.mbins && valid && alive)
+        atomicAdd(&B.L.buf[(B.k & 1) * B.L.row + 2 * B.L.cells + B.L.wcells + year_bins_cell(B.L.medges, B.L.mn, r.m)], 1u);
+}
+__device__ __forceinline__ void rule_bins_begin(YearBinsRuleState& B, const void* record) {
+    const RuleBinsRecord* const rec = static_cast<const RuleBinsRecord*>(record);
+    B.R.upper = rec->upper; B.R.lower = rec->lower; B.R.keep = rec->keep; B.R.grow = rec->grow; B.R.floor = rec->floor; B.R.ceiling = rec->ceiling;
+    B.R.year_counts = rec->year_counts;
+}
+__device__ __forceinline__ void rule_bins_begin(YearBinsState&, const void*) {}
 template <typename IO>
 __device__ __forceinline__ void rule_year(NoRuleState&, const IO&, int, bool, bool, double, double, double, uint64_t) {}
 // a year the whole wave does not begin (the pad loop): NaN in the multiplier row
@@ -525,8 +583,8 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     // written in place under `if constexpr (RULE)` cost the time-sliced trajectory kernels, which never run them, one or two
     // spilled SGPRs each.)
     static_assert(!RULE || (RNG == (int)MCR_RNG_PHILOX && TAXED == 3 && !INJ && !XS && EXACT == kExactMonthDefault && GF == 0 && MF == 0 && SF == 0 && !LIST && NPROD == 1 &&
-                            (((MODE == 0 || MODE == 1) && PHASE == 0 && !SPLIT && !OUT) || (MODE == 0 && PHASE == 11 && SPLIT))),
-                  "the spending rule exists for the plain whole-path Philox launches, count-only and summary, and for the rule fan-out, on the generic tax mask");
+                            (((MODE == 0 || MODE == 1 || MODE == 3) && PHASE == 0 && !SPLIT && !OUT) || (MODE == 0 && PHASE == 11 && SPLIT))),
+                  "the spending rule exists for the plain whole-path Philox launches, count-only, summary and yearly bins, and for the rule fan-out, on the generic tax mask");
     // PHASE 4 = PHASE 2 (a candidate's decumulation resumed from its accumulation snapshot) time-sliced like PHASE 3: the
     // 17-month verification window of the search is 17 x 196 workgroups = 2.17 rounds of the resident slots.
     constexpr bool kExpFan = PHASE == 5 || PHASE == 6;    // expense fan-out: the levels are monthly_expenses, resumed at retirement
@@ -687,13 +745,17 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     const int n_hist = ((PHASE == 0 || PHASE == 3) && io.out.hist_bins != nullptr) ? io.out.hist_n_bins : 0;
     for (int k = threadIdx.x; k < n_blk + n_hist; k += kThreads) blk[k] = 0u;
     // MODE 3: behind the block counters the edge arrays, the row buffers and the final_success cells (YearBinsLds)
-    [[maybe_unused]] std::conditional_t<kBins, YearBinsState, NoYearBins> YB;    // (an empty object in every other variant)
+    // (RULE: the state with the rule and the multiplier segment, from the launch's one record behind `cand_params`)
+    constexpr bool kBinsRule = kBins && RULE;
+    [[maybe_unused]] std::conditional_t<kBins, std::conditional_t<kBinsRule, YearBinsRuleState, YearBinsState>, NoYearBins> YB;    // (an empty object in every other variant)
     if constexpr (kBins) {
-        YB.L = year_bins_lds(io.yb, blk + n_blk + n_hist);
+        year_bins_plan(YB.L, io.yb, cand_params, blk + n_blk + n_hist);
+        rule_bins_begin(YB, cand_params);
         YB.k = 0; YB.last = 0.0;
         const YearBinsLds& YL = YB.L;
         if (YL.n > 0) for (int k = threadIdx.x; k <= YL.n; k += kThreads) YL.edges[k] = io.yb.edges[k];
         if (YL.wn > 0) for (int k = threadIdx.x; k <= YL.wn; k += kThreads) YL.wedges[k] = io.yb.wr_edges[k];
+        year_bins_load_m_edges(YB.L, cand_params, (int)threadIdx.x, kThreads);
         for (int k = threadIdx.x; k < 2 * YL.row + YL.cells; k += kThreads) YL.buf[k] = 0u;
     }
     __syncthreads();
@@ -1105,6 +1167,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         if (!SPLIT && __builtin_amdgcn_ballot_w64(alive) == 0ull) break;  // every lane of this wave has failed: nothing left to simulate
         if (SPLIT) { lane_alive = alive; if (wg_dead) break; }           // (SPLIT: the wave keeps pace with its producers' barriers until the workgroup votes to stop)
         if constexpr (kRuleFan) rule_year_from(RS, FR, year, valid, alive, b1, b2, infl, li);   // (PHASE 11: the wave's own rule and year counts, no multiplier row)
+        else if constexpr (kBinsRule) rule_year_binned(RS, YB, year, valid, alive, b1, b2, infl, li);   // (MODE 3: the record's rule; m binned, no multiplier row)
         else
         rule_year(RS, io, year, valid, alive, b1, b2, infl, li);      // (RULE: the year's decision, counts and multiplier row; nothing in every other kernel)
         double tg1 = 0.0, tg2 = 0.0, treal = 0.0;  // :635-637
@@ -1303,7 +1366,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         if constexpr (kBins) year_bins_row(io.yb, YB.L, YB.k++, valid, t_idx++, !(P.total_months % kMPY != 0 && year == ry - 1), 0.0, infl, year, kNanBits);
         else put_sample(t_idx++, 0.0, infl);
         if (kTraj && valid && wrt) store_bits(&wrt[(int64_t)year * stride + (int64_t)li], kNanBits);
-        if constexpr (!kRuleFan) rule_pad(RS, io, year, valid, li);   // (PHASE 11 writes no multiplier row)
+        if constexpr (!kRuleFan && !kBinsRule) rule_pad(RS, io, year, valid, li);   // (PHASE 11 and MODE 3 write no multiplier row)
     }
     if (kSliced && seg >= 0 && seg < io.seg_q - 1) {
         // Not the block's last segment: raise the flag, to 1 with the lanes' state handed over, or to 2 (every wave gets here:
@@ -3133,6 +3196,96 @@ static int launch_year_bins(const mcr_params* p, const mcr_rng* rng, uint32_t st
     return MCR_OK;
 }
 
+// Yearly bins under a spending rule (MODE 3 of path_kernel with RULE; mcr_run_rule_year_bins_rng): path_kernel<3, Philox, mask 3,
+// annual-gains tax or not, ..., RULE>, two instantiations.  The checks need no device: check_year_bins' rules for `out` / `yb`,
+// validate_spending_rule's for the rule, the multiplier table's own, and by name everything launch_rule refuses.  On success the
+// parameter block and the launch's dynamic LDS are planned.
+static int plan_rule_year_bins(const mcr_params* p, const mcr_rng* rng, uint64_t path_begin, uint64_t n_paths, int32_t wm,
+                               const mcr_spending_rule* rule, const mcr_outputs* out, const mcr_year_bins* yb,
+                               const mcr_rule_year_bins* rule_yb, DevParams* d_out, size_t* lds) {
+    DevParams d;
+    std::vector<DevStream> extra;
+    int rc = derive_params(p, wm, &d, &extra);
+    if (rc != MCR_OK) return rc;
+    if ((rc = check_rng(rng)) != MCR_OK) return rc;
+    if ((rc = validate_spending_rule(rule)) != MCR_OK) return rc;
+    if ((rc = check_year_bins(out, yb)) != MCR_OK) return rc;
+    if (!rule_yb) { set_error("rule year bins: null rule_yb"); return MCR_ERR_INVALID_ARG; }
+    if (rule_yb->multiplier_bins) {
+        if (rule_yb->n_m_bins < 1 || rule_yb->n_m_bins > MCR_MAX_YEAR_BINS) {
+            set_error("rule year bins: n_m_bins = %d (1..%d)", rule_yb->n_m_bins, MCR_MAX_YEAR_BINS);
+            return MCR_ERR_INVALID_ARG;
+        }
+        if (!rule_yb->m_edges) { set_error("rule year bins: null m_edges under multiplier_bins"); return MCR_ERR_INVALID_ARG; }
+    }
+    if (n_paths > (uint64_t)INT32_MAX * kBlock) { set_error("n_paths too large for one launch"); return MCR_ERR_INVALID_ARG; }
+    if (path_begin + n_paths < path_begin) { set_error("path range overflows 64 bits"); return MCR_ERR_INVALID_ARG; }
+    if (rng->kind == MCR_RNG_NUMPY) { set_error("spending rule: the NumPy stream is not supported (the engine's own stream only)"); return MCR_ERR_UNSUPPORTED; }
+    if (rng->kind == MCR_RNG_HISTORY) { set_error("spending rule: the history stream is not supported (the engine's own stream only)"); return MCR_ERR_UNSUPPORTED; }
+    if (out->hist_bins && out->hist_n_bins != 0) { set_error("spending rule: the in-kernel histogram (hist_bins) is not supported"); return MCR_ERR_UNSUPPORTED; }
+    if (p->n_streams > MCR_INLINE_STREAMS && d.n_extra_streams > 0) {
+        set_error("spending rule: %d income streams need the generic variant (at most %d are supported)", (int)p->n_streams, MCR_INLINE_STREAMS);
+        return MCR_ERR_UNSUPPORTED;
+    }
+    if (needs_generic_variant(d)) { set_error("spending rule: the exact month (a realized-gains rate above 1 - 1e-6) needs the generic variant, which is not supported"); return MCR_ERR_UNSUPPORTED; }
+    const bool balance_tables = yb->trajectory_bins || yb->real_trajectory_bins || yb->final_success_bins;
+    const int n_m = rule_yb->multiplier_bins ? rule_yb->n_m_bins : 0;
+    // the multiplier segment: its edges as doubles and a cell in each row buffer, 8 + 2 x 4 = 16 bytes per bin like a withdrawal-rate bin
+    const size_t m_bytes = ((size_t)n_m + 1) * sizeof(double) + 2 * ((size_t)n_m + 2) * sizeof(unsigned int);
+    rc = plan_path_kernel_lds(d, 3, MCR_RNG_PHILOX, false, false, 0, lds,
+                              year_bins_lds(balance_tables ? yb->n_bins : 0, yb->wr_bins ? yb->n_wr_bins : 0) + m_bytes);
+    if (rc != MCR_OK) return rc;
+    if (d.n_lock_slots < d.n_lock_slots_total) {
+        set_error("spending rule: %d frozen income streams exceed the LDS budget and need the generic variant, which is not supported", (int)d.n_lock_slots_total);
+        return MCR_ERR_UNSUPPORTED;
+    }
+    *d_out = d;
+    return MCR_OK;
+}
+// The launch: device pointers in `out` / `yb` / `rule_yb`.  The rule and the rule's tables travel in ONE device record behind
+// path_kernel's third argument (RuleBinsRecord; a stream-ordered allocation released behind the launch, like a fan-out's table):
+// KernelIO keeps its size and every field its place.
+static int launch_rule_year_bins(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                                 int32_t wm, const mcr_spending_rule* rule, const mcr_outputs* out, const mcr_year_bins* yb,
+                                 const mcr_rule_year_bins* rule_yb, hipStream_t stream) {
+    DevParams d;
+    size_t lds = 0;
+    int rc = plan_rule_year_bins(p, rng, path_begin, n_paths, wm, rule, out, yb, rule_yb, &d, &lds);
+    if (rc != MCR_OK) return rc;
+    if (n_paths == 0) return MCR_OK;
+    KernelIO io = make_io(rng, nullptr, stream_id, path_begin, n_paths);
+    io.out = *out;
+    io.out.path_stride = (int64_t)n_paths;
+    io.out.hist_bins = nullptr; io.out.hist_edges = nullptr; io.out.hist_n_bins = 0;
+    const bool balance_tables = yb->trajectory_bins || yb->real_trajectory_bins || yb->final_success_bins;
+    io.yb.edges = balance_tables ? yb->edges : nullptr;
+    io.yb.n_bins = balance_tables ? yb->n_bins : 0;
+    io.yb.wr_edges = yb->wr_bins ? yb->wr_edges : nullptr;
+    io.yb.n_wr_bins = yb->wr_bins ? yb->n_wr_bins : 0;
+    io.yb.trajectory = (unsigned long long*)yb->trajectory_bins;
+    io.yb.real_trajectory = (unsigned long long*)yb->real_trajectory_bins;
+    io.yb.wr = (unsigned long long*)yb->wr_bins;
+    io.yb.final_success = (unsigned long long*)yb->final_success_bins;
+    RuleBinsRecord host = {rule->upper, rule->lower, 1.0 - rule->cut, 1.0 + rule->raise, rule->floor, rule->ceiling,
+                           (unsigned long long*)rule_yb->year_counts, (unsigned long long*)rule_yb->multiplier_bins,
+                           rule_yb->multiplier_bins ? rule_yb->m_edges : nullptr, rule_yb->multiplier_bins ? rule_yb->n_m_bins : 0, 0};
+    StreamAlloc record(stream);
+    if (!record.alloc(sizeof(host))) { set_error("rule year bins: the device record's allocation was refused"); return MCR_ERR_HIP; }
+    hipError_t e = hipMemcpyAsync(record.p, &host, sizeof(host), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) {
+        const dim3 grid((unsigned)((n_paths + kBlock - 1) / kBlock)), block(kBlock);
+        for_bool(d.any_annual_tax, [&](auto A) {
+            hipLaunchKernelGGL((path_kernel<3, 0, 3, decltype(A)::value, false, 0, false, false, kExactMonthDefault, 0, 0, 0, false, false, 1, true>),
+                               grid, block, lds, stream, d, io, (const DevParams*)record.p);
+        });
+        e = hipGetLastError();
+    }
+    const hipError_t ef = record.release();
+    if (e != hipSuccess) return hip_fail(e, "path_kernel launch (rule yearly bins)");
+    if (ef != hipSuccess) return hip_fail(ef, "path_kernel launch (rule yearly bins): record release");
+    return MCR_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Search probes: several candidates (months, spending or contribution levels, or a grid of both) over the same paths
 // ---------------------------------------------------------------------------------------------
@@ -4787,6 +4940,86 @@ int mcr_run_year_bins_multi_host_rng(const mcr_params* p, const mcr_rng* rng, ui
                                      int32_t working_months, const mcr_outputs* out, const mcr_year_bins* yb, const int32_t* devices,
                                      int32_t n_devices) {
     return run_year_bins_host_multi(devices, n_devices, p, rng, stream_id, path_begin, n_paths, working_months, out, yb);
+}
+
+// ---- yearly bins under a spending rule ---------------------------------------------------------------------------------
+// (both entry points check every argument before they look for a device: a refusal names its field with no GPU in the box)
+int mcr_run_rule_year_bins_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                               int32_t working_months, const mcr_spending_rule* rule, const mcr_outputs* out, const mcr_year_bins* yb,
+                               const mcr_rule_year_bins* rule_yb, int device, void* hip_stream) {
+    DevParams d;
+    size_t lds = 0;
+    const int rc = plan_rule_year_bins(p, rng, path_begin, n_paths, working_months, rule, out, yb, rule_yb, &d, &lds);
+    if (rc != MCR_OK) return rc;
+    MCR_ENTER_DEVICE(device);
+    return launch_rule_year_bins(p, rng, stream_id, path_begin, n_paths, working_months, rule, out, yb, rule_yb, (hipStream_t)hip_stream);
+}
+
+// HOST pointers, one device: the pooled context's block holds every table, both rule tables and the three edge arrays; the tables
+// come back through a staging copy, so the caller's stay untouched unless the whole call succeeds (run_year_bins_host_on's plan).
+int mcr_run_rule_year_bins_host_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                                    int32_t working_months, const mcr_spending_rule* rule, const mcr_outputs* out, const mcr_year_bins* yb,
+                                    const mcr_rule_year_bins* rule_yb, int device) {
+    mcr_sizes sz;
+    DevParams dp;
+    size_t lds = 0;
+    int rc = check_rng(rng, true);
+    if (rc != MCR_OK) return rc;
+    if ((rc = query_sizes(p, working_months, &sz)) != MCR_OK) return rc;
+    if ((rc = validate_params(p)) != MCR_OK) return rc;
+    if ((rc = plan_rule_year_bins(p, rng, path_begin, n_paths, working_months, rule, out, yb, rule_yb, &dp, &lds)) != MCR_OK) return rc;
+    if ((yb->trajectory_bins || yb->real_trajectory_bins || yb->final_success_bins) && (rc = check_edges_host("edges", yb->edges, yb->n_bins)) != MCR_OK) return rc;
+    if (yb->wr_bins && (rc = check_edges_host("wr_edges", yb->wr_edges, yb->n_wr_bins)) != MCR_OK) return rc;
+    if (rule_yb->multiplier_bins && (rc = check_edges_host("m_edges", rule_yb->m_edges, rule_yb->n_m_bins)) != MCR_OK) return rc;
+    MCR_ENTER_DEVICE(device);
+    if (n_paths == 0) return MCR_OK;
+    mcr_outputs d = {};
+    mcr_year_bins dy = {};
+    mcr_rule_year_bins dr = {};
+    dy.n_bins = yb->n_bins; dy.n_wr_bins = yb->n_wr_bins; dr.n_m_bins = rule_yb->n_m_bins;
+    struct Buf { void** dev; void* host; size_t bytes, offset; bool download; };
+    std::vector<Buf> bufs;
+    size_t total = 0;
+    auto plan = [&](void** dev, const void* host, size_t bytes, bool down) {
+        if (!host || bytes == 0) return;
+        bufs.push_back({dev, const_cast<void*>(host), bytes, total, down});
+        total += (bytes + 255) & ~(size_t)255;
+    };
+    const size_t ry = (size_t)sz.retirement_years;
+    for (const YearBinsBlock& b : year_bins_blocks(sz, out, yb, &d, &dy)) plan((void**)b.dst, *b.src, b.n * sizeof(uint64_t), true);
+    plan((void**)&dr.year_counts, rule_yb->year_counts, ry * MCR_RULE_N_COUNTS * sizeof(uint64_t), true);
+    if (rule_yb->multiplier_bins) {
+        plan((void**)&dr.multiplier_bins, rule_yb->multiplier_bins, ry * ((size_t)rule_yb->n_m_bins + 2) * sizeof(uint64_t), true);
+        plan((void**)&dr.m_edges, rule_yb->m_edges, (size_t)(rule_yb->n_m_bins + 1) * sizeof(double), false);
+    }
+    if (yb->trajectory_bins || yb->real_trajectory_bins || yb->final_success_bins) plan((void**)&dy.edges, yb->edges, (size_t)(yb->n_bins + 1) * sizeof(double), false);
+    if (yb->wr_bins) plan((void**)&dy.wr_edges, yb->wr_edges, (size_t)(yb->n_wr_bins + 1) * sizeof(double), false);
+
+    HostCtxLease lease(device);
+    HostCtx* ctx = lease.ctx;
+    if (!ctx) return MCR_ERR_HIP;
+    hipError_t e = host_ctx_reserve(ctx, total);
+    if (e != hipSuccess) return hip_fail(e, "device allocation (rule yearly bins)");
+    for (Buf& b : bufs) {   // accumulated blocks start from the caller's current values
+        *b.dev = (char*)ctx->block + b.offset;
+        if (e == hipSuccess) e = hipMemcpyAsync(*b.dev, b.host, b.bytes, hipMemcpyHostToDevice, ctx->stream);
+    }
+    if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return hip_fail(e, "upload"); }
+    rc = launch_rule_year_bins(p, rng, stream_id, path_begin, n_paths, working_months, rule, &d, &dy, &dr, ctx->stream);
+    std::vector<std::vector<unsigned char>> staged(bufs.size());
+    if (rc == MCR_OK)
+        for (size_t i = 0; i < bufs.size(); ++i) {
+            if (!bufs[i].download || e != hipSuccess) continue;
+            staged[i].resize(bufs[i].bytes);
+            e = hipMemcpyAsync(staged[i].data(), *bufs[i].dev, bufs[i].bytes, hipMemcpyDeviceToHost, ctx->stream);
+        }
+    const hipError_t es = hipStreamSynchronize(ctx->stream);
+    if (rc != MCR_OK) return rc;
+    if (e != hipSuccess) return hip_fail(e, "download");
+    if (es != hipSuccess) return hip_fail(es, "path_kernel execution (rule yearly bins)");
+    for (size_t i = 0; i < bufs.size(); ++i)
+        if (!staged[i].empty()) std::memcpy(bufs[i].host, staged[i].data(), bufs[i].bytes);
+    return MCR_OK;
 }
 
 int mcr_validate_params(const mcr_params* p) { return validate_params(p); }

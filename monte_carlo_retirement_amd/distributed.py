@@ -279,13 +279,18 @@ def run_sharded_bands(params, rng_or_seed, stream_id: int, n_total: int, working
     return out
 
 
-def run_sharded_year_bins(params, rng_or_seed, stream_id: int, n_total: int, working_months: int, edges=None, wr_edges=None):
+def run_sharded_year_bins(params, rng_or_seed, stream_id: int, n_total: int, working_months: int, edges=None, wr_edges=None,
+                          rule=None, m_edges=None):
     """The fan chart of ``n_total`` paths on N GPUs with no trajectory slab: every rank runs the yearly-bins kernel over its
     shard of the global path range (``engine.YearBinsBatch``; nothing is kept per path) and the exchange is ONE sum
     all-reduce of the integer vector ``[success, paths | wr_obs[ry] | ruin_bins[ry+2] | trajectory_bins[T][n+2] |
     real_trajectory_bins[T][n+2] | wr_bins[ry][nw+2] | final_success_bins[n+2]]``.  Returns the same dict on every rank:
     the named blocks (numpy int64), ``vector`` (the whole block), ``edges`` / ``wr_edges``, ``counts``, ``shard`` and
-    ``exchange`` (the collectives that ran); quantile brackets come from ``aggregation.bands_from_bins``."""
+    ``exchange`` (the collectives that ran); quantile brackets come from ``aggregation.bands_from_bins``.
+
+    ``rule`` (a `spending_rules.SpendingRule`): the paths spend under that guardrail (``mcr_run_rule_year_bins_rng``) and the
+    vector ends ``... | rule_year_counts[ry][4] | multiplier_bins[ry][nm+2]]`` (binned on ``m_edges``, returned too): still ONE
+    sum all-reduce, of the longer vector."""
     import torch
     import torch.distributed as dist
 
@@ -293,7 +298,7 @@ def run_sharded_year_bins(params, rng_or_seed, stream_id: int, n_total: int, wor
 
     rank, world = (dist.get_rank(), dist.get_world_size()) if is_active() else (0, 1)
     begin, count = shard_range(int(n_total), rank, world)
-    batch = E.YearBinsBatch(params, working_months, edges, wr_edges, device=torch.cuda.current_device())
+    batch = E.YearBinsBatch(params, working_months, edges, wr_edges, device=torch.cuda.current_device(), rule=rule, m_edges=m_edges)
     if count > 0:
         batch.launch(rng_or_seed, stream_id, begin, count)
     vec = batch.reduce_vec
@@ -302,7 +307,9 @@ def run_sharded_year_bins(params, rng_or_seed, stream_id: int, n_total: int, wor
             vec = vec.cpu()
         all_reduce_sum_(vec)
     host = vec.cpu().numpy()
-    res = E.split_year_bins(host, batch.sizes, batch.n_bins, batch.n_wr_bins)
+    res = E.split_year_bins(host, batch.sizes, batch.n_bins, batch.n_wr_bins, batch.n_m_bins)
+    if batch.rule is not None:
+        res["m_edges"] = batch.m_edges
     ry = batch.sizes.retirement_years
     res.update({
         "vector": host, "edges": batch.edges, "wr_edges": batch.wr_edges, "shard": (begin, count),

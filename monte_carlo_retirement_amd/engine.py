@@ -17,7 +17,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from . import _native as N
-from ._native import McrAssumptions, McrIncomeOption, McrOptionOutcomes, McrOutputs, McrParams, McrRng, McrScenario, McrSizes, McrYearBins
+from ._native import McrAssumptions, McrIncomeOption, McrOptionOutcomes, McrOutputs, McrParams, McrRng, McrScenario, McrSizes, McrYearBins, McrRuleYearBins
 
 SUMMARY_FIELDS = (
     "start_balance",
@@ -327,22 +327,30 @@ def default_wr_edges(n_bins: int = 256, hi: float = 100.0) -> np.ndarray:
 
 
 #: (name, rows, cells) of the blocks of a yearly-bins result, in the order of the one vector; T / ry / nb / nw filled in
-def _year_bins_layout(sz: McrSizes, n_bins: int, n_wr_bins: int):
+def _year_bins_layout(sz: McrSizes, n_bins: int, n_wr_bins: int, n_m_bins: Optional[int] = None):
+    """``n_m_bins`` (a launch under a spending rule): the rule's two blocks BEHIND the others, so the plain layout is a prefix."""
     T, ry = sz.trajectory_len, sz.retirement_years
-    return (
+    plain = (
         ("counters", 1, N.MCR_N_COUNTERS), ("wr_obs_counts", 1, ry), ("ruin_year_bins", 1, sz.ruin_bins),
         ("trajectory_bins", T, n_bins + 2), ("real_trajectory_bins", T, n_bins + 2), ("wr_bins", ry, n_wr_bins + 2),
         ("final_success_bins", 1, n_bins + 2),
     )
+    if n_m_bins is None:
+        return plain
+    return plain + (("rule_year_counts", ry, N.MCR_RULE_N_COUNTS), ("multiplier_bins", ry, int(n_m_bins) + 2))
 
 
-def split_year_bins(vec, sz: McrSizes, n_bins: int, n_wr_bins: int) -> dict:
+_YEAR_BINS_TABLES = ("trajectory_bins", "real_trajectory_bins", "wr_bins", "rule_year_counts", "multiplier_bins")
+
+
+def split_year_bins(vec, sz: McrSizes, n_bins: int, n_wr_bins: int, n_m_bins: Optional[int] = None) -> dict:
     """Named views of the one vector ``[counters | wr_obs | ruin | trajectory | real | wr | final_success]`` (numpy
-    array or torch tensor): tables ``[rows, cells]``, the others flat."""
+    array or torch tensor): tables ``[rows, cells]``, the others flat.  With ``n_m_bins`` (a launch under a spending rule)
+    the vector ends ``... | rule_year_counts[ry][4] | multiplier_bins[ry][n_m_bins + 2]]``."""
     out, at = {}, 0
-    for name, rows, cells in _year_bins_layout(sz, n_bins, n_wr_bins):
+    for name, rows, cells in _year_bins_layout(sz, n_bins, n_wr_bins, n_m_bins):
         v = vec[at:at + rows * cells]
-        out[name] = v.reshape(rows, cells) if name.endswith("_bins") and name not in ("ruin_year_bins", "final_success_bins") else v
+        out[name] = v.reshape(rows, cells) if name in _YEAR_BINS_TABLES else v
         at += rows * cells
     assert at == vec.shape[0]
     return out
@@ -352,9 +360,14 @@ class YearBinsBatch:
     """The integer block of a yearly-bins run resident in HBM: ONE contiguous int64 device vector ``reduce_vec`` =
     ``[counters | wr_obs_counts | ruin_year_bins | trajectory_bins | real_trajectory_bins | wr_bins | final_success_bins]``
     with named views into it, accumulated into by every :meth:`launch` (``mcr_run_year_bins_rng`` on torch's current
-    stream).  Nothing is kept per path: the vector is all a multi-GPU caller has to sum."""
+    stream).  Nothing is kept per path: the vector is all a multi-GPU caller has to sum.
 
-    def __init__(self, params: McrParams, working_months: int, edges=None, wr_edges=None, device: int = 0):
+    ``rule`` (a `spending_rules.SpendingRule` or ``McrSpendingRule``): the paths spend under that guardrail
+    (``mcr_run_rule_year_bins_rng``), and the vector gains two blocks behind the others,
+    ``[... | final_success_bins | rule_year_counts[ry][4] | multiplier_bins[ry][nm + 2]]``, the multipliers binned on
+    ``m_edges`` (default: `default_multiplier_edges`)."""
+
+    def __init__(self, params: McrParams, working_months: int, edges=None, wr_edges=None, device: int = 0, rule=None, m_edges=None):
         import torch
 
         N.require_device()
@@ -366,10 +379,15 @@ class YearBinsBatch:
         self.edges = year_edge_array(default_year_edges() if edges is None else edges)
         self.wr_edges = year_edge_array(default_wr_edges() if wr_edges is None else wr_edges, "wr_edges")
         self.n_bins, self.n_wr_bins = self.edges.shape[0] - 1, self.wr_edges.shape[0] - 1
+        if rule is None and m_edges is not None:
+            raise ValueError("m_edges without a spending rule")
+        self.rule = None if rule is None else _rule_record(rule)
+        self.m_edges = None if rule is None else year_edge_array(default_multiplier_edges(self.rule) if m_edges is None else m_edges, "m_edges")
+        self.n_m_bins = None if rule is None else self.m_edges.shape[0] - 1
         dev = torch.device("cuda", self.device)
-        n_words = sum(rows * cells for _, rows, cells in _year_bins_layout(self.sizes, self.n_bins, self.n_wr_bins))
+        n_words = sum(rows * cells for _, rows, cells in _year_bins_layout(self.sizes, self.n_bins, self.n_wr_bins, self.n_m_bins))
         self.reduce_vec = torch.zeros(n_words, dtype=torch.int64, device=dev)
-        for name, view in split_year_bins(self.reduce_vec, self.sizes, self.n_bins, self.n_wr_bins).items():
+        for name, view in split_year_bins(self.reduce_vec, self.sizes, self.n_bins, self.n_wr_bins, self.n_m_bins).items():
             setattr(self, name, view)
         self._edges_dev = torch.as_tensor(self.edges, device=dev)
         self._wr_edges_dev = torch.as_tensor(self.wr_edges, device=dev)
@@ -385,6 +403,14 @@ class YearBinsBatch:
         y.wr_bins = self.wr_bins.data_ptr()
         y.final_success_bins = self.final_success_bins.data_ptr()
         self._out, self._yb = o, y
+        self._rule_yb = None
+        if self.rule is not None:
+            self._m_edges_dev = torch.as_tensor(self.m_edges, device=dev)
+            r = McrRuleYearBins()
+            r.m_edges, r.n_m_bins = self._m_edges_dev.data_ptr(), self.n_m_bins
+            r.multiplier_bins = self.multiplier_bins.data_ptr()
+            r.year_counts = self.rule_year_counts.data_ptr()
+            self._rule_yb = r
         self._lib = N.load_library()
 
     def zero(self) -> None:
@@ -395,6 +421,13 @@ class YearBinsBatch:
         accumulate.  ``seed``: int (Philox key) or an ``McrRng`` descriptor."""
         stream = self.torch.cuda.current_stream(self.device).cuda_stream
         rng = _as_rng(seed, self.device)
+        if self.rule is not None:
+            rc = self._lib.mcr_run_rule_year_bins_rng(
+                C.byref(self.params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), self.working_months,
+                C.byref(self.rule), C.byref(self._out), C.byref(self._yb), C.byref(self._rule_yb), self.device, C.c_void_p(stream),
+            )
+            N.check(rc, "mcr_run_rule_year_bins_rng")
+            return
         rc = self._lib.mcr_run_year_bins_rng(
             C.byref(self.params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), self.working_months,
             C.byref(self._out), C.byref(self._yb), self.device, C.c_void_p(stream),
@@ -403,8 +436,10 @@ class YearBinsBatch:
 
     def host(self) -> Dict[str, np.ndarray]:
         """The block on the host (synchronises): named numpy arrays, plus the edges."""
-        res = split_year_bins(self.reduce_vec.cpu().numpy(), self.sizes, self.n_bins, self.n_wr_bins)
+        res = split_year_bins(self.reduce_vec.cpu().numpy(), self.sizes, self.n_bins, self.n_wr_bins, self.n_m_bins)
         res["edges"], res["wr_edges"] = self.edges, self.wr_edges
+        if self.rule is not None:
+            res["m_edges"] = self.m_edges
         return res
 
 
@@ -1023,3 +1058,59 @@ def run_rule_host(params: McrParams, seed, stream_id: int, path_begin: int, n_pa
     out["counters"] = counts[:N.MCR_N_COUNTERS].astype(np.uint64)
     out["year_counts"] = counts[N.MCR_N_COUNTERS:].reshape(-1, N.MCR_RULE_N_COUNTS).astype(np.uint64)
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Yearly bins under a spending rule: the fan charts of balance and spending (mcr_run_rule_year_bins_rng)
+# ---------------------------------------------------------------------------------------------
+def default_multiplier_edges(rule, n_bins: int = 64) -> np.ndarray:
+    """Edges for the spending multiplier: ``n_bins`` equal bins over ``[floor, ceiling]``, the range the rule keeps it in.
+    The neutral rule's range may be the single point 1.0: zero-width bins, which are legal (every m = 1 lands in the last)."""
+    n_bins = int(n_bins)
+    if not (1 <= n_bins <= N.MCR_MAX_YEAR_BINS):
+        raise ValueError(f"default_multiplier_edges: n_bins must be 1..{N.MCR_MAX_YEAR_BINS}, got {n_bins}")
+    rec = _rule_record(rule)
+    return np.linspace(float(rec.floor), float(rec.ceiling), n_bins + 1)
+
+
+def run_rule_year_bins_host(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int, rule,
+                            edges=None, wr_edges=None, m_edges=None, device: int = 0,
+                            into: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, np.ndarray]:
+    """`run_year_bins_host` under a spending rule (``mcr_run_rule_year_bins_host_rng``, one device): its arrays for paths
+    that spend ``(monthly_expenses m) price``, and ``rule_year_counts`` ``[ry, 4]`` (``mcr_run_rule_rng``'s year counts),
+    ``multiplier_bins`` ``[ry, n_m_bins+2]`` (row ``y``: the multipliers of the paths that begin year ``y`` alive) and
+    ``m_edges``.  ``into``: a previous result to accumulate into (same edges)."""
+    lib = N.load_library()
+    N.require_device()
+    sz = query_sizes(params, working_months)
+    rec = _rule_record(rule)
+    e = year_edge_array(default_year_edges() if edges is None else edges)
+    we = year_edge_array(default_wr_edges() if wr_edges is None else wr_edges, "wr_edges")
+    me = year_edge_array(default_multiplier_edges(rec) if m_edges is None else m_edges, "m_edges")
+    nb, nw, nm = e.shape[0] - 1, we.shape[0] - 1, me.shape[0] - 1
+    if into is not None:
+        res = into
+        if not (np.array_equal(res["edges"], e) and np.array_equal(res["wr_edges"], we) and np.array_equal(res["m_edges"], me)):
+            raise ValueError("`into` was binned on other edges")
+    else:
+        res = {name: np.zeros((rows, cells) if name in _YEAR_BINS_TABLES else cells, dtype=np.uint64)
+               for name, rows, cells in _year_bins_layout(sz, nb, nw, nm)}
+        res["edges"], res["wr_edges"], res["m_edges"] = e, we, me
+    o = McrOutputs()
+    o.counters = res["counters"].ctypes.data
+    o.wr_obs_counts = res["wr_obs_counts"].ctypes.data
+    o.ruin_year_bins = res["ruin_year_bins"].ctypes.data
+    y = McrYearBins()
+    y.edges, y.n_bins, y.wr_edges, y.n_wr_bins = e.ctypes.data, nb, we.ctypes.data, nw
+    for name in ("trajectory_bins", "real_trajectory_bins", "wr_bins", "final_success_bins"):
+        setattr(y, name, res[name].ctypes.data)
+    r = McrRuleYearBins()
+    r.m_edges, r.n_m_bins = me.ctypes.data, nm
+    r.multiplier_bins = res["multiplier_bins"].ctypes.data
+    r.year_counts = res["rule_year_counts"].ctypes.data
+    rng = _as_rng(seed)
+    rc = lib.mcr_run_rule_year_bins_host_rng(
+        C.byref(params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), int(working_months), C.byref(rec),
+        C.byref(o), C.byref(y), C.byref(r), int(device))
+    N.check(rc, "mcr_run_rule_year_bins_host_rng")
+    return res

@@ -284,7 +284,7 @@ def _bracket_payload(lo: np.ndarray, hi: np.ndarray, qs, digits: int) -> dict:
 
 def streamed_result(config: Config, simulator: RetirementMonteCarloSimulator, required_w_months: int,
                     search_curve: Optional[List[dict]] = None, num_simulations: Optional[int] = None,
-                    edges=None, wr_edges=None) -> dict:
+                    edges=None, wr_edges=None, rule=None, m_edges=None) -> dict:
     """The keys of ``compact_result`` for ANY number of paths: the path kernel bins every yearly sample itself
     (``mcr_run_year_bins_rng``), so nothing is kept per path — the document comes out of a few hundred KB of integers, and
     under a process group out of ONE all-reduce (``distributed.run_sharded_year_bins``).
@@ -299,7 +299,14 @@ def streamed_result(config: Config, simulator: RetirementMonteCarloSimulator, re
     NOT AVAILABLE: ``summary.swr`` (the first-year withdrawal-rate median is taken over another cohort than ``wr_bins[0]``:
     it leaves out paths whose start balance is <= 1e-6 and includes paths that fail in year 0) — None, and named in
     ``not_available``; a median whose order statistic falls outside the caller's edges is None and named there too.
-    ``histogram_binned`` is ``final_success_bins`` on ``edges`` (with its below / above counts)."""
+    ``histogram_binned`` is ``final_success_bins`` on ``edges`` (with its below / above counts).
+
+    ``rule`` (a `spending_rules.SpendingRule`): every path spends under that guardrail (``mcr_run_rule_year_bins_rng``; the
+    engine's own stream only).  The document gains ``spending_rule`` (the rule) and ``spending``: per retirement year the
+    5 / 25 / 50 / 75 / 95 % real monthly spending among the paths that begin the year alive (`spending_rules.SpendingBands`
+    on ``m_edges``; its brackets in ``band_brackets["spending"]``) and the EXACT alive / cut / at-floor / raised shares of the
+    year counts.  The five sample paths would need a trajectory launch, which a rule refuses: they are None and named in
+    ``not_available``."""
     wm = int(required_w_months)
     n = int(config.num_simulations_main if num_simulations is None else num_simulations)
     if n <= 0:
@@ -307,12 +314,12 @@ def streamed_result(config: Config, simulator: RetirementMonteCarloSimulator, re
     params = simulator._current_params()
     rng = simulator._batch_rng(n)
     if D.is_active():
-        yb = D.run_sharded_year_bins(params, rng, simulator._stream_id, n, wm, edges, wr_edges)
+        yb = D.run_sharded_year_bins(params, rng, simulator._stream_id, n, wm, edges, wr_edges, rule=rule, m_edges=m_edges)
     else:
         import torch
 
         with torch.cuda.device(simulator._local_device()):
-            yb = D.run_sharded_year_bins(params, rng, simulator._stream_id, n, wm, edges, wr_edges)
+            yb = D.run_sharded_year_bins(params, rng, simulator._stream_id, n, wm, edges, wr_edges, rule=rule, m_edges=m_edges)
     e, we = yb["edges"], yb["wr_edges"]
     ok_count = int(yb["counters"][0])
     tq, wq = list(A.TRAJECTORY_QUANTILES), list(A.WR_QUANTILES)
@@ -325,7 +332,7 @@ def streamed_result(config: Config, simulator: RetirementMonteCarloSimulator, re
     f_lo, f_hi, f_est = A.bands_from_bins(yb["trajectory_bins"][T - 1], e, FINAL_BALANCE_PERCENTILES)
     m_lo, m_hi, m_est = A.bands_from_bins(yb["final_success_bins"], e, [0.50])
     # the five sample paths, exactly: one-path full-output launches at the picked global indices
-    picked = simulator._sample_columns(n)
+    picked = simulator._sample_columns(n) if rule is None else None
     samples = real_samples = None
     if picked is not None:
         samples, real_samples = [], []
@@ -341,6 +348,8 @@ def streamed_result(config: Config, simulator: RetirementMonteCarloSimulator, re
     # an estimate is NaN where the order statistic lies outside the edges (or the row is empty): None in the document, and the
     # field is named in not_available
     not_available = ["summary.swr"]
+    if rule is not None:      # (a sample path is a trajectory launch, which there is none of under a rule)
+        not_available += ["trajectory.samples", "trajectory_real.samples"]
 
     def value(a, field):
         if math.isfinite(a[0, 0]):
@@ -388,6 +397,27 @@ def streamed_result(config: Config, simulator: RetirementMonteCarloSimulator, re
     if search_curve:
         doc["search_curve"] = {"points": dedupe_search_curve(search_curve), "target_probability": config.target_probability,
                                "selected_working_months": wm}
+    if rule is not None:
+        from .spending_rules import SpendingBands, SpendingRuleOutcomes
+
+        bands = SpendingBands(yb["multiplier_bins"], yb["m_edges"], float(params.monthly_expenses))
+        shares = SpendingRuleOutcomes(ok_count, n, yb["rule_year_counts"], config.current_age + wm / MONTHS_PER_YEAR).years()
+        keys = [_pct_key(q) for q in bands.quantiles]
+
+        def col(a, j):
+            return [round(float(v), 2) if math.isfinite(v) else None for v in a[:, j]]
+
+        for fam in ("trajectory", "trajectory_real"):
+            doc[fam]["sample_paths"] = None
+        doc["spending_rule"] = rule.as_dict() if hasattr(rule, "as_dict") else {f: float(getattr(rule, f)) for f in ("upper", "lower", "cut", "raise", "floor", "ceiling")}
+        doc["spending"] = {
+            "base_monthly_expenses": float(params.monthly_expenses),
+            "years": shares,
+            "percentiles": {k: col(bands.estimate, j) for j, k in enumerate(keys)},
+            "m_edges": [float(x) for x in yb["m_edges"]],
+        }
+        doc["band_brackets"]["spending"] = {"lo": {k: col(bands.lo, j) for j, k in enumerate(keys)},
+                                             "hi": {k: col(bands.hi, j) for j, k in enumerate(keys)}}
     return doc
 
 

@@ -1017,6 +1017,34 @@ class RetirementMonteCarloSimulator:
                                     retirement_age(self.params_model.current_age, int(working_months)),
                                     ever_cut=int(flat[k]) if multipliers else None)
 
+    def spending_rule_fan_chart(self, working_months: int, rule, num_simulations: Optional[int] = None, edges=None, wr_edges=None,
+                                m_edges=None) -> Dict[str, object]:
+        """The fan charts of a household that follows `rule` at ``working_months``, for any number of paths: one yearly-bins
+        launch under the rule over the active stream's batch (``mcr_run_rule_year_bins_rng``; nothing is kept per path, one
+        all-reduce under a process group).  Returns the tables of ``distributed.run_sharded_year_bins(rule=...)`` (balance,
+        real balance, withdrawal rate, final balance, ``rule_year_counts``, ``multiplier_bins`` and the edges) with
+        ``spending`` = the `spending_rules.SpendingBands` of the real monthly spending per retirement year and ``outcomes`` =
+        the `spending_rules.SpendingRuleOutcomes` of the year counts."""
+        from . import distributed as D
+        from .spending_rules import SpendingBands, SpendingRuleOutcomes
+
+        n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
+        if n <= 0:
+            raise ValueError("spending_rule_fan_chart needs at least one path")
+        params = self._current_params()
+        rng = self._batch_rng(n)
+        if D.is_active():
+            yb = D.run_sharded_year_bins(params, rng, self._stream_id, n, int(working_months), edges, wr_edges, rule=rule, m_edges=m_edges)
+        else:
+            import torch
+
+            with torch.cuda.device(self._local_device()):
+                yb = D.run_sharded_year_bins(params, rng, self._stream_id, n, int(working_months), edges, wr_edges, rule=rule, m_edges=m_edges)
+        yb["spending"] = SpendingBands(yb["multiplier_bins"], yb["m_edges"], float(params.monthly_expenses))
+        yb["outcomes"] = SpendingRuleOutcomes(int(yb["counters"][0]), n, yb["rule_year_counts"],
+                                              retirement_age(self.params_model.current_age, int(working_months)))
+        return yb
+
     def find_maximum_initial_expenses(
         self,
         working_months: int,

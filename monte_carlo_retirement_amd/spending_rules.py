@@ -180,3 +180,47 @@ class SpendingRuleOutcomes:
         if self.ever_cut is not None:
             doc["ever_cut_share"] = self.ever_cut_share
         return doc
+
+
+SPENDING_QUANTILES = (0.05, 0.25, 0.50, 0.75, 0.95)
+
+
+class SpendingBands:
+    """The spending fan chart of a launch under a rule: per retirement year the 5 / 25 / 50 / 75 / 95 % REAL monthly spending
+    ``monthly_expenses * m`` among the paths that begin the year alive, from ``multiplier_bins`` ``[retirement_years,
+    n_m_bins + 2]`` binned on ``m_edges`` (``mcr_run_rule_year_bins_rng``).  ``estimate`` is the rank-interpolated value and
+    ``lo`` / ``hi`` the bracket that contains the exact quantile (`aggregation.bands_from_bins`), each ``[retirement_years,
+    5]``, scaled by the base ``monthly_expenses``; a year nobody begins is NaN, and a side outside the edges is infinite."""
+
+    def __init__(self, multiplier_bins, m_edges, monthly_expenses: float, quantiles: Sequence[float] = SPENDING_QUANTILES):
+        from . import aggregation as A
+
+        self.multiplier_bins = np.asarray(multiplier_bins)
+        self.m_edges = np.asarray(m_edges, dtype=np.float64)
+        if self.multiplier_bins.ndim != 2 or self.multiplier_bins.shape[1] != self.m_edges.shape[0] + 1:
+            raise ValueError(f"multiplier_bins must be [retirement_years, n_m_bins + 2] for {self.m_edges.shape[0]} edges, "
+                             f"got shape {self.multiplier_bins.shape}")
+        self.monthly_expenses = float(monthly_expenses)
+        if not (np.isfinite(self.monthly_expenses) and self.monthly_expenses >= 0.0):
+            raise ValueError("monthly_expenses must be finite and >= 0")
+        self.quantiles = tuple(float(q) for q in quantiles)
+        lo, hi, est = A.bands_from_bins(self.multiplier_bins, self.m_edges, list(self.quantiles))
+        self.multiplier_lo, self.multiplier_hi, self.multiplier_estimate = lo, hi, est
+        self.lo, self.hi, self.estimate = lo * self.monthly_expenses, hi * self.monthly_expenses, est * self.monthly_expenses
+        self.alive = self.multiplier_bins.sum(axis=1).astype(np.int64)
+
+    @property
+    def retirement_years(self) -> int:
+        return int(self.multiplier_bins.shape[0])
+
+    def years(self) -> List[Dict[str, object]]:
+        """Per year: ``alive`` paths and ``{"p50": {"estimate", "lo", "hi"}, ...}``; non-finite values are None."""
+        def num(v):
+            return float(v) if np.isfinite(v) else None
+        out = []
+        for y in range(self.retirement_years):
+            row: Dict[str, object] = {"year": y, "alive": int(self.alive[y])}
+            for j, q in enumerate(self.quantiles):
+                row[f"p{int(round(q * 100))}"] = {"estimate": num(self.estimate[y, j]), "lo": num(self.lo[y, j]), "hi": num(self.hi[y, j])}
+            out.append(row)
+        return out
