@@ -561,7 +561,11 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     // from a bound: it cannot read the count without a synchronisation).  Last, with a default: every other instantiation
     // keeps its instruction stream.
     static_assert(!LIST || (MODE == 0 && RNG == (int)MCR_RNG_PHILOX && !ANNUAL && !INJ && PHASE == 0 && !XS), "path lists exist for the whole-path count-only Philox launches, split or not");
-    // NPROD = 2 (the re-run of a screened launch whose expected list is latency-bound, under MCR_K1_RERUN_PRODUCERS=2): the SPLIT form
+    // The split LIST kernels (either NPROD) run in the launch's stream and month forms: screen_qualified gives every screened
+    // launch kStreamsInRegs, so the consumer fills StreamRegs once (the producers have returned by then) and its month tests
+    // two windows against wm + rmi; MF follows month_form_qualified; and the month is the straight-line one (MM below).  Re-run
+    // of 10^6 config.json paths, 256-path form 0.588 -> 0.515 ms, 64-path form 0.498 -> 0.456 ms (LABNOTES R30).
+    // NPROD = 2 (the re-run of a screened launch whose expected list is at most kRerunTwoProducersMaxList paths, or MCR_K1_RERUN_PRODUCERS=2): the SPLIT form
     // on ONE 64-path block per workgroup, one consumer wave and TWO producer waves (192 threads).  A short list then spreads
     // over every CU, about a wave to a SIMD, and the consumer no longer waits for its producer: producer 0 stages every HALF 0
     // of the path, producer 1 every HALF 1 (growth_rows2_own_half), each with two barrier intervals for its pair.  The stage
@@ -590,7 +594,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     constexpr bool kExpFan = PHASE == 5 || PHASE == 6;    // expense fan-out: the levels are monthly_expenses, resumed at retirement
     constexpr bool kConFan = PHASE == 7;                  // contribution fan-out: the levels are monthly_contribution, the whole path
     constexpr bool kAsmFan = PHASE == 9;                  // assumption fan-out: the scenario fan-out with the market per wave as well
-    constexpr bool kStreamRegs = SPLIT && !kAsmFan;       // the first two income streams stay in SGPRs for the whole launch (S0, S1 below)
+    constexpr bool kStreamRegs = SPLIT && !kAsmFan && !(LIST && (SF & kStreamsInRegs) != 0);   // the first two income streams stay in SGPRs for the whole launch (S0, S1 below; the split re-run's stream form keeps StreamRegs instead)
     constexpr bool kIncFan = PHASE == 10;                 // income fan-out: the scenario fan-out with one income stream per wave as well
     constexpr bool kRuleFan = PHASE == 11;                // rule fan-out: the scenario fan-out with a spending rule per wave as well
     constexpr bool kScnFan = PHASE == 8 || kAsmFan || kIncFan || kRuleFan;   // scenario fan-out: balance, contribution and spending per wave, the whole path
@@ -628,16 +632,16 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     // MF: the launch's month form (mcr_device.h: kMonthEqualRates; masks 0 and 1), for the kernels that have growth forms.  Behind
     // GF, with a default, for the same reason.
     static_assert(MF == 0 || MF == kMonthEqualRates, "month forms: masks 0 and 1");
-    static_assert(MF == 0 || (MODE == 0 && RNG == (int)MCR_RNG_PHILOX && !ANNUAL && !INJ && (PHASE == 0 || PHASE == 3) && !SPLIT && !XS && !EXACT),
-                  "month forms exist for the kernels that have growth forms, in the tolerance form of the month");
+    static_assert(MF == 0 || (MODE == 0 && RNG == (int)MCR_RNG_PHILOX && !ANNUAL && !INJ && (PHASE == 0 || PHASE == 3) && (!SPLIT || LIST) && !XS && !EXACT),
+                  "month forms exist for the kernels that have growth forms and for the split re-run of a screened launch, in the tolerance form of the month");
     static_assert(!(MF & kMonthEqualRates) || TAXED == 3, "equal realized-gains rates: both assets are taxed");
     constexpr bool EQR = (MF & kMonthEqualRates) != 0;
     // SF: the launch's stream form (mcr_device.h: kStreamsInRegs; masks 0 and 1), for the same kernels.  Behind MF, with a default.
     static_assert(SF == 0 || SF == kStreamsInRegs, "stream forms: masks 0 and 1");
-    static_assert(SF == 0 || (MODE == 0 && RNG == (int)MCR_RNG_PHILOX && !ANNUAL && !INJ && (PHASE == 0 || PHASE == 3) && !SPLIT && !XS && !EXACT),
-                  "stream forms exist for the kernels that have growth forms, in the tolerance form of the month");
+    static_assert(SF == 0 || (MODE == 0 && RNG == (int)MCR_RNG_PHILOX && !ANNUAL && !INJ && (PHASE == 0 || PHASE == 3) && (!SPLIT || LIST) && !XS && !EXACT),
+                  "stream forms exist for the kernels that have growth forms and for the split re-run of a screened launch, in the tolerance form of the month");
     constexpr bool TOL = !EXACT;         // the month in its tolerance form (mcr_device.h: "TOLERANCE FORM of the month")
-    constexpr bool MM = !SPLIT || kFan || NPROD == 2;  // exec-masked moves (issue-bound launches, and the lone consumer wave of NPROD = 2) vs the compiler's selects (latency-bound SPLIT launches): MCR_MASKED_MOVE, mcr_device.h
+    constexpr bool MM = !SPLIT || kFan || NPROD == 2 || LIST;  // exec-masked moves (issue-bound launches, and the consumer waves of a screened launch's re-run, either form) vs the compiler's selects (the lone probes' latency-bound SPLIT launches): MCR_MASKED_MOVE, mcr_device.h
     // the tolerance month's dust / empty fix-ups tested once per wave (mcr_device.h: WAVE-UNIFORM fix-ups), issue-bound launches only
     constexpr bool kFastMonth = TOL && MM && kUniformFixups;
     constexpr int kPaths = (kFan || NPROD == 2) ? 64 : kBlock;   // paths of a workgroup = columns of every per-path LDS array
@@ -1210,6 +1214,10 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
                     if (P.n_streams > 1) stream_income(S1);
                     s = 2;
                 }
+                if constexpr (kSIR && SPLIT && LIST) {   // the split re-run: the same two tests on the month's own row (it keeps no running counters)
+                    if ((unsigned)(wm + rmi - SR.s0) < SR.n0) { asm volatile(""); income = __builtin_fma(-SR.a0, price, income); }
+                    if ((unsigned)(wm + rmi - SR.s1) < SR.n1) { asm volatile(""); income = __builtin_fma(-SR.a1, price, income); }
+                } else
                 if constexpr (kSIR) {   // the whole list: two indexed records in SGPRs, the same FMAs in list order
                     // (wave-uniform: scalar branches, not selects; one unsigned compare tests both ends of a window)
                     if ((unsigned)(SC.row - SR.s0) < SR.n0) { asm volatile(""); income = __builtin_fma(-SR.a0, price, income); }
@@ -2724,10 +2732,15 @@ static const char* const kClassicKnobs[] = {"MCR_K1_SEGMENTS", "MCR_K1_SEGMENTS_
                                             "MCR_K1_GROWTH_FORM", "MCR_K1_MONTH_FORM", "MCR_K1_STREAM_FORM"};
 // Producer waves per consumer wave of the re-run's producer / consumer form: 1 = the 256-path workgroup of the lone probes
 // (four consumer and four producer waves), 2 = one 64-path block per workgroup with one consumer and two producer waves
-// (path_kernel's NPROD).  MCR_K1_RERUN_PRODUCERS, read at every launch.
-constexpr int kRerunProducersDefault = 1;     // (the 64-path form gains 0.085 ms of a 10^6-path step: under the bar set for a new default, LABNOTES R25)
-static int rerun_producers_of(int* producers) {
-    *producers = kRerunProducersDefault;
+// (path_kernel's NPROD).  MCR_K1_RERUN_PRODUCERS, read at every launch, forces one; left alone, a launch whose EXPECTED list
+// (n x MCR_K1_SCREEN_EXPECTED) is at most kRerunTwoProducersMaxList paths takes the 64-path form and every other one the
+// 256-path form.  The limit is the largest measured size at which the 64-path form is not the slower one: faster by 0.11 ms
+// at 250 000 and 500 000 paths, by 0.058 ms of the re-run at 10^6, SLOWER by 0.09 ms at 2 10^6 (LABNOTES R30; nothing was
+// measured between the last two, so the limit stands at the lower).  `expected_list` < 0: the caller only validates the knob.
+constexpr int kRerunProducersDefault = 1;
+constexpr double kRerunTwoProducersMaxList = 80000.0;     // = 10^6 paths x the default MCR_K1_SCREEN_EXPECTED
+static int rerun_producers_of(int* producers, double expected_list = -1.0) {
+    *producers = (expected_list >= 0.0 && expected_list <= kRerunTwoProducersMaxList) ? 2 : kRerunProducersDefault;
     if (const char* e = std::getenv("MCR_K1_RERUN_PRODUCERS"); e && *e) {
         if ((e[0] != '1' && e[0] != '2') || e[1] != '\0') { set_error("MCR_K1_RERUN_PRODUCERS=%s: 1 (the 256-path form) or 2 (64 paths, two producer waves)", e); return MCR_ERR_INVALID_ARG; }
         *producers = e[0] - '0';
@@ -2802,11 +2815,12 @@ static void launch_screen_kernel(const DevParams& d, const ScreenParams& sp, con
 // behind the re-run.  The host never reads the count: the re-run's grid is sized from the bound ceil(n / 256) (ceil(n / 64)
 // for the 64-path form), and its workgroups beyond the count return at once.  The re-run takes a producer / consumer form
 // when the EXPECTED list (n x MCR_K1_SCREEN_EXPECTED) is a latency-bound launch: the 64-path form with two producer waves, or
-// the 256-path one (MCR_K1_RERUN_PRODUCERS).  MCR_ERR_UNSUPPORTED: the allocation was refused, nothing enqueued.
+// the 256-path one (rerun_producers_of), both in the launch's stream and month forms (screen_qualified gives every screened
+// launch the stream form).  MCR_ERR_UNSUPPORTED: the allocation was refused, nothing enqueued.
 static int launch_screened(DevParams d, KernelIO io, hipStream_t stream) {
     const uint64_t n = io.n_paths;
     int producers = 1;
-    int rc = rerun_producers_of(&producers);
+    int rc = rerun_producers_of(&producers, (double)n * screen_expected());
     if (rc != MCR_OK) return rc;
     StreamAlloc mem(stream);
     if (!mem.alloc(4 * (size_t)n + 8)) return MCR_ERR_UNSUPPORTED;
@@ -2830,22 +2844,27 @@ static int launch_screened(DevParams d, KernelIO io, hipStream_t stream) {
     if (rc != MCR_OK) return rc;
     io.path_list = list; io.path_list_count = count;
     const DevParams* const no_cand = nullptr;
+    const int mf = month_form_qualified(d);
     if (split && producers == 2) {
         // the grid's bound is ceil(n / 64) workgroups of one 64-path block; those beyond the count return at once
         const dim3 grid64((unsigned)((n + 63) / 64));
         for_tax_variant(d, [&](auto T, auto A) {
-            if constexpr (!decltype(A)::value)
-                hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, false, false, 0, true, false, kExactMonthDefault, 0, 0, 0, false, true, 2>),
-                                   grid64, dim3(3 * 64), lds, stream, d, io, no_cand);
+            if constexpr (!decltype(A)::value && !kExactMonthDefault)
+                for_month_form<decltype(T)::value>(mf, [&](auto F) {
+                    hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, false, false, 0, true, false, false, 0, decltype(F)::value, kStreamsInRegs, false, true, 2>),
+                                       grid64, dim3(3 * 64), lds, stream, d, io, no_cand);
+                });
         });
     } else if (split) {
         for_tax_variant(d, [&](auto T, auto A) {
-            if constexpr (!decltype(A)::value)
-                hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, false, false, 0, true, false, kExactMonthDefault, 0, 0, 0, false, true>),
-                                   grid, dim3(2 * kBlock), lds, stream, d, io, no_cand);
+            if constexpr (!decltype(A)::value && !kExactMonthDefault)
+                for_month_form<decltype(T)::value>(mf, [&](auto F) {
+                    hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, false, false, 0, true, false, false, 0, decltype(F)::value, kStreamsInRegs, false, true>),
+                                       grid, dim3(2 * kBlock), lds, stream, d, io, no_cand);
+                });
         });
     } else {
-        const int gf = growth_form_qualified(d), mf = month_form_qualified(d);
+        const int gf = growth_form_qualified(d);
         for_tax_variant(d, [&](auto T, auto A) {
             if constexpr (!decltype(A)::value && !kExactMonthDefault)
                 for_growth_form(gf, [&](auto G) {
