@@ -3570,13 +3570,47 @@ static void set_fan_rows(KernelIO& fio, const mcr_option_outcomes* rows, int fir
     fio.fan_rows.years_to_ruin = rows->years_to_ruin ? rows->years_to_ruin + (size_t)first * (size_t)rows->path_stride : nullptr;
 }
 
-// Several (initial_balance, monthly_contribution, monthly_expenses) records over the same paths, Philox stream: scenario fan-out
-// launches (PHASE 8) over groups of at most fanout_max_levels records, the whole path each, like the contribution fan-out.
-// The records go to ONE stream-ordered device table (SnapshotBlock's records, no snapshot column), filled with one async
-// copy and released behind the launches; group g's launch gets the table at its first record through `cand_params`.
-// Nothing derive_params, the lock-slot plan or the tax variant reads depends on the three fields (they are copied through),
-// so one parameter block serves every record.  Returns MCR_ERR_UNSUPPORTED, having enqueued nothing, for shapes this form
-// does not cover and when the table's allocation is refused.
+// The record fan-outs (PHASE 8 .. 11: scenarios, assumptions, income options, spending rules) share this skeleton: fan-out
+// launches over groups of at most `lmax` records, the whole path each, like the contribution fan-out.  The records (`host`, as
+// the kernel reads them) go to ONE stream-ordered device table (SnapshotBlock's records, no snapshot column), filled with one
+// async copy and released behind the launches; group g's launch gets the table at its first record through `cand_params`, its
+// counters, masks and rows at that record, and whatever `launch(fio, first, grid, block, lds, table)` adds before it launches
+// the family's kernel.  One parameter block `d` (plan_level_fanout's) serves every record: each family says below why.
+// `launches`, where given, counts the launches and is reset when they report an error; `what` names the probe in HIP errors.
+// Returns MCR_ERR_UNSUPPORTED, having enqueued nothing, when the table's allocation is refused.
+template <typename Record, typename Launch>
+static int launch_record_fanout(const DevParams& d, int lmax, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                                const Record* host, int32_t n_records, uint64_t* counts, hipStream_t stream, uint64_t* masks,
+                                const mcr_option_outcomes* rows, int* launches, const char* what, Launch&& launch) {
+    KernelIO io = make_io(rng, nullptr, stream_id, path_begin, n_paths);
+    SnapshotBlock table(stream);
+    hipError_t e = hipSuccess;
+    if (!table.attach(io, 0, host, (size_t)n_records * sizeof(Record), &e, SIZE_MAX)) return MCR_ERR_UNSUPPORTED;
+    io.snap = nullptr;   // (no snapshot column: the block is the table alone)
+    if (e == hipSuccess) {
+        const Record* d_table = (const Record*)table.records;
+        const dim3 grid((unsigned)((n_paths + 63) / 64));
+        LevelGroups(n_records, lmax).for_each([&](int, int first, int lg) {
+            KernelIO fio = io;
+            fio.out.counters = counts + (size_t)first * MCR_N_COUNTERS;
+            fio.fan_n = lg;
+            fio.fan_masks = masks ? masks + (size_t)first * ((n_paths + 63) / 64) : nullptr;
+            set_fan_rows(fio, rows, first);
+            launch(fio, first, grid, dim3(64 * (lg + 1)), fanout_dynamic_lds(d, lg), (const DevParams*)(d_table + first));
+            if (launches) ++*launches;
+        });
+        e = hipGetLastError();
+    }
+    const hipError_t ef = table.mem.release();
+    if (e != hipSuccess && launches) *launches = 0;
+    if (e != hipSuccess) return hip_fail(e, what);
+    if (ef != hipSuccess) return hip_fail(ef, (std::string(what) + " (free)").c_str());
+    return MCR_OK;
+}
+
+// Several (initial_balance, monthly_contribution, monthly_expenses) records over the same paths, Philox stream (PHASE 8).  The
+// records are the table as they come.  Nothing derive_params, the lock-slot plan or the tax variant reads depends on the three
+// fields (they are copied through).  Returns MCR_ERR_UNSUPPORTED, having enqueued nothing, for shapes this form does not cover.
 static int probe_scenarios_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
                                   int32_t wm, const mcr_scenario* scenarios, int32_t n_scenarios, uint64_t* counts, hipStream_t stream,
                                   uint64_t* masks = nullptr /* joint probes: KernelIO::fan_masks of the whole option list */,
@@ -3584,44 +3618,24 @@ static int probe_scenarios_fanout(const mcr_params* p, const mcr_rng* rng, uint3
     DevParams d;
     int lmax = 0;
     if (int rc = plan_level_fanout(p, rng, n_paths, wm, n_scenarios, fanout_min_waves("MCR_SCENARIO_FANOUT_MIN_WAVES"), &d, &lmax)) return rc;
-    KernelIO io = make_io(rng, nullptr, stream_id, path_begin, n_paths);
-    SnapshotBlock table(stream);
-    hipError_t e = hipSuccess;
-    if (!table.attach(io, 0, scenarios, (size_t)n_scenarios * sizeof(mcr_scenario), &e, SIZE_MAX)) return MCR_ERR_UNSUPPORTED;
-    io.snap = nullptr;   // (no snapshot column: the block is the table alone)
-    if (e == hipSuccess) {
-        const mcr_scenario* d_table = (const mcr_scenario*)table.records;
-        const dim3 grid((unsigned)((n_paths + 63) / 64));
-        const LevelGroups groups(n_scenarios, lmax);
+    return launch_record_fanout(d, lmax, rng, stream_id, path_begin, n_paths, scenarios, n_scenarios, counts, stream, masks, rows, nullptr,
+                                "scenario fan-out probe", [&](const KernelIO& fio, int, dim3 grid, dim3 block, size_t lds, const DevParams* table) {
         for_tax_variant(d, [&](auto T, auto A) {
-            groups.for_each([&](int, int first, int lg) {
-                KernelIO fio = io;
-                fio.out.counters = counts + (size_t)first * MCR_N_COUNTERS;
-                fio.fan_n = lg;
-                fio.fan_masks = masks ? masks + (size_t)first * ((n_paths + 63) / 64) : nullptr;
-                set_fan_rows(fio, rows, first);
-                for_bool(rows != nullptr, [&](auto O) {
-                    hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 8, true, false, kExactMonthDefault, 0, 0, 0, decltype(O)::value>),
-                                       grid, dim3(64 * (lg + 1)), fanout_dynamic_lds(d, lg), stream, d, fio, (const DevParams*)(d_table + first));
-                });
+            for_bool(rows != nullptr, [&](auto O) {
+                hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 8, true, false, kExactMonthDefault, 0, 0, 0, decltype(O)::value>),
+                                   grid, block, lds, stream, d, fio, table);
             });
         });
-        e = hipGetLastError();
-    }
-    const hipError_t ef = table.mem.release();
-    if (e != hipSuccess) return hip_fail(e, "scenario fan-out probe");
-    if (ef != hipSuccess) return hip_fail(ef, "scenario fan-out probe (free)");
-    return MCR_OK;
+    });
 }
 
 // Several records of (initial_balance, monthly_contribution, monthly_expenses, the market's seven lognormal parameters) over the
-// same paths, Philox stream: assumption fan-out launches (PHASE 9) over groups of at most fanout_max_levels(parts) records, the
-// whole path each.  The records are derived on the host (derive_market: the bits derive_params gives a block with those seven
-// fields) into ONE stream-ordered device table, as the scenario fan-out's.  Of everything the host derives from the parameter
-// block only a1 .. binf_rho_c, rho and rho_c depend on the seven fields, and the kernel reads them in growth_rows2 alone —
-// which PHASE 9's consumers replace by their record's; the tax variant, needs_generic_variant, the lock-slot plan, the kept
-// streams and the barrier counts read none of the ten fields, so one parameter block serves every record.  Returns
-// MCR_ERR_UNSUPPORTED, having enqueued nothing, for shapes this form does not cover and when the table's allocation is refused.
+// same paths, Philox stream (PHASE 9, groups of at most fanout_max_levels(parts) records).  The records are derived on the host
+// (derive_market: the bits derive_params gives a block with those seven fields).  Of everything the host derives from the
+// parameter block only a1 .. binf_rho_c, rho and rho_c depend on the seven fields, and the kernel reads them in growth_rows2
+// alone — which PHASE 9's consumers replace by their record's; the tax variant, needs_generic_variant, the lock-slot plan, the
+// kept streams and the barrier counts read none of the ten fields.  Returns MCR_ERR_UNSUPPORTED, having enqueued nothing, for
+// shapes this form does not cover.
 static thread_local int g_last_assumption_fanout_launches = 0;   // (mcr_probe_assumptions_last_fanout_launches)
 static int probe_assumptions_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
                                     int32_t wm, const mcr_assumptions* records, int32_t n_records, uint64_t* counts, hipStream_t stream,
@@ -3638,47 +3652,25 @@ static int probe_assumptions_fanout(const mcr_params* p, const mcr_rng* rng, uin
         host[(size_t)k] = AssumptionRecord{r.initial_balance, r.monthly_contribution, r.monthly_expenses,
                                            mk.a1, mk.b1, mk.ainf, mk.binf_rho, mk.binf_rho_c, mk.aprem, mk.bprem};
     }
-    KernelIO io = make_io(rng, nullptr, stream_id, path_begin, n_paths);
-    SnapshotBlock table(stream);
-    hipError_t e = hipSuccess;
-    if (!table.attach(io, 0, host.data(), host.size() * sizeof(AssumptionRecord), &e, SIZE_MAX)) return MCR_ERR_UNSUPPORTED;
-    io.snap = nullptr;   // (no snapshot column: the block is the table alone)
-    if (e == hipSuccess) {
-        const AssumptionRecord* d_table = (const AssumptionRecord*)table.records;
-        const dim3 grid((unsigned)((n_paths + 63) / 64));
-        const LevelGroups groups(n_records, lmax);
+    return launch_record_fanout(d, lmax, rng, stream_id, path_begin, n_paths, host.data(), n_records, counts, stream, masks, rows,
+                                &g_last_assumption_fanout_launches, "assumption fan-out probe",
+                                [&](const KernelIO& fio, int, dim3 grid, dim3 block, size_t lds, const DevParams* table) {
         for_tax_variant(d, [&](auto T, auto A) {
-            groups.for_each([&](int, int first, int lg) {
-                KernelIO fio = io;
-                fio.out.counters = counts + (size_t)first * MCR_N_COUNTERS;
-                fio.fan_n = lg;
-                fio.fan_masks = masks ? masks + (size_t)first * ((n_paths + 63) / 64) : nullptr;
-                set_fan_rows(fio, rows, first);
-                for_bool(rows != nullptr, [&](auto O) {
-                    hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 9, true, false, kExactMonthDefault, 0, 0, 0, decltype(O)::value>),
-                                       grid, dim3(64 * (lg + 1)), fanout_dynamic_lds(d, lg), stream, d, fio, (const DevParams*)(d_table + first));
-                });
-                ++g_last_assumption_fanout_launches;
+            for_bool(rows != nullptr, [&](auto O) {
+                hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 9, true, false, kExactMonthDefault, 0, 0, 0, decltype(O)::value>),
+                                   grid, block, lds, stream, d, fio, table);
             });
         });
-        e = hipGetLastError();
-    }
-    const hipError_t ef = table.mem.release();
-    if (e != hipSuccess) g_last_assumption_fanout_launches = 0;
-    if (e != hipSuccess) return hip_fail(e, "assumption fan-out probe");
-    if (ef != hipSuccess) return hip_fail(ef, "assumption fan-out probe (free)");
-    return MCR_OK;
+    });
 }
 
-// Several versions of ONE income stream (and of the scenario fan-out's three fields) over the same paths, Philox stream: income
-// fan-out launches (PHASE 10) over groups of at most fanout_max_levels records, the whole path each.  The records are derived on
-// the host (derive_stream: the bits derive_params gives a block whose stream has those fields) into ONE stream-ordered device
-// table, as the scenario fan-out's.  The parameter block is derived with the probed stream KEPT whatever its own amount
-// (derive_params' keep_index), so the kernel has a record to replace at the stream's list position and, for a frozen stream, a
-// lock column per consumer wave; the stream's keep, indexed and lock_slot are the list's own for every record, and nothing else
-// derive_params, the lock-slot plan or the tax variant reads depends on the six fields: one parameter block serves every record.
-// Returns MCR_ERR_UNSUPPORTED, having enqueued nothing, for shapes this form does not cover and when the table's allocation is
-// refused.
+// Several versions of ONE income stream (and of the scenario fan-out's three fields) over the same paths, Philox stream (PHASE
+// 10).  The records are derived on the host (derive_stream: the bits derive_params gives a block whose stream has those fields).
+// The parameter block is derived with the probed stream KEPT whatever its own amount (derive_params' keep_index), so the kernel
+// has a record to replace at the stream's list position and, for a frozen stream, a lock column per consumer wave; the stream's
+// keep, indexed and lock_slot are the list's own for every record, and nothing else derive_params, the lock-slot plan or the tax
+// variant reads depends on the six fields.  Returns MCR_ERR_UNSUPPORTED, having enqueued nothing, for shapes this form does not
+// cover.
 static thread_local int g_last_income_fanout_launches = 0;   // (mcr_probe_income_last_fanout_launches)
 static int probe_income_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
                                int32_t wm, int32_t stream_index, const mcr_income_option* options, int32_t n_options, uint64_t* counts,
@@ -3699,46 +3691,24 @@ static int probe_income_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t
         const DevStreamWindow w = derive_stream(p->current_age, wm, r.monthly_amount_today, own.tax_rate, r.start_at_age, r.duration_years);
         host[(size_t)k] = IncomeRecord{r.initial_balance, r.monthly_contribution, r.monthly_expenses, w.amount, w.amount_keep, w.start_month, w.end_month};
     }
-    KernelIO io = make_io(rng, nullptr, stream_id, path_begin, n_paths);
-    SnapshotBlock table(stream);
-    hipError_t e = hipSuccess;
-    if (!table.attach(io, 0, host.data(), host.size() * sizeof(IncomeRecord), &e, SIZE_MAX)) return MCR_ERR_UNSUPPORTED;
-    io.snap = nullptr;   // (no snapshot column: the block is the table alone)
-    if (e == hipSuccess) {
-        const IncomeRecord* d_table = (const IncomeRecord*)table.records;
-        const dim3 grid((unsigned)((n_paths + 63) / 64));
-        const LevelGroups groups(n_options, lmax);
+    return launch_record_fanout(d, lmax, rng, stream_id, path_begin, n_paths, host.data(), n_options, counts, stream, masks, rows,
+                                &g_last_income_fanout_launches, "income fan-out probe",
+                                [&](KernelIO& fio, int, dim3 grid, dim3 block, size_t lds, const DevParams* table) {
+        fio.fan_stream = kept_k;
         for_tax_variant(d, [&](auto T, auto A) {
-            groups.for_each([&](int, int first, int lg) {
-                KernelIO fio = io;
-                fio.out.counters = counts + (size_t)first * MCR_N_COUNTERS;
-                fio.fan_n = lg;
-                fio.fan_masks = masks ? masks + (size_t)first * ((n_paths + 63) / 64) : nullptr;
-                fio.fan_stream = kept_k;
-                set_fan_rows(fio, rows, first);
-                for_bool(rows != nullptr, [&](auto O) {
-                    hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 10, true, false, kExactMonthDefault, 0, 0, 0, decltype(O)::value>),
-                                       grid, dim3(64 * (lg + 1)), fanout_dynamic_lds(d, lg), stream, d, fio, (const DevParams*)(d_table + first));
-                });
-                ++g_last_income_fanout_launches;
+            for_bool(rows != nullptr, [&](auto O) {
+                hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 10, true, false, kExactMonthDefault, 0, 0, 0, decltype(O)::value>),
+                                   grid, block, lds, stream, d, fio, table);
             });
         });
-        e = hipGetLastError();
-    }
-    const hipError_t ef = table.mem.release();
-    if (e != hipSuccess) g_last_income_fanout_launches = 0;
-    if (e != hipSuccess) return hip_fail(e, "income fan-out probe");
-    if (ef != hipSuccess) return hip_fail(ef, "income fan-out probe (free)");
-    return MCR_OK;
+    });
 }
 
-// Several (initial_balance, monthly_contribution, monthly_expenses, spending rule) options over the same paths, Philox stream:
-// rule fan-out launches (PHASE 11) over groups of at most fanout_max_levels records, the whole path each.  The records are made
-// on the host (keep = 1 - cut, grow = 1 + raise: launch_rule's two operations) into ONE stream-ordered device table, as the
-// scenario fan-out's.  The kernels are the generic tax mask's (TAXED = 3), like the plain rule launch's: a zero-rate asset's
-// arithmetic is exact zeros there.  Group g's launch counts the years of its options into year_counts at its first option.
-// Returns MCR_ERR_UNSUPPORTED, having enqueued nothing, for shapes this form does not cover and when the table's allocation
-// is refused.
+// Several (initial_balance, monthly_contribution, monthly_expenses, spending rule) options over the same paths, Philox stream
+// (PHASE 11).  The records are made on the host (keep = 1 - cut, grow = 1 + raise: launch_rule's two operations).  The kernels
+// are the generic tax mask's (TAXED = 3), like the plain rule launch's: a zero-rate asset's arithmetic is exact zeros there.
+// Group g's launch counts the years of its options into year_counts at its first option.  Returns MCR_ERR_UNSUPPORTED, having
+// enqueued nothing, for shapes this form does not cover.
 static thread_local int g_last_rule_fanout_launches = 0;   // (mcr_probe_rules_last_fanout_launches)
 static int probe_rules_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
                               int32_t wm, const mcr_rule_option* options, int32_t n_options, uint64_t* counts, uint64_t* year_counts,
@@ -3753,38 +3723,35 @@ static int probe_rules_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t 
         host[(size_t)k] = RuleRecord{r.initial_balance, r.monthly_contribution, r.monthly_expenses,
                                      r.rule.upper, r.rule.lower, 1.0 - r.rule.cut, 1.0 + r.rule.raise, r.rule.floor, r.rule.ceiling};
     }
-    KernelIO io = make_io(rng, nullptr, stream_id, path_begin, n_paths);
-    SnapshotBlock table(stream);
-    hipError_t e = hipSuccess;
-    if (!table.attach(io, 0, host.data(), host.size() * sizeof(RuleRecord), &e, SIZE_MAX)) return MCR_ERR_UNSUPPORTED;
-    io.snap = nullptr;   // (no snapshot column: the block is the table alone)
-    if (e == hipSuccess) {
-        const RuleRecord* d_table = (const RuleRecord*)table.records;
-        const dim3 grid((unsigned)((n_paths + 63) / 64));
-        const LevelGroups groups(n_options, lmax);
+    return launch_record_fanout(d, lmax, rng, stream_id, path_begin, n_paths, host.data(), n_options, counts, stream, masks, rows,
+                                &g_last_rule_fanout_launches, "rule fan-out probe",
+                                [&](KernelIO& fio, int first, dim3 grid, dim3 block, size_t lds, const DevParams* table) {
+        // (fan_rule.rows are fan_rows' bytes, which the skeleton has set; the rest of the block is make_io's zeros)
+        fio.fan_rule.year_counts = year_counts ? (unsigned long long*)year_counts + (size_t)first * (size_t)d.retirement_years * MCR_RULE_N_COUNTS : nullptr;
         for_bool(d.any_annual_tax, [&](auto A) {
-            groups.for_each([&](int, int first, int lg) {
-                KernelIO fio = io;
-                fio.out.counters = counts + (size_t)first * MCR_N_COUNTERS;
-                fio.fan_n = lg;
-                fio.fan_masks = masks ? masks + (size_t)first * ((n_paths + 63) / 64) : nullptr;
-                fio.fan_rule = KernelIO::FanRuleRows{};
-                set_fan_rows(fio, rows, first);
-                fio.fan_rule.year_counts = year_counts ? (unsigned long long*)year_counts + (size_t)first * (size_t)d.retirement_years * MCR_RULE_N_COUNTS : nullptr;
-                for_bool(rows != nullptr, [&](auto O) {
-                    hipLaunchKernelGGL((path_kernel<0, 0, 3, decltype(A)::value, false, 11, true, false, kExactMonthDefault, 0, 0, 0, decltype(O)::value, false, 1, true>),
-                                       grid, dim3(64 * (lg + 1)), fanout_dynamic_lds(d, lg), stream, d, fio, (const DevParams*)(d_table + first));
-                });
-                ++g_last_rule_fanout_launches;
+            for_bool(rows != nullptr, [&](auto O) {
+                hipLaunchKernelGGL((path_kernel<0, 0, 3, decltype(A)::value, false, 11, true, false, kExactMonthDefault, 0, 0, 0, decltype(O)::value, false, 1, true>),
+                                   grid, block, lds, stream, d, fio, table);
             });
         });
-        e = hipGetLastError();
+    });
+}
+
+// The three amounts every probe record carries (validate_params' rule for each), of record `k` of the list `list` names.
+template <typename Record>
+static bool amounts_valid(const char* list, int32_t k, const Record& r) {
+    static const struct { double Record::*field; const char* name; int config_line; } kAmounts[3] = {
+        {&Record::initial_balance, "initial_balance", 56},
+        {&Record::monthly_contribution, "monthly_contribution", 57},
+        {&Record::monthly_expenses, "monthly_expenses", 59}};
+    for (const auto& f : kAmounts) {
+        const double v = r.*(f.field);
+        if (!(std::isfinite(v) && v >= 0.0)) {
+            set_error("%s[%d].%s = %g: must be finite and >= 0 (config.py:%d)", list, k, f.name, v, f.config_line);
+            return false;
+        }
     }
-    const hipError_t ef = table.mem.release();
-    if (e != hipSuccess) g_last_rule_fanout_launches = 0;
-    if (e != hipSuccess) return hip_fail(e, "rule fan-out probe");
-    if (ef != hipSuccess) return hip_fail(ef, "rule fan-out probe (free)");
-    return MCR_OK;
+    return true;
 }
 
 // A level probe (mcr_probe_expenses_rng / mcr_probe_contributions_rng): n_levels values of one field of the parameter block,
@@ -4194,18 +4161,8 @@ static int probe_scenarios(const mcr_params* p, const mcr_rng* rng, uint32_t str
     if (rc != MCR_OK) return rc;
     rc = check_rng(rng);
     if (rc != MCR_OK) return rc;
-    static const struct { double mcr_scenario::*field; const char* name; int config_line; } kFields[3] = {
-        {&mcr_scenario::initial_balance, "initial_balance", 56},
-        {&mcr_scenario::monthly_contribution, "monthly_contribution", 57},
-        {&mcr_scenario::monthly_expenses, "monthly_expenses", 59}};
     for (int32_t k = 0; k < n_scenarios; ++k)
-        for (const auto& f : kFields) {
-            const double v = scenarios[k].*(f.field);
-            if (!(std::isfinite(v) && v >= 0.0)) {
-                set_error("scenarios[%d].%s = %g: must be finite and >= 0 (config.py:%d)", k, f.name, v, f.config_line);
-                return MCR_ERR_INVALID_ARG;
-            }
-        }
+        if (!amounts_valid("scenarios", k, scenarios[k])) return MCR_ERR_INVALID_ARG;
     rc = zero_counters(counts, (size_t)n_scenarios, main);
     if (rc != MCR_OK) return rc;
     mcr_params q = *p;
@@ -4266,23 +4223,13 @@ static int probe_assumptions(const mcr_params* p, const mcr_rng* rng, uint32_t s
     if (rc != MCR_OK) return rc;
     rc = check_rng(rng);
     if (rc != MCR_OK) return rc;
-    static const struct { double mcr_assumptions::*field; const char* name; int config_line; } kAmounts[3] = {
-        {&mcr_assumptions::initial_balance, "initial_balance", 56},
-        {&mcr_assumptions::monthly_contribution, "monthly_contribution", 57},
-        {&mcr_assumptions::monthly_expenses, "monthly_expenses", 59}};
     static const struct { double mcr_assumptions::*mu; double mcr_assumptions::*sigma; const char* name; } kSeries[3] = {
         {&mcr_assumptions::inv1_mu_log, &mcr_assumptions::inv1_sigma_log, "inv1"},
         {&mcr_assumptions::inf_mu_log, &mcr_assumptions::inf_sigma_log, "inf"},
         {&mcr_assumptions::prem_mu_log, &mcr_assumptions::prem_sigma_log, "prem"}};
     for (int32_t k = 0; k < n_records; ++k) {
         const mcr_assumptions& r = records[k];
-        for (const auto& f : kAmounts) {
-            const double v = r.*(f.field);
-            if (!(std::isfinite(v) && v >= 0.0)) {
-                set_error("records[%d].%s = %g: must be finite and >= 0 (config.py:%d)", k, f.name, v, f.config_line);
-                return MCR_ERR_INVALID_ARG;
-            }
-        }
+        if (!amounts_valid("records", k, r)) return MCR_ERR_INVALID_ARG;
         for (const auto& f : kSeries) {
             const double mu = r.*(f.mu), sg = r.*(f.sigma);
             if (!log_growth_in_domain(mu, sg)) {
@@ -4363,19 +4310,12 @@ static int probe_income(const mcr_params* p, const mcr_rng* rng, uint32_t stream
         set_error("stream_index = %d: must be in [0, n_streams = %d)", stream_index, p->n_streams);
         return MCR_ERR_INVALID_ARG;
     }
-    static const struct { double mcr_income_option::*field; const char* name; int config_line; } kAmounts[4] = {
-        {&mcr_income_option::initial_balance, "initial_balance", 56},
-        {&mcr_income_option::monthly_contribution, "monthly_contribution", 57},
-        {&mcr_income_option::monthly_expenses, "monthly_expenses", 59},
-        {&mcr_income_option::monthly_amount_today, "monthly_amount_today", 18}};
     for (int32_t k = 0; k < n_options; ++k) {
         const mcr_income_option& r = options[k];
-        for (const auto& f : kAmounts) {
-            const double v = r.*(f.field);
-            if (!(std::isfinite(v) && v >= 0.0)) {
-                set_error("options[%d].%s = %g: must be finite and >= 0 (config.py:%d)", k, f.name, v, f.config_line);
-                return MCR_ERR_INVALID_ARG;
-            }
+        if (!amounts_valid("options", k, r)) return MCR_ERR_INVALID_ARG;
+        if (!(std::isfinite(r.monthly_amount_today) && r.monthly_amount_today >= 0.0)) {
+            set_error("options[%d].monthly_amount_today = %g: must be finite and >= 0 (config.py:18)", k, r.monthly_amount_today);
+            return MCR_ERR_INVALID_ARG;
         }
         if (!(std::isfinite(r.start_at_age) && r.start_at_age >= 0.0 && r.start_at_age <= 120.0)) {
             set_error("options[%d].start_at_age = %g: must be finite and in [0, 120] (config.py:23)", k, r.start_at_age);
@@ -4460,18 +4400,8 @@ static int check_rule_probe(const mcr_params* p, const mcr_rng* rng, uint64_t pa
     if (rc != MCR_OK) return rc;
     rc = check_rng(rng);
     if (rc != MCR_OK) return rc;
-    static const struct { double mcr_rule_option::*field; const char* name; int config_line; } kAmounts[3] = {
-        {&mcr_rule_option::initial_balance, "initial_balance", 56},
-        {&mcr_rule_option::monthly_contribution, "monthly_contribution", 57},
-        {&mcr_rule_option::monthly_expenses, "monthly_expenses", 59}};
     for (int32_t k = 0; k < n_options; ++k) {
-        for (const auto& f : kAmounts) {
-            const double v = options[k].*(f.field);
-            if (!(std::isfinite(v) && v >= 0.0)) {
-                set_error("options[%d].%s = %g: must be finite and >= 0 (config.py:%d)", k, f.name, v, f.config_line);
-                return MCR_ERR_INVALID_ARG;
-            }
-        }
+        if (!amounts_valid("options", k, options[k])) return MCR_ERR_INVALID_ARG;
         if (validate_spending_rule(&options[k].rule) != MCR_OK) {
             // "spending rule: <field> = ..." -> "options[k].rule.<field> = ..."
             const std::string msg = g_err;

@@ -11,15 +11,15 @@ balance for 1 100 a month" is one option): the six fields of `INCOME_OPTION_FIEL
 up to ``MCR_MAX_EXPENSE_FANOUT`` options over the same random numbers (`mcr_probe_income_rng`).
 
 The search is a pure function of a ``probe_levels(levels) -> [success %]`` callable, so it runs (and is tested) without a
-GPU.  Its procedure is `nestegg._search`'s bracket-and-refine generator, with the level's key and the event name passed in.
+GPU.  Its procedure is `nestegg`'s (`search.cent_search`), with the level's key and the event name passed in.
 """
 
 from __future__ import annotations
 
 from typing import Callable, List, Optional, Sequence, Union
 
-from .nestegg import _search
-from .spending import SearchResult, _check
+from .nestegg import _steps
+from .search import SearchResult, check, run
 
 #: Highest monthly amount the search tries: `saving.CONTRIBUTION_CAP`'s headroom argument, for money that flows the other
 #: way.  An income of 1e8 a month offsets that much spending; a plan whose target such an income does not reach fails before
@@ -83,12 +83,6 @@ def search_minimum_income_amount(
     income is needed, ``-1.0`` with a ``RuntimeWarning`` when even ``cap`` misses), its probability, and
     ``{"monthly_amount_today", "probability"}`` per evaluated level in evaluation order.  ``on_level`` receives one
     ``"income_amount_search_iter"`` event per evaluated level."""
-    _check(levels_per_call, resolution)
-    gen = _search(target, start, int(levels_per_call), resolution, cap, on_level, key="monthly_amount_today",
-                  event="income_amount_search_iter", what="required-income")
-    try:
-        levels = next(gen)
-        while True:
-            levels = gen.send(probe_levels(levels))
-    except StopIteration as done:
-        return done.value
+    check(levels_per_call, resolution)
+    return run(_steps(target, start, levels_per_call, resolution, cap, on_level, key="monthly_amount_today",
+                      event="income_amount_search_iter", what="required-income"), probe_levels)

@@ -834,22 +834,73 @@ class RetirementMonteCarloSimulator:
 
 
     # ---- maximum-spending search -----------------------------------------------------------------
-    def _level_probabilities(self, engine_probe, working_months: int, levels: Sequence[float],
-                             num_simulations: Optional[int]) -> np.ndarray:
-        """The body of `success_probability_by_expenses` / `..._by_contributions`: `engine_probe` is `E.probe_expenses` or
-        `E.probe_contributions`."""
-        levels = [float(x) for x in levels]
+    def _level_probabilities(self, engine_probe, working_months: int, levels: Sequence, num_simulations: Optional[int],
+                             lead: tuple = ()) -> np.ndarray:
+        """The body of every `success_probability_by_*` whose probe returns counters alone: `engine_probe` is the `engine`
+        function (`E.probe_expenses`, `E.probe_scenarios`, ...), ``levels`` its levels or records and ``lead`` the
+        arguments it takes in front of them (the income probe's stream index)."""
         n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
         wm = int(working_months)
         params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
 
         def probe(path_begin, count, idx):
-            return engine_probe(params, rng, self._stream_id, path_begin, count, wm, [levels[i] for i in idx], device=dev)
+            return engine_probe(params, rng, self._stream_id, path_begin, count, wm, *lead, [levels[i] for i in idx], device=dev)
 
         if not levels:
             return np.zeros(0, dtype=np.float64)
         counts = D.probe_candidates(list(range(len(levels))), n, self.shard_min_paths, probe)
         return np.array([self._count_percent(counts[i, N.MCR_CTR_SUCCESS], n) for i in range(len(levels))], dtype=np.float64)
+
+    def _option_records(self, family: str, options: Sequence[dict], stream=None) -> Tuple[List[tuple], tuple]:
+        """What is specific to an option family -- ``"scenarios"``, ``"income"``, ``"assumptions"`` or ``"rules"``, which is also
+        the middle of its three `engine` entry points ``probe_<family>``, ``probe_<family>_joint`` and
+        ``probe_<family>_outcomes``: ``(records, lead)``, the validated records of ``options`` and the arguments the engine
+        calls take in front of them.  Raises ``ValueError`` as the family's record builder does."""
+        p = self.params_model
+        if family == "scenarios":
+            from .nestegg import scenario_records
+
+            return scenario_records(options, (p.initial_balance, p.monthly_contribution, p.monthly_expenses)), ()
+        if family == "income":
+            from .income import income_options, stream_index
+
+            index = stream_index(p, stream)
+            return income_options(p, index, options), (index,)
+        if family == "assumptions":
+            from .stress import assumption_records
+
+            return assumption_records(p, options), ()
+        from .spending_rules import rule_options
+
+        return rule_options(p, options), ()
+
+    def _option_probabilities(self, family: str, working_months: int, options: Sequence[dict], num_simulations: Optional[int],
+                              stream=None) -> np.ndarray:
+        """The body of `success_probability_by_scenarios`, `..._by_income_options` and `..._by_assumptions`."""
+        records, lead = self._option_records(family, options, stream)
+        if not records:
+            return np.zeros(0, dtype=np.float64)
+        return self._level_probabilities(getattr(E, f"probe_{family}"), working_months, records, num_simulations, lead)
+
+    def _option_probe(self, kind: str, family: str, working_months: int, options: Sequence[dict], num_simulations: Optional[int],
+                      stream=None, quantiles=None):
+        """The body of every `joint_outcomes_by_*` (``kind = "joint"``) and `option_outcomes_by_*` (``"outcomes"``): the
+        family's records, validated before any device work, through ``engine.probe_<family>_<kind>`` (looked up at call time)
+        into `_joint_outcomes` / `_option_outcomes`.  The rule probes also return their year counts, which are not asked for."""
+        records, lead = self._option_records(family, options, stream)
+        n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
+        wm = int(working_months)
+        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
+        extra = dict({"masks": None} if kind == "joint" else {}, **({"year_counts": False} if family == "rules" else {}))
+
+        def probe(path_begin, count):
+            out = getattr(E, f"probe_{family}_{kind}")(params, rng, self._stream_id, path_begin, count, wm, *lead, records,
+                                                       device=dev, **extra)
+            return out[:1] + out[2:] if family == "rules" else out      # (counts, year counts, ...) -> (counts, ...)
+
+        if kind == "joint":
+            return self._joint_outcomes(probe, len(records), n)
+        return self._option_outcomes(probe, len(records), wm, n, quantiles)
 
     def _joint_outcomes(self, joint_probe, n_records: int, num_simulations: Optional[int]):
         """The body of the `joint_outcomes_by_*` methods: ``joint_probe(path_begin, count) -> (counts, joint, extremes, masks)``
@@ -921,7 +972,7 @@ class RetirementMonteCarloSimulator:
         ``_success_probability(run_monte_carlo_simulations(working_months, n)[0])`` of a simulator whose config differs
         only in ``monthly_expenses``.  Under a process group the levels go through ``distributed.probe_candidates`` (as
         candidate indices), so every rank returns the same array."""
-        return self._level_probabilities(E.probe_expenses, working_months, monthly_expenses, num_simulations)
+        return self._level_probabilities(E.probe_expenses, working_months, [float(x) for x in monthly_expenses], num_simulations)
 
     def find_maximum_monthly_expenses(
         self,
@@ -936,26 +987,35 @@ class RetirementMonteCarloSimulator:
         zero spending misses the target.  Deterministic for a given seed, and the same on every rank."""
         from .spending import EXPENSE_CAP, search_maximum_expenses
 
+        def plan(p, n_sims, target):
+            def probe_levels(levels):
+                return list(self.success_probability_by_expenses(working_months, levels, n_sims))
+
+            return (f"Searching the maximum monthly expenses at {int(working_months)} working months for '{p.Nickname}' "
+                    f"(target {target:.2f}%, {n_sims} sims per level, resolution {resolution}).",
+                    lambda: search_maximum_expenses(
+                        probe_levels, target, max(float(p.monthly_expenses), 1.0), levels_per_call=N.MCR_MAX_EXPENSE_FANOUT,
+                        resolution=resolution, cap=EXPENSE_CAP, on_level=progress_callback),
+                    lambda expenses, prob, curve: (expenses >= 0, (
+                        f"Target not met even without spending: {prob:.2f}% at {int(working_months)} months." if expenses < 0 else
+                        f"  Expense search complete: {expenses:.2f} per month with prob {prob:.2f}% ({len(curve)} levels evaluated).")))
+
+        return self._find_level(verbose, plan)
+
+    def _find_level(self, verbose: bool, plan):
+        """The frame of the single-level `find_*` searches.  Switches to the search seeds; ``plan(params_model, paths per level,
+        target)`` then gives ``(opening, search, closing)``: the opening log line, the search to run (no arguments; its tuple
+        is the result) and ``closing(*result) -> (met, text)``, logged as a line or, when the target was not met, as a warning."""
         self.use_search_seeds()
         p = self.params_model
-        n_sims, target = int(p.num_simulations_search), float(p.target_probability)
+        opening, search, closing = plan(p, int(p.num_simulations_search), float(p.target_probability))
         if verbose:
-            logger.info(f"Searching the maximum monthly expenses at {int(working_months)} working months for '{p.Nickname}' "
-                        f"(target {target:.2f}%, {n_sims} sims per level, resolution {resolution}).")
-
-        def probe_levels(levels):
-            return list(self.success_probability_by_expenses(working_months, levels, n_sims))
-
-        expenses, prob, curve = search_maximum_expenses(
-            probe_levels, target, max(float(p.monthly_expenses), 1.0), levels_per_call=N.MCR_MAX_EXPENSE_FANOUT,
-            resolution=resolution, cap=EXPENSE_CAP, on_level=progress_callback)
+            logger.info(opening)
+        result = search()
         if verbose:
-            if expenses < 0:
-                logger.warning(f"Target not met even without spending: {prob:.2f}% at {int(working_months)} months.")
-            else:
-                logger.info(f"  Expense search complete: {expenses:.2f} per month with prob {prob:.2f}% "
-                            f"({len(curve)} levels evaluated).")
-        return expenses, prob, curve
+            met, text = closing(*result)
+            (logger.info if met else logger.warning)(text)
+        return result
 
     # ---- spending rules ------------------------------------------------------------------------------
     def _rule_counts(self, working_months: int, rule, params, n: int, multipliers: bool = False) -> np.ndarray:
@@ -1060,26 +1120,21 @@ class RetirementMonteCarloSimulator:
         `find_maximum_monthly_expenses`'."""
         from .spending import EXPENSE_CAP, search_maximum_expenses
 
-        self.use_search_seeds()
-        p = self.params_model
-        n_sims, target = int(p.num_simulations_search), float(p.target_probability)
-        if verbose:
-            logger.info(f"Searching the maximum initial monthly expenses under a spending rule at {int(working_months)} working "
-                        f"months for '{p.Nickname}' (target {target:.2f}%, {n_sims} sims per level, resolution {resolution}).")
+        def plan(p, n_sims, target):
+            def probe_levels(levels):
+                return list(self.success_probability_with_rule(working_months, rule, list(levels), n_sims))
 
-        def probe_levels(levels):
-            return list(self.success_probability_with_rule(working_months, rule, list(levels), n_sims))
+            return (f"Searching the maximum initial monthly expenses under a spending rule at {int(working_months)} working "
+                    f"months for '{p.Nickname}' (target {target:.2f}%, {n_sims} sims per level, resolution {resolution}).",
+                    lambda: search_maximum_expenses(
+                        probe_levels, target, max(float(p.monthly_expenses), 1.0), levels_per_call=N.MCR_MAX_EXPENSE_FANOUT,
+                        resolution=resolution, cap=EXPENSE_CAP, on_level=progress_callback),
+                    lambda expenses, prob, curve: (expenses >= 0, (
+                        f"Target not met even without spending: {prob:.2f}% at {int(working_months)} months." if expenses < 0 else
+                        f"  Rule expense search complete: {expenses:.2f} per month to begin with, prob {prob:.2f}% "
+                        f"({len(curve)} levels evaluated).")))
 
-        expenses, prob, curve = search_maximum_expenses(
-            probe_levels, target, max(float(p.monthly_expenses), 1.0), levels_per_call=N.MCR_MAX_EXPENSE_FANOUT,
-            resolution=resolution, cap=EXPENSE_CAP, on_level=progress_callback)
-        if verbose:
-            if expenses < 0:
-                logger.warning(f"Target not met even without spending: {prob:.2f}% at {int(working_months)} months.")
-            else:
-                logger.info(f"  Rule expense search complete: {expenses:.2f} per month to begin with, prob {prob:.2f}% "
-                            f"({len(curve)} levels evaluated).")
-        return expenses, prob, curve
+        return self._find_level(verbose, plan)
 
     # ---- spending rules compared on shared paths ----------------------------------------------------
     def _rule_probe_counts(self, working_months: int, records, n: int) -> np.ndarray:
@@ -1120,38 +1175,14 @@ class RetirementMonteCarloSimulator:
         """The joint outcomes of the options of `success_probability_by_rules` (same arguments) over their shared paths,
         from the joint rule probe (``mcr_probe_rules_joint_rng``): a `paired.JointOutcomes` whose ``.probabilities`` equal
         that method's array bit for bit.  At most ``MCR_MAX_JOINT_OPTIONS`` options."""
-        from .spending_rules import rule_options
-
-        records = rule_options(self.params_model, options)
-        n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
-        wm = int(working_months)
-        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
-
-        def probe(path_begin, count):
-            counts, _, joint, extremes, masks = E.probe_rules_joint(params, rng, self._stream_id, path_begin, count, wm, records,
-                                                                    device=dev, masks=None, year_counts=False)
-            return counts, joint, extremes, masks
-
-        return self._joint_outcomes(probe, len(records), n)
+        return self._option_probe("joint", "rules", working_months, options, num_simulations)
 
     def option_outcomes_by_rules(self, working_months: int, options: Sequence[dict], num_simulations: Optional[int] = None,
                                  quantiles: Sequence[float] = (0.05, 0.25, 0.5, 0.75, 0.95)):
         """The per-option outcomes of the options of `success_probability_by_rules` (same arguments and validation) over
         their shared paths, from the rule outcomes probe (``mcr_probe_rules_outcomes_rng``): an `outcomes.OptionOutcomes`
         whose ``.probabilities`` equal that method's array bit for bit."""
-        from .spending_rules import rule_options
-
-        records = rule_options(self.params_model, options)
-        n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
-        wm = int(working_months)
-        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
-
-        def probe(path_begin, count):
-            counts, _, final_rows, ruin_rows = E.probe_rules_outcomes(params, rng, self._stream_id, path_begin, count, wm, records,
-                                                                      device=dev, year_counts=False)
-            return counts, final_rows, ruin_rows
-
-        return self._option_outcomes(probe, len(records), wm, n, quantiles)
+        return self._option_probe("outcomes", "rules", working_months, options, num_simulations, quantiles=quantiles)
 
     def compare_spending_rules(self, working_months: int, options: Sequence[dict], num_simulations: Optional[int] = None,
                                paired: bool = False, outcomes: bool = False) -> dict:
@@ -1175,16 +1206,24 @@ class RetirementMonteCarloSimulator:
             o = SpendingRuleOutcomes(int(c[N.MCR_CTR_SUCCESS]), n, c[N.MCR_N_COUNTERS:].reshape(ry, N.MCR_RULE_N_COUNTS), age)
             rows.append(dict(zip(SCENARIO_FIELDS, r[:3]), rule=None if r[3] is None else r[3].as_dict(),
                              probability=self._count_percent(c[N.MCR_CTR_SUCCESS], n), years=o.years()))
+        joint = self.joint_outcomes_by_rules(working_months, options, num_simulations) if paired else None
+        per_option = self.option_outcomes_by_rules(working_months, options, num_simulations) if outcomes else None
+        return self._best_option_document({}, rows, joint, per_option)
+
+    @staticmethod
+    def _best_option_document(head: dict, rows: List[dict], joint, per_option) -> dict:
+        """The tail `compare_claiming_options` and `compare_spending_rules` share: ``head`` + ``{"options": rows, "best":
+        index of the highest probability (the first of equals)}``; with ``joint`` (a `paired.JointOutcomes`) every row gains
+        ``"vs_best"`` and the document ``"tied_with_best"``, ``"all_succeed"`` and ``"none_succeed"``; with ``per_option`` (an
+        `outcomes.OptionOutcomes`) every row gains its `OptionOutcomes.row`."""
         best = max(range(len(rows)), key=lambda i: (rows[i]["probability"], -i)) if rows else None
-        doc = {"options": rows, "best": best}
-        if paired:
-            joint = self.joint_outcomes_by_rules(working_months, options, num_simulations)
+        doc = dict(head, options=rows, best=best)
+        if joint is not None:
             for i, row in enumerate(rows):
                 row["vs_best"] = joint.difference(best, i)
             doc["tied_with_best"] = joint.indistinguishable_from(best) if rows else []
             doc["all_succeed"], doc["none_succeed"] = joint.all_succeed, joint.none_succeed
-        if outcomes:
-            per_option = self.option_outcomes_by_rules(working_months, options, num_simulations)
+        if per_option is not None:
             for i, row in enumerate(rows):
                 row.update(per_option.row(i))
         return doc
@@ -1198,7 +1237,7 @@ class RetirementMonteCarloSimulator:
         ``_success_probability(run_monte_carlo_simulations(working_months, n)[0])`` of a simulator whose config differs
         only in ``monthly_contribution``.  Under a process group the levels go through ``distributed.probe_candidates`` (as
         candidate indices), so every rank returns the same array."""
-        return self._level_probabilities(E.probe_contributions, working_months, monthly_contributions, num_simulations)
+        return self._level_probabilities(E.probe_contributions, working_months, [float(x) for x in monthly_contributions], num_simulations)
 
     def find_minimum_monthly_contribution(
         self,
@@ -1215,35 +1254,31 @@ class RetirementMonteCarloSimulator:
         given seed, and the same on every rank."""
         from .saving import CONTRIBUTION_CAP, search_minimum_contribution
 
-        self.use_search_seeds()
-        p = self.params_model
-        wm = int(working_months)
-        n_sims, target = int(p.num_simulations_search), float(p.target_probability)
-        if verbose:
-            logger.info(f"Searching the minimum monthly contribution at {wm} working months for '{p.Nickname}' "
-                        f"(target {target:.2f}%, {n_sims} sims per level, resolution {resolution}).")
+        def plan(p, n_sims, target):
+            wm = int(working_months)
 
-        def probe_levels(levels):
-            return list(self.success_probability_by_contributions(wm, levels, n_sims))
+            def probe_levels(levels):
+                return list(self.success_probability_by_contributions(wm, levels, n_sims))
 
-        if wm == 0:   # nothing is ever contributed: every level has P(0)
-            prob = probe_levels([0.0])[0]
-            curve = [{"monthly_contribution": 0.0, "probability": prob}]
-            if progress_callback:
-                progress_callback({"type": "contribution_search_iter", "iteration": 1, "monthly_contribution": 0.0,
-                                   "probability": round(prob, 2), "target": target, "lo": None, "hi": None})
-            contribution = 0.0 if prob >= target else -1.0
-        else:
-            contribution, prob, curve = search_minimum_contribution(
-                probe_levels, target, max(float(p.monthly_contribution), 1.0), levels_per_call=N.MCR_MAX_EXPENSE_FANOUT,
-                resolution=resolution, cap=CONTRIBUTION_CAP, on_level=progress_callback)
-        if verbose:
-            if contribution < 0:
-                logger.warning(f"Target not met at any monthly contribution: {prob:.2f}% at {wm} months.")
-            else:
-                logger.info(f"  Contribution search complete: {contribution:.2f} per month with prob {prob:.2f}% "
-                            f"({len(curve)} levels evaluated).")
-        return contribution, prob, curve
+            def search():
+                if wm != 0:
+                    return search_minimum_contribution(
+                        probe_levels, target, max(float(p.monthly_contribution), 1.0), levels_per_call=N.MCR_MAX_EXPENSE_FANOUT,
+                        resolution=resolution, cap=CONTRIBUTION_CAP, on_level=progress_callback)
+                prob = probe_levels([0.0])[0]      # nothing is ever contributed: every level has P(0)
+                if progress_callback:
+                    progress_callback({"type": "contribution_search_iter", "iteration": 1, "monthly_contribution": 0.0,
+                                       "probability": round(prob, 2), "target": target, "lo": None, "hi": None})
+                return (0.0 if prob >= target else -1.0), prob, [{"monthly_contribution": 0.0, "probability": prob}]
+
+            return (f"Searching the minimum monthly contribution at {wm} working months for '{p.Nickname}' "
+                    f"(target {target:.2f}%, {n_sims} sims per level, resolution {resolution}).", search,
+                    lambda contribution, prob, curve: (contribution >= 0, (
+                        f"Target not met at any monthly contribution: {prob:.2f}% at {wm} months." if contribution < 0 else
+                        f"  Contribution search complete: {contribution:.2f} per month with prob {prob:.2f}% "
+                        f"({len(curve)} levels evaluated).")))
+
+        return self._find_level(verbose, plan)
 
     # ---- what-if scenarios and the required-starting-balance search -----------------------------------
     def success_probability_by_scenarios(self, working_months: int, scenarios: Sequence[dict],
@@ -1256,39 +1291,14 @@ class RetirementMonteCarloSimulator:
         ``_success_probability(run_monte_carlo_simulations(working_months, n)[0])`` of a simulator whose config differs in
         those fields only.  Under a process group the scenarios go through ``distributed.probe_candidates`` (as candidate
         indices), so every rank returns the same array."""
-        from .nestegg import scenario_records
-
-        p = self.params_model
-        records = scenario_records(scenarios, (p.initial_balance, p.monthly_contribution, p.monthly_expenses))
-        if not records:
-            return np.zeros(0, dtype=np.float64)
-        n = int(p.num_simulations_main if num_simulations is None else num_simulations)
-        wm = int(working_months)
-        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
-
-        def probe(path_begin, count, idx):
-            return E.probe_scenarios(params, rng, self._stream_id, path_begin, count, wm, [records[i] for i in idx], device=dev)
-
-        counts = D.probe_candidates(list(range(len(records))), n, self.shard_min_paths, probe)
-        return np.array([self._count_percent(counts[i, N.MCR_CTR_SUCCESS], n) for i in range(len(records))], dtype=np.float64)
+        return self._option_probabilities("scenarios", working_months, scenarios, num_simulations)
 
     def joint_outcomes_by_scenarios(self, working_months: int, scenarios: Sequence[dict],
                                     num_simulations: Optional[int] = None):
         """The joint outcomes of the scenarios of `success_probability_by_scenarios` (same arguments) over their shared
         paths, from the joint scenario probe (``mcr_probe_scenarios_joint_rng``): a `paired.JointOutcomes` whose
         ``.probabilities`` equal that method's array bit for bit.  At most ``MCR_MAX_JOINT_OPTIONS`` scenarios."""
-        from .nestegg import scenario_records
-
-        p = self.params_model
-        records = scenario_records(scenarios, (p.initial_balance, p.monthly_contribution, p.monthly_expenses))
-        n = int(p.num_simulations_main if num_simulations is None else num_simulations)
-        wm = int(working_months)
-        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
-
-        def probe(path_begin, count):
-            return E.probe_scenarios_joint(params, rng, self._stream_id, path_begin, count, wm, records, device=dev, masks=None)
-
-        return self._joint_outcomes(probe, len(records), n)
+        return self._option_probe("joint", "scenarios", working_months, scenarios, num_simulations)
 
     def option_outcomes_by_scenarios(self, working_months: int, scenarios: Sequence[dict], num_simulations: Optional[int] = None,
                                      quantiles: Sequence[float] = (0.05, 0.25, 0.5, 0.75, 0.95)):
@@ -1296,18 +1306,7 @@ class RetirementMonteCarloSimulator:
         over their shared paths, from the scenario outcomes probe (``mcr_probe_scenarios_outcomes_rng``): an
         `outcomes.OptionOutcomes` -- ruin-month counts, the `quantiles` of the successful cohort's final balance --
         whose ``.probabilities`` equal that method's array bit for bit."""
-        from .nestegg import scenario_records
-
-        p = self.params_model
-        records = scenario_records(scenarios, (p.initial_balance, p.monthly_contribution, p.monthly_expenses))
-        n = int(p.num_simulations_main if num_simulations is None else num_simulations)
-        wm = int(working_months)
-        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
-
-        def probe(path_begin, count):
-            return E.probe_scenarios_outcomes(params, rng, self._stream_id, path_begin, count, wm, records, device=dev)
-
-        return self._option_outcomes(probe, len(records), wm, n, quantiles)
+        return self._option_probe("outcomes", "scenarios", working_months, scenarios, num_simulations, quantiles=quantiles)
 
     def find_minimum_initial_balance(
         self,
@@ -1392,41 +1391,14 @@ class RetirementMonteCarloSimulator:
         bit, ``_success_probability(run_monte_carlo_simulations(working_months, n)[0])`` of a simulator whose config differs
         in those fields only.  Under a process group the options go through ``distributed.probe_candidates`` (as candidate
         indices), so every rank returns the same array."""
-        from .income import income_options, stream_index
-
-        p = self.params_model
-        index = stream_index(p, stream)
-        records = income_options(p, index, options)
-        if not records:
-            return np.zeros(0, dtype=np.float64)
-        n = int(p.num_simulations_main if num_simulations is None else num_simulations)
-        wm = int(working_months)
-        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
-
-        def probe(path_begin, count, idx):
-            return E.probe_income(params, rng, self._stream_id, path_begin, count, wm, index, [records[i] for i in idx], device=dev)
-
-        counts = D.probe_candidates(list(range(len(records))), n, self.shard_min_paths, probe)
-        return np.array([self._count_percent(counts[i, N.MCR_CTR_SUCCESS], n) for i in range(len(records))], dtype=np.float64)
+        return self._option_probabilities("income", working_months, options, num_simulations, stream)
 
     def joint_outcomes_by_income_options(self, working_months: int, stream, options: Sequence[dict],
                                          num_simulations: Optional[int] = None):
         """The joint outcomes of the options of `success_probability_by_income_options` (same arguments) over their shared
         paths, from the joint income probe (``mcr_probe_income_joint_rng``): a `paired.JointOutcomes` whose
         ``.probabilities`` equal that method's array bit for bit.  At most ``MCR_MAX_JOINT_OPTIONS`` options."""
-        from .income import income_options, stream_index
-
-        p = self.params_model
-        index = stream_index(p, stream)
-        records = income_options(p, index, options)
-        n = int(p.num_simulations_main if num_simulations is None else num_simulations)
-        wm = int(working_months)
-        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
-
-        def probe(path_begin, count):
-            return E.probe_income_joint(params, rng, self._stream_id, path_begin, count, wm, index, records, device=dev, masks=None)
-
-        return self._joint_outcomes(probe, len(records), n)
+        return self._option_probe("joint", "income", working_months, options, num_simulations, stream)
 
     def option_outcomes_by_income_options(self, working_months: int, stream, options: Sequence[dict],
                                           num_simulations: Optional[int] = None,
@@ -1434,19 +1406,7 @@ class RetirementMonteCarloSimulator:
         """The per-option outcomes of the options of `success_probability_by_income_options` (same arguments and
         validation) over their shared paths, from the income outcomes probe (``mcr_probe_income_outcomes_rng``): an
         `outcomes.OptionOutcomes` whose ``.probabilities`` equal that method's array bit for bit."""
-        from .income import income_options, stream_index
-
-        p = self.params_model
-        index = stream_index(p, stream)
-        records = income_options(p, index, options)
-        n = int(p.num_simulations_main if num_simulations is None else num_simulations)
-        wm = int(working_months)
-        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
-
-        def probe(path_begin, count):
-            return E.probe_income_outcomes(params, rng, self._stream_id, path_begin, count, wm, index, records, device=dev)
-
-        return self._option_outcomes(probe, len(records), wm, n, quantiles)
+        return self._option_probe("outcomes", "income", working_months, options, num_simulations, stream, quantiles)
 
     def compare_claiming_options(self, working_months: int, stream, options: Sequence[dict],
                                  num_simulations: Optional[int] = None, paired: bool = False, outcomes: bool = False) -> dict:
@@ -1474,17 +1434,7 @@ class RetirementMonteCarloSimulator:
         probs = (joint.probabilities if paired else per_option.probabilities if outcomes else
                  self.success_probability_by_income_options(working_months, index, options, num_simulations))
         rows = [dict(zip(INCOME_OPTION_FIELDS, r), probability=float(pr)) for r, pr in zip(records, probs)]
-        best = max(range(len(rows)), key=lambda i: (rows[i]["probability"], -i)) if rows else None
-        doc = {"stream": index, "options": rows, "best": best}
-        if paired:
-            for i, row in enumerate(rows):
-                row["vs_best"] = joint.difference(best, i)
-            doc["tied_with_best"] = joint.indistinguishable_from(best) if rows else []
-            doc["all_succeed"], doc["none_succeed"] = joint.all_succeed, joint.none_succeed
-        if outcomes:
-            for i, row in enumerate(rows):
-                row.update(per_option.row(i))
-        return doc
+        return self._best_option_document({"stream": index}, rows, joint, per_option)
 
     _UNCHANGED = object()   # (find_minimum_income_amount: "the stream's own duration_years", which may itself be None)
 
@@ -1507,35 +1457,29 @@ class RetirementMonteCarloSimulator:
         rank."""
         from .income import INCOME_AMOUNT_CAP, search_minimum_income_amount, stream_index
 
-        self.use_search_seeds()
-        p = self.params_model
-        wm = int(working_months)
-        index = stream_index(p, stream)
-        fixed = {}
-        if start_at_age is not None:
-            fixed["start_at_age"] = float(start_at_age)
-        if duration_years is not self._UNCHANGED:
-            fixed["duration_years"] = duration_years
-        n_sims, target = int(p.num_simulations_search), float(p.target_probability)
-        if verbose:
-            logger.info(f"Searching the minimum monthly amount of income stream {index} at {wm} working months for "
-                        f"'{p.Nickname}' (target {target:.2f}%, {n_sims} sims per level, resolution {resolution}).")
+        def plan(p, n_sims, target):
+            wm = int(working_months)
+            index = stream_index(p, stream)
+            fixed = {}
+            if start_at_age is not None:
+                fixed["start_at_age"] = float(start_at_age)
+            if duration_years is not self._UNCHANGED:
+                fixed["duration_years"] = duration_years
 
-        def probe_levels(levels):
-            return list(self.success_probability_by_income_options(
-                wm, index, [dict(fixed, monthly_amount_today=x) for x in levels], n_sims))
+            def probe_levels(levels):
+                return list(self.success_probability_by_income_options(
+                    wm, index, [dict(fixed, monthly_amount_today=x) for x in levels], n_sims))
 
-        start = max(float(p.other_income_streams[index].monthly_amount_today), 1.0)
-        amount, prob, curve = search_minimum_income_amount(
-            probe_levels, target, start, levels_per_call=N.MCR_MAX_EXPENSE_FANOUT, resolution=resolution,
-            cap=INCOME_AMOUNT_CAP, on_level=progress_callback)
-        if verbose:
-            if amount < 0:
-                logger.warning(f"Target not met at any amount of income stream {index}: {prob:.2f}% at {wm} months.")
-            else:
-                logger.info(f"  Income search complete: {amount:.2f} per month with prob {prob:.2f}% "
-                            f"({len(curve)} levels evaluated).")
-        return amount, prob, curve
+            return (f"Searching the minimum monthly amount of income stream {index} at {wm} working months for "
+                    f"'{p.Nickname}' (target {target:.2f}%, {n_sims} sims per level, resolution {resolution}).",
+                    lambda: search_minimum_income_amount(
+                        probe_levels, target, max(float(p.other_income_streams[index].monthly_amount_today), 1.0),
+                        levels_per_call=N.MCR_MAX_EXPENSE_FANOUT, resolution=resolution, cap=INCOME_AMOUNT_CAP, on_level=progress_callback),
+                    lambda amount, prob, curve: (amount >= 0, (
+                        f"Target not met at any amount of income stream {index}: {prob:.2f}% at {wm} months." if amount < 0 else
+                        f"  Income search complete: {amount:.2f} per month with prob {prob:.2f}% ({len(curve)} levels evaluated).")))
+
+        return self._find_level(verbose, plan)
 
     # ---- market-assumption stress and the break-even assumption search ---------------------------------
     def success_probability_by_assumptions(self, working_months: int, scenarios: Sequence[dict],
@@ -1548,57 +1492,21 @@ class RetirementMonteCarloSimulator:
         with the input; each value equals, bit for bit, ``_success_probability(run_monte_carlo_simulations(working_months,
         n)[0])`` of a simulator whose config differs in those fields only.  Under a process group the records go through
         ``distributed.probe_candidates`` (as candidate indices), so every rank returns the same array."""
-        from .stress import assumption_records
-
-        p = self.params_model
-        records = assumption_records(p, scenarios)
-        if not records:
-            return np.zeros(0, dtype=np.float64)
-        n = int(p.num_simulations_main if num_simulations is None else num_simulations)
-        wm = int(working_months)
-        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
-
-        def probe(path_begin, count, idx):
-            return E.probe_assumptions(params, rng, self._stream_id, path_begin, count, wm, [records[i] for i in idx], device=dev)
-
-        counts = D.probe_candidates(list(range(len(records))), n, self.shard_min_paths, probe)
-        return np.array([self._count_percent(counts[i, N.MCR_CTR_SUCCESS], n) for i in range(len(records))], dtype=np.float64)
+        return self._option_probabilities("assumptions", working_months, scenarios, num_simulations)
 
     def joint_outcomes_by_assumptions(self, working_months: int, scenarios: Sequence[dict],
                                       num_simulations: Optional[int] = None):
         """The joint outcomes of the records of `success_probability_by_assumptions` (same arguments) over their shared
         paths, from the joint assumption probe (``mcr_probe_assumptions_joint_rng``): a `paired.JointOutcomes` whose
         ``.probabilities`` equal that method's array bit for bit.  At most ``MCR_MAX_JOINT_OPTIONS`` records."""
-        from .stress import assumption_records
-
-        p = self.params_model
-        records = assumption_records(p, scenarios)
-        n = int(p.num_simulations_main if num_simulations is None else num_simulations)
-        wm = int(working_months)
-        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
-
-        def probe(path_begin, count):
-            return E.probe_assumptions_joint(params, rng, self._stream_id, path_begin, count, wm, records, device=dev, masks=None)
-
-        return self._joint_outcomes(probe, len(records), n)
+        return self._option_probe("joint", "assumptions", working_months, scenarios, num_simulations)
 
     def option_outcomes_by_assumptions(self, working_months: int, scenarios: Sequence[dict], num_simulations: Optional[int] = None,
                                        quantiles: Sequence[float] = (0.05, 0.25, 0.5, 0.75, 0.95)):
         """The per-option outcomes of the records of `success_probability_by_assumptions` (same arguments and validation)
         over their shared paths, from the assumption outcomes probe (``mcr_probe_assumptions_outcomes_rng``): an
         `outcomes.OptionOutcomes` whose ``.probabilities`` equal that method's array bit for bit."""
-        from .stress import assumption_records
-
-        p = self.params_model
-        records = assumption_records(p, scenarios)
-        n = int(p.num_simulations_main if num_simulations is None else num_simulations)
-        wm = int(working_months)
-        params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
-
-        def probe(path_begin, count):
-            return E.probe_assumptions_outcomes(params, rng, self._stream_id, path_begin, count, wm, records, device=dev)
-
-        return self._option_outcomes(probe, len(records), wm, n, quantiles)
+        return self._option_probe("outcomes", "assumptions", working_months, scenarios, num_simulations, quantiles=quantiles)
 
     def stress_test(self, working_months: int, shifts: Optional[Sequence[Tuple[str, dict]]] = None,
                     num_simulations: Optional[int] = None, paired: bool = False, outcomes: bool = False) -> List[Dict[str, object]]:
@@ -1654,26 +1562,22 @@ class RetirementMonteCarloSimulator:
         (``None``).  Deterministic for a given seed, and the same on every rank."""
         from .stress import search_breakeven
 
-        self.use_search_seeds()
-        p = self.params_model
-        wm = int(working_months)
-        n_sims, target = int(p.num_simulations_search), float(p.target_probability)
-        if verbose:
-            logger.info(f"Searching the break-even {field} at {wm} working months for '{p.Nickname}' "
-                        f"(target {target:.2f}%, {n_sims} sims per level, window {window}, resolution {resolution}).")
+        def plan(p, n_sims, target):
+            wm = int(working_months)
 
-        def probe_levels(values):
-            return list(self.success_probability_by_assumptions(wm, [{field: v} for v in values], n_sims))
+            def probe_levels(values):
+                return list(self.success_probability_by_assumptions(wm, [{field: v} for v in values], n_sims))
 
-        value, prob, curve, status = search_breakeven(probe_levels, target, field, float(getattr(p, field)), window=window,
-                                                      resolution=resolution, levels_per_call=N.MCR_MAX_EXPENSE_FANOUT, on_level=progress_callback)
-        if verbose:
-            if status == "not_reached":
-                logger.warning(f"Target not met at any {field} of the window: {prob:.2f}% at its favourable end.")
-            else:
-                logger.info(f"  Break-even search complete ({status}): {field} = {value:.4f} with prob {prob:.2f}% "
-                            f"({len(curve)} levels evaluated).")
-        return value, prob, curve, status
+            return (f"Searching the break-even {field} at {wm} working months for '{p.Nickname}' "
+                    f"(target {target:.2f}%, {n_sims} sims per level, window {window}, resolution {resolution}).",
+                    lambda: search_breakeven(probe_levels, target, field, float(getattr(p, field)), window=window, resolution=resolution,
+                                             levels_per_call=N.MCR_MAX_EXPENSE_FANOUT, on_level=progress_callback),
+                    lambda value, prob, curve, status: (status != "not_reached", (
+                        f"Target not met at any {field} of the window: {prob:.2f}% at its favourable end." if status == "not_reached" else
+                        f"  Break-even search complete ({status}): {field} = {value:.4f} with prob {prob:.2f}% "
+                        f"({len(curve)} levels evaluated).")))
+
+        return self._find_level(verbose, plan)
 
     def _grid_probabilities(self, working_months: Sequence[int], levels_2d: Sequence[Sequence[float]],
                             num_simulations: int) -> np.ndarray:

@@ -14,11 +14,9 @@ window]`` clipped to the field's `Config` bounds.
 
 * FIRST CALL: both window ends and up to ``levels_per_call - 2`` evenly spaced interior levels.  The adverse end hits ->
   ``"holds_at_window_end"``; no level hits -> ``"not_reached"`` (``None``, with a ``RuntimeWarning``).
-* REFINE: `nestegg`'s step on the bracket ``(lo, hi)``, ``hi`` the hit on the favourable side and ``lo`` the evaluated level next
-  to it on the adverse side: up to ``levels_per_call`` evenly spaced interior levels, new ``hi`` = the most adverse hit among
-  them and ``hi``, new ``lo`` = the evaluated level next to it.  Monte Carlo estimates are not monotone in the level, but this
-  keeps ``P(hi) >= target > P(lo)``.  Stops when ``|hi - lo| <= resolution``: at most ``1 + ceil(log16(2 window /
-  resolution))`` calls at 15 levels a call.
+* REFINE: `search.refine` on the bracket ``(lo, hi)`` in units of the resolution, ``hi`` the hit on the favourable side and
+  ``lo`` the evaluated level next to it on the adverse side.  Stops when ``|hi - lo| <= resolution``: at most ``1 + ceil(log16(2
+  window / resolution))`` calls at 15 levels a call.
 """
 
 from __future__ import annotations
@@ -33,6 +31,7 @@ from ._logging import logger
 from .config import Config
 from .nestegg import SCENARIO_FIELDS
 from .params import arithmetic_to_log_params
+from .search import CALLER, Evaluation, refine, run
 
 #: the `Config` names of the market's assumptions, as (mean, volatility) per series and the correlation
 MARKET_FIELDS = (
@@ -191,55 +190,25 @@ def search_breakeven(
     def value_of(t: int) -> float:
         return round(sign * t * res, 12)
 
-    memo: Dict[int, float] = {}
-    curve: List[Dict[str, float]] = []
-    state = {"call": 0, "lo": None, "hi": None}
+    ev = Evaluation(value_of, "value", "breakeven_search_iter", target, on_level, {"field": field})
+    memo = ev.memo
 
-    def evaluate(ts: List[int]) -> None:
-        ts = [t for t in dict.fromkeys(ts) if t not in memo]
-        if not ts:
-            return
-        state["call"] += 1
-        probs = list(probe_levels([value_of(t) for t in ts]))
-        if len(probs) != len(ts):
-            raise RuntimeError(f"probe_levels returned {len(probs)} values for {len(ts)} levels")
-        for t, pr in zip(ts, probs):
-            pr = float(pr)
-            memo[t] = pr
-            curve.append({"value": value_of(t), "probability": pr})
-            if on_level:
-                on_level({"type": "breakeven_search_iter", "field": field, "iteration": state["call"], "value": value_of(t),
-                          "probability": round(pr, 2), "target": target,
-                          "lo": None if state["lo"] is None else value_of(state["lo"]),
-                          "hi": None if state["hi"] is None else value_of(state["hi"])})
+    def steps():
+        # first call: both ends and evenly spaced interior levels
+        span = t_max - t_min
+        n_int = min(L - 2, max(0, span - 1))
+        first = sorted({t_min, t_max, *(t_min + (i * span) // (n_int + 1) for i in range(1, n_int + 1))})
+        yield from ev.evaluate(first)
+        if ev.hit(t_min):
+            return value_of(t_min), memo[t_min], ev.curve, "holds_at_window_end"
+        hits = [t for t in first if ev.hit(t)]
+        if not hits:
+            ends = sorted((value_of(t_min), value_of(t_max)))
+            warnings.warn(f"break-even search: no value of {field} in [{ends[0]:g}, {ends[1]:g}] reaches the target",
+                          RuntimeWarning, stacklevel=CALLER)
+            return None, memo[t_max], ev.curve, "not_reached"
+        hi = min(hits)
+        hi = yield from refine(ev, max(t for t in first if t < hi), hi, L, 1, largest=False)
+        return value_of(hi), memo[hi], ev.curve, "found"
 
-    # first call: both ends and evenly spaced interior levels
-    span = t_max - t_min
-    n_int = min(L - 2, max(0, span - 1))
-    first = sorted({t_min, t_max, *(t_min + (i * span) // (n_int + 1) for i in range(1, n_int + 1))})
-    evaluate(first)
-    if memo[t_min] >= target:
-        return value_of(t_min), memo[t_min], curve, "holds_at_window_end"
-    hits = [t for t in first if memo[t] >= target]
-    if not hits:
-        ends = sorted((value_of(t_min), value_of(t_max)))
-        warnings.warn(f"break-even search: no value of {field} in [{ends[0]:g}, {ends[1]:g}] reaches the target",
-                      RuntimeWarning, stacklevel=2)
-        return None, memo[t_max], curve, "not_reached"
-    hi = min(hits)
-    lo = max(t for t in first if t < hi)
-    state["lo"], state["hi"] = lo, hi
-    # refine (nestegg's step, in units of the resolution)
-    while hi - lo > 1:
-        w = hi - lo
-        n_pts = min(L, w - 1)
-        step = -(-w // (n_pts + 1))
-        pts = [lo + i * step for i in range(1, n_pts + 1) if lo + i * step < hi]
-        if not pts:
-            break
-        evaluate(pts)
-        new_hi = min([hi] + [t for t in pts if memo[t] >= target])
-        lo = max(t for t in pts + [lo] if t < new_hi)
-        hi = new_hi
-        state["lo"], state["hi"] = lo, hi
-    return value_of(hi), memo[hi], curve, "found"
+    return run(steps(), probe_levels)
