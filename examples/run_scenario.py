@@ -24,6 +24,8 @@ switch to the final seed stream, run the final batch, print the response documen
         --history-first-month 1926-01 --working-months 240 --cohorts
     python examples/run_scenario.py scenarios/config.json --working-months 240 --spending-rule 1.2,0.8,0.1,0.1,0.5,1.5 [--max-expenses]
     python examples/run_scenario.py scenarios/config.json --working-months 240 --spending-rule 1.2,0.8,0.1,0.1,0.5,1.5 --streamed
+    python examples/run_scenario.py scenarios/config.json --spending-rule 1.2,0.8,0.1,0.1,0.5,1.5 --earliest-retirement
+    python examples/run_scenario.py scenarios/config.json --spending-rule 1.2,0.8,0.1,0.1,0.5,1.5 --frontier 180,240,300
 
 `--rng numpy` uses the reference's own NumPy stream (same seed -> the reference's numbers); `--rng philox`
 (default) the engine's counter-based stream.  `--history FILE.csv` asks every question of a recorded market instead: months
@@ -66,7 +68,11 @@ paths, so every row also gets the paired difference against the best option (`vs
 `tied_with_best`, `all_succeed` and `none_succeed`.
 `--outcomes` (with `--income-options` and / or `--stress`, alone or with `--paired`) says when it goes wrong and what is left:
 every row also gets `lasts_until_age` (the age the money lasts to with 90 / 95 / 99 % confidence; null = the whole horizon),
-`median_ruin_age` (among the failing paths) and `final_balance` (p5 .. p95 of the successful paths' nominal final balance)."""
+`median_ruin_age` (among the failing paths) and `final_balance` (p5 .. p95 of the successful paths' nominal final balance).
+`--spending-rule R --earliest-retirement` answers "how much sooner can I retire if I accept the guardrail": both month searches
+on the same search stream, printed as `{fixed_spending: {working_months, ...}, with_spending_rule: {working_months, ...},
+months_sooner}` (`--full` adds both search curves).  `--frontier M1,M2,... --spending-rule R` adds the rule's frontier beside the
+fixed one: every row gains `with_spending_rule: {max_initial_monthly_expenses, probability, levels_evaluated}`."""
 
 from __future__ import annotations
 
@@ -141,6 +147,9 @@ def main() -> int:
                          "maximum spending to begin with under the rule beside the fixed-spending answer; with --streamed, the "
                          "response document under the rule from in-kernel yearly bins: balance and spending fan charts "
                          "(needs --working-months)")
+    ap.add_argument("--earliest-retirement", action="store_true",
+                    help="--spending-rule: how much sooner can I retire?  Searches the minimum working months with fixed spending "
+                         "and under the rule, and prints both with their difference in months")
     ap.add_argument("--compare-rules", default=None, metavar="RULE;RULE;...",
                     help="spending rules compared over the same paths at --working-months: each UPPER,LOWER,CUT,RAISE,FLOOR,CEILING "
                          "or 'none' (fixed spending), separated by ';'; composes with --paired and --outcomes")
@@ -163,14 +172,18 @@ def main() -> int:
     if args.spending_rule is not None:
         from monte_carlo_retirement_amd.spending_rules import SpendingRule
 
-        if args.working_months is None:
+        if args.working_months is None and not (args.earliest_retirement or args.frontier):
             ap.error("--spending-rule needs --working-months")
+        if args.earliest_retirement and (args.frontier or args.max_expenses or args.streamed):
+            ap.error("--earliest-retirement and --frontier / --max-expenses / --streamed are separate questions")
         if args.rng != "philox" or args.history:
             ap.error("--spending-rule runs on the engine's own stream")
         try:
             args.spending_rule = SpendingRule.parse(args.spending_rule)
         except ValueError as e:
             ap.error(str(e))
+    if args.earliest_retirement and args.spending_rule is None:
+        ap.error("--earliest-retirement goes with --spending-rule")
     if args.min_contribution and args.working_months is None:
         ap.error("--min-contribution needs --working-months")
     if args.min_contribution and args.max_expenses:
@@ -253,7 +266,9 @@ def main() -> int:
         return cohorts(args, config, world, rank0)
     if args.compare_rules is not None:
         return compare_rules(args, config, world, rank0)
-    if args.spending_rule is not None and not args.max_expenses:
+    if args.earliest_retirement:
+        return earliest_retirement(args, config, world, rank0)
+    if args.spending_rule is not None and not args.max_expenses and not args.frontier:
         return spending_rule(args, config, world, rank0)
     if args.max_expenses:
         return max_expenses(args, config, world, rank0)
@@ -382,6 +397,31 @@ def spending_rule(args, config: Config, world: int, rank0: bool) -> int:
             print(f"{'year':>4} {'age':>6} {'alive':>7} {'cut':>7} {'floor':>7} {'raised':>7}")
             for y in out["years"]:
                 print(f"{y['year']:>4} {y['age']:>6.1f} {100 * y['alive']:>6.1f}% {100 * y['cut']:>6.1f}% {100 * y['at_floor']:>6.1f}% {100 * y['raised']:>6.1f}%")
+    if world > 1:
+        import torch.distributed as dist
+
+        dist.barrier()
+        dist.destroy_process_group()
+    return 0
+
+
+def earliest_retirement(args, config: Config, world: int, rank0: bool) -> int:
+    """How much sooner can I retire?  The minimum working months with fixed spending and under --spending-rule, on the same
+    search stream, and their difference."""
+    sim = _simulator(args, config)
+    fixed = sim.find_minimum_working_months(verbose=False)
+    ruled = sim.find_minimum_working_months_with_rule(args.spending_rule, verbose=False)
+    sooner = None if fixed[0] < 0 or ruled[0] < 0 else int(fixed[0] - ruled[0])
+    out = {"scenario": config.Nickname, "rng": args.rng, "rule": args.spending_rule.as_dict(),
+           "num_simulations": int(config.num_simulations_search), "target_probability": float(config.target_probability),
+           "fixed_spending": {"working_months": int(fixed[0]), "probability": fixed[1], "months_evaluated": len(fixed[2])},
+           "with_spending_rule": {"working_months": int(ruled[0]), "probability": ruled[1], "months_evaluated": len(ruled[2])},
+           "months_sooner": sooner}
+    if rank0:
+        if args.full:
+            print(json.dumps(dict(out, fixed_curve=fixed[2], rule_curve=ruled[2])))
+        else:
+            print(json.dumps(out))
     if world > 1:
         import torch.distributed as dist
 
@@ -611,6 +651,10 @@ def frontier_or_grid(args, config: Config, world: int, rank0: bool) -> int:
         results = sim.find_maximum_monthly_expenses_by_months(months, verbose=False, resolution=args.resolution)
         out = [{"working_months": m, "max_monthly_expenses": expenses, "probability": prob, "levels_evaluated": len(curve)}
                for m, (expenses, prob, curve) in zip(months, results)]
+        if args.spending_rule is not None:    # the rule's frontier beside the fixed one: the spending to BEGIN retirement with
+            ruled = sim.find_maximum_initial_expenses_by_months(months, args.spending_rule, verbose=False, resolution=args.resolution)
+            for row, (expenses, prob, curve) in zip(out, ruled):
+                row["with_spending_rule"] = {"max_initial_monthly_expenses": expenses, "probability": prob, "levels_evaluated": len(curve)}
     else:
         months, levels = _csv(args.grid_months, int), _csv(args.grid_expenses, float)
         table = sim.success_probability_grid(months, levels)

@@ -784,6 +784,38 @@ int mcr_probe_rules_outcomes_rng(const mcr_params* p, const mcr_rng* rng, uint32
                                  int device, void* hip_stream);
 int mcr_probe_rules_last_fanout_launches(void);
 
+/*
+ * Retirement-month x spending grid UNDER ONE SPENDING RULE: how much sooner can I retire if I accept the guardrail?  The probe of
+ * the month search and of the max-spending frontier under a rule.  Cell [c][k] of counts and of year_counts equals, bit for
+ * bit, the counters and the year_counts of a count-only mcr_run_rule_rng call at working_months[c] with p->monthly_expenses =
+ * monthly_expenses[c][k] under `rule`, over the same path range; under the neutral rule (cut = raise = 0) the counters are
+ * mcr_probe_grid_rng's.
+ *   working_months:   n_candidates >= 0 months (any order, repeats allowed);
+ *   monthly_expenses: HOST [n_candidates][n_levels] row-major, each finite and >= 0 (config.py:59);
+ *   counts:           DEVICE uint64 [n_candidates][n_levels][MCR_N_COUNTERS] = {successes, paths};
+ *   year_counts:      DEVICE uint64 [n_candidates][n_levels][retirement_years][MCR_RULE_N_COUNTS] or NULL = not requested.
+ * Both are ZEROED by the call.  n_candidates == 0 or n_levels == 0 does nothing.  Every month, every level and the rule
+ * (mcr_validate_spending_rule's ranges) are validated on the host before a device is looked for and before anything is
+ * enqueued: on any error both outputs stay untouched.  What mcr_run_rule_rng refuses is refused here by the same words,
+ * MCR_ERR_UNSUPPORTED with nothing computed: the NumPy and history streams, more than MCR_INLINE_STREAMS kept income streams,
+ * frozen streams beyond the LDS budget, the exact month.
+ * A rule acts only after retirement, so the grid probe's form fits: with 2 .. MCR_MAX_PROBE_CANDIDATES distinct months, n_paths
+ * <= 2^31, at least MCR_EXPENSE_FANOUT_MIN_WAVES path-wavefronts (the grid probe's knob) and at most 4 GiB of snapshots, ONE
+ * accumulation sweep (the grid probe's own) stores the state at every distinct month, then one RULE GRID FAN-OUT launch per group
+ * of levels resumes every row (grid.y) with one consumer wave per level; each wave carries its lanes' multiplier from the resumed
+ * balance and price level and counts its own years.  The rows' records (the grid's record, upper, lower, 1 - cut, 1 + raise,
+ * floor, ceiling, the row's year counts) travel behind the snapshots in the same stream-ordered allocation.  The kernels are the
+ * generic tax mask's, like every rule kernel.  Any other shape, one distinct month included: mcr_probe_rules_rng per row over the
+ * row's levels.  Whichever route runs, the integers are the same.  Asynchronous like mcr_probe_grid_rng.
+ * mcr_probe_rule_grid_last_fanout_launches reports, for the calling thread's last call, how many rule grid fan-out launches it
+ * enqueued: the number of level groups on the shared route, 0 on the per-row route and after an error.
+ */
+int mcr_probe_rule_grid_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                            uint64_t n_paths, const int32_t* working_months, int32_t n_candidates,
+                            const double* monthly_expenses, int32_t n_levels, const mcr_spending_rule* rule,
+                            uint64_t* counts, uint64_t* year_counts, int device, void* hip_stream);
+int mcr_probe_rule_grid_last_fanout_launches(void);
+
 /* _draw_shock_path (simulation.py:452-466) for n_paths paths: host out [n_paths][n_months][3]. */
 int mcr_draw_shocks_host(uint64_t seed, uint32_t stream_id, uint64_t path_begin,
                          uint64_t n_paths, int32_t n_months, double rho, double* out,

@@ -429,6 +429,8 @@ ABI_SYMBOLS = (
     "mcr_probe_rules_joint_rng",
     "mcr_probe_rules_outcomes_rng",
     "mcr_probe_rules_last_fanout_launches",
+    "mcr_probe_rule_grid_rng",
+    "mcr_probe_rule_grid_last_fanout_launches",
     "mcr_release_cached",
     "mcr_sample_columns",
     "mcr_eval_helper_host",
@@ -620,6 +622,14 @@ def _declare(lib: C.CDLL) -> None:
         lib.mcr_probe_rules_outcomes_rng.argtypes = head + [P(McrOptionOutcomes), C.c_int, C.c_void_p]
         lib.mcr_probe_rules_last_fanout_launches.restype = C.c_int
         lib.mcr_probe_rules_last_fanout_launches.argtypes = []
+    if hasattr(lib, "mcr_probe_rule_grid_rng"):   # (likewise)
+        lib.mcr_probe_rule_grid_rng.restype = C.c_int
+        lib.mcr_probe_rule_grid_rng.argtypes = [
+            P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, P(C.c_int32), C.c_int32, P(C.c_double), C.c_int32,
+            P(McrSpendingRule), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,   # ..., rule, counts, year_counts
+        ]
+        lib.mcr_probe_rule_grid_last_fanout_launches.restype = C.c_int
+        lib.mcr_probe_rule_grid_last_fanout_launches.argtypes = []
     lib.mcr_release_cached.restype = C.c_int
     lib.mcr_release_cached.argtypes = [C.c_int]
     lib.mcr_sample_columns.restype = C.c_int

@@ -153,6 +153,17 @@ struct GridCell {
     int32_t snap;                                 // the snapshot column of the row's month
     int32_t pad;
 };
+// PHASE 6 with RULE (rule grid probe, mcr_probe_rule_grid_rng): the row's record under a spending rule.  The grid's own record
+// first, so the kernel reads the row's block, levels, counters and snapshot column where PHASE 6 reads them; behind it the rule as
+// the year's decision reads it (KernelIO::RuleIO's six values, formed on the host by the two operations launch_rule performs) and
+// the year counts of the row's first level of the launch: level j counts at year_counts + j * ry * MCR_RULE_N_COUNTS
+struct RuleGridCell {
+    GridCell cell;
+    double upper, lower, keep, grow, floor, ceiling;
+    unsigned long long* year_counts;              // [lg][ry][MCR_RULE_N_COUNTS] or nullptr, accumulated into
+};
+static_assert(offsetof(RuleGridCell, cell) == 0 && sizeof(RuleGridCell) == sizeof(GridCell) + 7 * sizeof(double),
+              "RuleGridCell is GridCell, six packed doubles and a pointer");
 // PHASE 8 (scenario probe, mcr_probe_scenarios_rng): consumer wave j of a launch runs record j of the launch's device table of
 // mcr_scenario (initial_balance, monthly_contribution, monthly_expenses), through `cand_params` like the grid's records
 static_assert(sizeof(mcr_scenario) == 3 * sizeof(double), "mcr_scenario is three packed doubles");
@@ -395,6 +406,13 @@ __device__ __forceinline__ void year_bins_flush_final(const KernelIO::YearBins& 
 // FanRule (its six values and option j's table of the launch's year counts), the month spends (scn_expenses m) price.  No
 // multiplier rows.  Mask 3 only, like the rule launch.  Counts and year counts are bit-identical to a count-only rule launch
 // with the three fields replaced by record j under record j's rule.
+// PHASE 6 with RULE (mcr_probe_rule_grid_rng): RULE GRID FAN-OUT = PHASE 6's workgroup, snapshots, barriers and votes under ONE
+// spending rule: how much sooner can I retire if I accept the guardrail?  A rule acts only after retirement, so a row resumes
+// from its snapshot column exactly as PHASE 6 does; the row's record is RuleGridCell (the grid's record, the rule, the row's year
+// counts).  The lanes carry the rule launch's RuleState from the resumed balance and price level; the year's decision and ballots
+// are rule_year_from on the wave's own FanRule, as in PHASE 11; the month spends (levels[j] m) price.  No multiplier rows.  Mask 3
+// only, like every rule kernel.  Counts and year counts are bit-identical to a count-only rule launch at the row's month with
+// monthly_expenses = levels[j].
 // EXACT = true: the month in its exact-rounding forms (mcr_device.h) instead of the tolerance form — for configurations whose
 // realized-gains rate lets the reference's denominator clamps bind (DevParams::exact_month), instantiated for the generic XS
 // variants only; -DMCR_K1_EXACT_MONTH builds a library that runs every variant that way (A/B).
@@ -587,8 +605,8 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     // written in place under `if constexpr (RULE)` cost the time-sliced trajectory kernels, which never run them, one or two
     // spilled SGPRs each.)
     static_assert(!RULE || (RNG == (int)MCR_RNG_PHILOX && TAXED == 3 && !INJ && !XS && EXACT == kExactMonthDefault && GF == 0 && MF == 0 && SF == 0 && !LIST && NPROD == 1 &&
-                            (((MODE == 0 || MODE == 1 || MODE == 3) && PHASE == 0 && !SPLIT && !OUT) || (MODE == 0 && PHASE == 11 && SPLIT))),
-                  "the spending rule exists for the plain whole-path Philox launches, count-only, summary and yearly bins, and for the rule fan-out, on the generic tax mask");
+                            (((MODE == 0 || MODE == 1 || MODE == 3) && PHASE == 0 && !SPLIT && !OUT) || (MODE == 0 && PHASE == 11 && SPLIT) || (MODE == 0 && PHASE == 6 && SPLIT && !OUT))),
+                  "the spending rule exists for the plain whole-path Philox launches, count-only, summary and yearly bins, and for the rule and the rule grid fan-outs, on the generic tax mask");
     // PHASE 4 = PHASE 2 (a candidate's decumulation resumed from its accumulation snapshot) time-sliced like PHASE 3: the
     // 17-month verification window of the search is 17 x 196 workgroups = 2.17 rounds of the resident slots.
     constexpr bool kExpFan = PHASE == 5 || PHASE == 6;    // expense fan-out: the levels are monthly_expenses, resumed at retirement
@@ -600,6 +618,8 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     constexpr bool kScnFan = PHASE == 8 || kAsmFan || kIncFan || kRuleFan;   // scenario fan-out: balance, contribution and spending per wave, the whole path
     constexpr bool kFan = kExpFan || kConFan || kScnFan;  // fan-out workgroup: one 64-path block, L consumer waves (levels), one producer wave
     constexpr bool kGrid = PHASE == 6;                    // ... of grid row blockIdx.y (GridCell)
+    constexpr bool kRuleGrid = kGrid && RULE;             // ... under a spending rule (RuleGridCell: the row's record carries the rule)
+    constexpr bool kWaveRule = kRuleFan || kRuleGrid;     // the consumer wave decides the year on its own FanRule
     constexpr bool kCand = PHASE == 2 || PHASE == 4 || kExpFan;   // resumes from a PHASE 1 snapshot (PHASE 2 / 4: per-candidate parameter block)
     constexpr bool kSliced = PHASE == 3 || PHASE == 4;    // time-sliced path blocks
     // the kernels that have growth, month and stream forms (kHasGrowthForms on the host) keep the month's wave-uniform counters
@@ -616,7 +636,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     [[maybe_unused]] std::conditional_t<kIncFan, IncomeRegs, NoIncomeRegs> IR;   // (likewise)
     [[maybe_unused]] std::conditional_t<OUT, RuinMonth, NoRuinMonth> RM;         // (likewise: the outcome probes' month of failure)
     [[maybe_unused]] std::conditional_t<RULE, RuleState, NoRuleState> RS;        // (likewise: the spending rule's multiplier)
-    [[maybe_unused]] std::conditional_t<kRuleFan, FanRule, NoFanRule> FR;        // (likewise: PHASE 11, the consumer wave's own rule)
+    [[maybe_unused]] std::conditional_t<kWaveRule, FanRule, NoFanRule> FR;       // (likewise: PHASE 11 and PHASE 6 with RULE, the consumer wave's own rule)
     static_assert(!kSliced || (RNG == 0 && !INJ && !SPLIT && !XS), "time-sliced blocks exist for the plain Philox variants");
     static_assert(PHASE != 4 || MODE == 0, "the search probes count only");
     // TAXED: which assets carry an effective realized-gains rate (bit 0: inv1, bit 1: inv2; DevParams::tax_mask)
@@ -666,7 +686,8 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     if constexpr (LIST) {
         if ((uint64_t)blockIdx.x * kPaths >= (uint64_t)*io.path_list_count) return;     // (wave-uniform; every thread of the workgroup, before any barrier)
     }
-    const GridCell* cell = kGrid ? reinterpret_cast<const GridCell*>(cand_params) + cand : nullptr;   // PHASE 6: the row's record
+    const GridCell* cell = kRuleGrid ? &(reinterpret_cast<const RuleGridCell*>(cand_params) + cand)->cell    // (RULE: the grid's record heads the row's)
+                           : kGrid ? reinterpret_cast<const GridCell*>(cand_params) + cand : nullptr;   // PHASE 6: the row's record
     const DevParams& P = kGrid ? cell->p : (kCand && !kFan) ? cand_params[cand] : P_arg;
     const int snap_c = kGrid ? cell->snap : (int)cand;   // snapshot column the row resumes from
     // LDS.  STATIC: the math tables (mcr_math.h) and, for the Philox stream, the [6][kBlock] stage of two months' gross
@@ -1000,6 +1021,11 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         // option j's own table of the launch's year counts (the pointer is a launch constant read late, like the epilogue's)
         unsigned long long* const yc = late_arg<unsigned long long*>(offsetof(KernelIO, fan_rule) + offsetof(KernelIO::FanRuleRows, year_counts));
         FR.year_counts = yc ? yc + (size_t)fan_j * (size_t)P.retirement_years * MCR_RULE_N_COUNTS : nullptr;
+    } else if constexpr (kRuleGrid) {            // PHASE 6 with RULE: the row's rule and this level's table of the row's year counts (scalar loads)
+        const RuleGridCell* const rec = reinterpret_cast<const RuleGridCell*>(cand_params) + cand;
+        FR.upper = rec->upper; FR.lower = rec->lower; FR.keep = rec->keep; FR.grow = rec->grow; FR.floor = rec->floor; FR.ceiling = rec->ceiling;
+        unsigned long long* const yc = rec->year_counts;
+        FR.year_counts = yc ? yc + (size_t)fan_j * (size_t)P.retirement_years * MCR_RULE_N_COUNTS : nullptr;
     } else if constexpr (kScnFan) {
         const mcr_scenario* const scn = reinterpret_cast<const mcr_scenario*>(cand_params) + fan_j;
         const double scn_balance = scn->initial_balance;
@@ -1170,7 +1196,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     for (; year < (kSliced ? y_end : ry); ++year) {
         if (!SPLIT && __builtin_amdgcn_ballot_w64(alive) == 0ull) break;  // every lane of this wave has failed: nothing left to simulate
         if (SPLIT) { lane_alive = alive; if (wg_dead) break; }           // (SPLIT: the wave keeps pace with its producers' barriers until the workgroup votes to stop)
-        if constexpr (kRuleFan) rule_year_from(RS, FR, year, valid, alive, b1, b2, infl, li);   // (PHASE 11: the wave's own rule and year counts, no multiplier row)
+        if constexpr (kWaveRule) rule_year_from(RS, FR, year, valid, alive, b1, b2, infl, li);   // (PHASE 11, PHASE 6 with RULE: the wave's own rule and year counts, no multiplier row)
         else if constexpr (kBinsRule) rule_year_binned(RS, YB, year, valid, alive, b1, b2, infl, li);   // (MODE 3: the record's rule; m binned, no multiplier row)
         else
         rule_year(RS, io, year, valid, alive, b1, b2, infl, li);      // (RULE: the year's decision, counts and multiplier row; nothing in every other kernel)
@@ -1185,7 +1211,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
                 if (kStaged) growth(month_row(SC, wm + rmi), g1, ginf, g2);    // staged factors: the LDS reads are issued early
                 const double price = infl;                             // :644
                 // (RULE: the multiplier comes in HERE, not inside tol_month: (monthly_expenses m) price, so that m == 1.0 leaves every bit alone)
-                const double expenses = (kExpFan ? fan_expenses : kScnFan ? rule_scaled(RS, scn_expenses) : rule_scaled(RS, P.monthly_expenses)) * price;   // :645-647
+                const double expenses = (kExpFan ? rule_scaled(RS, fan_expenses) : kScnFan ? rule_scaled(RS, scn_expenses) : rule_scaled(RS, P.monthly_expenses)) * price;   // :645-647
                 // exact form: income accumulates (:649-677) and need = max(0, expenses - income); tolerance form: `income` runs
                 // DOWN from the expenses, one FMA per indexed stream ((amount keep) price), one subtraction per frozen stream
                 // (its slot holds the netted amount): need = max(0, what is left)
@@ -1374,7 +1400,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         if constexpr (kBins) year_bins_row(io.yb, YB.L, YB.k++, valid, t_idx++, !(P.total_months % kMPY != 0 && year == ry - 1), 0.0, infl, year, kNanBits);
         else put_sample(t_idx++, 0.0, infl);
         if (kTraj && valid && wrt) store_bits(&wrt[(int64_t)year * stride + (int64_t)li], kNanBits);
-        if constexpr (!kRuleFan && !kBinsRule) rule_pad(RS, io, year, valid, li);   // (PHASE 11 and MODE 3 write no multiplier row)
+        if constexpr (!kWaveRule && !kBinsRule) rule_pad(RS, io, year, valid, li);   // (PHASE 11, PHASE 6 with RULE and MODE 3 write no multiplier row)
     }
     if (kSliced && seg >= 0 && seg < io.seg_q - 1) {
         // Not the block's last segment: raise the flag, to 1 with the lanes' state handed over, or to 2 (every wave gets here:
@@ -3793,9 +3819,17 @@ static int probe_levels(const mcr_params* p, const mcr_rng* rng, uint32_t stream
 // the state at the end of every distinct month, then grid fan-out launches (PHASE 6, grid.y = row) resume every row's
 // decumulation with up to fanout_max_levels of its levels per launch.  Rows of a repeated month share its snapshot column.
 // Returns MCR_ERR_UNSUPPORTED, having enqueued nothing, for shapes this form does not cover.
-static int probe_grid_shared(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
-                             const int32_t* working_months, int32_t n_rows, const double* levels, int32_t n_levels, uint64_t* counts,
-                             hipStream_t stream) {
+// The skeleton serves the plain grid (Cell = GridCell) and the grid under a spending rule (Cell = RuleGridCell): the month
+// sorting, the snapshot plan, the rows' records level group by level group and the sweep are the same.  `fill(cell, row, first)`
+// adds what the family's record carries beyond the grid's; `launch(gio, grid, block, lds, top, table)` launches the family's
+// kernel for one level group on the group's records.  `launches`, where given, counts the fan-out launches and is reset when
+// they report an error; `what` names the probe in HIP errors.
+static GridCell& grid_part(GridCell& x) { return x; }
+static GridCell& grid_part(RuleGridCell& x) { return x.cell; }
+template <typename Cell, typename Fill, typename Launch>
+static int launch_grid_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                              const int32_t* working_months, int32_t n_rows, const double* levels, int32_t n_levels, uint64_t* counts,
+                              hipStream_t stream, int* launches, const char* what, Fill&& fill, Launch&& launch) {
     if (rng->kind != MCR_RNG_PHILOX || n_rows < 2 || n_paths == 0 || n_paths > ((uint64_t)1 << 31)) return MCR_ERR_UNSUPPORTED;
     if ((n_paths + 63) / 64 < fanout_min_waves()) return MCR_ERR_UNSUPPORTED;
     std::vector<int> order((size_t)n_rows), col((size_t)n_rows);
@@ -3827,38 +3861,71 @@ static int probe_grid_shared(const mcr_params* p, const mcr_rng* rng, uint32_t s
     for (int c = 0; c < n_cand; ++c) io.snap_months[c] = months[(size_t)c];
     // the rows' records, level group by level group: group g covers levels [first, first + lg) of every row
     const LevelGroups groups(n_levels, lmax);
-    std::vector<GridCell> cells((size_t)groups.n_groups * (size_t)n_rows);
-    std::memset(cells.data(), 0, cells.size() * sizeof(GridCell));
+    std::vector<Cell> cells((size_t)groups.n_groups * (size_t)n_rows);
+    std::memset(static_cast<void*>(cells.data()), 0, cells.size() * sizeof(Cell));
     groups.for_each([&](int g, int first, int lg) {
         for (int r = 0; r < n_rows; ++r) {
-            GridCell& x = cells[(size_t)g * n_rows + r];
+            GridCell& x = grid_part(cells[(size_t)g * n_rows + r]);
             x.p = blocks[(size_t)col[(size_t)r]];
             x.snap = col[(size_t)r];
             x.counters = counts + ((size_t)r * n_levels + first) * MCR_N_COUNTERS;
             for (int k = 0; k < lg; ++k) x.levels[k] = levels[(size_t)r * n_levels + first + k];
+            fill(cells[(size_t)g * n_rows + r], r, first);
         }
     });
     SnapshotBlock snap(stream);
     hipError_t e = hipSuccess;
-    if (!snap.attach(io, n_cand, cells.data(), cells.size() * sizeof(GridCell), &e)) return MCR_ERR_UNSUPPORTED;
-    const GridCell* d_cells = (const GridCell*)snap.records;
+    if (!snap.attach(io, n_cand, cells.data(), cells.size() * sizeof(Cell), &e)) return MCR_ERR_UNSUPPORTED;
+    const Cell* d_cells = (const Cell*)snap.records;
     if (e == hipSuccess) {
         const dim3 g6((unsigned)((n_paths + 63) / 64), (unsigned)n_rows);
         launch_accumulation(d1, io, nullptr, lds1, stream);
-        for_tax_variant(top, [&](auto T, auto A) {
-            groups.for_each([&](int g, int, int lg) {
-                KernelIO gio = io;
-                gio.fan_n = lg;
-                hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 6, true>), g6, dim3(64 * (lg + 1)),
-                                   fanout_dynamic_lds(top, lg), stream, top, gio, (const DevParams*)(d_cells + (size_t)g * n_rows));
-            });
+        groups.for_each([&](int g, int, int lg) {
+            KernelIO gio = io;
+            gio.fan_n = lg;
+            launch(gio, g6, dim3(64 * (lg + 1)), fanout_dynamic_lds(top, lg), top, (const DevParams*)(d_cells + (size_t)g * n_rows));
+            if (launches) ++*launches;
         });
         e = hipGetLastError();
     }
     const hipError_t ef = snap.mem.release();
-    if (e != hipSuccess) return hip_fail(e, "grid probe");
-    if (ef != hipSuccess) return hip_fail(ef, "grid probe (free)");
+    if (e != hipSuccess && launches) *launches = 0;
+    if (e != hipSuccess) return hip_fail(e, what);
+    if (ef != hipSuccess) return hip_fail(ef, (std::string(what) + " (free)").c_str());
     return MCR_OK;
+}
+static int probe_grid_shared(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                             const int32_t* working_months, int32_t n_rows, const double* levels, int32_t n_levels, uint64_t* counts,
+                             hipStream_t stream) {
+    return launch_grid_fanout<GridCell>(p, rng, stream_id, path_begin, n_paths, working_months, n_rows, levels, n_levels, counts, stream,
+                                        nullptr, "grid probe", [](GridCell&, int, int) {},
+                                        [&](const KernelIO& gio, dim3 grid, dim3 block, size_t lds, const DevParams& top, const DevParams* table) {
+        for_tax_variant(top, [&](auto T, auto A) {
+            hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 6, true>), grid, block, lds, stream, top, gio, table);
+        });
+    });
+}
+
+// The grid under ONE spending rule (mcr_probe_rule_grid_rng): the grid probe's sweep and records, then rule grid fan-out launches
+// (PHASE 6 with RULE) on the generic tax mask, like every rule kernel.  A row's record carries the rule (keep = 1 - cut, grow =
+// 1 + raise: launch_rule's two operations) and the year counts of its first level of the group.  Returns MCR_ERR_UNSUPPORTED,
+// having enqueued nothing, for shapes the grid probe's form does not cover.
+static thread_local int g_last_rule_grid_fanout_launches = 0;   // (mcr_probe_rule_grid_last_fanout_launches)
+static int probe_rule_grid_shared(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                                  const int32_t* working_months, int32_t n_rows, const double* levels, int32_t n_levels,
+                                  const mcr_spending_rule* rule, uint64_t* counts, uint64_t* year_counts, hipStream_t stream) {
+    const size_t year_block = (size_t)p->retirement_years * MCR_RULE_N_COUNTS;   // one cell's year counts
+    return launch_grid_fanout<RuleGridCell>(p, rng, stream_id, path_begin, n_paths, working_months, n_rows, levels, n_levels, counts, stream,
+                                            &g_last_rule_grid_fanout_launches, "rule grid probe", [&](RuleGridCell& x, int r, int first) {
+        x.upper = rule->upper; x.lower = rule->lower; x.keep = 1.0 - rule->cut; x.grow = 1.0 + rule->raise;
+        x.floor = rule->floor; x.ceiling = rule->ceiling;
+        x.year_counts = year_counts ? (unsigned long long*)year_counts + ((size_t)r * n_levels + first) * year_block : nullptr;
+    }, [&](const KernelIO& gio, dim3 grid, dim3 block, size_t lds, const DevParams& top, const DevParams* table) {
+        for_bool(top.any_annual_tax, [&](auto A) {
+            hipLaunchKernelGGL((path_kernel<0, 0, 3, decltype(A)::value, false, 6, true, false, kExactMonthDefault, 0, 0, 0, false, false, 1, true>),
+                               grid, block, lds, stream, top, gio, table);
+        });
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -4386,6 +4453,30 @@ int mcr_probe_income_outcomes_rng(const mcr_params* p, const mcr_rng* rng, uint3
 
 int mcr_probe_income_last_fanout_launches(void) { return g_last_income_fanout_launches; }
 
+// Everything launch_rule refuses of a launch's shape, for a probe that has no route behind the rule kernels: `who` heads the
+// message ("spending rule" gives launch_rule's own words).  `d` = derive_params' block of the probed month; `summary`: the
+// launches behind the probe are summary launches.
+static int refuse_rule_shapes(const char* who, const mcr_params* p, const mcr_rng* rng, uint64_t path_begin, uint64_t n_paths, DevParams& d,
+                              bool summary) {
+    if (n_paths > (uint64_t)INT32_MAX * kBlock) { set_error("n_paths too large for one launch"); return MCR_ERR_INVALID_ARG; }
+    if (path_begin + n_paths < path_begin) { set_error("path range overflows 64 bits"); return MCR_ERR_INVALID_ARG; }
+    if (rng->kind == MCR_RNG_NUMPY) { set_error("%s: the NumPy stream is not supported (the engine's own stream only)", who); return MCR_ERR_UNSUPPORTED; }
+    if (rng->kind == MCR_RNG_HISTORY) { set_error("%s: the history stream is not supported (the engine's own stream only)", who); return MCR_ERR_UNSUPPORTED; }
+    if (p->n_streams > MCR_INLINE_STREAMS && d.n_extra_streams > 0) {
+        set_error("%s: %d income streams need the generic variant (at most %d are supported)", who, (int)p->n_streams, MCR_INLINE_STREAMS);
+        return MCR_ERR_UNSUPPORTED;
+    }
+    if (needs_generic_variant(d)) { set_error("%s: the exact month (a realized-gains rate above 1 - 1e-6) needs the generic variant, which is not supported", who); return MCR_ERR_UNSUPPORTED; }
+    size_t lds = 0;
+    const int rc = plan_path_kernel_lds(d, summary ? 1 : 0, MCR_RNG_PHILOX, false, false, 0, &lds);
+    if (rc != MCR_OK) return rc;
+    if (d.n_lock_slots < d.n_lock_slots_total) {
+        set_error("%s: %d frozen income streams exceed the LDS budget and need the generic variant, which is not supported", who, (int)d.n_lock_slots_total);
+        return MCR_ERR_UNSUPPORTED;
+    }
+    return MCR_OK;
+}
+
 // What the rule probes check on the host, before the device and their outputs are touched: the block and the month, the stream,
 // every record (the message names options[k].<field> / options[k].rule.<field>), and everything launch_rule refuses -- there is
 // no route behind the rule kernels.  `summary`: the per-option route's launches are summary launches (joint, outcomes).
@@ -4410,23 +4501,7 @@ static int check_rule_probe(const mcr_params* p, const mcr_rng* rng, uint64_t pa
             return MCR_ERR_INVALID_ARG;
         }
     }
-    if (n_paths > (uint64_t)INT32_MAX * kBlock) { set_error("n_paths too large for one launch"); return MCR_ERR_INVALID_ARG; }
-    if (path_begin + n_paths < path_begin) { set_error("path range overflows 64 bits"); return MCR_ERR_INVALID_ARG; }
-    if (rng->kind == MCR_RNG_NUMPY) { set_error("rule probe: the NumPy stream is not supported (the engine's own stream only)"); return MCR_ERR_UNSUPPORTED; }
-    if (rng->kind == MCR_RNG_HISTORY) { set_error("rule probe: the history stream is not supported (the engine's own stream only)"); return MCR_ERR_UNSUPPORTED; }
-    if (p->n_streams > MCR_INLINE_STREAMS && d.n_extra_streams > 0) {
-        set_error("rule probe: %d income streams need the generic variant (at most %d are supported)", (int)p->n_streams, MCR_INLINE_STREAMS);
-        return MCR_ERR_UNSUPPORTED;
-    }
-    if (needs_generic_variant(d)) { set_error("rule probe: the exact month (a realized-gains rate above 1 - 1e-6) needs the generic variant, which is not supported"); return MCR_ERR_UNSUPPORTED; }
-    size_t lds = 0;
-    rc = plan_path_kernel_lds(d, summary ? 1 : 0, MCR_RNG_PHILOX, false, false, 0, &lds);
-    if (rc != MCR_OK) return rc;
-    if (d.n_lock_slots < d.n_lock_slots_total) {
-        set_error("rule probe: %d frozen income streams exceed the LDS budget and need the generic variant, which is not supported", (int)d.n_lock_slots_total);
-        return MCR_ERR_UNSUPPORTED;
-    }
-    return MCR_OK;
+    return refuse_rule_shapes("rule probe", p, rng, path_begin, n_paths, d, summary);
 }
 
 // mcr_probe_rules_rng (jo == nullptr, rows == nullptr), mcr_probe_rules_joint_rng and mcr_probe_rules_outcomes_rng, on the entered
@@ -4528,6 +4603,61 @@ int mcr_probe_grid_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_
                                     n_levels, counts + (size_t)c * n_levels * MCR_N_COUNTERS, device, hip_stream);
     return rc;
 }
+
+// The grid under one spending rule.  Everything is checked on the host before a device is looked for: the months (and, month by
+// month, whatever launch_rule refuses, by its words), every level, the rule.  Then the shared route (probe_rule_grid_shared) or,
+// where it answers MCR_ERR_UNSUPPORTED (one distinct month, more than MCR_MAX_PROBE_CANDIDATES of them, a launch below the
+// fan-out's minimum wave count, the allocation refused), one rule probe per row over the row's levels.
+int mcr_probe_rule_grid_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                            uint64_t n_paths, const int32_t* working_months, int32_t n_candidates,
+                            const double* monthly_expenses, int32_t n_levels, const mcr_spending_rule* rule,
+                            uint64_t* counts, uint64_t* year_counts, int device, void* hip_stream) {
+    g_last_rule_grid_fanout_launches = 0;
+    if (n_candidates < 0 || n_levels < 0) { set_error("n_candidates %d / n_levels %d must be >= 0", n_candidates, n_levels); return MCR_ERR_INVALID_ARG; }
+    if (n_candidates == 0 || n_levels == 0) return MCR_OK;
+    if (!working_months || !monthly_expenses || !counts) { set_error("null months / levels / counts"); return MCR_ERR_INVALID_ARG; }
+    int rc = validate_months(p, working_months, n_candidates);
+    if (rc != MCR_OK) return rc;
+    if ((rc = check_rng(rng)) != MCR_OK) return rc;
+    const size_t n_cells = (size_t)n_candidates * (size_t)n_levels;
+    for (size_t k = 0; k < n_cells; ++k)
+        if (!(std::isfinite(monthly_expenses[k]) && monthly_expenses[k] >= 0.0)) {
+            set_error("monthly_expenses[%d][%d] = %g: must be finite and >= 0 (config.py:59)", (int)(k / (size_t)n_levels),
+                      (int)(k % (size_t)n_levels), monthly_expenses[k]);
+            return MCR_ERR_INVALID_ARG;
+        }
+    if ((rc = validate_spending_rule(rule)) != MCR_OK) return rc;
+    for (int32_t c = 0; c < n_candidates; ++c) {
+        DevParams d;
+        std::vector<DevStream> extra;
+        if ((rc = derive_params(p, working_months[c], &d, &extra)) != MCR_OK) return rc;
+        if ((rc = refuse_rule_shapes("spending rule", p, rng, path_begin, n_paths, d, false)) != MCR_OK) return rc;
+    }
+    MCR_ENTER_DEVICE(device);
+    hipStream_t main = (hipStream_t)hip_stream;
+    const size_t year_block = (size_t)p->retirement_years * MCR_RULE_N_COUNTS;   // one cell's year counts
+    rc = zero_counters(counts, n_cells, main);
+    if (rc != MCR_OK) return rc;
+    if (year_counts) {
+        const hipError_t e = hipMemsetAsync(year_counts, 0, sizeof(uint64_t) * year_block * n_cells, main);
+        if (e != hipSuccess) return hip_fail(e, "rule grid probe year counts memset");
+    }
+    rc = probe_rule_grid_shared(p, rng, stream_id, path_begin, n_paths, working_months, n_candidates, monthly_expenses, n_levels, rule,
+                                counts, year_counts, main);
+    if (rc != MCR_ERR_UNSUPPORTED) return rc;     // (unsupported shape / allocation refused: the per-row route below)
+    std::vector<mcr_rule_option> options((size_t)n_levels);
+    rc = MCR_OK;
+    for (int32_t c = 0; c < n_candidates && rc == MCR_OK; ++c) {
+        for (int32_t k = 0; k < n_levels; ++k)
+            options[(size_t)k] = mcr_rule_option{p->initial_balance, p->monthly_contribution, monthly_expenses[(size_t)c * n_levels + k], *rule};
+        rc = mcr_probe_rules_rng(p, rng, stream_id, path_begin, n_paths, working_months[c], options.data(), n_levels,
+                                 counts + (size_t)c * n_levels * MCR_N_COUNTERS,
+                                 year_counts ? year_counts + (size_t)c * n_levels * year_block : nullptr, device, hip_stream);
+    }
+    return rc;
+}
+
+int mcr_probe_rule_grid_last_fanout_launches(void) { return g_last_rule_grid_fanout_launches; }
 
 int mcr_run_batch(const mcr_params* p, uint64_t seed, uint32_t stream_id, uint64_t path_begin,
                   uint64_t n_paths, int32_t working_months, const double* injected_shocks,

@@ -971,20 +971,11 @@ def probe_grid(params: McrParams, seed, stream_id: int, path_begin: int, n_paths
     import torch
 
     N.require_device()
-    months = [int(m) for m in working_months]
-    rows = [[float(x) for x in row] for row in levels_2d]
-    if len(rows) != len(months):
-        raise ValueError(f"levels_2d has {len(rows)} rows for {len(months)} working months")
-    n_levels = len(rows[0]) if rows else 0
-    if any(len(r) != n_levels for r in rows):
-        raise ValueError("levels_2d must be rectangular")
+    months, n_levels, marr, larr = _grid_arrays(working_months, levels_2d)
     counts = torch.empty((len(months), n_levels, N.MCR_N_COUNTERS), dtype=torch.int64,
                          device=torch.device("cuda", int(device)))
     if not months or n_levels == 0:
         return counts
-    marr = (C.c_int32 * len(months))(*months)
-    flat = [x for r in rows for x in r]
-    larr = (C.c_double * len(flat))(*flat)
     rng = _as_rng(seed, int(device))
     stream = torch.cuda.current_stream(int(device)).cuda_stream
     rc = N.load_library().mcr_probe_grid_rng(
@@ -993,6 +984,53 @@ def probe_grid(params: McrParams, seed, stream_id: int, path_begin: int, n_paths
     )
     N.check(rc, "mcr_probe_grid_rng")
     return counts
+
+
+def _grid_arrays(working_months, levels_2d):
+    """The months and the rectangular level rows of a grid probe as the C ABI takes them: ``(months, n_levels, int32 array,
+    row-major double array)``."""
+    months = [int(m) for m in working_months]
+    rows = [[float(x) for x in row] for row in levels_2d]
+    if len(rows) != len(months):
+        raise ValueError(f"levels_2d has {len(rows)} rows for {len(months)} working months")
+    n_levels = len(rows[0]) if rows else 0
+    if any(len(r) != n_levels for r in rows):
+        raise ValueError("levels_2d must be rectangular")
+    flat = [x for r in rows for x in r]
+    return months, n_levels, (C.c_int32 * max(1, len(months)))(*months), (C.c_double * max(1, len(flat)))(*flat)
+
+
+def probe_rule_grid(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months, levels_2d, rule,
+                    device: int = 0, year_counts: bool = True):
+    """`probe_grid` under ONE spending rule (``mcr_probe_rule_grid_rng``): cell ``[c, k]`` counts exactly what a count-only
+    `run_rule` at ``working_months[c]`` with ``monthly_expenses = levels_2d[c][k]`` counts under `rule` (a
+    `spending_rules.SpendingRule` or ``McrSpendingRule``), year counts included.  A rule acts only after retirement, so the
+    accumulation runs once for every month and one launch per level group covers all rows.  Returns device int64 tensors
+    ``(counts [R, L, 2], year_counts [R, L, ry, MCR_RULE_N_COUNTS])`` (the second None with ``year_counts=False``);
+    asynchronous (reading a tensor synchronises)."""
+    import torch
+
+    N.require_device()
+    months, n_levels, marr, larr = _grid_arrays(working_months, levels_2d)
+    dev = torch.device("cuda", int(device))
+    empty = not months or n_levels == 0
+    alloc = torch.zeros if empty else torch.empty         # (the call zeroes both; an empty grid: no call)
+    counts = alloc((len(months), n_levels, N.MCR_N_COUNTERS), dtype=torch.int64, device=dev)
+    yc = None
+    if year_counts:
+        ry = int(query_sizes(params, months[0] if months else 0).retirement_years)
+        yc = alloc((len(months), n_levels, ry, N.MCR_RULE_N_COUNTS), dtype=torch.int64, device=dev)
+    if empty:
+        return counts, yc
+    rng = _as_rng(seed, int(device))
+    record = _rule_record(rule)
+    stream = torch.cuda.current_stream(int(device)).cuda_stream
+    rc = N.load_library().mcr_probe_rule_grid_rng(
+        C.byref(params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), marr, len(months), larr, n_levels,
+        C.byref(record), counts.data_ptr(), yc.data_ptr() if yc is not None else None, int(device), C.c_void_p(stream),
+    )
+    N.check(rc, "mcr_probe_rule_grid_rng")
+    return counts, yc
 
 
 def _rule_record(rule):

@@ -698,6 +698,39 @@ class RetirementMonteCarloSimulator:
         search stream with common random numbers.  Returns ``(months, probability, search_curve)``;
         ``months == -1`` when the target is not reachable within 70 years.
         """
+        # the reference's tests (and callers) may replace run_monte_carlo_simulations per instance;
+        # then the search must go through it.  Otherwise use the count-only kernels.
+        # (replaced on the instance, by a subclass, or by patching the class attribute)
+        patched = ("run_monte_carlo_simulations" in self.__dict__
+                   or getattr(type(self), "run_monte_carlo_simulations", None) is not _ENGINE_RUN)
+        return self._search_minimum_working_months(self._probe_many, verbose, progress_callback, patched=patched)
+
+    def find_minimum_working_months_with_rule(
+        self,
+        rule,
+        verbose: bool = True,
+        progress_callback: Optional[Callable[[dict], None]] = None,
+    ) -> Tuple[int, float, List[Dict[str, float]]]:
+        """`find_minimum_working_months` for a household that follows `rule` (a `spending_rules.SpendingRule`) once it has
+        retired: how much sooner can I retire if I accept the guardrail?  The same driver, stream, path count, return shape
+        and events; every round of candidates is ONE rule-grid probe with one level per row (``mcr_probe_rule_grid_rng``:
+        the accumulation runs once for the round's months).  With `SpendingRule.neutral` the result, curve and events are
+        exactly `find_minimum_working_months`'."""
+        return self._search_minimum_working_months(lambda months, n: self._probe_many_with_rule(months, n, rule),
+                                                   verbose, progress_callback)
+
+    def _probe_many_with_rule(self, months: Sequence[int], num_simulations: int, rule) -> Dict[int, float]:
+        """`_probe_many` under `rule`: success % of several candidate working-month counts over the same paths, at the
+        config's own spending level, from one rule-grid probe with one level per row."""
+        months = [int(m) for m in months]
+        grid = self._rule_grid_probabilities(months, [[float(self.params_model.monthly_expenses)]] * len(months), rule,
+                                             int(num_simulations))
+        return {m: float(grid[i, 0]) for i, m in enumerate(months)}
+
+    def _search_minimum_working_months(self, probe_many, verbose: bool, progress_callback, patched: bool = False
+                                       ) -> Tuple[int, float, List[Dict[str, float]]]:
+        """The driver of the month searches: bracket, bisection, verification window and the `ahead` speculation, over
+        ``probe_many(months, n) -> {month: %}``.  ``patched``: go through `run_monte_carlo_simulations` month by month."""
         self.use_search_seeds()
         p = self.params_model
         first = p.starting_working_months_search
@@ -707,15 +740,10 @@ class RetirementMonteCarloSimulator:
         curve: List[Dict[str, float]] = []
         memo: Dict[int, float] = {}
         state = {"iter": 0, "best_seen": -1.0, "lo": first, "hi": None}
-        # the reference's tests (and callers) may replace run_monte_carlo_simulations per instance;
-        # then the search must go through it.  Otherwise use the count-only kernels, and evaluate
-        # candidates the driver is about to ask for TOGETHER with the one it asks for now (they share
-        # the GPU concurrently / are split across ranks).  `ahead` only holds results early: months
-        # are still reported one by one, in the reference's order, and a month the reference would
-        # not have probed never reaches memo, the curve or the callback.
-        # (replaced on the instance, by a subclass, or by patching the class attribute)
-        patched = ("run_monte_carlo_simulations" in self.__dict__
-                   or getattr(type(self), "run_monte_carlo_simulations", None) is not _ENGINE_RUN)
+        # Unless `patched`, evaluate candidates the driver is about to ask for TOGETHER with the one
+        # it asks for now (they share the GPU concurrently / are split across ranks).  `ahead` only
+        # holds results early: months are still reported one by one, in the reference's order, and a
+        # month the reference would not have probed never reaches memo, the curve or the callback.
         ahead: Dict[int, float] = {}
         slots = 1 if patched else self._speculation_slots(n_sims)
 
@@ -737,7 +765,7 @@ class RetirementMonteCarloSimulator:
                 if months not in ahead:
                     batch = [months] + [m for m in dict.fromkeys(likely_next)
                                         if m != months and m not in ahead and m not in memo]
-                    ahead.update(self._probe_many(batch, n_sims))
+                    ahead.update(probe_many(batch, n_sims))
                 prob = ahead[months]
             memo[months] = prob
             if verbose:
@@ -1580,9 +1608,10 @@ class RetirementMonteCarloSimulator:
         return self._find_level(verbose, plan)
 
     def _grid_probabilities(self, working_months: Sequence[int], levels_2d: Sequence[Sequence[float]],
-                            num_simulations: int) -> np.ndarray:
+                            num_simulations: int, rule=None) -> np.ndarray:
         """Success % ``[len(working_months), n_levels]`` of month ``c`` at the levels of row ``c`` (rectangular), over the
-        active stream's batch, from the grid probe (``mcr_probe_grid_rng``).  Under a process group the rows go through
+        active stream's batch, from the grid probe (``mcr_probe_grid_rng``) or, with `rule`, from the rule-grid probe
+        (``mcr_probe_rule_grid_rng``, its counters alone).  Under a process group the rows go through
         ``distributed.probe_candidates`` (candidate = row, ``2 n_levels`` counters each): one all-reduce, the same matrix
         on every rank."""
         months = [int(m) for m in working_months]
@@ -1594,6 +1623,9 @@ class RetirementMonteCarloSimulator:
         params, rng, dev = self._current_params(), self._batch_rng(n), self._local_device()
 
         def probe(path_begin, count, idx):
+            if rule is not None:
+                return E.probe_rule_grid(params, rng, self._stream_id, path_begin, count, [months[i] for i in idx],
+                                         [rows[i] for i in idx], rule, device=dev, year_counts=False)[0]
             return E.probe_grid(params, rng, self._stream_id, path_begin, count, [months[i] for i in idx],
                                 [rows[i] for i in idx], device=dev)
 
@@ -1613,6 +1645,41 @@ class RetirementMonteCarloSimulator:
         n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
         return self._grid_probabilities(months, [levels] * len(months), n)
 
+    def _rule_grid_probabilities(self, working_months: Sequence[int], levels_2d: Sequence[Sequence[float]], rule,
+                                 num_simulations: int) -> np.ndarray:
+        """`_grid_probabilities` under `rule` (a `spending_rules.SpendingRule`)."""
+        if rule is None:
+            raise ValueError("a spending rule is required (SpendingRule.neutral() is fixed spending)")
+        return self._grid_probabilities(working_months, levels_2d, num_simulations, rule=rule)
+
+    def success_probability_grid_with_rule(self, working_months: Sequence[int], rule, monthly_expenses=None,
+                                           num_simulations: Optional[int] = None) -> np.ndarray:
+        """`success_probability_grid` for a household that follows `rule`: ``[len(working_months), n_levels]`` success %,
+        ``monthly_expenses`` the levels the paths START retirement with (None: one column at the config's own level).  Row
+        ``c`` equals, bit for bit, ``success_probability_with_rule(working_months[c], rule, monthly_expenses)``; a rule
+        acts only after retirement, so the accumulation runs once for all months (``mcr_probe_rule_grid_rng``).  The same
+        matrix on every rank."""
+        months = [int(m) for m in working_months]
+        levels = ([float(self.params_model.monthly_expenses)] if monthly_expenses is None
+                  else [float(x) for x in np.atleast_1d(np.asarray(monthly_expenses, dtype=np.float64))])
+        n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
+        return self._rule_grid_probabilities(months, [levels] * len(months), rule, n)
+
+    def find_maximum_initial_expenses_by_months(
+        self,
+        working_months: Sequence[int],
+        rule,
+        verbose: bool = True,
+        progress_callback: Optional[Callable[[dict], None]] = None,
+        resolution: float = 1.0,
+    ) -> List[Tuple[float, float, List[Dict[str, float]]]]:
+        """`find_maximum_monthly_expenses_by_months` for a household that follows `rule`: the frontier of the spending to
+        START retirement with.  Entry ``i`` equals ``find_maximum_initial_expenses(working_months[i], rule)`` for the same
+        seed; every round of the lockstep searches is ONE rule-grid probe over the unfinished months' levels."""
+        return self._maximum_expenses_by_months(
+            working_months, verbose, progress_callback, resolution, "initial monthly expenses under a spending rule",
+            lambda months, levels_2d, n_sims: self._rule_grid_probabilities(months, levels_2d, rule, n_sims))
+
     def find_maximum_monthly_expenses_by_months(
         self,
         working_months: Sequence[int],
@@ -1625,6 +1692,12 @@ class RetirementMonteCarloSimulator:
         ``find_maximum_monthly_expenses(working_months[i])`` returns for the same seed.  The searches run in lockstep
         (`spending.search_maximum_expenses_many`): every round is ONE grid probe over the unfinished months' levels.
         ``progress_callback`` events also carry ``working_months``."""
+        return self._maximum_expenses_by_months(working_months, verbose, progress_callback, resolution, "monthly expenses",
+                                                self._grid_probabilities)
+
+    def _maximum_expenses_by_months(self, working_months: Sequence[int], verbose: bool, progress_callback, resolution: float,
+                                    what: str, grid_probabilities):
+        """The frame of the frontier searches: ``grid_probabilities(months, levels_2d, n) -> [rows, levels]`` success %."""
         from .spending import EXPENSE_CAP, search_maximum_expenses_many
 
         months = [int(m) for m in working_months]
@@ -1632,11 +1705,11 @@ class RetirementMonteCarloSimulator:
         p = self.params_model
         n_sims, target = int(p.num_simulations_search), float(p.target_probability)
         if verbose:
-            logger.info(f"Searching the maximum monthly expenses at {len(months)} retirement months for '{p.Nickname}' "
+            logger.info(f"Searching the maximum {what} at {len(months)} retirement months for '{p.Nickname}' "
                         f"(target {target:.2f}%, {n_sims} sims per level, resolution {resolution}).")
 
         def probe_rows(rows, levels_2d):
-            return self._grid_probabilities([months[i] for i in rows], levels_2d, n_sims).tolist()
+            return np.asarray(grid_probabilities([months[i] for i in rows], levels_2d, n_sims)).tolist()
 
         start = max(float(p.monthly_expenses), 1.0)
         results = search_maximum_expenses_many(
