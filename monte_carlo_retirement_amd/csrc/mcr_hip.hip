@@ -1575,6 +1575,8 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
 // (capacity_tol, sell_fraction_tol, rebalance_tol, the income FMAs of the stream form) restated in fp32: selects stay selects,
 // and instead of the dust fix-ups a lane becomes DOUBTFUL when a balance falls to one dollar.  (The rebalance that closes a
 // tax year without an annual-gains tax comes right behind the month's own and moves a rounding's worth: it is left out.)
+// The month is stated as mcr_screen.h's "month as restated" says: one net need level per window state, the price level as a
+// logarithm, no dead clamps, a running minimum of the balances.  RHO0: a launch whose rho is 0 (screen_factors2).
 // A lane is SAFE only if in every retirement month cap >= kScreenNeedMargin need and cap >= peak / kScreenPeakDiv, `need` and
 // `cap` the month's own values and `peak` the running maximum of b1 + b2 (need <= 0: the second test alone decides, as the
 // first then holds for any positive cap).  SAFE lanes are counted as path_kernel's epilogue counts a successful path whose
@@ -1593,7 +1595,7 @@ struct ScreenIO {
     float* min_ratio;            // HOOK: [n_paths] lowest cap / need of the months the lane ran (+inf: no month with a need)
     float* final_total;          // HOOK: [n_paths] b1 + b2 where the lane stopped
 };
-template <int TAXED, bool EQR, bool HOOK = false>
+template <int TAXED, bool EQR, bool RHO0, bool HOOK = false>
 __global__ __launch_bounds__(kBlock, 8) void screen_kernel(const ScreenParams S, const ScreenIO io) {
     static_assert(TAXED >= 0 && TAXED <= 3 && (!EQR || TAXED == 3), "TAXED is path_kernel's mask; equal rates need both assets taxed");
     constexpr bool T1 = (TAXED & 1) != 0, T2 = (TAXED & 2) != 0;
@@ -1604,12 +1606,16 @@ __global__ __launch_bounds__(kBlock, 8) void screen_kernel(const ScreenParams S,
     const bool valid = local < io.n_paths;
     const uint64_t path = io.path_begin + (valid ? local : io.n_paths - 1);   // tail lanes shadow the last path
     const PhiloxPath PQ = philox_path(path, io.stream_id, io.seed);           // (the whole wave is here: philox_path's ballot)
-    float b1 = S.b1_0, b2 = S.b2_0, c1 = b1, c2 = b2, infl = 1.0f;
+    float b1 = S.b1_0, b2 = S.b2_0, c1 = b1, c2 = b2;
+    float lvl = 0.0f;                                                // log2 of the price level
     float peak = b1 + b2;
     float contrib = S.contrib, k1 = contrib * S.alloc1, k2 = contrib - k1;
-    bool ok = __builtin_fminf(b1, b2) > kScreenMinBalance;
+    bool ok = true;
+    float rmin = __builtin_fminf(b1, b2);
     [[maybe_unused]] float min_ratio = __builtin_inff();
     PairCarry carry{0u, 0u};
+    ScreenConsts K{S.a1, S.ainf, S.aprem, S.ar1, S.ar2};
+    asm volatile("" : "+v"(K.a1), "+v"(K.ainf), "+v"(K.aprem), "+v"(K.ar1), "+v"(K.ar2));      // (ScreenConsts: VGPRs for the whole path)
     const int wm = S.working_months, total = S.total_months;
     int moy = 0;                                                     // accumulation month of the year, 0 .. 11
     // laggards first, as in path_kernel: the wave's priority falls at half, three quarters and nine tenths of the path (even rows)
@@ -1617,7 +1623,8 @@ __global__ __launch_bounds__(kBlock, 8) void screen_kernel(const ScreenParams S,
     int prio_next = prio_t1;
     __builtin_amdgcn_s_setprio(3);
     for (int row = 0; row < total; row += 2) {
-        if (__builtin_amdgcn_ballot_w64(ok) == 0ull) break;          // every lane of the wave is doubtful: nothing left to decide
+        // every lane of the wave is doubtful: nothing left to decide (asked every 8th row pair)
+        if ((row & 14) == 0 && __builtin_amdgcn_ballot_w64(ok && rmin > kScreenMinBalance) == 0ull) break;
         if (row == prio_next) {
             if (row == prio_t1) __builtin_amdgcn_s_setprio(2);
             else if (row == prio_t2) __builtin_amdgcn_s_setprio(1);
@@ -1626,46 +1633,51 @@ __global__ __launch_bounds__(kBlock, 8) void screen_kernel(const ScreenParams S,
         }
         float g[6];
         if (PQ.hi_uniform) {
-            if ((row & 2) == 0) screen_factors2<0, true>(S, PQ, io.seed, (uint32_t)row >> 2, carry, g);
-            else screen_factors2<1, true>(S, PQ, io.seed, (uint32_t)row >> 2, carry, g);
+            if ((row & 2) == 0) screen_factors2<0, true, RHO0>(S, K, PQ, io.seed, (uint32_t)row >> 2, carry, g);
+            else screen_factors2<1, true, RHO0>(S, K, PQ, io.seed, (uint32_t)row >> 2, carry, g);
         } else {                                                     // a wave that straddles a multiple of 2^32 paths
-            if ((row & 2) == 0) screen_factors2<0, false>(S, PQ, io.seed, (uint32_t)row >> 2, carry, g);
-            else screen_factors2<1, false>(S, PQ, io.seed, (uint32_t)row >> 2, carry, g);
+            if ((row & 2) == 0) screen_factors2<0, false, RHO0>(S, K, PQ, io.seed, (uint32_t)row >> 2, carry, g);
+            else screen_factors2<1, false, RHO0>(S, K, PQ, io.seed, (uint32_t)row >> 2, carry, g);
         }
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             const int m = row + r;                                   // wave-uniform
             if (m >= total) break;
-            const float g1 = g[3 * r], ginf = g[3 * r + 1], g2 = g[3 * r + 2];
+            const float g1 = g[3 * r], xinf = g[3 * r + 1], g2 = g[3 * r + 2];
             if (m < wm) {                                            // accumulation (:513-553)
                 if (moy == kMPY) {
                     moy = 0;
-                    if (S.contrib_grows) { contrib *= S.contrib_growth_factor; k1 = contrib * S.alloc1; k2 = contrib - k1; }
+                    if (S.contrib_grows) {
+                        asm volatile("");                            // (keeps the yearly step a scalar branch: if-converted, it costs six VALU every month)
+                        contrib *= S.contrib_growth_factor; k1 = contrib * S.alloc1; k2 = contrib - k1;
+                    }
                 }
                 ++moy;
-                b1 *= g1; b2 *= g2; infl *= ginf;
+                b1 *= g1; b2 *= g2; lvl += xinf;
                 b1 += k1; c1 += k1; b2 += k2; c2 += k2;
             } else {                                                 // decumulation (:644-796)
-                const float price = infl;
-                float income = S.expenses * price;
-                if ((unsigned)(m - S.s0) < S.n0) income = __builtin_fmaf(-S.sa0, price, income);
-                if ((unsigned)(m - S.s1) < S.n1) income = __builtin_fmaf(-S.sa1, price, income);
-                const float need = __builtin_fmaxf(0.0f, income);
-                b1 *= g1; b2 *= g2; infl *= ginf;
+                const float price = __builtin_amdgcn_exp2f(lvl);
+                const bool w0 = (unsigned)(m - S.s0) < S.n0, w1 = (unsigned)(m - S.s1) < S.n1;
+                const uint32_t on0 = w1 ? __builtin_bit_cast(uint32_t, S.e11) : __builtin_bit_cast(uint32_t, S.e10);
+                const uint32_t off0 = w1 ? __builtin_bit_cast(uint32_t, S.e01) : __builtin_bit_cast(uint32_t, S.e00);
+                const float level = __builtin_bit_cast(float, w0 ? on0 : off0);      // (selected as words: s_cselect_b32, not v_cndmask)
+                const float need = __builtin_fmaxf(0.0f, price * level);
+                b1 *= g1; b2 *= g2; lvl += xinf;
                 const float v1 = T1 ? __builtin_fmaf(-__builtin_fmaxf(0.0f, b1 - c1), S.rate1, b1) : b1;
                 const float v2 = T2 ? __builtin_fmaf(-__builtin_fmaxf(0.0f, b2 - c2), EQR ? S.rate1 : S.rate2, b2) : b2;
                 const float cap = v1 + v2;
                 ok = ok && cap >= kScreenNeedMargin * need && cap >= peak * (1.0f / kScreenPeakDiv);
                 const float inv_cap = __builtin_amdgcn_rcpf(cap);
-                const float phi = __builtin_fminf(need, cap) * inv_cap;
+                const float phi = need * inv_cap;
                 if constexpr (HOOK) { if (need > 0.0f) min_ratio = __builtin_fminf(min_ratio, cap * __builtin_amdgcn_rcpf(need)); }
                 b1 = __builtin_fmaf(-b1, phi, b1); c1 = __builtin_fmaf(-c1, phi, c1);
                 b2 = __builtin_fmaf(-b2, phi, b2); c2 = __builtin_fmaf(-c2, phi, c2);
             }
-            peak = __builtin_fmaxf(peak, screen_rebalance<TAXED, EQR>(S, b1, c1, b2, c2));
-            ok = ok && __builtin_fminf(b1, b2) > kScreenMinBalance;
+            peak = __builtin_fmaxf(peak, screen_rebalance<TAXED, EQR>(S, K, b1, c1, b2, c2));
+            rmin = __builtin_fminf(rmin, __builtin_fminf(b1, b2));
         }
     }
+    ok = ok && rmin > kScreenMinBalance;
     ok = ok && peak < kScreenMaxTotal;
     const bool safe = valid && ok, doubt = valid && !ok;
     const unsigned long long safe_mask = __builtin_amdgcn_ballot_w64(safe), doubt_mask = __builtin_amdgcn_ballot_w64(doubt);
@@ -2813,28 +2825,36 @@ static ScreenParams screen_params(const DevParams& d) {
     const double b1 = d.initial_balance * d.alloc1;
     s.b1_0 = (float)b1; s.b2_0 = (float)(d.initial_balance - b1);
     s.contrib = (float)d.monthly_contribution; s.contrib_growth_factor = (float)d.contrib_growth_factor;
-    s.expenses = (float)d.monthly_expenses; s.alloc1 = (float)d.alloc1;
+    s.alloc1 = (float)d.alloc1;
+    const double keep0 = d.n_streams > 0 ? d.streams[0].amount_keep : 0.0, keep1 = d.n_streams > 1 ? d.streams[1].amount_keep : 0.0;
+    s.e00 = (float)d.monthly_expenses; s.e10 = (float)(d.monthly_expenses - keep0);
+    s.e01 = (float)(d.monthly_expenses - keep1); s.e11 = (float)(d.monthly_expenses - keep0 - keep1);
     s.rate1 = (float)d.real_rate1; s.rate2 = (float)d.real_rate2;
     s.ar1 = (float)(d.alloc1 * d.real_rate1); s.ar2 = (float)(d.alloc2 * d.real_rate2);
     const int wm = d.working_months;
     auto to_row = [&](int32_t m) { return m > INT32_MAX - wm ? INT32_MAX : m + wm; };      // (path_kernel's StreamRegs)
     auto window_months = [](int first, int end) { return end > first ? (uint32_t)(end - first) : 0u; };
-    if (d.n_streams > 0) { s.sa0 = (float)d.streams[0].amount_keep; s.s0 = to_row(d.streams[0].start_month); s.n0 = window_months(s.s0, to_row(d.streams[0].end_month)); }
-    if (d.n_streams > 1) { s.sa1 = (float)d.streams[1].amount_keep; s.s1 = to_row(d.streams[1].start_month); s.n1 = window_months(s.s1, to_row(d.streams[1].end_month)); }
+    if (d.n_streams > 0) { s.s0 = to_row(d.streams[0].start_month); s.n0 = window_months(s.s0, to_row(d.streams[0].end_month)); }
+    if (d.n_streams > 1) { s.s1 = to_row(d.streams[1].start_month); s.n1 = window_months(s.s1, to_row(d.streams[1].end_month)); }
     s.working_months = wm; s.retirement_years = d.retirement_years; s.total_months = d.total_months; s.contrib_grows = d.contrib_grows;
     return s;
 }
 template <bool HOOK>
 static void launch_screen_kernel(const DevParams& d, const ScreenParams& sp, const ScreenIO& sio, dim3 grid, hipStream_t stream) {
     const bool eqr = month_form_qualified(d) == kMonthEqualRates;
-    switch (d.tax_mask) {
-        case 0: hipLaunchKernelGGL((screen_kernel<0, false, HOOK>), grid, dim3(kBlock), 0, stream, sp, sio); break;
-        case 1: hipLaunchKernelGGL((screen_kernel<1, false, HOOK>), grid, dim3(kBlock), 0, stream, sp, sio); break;
-        case 2: hipLaunchKernelGGL((screen_kernel<2, false, HOOK>), grid, dim3(kBlock), 0, stream, sp, sio); break;
-        default:
-            if (eqr) hipLaunchKernelGGL((screen_kernel<3, true, HOOK>), grid, dim3(kBlock), 0, stream, sp, sio);
-            else hipLaunchKernelGGL((screen_kernel<3, false, HOOK>), grid, dim3(kBlock), 0, stream, sp, sio);
-    }
+    const bool rho0 = d.rho == 0.0;          // (growth_form_qualified's test: binf_rho is then an exact zero)
+    auto go = [&](auto R) {
+        constexpr bool RHO0 = decltype(R)::value;
+        switch (d.tax_mask) {
+            case 0: hipLaunchKernelGGL((screen_kernel<0, false, RHO0, HOOK>), grid, dim3(kBlock), 0, stream, sp, sio); break;
+            case 1: hipLaunchKernelGGL((screen_kernel<1, false, RHO0, HOOK>), grid, dim3(kBlock), 0, stream, sp, sio); break;
+            case 2: hipLaunchKernelGGL((screen_kernel<2, false, RHO0, HOOK>), grid, dim3(kBlock), 0, stream, sp, sio); break;
+            default:
+                if (eqr) hipLaunchKernelGGL((screen_kernel<3, true, RHO0, HOOK>), grid, dim3(kBlock), 0, stream, sp, sio);
+                else hipLaunchKernelGGL((screen_kernel<3, false, RHO0, HOOK>), grid, dim3(kBlock), 0, stream, sp, sio);
+        }
+    };
+    if (rho0) go(std::true_type{}); else go(std::false_type{});
 }
 // One screened launch.  `d` is the launch's parameter block (screen_qualified), `io` its kernel arguments (count-only).  The
 // list and its count are one stream-ordered allocation, 4 n + 8 bytes, the count zeroed on the stream and the block freed

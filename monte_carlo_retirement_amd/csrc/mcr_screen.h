@@ -12,6 +12,20 @@
 // capacity were off by a factor of kScreenNeedMargin (a relative deviation of 0.95) where the expected deviation of the fp32
 // path from the fp64 one is 1e-5 to 1e-4 (833 months of fp32 roundings and ~1e-6 absolute on each normal variate).
 //
+// The month as restated.  The kernel is bound to the fp64 month by a tolerance, not bit for bit, so the month is stated the way
+// that costs the fewest VALU instructions: need = max(0, price x E), E one of the four wave-uniform net levels of ScreenParams,
+// chosen with scalar selects; the price level is carried as its base-2 logarithm L (L += x_inf every month, price = exp2(L) in
+// retirement months only); the yearly contribution step sits behind a scalar branch; and the balance test is one running minimum
+// rmin = min3(rmin, b1, b2), compared with kScreenMinBalance where the class is read: at the exit, and in the whole-wave vote
+// every 8th row pair.  A lane is doubtful when rmin <= kScreenMinBalance exactly as when the test ran every month.
+//
+// Two clamps of the fp64 month are dead here and are not restated.  (1) min(need, cap): a lane that is still ok has
+// cap >= 24 need, so the minimum is `need`; a lane that is not ok stays doubtful whatever its state becomes (`ok` only ever
+// falls, rmin only ever falls).  (2) min(1, fraction_sold) of the rebalance: with w the sold asset's allocation, rate <= 1 and
+// 0 <= G <= bs, drift <= (1 - w) bs <= bs - w rate G, so the quotient is at most 1 up to rounding, for every qualifying
+// parameter block (allocations and rates in [0, 1]); a rounding above 1 leaves the seller's balance negative, which rmin holds
+// from then on: doubtful.
+//
 // Random numbers: the Philox words of growth_parts2_form (mcr_device.h), the same word-to-pair assignment and row order, so
 // normal j of month k is the fp64 kernel's variate to fp32 accuracy.  No LDS tables, no stage.
 #pragma once
@@ -30,18 +44,26 @@ constexpr float kScreenMaxTotal = 1e30f;         // a total beyond this: doubtfu
 struct ScreenParams {
     float a1, b1, ainf, binf_rho, binf_rho_c, aprem, bprem;
     float b1_0, b2_0;                  // initial balances (initial_balance alloc1, initial_balance - that)
-    float contrib, contrib_growth_factor, expenses, alloc1;
+    float contrib, contrib_growth_factor, alloc1;
     float rate1, rate2, ar1, ar2;      // realized-gains rates, and weight x rate (lane_params_tol)
-    float sa0, sa1;                    // netted amounts of the (at most two) indexed income records
-    int32_t s0, s1;                    // their first ROW (start + wm, saturated) ...
+    float e00, e10, e01, e11;          // net need LEVEL per window state of the (at most two) indexed income records: expenses, less
+                                       // the first record's netted amount (e10), less the second's (e01), less both (e11)
+    int32_t s0, s1;                    // the records' first ROW (start + wm, saturated) ...
     uint32_t n0, n1;                   // ... and length in months (StreamRegs of path_kernel)
     int32_t working_months, retirement_years, total_months, contrib_grows;
 };
 
-// The three gross factors (equity, inflation, inv2 = inflation x premium) of the two months of a HALF (growth_parts2_form's
-// halves, words and carry), in registers.  UNIFORM: philox_path_rounds with the wave's path_hi (PhiloxPath::hi_uniform).
-template <int HALF, bool UNIFORM>
-__device__ __forceinline__ void screen_factors2(const ScreenParams& S, const PhiloxPath& Q, uint64_t seed, uint32_t t, PairCarry& C, float (&g)[6]) {
+// The launch constants that meet a second scalar operand in an FMA or a select (the three growth intercepts, the rebalance's
+// weight x rate pair): held in VGPRs across the path, opaque to the compiler (screen_kernel), since a VALU instruction reads one
+// SGPR and the compiler otherwise copies them into a VGPR again every month.
+struct ScreenConsts { float a1, ainf, aprem, ar1, ar2; };
+
+// The growth of the two months of a HALF (growth_parts2_form's halves, words and carry), in registers: per month the equity
+// factor g1, the base-2 logarithm x_inf of the inflation factor and the inv2 factor exp2(x_inf + x_prem) (inflation x premium
+// under one exponential).  UNIFORM: philox_path_rounds with the wave's path_hi (PhiloxPath::hi_uniform).  RHO0: the launch's
+// rho is 0, binf_rho an exact zero, and its term is left out.
+template <int HALF, bool UNIFORM, bool RHO0>
+__device__ __forceinline__ void screen_factors2(const ScreenParams& S, const ScreenConsts& K, const PhiloxPath& Q, uint64_t seed, uint32_t t, PairCarry& C, float (&g)[6]) {
     float rad[3], trig[6];
     auto parts = [&](uint32_t xr, uint32_t xa, int i) {
         // u = (w + 0.5) 2^-32 in (0, 1]; radius = sqrt(-2 ln u) = sqrt(-2 ln 2 log2 u); angle in revolutions
@@ -69,17 +91,18 @@ __device__ __forceinline__ void screen_factors2(const ScreenParams& S, const Phi
     for (int r = 0; r < 2; ++r) {      // growth_factors_row on normals 3 r, 3 r + 1, 3 r + 2 of the half
         const int je = 3 * r, ji = 3 * r + 1, jp = 3 * r + 2;
         const float ne = rad[je >> 1] * trig[je], ni = rad[ji >> 1] * trig[ji], np = rad[jp >> 1] * trig[jp];
-        const float g1 = __builtin_amdgcn_exp2f(__builtin_fmaf(S.b1, ne, S.a1));
-        const float ginf = __builtin_amdgcn_exp2f(__builtin_fmaf(S.binf_rho, ne, __builtin_fmaf(S.binf_rho_c, ni, S.ainf)));
-        const float gprem = __builtin_amdgcn_exp2f(__builtin_fmaf(S.bprem, np, S.aprem));
-        g[3 * r + 0] = g1; g[3 * r + 1] = ginf; g[3 * r + 2] = ginf * gprem;
+        const float g1 = __builtin_amdgcn_exp2f(__builtin_fmaf(S.b1, ne, K.a1));
+        float xinf = __builtin_fmaf(S.binf_rho_c, ni, K.ainf);
+        if (!RHO0) xinf = __builtin_fmaf(S.binf_rho, ne, xinf);
+        const float xprem = __builtin_fmaf(S.bprem, np, K.aprem);
+        g[3 * r + 0] = g1; g[3 * r + 1] = xinf; g[3 * r + 2] = __builtin_amdgcn_exp2f(xinf + xprem);
     }
 }
 
 // rebalance_tol (mcr_device.h) in fp32: selects stay selects, no guard and no dust fix-ups (a lane whose balance falls to
 // kScreenMinBalance is doubtful; with both balances above it every denominator is positive).  Returns b1 + b2 before the trade.
 template <int TAXED, bool EQR>
-__device__ __forceinline__ float screen_rebalance(const ScreenParams& S, float& b1, float& c1, float& b2, float& c2) {
+__device__ __forceinline__ float screen_rebalance(const ScreenParams& S, const ScreenConsts& K, float& b1, float& c1, float& b2, float& c2) {
     const float total = b1 + b2;
     const float drift1 = __builtin_fmaf(-total, S.alloc1, b1);
     const bool sell1 = drift1 > 0.0f;
@@ -88,12 +111,12 @@ __device__ __forceinline__ float screen_rebalance(const ScreenParams& S, float& 
     float fraction_sold, net_purchase;
     if (TAXED != 0) {
         const float rate_s = EQR ? S.rate1 : sell1 ? S.rate1 : S.rate2;
-        const float ar_s = sell1 ? S.ar1 : S.ar2;
+        const float ar_s = sell1 ? K.ar1 : K.ar2;
         const float G = __builtin_fmaxf(0.0f, bs - cs);
-        fraction_sold = __builtin_fminf(1.0f, drift * __builtin_amdgcn_rcpf(__builtin_fmaf(-ar_s, G, bs)));
+        fraction_sold = drift * __builtin_amdgcn_rcpf(__builtin_fmaf(-ar_s, G, bs));
         net_purchase = fraction_sold * __builtin_fmaf(-G, rate_s, bs);
     } else {
-        fraction_sold = __builtin_fminf(1.0f, drift * __builtin_amdgcn_rcpf(bs));
+        fraction_sold = drift * __builtin_amdgcn_rcpf(bs);
         net_purchase = fraction_sold * bs;
     }
     const float nbs = __builtin_fmaf(-bs, fraction_sold, bs), ncs = __builtin_fmaf(-cs, fraction_sold, cs);

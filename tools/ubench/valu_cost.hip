@@ -90,6 +90,12 @@ KERNEL(mix_xor_per_fma, double, seed + threadIdx.x + c, { uint32_t t; asm volati
 KERNEL(lshl_add_u32, uint32_t, seed + threadIdx.x + c, asm volatile("v_lshl_add_u32 %0, %0, 3, %1" : "+v"(x) : "v"(seed)))
 KERNEL(add3_u32, uint32_t, seed + threadIdx.x + c, ASM3("v_add3_u32"))
 KERNEL(frexp_exp_f64, double, seed + threadIdx.x + c, { uint32_t e; asm volatile("v_frexp_exp_i32_f64 %0, %1" : "=v"(e) : "v"(x)); })
+// the screening kernel's Box-Muller angle: one v_alignbit_b32 (the word's top 23 bits under exponent 0x7F) against the
+// v_cvt_f32_u32 + v_mul_f32 pair it replaces
+KERNEL(alignbit_b32, uint32_t, seed + threadIdx.x + c, asm volatile("v_alignbit_b32 %0, %1, %0, 9" : "+v"(x) : "v"(seed)))
+KERNEL(alignbit_b32_sgpr, uint32_t, seed + threadIdx.x + c, asm volatile("v_alignbit_b32 %0, s20, %0, 9" : "+v"(x)))
+KERNEL(cvt_f32_u32, uint32_t, seed + threadIdx.x + c, ASM1("v_cvt_f32_u32"))
+KERNEL(mul_f32, float, seed + threadIdx.x + c, ASM2("v_mul_f32"))
 
 template <typename T>
 static void run(const char* name, void (*k)(T*, T), T seed) {
@@ -134,5 +140,6 @@ int main() {
     RUN(mix_mad64_per_fma, double, 1.0000001);
     RUN(mad_u64_u32_sgpr, uint64_t, 3); RUN(xor_b32_sgpr, uint32_t, 3); RUN(mix_mad64_sgpr_per_fma, double, 1.0000001);
     RUN(mix_bitop3_per_fma, double, 1.0000001); RUN(mix_bitop3_sgpr_per_fma, double, 1.0000001); RUN(mix_xor_per_fma, double, 1.0000001);
+    RUN(alignbit_b32, uint32_t, 3); RUN(alignbit_b32_sgpr, uint32_t, 3); RUN(cvt_f32_u32, uint32_t, 3); RUN(mul_f32, float, 1.0000001f);
     return 0;
 }
