@@ -1576,7 +1576,8 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
 // and instead of the dust fix-ups a lane becomes DOUBTFUL when a balance falls to one dollar.  (The rebalance that closes a
 // tax year without an annual-gains tax comes right behind the month's own and moves a rounding's worth: it is left out.)
 // The month is stated as mcr_screen.h's "month as restated" says: one net need level per window state, the price level as a
-// logarithm, no dead clamps, a running minimum of the balances.  RHO0: a launch whose rho is 0 (screen_factors2).
+// logarithm, no dead clamps, one compare for both capacity tests, closed-form balances, a running minimum of the balances.
+// The rows run four to a loop iteration, one loop per Philox form (screen_rows).  RHO0: a launch whose rho is 0 (screen_factors2).
 // A lane is SAFE only if in every retirement month cap >= kScreenNeedMargin need and cap >= peak / kScreenPeakDiv, `need` and
 // `cap` the month's own values and `peak` the running maximum of b1 + b2 (need <= 0: the second test alone decides, as the
 // first then holds for any positive cap).  SAFE lanes are counted as path_kernel's epilogue counts a successful path whose
@@ -1595,10 +1596,86 @@ struct ScreenIO {
     float* min_ratio;            // HOOK: [n_paths] lowest cap / need of the months the lane ran (+inf: no month with a need)
     float* final_total;          // HOOK: [n_paths] b1 + b2 where the lane stopped
 };
+// One lane's state across the path
+struct ScreenLane { float b1, c1, b2, c2, lvl, peak, contrib, k1, k2, rmin, min_ratio; bool ok; };
+// The four net levels as words in SGPRs, opaque to the compiler (screen_kernel): selected with s_cselect_b32.  Passed by
+// value: by reference the selects become one indexed read of a 16-byte table, which the backend places in LDS
+struct ScreenLevels { uint32_t e00, e10, e01, e11; };
+// One month of one lane: row m (wave-uniform), its growth (screen_factors2), `moy` the accumulation month of the year
+template <int TAXED, bool EQR, bool HOOK>
+__device__ __forceinline__ void screen_month(const ScreenParams& S, const ScreenConsts& K, const ScreenLevels E, ScreenLane& L, int& moy, int m, float g1, float xinf, float g2) {
+    constexpr bool T1 = (TAXED & 1) != 0, T2 = (TAXED & 2) != 0;
+    if (m < S.working_months) {                              // accumulation (:513-553)
+        if (moy == kMPY) {
+            moy = 0;
+            if (S.contrib_grows) {
+                asm volatile("");                            // (keeps the yearly step a scalar branch: if-converted, it costs six VALU every month)
+                L.contrib *= S.contrib_growth_factor; L.k1 = L.contrib * S.alloc1; L.k2 = L.contrib - L.k1;
+            }
+        }
+        ++moy;
+        L.b1 *= g1; L.b2 *= g2; L.lvl += xinf;
+        L.b1 += L.k1; L.c1 += L.k1; L.b2 += L.k2; L.c2 += L.k2;
+    } else {                                                 // decumulation (:644-796)
+        const float price = __builtin_amdgcn_exp2f(L.lvl);
+        const bool w0 = (unsigned)(m - S.s0) < S.n0, w1 = (unsigned)(m - S.s1) < S.n1;
+        const float level = __builtin_bit_cast(float, w0 ? (w1 ? E.e11 : E.e10) : (w1 ? E.e01 : E.e00));     // (s_cselect_b32)
+        const float need = price * level;                            // (level >= 0: clamped where it is derived, screen_params)
+        L.b1 *= g1; L.b2 *= g2; L.lvl += xinf;
+        const float v1 = T1 ? __builtin_fmaf(-__builtin_fmaxf(0.0f, L.b1 - L.c1), S.rate1, L.b1) : L.b1;
+        const float v2 = T2 ? __builtin_fmaf(-__builtin_fmaxf(0.0f, L.b2 - L.c2), EQR ? S.rate1 : S.rate2, L.b2) : L.b2;
+        const float cap = v1 + v2;
+        L.ok = L.ok && cap >= __builtin_fmaxf(kScreenNeedMargin * need, L.peak * (1.0f / kScreenPeakDiv));      // (both tests under one compare)
+        const float inv_cap = __builtin_amdgcn_rcpf(cap);
+        const float phi = need * inv_cap;
+        if constexpr (HOOK) { if (need > 0.0f) L.min_ratio = __builtin_fminf(L.min_ratio, cap * __builtin_amdgcn_rcpf(need)); }
+        L.b1 = __builtin_fmaf(-L.b1, phi, L.b1); L.c1 = __builtin_fmaf(-L.c1, phi, L.c1);
+        L.b2 = __builtin_fmaf(-L.b2, phi, L.b2); L.c2 = __builtin_fmaf(-L.c2, phi, L.c2);
+    }
+    L.peak = __builtin_fmaxf(L.peak, screen_rebalance<TAXED, EQR>(S, K, L.b1, L.c1, L.b2, L.c2));
+    L.rmin = __builtin_fminf(L.rmin, __builtin_fminf(L.b1, L.b2));
+}
+// The rows of a path, four to an iteration: HALF 0 and HALF 1 of one Philox block triple straight-line, the pair carry local to
+// the iteration (carried across a two-row loop's back edge it travelled between two register pairs, four v_mov a row pair, and
+// the four-arm choice of half and form left three v_readfirstlane_b32 of undefined values in the loop header).  Functions over
+// a state struct, not lambdas: a capturing lambda of this size is inlined too late for its captures to leave private memory,
+// and every scalar select then becomes a v_cndmask.  UNIFORM: screen_factors2, chosen once outside the loop.
+template <int TAXED, bool EQR, bool RHO0, bool HOOK, bool UNIFORM>
+__device__ __forceinline__ void screen_rows(const ScreenParams& S, const ScreenConsts& K, const ScreenLevels E, const PhiloxPath& PQ, uint64_t seed, ScreenLane& L) {
+    const int total = S.total_months;
+    // laggards first, as in path_kernel: the wave's priority falls at half, three quarters and nine tenths of the path (even rows)
+    const int prio_t1 = (total / 2) & ~1, prio_t2 = ((total * 3) / 4) & ~1, prio_t3 = ((total * 9) / 10) & ~1;
+    int prio_next = prio_t1;
+    int moy = 0;                                                     // accumulation month of the year, 0 .. 11
+    auto prio = [&](int row) {
+        if (row == prio_next) {
+            if (row == prio_t1) __builtin_amdgcn_s_setprio(2);
+            else if (row == prio_t2) __builtin_amdgcn_s_setprio(1);
+            else if (row == prio_t3) __builtin_amdgcn_s_setprio(0);
+            prio_next = prio_from(prio_t1, prio_t2, prio_t3, row + 2);
+        }
+    };
+    for (int row = 0; row < total; row += 4) {
+        // every lane of the wave is doubtful: nothing left to decide (asked every 16th row)
+        if ((row & 12) == 0 && __builtin_amdgcn_ballot_w64(L.ok && L.rmin > kScreenMinBalance) == 0ull) break;
+        PairCarry carry;
+        float g[6];
+        prio(row);
+        screen_factors2<0, UNIFORM, RHO0>(S, K, PQ, seed, (uint32_t)row >> 2, carry, g);
+        screen_month<TAXED, EQR, HOOK>(S, K, E, L, moy, row, g[0], g[1], g[2]);
+        if (row + 1 >= total) break;
+        screen_month<TAXED, EQR, HOOK>(S, K, E, L, moy, row + 1, g[3], g[4], g[5]);
+        if (row + 2 >= total) break;
+        prio(row + 2);
+        screen_factors2<1, UNIFORM, RHO0>(S, K, PQ, seed, (uint32_t)row >> 2, carry, g);
+        screen_month<TAXED, EQR, HOOK>(S, K, E, L, moy, row + 2, g[0], g[1], g[2]);
+        if (row + 3 >= total) break;
+        screen_month<TAXED, EQR, HOOK>(S, K, E, L, moy, row + 3, g[3], g[4], g[5]);
+    }
+}
 template <int TAXED, bool EQR, bool RHO0, bool HOOK = false>
 __global__ __launch_bounds__(kBlock, 8) void screen_kernel(const ScreenParams S, const ScreenIO io) {
     static_assert(TAXED >= 0 && TAXED <= 3 && (!EQR || TAXED == 3), "TAXED is path_kernel's mask; equal rates need both assets taxed");
-    constexpr bool T1 = (TAXED & 1) != 0, T2 = (TAXED & 2) != 0;
     __shared__ unsigned int safe_s;
     if (threadIdx.x == 0) safe_s = 0u;
     __syncthreads();
@@ -1606,79 +1683,23 @@ __global__ __launch_bounds__(kBlock, 8) void screen_kernel(const ScreenParams S,
     const bool valid = local < io.n_paths;
     const uint64_t path = io.path_begin + (valid ? local : io.n_paths - 1);   // tail lanes shadow the last path
     const PhiloxPath PQ = philox_path(path, io.stream_id, io.seed);           // (the whole wave is here: philox_path's ballot)
-    float b1 = S.b1_0, b2 = S.b2_0, c1 = b1, c2 = b2;
-    float lvl = 0.0f;                                                // log2 of the price level
-    float peak = b1 + b2;
-    float contrib = S.contrib, k1 = contrib * S.alloc1, k2 = contrib - k1;
-    bool ok = true;
-    float rmin = __builtin_fminf(b1, b2);
-    [[maybe_unused]] float min_ratio = __builtin_inff();
-    PairCarry carry{0u, 0u};
+    ScreenLane L;
+    L.b1 = S.b1_0; L.b2 = S.b2_0; L.c1 = L.b1; L.c2 = L.b2;
+    L.lvl = 0.0f;                                                    // log2 of the price level
+    L.peak = L.b1 + L.b2;
+    L.contrib = S.contrib; L.k1 = L.contrib * S.alloc1; L.k2 = L.contrib - L.k1;
+    L.ok = true;
+    L.rmin = __builtin_fminf(L.b1, L.b2);
+    L.min_ratio = __builtin_inff();
     ScreenConsts K{S.a1, S.ainf, S.aprem, S.ar1, S.ar2};
     asm volatile("" : "+v"(K.a1), "+v"(K.ainf), "+v"(K.aprem), "+v"(K.ar1), "+v"(K.ar2));      // (ScreenConsts: VGPRs for the whole path)
-    const int wm = S.working_months, total = S.total_months;
-    int moy = 0;                                                     // accumulation month of the year, 0 .. 11
-    // laggards first, as in path_kernel: the wave's priority falls at half, three quarters and nine tenths of the path (even rows)
-    const int prio_t1 = (total / 2) & ~1, prio_t2 = ((total * 3) / 4) & ~1, prio_t3 = ((total * 9) / 10) & ~1;
-    int prio_next = prio_t1;
+    ScreenLevels E{__builtin_bit_cast(uint32_t, S.e00), __builtin_bit_cast(uint32_t, S.e10), __builtin_bit_cast(uint32_t, S.e01), __builtin_bit_cast(uint32_t, S.e11)};
+    asm volatile("" : "+s"(E.e00), "+s"(E.e10), "+s"(E.e01), "+s"(E.e11));                     // (ScreenLevels: SGPRs, selected as words)
     __builtin_amdgcn_s_setprio(3);
-    for (int row = 0; row < total; row += 2) {
-        // every lane of the wave is doubtful: nothing left to decide (asked every 8th row pair)
-        if ((row & 14) == 0 && __builtin_amdgcn_ballot_w64(ok && rmin > kScreenMinBalance) == 0ull) break;
-        if (row == prio_next) {
-            if (row == prio_t1) __builtin_amdgcn_s_setprio(2);
-            else if (row == prio_t2) __builtin_amdgcn_s_setprio(1);
-            else if (row == prio_t3) __builtin_amdgcn_s_setprio(0);
-            prio_next = prio_from(prio_t1, prio_t2, prio_t3, row + 2);
-        }
-        float g[6];
-        if (PQ.hi_uniform) {
-            if ((row & 2) == 0) screen_factors2<0, true, RHO0>(S, K, PQ, io.seed, (uint32_t)row >> 2, carry, g);
-            else screen_factors2<1, true, RHO0>(S, K, PQ, io.seed, (uint32_t)row >> 2, carry, g);
-        } else {                                                     // a wave that straddles a multiple of 2^32 paths
-            if ((row & 2) == 0) screen_factors2<0, false, RHO0>(S, K, PQ, io.seed, (uint32_t)row >> 2, carry, g);
-            else screen_factors2<1, false, RHO0>(S, K, PQ, io.seed, (uint32_t)row >> 2, carry, g);
-        }
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const int m = row + r;                                   // wave-uniform
-            if (m >= total) break;
-            const float g1 = g[3 * r], xinf = g[3 * r + 1], g2 = g[3 * r + 2];
-            if (m < wm) {                                            // accumulation (:513-553)
-                if (moy == kMPY) {
-                    moy = 0;
-                    if (S.contrib_grows) {
-                        asm volatile("");                            // (keeps the yearly step a scalar branch: if-converted, it costs six VALU every month)
-                        contrib *= S.contrib_growth_factor; k1 = contrib * S.alloc1; k2 = contrib - k1;
-                    }
-                }
-                ++moy;
-                b1 *= g1; b2 *= g2; lvl += xinf;
-                b1 += k1; c1 += k1; b2 += k2; c2 += k2;
-            } else {                                                 // decumulation (:644-796)
-                const float price = __builtin_amdgcn_exp2f(lvl);
-                const bool w0 = (unsigned)(m - S.s0) < S.n0, w1 = (unsigned)(m - S.s1) < S.n1;
-                const uint32_t on0 = w1 ? __builtin_bit_cast(uint32_t, S.e11) : __builtin_bit_cast(uint32_t, S.e10);
-                const uint32_t off0 = w1 ? __builtin_bit_cast(uint32_t, S.e01) : __builtin_bit_cast(uint32_t, S.e00);
-                const float level = __builtin_bit_cast(float, w0 ? on0 : off0);      // (selected as words: s_cselect_b32, not v_cndmask)
-                const float need = __builtin_fmaxf(0.0f, price * level);
-                b1 *= g1; b2 *= g2; lvl += xinf;
-                const float v1 = T1 ? __builtin_fmaf(-__builtin_fmaxf(0.0f, b1 - c1), S.rate1, b1) : b1;
-                const float v2 = T2 ? __builtin_fmaf(-__builtin_fmaxf(0.0f, b2 - c2), EQR ? S.rate1 : S.rate2, b2) : b2;
-                const float cap = v1 + v2;
-                ok = ok && cap >= kScreenNeedMargin * need && cap >= peak * (1.0f / kScreenPeakDiv);
-                const float inv_cap = __builtin_amdgcn_rcpf(cap);
-                const float phi = need * inv_cap;
-                if constexpr (HOOK) { if (need > 0.0f) min_ratio = __builtin_fminf(min_ratio, cap * __builtin_amdgcn_rcpf(need)); }
-                b1 = __builtin_fmaf(-b1, phi, b1); c1 = __builtin_fmaf(-c1, phi, c1);
-                b2 = __builtin_fmaf(-b2, phi, b2); c2 = __builtin_fmaf(-c2, phi, c2);
-            }
-            peak = __builtin_fmaxf(peak, screen_rebalance<TAXED, EQR>(S, K, b1, c1, b2, c2));
-            rmin = __builtin_fminf(rmin, __builtin_fminf(b1, b2));
-        }
-    }
-    ok = ok && rmin > kScreenMinBalance;
-    ok = ok && peak < kScreenMaxTotal;
+    if (PQ.hi_uniform) screen_rows<TAXED, EQR, RHO0, HOOK, true>(S, K, E, PQ, io.seed, L);
+    else screen_rows<TAXED, EQR, RHO0, HOOK, false>(S, K, E, PQ, io.seed, L);                  // (a wave that straddles a multiple of 2^32 paths)
+    bool ok = L.ok && L.rmin > kScreenMinBalance;
+    ok = ok && L.peak < kScreenMaxTotal;
     const bool safe = valid && ok, doubt = valid && !ok;
     const unsigned long long safe_mask = __builtin_amdgcn_ballot_w64(safe), doubt_mask = __builtin_amdgcn_ballot_w64(doubt);
     const unsigned int lane = threadIdx.x & 63u;
@@ -1693,8 +1714,8 @@ __global__ __launch_bounds__(kBlock, 8) void screen_kernel(const ScreenParams S,
     if constexpr (HOOK) {
         if (valid) {
             if (io.cls) io.cls[local] = ok ? MCR_SCREEN_SAFE : MCR_SCREEN_DOUBTFUL;
-            if (io.min_ratio) io.min_ratio[local] = min_ratio;
-            if (io.final_total) io.final_total[local] = b1 + b2;
+            if (io.min_ratio) io.min_ratio[local] = L.min_ratio;
+            if (io.final_total) io.final_total[local] = L.b1 + L.b2;
         }
     }
     __syncthreads();
@@ -2817,18 +2838,20 @@ static double screen_expected() {
 // The screening kernel's parameter block: every value derived in double, rounded once
 static ScreenParams screen_params(const DevParams& d) {
     const double log2e = 1.4426950408889634074;
+    const double bscale = log2e * 1.1774100225154746910;      // the slopes carry sqrt(2 ln 2): a normal is sqrt(-log2 u) x trig (screen_factors2)
     ScreenParams s;
     std::memset(&s, 0, sizeof(s));
-    s.a1 = (float)(d.a1 * log2e); s.b1 = (float)(d.b1 * log2e);
-    s.ainf = (float)(d.ainf * log2e); s.binf_rho = (float)(d.binf_rho * log2e); s.binf_rho_c = (float)(d.binf_rho_c * log2e);
-    s.aprem = (float)(d.aprem * log2e); s.bprem = (float)(d.bprem * log2e);
+    s.a1 = (float)(d.a1 * log2e); s.b1 = (float)(d.b1 * bscale);
+    s.ainf = (float)(d.ainf * log2e); s.binf_rho = (float)(d.binf_rho * bscale); s.binf_rho_c = (float)(d.binf_rho_c * bscale);
+    s.aprem = (float)(d.aprem * log2e); s.bprem = (float)(d.bprem * bscale);
     const double b1 = d.initial_balance * d.alloc1;
     s.b1_0 = (float)b1; s.b2_0 = (float)(d.initial_balance - b1);
     s.contrib = (float)d.monthly_contribution; s.contrib_growth_factor = (float)d.contrib_growth_factor;
     s.alloc1 = (float)d.alloc1;
     const double keep0 = d.n_streams > 0 ? d.streams[0].amount_keep : 0.0, keep1 = d.n_streams > 1 ? d.streams[1].amount_keep : 0.0;
-    s.e00 = (float)d.monthly_expenses; s.e10 = (float)(d.monthly_expenses - keep0);
-    s.e01 = (float)(d.monthly_expenses - keep1); s.e11 = (float)(d.monthly_expenses - keep0 - keep1);
+    auto lvl0 = [](double e) { return (float)(e < 0.0 ? 0.0 : e); };       // (price > 0: max(0, price x E) = price x max(0, E))
+    s.e00 = lvl0(d.monthly_expenses); s.e10 = lvl0(d.monthly_expenses - keep0);
+    s.e01 = lvl0(d.monthly_expenses - keep1); s.e11 = lvl0(d.monthly_expenses - keep0 - keep1);
     s.rate1 = (float)d.real_rate1; s.rate2 = (float)d.real_rate2;
     s.ar1 = (float)(d.alloc1 * d.real_rate1); s.ar2 = (float)(d.alloc2 * d.real_rate2);
     const int wm = d.working_months;

@@ -13,18 +13,29 @@
 // path from the fp64 one is 1e-5 to 1e-4 (833 months of fp32 roundings and ~1e-6 absolute on each normal variate).
 //
 // The month as restated.  The kernel is bound to the fp64 month by a tolerance, not bit for bit, so the month is stated the way
-// that costs the fewest VALU instructions: need = max(0, price x E), E one of the four wave-uniform net levels of ScreenParams,
-// chosen with scalar selects; the price level is carried as its base-2 logarithm L (L += x_inf every month, price = exp2(L) in
-// retirement months only); the yearly contribution step sits behind a scalar branch; and the balance test is one running minimum
-// rmin = min3(rmin, b1, b2), compared with kScreenMinBalance where the class is read: at the exit, and in the whole-wave vote
-// every 8th row pair.  A lane is doubtful when rmin <= kScreenMinBalance exactly as when the test ran every month.
+// that costs the fewest VALU instructions: need = price x E, E one of the four wave-uniform net levels of ScreenParams, clamped
+// at zero where they are derived (price > 0, so max(0, price x E) = price x max(0, E)) and chosen with scalar selects of their
+// words (ScreenLevels, mcr_hip.hip); the price level is carried as its base-2 logarithm L (L += x_inf every month, price = exp2(L)
+// in retirement months only); the yearly contribution step sits behind a scalar branch; the two capacity tests are one compare,
+// cap >= max(24 need, peak / 64), the same predicate bit for bit; the Box-Muller radius is sqrt(-log2 u), its constant
+// sqrt(2 ln 2) folded into the growth slopes in double; the rebalance states the balances in closed form (screen_rebalance:
+// b1 = alloc1 T', b2 = T' - b1, T' = T - f bs + net_purchase, which moves them by fp32 roundings of the total a month, inside
+// the tolerance); and the balance test is one running minimum rmin = min3(rmin, b1, b2), compared with kScreenMinBalance where
+// the class is read: at the exit, and in the whole-wave vote every 16th row.  A lane is doubtful when rmin <= kScreenMinBalance
+// exactly as when the test ran every month.  The rows run four to a loop iteration (screen_rows, mcr_hip.hip): both halves of
+// a Philox block triple straight-line, the pair carry local to the iteration, one loop per Philox form.
 //
 // Two clamps of the fp64 month are dead here and are not restated.  (1) min(need, cap): a lane that is still ok has
 // cap >= 24 need, so the minimum is `need`; a lane that is not ok stays doubtful whatever its state becomes (`ok` only ever
 // falls, rmin only ever falls).  (2) min(1, fraction_sold) of the rebalance: with w the sold asset's allocation, rate <= 1 and
-// 0 <= G <= bs, drift <= (1 - w) bs <= bs - w rate G, so the quotient is at most 1 up to rounding, for every qualifying
-// parameter block (allocations and rates in [0, 1]); a rounding above 1 leaves the seller's balance negative, which rmin holds
-// from then on: doubtful.
+// 0 <= G <= bs, drift <= (1 - w) bs <= bs - w rate G, so the quotient f is at most 1 up to rounding, for every qualifying
+// parameter block (allocations and rates in [0, 1]), and it comes near 1 only where w (bs - rate G) is near 0: the seller's
+// allocation is 0, or rate = 1 with a cost basis of 0.  With closed-form balances a rounding of f above 1 no longer turns the
+// seller's balance negative; what it does is bounded instead.  f = 1 + e (e a few 2^-24) leaves the seller's cost basis at
+// cs' = -e cs, a rounding's worth of cs below zero, which enters later months only through G = max(0, b - c): a gain larger by
+// e cs.  T' = T - f rate G is linear in f with no sign to lose: it moves by e rate G <= e T, a rounding of the total like any
+// other.  And the two cases that bring f near 1 are doubtful on their own: with w = 0 the seller's new balance is w T' = 0,
+// which rmin holds from then on; a cost basis of 0 needs a balance of 0 at the start or a sale of f = 1 exactly, the first case.
 //
 // Random numbers: the Philox words of growth_parts2_form (mcr_device.h), the same word-to-pair assignment and row order, so
 // normal j of month k is the fp64 kernel's variate to fp32 accuracy.  No LDS tables, no stage.
@@ -40,14 +51,15 @@ constexpr float kScreenMinBalance = 1.0f;        // a balance at or below one do
 constexpr float kScreenMaxTotal = 1e30f;         // a total beyond this: doubtful (every fp32 intermediate of a SAFE path is finite)
 
 // Wave-uniform parameter block of the screening kernel, derived on the host in double and rounded once (screen_params,
-// mcr_hip.hip).  The growth coefficients are pre-scaled by log2(e): a factor is exp2(fma(b', r t, a')).
+// mcr_hip.hip).  The growth coefficients are pre-scaled by log2(e), the slopes b also by sqrt(2 ln 2) (the Box-Muller radius
+// constant, screen_factors2): a factor is exp2(fma(b', sqrt(-log2 u) t, a')).
 struct ScreenParams {
     float a1, b1, ainf, binf_rho, binf_rho_c, aprem, bprem;
     float b1_0, b2_0;                  // initial balances (initial_balance alloc1, initial_balance - that)
     float contrib, contrib_growth_factor, alloc1;
     float rate1, rate2, ar1, ar2;      // realized-gains rates, and weight x rate (lane_params_tol)
     float e00, e10, e01, e11;          // net need LEVEL per window state of the (at most two) indexed income records: expenses, less
-                                       // the first record's netted amount (e10), less the second's (e01), less both (e11)
+                                       // the first record's netted amount (e10), less the second's (e01), less both (e11); each >= 0
     int32_t s0, s1;                    // the records' first ROW (start + wm, saturated) ...
     uint32_t n0, n1;                   // ... and length in months (StreamRegs of path_kernel)
     int32_t working_months, retirement_years, total_months, contrib_grows;
@@ -66,9 +78,10 @@ template <int HALF, bool UNIFORM, bool RHO0>
 __device__ __forceinline__ void screen_factors2(const ScreenParams& S, const ScreenConsts& K, const PhiloxPath& Q, uint64_t seed, uint32_t t, PairCarry& C, float (&g)[6]) {
     float rad[3], trig[6];
     auto parts = [&](uint32_t xr, uint32_t xa, int i) {
-        // u = (w + 0.5) 2^-32 in (0, 1]; radius = sqrt(-2 ln u) = sqrt(-2 ln 2 log2 u); angle in revolutions
+        // u = (w + 0.5) 2^-32 in (0, 1]; radius = sqrt(-2 ln u) = sqrt(2 ln 2) sqrt(-log2 u), the constant folded into the slopes
+        // (screen_params), the negation a source modifier of v_sqrt_f32; angle in revolutions
         const float u = __builtin_fmaf((float)xr, 0x1p-32f, 0x1p-33f);
-        rad[i] = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u));
+        rad[i] = __builtin_amdgcn_sqrtf(-__builtin_amdgcn_logf(u));
         const float rev = (float)xa * 0x1p-32f;
         trig[2 * i] = __builtin_amdgcn_cosf(rev);
         trig[2 * i + 1] = __builtin_amdgcn_sinf(rev);
@@ -119,10 +132,13 @@ __device__ __forceinline__ float screen_rebalance(const ScreenParams& S, const S
         fraction_sold = drift * __builtin_amdgcn_rcpf(bs);
         net_purchase = fraction_sold * bs;
     }
-    const float nbs = __builtin_fmaf(-bs, fraction_sold, bs), ncs = __builtin_fmaf(-cs, fraction_sold, cs);
-    const float r1b = b1 + net_purchase, r1c = c1 + net_purchase, r2b = b2 + net_purchase, r2c = c2 + net_purchase;
-    b1 = sell1 ? nbs : r1b; c1 = sell1 ? ncs : r1c;
-    b2 = sell1 ? r2b : nbs; c2 = sell1 ? r2c : ncs;
+    const float ncs = __builtin_fmaf(-cs, fraction_sold, cs);
+    const float r1c = c1 + net_purchase, r2c = c2 + net_purchase;
+    c1 = sell1 ? ncs : r1c; c2 = sell1 ? r2c : ncs;
+    // the balances in closed form: the trade leaves b1 = alloc1 T' and b2 = T' - b1 whoever sells, T' the total less the tax on
+    // the realised share (untaxed: the total itself)
+    const float after = TAXED != 0 ? __builtin_fmaf(-fraction_sold, bs, total) + net_purchase : total;
+    b1 = after * S.alloc1; b2 = after - b1;
     return total;
 }
 

@@ -96,6 +96,12 @@ KERNEL(alignbit_b32, uint32_t, seed + threadIdx.x + c, asm volatile("v_alignbit_
 KERNEL(alignbit_b32_sgpr, uint32_t, seed + threadIdx.x + c, asm volatile("v_alignbit_b32 %0, s20, %0, 9" : "+v"(x)))
 KERNEL(cvt_f32_u32, uint32_t, seed + threadIdx.x + c, ASM1("v_cvt_f32_u32"))
 KERNEL(mul_f32, float, seed + threadIdx.x + c, ASM2("v_mul_f32"))
+// the packed fp32 forms the compiler's SLP pass makes of the screening kernel's adjacent multiplies, FMAs and adds (a register
+// pair per operand, held in a double): one of them against the two plain instructions it replaces
+KERNEL(pk_fma_f32, double, seed + threadIdx.x + c, ASM3("v_pk_fma_f32"))
+KERNEL(pk_mul_f32, double, seed + threadIdx.x + c, ASM2("v_pk_mul_f32"))
+KERNEL(pk_add_f32, double, seed + threadIdx.x + c, ASM2("v_pk_add_f32"))
+KERNEL(add_f32, float, seed + threadIdx.x + c, ASM2("v_add_f32"))
 
 template <typename T>
 static void run(const char* name, void (*k)(T*, T), T seed) {
@@ -141,5 +147,6 @@ int main() {
     RUN(mad_u64_u32_sgpr, uint64_t, 3); RUN(xor_b32_sgpr, uint32_t, 3); RUN(mix_mad64_sgpr_per_fma, double, 1.0000001);
     RUN(mix_bitop3_per_fma, double, 1.0000001); RUN(mix_bitop3_sgpr_per_fma, double, 1.0000001); RUN(mix_xor_per_fma, double, 1.0000001);
     RUN(alignbit_b32, uint32_t, 3); RUN(alignbit_b32_sgpr, uint32_t, 3); RUN(cvt_f32_u32, uint32_t, 3); RUN(mul_f32, float, 1.0000001f);
+    RUN(pk_fma_f32, double, 1.0000001); RUN(pk_mul_f32, double, 1.0000001); RUN(pk_add_f32, double, 1e-9); RUN(add_f32, float, 1e-9f);
     return 0;
 }
