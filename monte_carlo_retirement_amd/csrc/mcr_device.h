@@ -873,23 +873,43 @@ __device__ __forceinline__ void sell_fraction_tol(double phi, double& b1, double
 // rate is not a per-lane choice and its select goes (the seller's weight x rate keeps its own).  The rate is read from the
 // lanes' resident copy, not from the scalar block: the kernel has no SGPR pair to spare (as a scalar operand it came back as
 // v_readlane + s_nop at every use).
-template <bool TAXED, bool MM = true, bool UNIFORM = false, bool EQR = false>
+// MASKSEL (the lone consumer wave of the screened launch's split re-run): the seller's three selects take their condition
+// from an SGPR pair (v_cndmask_b32_e64 with the compare's ballot) instead of the VCC-implicit encoding behind v_cmp + s_nop
+// (tools/ubench/valu_cost.hip: 4.7 against 22.6 cycles an instruction); the same words either way.
+__device__ __forceinline__ void seller_select3(bool sell1, double a1, double a2, double b1, double b2, double c1, double c2, double& a, double& b, double& c) {
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(sell1);
+    auto bits = [](double x) { return (unsigned long long)__double_as_longlong(x); };
+    const unsigned long long a1b = bits(a1), a2b = bits(a2), b1b = bits(b1), b2b = bits(b2), c1b = bits(c1), c2b = bits(c2);
+    uint32_t alo, ahi, blo, bhi, clo, chi;
+    asm("s_nop 1\n\tv_cndmask_b32_e64 %0, %7, %6, %18\n\tv_cndmask_b32_e64 %1, %9, %8, %18\n\tv_cndmask_b32_e64 %2, %11, %10, %18\n\t"
+        "v_cndmask_b32_e64 %3, %13, %12, %18\n\tv_cndmask_b32_e64 %4, %15, %14, %18\n\tv_cndmask_b32_e64 %5, %17, %16, %18"
+        : "=&v"(alo), "=&v"(ahi), "=&v"(blo), "=&v"(bhi), "=&v"(clo), "=&v"(chi)
+        : "v"((uint32_t)a1b), "v"((uint32_t)a2b), "v"((uint32_t)(a1b >> 32)), "v"((uint32_t)(a2b >> 32)),
+          "v"((uint32_t)b1b), "v"((uint32_t)b2b), "v"((uint32_t)(b1b >> 32)), "v"((uint32_t)(b2b >> 32)),
+          "v"((uint32_t)c1b), "v"((uint32_t)c2b), "v"((uint32_t)(c1b >> 32)), "v"((uint32_t)(c2b >> 32)), "s"(m));
+    auto f64 = [](uint32_t hi, uint32_t lo) { return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo)); };
+    a = f64(ahi, alo); b = f64(bhi, blo); c = f64(chi, clo);
+}
+template <bool TAXED, bool MM = true, bool UNIFORM = false, bool EQR = false, bool MASKSEL = false>
 __device__ __forceinline__ void rebalance_tol(const DevParams& P, const LaneParams& L, double& b1, double& c1, double& b2, double& c2) {
     const double total = b1 + b2;                                  // :288
     const double drift1 = __builtin_fma(-total, P.alloc1, b1);     // :293-294
     if (UNIFORM && wave_any(fmin(total, fabs(drift1)) <= kEps)) {  // (one compare: a ballot of an OR comes out as a 0/1 VGPR compared again)
-        rebalance_tol<TAXED, MM, false, EQR>(P, L, b1, c1, b2, c2);
+        rebalance_tol<TAXED, MM, false, EQR, MASKSEL>(P, L, b1, c1, b2, c2);
         return;
     }
     if (UNIFORM || ((total > kEps) && (fabs(drift1) > kEps))) {   // :290-296
         MCR_MASKED_MOVE;
         const bool sell1 = drift1 > 0.0;                           // :298
-        const double bs = sell1 ? b1 : b2, cs = sell1 ? c1 : c2;   // seller
+        constexpr bool kMaskSel = MASKSEL && TAXED && EQR;         // (the form the headline launch takes; the others keep their selects)
+        [[maybe_unused]] double m_ar = 0.0, m_bs = 0.0, m_cs = 0.0;
+        if constexpr (kMaskSel) seller_select3(sell1, L.alloc1, L.alloc2, b1, b2, c1, c2, m_ar, m_bs, m_cs);
+        const double bs = kMaskSel ? m_bs : sell1 ? b1 : b2, cs = kMaskSel ? m_cs : sell1 ? c1 : c2;   // seller
         const double drift = fabs(drift1);                         // :328: b2 - total (1 - alloc1) = -(b1 - total alloc1)
         double fraction_sold, net_purchase;
         if (TAXED) {
             const double rate_s = EQR ? L.real_rate1 : sell1 ? L.real_rate1 : L.real_rate2;
-            const double ar_s = sell1 ? L.alloc1 : L.alloc2;       // the SOLD asset's own weight (:309,:337) x its rate
+            const double ar_s = kMaskSel ? m_ar : sell1 ? L.alloc1 : L.alloc2;       // the SOLD asset's own weight (:309,:337) x its rate
             const double G = fmax(0.0, bs - cs);                   // :301 / :329 (x bs)
             fraction_sold = fmin(1.0, drift * recip_nr<false>(__builtin_fma(-ar_s, G, bs)));   // :302-312
             net_purchase = fraction_sold * __builtin_fma(-G, rate_s, bs);                       // :314-320: gross - (fraction G) rate

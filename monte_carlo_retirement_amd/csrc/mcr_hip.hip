@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "mcr_device.h"
+#include "mcr_events.h"
 #include "mcr_numpy_rng.h"
 #include "mcr_screen.h"
 #include "mcr_host.h"
@@ -664,6 +665,12 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     constexpr bool MM = !SPLIT || kFan || NPROD == 2 || LIST;  // exec-masked moves (issue-bound launches, and the consumer waves of a screened launch's re-run, either form) vs the compiler's selects (the lone probes' latency-bound SPLIT launches): MCR_MASKED_MOVE, mcr_device.h
     // the tolerance month's dust / empty fix-ups tested once per wave (mcr_device.h: WAVE-UNIFORM fix-ups), issue-bound launches only
     constexpr bool kFastMonth = TOL && MM && kUniformFixups;
+    // The split re-run's consumer wave runs its months in PAIRS, on an event row (mcr_events.h; "PAIRS" below)
+    constexpr bool kPairs = SPLIT && LIST;
+    // (MODE 0, PHASE 0: the block runs the WHOLE path from month 1 and year 0 behind the statements that set the retirement's
+    // initial state — no snapshot, no time slice, no candidate — and keeps none of the summary's columns)
+    static_assert(!kPairs || (MODE == 0 && PHASE == 0 && kSIR && TOL && MM && !ANNUAL && !OUT && !RULE && !kFan),
+                  "the paired consumer is stated for the re-run's own forms: a whole-path count-only launch, the tolerance month, the stream form");
     constexpr int kPaths = (kFan || NPROD == 2) ? 64 : kBlock;   // paths of a workgroup = columns of every per-path LDS array
     const int kThreads = kFan ? (int)blockDim.x : NPROD == 2 ? 3 * 64 : SPLIT ? 2 * kBlock : kBlock;
     const int tid = SPLIT ? (int)(threadIdx.x & (kPaths - 1)) : (int)threadIdx.x;    // the path's lane column in every per-path LDS array
@@ -1097,7 +1104,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     }
     // ---- accumulation (:513-579): no lane leaves this loop early ----
     // (kScalarCounters: moy = m mod 12 in 1 .. 12, a running month of the year instead of the two % kMPY tests)
-    for (int m = 1; m <= ((kCand || (kSliced && seg_resumed)) ? 0 : wm); ++m) {
+    for (int m = 1; m <= ((kPairs || kCand || (kSliced && seg_resumed)) ? 0 : wm); ++m) {    // (kPairs: in pairs, below)
         if constexpr (kScalarCounters) ++SC.moy;
         if (P.contrib_grows && year_opens(SC, m - 1) && m > 1) {  // :514-517 (wave-uniform: a scalar branch, not a select)
             asm volatile("");
@@ -1122,7 +1129,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     }
     if (PHASE == 1) return;   // (every thread of the workgroup: nothing below is needed)
     if constexpr (kScalarCounters) { if (!(kSliced && seg_resumed)) SC.row = wm; }   // (a resumed segment starts at its own row)
-    double start_balance = b1 + b2;        // :581
+    double start_balance = b1 + b2;        // :581 (kPairs: the accumulation runs further down, so this is the INITIAL balance there, like infl_ret, alive, succeeded and ruin_bin below — stale and, in a count-only kernel, unread; the block sets the last three again)
     double infl_ret = infl;                // :582
     if (kSliced && seg_resumed) { start_balance = seg_start_balance; infl_ret = seg_infl_ret; t_idx = P.trajectory_len - ry + y_begin; }
     else if (wm > 0 && wm % kMPY != 0) put_sample(t_idx++, start_balance, infl_ret);  // :590-594
@@ -1193,7 +1200,174 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         done_years = (int)(seg_state_flags >> 24);
         year = y_begin;
     }
-    for (; year < (kSliced ? y_end : ry); ++year) {
+    // ---- PAIRS (kPairs: the consumer wave of a screened launch's split re-run, either form) ----
+    // One consumer wave issues in order, and in the 64-path form it is alone on its SIMD: every scalar instruction of its
+    // month stands on the path's dependent chain, where the throughput kernels' eight waves hide it.  So the whole path, both
+    // loops, is restated here with the month's wave-uniform bookkeeping taken off the month (mcr_events.h):
+    //  - EVENT ROW.  The row is compared with the next row at which anything happens, once; only there the priority falls or
+    //    an income window's flag flips.  The month reads the two flags; the income FMAs stay FMAs behind scalar branches, in
+    //    list order.
+    //  - PAIRS.  Twelve is even, so a retirement month's row has the parity of working_months for the whole path: the loop is
+    //    chosen once on it and runs two months to an iteration, like the accumulation.  The barrier stands at a fixed place
+    //    of the body, the stage buffer alternates by a toggled offset, the vote is a pair counter tested once a pair.
+    //    THE BARRIER SCHEDULE IS THE OTHER KERNELS' begin_month's: barrier p at row 2 p, in front of that row's month, for
+    //    every p < ceil(total_months / 2) until a vote has ended the workgroup; a vote at every kSplitVotePairs-th barrier from
+    //    barrier 0 on, on lane_alive as the retirement year began with it (tests/test_screened_pairs_cpu.py holds the loops below,
+    //    restated on the host, to the producers' schedule).  That restatement (tests/screened_pairs_model.cpp: paired_consumer) is a
+    //    COPY of the loops below, not this code: any change to their structure — where handover() stands in a body, the
+    //    accumulation's odd tail, the `dead` tests — goes into the copy first and passes there BEFORE a GPU run; a barrier too
+    //    many or too few hangs the workgroup.
+    //  - FACTORS EARLY.  The six staged factors of a pair are read directly behind its barrier, into registers: no month
+    //    behind the first waits for LDS at its head.
+    // The arithmetic of a lane, its order and every rounding are the other loops': the statements are theirs, less what a
+    // count-only kernel without an annual-gains tax never reads.
+    if constexpr (kPairs) {
+        static_assert(kMPY % 2 == 0, "a retirement year is a whole number of pairs");
+        constexpr bool kSel = true;     // the seller's selects of the month's rebalance on an SGPR-pair mask (rebalance_tol's MASKSEL)
+        const EventPlan EP{prio_t1, prio_t2, prio_t3, SR.s0, SR.n0, SR.s1, SR.n1};
+        EventRow EV = event_begin(EP);
+        PairCursor PC{0, 0u};
+        int row = 0;
+        int dead = 0;          // the workgroup has voted to stop (wave-uniform: an SGPR, not a lane mask)
+        double f0 = 0.0, f1 = 0.0, f2 = 0.0, f3 = 0.0, f4 = 0.0, f5 = 0.0;   // the pair in hand: g1, ginf, g2 of its even row, then of its odd row
+        auto handover = [&]() __attribute__((always_inline)) {     // barrier PC.pair, then the pair it hands over
+            if (dead) return;
+            if (pair_votes(PC, kSplitVotePairs)) {
+                const int any = __syncthreads_or(__builtin_amdgcn_ballot_w64(lane_alive) != 0ull ? 1 : 0);
+                if (__builtin_amdgcn_readfirstlane(any) == 0) { dead = 1; return; }
+            } else __syncthreads();
+            const double* const c = stage + PC.off;
+            f0 = c[0]; f1 = c[kPaths]; f2 = c[2 * kPaths]; f3 = c[3 * kPaths]; f4 = c[4 * kPaths]; f5 = c[5 * kPaths];
+            pair_advance(PC, (unsigned)kStageLen);
+        };
+        auto events = [&]() __attribute__((always_inline)) {
+            if (row == EV.next) {
+                const int p = event_fire(EV, EP, row);
+                if (p == 2) __builtin_amdgcn_s_setprio(2);
+                else if (p == 1) __builtin_amdgcn_s_setprio(1);
+                else if (p == 0) __builtin_amdgcn_s_setprio(0);
+            }
+        };
+        // the factors of the pair's even (half 0) or odd (half 1) row; `half` is a constant at every call
+        auto factors = [&](int half, double& g1, double& ginf, double& g2) __attribute__((always_inline)) {
+            g1 = half ? f3 : f0; ginf = half ? f4 : f1; g2 = half ? f5 : f2;
+        };
+        // accumulation (:513-579), month m = row + 1; moy = months of the plan year behind it
+        int moy = 0;
+        auto acc_month = [&](int m, int half) __attribute__((always_inline)) {
+            if (P.contrib_grows && moy == 0 && m > 1) {                    // :514-517
+                asm volatile("");
+                contrib *= P.contrib_growth_factor;
+            }
+            events();
+            double g1, ginf, g2;
+            factors(half, g1, ginf, g2);
+            market_step<ANNUAL, TOL>(g1, ginf, g2, b1, b2, gacc1, gacc2, infl); // :534-538
+            const double k1 = contrib * P.alloc1;                          // :540-542
+            const double k2 = contrib - k1;                                // :543
+            b1 += k1; c1 += k1; b2 += k2; c2 += k2;                        // :544-547
+            rebalance_tol<TANY, MM, kFastMonth, EQR, kSel>(P, L, b1, c1, b2, c2);  // :549-553
+            if (++moy == kMPY) {                                           // :557
+                moy = 0;
+                pre_fail |= annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, TOL, EQR>(P, L, b1, c1, b2, c2, gacc1, gacc2);  // :558-573
+                gacc1 = 0.0; gacc2 = 0.0;                                  // :578-579
+            }
+            ++row;
+        };
+        {
+            int m = 1;
+            for (; m < wm; m += 2) { handover(); acc_month(m, 0); acc_month(m + 1, 1); }
+            if (m == wm) { handover(); acc_month(m, 0); }        // (working_months odd: the pair's second row is retirement's first)
+        }
+        // decumulation (:632-868)
+        alive = !pre_fail; succeeded = !pre_fail; ruin_bin = pre_fail ? 0 : -1;
+        const int ye_mi = kMPY - 1 - wm % kMPY;      // the month of a retirement year in which a year of the plan ends
+        auto ret_month = [&](int mi, int half, bool& yfail) __attribute__((always_inline)) {
+            events();
+            if (alive && !yfail) {
+                const double price = infl;                                 // :644
+                const double expenses = P.monthly_expenses * price;        // :645-647
+                double income = expenses;                                  // :649 (tolerance form: runs down from the expenses)
+                if (EV.w0) { asm volatile(""); income = __builtin_fma(-SR.a0, price, income); }
+                if (EV.w1) { asm volatile(""); income = __builtin_fma(-SR.a1, price, income); }
+                const double need = fmax(0.0, income);                     // :679-682
+                bool stop = false;
+                if (b1 + b2 <= kEps && need > kEps) {                      // :684-690 (FAIL-1, no shock consumed)
+                    yfail = true; stop = true;
+                }
+                auto tol_month = [&](auto fast_tag) __attribute__((always_inline)) {   // (the other loop's, less the summary columns)
+                    constexpr bool FAST = decltype(fast_tag)::value;
+                    const double cap = capacity_tol<T1, T2, MM, FAST>(b1, c1, L.real_rate1, b2, c2, L.real_rate2);   // :726-738
+                    const double target = fmin(need, cap);                            // :739-742
+                    bool fail = need > kEps && target < need - kEps;                  // :743-748 (FAIL-3) = :784-790 (FAIL-4)
+                    double phi = target * recip_nr<false>(cap);                       // :750-765
+                    if (!FAST && wave_any(!(cap > kEps))) {                           // the dust sub-case
+                        if (!(cap > kEps)) {
+                            MCR_MASKED_MOVE;
+                            double cap1, cap2, gw1, nw1, gw2, nw2;
+                            net_liquidation_values2<T1, T2, MM>(b1, c1, L.real_rate1, b2, c2, L.real_rate2, cap1, cap2);
+                            const double xcap = cap1 + cap2, xtarget = fmin(need, xcap);
+                            const double prop1 = xcap > kEps ? fdiv<false>(cap1, xcap) : P.alloc1;
+                            withdraw2<T1, T2, MM>(b1, c1, xtarget * prop1, L.real_rate1, gw1, nw1,
+                                                  b2, c2, xtarget * (1.0 - prop1), L.real_rate2, gw2, nw2);
+                            fail = need > kEps && (xtarget < need - kEps || nw1 + nw2 < need - kEps);
+                            phi = 0.0;
+                        }
+                    }
+                    if (fail) yfail = true;
+                    sell_fraction_tol<MM, FAST>(phi, b1, c1, b2, c2);                 // :757-776
+                    rebalance_tol<TANY, MM, kFastMonth, EQR, kSel>(P, L, b1, c1, b2, c2);   // :792-796
+                    if (!yfail && mi == ye_mi) {                                      // :798-804
+                        const bool tf = annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, true, EQR>(P, L, b1, c1, b2, c2, gacc1, gacc2);  // :805-818
+                        gacc1 = 0.0; gacc2 = 0.0;                                     // :819-820
+                        yfail = yfail || tf;                                          // :821-822
+                    }
+                };
+                if (!stop) {
+                    double g1, ginf, g2;
+                    factors(half, g1, ginf, g2);
+                    market_step<ANNUAL, TOL>(g1, ginf, g2, b1, b2, gacc1, gacc2, infl);  // :706-714
+                    if (kFastMonth && !wave_any(fmin(b1, b2) <= P.fast_floor)) {
+                        tol_month(std::true_type{});
+                    } else {
+                        if (b1 + b2 <= kEps && need > kEps) {              // :717-724 (FAIL-2)
+                            MCR_MASKED_MOVE;
+                            b1 = fmax(0.0, b1); b2 = fmax(0.0, b2);
+                            yfail = true; stop = true;
+                        }
+                        if (!stop) tol_month(std::false_type{});
+                    }
+                }
+            }
+            ++row;
+        };
+        auto ret_years = [&](auto odd_tag) __attribute__((always_inline)) {
+            constexpr bool ODD = decltype(odd_tag)::value;     // the parity of every row wm + 12 year + mi with mi even
+            for (; year < ry; ++year) {
+                lane_alive = alive;
+                if (dead) break;
+                bool yfail = false;                            // :638
+#pragma nounroll
+                for (int mi = 0; mi < kMPY; mi += 2) {
+                    if constexpr (ODD) {
+                        ret_month(mi, 1, yfail);
+                        handover();
+                        ret_month(mi + 1, 0, yfail);
+                    } else {
+                        handover();
+                        ret_month(mi, 0, yfail);
+                        ret_month(mi + 1, 1, yfail);
+                    }
+                }
+                if (alive) {                                   // :830-868, the counts' part
+                    if (yfail) { succeeded = false; ruin_bin = 1 + year; alive = false; }
+                    else done_years = year + 1;
+                }
+            }
+        };
+        if (wm & 1) ret_years(std::true_type{}); else ret_years(std::false_type{});
+    }
+    for (; !kPairs && year < (kSliced ? y_end : ry); ++year) {
         if (!SPLIT && __builtin_amdgcn_ballot_w64(alive) == 0ull) break;  // every lane of this wave has failed: nothing left to simulate
         if (SPLIT) { lane_alive = alive; if (wg_dead) break; }           // (SPLIT: the wave keeps pace with its producers' barriers until the workgroup votes to stop)
         if constexpr (kWaveRule) rule_year_from(RS, FR, year, valid, alive, b1, b2, infl, li);   // (PHASE 11, PHASE 6 with RULE: the wave's own rule and year counts, no multiplier row)

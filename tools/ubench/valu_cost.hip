@@ -103,6 +103,51 @@ KERNEL(pk_mul_f32, double, seed + threadIdx.x + c, ASM2("v_pk_mul_f32"))
 KERNEL(pk_add_f32, double, seed + threadIdx.x + c, ASM2("v_pk_add_f32"))
 KERNEL(add_f32, float, seed + threadIdx.x + c, ASM2("v_add_f32"))
 
+// A LONE wave (one workgroup of 64 threads on the whole device), the consumer wave of the screened launch's split re-run: it
+// issues in order and nothing hides its scalar instructions.  Cost per BODY of a long unrolled stream; the scalar cases leave
+// exec whole and skip at most one s_nop.  (`lone_fma_f64` / `lone_add_u32` / `lone_s_add_u32`: the plain instructions next to them.)
+#define LONE_ITERS (16 * ITERS)
+#define KERNEL_LONE(NAME, BODY)                                                          \
+    __global__ __launch_bounds__(64) void kl_##NAME(double* out, double seed, uint32_t su) { \
+        double v[CHAINS];                                                               \
+        _Pragma("unroll") for (int c = 0; c < CHAINS; ++c) v[c] = seed + threadIdx.x + c; \
+        for (int i = 0; i < LONE_ITERS; ++i) {                                          \
+            _Pragma("unroll") for (int c = 0; c < CHAINS; ++c) { double& x = v[c]; (void)x; (void)su; BODY; } \
+        }                                                                               \
+        double acc = v[0];                                                              \
+        _Pragma("unroll") for (int c = 1; c < CHAINS; ++c) acc = acc + v[c];            \
+        if (acc == 123456789.0) out[0] = acc;                                           \
+    }
+KERNEL_LONE(fma_f64, asm volatile("v_fma_f64 %0, %0, %1, %0" : "+v"(x) : "v"(seed)))
+KERNEL_LONE(add_u32, { uint32_t t; asm volatile("v_add_u32 %0, %1, %1" : "=v"(t) : "v"((uint32_t)c)); })
+KERNEL_LONE(s_add_u32, asm volatile("s_add_u32 s20, s20, %0" : : "s"(su) : "s20", "scc"))
+KERNEL_LONE(s_cmp, asm volatile("s_cmp_lg_u32 %0, s20" : : "s"(su) : "scc"))
+KERNEL_LONE(s_cmp_branch_not_taken, asm volatile("s_cmp_eq_u32 %0, %0\n\ts_cbranch_scc0 .Lnt%=\n.Lnt%=:" : : "s"(su) : "scc"))
+KERNEL_LONE(s_cmp_branch_taken, asm volatile("s_cmp_eq_u32 %0, %0\n\ts_cbranch_scc1 .Ltk%=\n\ts_nop 0\n.Ltk%=:" : : "s"(su) : "scc"))
+KERNEL_LONE(s_cselect_b64, asm volatile("s_cselect_b64 s[20:21], s[20:21], exec" : : : "s20", "s21"))
+KERNEL_LONE(s_and_saveexec_or_exec, asm volatile("s_and_saveexec_b64 s[20:21], exec\n\ts_or_b64 exec, exec, s[20:21]" : : : "s20", "s21", "scc"))
+
+static void run_lone(const char* name, void (*k)(double*, double, uint32_t)) {
+    double* d;
+    hipMalloc(&d, 64);
+    hipLaunchKernelGGL(k, dim3(1), dim3(64), 0, 0, d, 1.0000001, 3u);
+    hipDeviceSynchronize();
+    hipEvent_t a, b;
+    hipEventCreate(&a); hipEventCreate(&b);
+    float best = 1e30f;
+    for (int r = 0; r < 5; ++r) {
+        hipEventRecord(a);
+        hipLaunchKernelGGL(k, dim3(1), dim3(64), 0, 0, d, 1.0000001, 3u);
+        hipEventRecord(b);
+        hipEventSynchronize(b);
+        float ms; hipEventElapsedTime(&ms, a, b);
+        if (ms < best) best = ms;
+    }
+    const double bodies = (double)LONE_ITERS * CHAINS, ns = best * 1e6;
+    printf("lone %-28s %8.3f ms  %6.2f ns/body  ~%5.2f cycles @2.4GHz\n", name, best, ns / bodies, ns / bodies * 2.4);
+    hipFree(d);
+}
+
 template <typename T>
 static void run(const char* name, void (*k)(T*, T), T seed) {
     T* d;
@@ -148,5 +193,8 @@ int main() {
     RUN(mix_bitop3_per_fma, double, 1.0000001); RUN(mix_bitop3_sgpr_per_fma, double, 1.0000001); RUN(mix_xor_per_fma, double, 1.0000001);
     RUN(alignbit_b32, uint32_t, 3); RUN(alignbit_b32_sgpr, uint32_t, 3); RUN(cvt_f32_u32, uint32_t, 3); RUN(mul_f32, float, 1.0000001f);
     RUN(pk_fma_f32, double, 1.0000001); RUN(pk_mul_f32, double, 1.0000001); RUN(pk_add_f32, double, 1e-9); RUN(add_f32, float, 1e-9f);
+#define RUN_LONE(NAME) run_lone(#NAME, kl_##NAME)
+    RUN_LONE(fma_f64); RUN_LONE(add_u32); RUN_LONE(s_add_u32); RUN_LONE(s_cmp); RUN_LONE(s_cmp_branch_not_taken); RUN_LONE(s_cmp_branch_taken);
+    RUN_LONE(s_cselect_b64); RUN_LONE(s_and_saveexec_or_exec);
     return 0;
 }
