@@ -19,6 +19,7 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
+import bin_rule
 import count_fuzz as F
 from monte_carlo_retirement_amd import _native as N
 from monte_carlo_retirement_amd import engine as E
@@ -49,34 +50,36 @@ def _ctx(scn, route):
     return scn.context(f"{route}; NumPy stream (main_seed, child_offset, path_begin) = {F.numpy_leg(scn)}")
 
 
-# ---- the comparisons (tests/test_count_fuzz_cpu.py feeds them perturbed oracle runs: they can fail) ---------------------------
-def same_flags(scn, got, ora, route):
-    assert np.array_equal(got["success"], ora["success"]), (np.nonzero(got["success"] != ora["success"])[0].tolist(), _ctx(scn, route + ": success"))
-    assert np.array_equal(got["years_to_ruin"], ora["years_to_ruin"], equal_nan=True), _ctx(scn, route + ": years_to_ruin")
+# ---- the comparisons (tests/test_count_fuzz_cpu.py and tests/test_bin_rule_cpu.py feed them perturbed oracle runs: they can fail) ----
+# `ctx(scn, route)`: the text a failure names the launch by.  The default names the plan's NumPy leg; a caller on another stream
+# (tests/test_gpu_output_modes_vs_oracle.py: the default Philox stream) passes its own.  What is asserted does not depend on it.
+def same_flags(scn, got, ora, route, ctx=_ctx):
+    assert np.array_equal(got["success"], ora["success"]), (np.nonzero(got["success"] != ora["success"])[0].tolist(), ctx(scn, route + ": success"))
+    assert np.array_equal(got["years_to_ruin"], ora["years_to_ruin"], equal_nan=True), ctx(scn, route + ": years_to_ruin")
 
 
-def within_path_tolerance(scn, got, ora, keys, route):
+def within_path_tolerance(scn, got, ora, keys, route, ctx=_ctx):
     """test_gpu_differential.py's: ABS + REL max(|ref|, the path's own money scale)."""
     scale = np.maximum(1.0, np.abs(ora["trajectory"]).max(axis=0))
     for key in keys:
-        assert got[key].shape == ora[key].shape, (key, got[key].shape, ora[key].shape, _ctx(scn, route))
+        assert got[key].shape == ora[key].shape, (key, got[key].shape, ora[key].shape, ctx(scn, route))
         err = np.abs(got[key] - ora[key])
-        assert np.all(err <= ABS + REL * np.maximum(np.abs(ora[key]), scale)), (key, float(np.nanmax(err)), _ctx(scn, route))
+        assert np.all(err <= ABS + REL * np.maximum(np.abs(ora[key]), scale)), (key, float(np.nanmax(err)), ctx(scn, route))
 
 
-def same_full_output(scn, got, ora, route="full output"):
+def same_full_output(scn, got, ora, route="full output", ctx=_ctx):
     _same_integers(scn, got, ora, route)
-    same_flags(scn, got, ora, route)
-    within_path_tolerance(scn, got, ora, ("trajectory", "real_trajectory") + SUMMARY, route)
+    same_flags(scn, got, ora, route, ctx)
+    within_path_tolerance(scn, got, ora, ("trajectory", "real_trajectory") + SUMMARY, route, ctx)
     gw, cw = got["withdrawal_rate_trajectory"], ora["withdrawal_rate_trajectory"]
-    assert np.array_equal(np.isnan(gw), np.isnan(cw)), _ctx(scn, route + ": withdrawal-rate NaN pattern")
-    np.testing.assert_allclose(gw, cw, rtol=1e-8, atol=1e-9, equal_nan=True, err_msg=_ctx(scn, route))    # (test_gpu_differential.py's)
+    assert np.array_equal(np.isnan(gw), np.isnan(cw)), ctx(scn, route + ": withdrawal-rate NaN pattern")
+    np.testing.assert_allclose(gw, cw, rtol=1e-8, atol=1e-9, equal_nan=True, err_msg=ctx(scn, route))    # (test_gpu_differential.py's)
 
 
-def same_summary(scn, got, ora, route="summary-only"):
+def same_summary(scn, got, ora, route="summary-only", ctx=_ctx):
     _same_integers(scn, got, ora, route)
-    same_flags(scn, got, ora, route)
-    within_path_tolerance(scn, got, ora, SUMMARY, route)
+    same_flags(scn, got, ora, route, ctx)
+    within_path_tolerance(scn, got, ora, SUMMARY, route, ctx)
 
 
 def same_count_only(scn, got, ora, route="count-only"):
@@ -85,28 +88,27 @@ def same_count_only(scn, got, ora, route="count-only"):
 
 
 def _cells(row, edges):
-    return np.concatenate(([np.count_nonzero(row < edges[0])], np.histogram(row, bins=edges)[0],
-                           [np.count_nonzero(row > edges[-1])])).astype(np.int64)
+    return bin_rule.cells(row, edges)
 
 
-def same_year_bins(scn, got, ora, route="year bins"):
-    """The per-row rule of test_gpu_year_bins.test_tables_vs_oracle: a row that is not equal may move at most 2 x its entries
-    within 1e-8 (relative) of an edge; every row holds each of its entries once."""
-    _same_integers(scn, got, ora, route)
+def year_bin_rows(got, ora):
+    """(table name, the oracle's rows, the table's edges) of the four yearly tables."""
     ok = ora["success"].astype(bool)
-    rows = [("trajectory_bins", ora["trajectory"], got["edges"]), ("real_trajectory_bins", ora["real_trajectory"], got["edges"]),
+    return [("trajectory_bins", ora["trajectory"], got["edges"]), ("real_trajectory_bins", ora["real_trajectory"], got["edges"]),
             ("wr_bins", ora["withdrawal_rate_trajectory"], got["wr_edges"]), ("final_success_bins", ora["final_balance"][ok][None, :], got["edges"])]
-    for name, data, edges in rows:
+
+
+def same_year_bins(scn, got, ora, route="year bins", ctx=_ctx):
+    """Every row of the four tables under the rule of tests/bin_rule.py: a row that is not equal may move at most 2 x its entries
+    within 1e-8 (relative) of an edge, the edge at 0 apart; every row holds each of its entries once, none below 0."""
+    _same_integers(scn, got, ora, route)
+    for name, data, edges in year_bin_rows(got, ora):
         table = got[name].astype(np.int64).reshape(data.shape[0], -1)
         for t, row in enumerate(data):
-            row = row[~np.isnan(row)]
-            exp = _cells(row, edges)
-            assert table[t].sum() == row.size, (name, t, int(table[t].sum()), row.size, _ctx(scn, route))
             if name in ("trajectory_bins", "real_trajectory_bins"):
-                assert row.size == scn.n, (name, t, _ctx(scn, route))
-            if not np.array_equal(table[t], exp):
-                near = int(np.count_nonzero(np.min(np.abs(row[:, None] - edges[None, :]) - 1e-8 * np.maximum(1.0, np.abs(edges))[None, :], axis=1) <= 0))
-                assert np.abs(table[t] - exp).sum() <= 2 * near, (f"{name}[{t}]: {np.abs(table[t] - exp).sum()} moved, {near} near an edge", _ctx(scn, route))
+                assert np.count_nonzero(~np.isnan(row)) == scn.n, (name, t, ctx(scn, route))
+            _, _, wrong = bin_rule.row_verdict(table[t], row, edges)
+            assert wrong is None, (f"{name}[{t}]: {wrong}", ctx(scn, route))
 
 
 # ---- a. the four whole-path launches ------------------------------------------------------------------------------------------

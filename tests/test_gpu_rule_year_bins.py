@@ -18,6 +18,7 @@ import sys
 import numpy as np
 import pytest
 
+import bin_rule
 import spending_rule_model as M
 from conftest import REPO
 from monte_carlo_retirement_amd import Config, params_from_config
@@ -410,15 +411,9 @@ def test_firing_rules_vs_the_oracle(oracle, plan, wm, rname):
     for name, data, edges in data_rows:
         got = yb[name].astype(np.int64).reshape(data.shape[0], -1)
         for t, row in enumerate(data):
-            row = row[~np.isnan(row)]
-            exp = _cells(row, edges)
-            assert got[t].sum() == row.size, (name, t)
-            if not np.array_equal(got[t], exp):
-                near = int(np.count_nonzero(np.min(np.abs(row[:, None] - edges[None, :]) - 1e-8 * np.maximum(1.0, np.abs(edges))[None, :], axis=1) <= 0))
-                moved = int(np.abs(got[t] - exp).sum())
-                moved_total, near_total = moved_total + moved, near_total + near
-                if moved > 2 * near:
-                    dist = np.min(np.abs(row[:, None] - edges[None, :]) / np.maximum(1.0, np.abs(edges))[None, :], axis=1)
-                    failures.append(f"{name}[{t}]: {moved} moved, {near} near an edge; smallest relative distances to an edge {np.sort(dist)[:4].tolist()}")
+            moved, near, wrong = bin_rule.row_verdict(got[t], row, edges)      # (the edge at 0 apart: tests/bin_rule.py)
+            moved_total, near_total = moved_total + moved, near_total + near
+            if wrong is not None:
+                failures.append(f"{name}[{t}]: {wrong}")
     print(f"{plan} wm={wm} {rname}: entries moved {moved_total}, entries within 1e-8 of an edge {near_total}, rows over the bound {len(failures)}")
     assert not failures, failures

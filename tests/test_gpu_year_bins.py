@@ -14,6 +14,7 @@ import sys
 import numpy as np
 import pytest
 
+import bin_rule
 from conftest import REPO, load_golden
 from monte_carlo_retirement_amd import Config, params_from_config
 from monte_carlo_retirement_amd import _native as N
@@ -243,7 +244,8 @@ def test_argument_errors_leave_the_tables_untouched():
 @pytest.mark.parametrize("scenario", ["s60", "jorge"])
 def test_tables_vs_oracle(oracle, scenario):
     """20 000 paths against np.histogram of the ORACLE's rows (reference arithmetic): a row that is not exactly equal may move
-    at most 2 x (its entries within 1e-8 relative of an edge), the rule of test_bins_vs_oracle_1e5 per row."""
+    at most 2 x (its entries within 1e-8 relative of an edge), the rule of test_bins_vs_oracle_1e5 per row, as tests/bin_rule.py
+    states it: the edge at 0 of the default edges moves nothing, and no entry lies below it."""
     if scenario == "s60":
         p, wm = params_from_config(_cfg(initial_balance=2.0e6, inv1_returns_volatility=0.15, equity_inflation_correlation=0.3)), 120
     else:
@@ -258,12 +260,7 @@ def test_tables_vs_oracle(oracle, scenario):
     for name, data, edges in rows:
         got = yb[name].astype(np.int64).reshape(data.shape[0], -1)
         for t, row in enumerate(data):
-            row = row[~np.isnan(row)]
-            exp = _cells(row, edges)
-            assert got[t].sum() == row.size, (name, t)
-            if not np.array_equal(got[t], exp):
-                near = int(np.count_nonzero(np.min(np.abs(row[:, None] - edges[None, :]) - 1e-8 * np.maximum(1.0, np.abs(edges))[None, :], axis=1) <= 0))
-                assert np.abs(got[t] - exp).sum() <= 2 * near, f"{name}[{t}]: {np.abs(got[t] - exp).sum()} moved, {near} near an edge"
+            bin_rule.check_row(got[t], row, edges, f"{name}[{t}]")
 
 
 def test_brackets_contain_the_exact_bands_and_the_streamed_document():
