@@ -25,6 +25,7 @@
 #include <cstring>
 #include <algorithm>
 #include <mutex>
+#include <optional>
 #include <thread>
 #include <type_traits>
 #include <utility>
@@ -2169,63 +2170,88 @@ int use_device(int device) {
     return MCR_OK;
 }
 
-// ---- leased contexts of the host-buffer entry points (mcr_host.h): a process-wide pool keyed by device ----
-static std::mutex g_pool_mu;
-static std::vector<HostCtx*> g_idle_ctx;   // idle contexts, most recently used last
-
-static void host_ctx_destroy(HostCtx* c) {   // (the caller has set the device)
-    if (c->block) (void)hipFree(c->block);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
-}
-
-HostCtx* host_ctx_acquire(int device) {
-    {
-        std::lock_guard<std::mutex> lock(g_pool_mu);
-        for (size_t i = g_idle_ctx.size(); i-- > 0;)
-            if (g_idle_ctx[i]->device == device) {
-                HostCtx* c = g_idle_ctx[i];
-                g_idle_ctx.erase(g_idle_ctx.begin() + (long)i);
-                return c;
-            }
+// ---- leased per-device resources (mcr_host.h: HostCtx, StreamFork): one process-wide idle pool per kind, keyed by device ----
+// acquire() hands out the most recently used idle entry of the device, or makes one (Create: nullptr on failure); release()
+// puts it back and, above kIdlePerDevice idle entries of that device, destroys the least recently used one — outside the
+// lock, on the device of the call that is ending (it is still current: Destroy expects the device set).
+template <class T, int kIdlePerDevice, T* (*Create)(int), void (*Destroy)(T*)>
+class IdlePool {
+public:
+    T* acquire(int device) {
+        {
+            std::lock_guard<std::mutex> lock(mu_);
+            for (size_t i = idle_.size(); i-- > 0;)
+                if (idle_[i]->device == device) return take(i);
+        }
+        return Create(device);
     }
+    void release(T* t) {
+        T* surplus = nullptr;
+        {
+            std::lock_guard<std::mutex> lock(mu_);
+            idle_.push_back(t);
+            int same = 0;
+            for (T* o : idle_) same += o->device == t->device;
+            for (size_t i = 0; same > kIdlePerDevice && !surplus; ++i)
+                if (idle_[i]->device == t->device) surplus = take(i);
+        }
+        if (surplus) Destroy(surplus);
+    }
+    // mcr_release_cached: destroys the idle entries of `device` (< 0: of every device), each on its own device
+    int release_cached(int device) {
+        std::vector<T*> gone;
+        {
+            std::lock_guard<std::mutex> lock(mu_);
+            for (size_t i = idle_.size(); i-- > 0;)
+                if (device < 0 || idle_[i]->device == device) gone.push_back(take(i));
+        }
+        int rc = MCR_OK;
+        for (T* t : gone) {
+            DeviceScope scope(t->device);
+            if (scope.rc != MCR_OK) rc = scope.rc;   // (device gone: drop the bookkeeping anyway)
+            Destroy(t);
+        }
+        return rc;
+    }
+    // An entry for the duration of a scope; p == nullptr: Create failed
+    struct Lease {
+        IdlePool& pool;
+        T* const p;
+        Lease(IdlePool& pool_, int device) : pool(pool_), p(pool_.acquire(device)) {}
+        Lease(const Lease&) = delete;
+        Lease& operator=(const Lease&) = delete;
+        ~Lease() { if (p) pool.release(p); }
+    };
+
+private:
+    T* take(size_t i) {   // (under the lock)
+        T* t = idle_[i];
+        idle_.erase(idle_.begin() + (long)i);
+        return t;
+    }
+    std::mutex mu_;
+    std::vector<T*> idle_;   // most recently used last
+};
+
+static HostCtx* host_ctx_create(int device) {   // (error set on failure)
     HostCtx* c = new HostCtx{device, nullptr, nullptr, 0};
     hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { (void)hip_fail(e, "hipStreamCreate (host context)"); delete c; return nullptr; }
     return c;
 }
-
-void host_ctx_release(HostCtx* c) {
-    if (c->capacity > kHostCtxKeepBytes) { (void)hipFree(c->block); c->block = nullptr; c->capacity = 0; }
-    HostCtx* surplus = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(g_pool_mu);
-        g_idle_ctx.push_back(c);
-        int same = 0;
-        for (HostCtx* o : g_idle_ctx) same += o->device == c->device;
-        if (same > kHostCtxIdlePerDevice)   // drop the least recently used idle context of this device
-            for (size_t i = 0; i < g_idle_ctx.size(); ++i)
-                if (g_idle_ctx[i]->device == c->device) { surplus = g_idle_ctx[i]; g_idle_ctx.erase(g_idle_ctx.begin() + (long)i); break; }
-    }
-    if (surplus) host_ctx_destroy(surplus);   // same device as the call that is ending: it is still current
+static void host_ctx_destroy(HostCtx* c) {
+    if (c->block) (void)hipFree(c->block);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
+    delete c;
 }
+using HostCtxPool = IdlePool<HostCtx, kHostCtxIdlePerDevice, host_ctx_create, host_ctx_destroy>;
+static HostCtxPool g_host_ctx;
 
-hipError_t host_ctx_reserve(HostCtx* c, size_t bytes) {
-    if (bytes <= c->capacity) return hipSuccess;
-    if (c->block) { (void)hipFree(c->block); c->block = nullptr; c->capacity = 0; }
-    hipError_t e = hipMalloc(&c->block, bytes);
-    if (e == hipSuccess) c->capacity = bytes; else c->block = nullptr;
-    return e;
-}
-
-// Fork/join streams (mcr_host.h: StreamFork): a few non-blocking side streams + events, leased from a process-wide pool
-// keyed by device for the duration of ONE call's enqueue (like HostCtx).  A lease only has to cover the host-side
-// enqueue: the side streams are in-order, and a stream that waits on an event waits for the record that preceded the
-// wait call, so the next lessee's records cannot disturb work that is still running.  User: mcr_probe_months_rng
-// (candidates forked onto side streams; mcr_row_quantiles' row-group pipelining was measured and dropped in round 3).
-static std::vector<StreamFork*> g_idle_fork;   // guarded by g_pool_mu
-constexpr int kStreamForkIdlePerDevice = 2;
-
+// Fork/join streams (mcr_host.h: StreamFork): a few non-blocking side streams + events, leased for the duration of ONE
+// call's enqueue.  A lease only has to cover the host-side enqueue: the side streams are in-order, and a stream that waits
+// on an event waits for the record that preceded the wait call, so the next lessee's records cannot disturb work that is
+// still running.  User: mcr_probe_months_rng (candidates forked onto side streams; mcr_row_quantiles' row-group pipelining
+// was measured and dropped in round 3).
 static void stream_fork_destroy(StreamFork* f) {   // pending work on a destroyed stream still completes (stream-ordered release)
     for (int i = 0; i < kForkStreams; ++i) {
         if (f->done[i]) (void)hipEventDestroy(f->done[i]);
@@ -2234,16 +2260,7 @@ static void stream_fork_destroy(StreamFork* f) {   // pending work on a destroye
     if (f->fork) (void)hipEventDestroy(f->fork);
     delete f;
 }
-StreamFork* stream_fork_acquire(int device) {
-    {
-        std::lock_guard<std::mutex> lock(g_pool_mu);
-        for (size_t i = g_idle_fork.size(); i-- > 0;)
-            if (g_idle_fork[i]->device == device) {
-                StreamFork* f = g_idle_fork[i];
-                g_idle_fork.erase(g_idle_fork.begin() + (long)i);
-                return f;
-            }
-    }
+static StreamFork* stream_fork_create(int device) {   // nullptr: out of resources
     StreamFork* f = new StreamFork();
     std::memset(f, 0, sizeof(*f));
     f->device = device;
@@ -2254,19 +2271,8 @@ StreamFork* stream_fork_acquire(int device) {
     if (!ok) { (void)hipGetLastError(); stream_fork_destroy(f); return nullptr; }
     return f;
 }
-void stream_fork_release(StreamFork* f) {
-    StreamFork* surplus = nullptr;
-    {
-        std::lock_guard<std::mutex> lock(g_pool_mu);
-        g_idle_fork.push_back(f);
-        int same = 0;
-        for (StreamFork* o : g_idle_fork) same += o->device == f->device;
-        if (same > kStreamForkIdlePerDevice)
-            for (size_t i = 0; i < g_idle_fork.size(); ++i)
-                if (g_idle_fork[i]->device == f->device) { surplus = g_idle_fork[i]; g_idle_fork.erase(g_idle_fork.begin() + (long)i); break; }
-    }
-    if (surplus) stream_fork_destroy(surplus);
-}
+using StreamForkPool = IdlePool<StreamFork, kStreamForkIdlePerDevice, stream_fork_create, stream_fork_destroy>;
+static StreamForkPool g_stream_fork;
 
 // Preconditions of the path kernel (its STRICT = false forms drop clamps that are no-ops only for rates and
 // weights in [0, 1] and non-negative amounts; fexp needs |x| < 700).  The reference enforces the same ranges
@@ -2634,38 +2640,55 @@ static int plan_path_kernel_lds(DevParams& d, int mode, uint32_t rng_kind, bool 
     return MCR_OK;
 }
 
+// Scope guard of one stream-ordered allocation: freed behind the work enqueued so far, by release() or at scope exit
+struct StreamAlloc {
+    void* p = nullptr;
+    hipStream_t stream;
+    explicit StreamAlloc(hipStream_t s) : stream(s) {}
+    StreamAlloc(const StreamAlloc&) = delete;
+    StreamAlloc& operator=(const StreamAlloc&) = delete;
+    ~StreamAlloc() { (void)release(); }
+    hipError_t alloc_status(size_t bytes) {     // refused: nothing enqueued, the HIP error cleared
+        const hipError_t e = hipMallocAsync(&p, bytes, stream);
+        if (e != hipSuccess) { (void)hipGetLastError(); p = nullptr; }
+        return e;
+    }
+    bool alloc(size_t bytes) { return alloc_status(bytes) == hipSuccess; }
+    hipError_t release() {
+        if (!p) return hipSuccess;
+        const hipError_t e = hipFreeAsync(p, stream);
+        p = nullptr;
+        return e;
+    }
+};
 // The device side of a launch's stream list: the table of the records beyond the by-value block and the overflow block of
 // lock slots, ONE stream-ordered allocation (freed behind the kernel).  The host copy of the table is owned by the stream
 // until the upload has run (hipLaunchHostFunc): nothing here waits for the device.
 struct StreamSideBlock {
-    void* mem = nullptr;
-    int attach(DevParams& d, const std::vector<DevStream>& extra, unsigned grid_x, hipStream_t stream) {
+    StreamAlloc mem;
+    explicit StreamSideBlock(hipStream_t s) : mem(s) {}
+    int attach(DevParams& d, const std::vector<DevStream>& extra, unsigned grid_x) {
         const int n_over = d.n_lock_slots_total - d.n_lock_slots;
         if (extra.empty() && n_over <= 0) return MCR_OK;
         d.lock_stride = (int64_t)grid_x * kBlock;
         const size_t table_bytes = (extra.size() * sizeof(DevStream) + 255) & ~(size_t)255;
         const size_t over_bytes = (size_t)(n_over > 0 ? n_over : 0) * (size_t)d.lock_stride * sizeof(double);
-        hipError_t e = hipMallocAsync(&mem, table_bytes + over_bytes, stream);
-        if (e != hipSuccess) { mem = nullptr; return hip_fail(e, "income-stream table / lock-slot overflow allocation"); }
+        hipError_t e = mem.alloc_status(table_bytes + over_bytes);
+        if (e != hipSuccess) return hip_fail(e, "income-stream table / lock-slot overflow allocation");
         if (!extra.empty()) {
             void* host = std::malloc(extra.size() * sizeof(DevStream));
             if (!host) { set_error("out of host memory"); return MCR_ERR_HIP; }
             std::memcpy(host, extra.data(), extra.size() * sizeof(DevStream));
-            e = hipMemcpyAsync(mem, host, extra.size() * sizeof(DevStream), hipMemcpyHostToDevice, stream);
-            const hipError_t ef = hipLaunchHostFunc(stream, [](void* h) { std::free(h); }, host);
-            if (ef != hipSuccess) { (void)hipStreamSynchronize(stream); std::free(host); }
+            e = hipMemcpyAsync(mem.p, host, extra.size() * sizeof(DevStream), hipMemcpyHostToDevice, mem.stream);
+            const hipError_t ef = hipLaunchHostFunc(mem.stream, [](void* h) { std::free(h); }, host);
+            if (ef != hipSuccess) { (void)hipStreamSynchronize(mem.stream); std::free(host); }
             if (e != hipSuccess) return hip_fail(e, "income-stream table upload");
-            d.extra_streams = (const DevStream*)mem;
+            d.extra_streams = (const DevStream*)mem.p;
         }
-        if (n_over > 0) d.lock_overflow = (double*)((char*)mem + table_bytes);
+        if (n_over > 0) d.lock_overflow = (double*)((char*)mem.p + table_bytes);
         return MCR_OK;
     }
-    hipError_t release(hipStream_t stream) {
-        if (!mem) return hipSuccess;
-        const hipError_t e = hipFreeAsync(mem, stream);
-        mem = nullptr;
-        return e;
-    }
+    hipError_t release() { return mem.release(); }
 };
 
 // Launches of at most this many path-wavefronts take the producer / consumer split (SPLIT = true): up to 3 per SIMD a
@@ -2908,27 +2931,6 @@ static int check_barrier_counts(const DevParams& d, int producers = 1) {
     return MCR_ERR_INVALID_ARG;
 }
 
-// Scope guard of one stream-ordered allocation: freed behind the work enqueued so far, by release() or at scope exit
-struct StreamAlloc {
-    void* p = nullptr;
-    hipStream_t stream;
-    explicit StreamAlloc(hipStream_t s) : stream(s) {}
-    StreamAlloc(const StreamAlloc&) = delete;
-    StreamAlloc& operator=(const StreamAlloc&) = delete;
-    ~StreamAlloc() { (void)release(); }
-    bool alloc(size_t bytes) {     // false: refused (nothing enqueued, the HIP error cleared)
-        if (hipMallocAsync(&p, bytes, stream) == hipSuccess) return true;
-        (void)hipGetLastError();
-        p = nullptr;
-        return false;
-    }
-    hipError_t release() {
-        if (!p) return hipSuccess;
-        const hipError_t e = hipFreeAsync(p, stream);
-        p = nullptr;
-        return e;
-    }
-};
 // The hand-over memory of a time-sliced launch (PHASE 3 / 4): [n_split][n_fields][kBlock] state + [n_split][q] flags, zeroed.
 struct SegmentHandOver {
     StreamAlloc mem;
@@ -3201,9 +3203,9 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
             if (rc != MCR_ERR_UNSUPPORTED) return rc;      // (allocation refused: the classic route below)
         }
     }
-    StreamSideBlock side;
-    rc = side.attach(d, extra, grid.x, stream);
-    if (rc != MCR_OK) { (void)side.release(stream); return rc; }
+    StreamSideBlock side(stream);
+    rc = side.attach(d, extra, grid.x);
+    if (rc != MCR_OK) return rc;
     const DevParams* const no_cand = nullptr;
     // the whole-path variants of the engine's streams (for_whole_path_variant), output mode M
     auto launch_whole_path = [&]() {
@@ -3232,7 +3234,7 @@ static int launch_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream
             else hipLaunchKernelGGL((path_kernel<2, 0, 3, true, true, 0, false, true>), grid, block, lds, stream, d, io, no_cand);
         } else launch_whole_path();
         hipError_t ex = hipGetLastError();
-        const hipError_t ef = side.release(stream);
+        const hipError_t ef = side.release();
         if (ex != hipSuccess) return hip_fail(ex, "path_kernel launch (extended streams)");
         if (ef != hipSuccess) return hip_fail(ef, "path_kernel launch (extended streams): side block release");
         return MCR_OK;
@@ -3409,6 +3411,26 @@ static int check_edges_host(const char* what, const double* e, int n) {   // np.
         if (!std::isfinite(e[k]) || (k > 0 && e[k] < e[k - 1])) { set_error("%s[%d] = %g: edges must be finite and ascending", what, k, e[k]); return MCR_ERR_INVALID_ARG; }
     return MCR_OK;
 }
+// The edge arrays of a yearly-bins request, where they are HOST pointers (`third`: hist_edges, or a rule's m_edges; null: not requested)
+static bool wants_balance_tables(const mcr_year_bins* yb) { return yb->trajectory_bins || yb->real_trajectory_bins || yb->final_success_bins; }
+static int check_year_bins_edges_host(const mcr_year_bins* yb, const char* third_name, const double* third, int n_third) {
+    int rc;
+    if (wants_balance_tables(yb) && (rc = check_edges_host("edges", yb->edges, yb->n_bins)) != MCR_OK) return rc;
+    if (yb->wr_bins && (rc = check_edges_host("wr_edges", yb->wr_edges, yb->n_wr_bins)) != MCR_OK) return rc;
+    return third ? check_edges_host(third_name, third, n_third) : MCR_OK;
+}
+// The kernel's view of a yearly-bins request: the edges and bin counts only of the tables that are asked for
+static void fill_io_year_bins(KernelIO& io, const mcr_year_bins* yb) {
+    const bool balance_tables = wants_balance_tables(yb);
+    io.yb.edges = balance_tables ? yb->edges : nullptr;
+    io.yb.n_bins = balance_tables ? yb->n_bins : 0;
+    io.yb.wr_edges = yb->wr_bins ? yb->wr_edges : nullptr;
+    io.yb.n_wr_bins = yb->wr_bins ? yb->n_wr_bins : 0;
+    io.yb.trajectory = (unsigned long long*)yb->trajectory_bins;
+    io.yb.real_trajectory = (unsigned long long*)yb->real_trajectory_bins;
+    io.yb.wr = (unsigned long long*)yb->wr_bins;
+    io.yb.final_success = (unsigned long long*)yb->final_success_bins;
+}
 // The launch: device pointers in `out` / `yb`.  Variants: the Philox stream per tax mask, the NumPy stream taxed / untaxed, and
 // the generic (XS) form for stream lists beyond the by-value block, lock slots beyond the LDS budget and the exact month.
 static int launch_year_bins(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
@@ -3426,15 +3448,7 @@ static int launch_year_bins(const mcr_params* p, const mcr_rng* rng, uint32_t st
     io.out = *out;
     io.out.path_stride = (int64_t)n_paths;
     if (io.out.hist_bins == nullptr || io.out.hist_n_bins == 0) { io.out.hist_bins = nullptr; io.out.hist_edges = nullptr; io.out.hist_n_bins = 0; }
-    const bool balance_tables = yb->trajectory_bins || yb->real_trajectory_bins || yb->final_success_bins;
-    io.yb.edges = balance_tables ? yb->edges : nullptr;
-    io.yb.n_bins = balance_tables ? yb->n_bins : 0;
-    io.yb.wr_edges = yb->wr_bins ? yb->wr_edges : nullptr;
-    io.yb.n_wr_bins = yb->wr_bins ? yb->n_wr_bins : 0;
-    io.yb.trajectory = (unsigned long long*)yb->trajectory_bins;
-    io.yb.real_trajectory = (unsigned long long*)yb->real_trajectory_bins;
-    io.yb.wr = (unsigned long long*)yb->wr_bins;
-    io.yb.final_success = (unsigned long long*)yb->final_success_bins;
+    fill_io_year_bins(io, yb);
     const uint32_t rng_kind = rng->kind;
     const dim3 grid((unsigned)((n_paths + kBlock - 1) / kBlock)), block(kBlock);
     size_t lds = 0;
@@ -3442,9 +3456,9 @@ static int launch_year_bins(const mcr_params* p, const mcr_rng* rng, uint32_t st
     if (rc != MCR_OK) return rc;
     const bool exact = needs_exact_month(d);
     const bool xs = d.n_lock_slots < d.n_lock_slots_total || needs_generic_variant(d);
-    StreamSideBlock side;
-    rc = side.attach(d, extra, grid.x, stream);
-    if (rc != MCR_OK) { (void)side.release(stream); return rc; }
+    StreamSideBlock side(stream);
+    rc = side.attach(d, extra, grid.x);
+    if (rc != MCR_OK) return rc;
     const DevParams* const no_cand = nullptr;
     for_whole_path_variant(d, kernel_rng_kind(rng), xs, exact, [&](auto R, auto T, auto A, auto X, auto EX) {
         hipLaunchKernelGGL((path_kernel<3, decltype(R)::value, decltype(T)::value, decltype(A)::value, false, 0, false, decltype(X)::value,
@@ -3452,7 +3466,7 @@ static int launch_year_bins(const mcr_params* p, const mcr_rng* rng, uint32_t st
                            grid, block, lds, stream, d, io, no_cand);
     });
     const hipError_t e = hipGetLastError();
-    const hipError_t ef = side.release(stream);
+    const hipError_t ef = side.release();
     if (e != hipSuccess) return hip_fail(e, "path_kernel launch (yearly bins)");
     if (ef != hipSuccess) return hip_fail(ef, "path_kernel launch (yearly bins): side block release");
     return MCR_OK;
@@ -3519,15 +3533,7 @@ static int launch_rule_year_bins(const mcr_params* p, const mcr_rng* rng, uint32
     io.out = *out;
     io.out.path_stride = (int64_t)n_paths;
     io.out.hist_bins = nullptr; io.out.hist_edges = nullptr; io.out.hist_n_bins = 0;
-    const bool balance_tables = yb->trajectory_bins || yb->real_trajectory_bins || yb->final_success_bins;
-    io.yb.edges = balance_tables ? yb->edges : nullptr;
-    io.yb.n_bins = balance_tables ? yb->n_bins : 0;
-    io.yb.wr_edges = yb->wr_bins ? yb->wr_edges : nullptr;
-    io.yb.n_wr_bins = yb->wr_bins ? yb->n_wr_bins : 0;
-    io.yb.trajectory = (unsigned long long*)yb->trajectory_bins;
-    io.yb.real_trajectory = (unsigned long long*)yb->real_trajectory_bins;
-    io.yb.wr = (unsigned long long*)yb->wr_bins;
-    io.yb.final_success = (unsigned long long*)yb->final_success_bins;
+    fill_io_year_bins(io, yb);
     RuleBinsRecord host = {rule->upper, rule->lower, 1.0 - rule->cut, 1.0 + rule->raise, rule->floor, rule->ceiling,
                            (unsigned long long*)rule_yb->year_counts, (unsigned long long*)rule_yb->multiplier_bins,
                            rule_yb->multiplier_bins ? rule_yb->m_edges : nullptr, rule_yb->multiplier_bins ? rule_yb->n_m_bins : 0, 0};
@@ -3555,8 +3561,8 @@ static int launch_rule_year_bins(const mcr_params* p, const mcr_rng* rng, uint32
 // side streams of a leased StreamFork; the caller's stream waits for all of them.  Returns the first error.
 template <typename Launch>
 static int fork_join(int device, hipStream_t main, int n, Launch&& launch) {
-    StreamForkLease fork_lease(device);
-    StreamFork* f = fork_lease.f;
+    StreamForkPool::Lease fork_lease(g_stream_fork, device);
+    StreamFork* f = fork_lease.p;
     if (!f) { set_error("could not create probe streams"); return MCR_ERR_HIP; }
     const int used = n < kForkStreams ? n : kForkStreams;
     hipError_t e;
@@ -4244,6 +4250,166 @@ static int check_outcome_args(const mcr_option_outcomes** rows, uint64_t n_paths
     return MCR_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Host-buffer calls (the *_host_rng entry points): NumPy pointers in, device work on a leased context, NumPy pointers out
+// ---------------------------------------------------------------------------------------------
+// The plan of one host-buffer call.  The entry point lists its buffers (plan / plan_rows / plan_rng), begin() leases a context
+// of the device, carves every device buffer from the context's block (256-byte aligned slices), points the planned device
+// slots at them and uploads; the entry point launches on stream(); finish() downloads, synchronises and maps the errors.
+class HostCall {
+public:
+    HostCall() = default;
+    HostCall(const HostCall&) = delete;
+    HostCall& operator=(const HostCall&) = delete;
+    ~HostCall() {   // a block above the keep limit does not go back to the pool
+        HostCtx* c = lease_ ? lease_->p : nullptr;
+        if (c && c->capacity > kHostCtxKeepBytes) { (void)hipFree(c->block); c->block = nullptr; c->capacity = 0; }
+    }
+    // A flat buffer of `bytes`: *dev_slot becomes its device address.  A null host pointer or no bytes plans nothing.
+    template <class T>
+    void plan(T** dev_slot, const void* host, size_t bytes, bool upload, bool download) {
+        add({(void**)dev_slot, const_cast<void*>(host), 1, bytes, 0, 0, 0, upload, download});
+    }
+    // A pitched matrix (download only): `rows` rows of row_bytes, dev_pitch apart on the device and host_pitch apart at the caller
+    template <class T>
+    void plan_rows(T** dev_slot, const void* host, size_t rows, size_t row_bytes, size_t dev_pitch, size_t host_pitch) {
+        add({(void**)dev_slot, const_cast<void*>(host), rows, row_bytes, dev_pitch, host_pitch, 0, false, true});
+    }
+    // The host tables of an rng descriptor (per-path seeds of n_paths, the history record): uploaded, and *rng — the call's own
+    // copy of the descriptor — pointed at the device copies
+    void plan_rng(mcr_rng* rng, uint64_t n_paths) {
+        plan(&rng->path_seeds, rng->path_seeds, (size_t)n_paths * sizeof(uint32_t), true, false);
+        if (rng->kind == MCR_RNG_HISTORY) plan(&rng->history, rng->history, (size_t)rng->history_months * 3 * sizeof(double), true, false);
+    }
+    // `what`: the allocation's name in the error text.  A failed upload is waited for before it is reported.
+    int begin(int device, const char* what) {
+        lease_.emplace(g_host_ctx, device);
+        HostCtx* ctx = lease_->p;
+        if (!ctx) return MCR_ERR_HIP;
+        hipError_t e = hipSuccess;
+        if (total_ > ctx->capacity) {   // grow the block (contents are not preserved)
+            if (ctx->block) { (void)hipFree(ctx->block); ctx->block = nullptr; ctx->capacity = 0; }
+            e = hipMalloc(&ctx->block, total_);
+            if (e != hipSuccess) { ctx->block = nullptr; return hip_fail(e, what); }
+            ctx->capacity = total_;
+        }
+        for (Buf& b : bufs_) {   // accumulated blocks start from the caller's current values
+            *b.dev = (char*)ctx->block + b.offset;
+            if (b.upload && e == hipSuccess) e = hipMemcpyAsync(*b.dev, b.host, b.row_bytes, hipMemcpyHostToDevice, ctx->stream);
+        }
+        if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return hip_fail(e, "upload"); }
+        return MCR_OK;
+    }
+    hipStream_t stream() const { return lease_->p->stream; }
+    // rc: the launch's.  ONE synchronisation, of this call's stream only, also behind a failed launch or copy.  `staged`: the flat
+    // downloads land in staging copies and reach the caller only if the whole call succeeded; pitched matrices always go straight
+    // to the caller (staging them would double host memory and copy time).  `what`: the execution's name in the error text.
+    int finish(int rc, bool staged, const char* what) {
+        const hipStream_t s = stream();
+        std::vector<std::vector<unsigned char>> stage(staged ? bufs_.size() : 0);
+        hipError_t e = hipSuccess;
+        for (size_t i = 0; i < bufs_.size() && rc == MCR_OK && e == hipSuccess; ++i) {
+            const Buf& b = bufs_[i];
+            if (!b.download) continue;
+            if (b.rows != 1) { e = hipMemcpy2DAsync(b.host, b.host_pitch, *b.dev, b.dev_pitch, b.row_bytes, b.rows, hipMemcpyDeviceToHost, s); continue; }
+            if (staged) stage[i].resize(b.row_bytes);
+            e = hipMemcpyAsync(staged ? stage[i].data() : b.host, *b.dev, b.row_bytes, hipMemcpyDeviceToHost, s);
+        }
+        const hipError_t es = hipStreamSynchronize(s);
+        if (rc != MCR_OK) return rc;
+        if (e != hipSuccess) return hip_fail(e, "download");
+        if (es != hipSuccess) return hip_fail(es, what);
+        for (size_t i = 0; i < stage.size(); ++i)
+            if (!stage[i].empty()) std::memcpy(bufs_[i].host, stage[i].data(), bufs_[i].row_bytes);
+        return MCR_OK;
+    }
+
+private:
+    struct Buf { void** dev; void* host; size_t rows, row_bytes, dev_pitch, host_pitch, offset; bool upload, download; };
+    void add(Buf b) {
+        if (!b.host || b.row_bytes == 0) return;
+        b.offset = total_;
+        total_ += ((b.rows == 1 ? b.row_bytes : b.rows * b.dev_pitch) + 255) & ~(size_t)255;
+        bufs_.push_back(b);
+    }
+    std::vector<Buf> bufs_;
+    size_t total_ = 0;
+    std::optional<HostCtxPool::Lease> lease_;
+};
+
+// The accumulated integer blocks of a host-buffer call, in one list: the caller's pointer, the slot of the copy that a device
+// or a shard works on, and the length.  The host forms upload, download and sum them alike.
+struct IntBlock { uint64_t* const* src; uint64_t** dst; size_t n; };
+static std::vector<IntBlock> output_blocks(const mcr_sizes& sz, const mcr_outputs* in, mcr_outputs* o) {
+    const bool hist = in->hist_bins && in->hist_n_bins > 0;
+    return {{&in->counters, &o->counters, MCR_N_COUNTERS}, {&in->wr_obs_counts, &o->wr_obs_counts, (size_t)sz.retirement_years},
+            {&in->ruin_year_bins, &o->ruin_year_bins, (size_t)sz.ruin_bins}, {&in->hist_bins, &o->hist_bins, hist ? (size_t)in->hist_n_bins : 0}};
+}
+struct YearBinsOut { mcr_outputs o; mcr_year_bins y; };   // what a yearly-bins call writes to
+static std::vector<IntBlock> year_bins_blocks(const mcr_sizes& sz, const YearBinsOut& in, YearBinsOut* o) {
+    const size_t T = (size_t)sz.trajectory_len, ry = (size_t)sz.retirement_years;
+    const size_t cells = (size_t)in.y.n_bins + 2, wcells = (size_t)in.y.n_wr_bins + 2;
+    std::vector<IntBlock> blocks = output_blocks(sz, &in.o, &o->o);
+    blocks.insert(blocks.end(), {{&in.y.trajectory_bins, &o->y.trajectory_bins, T * cells}, {&in.y.real_trajectory_bins, &o->y.real_trajectory_bins, T * cells},
+                                 {&in.y.wr_bins, &o->y.wr_bins, ry * wcells}, {&in.y.final_success_bins, &o->y.final_success_bins, cells}});
+    return blocks;
+}
+
+// One host-buffer call sharded over a device list (null / empty: every device): contiguous global path ranges of
+// ceil(n_paths / W) paths, one host thread per entry that has paths (each leases its own context), every integer block summed
+// on the host.  No collective is needed: what the devices exchange is a few KB and lands in host memory anyway.
+//   blocks(Out* shard): the integer blocks, src in `caller`, dst in *shard — each shard gets zeroed blocks of its own there
+//   run(device, begin, count, shard_out): the one-device call on paths [begin, begin + count) of the range
+// One device in the list: run(device, 0, n_paths, caller) on the calling thread.  The first failing shard's error is reported
+// with its device in front.
+template <class Out, class Blocks, class Run>
+static int run_sharded(const int32_t* devices, int32_t n_devices, uint64_t n_paths, const Out& caller, Blocks blocks, Run run) {
+    std::vector<int> devs;
+    if (!devices || n_devices <= 0) {
+        const int n = mcr_device_count();
+        if (n <= 0) { set_error("no usable HIP device (the engine has no CPU fallback)"); return MCR_ERR_NO_DEVICE; }
+        for (int i = 0; i < n; ++i) devs.push_back(i);
+    } else {
+        devs.assign(devices, devices + n_devices);
+    }
+    const size_t W = devs.size();
+    if (W == 1) return run(devs[0], (uint64_t)0, n_paths, caller);
+    const uint64_t per = (n_paths + W - 1) / W;
+    struct Shard {
+        int rc = MCR_OK;
+        char err[512] = "";
+        Out out;
+        std::vector<std::vector<uint64_t>> mem;   // empty: the shard has no paths
+    };
+    std::vector<Shard> shards(W);
+    std::vector<std::thread> threads;
+    for (size_t w = 0; w < W; ++w) {
+        const uint64_t begin = std::min<uint64_t>(w * per, n_paths);
+        const uint64_t count = std::min<uint64_t>(per, n_paths - begin);
+        if (count == 0) continue;
+        Shard& S = shards[w];
+        S.out = caller;
+        for (const IntBlock& b : blocks(&S.out)) {
+            S.mem.emplace_back(*b.src && b.n ? b.n : 0, 0);
+            *b.dst = S.mem.back().empty() ? nullptr : S.mem.back().data();
+        }
+        threads.emplace_back([&shards, &devs, &run, w, begin, count]() {
+            Shard& T = shards[w];
+            T.rc = run(devs[w], begin, count, T.out);
+            if (T.rc != MCR_OK) std::snprintf(T.err, sizeof(T.err), "device %d: %s", devs[w], mcr_last_error());
+        });
+    }
+    for (std::thread& t : threads) t.join();
+    for (const Shard& S : shards)
+        if (S.rc != MCR_OK) { set_error("%s", S.err); return S.rc; }
+    Out scratch = caller;
+    const std::vector<IntBlock> sums = blocks(&scratch);
+    for (const Shard& S : shards)
+        for (size_t i = 0; i < S.mem.size(); ++i)
+            for (size_t k = 0; k < S.mem[i].size(); ++k) (*sums[i].src)[k] += S.mem[i][k];
+    return MCR_OK;
+}
+
 }  // namespace mcr
 
 // =============================================================================================
@@ -4267,42 +4433,21 @@ int mcr_query_sizes(const mcr_params* p, int32_t working_months, mcr_sizes* out)
     return query_sizes(p, working_months, out);
 }
 
-int mcr_k1_growth_form(const mcr_params* p, int32_t working_months, int32_t* mask) {
+// mcr_k1_*_form: the mask a launch on this parameter block runs, by the form's own rule (growth_form_of, ...)
+static int k1_form(const mcr_params* p, int32_t working_months, int32_t* mask, int (*form_of)(const DevParams&, bool, int*)) {
     if (!mask) { set_error("null mask"); return MCR_ERR_INVALID_ARG; }
     DevParams d;
     int rc = derive_params(p, working_months, &d);
     if (rc != MCR_OK) return rc;
     int m = 0;
-    rc = growth_form_of(d, true, &m);
+    rc = form_of(d, true, &m);
     if (rc != MCR_OK) return rc;
     *mask = m;
     return MCR_OK;
 }
-
-int mcr_k1_month_form(const mcr_params* p, int32_t working_months, int32_t* mask) {
-    if (!mask) { set_error("null mask"); return MCR_ERR_INVALID_ARG; }
-    DevParams d;
-    int rc = derive_params(p, working_months, &d);
-    if (rc != MCR_OK) return rc;
-    int m = 0;
-    rc = month_form_of(d, true, &m);
-    if (rc != MCR_OK) return rc;
-    *mask = m;
-    return MCR_OK;
-}
-
-int mcr_k1_stream_form(const mcr_params* p, int32_t working_months, int32_t* mask) {
-    if (!mask) { set_error("null mask"); return MCR_ERR_INVALID_ARG; }
-    DevParams d;
-    std::vector<DevStream> extra;
-    int rc = derive_params(p, working_months, &d, &extra);
-    if (rc != MCR_OK) return rc;
-    int m = 0;
-    rc = stream_form_of(d, true, &m);
-    if (rc != MCR_OK) return rc;
-    *mask = m;
-    return MCR_OK;
-}
+int mcr_k1_growth_form(const mcr_params* p, int32_t working_months, int32_t* mask) { return k1_form(p, working_months, mask, growth_form_of); }
+int mcr_k1_month_form(const mcr_params* p, int32_t working_months, int32_t* mask) { return k1_form(p, working_months, mask, month_form_of); }
+int mcr_k1_stream_form(const mcr_params* p, int32_t working_months, int32_t* mask) { return k1_form(p, working_months, mask, stream_form_of); }
 
 int mcr_k1_screen(const mcr_params* p, const mcr_rng* rng, int32_t working_months, uint64_t n_paths, int32_t hist_n_bins, int32_t* screened) {
     if (!screened) { set_error("null screened"); return MCR_ERR_INVALID_ARG; }
@@ -4890,8 +5035,7 @@ int mcr_run_batch_host(const mcr_params* p, uint64_t seed, uint32_t stream_id, u
     return mcr_run_batch_host_rng(p, &r, stream_id, path_begin, n_paths, working_months, injected_shocks, out, device);
 }
 
-// One host-buffer batch on `device`: device buffers carved from the thread's cached block, uploads / kernel /
-// downloads on the thread's private stream, ONE stream synchronisation at the end.
+// One host-buffer batch on `device` (HostCall): the per-path columns and trajectory slabs come straight back to the caller
 static int run_batch_host_on(int device, const mcr_params* p, const mcr_rng* rng_in, uint32_t stream_id, uint64_t path_begin,
                              uint64_t n_paths, int32_t working_months, const double* injected_shocks, const mcr_outputs* out) {
     MCR_ENTER_DEVICE(device);
@@ -4907,18 +5051,10 @@ static int run_batch_host_on(int device, const mcr_params* p, const mcr_rng* rng
     const size_t n = (size_t)n_paths;
     mcr_outputs d = {};
     d.path_stride = (int64_t)((n + 63) / 64 * 64);  // device rows padded to whole wavefronts
-    // plan: every device buffer is a slice of one block (256-byte aligned)
-    struct Buf { void** dev; void* host; size_t rows, row_bytes, dev_pitch, host_pitch, offset; bool upload, download; };
-    std::vector<Buf> bufs;
-    size_t total = 0;
-    auto plan = [&](void** dev, const void* host, size_t rows, size_t row_bytes, size_t dev_pitch, size_t host_pitch, bool up, bool down) {
-        if (!host) return;
-        bufs.push_back({dev, const_cast<void*>(host), rows, row_bytes, dev_pitch, host_pitch, total, up, down});
-        total += ((rows == 1 ? row_bytes : rows * dev_pitch) + 255) & ~(size_t)255;
-    };
-    auto vec = [&](double* host, double** dev) { plan((void**)dev, host, 1, n * sizeof(double), 0, 0, false, true); };
+    HostCall call;
+    auto vec = [&](double* host, double** dev) { call.plan(dev, host, n * sizeof(double), false, true); };
     auto mat = [&](double* host, double** dev, int rows) {
-        plan((void**)dev, host, (size_t)rows, n * sizeof(double), (size_t)d.path_stride * sizeof(double), (size_t)hstride * sizeof(double), false, true);
+        call.plan_rows(dev, host, (size_t)rows, n * sizeof(double), (size_t)d.path_stride * sizeof(double), (size_t)hstride * sizeof(double));
     };
     vec(out->start_balance, &d.start_balance);
     vec(out->final_balance, &d.final_balance);
@@ -4926,65 +5062,29 @@ static int run_batch_host_on(int device, const mcr_params* p, const mcr_rng* rng
     vec(out->first_year_gross_withdrawal, &d.first_year_gross_withdrawal);
     vec(out->first_year_real_gross_withdrawal, &d.first_year_real_gross_withdrawal);
     vec(out->inflation_at_retirement, &d.inflation_at_retirement);
-    plan((void**)&d.success, out->success, 1, n, 0, 0, false, true);
+    call.plan(&d.success, out->success, n, false, true);
     mat(out->trajectory, &d.trajectory, sz.trajectory_len);
     mat(out->real_trajectory, &d.real_trajectory, sz.trajectory_len);
     mat(out->withdrawal_rate_trajectory, &d.withdrawal_rate_trajectory, sz.retirement_years);
-    // accumulated counters: the device copy starts from the caller's current values
-    plan((void**)&d.counters, out->counters, 1, MCR_N_COUNTERS * sizeof(uint64_t), 0, 0, true, true);
-    plan((void**)&d.wr_obs_counts, out->wr_obs_counts, 1, (size_t)sz.retirement_years * sizeof(uint64_t), 0, 0, true, true);
-    plan((void**)&d.ruin_year_bins, out->ruin_year_bins, 1, (size_t)sz.ruin_bins * sizeof(uint64_t), 0, 0, true, true);
     if (out->hist_bins && out->hist_n_bins != 0) {   // in-kernel final-balance histogram on the caller's edges
         const int nb = out->hist_n_bins;
         if (nb < 0 || nb > MCR_MAX_HIST_BINS || !out->hist_edges) { set_error("hist_bins requested with hist_n_bins = %d (1..%d) / null hist_edges", nb, MCR_MAX_HIST_BINS); return MCR_ERR_INVALID_ARG; }
-        for (int k = 0; k <= nb; ++k)   // host pointer: the edges can be checked here (np.histogram: "bins must increase monotonically")
-            if (!std::isfinite(out->hist_edges[k]) || (k > 0 && out->hist_edges[k] < out->hist_edges[k - 1])) {
-                set_error("hist_edges[%d] = %g: edges must be finite and ascending", k, out->hist_edges[k]);
-                return MCR_ERR_INVALID_ARG;
-            }
+        if ((rc = check_edges_host("hist_edges", out->hist_edges, nb)) != MCR_OK) return rc;   // host pointer: the edges can be checked here
         d.hist_n_bins = nb;
-        plan((void**)&d.hist_edges, out->hist_edges, 1, (size_t)(nb + 1) * sizeof(double), 0, 0, true, false);
-        plan((void**)&d.hist_bins, out->hist_bins, 1, (size_t)nb * sizeof(uint64_t), 0, 0, true, true);
+        call.plan(&d.hist_edges, out->hist_edges, (size_t)(nb + 1) * sizeof(double), true, false);
     }
+    // accumulated counters: the device copy starts from the caller's current values
+    for (const IntBlock& b : output_blocks(sz, out, &d)) call.plan(b.dst, *b.src, b.n * sizeof(uint64_t), true, true);
     double* d_inj = nullptr;
-    plan((void**)&d_inj, injected_shocks, 1, n * (size_t)sz.shock_rows * 3 * sizeof(double), 0, 0, true, false);
+    call.plan(&d_inj, injected_shocks, n * (size_t)sz.shock_rows * 3 * sizeof(double), true, false);
     mcr_rng rng = *rng_in;
-    uint32_t* d_seeds = nullptr;   // explicit per-path seeds: upload
-    plan((void**)&d_seeds, rng.path_seeds, 1, n * sizeof(uint32_t), 0, 0, true, false);
-    const bool history = rng.kind == MCR_RNG_HISTORY;
-    double* d_history = nullptr;   // the history stream's table: upload
-    if (history) plan((void**)&d_history, rng.history, 1, (size_t)rng.history_months * 3 * sizeof(double), 0, 0, true, false);
-
-    HostCtxLease lease(device);
-    HostCtx* ctx = lease.ctx;
-    if (!ctx) return MCR_ERR_HIP;
-    hipError_t e = host_ctx_reserve(ctx, total);
-    if (e != hipSuccess) return hip_fail(e, "device allocation (host-buffer batch)");
-    for (Buf& b : bufs) {
-        *b.dev = (char*)ctx->block + b.offset;
-        if (b.upload && e == hipSuccess) e = hipMemcpyAsync(*b.dev, b.host, b.row_bytes, hipMemcpyHostToDevice, ctx->stream);
-    }
-    if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return hip_fail(e, "upload"); }
-    if (rng.path_seeds) rng.path_seeds = d_seeds;
-    if (history) rng.history = d_history;
-    rc = launch_paths(p, &rng, stream_id, path_begin, n_paths, working_months, d_inj, &d, ctx->stream);
-    if (rc == MCR_OK) {
-        for (const Buf& b : bufs) {
-            if (!b.download || e != hipSuccess) continue;
-            if (b.rows == 1) e = hipMemcpyAsync(b.host, *b.dev, b.row_bytes, hipMemcpyDeviceToHost, ctx->stream);
-            else e = hipMemcpy2DAsync(b.host, b.host_pitch, *b.dev, b.dev_pitch, b.row_bytes, b.rows, hipMemcpyDeviceToHost, ctx->stream);
-        }
-    }
-    const hipError_t es = hipStreamSynchronize(ctx->stream);   // this call's stream only
-    if (rc != MCR_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "download");
-    if (es != hipSuccess) return hip_fail(es, "path_kernel execution");
-    return MCR_OK;
+    call.plan_rng(&rng, n_paths);
+    if ((rc = call.begin(device, "device allocation (host-buffer batch)")) != MCR_OK) return rc;
+    rc = launch_paths(p, &rng, stream_id, path_begin, n_paths, working_months, d_inj, &d, call.stream());
+    return call.finish(rc, false, "path_kernel execution");
 }
 
-// The same batch sharded over several devices: contiguous global path ranges, one host thread per device
-// (each with its own stream and scratch), counter / bin vectors summed on the host.  No collective is needed:
-// the exchange step of the path is < 2 KB and lands in host memory anyway.
+// The same batch sharded over several devices (run_sharded): a shard's per-path columns are the caller's, shifted to its range
 static int run_batch_host_multi(const int32_t* devices, int32_t n_devices, const mcr_params* p, const mcr_rng* rng_in,
                                 uint32_t stream_id, uint64_t path_begin, uint64_t n_paths, int32_t working_months,
                                 const double* injected_shocks, const mcr_outputs* out) {
@@ -4992,65 +5092,22 @@ static int run_batch_host_multi(const int32_t* devices, int32_t n_devices, const
     mcr_sizes sz;
     int rc = query_sizes(p, working_months, &sz);
     if (rc != MCR_OK) return rc;
-    std::vector<int> devs;
-    if (!devices || n_devices <= 0) {
-        const int n = mcr_device_count();
-        if (n <= 0) { set_error("no usable HIP device (the engine has no CPU fallback)"); return MCR_ERR_NO_DEVICE; }
-        for (int i = 0; i < n; ++i) devs.push_back(i);
-    } else {
-        devs.assign(devices, devices + n_devices);
-    }
-    const size_t W = devs.size();
-    if (W == 1) return run_batch_host_on(devs[0], p, rng_in, stream_id, path_begin, n_paths, working_months, injected_shocks, out);
     const int64_t hstride = out->path_stride > 0 ? out->path_stride : (int64_t)n_paths;
-    const uint64_t per = (n_paths + W - 1) / W;
-    struct Shard {
-        int rc = MCR_OK;
-        char err[512] = "";
-        std::vector<uint64_t> counters, wr, ruin, hist;
-    };
-    std::vector<Shard> shards(W);
-    std::vector<std::thread> threads;
-    for (size_t w = 0; w < W; ++w) {
-        const uint64_t begin = std::min<uint64_t>(w * per, n_paths);
-        const uint64_t count = std::min<uint64_t>(per, n_paths - begin);
-        if (count == 0) continue;
-        Shard& S = shards[w];
-        S.counters.assign(MCR_N_COUNTERS, 0);
-        S.wr.assign((size_t)sz.retirement_years, 0);
-        S.ruin.assign((size_t)sz.ruin_bins, 0);
-        if (out->hist_bins && out->hist_n_bins > 0) S.hist.assign((size_t)out->hist_n_bins, 0);
-        threads.emplace_back([&, w, begin, count]() {
-            Shard& T = shards[w];
-            mcr_outputs o = *out;    // host pointers of this shard's columns
+    return run_sharded(devices, n_devices, n_paths, *out,
+        [&](mcr_outputs* shard) { return output_blocks(sz, out, shard); },
+        [&](int device, uint64_t begin, uint64_t count, const mcr_outputs& shard) {
+            mcr_outputs o = shard;    // host pointers of this shard's columns
             auto shift = [&](double*& ptr) { if (ptr) ptr += begin; };
             shift(o.start_balance); shift(o.final_balance); shift(o.years_to_ruin);
             shift(o.first_year_gross_withdrawal); shift(o.first_year_real_gross_withdrawal); shift(o.inflation_at_retirement);
             if (o.success) o.success += begin;
             shift(o.trajectory); shift(o.real_trajectory); shift(o.withdrawal_rate_trajectory);
             o.path_stride = hstride;
-            o.counters = out->counters ? T.counters.data() : nullptr;
-            o.wr_obs_counts = out->wr_obs_counts ? T.wr.data() : nullptr;
-            o.ruin_year_bins = out->ruin_year_bins ? T.ruin.data() : nullptr;
-            o.hist_bins = T.hist.empty() ? nullptr : T.hist.data();
             mcr_rng r = *rng_in;
             if (r.path_seeds) r.path_seeds += begin;
             const double* inj = injected_shocks ? injected_shocks + (size_t)begin * (size_t)sz.shock_rows * 3u : nullptr;
-            T.rc = run_batch_host_on(devs[w], p, &r, stream_id, path_begin + begin, count, working_months, inj, &o);
-            if (T.rc != MCR_OK) std::snprintf(T.err, sizeof(T.err), "device %d: %s", devs[w], mcr_last_error());
+            return run_batch_host_on(device, p, &r, stream_id, path_begin + begin, count, working_months, inj, &o);
         });
-    }
-    for (std::thread& t : threads) t.join();
-    for (const Shard& S : shards)
-        if (S.rc != MCR_OK) { set_error("%s", S.err); return S.rc; }
-    for (const Shard& S : shards) {
-        if (S.counters.empty()) continue;
-        if (out->counters) for (int k = 0; k < MCR_N_COUNTERS; ++k) out->counters[k] += S.counters[k];
-        if (out->wr_obs_counts) for (int k = 0; k < sz.retirement_years; ++k) out->wr_obs_counts[k] += S.wr[k];
-        if (out->ruin_year_bins) for (int k = 0; k < sz.ruin_bins; ++k) out->ruin_year_bins[k] += S.ruin[k];
-        for (size_t k = 0; k < S.hist.size(); ++k) out->hist_bins[k] += S.hist[k];
-    }
-    return MCR_OK;
 }
 
 int mcr_run_batch_host_rng(const mcr_params* p, const mcr_rng* rng_in, uint32_t stream_id, uint64_t path_begin,
@@ -5078,19 +5135,6 @@ int mcr_run_year_bins_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stre
     return launch_year_bins(p, rng, stream_id, path_begin, n_paths, working_months, out, yb, (hipStream_t)hip_stream);
 }
 
-// The accumulated integer blocks of a yearly-bins call, in one list: the host forms upload, download and sum them alike
-struct YearBinsBlock { uint64_t* const* src; uint64_t** dst; size_t n; };
-static std::vector<YearBinsBlock> year_bins_blocks(const mcr_sizes& sz, const mcr_outputs* in, const mcr_year_bins* yin, mcr_outputs* o, mcr_year_bins* y) {
-    const size_t T = (size_t)sz.trajectory_len, ry = (size_t)sz.retirement_years;
-    const size_t cells = (size_t)yin->n_bins + 2, wcells = (size_t)yin->n_wr_bins + 2;
-    const bool hist = in->hist_bins && in->hist_n_bins > 0;
-    return {
-        {&in->counters, &o->counters, MCR_N_COUNTERS}, {&in->wr_obs_counts, &o->wr_obs_counts, ry}, {&in->ruin_year_bins, &o->ruin_year_bins, (size_t)sz.ruin_bins},
-        {&in->hist_bins, &o->hist_bins, hist ? (size_t)in->hist_n_bins : 0},
-        {&yin->trajectory_bins, &y->trajectory_bins, T * cells}, {&yin->real_trajectory_bins, &y->real_trajectory_bins, T * cells},
-        {&yin->wr_bins, &y->wr_bins, ry * wcells}, {&yin->final_success_bins, &y->final_success_bins, cells},
-    };
-}
 // Everything that can be checked on the host, before any device work
 static int check_year_bins_host(const mcr_params* p, const mcr_rng* rng, int32_t working_months, const mcr_outputs* out,
                                 const mcr_year_bins* yb, mcr_sizes* sz) {
@@ -5099,11 +5143,16 @@ static int check_year_bins_host(const mcr_params* p, const mcr_rng* rng, int32_t
     if ((rc = query_sizes(p, working_months, sz)) != MCR_OK) return rc;
     if ((rc = validate_params(p)) != MCR_OK) return rc;
     if ((rc = check_year_bins(out, yb)) != MCR_OK) return rc;
-    if ((yb->trajectory_bins || yb->real_trajectory_bins || yb->final_success_bins) && (rc = check_edges_host("edges", yb->edges, yb->n_bins)) != MCR_OK) return rc;
-    if (yb->wr_bins && (rc = check_edges_host("wr_edges", yb->wr_edges, yb->n_wr_bins)) != MCR_OK) return rc;
-    if (out->hist_bins && out->hist_n_bins > 0 && (rc = check_edges_host("hist_edges", out->hist_edges, out->hist_n_bins)) != MCR_OK) return rc;
-    return MCR_OK;
+    return check_year_bins_edges_host(yb, "hist_edges", out->hist_bins && out->hist_n_bins > 0 ? out->hist_edges : nullptr, out->hist_n_bins);
 }
+// The buffers every yearly-bins form plans: the integer blocks of `host` (up and down) and the edges of the requested tables (up)
+static void plan_year_bins(HostCall& call, const mcr_sizes& sz, const YearBinsOut& host, YearBinsOut* dev) {
+    dev->y.n_bins = host.y.n_bins; dev->y.n_wr_bins = host.y.n_wr_bins;
+    for (const IntBlock& b : year_bins_blocks(sz, host, dev)) call.plan(b.dst, *b.src, b.n * sizeof(uint64_t), true, true);
+    if (wants_balance_tables(&host.y)) call.plan(&dev->y.edges, host.y.edges, (size_t)(host.y.n_bins + 1) * sizeof(double), true, false);
+    if (host.y.wr_bins) call.plan(&dev->y.wr_edges, host.y.wr_edges, (size_t)(host.y.n_wr_bins + 1) * sizeof(double), true, false);
+}
+// One device (HostCall): the tables come back through staging copies, so the caller's stay untouched unless the whole call succeeds
 static int run_year_bins_host_on(int device, const mcr_params* p, const mcr_rng* rng_in, uint32_t stream_id, uint64_t path_begin,
                                  uint64_t n_paths, int32_t working_months, const mcr_outputs* out, const mcr_year_bins* yb) {
     MCR_ENTER_DEVICE(device);
@@ -5111,119 +5160,36 @@ static int run_year_bins_host_on(int device, const mcr_params* p, const mcr_rng*
     int rc = check_year_bins_host(p, rng_in, working_months, out, yb, &sz);
     if (rc != MCR_OK) return rc;
     if (n_paths == 0) return MCR_OK;
-    mcr_outputs d = {};
-    mcr_year_bins dy = {};
-    dy.n_bins = yb->n_bins; dy.n_wr_bins = yb->n_wr_bins;
-    if (out->hist_bins && out->hist_n_bins > 0) d.hist_n_bins = out->hist_n_bins;
-    // plan: every device buffer is a slice of the leased context's block (256-byte aligned)
-    struct Buf { void** dev; void* host; size_t bytes, offset; bool download; };
-    std::vector<Buf> bufs;
-    size_t total = 0;
-    auto plan = [&](void** dev, const void* host, size_t bytes, bool down) {
-        if (!host || bytes == 0) return;
-        bufs.push_back({dev, const_cast<void*>(host), bytes, total, down});
-        total += (bytes + 255) & ~(size_t)255;
-    };
-    for (const YearBinsBlock& b : year_bins_blocks(sz, out, yb, &d, &dy)) plan((void**)b.dst, *b.src, b.n * sizeof(uint64_t), true);
-    if (d.hist_n_bins > 0) plan((void**)&d.hist_edges, out->hist_edges, (size_t)(d.hist_n_bins + 1) * sizeof(double), false);
-    if (yb->trajectory_bins || yb->real_trajectory_bins || yb->final_success_bins) plan((void**)&dy.edges, yb->edges, (size_t)(yb->n_bins + 1) * sizeof(double), false);
-    if (yb->wr_bins) plan((void**)&dy.wr_edges, yb->wr_edges, (size_t)(yb->n_wr_bins + 1) * sizeof(double), false);
-    mcr_rng rng = *rng_in;
-    uint32_t* d_seeds = nullptr;
-    plan((void**)&d_seeds, rng.path_seeds, (size_t)n_paths * sizeof(uint32_t), false);
-    const bool history = rng.kind == MCR_RNG_HISTORY;
-    double* d_history = nullptr;   // the history stream's table: upload
-    if (history) plan((void**)&d_history, rng.history, (size_t)rng.history_months * 3 * sizeof(double), false);
-
-    HostCtxLease lease(device);
-    HostCtx* ctx = lease.ctx;
-    if (!ctx) return MCR_ERR_HIP;
-    hipError_t e = host_ctx_reserve(ctx, total);
-    if (e != hipSuccess) return hip_fail(e, "device allocation (yearly bins)");
-    for (Buf& b : bufs) {   // accumulated blocks start from the caller's current values
-        *b.dev = (char*)ctx->block + b.offset;
-        if (e == hipSuccess) e = hipMemcpyAsync(*b.dev, b.host, b.bytes, hipMemcpyHostToDevice, ctx->stream);
+    const YearBinsOut host = {*out, *yb};
+    YearBinsOut d = {};
+    HostCall call;
+    plan_year_bins(call, sz, host, &d);
+    if (out->hist_bins && out->hist_n_bins > 0) {
+        d.o.hist_n_bins = out->hist_n_bins;
+        call.plan(&d.o.hist_edges, out->hist_edges, (size_t)(out->hist_n_bins + 1) * sizeof(double), true, false);
     }
-    if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return hip_fail(e, "upload"); }
-    if (rng.path_seeds) rng.path_seeds = d_seeds;
-    if (history) rng.history = d_history;
-    rc = launch_year_bins(p, &rng, stream_id, path_begin, n_paths, working_months, &d, &dy, ctx->stream);
-    // the tables come back through a staging copy: the caller's stay untouched unless the whole call succeeds
-    std::vector<std::vector<unsigned char>> staged(bufs.size());
-    if (rc == MCR_OK)
-        for (size_t i = 0; i < bufs.size(); ++i) {
-            if (!bufs[i].download || e != hipSuccess) continue;
-            staged[i].resize(bufs[i].bytes);
-            e = hipMemcpyAsync(staged[i].data(), *bufs[i].dev, bufs[i].bytes, hipMemcpyDeviceToHost, ctx->stream);
-        }
-    const hipError_t es = hipStreamSynchronize(ctx->stream);
-    if (rc != MCR_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "download");
-    if (es != hipSuccess) return hip_fail(es, "path_kernel execution (yearly bins)");
-    for (size_t i = 0; i < bufs.size(); ++i)
-        if (!staged[i].empty()) std::memcpy(bufs[i].host, staged[i].data(), bufs[i].bytes);
-    return MCR_OK;
+    mcr_rng rng = *rng_in;
+    call.plan_rng(&rng, n_paths);
+    if ((rc = call.begin(device, "device allocation (yearly bins)")) != MCR_OK) return rc;
+    rc = launch_year_bins(p, &rng, stream_id, path_begin, n_paths, working_months, &d.o, &d.y, call.stream());
+    return call.finish(rc, true, "path_kernel execution (yearly bins)");
 }
 
-// Sharded over a device list like run_batch_host_multi: contiguous global path ranges, one host thread per entry, every
-// integer block summed on the host.
+// Sharded over a device list (run_sharded): a shard has no per-path pointer but its seeds
 static int run_year_bins_host_multi(const int32_t* devices, int32_t n_devices, const mcr_params* p, const mcr_rng* rng_in, uint32_t stream_id,
                                     uint64_t path_begin, uint64_t n_paths, int32_t working_months, const mcr_outputs* out, const mcr_year_bins* yb) {
     if (!rng_in) { set_error("null rng"); return MCR_ERR_INVALID_ARG; }
     mcr_sizes sz;
     int rc = check_year_bins_host(p, rng_in, working_months, out, yb, &sz);
     if (rc != MCR_OK) return rc;
-    std::vector<int> devs;
-    if (!devices || n_devices <= 0) {
-        const int n = mcr_device_count();
-        if (n <= 0) { set_error("no usable HIP device (the engine has no CPU fallback)"); return MCR_ERR_NO_DEVICE; }
-        for (int i = 0; i < n; ++i) devs.push_back(i);
-    } else {
-        devs.assign(devices, devices + n_devices);
-    }
-    const size_t W = devs.size();
-    if (W == 1) return run_year_bins_host_on(devs[0], p, rng_in, stream_id, path_begin, n_paths, working_months, out, yb);
-    const uint64_t per = (n_paths + W - 1) / W;
-    struct Shard {
-        int rc = MCR_OK;
-        char err[512] = "";
-        bool ran = false;
-        mcr_outputs o;
-        mcr_year_bins y;
-        std::vector<std::vector<uint64_t>> mem;
-    };
-    std::vector<Shard> shards(W);
-    std::vector<std::thread> threads;
-    for (size_t w = 0; w < W; ++w) {
-        const uint64_t begin = std::min<uint64_t>(w * per, n_paths);
-        const uint64_t count = std::min<uint64_t>(per, n_paths - begin);
-        if (count == 0) continue;
-        Shard& S = shards[w];
-        S.ran = true;
-        S.o = *out; S.y = *yb;
-        for (const YearBinsBlock& b : year_bins_blocks(sz, out, yb, &S.o, &S.y)) {   // zeroed blocks of the shard's own
-            S.mem.emplace_back(*b.src && b.n ? b.n : 0, 0);
-            *b.dst = S.mem.back().empty() ? nullptr : S.mem.back().data();
-        }
-        threads.emplace_back([&, w, begin, count]() {
-            Shard& T = shards[w];
+    const YearBinsOut caller = {*out, *yb};
+    return run_sharded(devices, n_devices, n_paths, caller,
+        [&](YearBinsOut* shard) { return year_bins_blocks(sz, caller, shard); },
+        [&](int device, uint64_t begin, uint64_t count, const YearBinsOut& shard) {
             mcr_rng r = *rng_in;
             if (r.path_seeds) r.path_seeds += begin;
-            T.rc = run_year_bins_host_on(devs[w], p, &r, stream_id, path_begin + begin, count, working_months, &T.o, &T.y);
-            if (T.rc != MCR_OK) std::snprintf(T.err, sizeof(T.err), "device %d: %s", devs[w], mcr_last_error());
+            return run_year_bins_host_on(device, p, &r, stream_id, path_begin + begin, count, working_months, &shard.o, &shard.y);
         });
-    }
-    for (std::thread& t : threads) t.join();
-    for (const Shard& S : shards)
-        if (S.rc != MCR_OK) { set_error("%s", S.err); return S.rc; }
-    for (Shard& S : shards) {
-        if (!S.ran) continue;
-        mcr_outputs o2; mcr_year_bins y2;
-        const std::vector<YearBinsBlock> blocks = year_bins_blocks(sz, out, yb, &o2, &y2);
-        for (size_t i = 0; i < blocks.size(); ++i)
-            for (size_t k = 0; k < S.mem[i].size(); ++k) (*blocks[i].src)[k] += S.mem[i][k];
-    }
-    return MCR_OK;
 }
 
 int mcr_run_year_bins_host_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
@@ -5251,8 +5217,7 @@ int mcr_run_rule_year_bins_rng(const mcr_params* p, const mcr_rng* rng, uint32_t
     return launch_rule_year_bins(p, rng, stream_id, path_begin, n_paths, working_months, rule, out, yb, rule_yb, (hipStream_t)hip_stream);
 }
 
-// HOST pointers, one device: the pooled context's block holds every table, both rule tables and the three edge arrays; the tables
-// come back through a staging copy, so the caller's stay untouched unless the whole call succeeds (run_year_bins_host_on's plan).
+// HOST pointers, one device: run_year_bins_host_on's plan with both rule tables and the multiplier edges added
 int mcr_run_rule_year_bins_host_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
                                     int32_t working_months, const mcr_spending_rule* rule, const mcr_outputs* out, const mcr_year_bins* yb,
                                     const mcr_rule_year_bins* rule_yb, int device) {
@@ -5264,58 +5229,24 @@ int mcr_run_rule_year_bins_host_rng(const mcr_params* p, const mcr_rng* rng, uin
     if ((rc = query_sizes(p, working_months, &sz)) != MCR_OK) return rc;
     if ((rc = validate_params(p)) != MCR_OK) return rc;
     if ((rc = plan_rule_year_bins(p, rng, path_begin, n_paths, working_months, rule, out, yb, rule_yb, &dp, &lds)) != MCR_OK) return rc;
-    if ((yb->trajectory_bins || yb->real_trajectory_bins || yb->final_success_bins) && (rc = check_edges_host("edges", yb->edges, yb->n_bins)) != MCR_OK) return rc;
-    if (yb->wr_bins && (rc = check_edges_host("wr_edges", yb->wr_edges, yb->n_wr_bins)) != MCR_OK) return rc;
-    if (rule_yb->multiplier_bins && (rc = check_edges_host("m_edges", rule_yb->m_edges, rule_yb->n_m_bins)) != MCR_OK) return rc;
+    if ((rc = check_year_bins_edges_host(yb, "m_edges", rule_yb->multiplier_bins ? rule_yb->m_edges : nullptr, rule_yb->n_m_bins)) != MCR_OK) return rc;
     MCR_ENTER_DEVICE(device);
     if (n_paths == 0) return MCR_OK;
-    mcr_outputs d = {};
-    mcr_year_bins dy = {};
+    const YearBinsOut host = {*out, *yb};
+    YearBinsOut d = {};
     mcr_rule_year_bins dr = {};
-    dy.n_bins = yb->n_bins; dy.n_wr_bins = yb->n_wr_bins; dr.n_m_bins = rule_yb->n_m_bins;
-    struct Buf { void** dev; void* host; size_t bytes, offset; bool download; };
-    std::vector<Buf> bufs;
-    size_t total = 0;
-    auto plan = [&](void** dev, const void* host, size_t bytes, bool down) {
-        if (!host || bytes == 0) return;
-        bufs.push_back({dev, const_cast<void*>(host), bytes, total, down});
-        total += (bytes + 255) & ~(size_t)255;
-    };
+    dr.n_m_bins = rule_yb->n_m_bins;
+    HostCall call;
+    plan_year_bins(call, sz, host, &d);
     const size_t ry = (size_t)sz.retirement_years;
-    for (const YearBinsBlock& b : year_bins_blocks(sz, out, yb, &d, &dy)) plan((void**)b.dst, *b.src, b.n * sizeof(uint64_t), true);
-    plan((void**)&dr.year_counts, rule_yb->year_counts, ry * MCR_RULE_N_COUNTS * sizeof(uint64_t), true);
+    call.plan(&dr.year_counts, rule_yb->year_counts, ry * MCR_RULE_N_COUNTS * sizeof(uint64_t), true, true);
     if (rule_yb->multiplier_bins) {
-        plan((void**)&dr.multiplier_bins, rule_yb->multiplier_bins, ry * ((size_t)rule_yb->n_m_bins + 2) * sizeof(uint64_t), true);
-        plan((void**)&dr.m_edges, rule_yb->m_edges, (size_t)(rule_yb->n_m_bins + 1) * sizeof(double), false);
+        call.plan(&dr.multiplier_bins, rule_yb->multiplier_bins, ry * ((size_t)rule_yb->n_m_bins + 2) * sizeof(uint64_t), true, true);
+        call.plan(&dr.m_edges, rule_yb->m_edges, (size_t)(rule_yb->n_m_bins + 1) * sizeof(double), true, false);
     }
-    if (yb->trajectory_bins || yb->real_trajectory_bins || yb->final_success_bins) plan((void**)&dy.edges, yb->edges, (size_t)(yb->n_bins + 1) * sizeof(double), false);
-    if (yb->wr_bins) plan((void**)&dy.wr_edges, yb->wr_edges, (size_t)(yb->n_wr_bins + 1) * sizeof(double), false);
-
-    HostCtxLease lease(device);
-    HostCtx* ctx = lease.ctx;
-    if (!ctx) return MCR_ERR_HIP;
-    hipError_t e = host_ctx_reserve(ctx, total);
-    if (e != hipSuccess) return hip_fail(e, "device allocation (rule yearly bins)");
-    for (Buf& b : bufs) {   // accumulated blocks start from the caller's current values
-        *b.dev = (char*)ctx->block + b.offset;
-        if (e == hipSuccess) e = hipMemcpyAsync(*b.dev, b.host, b.bytes, hipMemcpyHostToDevice, ctx->stream);
-    }
-    if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->stream); return hip_fail(e, "upload"); }
-    rc = launch_rule_year_bins(p, rng, stream_id, path_begin, n_paths, working_months, rule, &d, &dy, &dr, ctx->stream);
-    std::vector<std::vector<unsigned char>> staged(bufs.size());
-    if (rc == MCR_OK)
-        for (size_t i = 0; i < bufs.size(); ++i) {
-            if (!bufs[i].download || e != hipSuccess) continue;
-            staged[i].resize(bufs[i].bytes);
-            e = hipMemcpyAsync(staged[i].data(), *bufs[i].dev, bufs[i].bytes, hipMemcpyDeviceToHost, ctx->stream);
-        }
-    const hipError_t es = hipStreamSynchronize(ctx->stream);
-    if (rc != MCR_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "download");
-    if (es != hipSuccess) return hip_fail(es, "path_kernel execution (rule yearly bins)");
-    for (size_t i = 0; i < bufs.size(); ++i)
-        if (!staged[i].empty()) std::memcpy(bufs[i].host, staged[i].data(), bufs[i].bytes);
-    return MCR_OK;
+    if ((rc = call.begin(device, "device allocation (rule yearly bins)")) != MCR_OK) return rc;
+    rc = launch_rule_year_bins(p, rng, stream_id, path_begin, n_paths, working_months, rule, &d.o, &d.y, &dr, call.stream());
+    return call.finish(rc, true, "path_kernel execution (rule yearly bins)");
 }
 
 int mcr_validate_params(const mcr_params* p) { return validate_params(p); }
@@ -5424,27 +5355,8 @@ int mcr_sample_columns(uint32_t seed, uint64_t n, int32_t k, int64_t* out) {
 }
 
 int mcr_release_cached(int device) {
-    std::vector<HostCtx*> ctxs;
-    std::vector<StreamFork*> forks;
-    {
-        std::lock_guard<std::mutex> lock(g_pool_mu);
-        for (size_t i = g_idle_ctx.size(); i-- > 0;)
-            if (device < 0 || g_idle_ctx[i]->device == device) { ctxs.push_back(g_idle_ctx[i]); g_idle_ctx.erase(g_idle_ctx.begin() + (long)i); }
-        for (size_t i = g_idle_fork.size(); i-- > 0;)
-            if (device < 0 || g_idle_fork[i]->device == device) { forks.push_back(g_idle_fork[i]); g_idle_fork.erase(g_idle_fork.begin() + (long)i); }
-    }
-    int rc = MCR_OK;
-    for (HostCtx* c : ctxs) {
-        DeviceScope scope(c->device);
-        if (scope.rc != MCR_OK) rc = scope.rc;   // (device gone: drop the bookkeeping anyway)
-        host_ctx_destroy(c);
-    }
-    for (StreamFork* f : forks) {
-        DeviceScope scope(f->device);
-        if (scope.rc != MCR_OK) rc = scope.rc;
-        stream_fork_destroy(f);
-    }
-    return rc;
+    const int rc_ctx = g_host_ctx.release_cached(device), rc_fork = g_stream_fork.release_cached(device);
+    return rc_fork != MCR_OK ? rc_fork : rc_ctx;
 }
 
 int mcr_draw_shocks_host(uint64_t seed, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,

@@ -61,7 +61,7 @@ private:
 // Context of one host-buffer call (mcr_run_batch_host*): a private NON-BLOCKING stream — concurrent callers (server
 // executor threads) do not serialise on the null stream or on a device-wide synchronise — and one scratch block that the
 // call carves its device buffers from.  Contexts live in a PROCESS-WIDE pool keyed by device (mutex-guarded): a call
-// leases one for its duration (HostCtxLease) and hands it back, so short-lived caller threads and the per-call shard
+// leases one for its duration (mcr_hip.hip: IdlePool, HostCall) and hands it back, so short-lived caller threads and the per-call shard
 // workers of the multi-device entry reuse the same few contexts instead of leaving one behind each (round 2 kept them in
 // thread-local storage: one stream + up to 256 MiB of HBM leaked per thread that ever called).  At most
 // kHostCtxIdlePerDevice idle contexts per device stay cached, each with a block of at most kHostCtxKeepBytes (larger
@@ -75,38 +75,18 @@ struct HostCtx {
     void* block;
     size_t capacity;
 };
-HostCtx* host_ctx_acquire(int device);               // nullptr + error set on failure; the caller owns it until release
-void host_ctx_release(HostCtx* c);                   // back to the pool (block above the keep limit freed; surplus contexts destroyed)
-hipError_t host_ctx_reserve(HostCtx* c, size_t bytes);  // grows the block (contents are not preserved)
-class HostCtxLease {
-public:
-    explicit HostCtxLease(int device) : ctx(host_ctx_acquire(device)) {}
-    HostCtxLease(const HostCtxLease&) = delete;
-    HostCtxLease& operator=(const HostCtxLease&) = delete;
-    ~HostCtxLease() { if (ctx) host_ctx_release(ctx); }
-    HostCtx* ctx;
-};
 
 // Fork/join streams for calls that spread independent pieces of work over several HIP streams and join them back onto
 // the caller's stream: kForkStreams non-blocking side streams with one "done" event each, and a fork event.  Leased from
-// a process-wide pool keyed by device (mcr_hip.hip) for the duration of the call's ENQUEUE; at most 2 idle sets per
-// device stay cached (mcr_release_cached frees them).
+// a process-wide pool keyed by device (mcr_hip.hip) for the duration of the call's ENQUEUE; at most
+// kStreamForkIdlePerDevice idle sets per device stay cached (mcr_release_cached frees them).
 constexpr int kForkStreams = 8;
+constexpr int kStreamForkIdlePerDevice = 2;
 struct StreamFork {
     int device;
     hipStream_t side[kForkStreams];
     hipEvent_t done[kForkStreams];
     hipEvent_t fork;
-};
-StreamFork* stream_fork_acquire(int device);         // nullptr on failure (out of resources)
-void stream_fork_release(StreamFork* f);
-class StreamForkLease {
-public:
-    explicit StreamForkLease(int device) : f(stream_fork_acquire(device)) {}
-    StreamForkLease(const StreamForkLease&) = delete;
-    StreamForkLease& operator=(const StreamForkLease&) = delete;
-    ~StreamForkLease() { if (f) stream_fork_release(f); }
-    StreamFork* f;
 };
 
 // Joint outcomes (mcr_aggregate.hip): option k's success mask is a row of joint_mask_words(n_paths) 64-bit words, bit b of

@@ -180,6 +180,15 @@ def test_accumulation_device_list_and_batch_views(jorge_full):
     for k in BLOCKS:
         assert np.array_equal(one[k], half[k]), k
         assert np.array_equal(one[k], three[k]), k
+    # a device list on top of nonzero caller tables: the shards' sums are added to what is there
+    onto = E.run_year_bins_host(p, 99, 1, 0, n // 2, wm, edges=e, wr_edges=we)
+    E.run_year_bins_host(p, 99, 1, n // 2, n - n // 2, wm, edges=e, wr_edges=we, into=onto, devices=[0, 0, 0])
+    # fewer paths than shards: ceil(2 / 3) = 1 path each, the last shard is empty
+    two = E.run_year_bins_host(p, 99, 1, 0, 2, wm, edges=e, wr_edges=we)
+    sparse = E.run_year_bins_host(p, 99, 1, 0, 2, wm, edges=e, wr_edges=we, devices=[0, 0, 0])
+    for k in BLOCKS:
+        assert np.array_equal(one[k], onto[k]), k
+        assert np.array_equal(two[k], sparse[k]), k
     b = E.YearBinsBatch(p, wm, e, we)
     b.launch(99, 1, 0, n // 2)
     b.launch(99, 1, n // 2, n - n // 2)
