@@ -26,6 +26,8 @@ switch to the final seed stream, run the final batch, print the response documen
     python examples/run_scenario.py scenarios/config.json --working-months 240 --spending-rule 1.2,0.8,0.1,0.1,0.5,1.5 --streamed
     python examples/run_scenario.py scenarios/config.json --spending-rule 1.2,0.8,0.1,0.1,0.5,1.5 --earliest-retirement
     python examples/run_scenario.py scenarios/config.json --spending-rule 1.2,0.8,0.1,0.1,0.5,1.5 --frontier 180,240,300
+    python examples/run_scenario.py scenarios/config.json --working-months 240 --allocations 0,0.2,0.4,0.6,0.8,1 [--paired] [--outcomes]
+    python examples/run_scenario.py scenarios/config.json --working-months 240 --best-allocation [--allocation-resolution 0.01]
 
 `--rng numpy` uses the reference's own NumPy stream (same seed -> the reference's numbers); `--rng philox`
 (default) the engine's counter-based stream.  `--history FILE.csv` asks every question of a recorded market instead: months
@@ -72,7 +74,13 @@ every row also gets `lasts_until_age` (the age the money lasts to with 90 / 95 /
 `--spending-rule R --earliest-retirement` answers "how much sooner can I retire if I accept the guardrail": both month searches
 on the same search stream, printed as `{fixed_spending: {working_months, ...}, with_spending_rule: {working_months, ...},
 months_sooner}` (`--full` adds both search curves).  `--frontier M1,M2,... --spending-rule R` adds the rule's frontier beside the
-fixed one: every row gains `with_spending_rule: {max_initial_monthly_expenses, probability, levels_evaluated}`."""
+fixed one: every row gains `with_spending_rule: {max_initial_monthly_expenses, probability, levels_evaluated}`.
+`--allocations a,b,c` (with `--working-months`) prints the allocation table: the success probability of each split between the
+two assets (`allocation_inv1_pct`) over the same random numbers, `{options: [{the three amounts, allocation_inv1_pct,
+probability}], best}`; `--paired` and `--outcomes` add what they add to the claiming table.  `--best-allocation` searches the
+split with the highest success probability on the search stream (a grid 0, 0.1, ..., 1 refined around its best point down to
+`--allocation-resolution`) and prints `{best_allocation_inv1_pct, probability, tied, probes, curve}`; `tied` lists the splits of
+the first grid that a paired test on the same paths cannot tell from the answer."""
 
 from __future__ import annotations
 
@@ -153,7 +161,33 @@ def main() -> int:
     ap.add_argument("--compare-rules", default=None, metavar="RULE;RULE;...",
                     help="spending rules compared over the same paths at --working-months: each UPPER,LOWER,CUT,RAISE,FLOOR,CEILING "
                          "or 'none' (fixed spending), separated by ';'; composes with --paired and --outcomes")
+    ap.add_argument("--allocations", default=None, metavar="A,B,...",
+                    help="comma-separated allocation_inv1_pct values compared over the same paths at --working-months; composes with "
+                         "--paired and --outcomes")
+    ap.add_argument("--best-allocation", action="store_true",
+                    help="search the allocation_inv1_pct with the highest success probability at --working-months")
+    ap.add_argument("--allocation-resolution", type=float, default=0.01, help="--best-allocation: the grid the answer lies on")
     args = ap.parse_args()
+    if args.allocations is not None or args.best_allocation:
+        if args.working_months is None:
+            ap.error("--allocations / --best-allocation need --working-months")
+        if args.allocations is not None and args.best_allocation:
+            ap.error("--allocations and --best-allocation are separate questions")
+        if (args.min_initial_balance or args.min_contribution or args.max_expenses or args.income_options is not None or args.min_income is not None
+                or args.compare_rules is not None or args.spending_rule is not None or args.stress or args.breakeven or args.cohorts
+                or args.frontier or args.grid_months or args.grid_expenses or args.earliest_retirement or args.streamed or args.compact):
+            ap.error("--allocations / --best-allocation and the other questions are separate")
+        if args.allocations is not None:
+            try:
+                if not _csv(args.allocations, float):
+                    ap.error("--allocations needs at least one value")
+            except ValueError:
+                ap.error("--allocations takes comma-separated numbers")
+        units = 1.0 / args.allocation_resolution if args.allocation_resolution > 0 else 0.0
+        if args.best_allocation and (units < 1.0 or abs(round(units) - units) > 1e-9 * units):
+            ap.error("--allocation-resolution: 1 / resolution must be a whole number (0.1, 0.05, 0.01, ...)")
+    elif args.allocation_resolution != 0.01:
+        ap.error("--allocation-resolution goes with --best-allocation")
     if args.compare_rules is not None:
         from monte_carlo_retirement_amd.spending_rules import SpendingRule
 
@@ -196,10 +230,10 @@ def main() -> int:
         ap.error("--income-options / --min-income and the other searches are separate questions")
     if args.income_options is not None and args.min_income is not None:
         ap.error("--income-options and --min-income are separate questions")
-    if args.paired and args.income_options is None and not args.stress and args.compare_rules is None:
-        ap.error("--paired goes with --income-options, --stress or --compare-rules")
-    if args.outcomes and args.income_options is None and not args.stress and args.compare_rules is None:
-        ap.error("--outcomes goes with --income-options, --stress or --compare-rules")
+    if args.paired and args.income_options is None and not args.stress and args.compare_rules is None and args.allocations is None:
+        ap.error("--paired goes with --income-options, --stress, --compare-rules or --allocations")
+    if args.outcomes and args.income_options is None and not args.stress and args.compare_rules is None and args.allocations is None:
+        ap.error("--outcomes goes with --income-options, --stress, --compare-rules or --allocations")
     if (args.claim_ages or args.claim_amounts) and args.income_options is None:
         ap.error("--claim-ages / --claim-amounts go with --income-options")
     if args.claim_age is not None and args.min_income is None:
@@ -264,6 +298,10 @@ def main() -> int:
 
     if args.cohorts:
         return cohorts(args, config, world, rank0)
+    if args.allocations is not None:
+        return allocation_table(args, config, world, rank0)
+    if args.best_allocation:
+        return best_allocation(args, config, world, rank0)
     if args.compare_rules is not None:
         return compare_rules(args, config, world, rank0)
     if args.earliest_retirement:
@@ -589,6 +627,53 @@ def income_table(args, config: Config, world: int, rank0: bool) -> int:
     table = sim.compare_claiming_options(wm, _stream_arg(args.income_options), options, **_table_flags(args))
     out = {"scenario": config.Nickname, "rng": args.rng, "working_months": wm, "num_simulations": int(config.num_simulations_main),
            "target_probability": config.target_probability, **table, "seconds": round(time.perf_counter() - t0, 3)}
+    if rank0:
+        print(json.dumps(_with_market(args, out)))
+    if world > 1:
+        import torch.distributed as dist
+
+        dist.barrier()
+        dist.destroy_process_group()
+    return 0
+
+
+def allocation_table(args, config: Config, world: int, rank0: bool) -> int:
+    t0 = time.perf_counter()
+    sim = _simulator(args, config)
+    sim.use_final_seeds()
+    try:
+        table = sim.compare_allocations(int(args.working_months), _csv(args.allocations, float), **_table_flags(args))
+    except ValueError as e:
+        print(json.dumps({"error": str(e)}))
+        return 2
+    out = {"scenario": config.Nickname, "rng": args.rng, "working_months": int(args.working_months),
+           "num_simulations": int(config.num_simulations_main), **table, "seconds": round(time.perf_counter() - t0, 3)}
+    if rank0:
+        print(json.dumps(_with_market(args, out)))
+    if world > 1:
+        import torch.distributed as dist
+
+        dist.barrier()
+        dist.destroy_process_group()
+    return 0
+
+
+def best_allocation(args, config: Config, world: int, rank0: bool) -> int:
+    t0 = time.perf_counter()
+    sim = _simulator(args, config)
+    events = []
+    try:
+        allocation, prob, curve, tied = sim.find_best_allocation(int(args.working_months), resolution=args.allocation_resolution,
+                                                                 verbose=False, progress_callback=events.append)
+    except ValueError as e:
+        print(json.dumps({"error": str(e)}))
+        return 2
+    out = {
+        "scenario": config.Nickname, "rng": args.rng, "working_months": int(args.working_months),
+        "own_allocation_inv1_pct": float(config.allocation_inv1_pct), "best_allocation_inv1_pct": allocation, "probability": prob,
+        "tied": tied, "probes": len({e["iteration"] for e in events}), "curve": curve,
+        "seconds": round(time.perf_counter() - t0, 3),
+    }
     if rank0:
         print(json.dumps(_with_market(args, out)))
     if world > 1:

@@ -816,6 +816,48 @@ int mcr_probe_rule_grid_rng(const mcr_params* p, const mcr_rng* rng, uint32_t st
                             uint64_t* counts, uint64_t* year_counts, int device, void* hip_stream);
 int mcr_probe_rule_grid_last_fanout_launches(void);
 
+/*
+ * Allocation options: SEVERAL splits between the two assets (and versions of the scenario probe's three fields) at one
+ * working-month count over the same path range -- how should the money be divided?  The probe of the allocation comparison
+ * table and of the best-split search.  counts[k] equals, bit for bit, the counters of a count-only mcr_run_batch_rng call with
+ * the same arguments and initial_balance, monthly_contribution, monthly_expenses and allocation_inv1_pct of *p replaced by
+ * options[k]'s; the second asset's weight is 1.0 - allocation_inv1_pct, the operation the plain launch performs on its block.
+ *   counts: DEVICE uint64 [n_options][MCR_N_COUNTERS] = {successes, paths}, ZEROED by the call.
+ * options is a HOST array of n_options >= 0 records (0 does nothing; duplicates allowed).  Everything is validated on the host
+ * before a device is looked for and before anything is enqueued: *p by mcr_validate_params' rules, the three amounts finite and
+ * >= 0 (config.py:56, 57, 59), the allocation finite and in [0, 1] (config.py:70); on any error every output stays untouched
+ * and the message names options[k].<field>.
+ * One option: the plain count-only launch.  Otherwise, on the Philox stream with at most MCR_INLINE_STREAMS kept income streams,
+ * every lock slot in LDS, the tolerance month, n_paths <= 2^31 and at least MCR_ALLOCATION_FANOUT_MIN_WAVES path-wavefronts
+ * (environment, default 0, read per call): ALLOCATION FAN-OUT launches, the scenario fan-out's workgroup in which each of up to
+ * MCR_MAX_EXPENSE_FANOUT consumer waves also carries its own pair of weights; the 32-byte records are the stream-ordered device
+ * table as they come, released behind the launches.  Any other shape (the NumPy and history streams, longer stream lists, the
+ * exact month, a refused allocation of the table): one count-only launch per option on internal side streams, joined back onto
+ * `hip_stream`.  Whichever route runs, the integers are the same.  Asynchronous like mcr_probe_scenarios_rng.
+ * mcr_probe_allocations_joint_rng and mcr_probe_allocations_outcomes_rng add the arguments of mcr_probe_scenarios_joint_rng and
+ * mcr_probe_scenarios_outcomes_rng with their contracts (JOINT OUTCOMES and PER-OPTION OUTCOMES above; the cap
+ * MCR_MAX_JOINT_OPTIONS and a null `joint`, and rows->path_stride < n_paths, are checked first): the mask rows are the success
+ * columns, and the rows are where(success, final_balance, NaN) and years_to_ruin, of summary launches of the options, bit for
+ * bit on both routes; elements of a row at or beyond n_paths are never written.
+ * mcr_probe_allocations_last_fanout_launches reports, for the calling thread's last call, how many allocation fan-out launches
+ * it enqueued: ceil(n_options / options per launch) on the fan-out route, 0 on the others and after an error.
+ */
+typedef struct mcr_allocation_option {
+    double initial_balance, monthly_contribution, monthly_expenses;   /* as mcr_scenario */
+    double allocation_inv1_pct;                                       /* config.py:70, in [0, 1] */
+} mcr_allocation_option;                                              /* 32 bytes */
+int mcr_probe_allocations_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                              uint64_t n_paths, int32_t working_months, const mcr_allocation_option* options, int32_t n_options,
+                              uint64_t* counts, int device, void* hip_stream);
+int mcr_probe_allocations_joint_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                    uint64_t n_paths, int32_t working_months, const mcr_allocation_option* options, int32_t n_options,
+                                    uint64_t* counts, uint64_t* masks, uint64_t* joint, uint64_t* extremes,
+                                    int device, void* hip_stream);
+int mcr_probe_allocations_outcomes_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                       uint64_t n_paths, int32_t working_months, const mcr_allocation_option* options, int32_t n_options,
+                                       uint64_t* counts, const mcr_option_outcomes* rows, int device, void* hip_stream);
+int mcr_probe_allocations_last_fanout_launches(void);
+
 /* _draw_shock_path (simulation.py:452-466) for n_paths paths: host out [n_paths][n_months][3]. */
 int mcr_draw_shocks_host(uint64_t seed, uint32_t stream_id, uint64_t path_begin,
                          uint64_t n_paths, int32_t n_months, double rho, double* out,

@@ -317,6 +317,18 @@ class McrRuleOption(C.Structure):
     ]
 
 
+class McrAllocationOption(C.Structure):
+    """One record of an allocation probe (include/mcr.h: mcr_allocation_option): the three scenario levers and the share of
+    the first asset."""
+
+    _fields_ = [
+        ("initial_balance", C.c_double),
+        ("monthly_contribution", C.c_double),
+        ("monthly_expenses", C.c_double),
+        ("allocation_inv1_pct", C.c_double),
+    ]
+
+
 class McrSizes(C.Structure):
     _fields_ = [
         ("total_months", C.c_int32),
@@ -431,6 +443,10 @@ ABI_SYMBOLS = (
     "mcr_probe_rules_last_fanout_launches",
     "mcr_probe_rule_grid_rng",
     "mcr_probe_rule_grid_last_fanout_launches",
+    "mcr_probe_allocations_rng",
+    "mcr_probe_allocations_joint_rng",
+    "mcr_probe_allocations_outcomes_rng",
+    "mcr_probe_allocations_last_fanout_launches",
     "mcr_release_cached",
     "mcr_sample_columns",
     "mcr_eval_helper_host",
@@ -622,6 +638,17 @@ def _declare(lib: C.CDLL) -> None:
         lib.mcr_probe_rules_outcomes_rng.argtypes = head + [P(McrOptionOutcomes), C.c_int, C.c_void_p]
         lib.mcr_probe_rules_last_fanout_launches.restype = C.c_int
         lib.mcr_probe_rules_last_fanout_launches.argtypes = []
+    if hasattr(lib, "mcr_probe_allocations_rng"):   # (likewise)
+        head = [P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32, P(McrAllocationOption), C.c_int32,
+                C.c_void_p]       # ..., options, n_options, counts
+        lib.mcr_probe_allocations_rng.restype = C.c_int
+        lib.mcr_probe_allocations_rng.argtypes = head + [C.c_int, C.c_void_p]
+        lib.mcr_probe_allocations_joint_rng.restype = C.c_int
+        lib.mcr_probe_allocations_joint_rng.argtypes = head + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]   # masks, joint, extremes
+        lib.mcr_probe_allocations_outcomes_rng.restype = C.c_int
+        lib.mcr_probe_allocations_outcomes_rng.argtypes = head + [P(McrOptionOutcomes), C.c_int, C.c_void_p]
+        lib.mcr_probe_allocations_last_fanout_launches.restype = C.c_int
+        lib.mcr_probe_allocations_last_fanout_launches.argtypes = []
     if hasattr(lib, "mcr_probe_rule_grid_rng"):   # (likewise)
         lib.mcr_probe_rule_grid_rng.restype = C.c_int
         lib.mcr_probe_rule_grid_rng.argtypes = [

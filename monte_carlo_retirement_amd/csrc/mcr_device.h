@@ -94,6 +94,15 @@ __device__ __forceinline__ LaneParams lane_params(const DevParams& P) {
     asm volatile("" : "+v"(L.alloc1), "+v"(L.alloc2), "+v"(L.real_rate1), "+v"(L.real_rate2));
     return L;
 }
+// PHASE 12 (the allocation fan-out, mcr_hip.hip): what the tolerance month's helpers read of the parameter block (rebalance_tol:
+// the weight; annual_gain_taxes: the annual-gains bill), with the CONSUMER WAVE's own weight in place of the block's.  Wave-uniform
+// like the block: scalar registers.  alloc2 = 1.0 - alloc1 is derive_params' operation on the block, made by the wave.
+struct WaveAllocParams {
+    double alloc1, alloc2;
+    double annual_rate1, annual_rate2;
+    int32_t any_annual_tax;
+};
+struct NoWaveAlloc { static constexpr double alloc1 = 0.0; };   // (named, never read: `kAlcFan ? WA.alloc1 : P.alloc1` folds to the block's)
 // The tolerance form of the month (below) selects the seller's rate and the seller's weight x rate; it needs neither weight
 // on its own (the drift of asset 2 is minus the drift of asset 1).  In the SAME struct, so that the helpers keep one
 // signature: alloc1 / alloc2 then hold the products.
@@ -107,6 +116,23 @@ __device__ __forceinline__ LaneParams lane_params_tol(const DevParams& P) {
     } else {
         asm volatile("" : "+v"(L.alloc1), "+v"(L.alloc2), "+v"(L.real_rate1), "+v"(L.real_rate2));
     }
+    return L;
+}
+// ... of a PHASE 12 consumer wave: the same two products, of the wave's weights (the single fp64 multiplies the plain launch
+// applies to its block; the fan-outs run the tolerance month and none of the month forms)
+__device__ __forceinline__ LaneParams lane_params_tol(const WaveAllocParams& W, const DevParams& P) {
+    LaneParams L{W.alloc1 * P.real_rate1, W.alloc2 * P.real_rate2, P.real_rate1, P.real_rate2};
+    asm volatile("" : "+v"(L.alloc1), "+v"(L.alloc2), "+v"(L.real_rate1), "+v"(L.real_rate2));
+    return L;
+}
+// the path kernel's resident copy: the block's in the launch's month form, or the consumer wave's
+template <bool TOL, bool EQR>
+__device__ __forceinline__ LaneParams month_lane_params(const NoWaveAlloc&, const DevParams& P) { return TOL ? lane_params_tol<EQR>(P) : lane_params(P); }
+template <bool TOL, bool EQR>
+__device__ __forceinline__ LaneParams month_lane_params(const WaveAllocParams& W, const DevParams& P) {
+    if (TOL) return lane_params_tol(W, P);
+    LaneParams L{W.alloc1, W.alloc2, P.real_rate1, P.real_rate2};    // (lane_params': the exact month's diagnostic build)
+    asm volatile("" : "+v"(L.alloc1), "+v"(L.alloc2), "+v"(L.real_rate1), "+v"(L.real_rate2));
     return L;
 }
 
@@ -890,8 +916,9 @@ __device__ __forceinline__ void seller_select3(bool sell1, double a1, double a2,
     auto f64 = [](uint32_t hi, uint32_t lo) { return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo)); };
     a = f64(ahi, alo); b = f64(bhi, blo); c = f64(chi, clo);
 }
-template <bool TAXED, bool MM = true, bool UNIFORM = false, bool EQR = false, bool MASKSEL = false>
-__device__ __forceinline__ void rebalance_tol(const DevParams& P, const LaneParams& L, double& b1, double& c1, double& b2, double& c2) {
+// PT: the parameter block, or the allocation fan-out's WaveAllocParams (the consumer wave's own weight; L then holds its products).
+template <bool TAXED, bool MM = true, bool UNIFORM = false, bool EQR = false, bool MASKSEL = false, typename PT = DevParams>
+__device__ __forceinline__ void rebalance_tol(const PT& P, const LaneParams& L, double& b1, double& c1, double& b2, double& c2) {
     const double total = b1 + b2;                                  // :288
     const double drift1 = __builtin_fma(-total, P.alloc1, b1);     // :293-294
     if (UNIFORM && wave_any(fmin(total, fabs(drift1)) <= kEps)) {  // (one compare: a ballot of an OR comes out as a 0/1 VGPR compared again)
@@ -932,8 +959,8 @@ __device__ __forceinline__ void rebalance_tol(const DevParams& P, const LanePara
 }
 
 // TOL: the closing rebalance in its tolerance form (then L = lane_params_tol(P)); EQR: rebalance_tol's.
-template <bool STRICT = true, bool TAXED = true, bool ANNUAL = true, bool T1 = TAXED, bool T2 = TAXED, bool MM = true, bool TOL = false, bool EQR = false>
-__device__ __forceinline__ bool annual_gain_taxes(const DevParams& P, const LaneParams& L, double& b1, double& c1,
+template <bool STRICT = true, bool TAXED = true, bool ANNUAL = true, bool T1 = TAXED, bool T2 = TAXED, bool MM = true, bool TOL = false, bool EQR = false, typename PT = DevParams>
+__device__ __forceinline__ bool annual_gain_taxes(const PT& P, const LaneParams& L, double& b1, double& c1,
                                                   double& b2, double& c2, double gain1, double gain2) {
     bool tax_failed = false;
     if (ANNUAL && P.any_annual_tax) {  // wave-uniform: with no annual-tax asset the bill is 0 (:380-390)
@@ -958,6 +985,27 @@ __device__ __forceinline__ bool annual_gain_taxes(const DevParams& P, const Lane
     else if (TOL) rebalance_tol<TAXED, MM, false, EQR>(P, L, b1, c1, b2, c2);
     else rebalance_path<TAXED, MM>(L, b1, c1, b2, c2);
     return tax_failed;
+}
+
+// The path kernel's calls of the two helpers above that read the weights: on the block in every kernel but PHASE 12's
+// consumers, which hand over their wave's view in its place (L = month_lane_params of the same object).
+template <bool TAXED, bool MM = true, bool UNIFORM = false, bool EQR = false, bool MASKSEL = false>
+__device__ __forceinline__ void month_rebalance_tol(const NoWaveAlloc&, const DevParams& P, const LaneParams& L, double& b1, double& c1, double& b2, double& c2) {
+    rebalance_tol<TAXED, MM, UNIFORM, EQR, MASKSEL>(P, L, b1, c1, b2, c2);
+}
+template <bool TAXED, bool MM = true, bool UNIFORM = false, bool EQR = false, bool MASKSEL = false>
+__device__ __forceinline__ void month_rebalance_tol(const WaveAllocParams& W, const DevParams&, const LaneParams& L, double& b1, double& c1, double& b2, double& c2) {
+    rebalance_tol<TAXED, MM, UNIFORM, EQR, MASKSEL>(W, L, b1, c1, b2, c2);
+}
+template <bool STRICT = true, bool TAXED = true, bool ANNUAL = true, bool T1 = TAXED, bool T2 = TAXED, bool MM = true, bool TOL = false, bool EQR = false>
+__device__ __forceinline__ bool month_annual_gain_taxes(const NoWaveAlloc&, const DevParams& P, const LaneParams& L, double& b1, double& c1,
+                                                        double& b2, double& c2, double gain1, double gain2) {
+    return annual_gain_taxes<STRICT, TAXED, ANNUAL, T1, T2, MM, TOL, EQR>(P, L, b1, c1, b2, c2, gain1, gain2);
+}
+template <bool STRICT = true, bool TAXED = true, bool ANNUAL = true, bool T1 = TAXED, bool T2 = TAXED, bool MM = true, bool TOL = false, bool EQR = false>
+__device__ __forceinline__ bool month_annual_gain_taxes(const WaveAllocParams& W, const DevParams&, const LaneParams& L, double& b1, double& c1,
+                                                        double& b2, double& c2, double gain1, double gain2) {
+    return annual_gain_taxes<STRICT, TAXED, ANNUAL, T1, T2, MM, TOL, EQR>(W, L, b1, c1, b2, c2, gain1, gain2);
 }
 
 // Market step shared by both phases (:522-538 and :695-714), given the month's gross factors.

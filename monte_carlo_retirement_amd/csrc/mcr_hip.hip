@@ -169,6 +169,7 @@ static_assert(offsetof(RuleGridCell, cell) == 0 && sizeof(RuleGridCell) == sizeo
 // PHASE 8 (scenario probe, mcr_probe_scenarios_rng): consumer wave j of a launch runs record j of the launch's device table of
 // mcr_scenario (initial_balance, monthly_contribution, monthly_expenses), through `cand_params` like the grid's records
 static_assert(sizeof(mcr_scenario) == 3 * sizeof(double), "mcr_scenario is three packed doubles");
+static_assert(sizeof(mcr_allocation_option) == 4 * sizeof(double), "mcr_allocation_option is four packed doubles: the allocation fan-out's table as it comes");
 // PHASE 9 (assumption probe, mcr_probe_assumptions_rng): consumer wave j of a launch runs record j of the launch's device table,
 // through `cand_params` as well: PHASE 8's three values and the market as growth_factors_row reads it (mcr_device.h), derived on
 // the host by the function derive_params uses (derive_market)
@@ -548,7 +549,7 @@ __device__ __forceinline__ void income_put(DevStream& S, const IncomeRegs& R) {
 }
 
 template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault, int GF = 0, int MF = 0, int SF = 0, bool OUT = false, bool LIST = false, int NPROD = 1, bool RULE = false>
-__global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE == 8 || PHASE == 9 || PHASE == 10 || PHASE == 11) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : NPROD == 2 ? 3 * 64 : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
+__global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE == 8 || PHASE == 9 || PHASE == 10 || PHASE == 11 || PHASE == 12) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : NPROD == 2 ? 3 * 64 : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
                                                          const DevParams* __restrict__ cand_params) {
     // MODE 3 (mcr_run_year_bins_rng): YEARLY BINS.  The arithmetic of MODE 2, but wherever that variant stores a yearly sample
     // (nominal balance, real balance, withdrawal rate) the lane bins it instead: cell 0 = below edges[0], cells 1 .. n = the
@@ -571,10 +572,11 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     static_assert(PHASE != 9 || SPLIT, "the assumption fan-out is a producer / consumer form");
     static_assert(PHASE != 10 || SPLIT, "the income fan-out is a producer / consumer form");
     static_assert(PHASE != 11 || (SPLIT && RULE), "the rule fan-out is a producer / consumer form of the rule kernels");
+    static_assert(PHASE != 12 || SPLIT, "the allocation fan-out is a producer / consumer form");
     // OUT (mcr_probe_*_outcomes_rng): the PHASE 8 / 9 / 10 consumer waves also store their paths' outcome rows (KernelIO::fan_final,
     // fan_ruin) in the epilogue.  A template flag, not a null check: the month of failure is one more VGPR through the month loop,
     // which the plain and the joint probes' kernels do not pay.
-    static_assert(!OUT || PHASE == 8 || PHASE == 9 || PHASE == 10 || PHASE == 11, "outcome rows exist for the scenario, assumption, income and rule fan-outs");
+    static_assert(!OUT || PHASE == 8 || PHASE == 9 || PHASE == 10 || PHASE == 11 || PHASE == 12, "outcome rows exist for the scenario, assumption, income, rule and allocation fan-outs");
     // LIST (the re-run of a screened launch; launch_screened): the lanes' local path indices come from a device list that
     // screen_kernel filled earlier on the stream, io.path_list[i] for i < *io.path_list_count; lanes beyond the count behave
     // like tail lanes, and a workgroup whose first index is at or beyond the count returns at once (the host sizes the grid
@@ -617,7 +619,8 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     constexpr bool kStreamRegs = SPLIT && !kAsmFan && !(LIST && (SF & kStreamsInRegs) != 0);   // the first two income streams stay in SGPRs for the whole launch (S0, S1 below; the split re-run's stream form keeps StreamRegs instead)
     constexpr bool kIncFan = PHASE == 10;                 // income fan-out: the scenario fan-out with one income stream per wave as well
     constexpr bool kRuleFan = PHASE == 11;                // rule fan-out: the scenario fan-out with a spending rule per wave as well
-    constexpr bool kScnFan = PHASE == 8 || kAsmFan || kIncFan || kRuleFan;   // scenario fan-out: balance, contribution and spending per wave, the whole path
+    constexpr bool kAlcFan = PHASE == 12;                 // allocation fan-out: the scenario fan-out with the split between the assets per wave as well
+    constexpr bool kScnFan = PHASE == 8 || kAsmFan || kIncFan || kRuleFan || kAlcFan;   // scenario fan-out: balance, contribution and spending per wave, the whole path
     constexpr bool kFan = kExpFan || kConFan || kScnFan;  // fan-out workgroup: one 64-path block, L consumer waves (levels), one producer wave
     constexpr bool kGrid = PHASE == 6;                    // ... of grid row blockIdx.y (GridCell)
     constexpr bool kRuleGrid = kGrid && RULE;             // ... under a spending rule (RuleGridCell: the row's record carries the rule)
@@ -639,6 +642,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     [[maybe_unused]] std::conditional_t<OUT, RuinMonth, NoRuinMonth> RM;         // (likewise: the outcome probes' month of failure)
     [[maybe_unused]] std::conditional_t<RULE, RuleState, NoRuleState> RS;        // (likewise: the spending rule's multiplier)
     [[maybe_unused]] std::conditional_t<kWaveRule, FanRule, NoFanRule> FR;       // (likewise: PHASE 11 and PHASE 6 with RULE, the consumer wave's own rule)
+    [[maybe_unused]] std::conditional_t<kAlcFan, WaveAllocParams, NoWaveAlloc> WA;   // (likewise: PHASE 12, the consumer wave's own weights, mcr_device.h)
     static_assert(!kSliced || (RNG == 0 && !INJ && !SPLIT && !XS), "time-sliced blocks exist for the plain Philox variants");
     static_assert(PHASE != 4 || MODE == 0, "the search probes count only");
     // TAXED: which assets carry an effective realized-gains rate (bit 0: inv1, bit 1: inv2; DevParams::tax_mask)
@@ -907,7 +911,16 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         g2 = ginf * monthly_gross(P.aprem, P.bprem, zp, tab);  // :532
     };
 
-    const LaneParams L = TOL ? lane_params_tol<EQR>(P) : lane_params(P);
+    // PHASE 12: the wave's weights from its record (wave-uniform: scalar loads from the launch's table, like PHASE 11's rule), and
+    // what else the month's helpers read of the block beside them.  alloc2 = 1.0 - alloc1: derive_params' operation.  The producer,
+    // wave fan_n, stands one past the group's records: it reads record 0's, and uses none of it.
+    if constexpr (kAlcFan) {
+        const mcr_allocation_option* const rec = reinterpret_cast<const mcr_allocation_option*>(cand_params) + (producer ? 0 : fan_j);
+        WA.alloc1 = rec->allocation_inv1_pct;
+        WA.alloc2 = 1.0 - WA.alloc1;
+        WA.annual_rate1 = P.annual_rate1; WA.annual_rate2 = P.annual_rate2; WA.any_annual_tax = P.any_annual_tax;
+    }
+    const LaneParams L = month_lane_params<TOL, EQR>(WA, P);
 
     // ---- initial state (:490-510) ----
     double b1 = P.initial_balance * P.alloc1;  // :499
@@ -1034,6 +1047,14 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         FR.upper = rec->upper; FR.lower = rec->lower; FR.keep = rec->keep; FR.grow = rec->grow; FR.floor = rec->floor; FR.ceiling = rec->ceiling;
         unsigned long long* const yc = rec->year_counts;
         FR.year_counts = yc ? yc + (size_t)fan_j * (size_t)P.retirement_years * MCR_RULE_N_COUNTS : nullptr;
+    } else if constexpr (kAlcFan) {              // PHASE 12: the record's three values likewise, split by the wave's own weight (WA, above)
+        const mcr_allocation_option* const rec = reinterpret_cast<const mcr_allocation_option*>(cand_params) + fan_j;
+        const double rec_balance = rec->initial_balance;
+        b1 = rec_balance * WA.alloc1;            // :499
+        b2 = rec_balance - b1;                   // :500
+        c1 = b1; c2 = b2;                        // :501-502
+        contrib = rec->monthly_contribution;     // :504
+        scn_expenses = rec->monthly_expenses;
     } else if constexpr (kScnFan) {
         const mcr_scenario* const scn = reinterpret_cast<const mcr_scenario*>(cand_params) + fan_j;
         const double scn_balance = scn->initial_balance;
@@ -1115,14 +1136,14 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         double g1, ginf, g2;
         growth(m - 1, g1, ginf, g2);                                   // :519-532
         market_step<ANNUAL, TOL>(g1, ginf, g2, b1, b2, gacc1, gacc2, infl); // :534-538
-        const double k1 = contrib * P.alloc1;                          // :540-542
+        const double k1 = contrib * (kAlcFan ? WA.alloc1 : P.alloc1);   // :540-542
         const double k2 = contrib - k1;                                // :543
         b1 += k1; c1 += k1; b2 += k2; c2 += k2;                        // :544-547
-        if (TOL) rebalance_tol<TANY, MM, kFastMonth, EQR>(P, L, b1, c1, b2, c2);  // :549-553
+        if (TOL) month_rebalance_tol<TANY, MM, kFastMonth, EQR>(WA, P, L, b1, c1, b2, c2);  // :549-553
         else rebalance_path<TANY, MM>(L, b1, c1, b2, c2);
         if (year_closes(SC, m)) {                                      // :557
             if constexpr (kScalarCounters) SC.moy = 0;
-            pre_fail |= annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, TOL, EQR>(P, L, b1, c1, b2, c2, gacc1, gacc2);  // :558-573
+            pre_fail |= month_annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, TOL, EQR>(WA, P, L, b1, c1, b2, c2, gacc1, gacc2);  // :558-573
             put_sample(t_idx++, b1 + b2, infl);                        // :574-576
             gacc1 = 0.0; gacc2 = 0.0;                                  // :578-579
         }
@@ -1264,13 +1285,13 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
             double g1, ginf, g2;
             factors(half, g1, ginf, g2);
             market_step<ANNUAL, TOL>(g1, ginf, g2, b1, b2, gacc1, gacc2, infl); // :534-538
-            const double k1 = contrib * P.alloc1;                          // :540-542
+            const double k1 = contrib * (kAlcFan ? WA.alloc1 : P.alloc1);   // :540-542
             const double k2 = contrib - k1;                                // :543
             b1 += k1; c1 += k1; b2 += k2; c2 += k2;                        // :544-547
-            rebalance_tol<TANY, MM, kFastMonth, EQR, kSel>(P, L, b1, c1, b2, c2);  // :549-553
+            month_rebalance_tol<TANY, MM, kFastMonth, EQR, kSel>(WA, P, L, b1, c1, b2, c2);  // :549-553
             if (++moy == kMPY) {                                           // :557
                 moy = 0;
-                pre_fail |= annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, TOL, EQR>(P, L, b1, c1, b2, c2, gacc1, gacc2);  // :558-573
+                pre_fail |= month_annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, TOL, EQR>(WA, P, L, b1, c1, b2, c2, gacc1, gacc2);  // :558-573
                 gacc1 = 0.0; gacc2 = 0.0;                                  // :578-579
             }
             ++row;
@@ -1308,7 +1329,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
                             double cap1, cap2, gw1, nw1, gw2, nw2;
                             net_liquidation_values2<T1, T2, MM>(b1, c1, L.real_rate1, b2, c2, L.real_rate2, cap1, cap2);
                             const double xcap = cap1 + cap2, xtarget = fmin(need, xcap);
-                            const double prop1 = xcap > kEps ? fdiv<false>(cap1, xcap) : P.alloc1;
+                            const double prop1 = xcap > kEps ? fdiv<false>(cap1, xcap) : (kAlcFan ? WA.alloc1 : P.alloc1);
                             withdraw2<T1, T2, MM>(b1, c1, xtarget * prop1, L.real_rate1, gw1, nw1,
                                                   b2, c2, xtarget * (1.0 - prop1), L.real_rate2, gw2, nw2);
                             fail = need > kEps && (xtarget < need - kEps || nw1 + nw2 < need - kEps);
@@ -1317,9 +1338,9 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
                     }
                     if (fail) yfail = true;
                     sell_fraction_tol<MM, FAST>(phi, b1, c1, b2, c2);                 // :757-776
-                    rebalance_tol<TANY, MM, kFastMonth, EQR, kSel>(P, L, b1, c1, b2, c2);   // :792-796
+                    month_rebalance_tol<TANY, MM, kFastMonth, EQR, kSel>(WA, P, L, b1, c1, b2, c2);   // :792-796
                     if (!yfail && mi == ye_mi) {                                      // :798-804
-                        const bool tf = annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, true, EQR>(P, L, b1, c1, b2, c2, gacc1, gacc2);  // :805-818
+                        const bool tf = month_annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, true, EQR>(WA, P, L, b1, c1, b2, c2, gacc1, gacc2);  // :805-818
                         gacc1 = 0.0; gacc2 = 0.0;                                     // :819-820
                         yfail = yfail || tf;                                          // :821-822
                     }
@@ -1463,7 +1484,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
                             double cap1, cap2, gw1, nw1, gw2, nw2;
                             net_liquidation_values2<T1, T2, MM>(b1, c1, L.real_rate1, b2, c2, L.real_rate2, cap1, cap2);
                             const double xcap = cap1 + cap2, xtarget = fmin(need, xcap);
-                            const double prop1 = xcap > kEps ? fdiv<false>(cap1, xcap) : P.alloc1;
+                            const double prop1 = xcap > kEps ? fdiv<false>(cap1, xcap) : (kAlcFan ? WA.alloc1 : P.alloc1);
                             withdraw2<T1, T2, MM>(b1, c1, xtarget * prop1, L.real_rate1, gw1, nw1,
                                                   b2, c2, xtarget * (1.0 - prop1), L.real_rate2, gw2, nw2);
                             fail = need > kEps && (xtarget < need - kEps || nw1 + nw2 < need - kEps);
@@ -1477,18 +1498,18 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
                         treal = __builtin_fma(gross * infl_ret, recip_nr<false>(fmax(price, kEps)), treal);  // :778-782
                     }
                     sell_fraction_tol<MM, FAST>(phi, b1, c1, b2, c2);                 // :757-776
-                    rebalance_tol<TANY, MM, kFastMonth, EQR>(P, L, b1, c1, b2, c2);   // :792-796
+                    month_rebalance_tol<TANY, MM, kFastMonth, EQR>(WA, P, L, b1, c1, b2, c2);   // :792-796
                     // (the counters' form in a branch of its own: named in the other kernels' month, SC would be one more capture of
                     // this lambda, which is enough to reorder their code)
                     if constexpr (kScalarCounters) {
                         if (!yfail && mi == SC.ye_mi) {                               // :798-804
-                            const bool tf = annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, true, EQR>(P, L, b1, c1, b2, c2, gacc1, gacc2);  // :805-818
+                            const bool tf = month_annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, true, EQR>(WA, P, L, b1, c1, b2, c2, gacc1, gacc2);  // :805-818
                             gacc1 = 0.0; gacc2 = 0.0;                                 // :819-820
                             yfail = yfail || tf;                                      // :821-822
                         }
                     } else
                     if (!yfail && (wm + rmi + 1) % kMPY == 0) {                       // :798-804
-                        const bool tf = annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, true, EQR>(P, L, b1, c1, b2, c2, gacc1, gacc2);  // :805-818
+                        const bool tf = month_annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, true, EQR>(WA, P, L, b1, c1, b2, c2, gacc1, gacc2);  // :805-818
                         gacc1 = 0.0; gacc2 = 0.0;                                     // :819-820
                         yfail = yfail || tf;                                          // :821-822
                     }
@@ -1517,7 +1538,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
                     const double target = fmin(need, cap);                            // :739-742 (need, cap >= 0: the max(0, .) is a no-op)
                     if (need > kEps && target < need - kEps) yfail = true;            // :743-748 (FAIL-3)
                     double prop1 = fdiv<false>(cap1, cap);                            // :750-754
-                    if (!(cap > kEps)) { MCR_MASKED_MOVE; prop1 = P.alloc1; }        // (exec-masked move, not a select)
+                    if (!(cap > kEps)) { MCR_MASKED_MOVE; prop1 = kAlcFan ? WA.alloc1 : P.alloc1; }   // (exec-masked move, not a select)
                     const double prop2 = 1.0 - prop1;                                 // :755
                     double gw1, nw1, gw2, nw2;
                     withdraw2<T1, T2, MM>(b1, c1, target * prop1, L.real_rate1, gw1, nw1,  // :757-765
@@ -1528,7 +1549,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
                     if (need > kEps && nw1 + nw2 < need - kEps) yfail = true;         // :784-790 (FAIL-4)
                     rebalance_path<TANY, MM>(L, b1, c1, b2, c2);                      // :792-796
                     if (!yfail && (wm + rmi + 1) % kMPY == 0) {                       // :798-804
-                        const bool tf = annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM>(P, L, b1, c1, b2, c2, gacc1, gacc2);  // :805-818
+                        const bool tf = month_annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM>(WA, P, L, b1, c1, b2, c2, gacc1, gacc2);  // :805-818
                         gacc1 = 0.0; gacc2 = 0.0;                                     // :819-820
                         yfail = yfail || tf;                                          // :821-822
                     }
@@ -1612,7 +1633,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     // ---- terminal partial tax period (:873-898) ----
     if (P.total_months % kMPY != 0) {  // wave-uniform
         if (succeeded) {
-            const bool tf = annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, TOL, EQR>(P, L, b1, c1, b2, c2, gacc1, gacc2);  // :880-893
+            const bool tf = month_annual_gain_taxes<false, TANY, ANNUAL, T1, T2, MM, TOL, EQR>(WA, P, L, b1, c1, b2, c2, gacc1, gacc2);  // :880-893
             if (tf) {                                                            // :894-896
                 succeeded = false; ruin_bin = ry + 1;
                 if (kSumLds) sum_col[2 * kBlock] = (double)ry; else ytr_bits = f64_bits((double)ry);
@@ -3986,6 +4007,32 @@ static int probe_rules_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t 
     });
 }
 
+// Several (initial_balance, monthly_contribution, monthly_expenses, allocation_inv1_pct) options over the same paths, Philox
+// stream (PHASE 12).  The records are the table as they come.  Of everything derive_params gives the block only alloc1 / alloc2
+// depend on the fourth field, and the consumers read their record's in every place the path reads them (the initial split, the
+// contribution split, the rebalances, the dust sub-case, lane_params_tol's two products); the tax variant, needs_generic_variant,
+// the lock-slot plan, the kept streams and the barrier counts read neither.  Returns MCR_ERR_UNSUPPORTED, having enqueued
+// nothing, for shapes this form does not cover.
+static thread_local int g_last_allocation_fanout_launches = 0;   // (mcr_probe_allocations_last_fanout_launches)
+static int probe_allocations_fanout(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                                    int32_t wm, const mcr_allocation_option* options, int32_t n_options, uint64_t* counts, hipStream_t stream,
+                                    uint64_t* masks = nullptr /* joint probes: KernelIO::fan_masks of the whole option list */,
+                                    const mcr_option_outcomes* rows = nullptr /* outcome probes: the rows of the whole option list */) {
+    DevParams d;
+    int lmax = 0;
+    if (int rc = plan_level_fanout(p, rng, n_paths, wm, n_options, fanout_min_waves("MCR_ALLOCATION_FANOUT_MIN_WAVES"), &d, &lmax)) return rc;
+    return launch_record_fanout(d, lmax, rng, stream_id, path_begin, n_paths, options, n_options, counts, stream, masks, rows,
+                                &g_last_allocation_fanout_launches, "allocation fan-out probe",
+                                [&](const KernelIO& fio, int, dim3 grid, dim3 block, size_t lds, const DevParams* table) {
+        for_tax_variant(d, [&](auto T, auto A) {
+            for_bool(rows != nullptr, [&](auto O) {
+                hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 12, true, false, kExactMonthDefault, 0, 0, 0, decltype(O)::value>),
+                                   grid, block, lds, stream, d, fio, table);
+            });
+        });
+    });
+}
+
 // The three amounts every probe record carries (validate_params' rule for each), of record `k` of the list `list` names.
 template <typename Record>
 static bool amounts_valid(const char* list, int32_t k, const Record& r) {
@@ -4814,6 +4861,84 @@ int mcr_probe_income_outcomes_rng(const mcr_params* p, const mcr_rng* rng, uint3
 }
 
 int mcr_probe_income_last_fanout_launches(void) { return g_last_income_fanout_launches; }
+
+// What the allocation probes check on the host, before a device is looked for: the block, the month, the stream, every option
+static int check_allocation_probe(const mcr_params* p, const mcr_rng* rng, int32_t working_months, const mcr_allocation_option* options,
+                                  int32_t n_options, const uint64_t* counts) {
+    if (n_options < 0) { set_error("n_options %d must be >= 0", n_options); return MCR_ERR_INVALID_ARG; }
+    if (n_options == 0) return MCR_OK;
+    if (!options || !counts) { set_error("null options / counts"); return MCR_ERR_INVALID_ARG; }
+    int rc = validate_months(p, &working_months, 1);
+    if (rc != MCR_OK) return rc;
+    if ((rc = check_rng(rng)) != MCR_OK) return rc;
+    for (int32_t k = 0; k < n_options; ++k) {
+        if (!amounts_valid("options", k, options[k])) return MCR_ERR_INVALID_ARG;
+        const double a = options[k].allocation_inv1_pct;
+        if (!(std::isfinite(a) && a >= 0.0 && a <= 1.0)) {
+            set_error("options[%d].allocation_inv1_pct = %.17g: must be finite and in [0, 1] (config.py:70)", k, a);
+            return MCR_ERR_INVALID_ARG;
+        }
+    }
+    return MCR_OK;
+}
+// mcr_probe_allocations_rng (jo == nullptr, rows == nullptr), mcr_probe_allocations_joint_rng and
+// mcr_probe_allocations_outcomes_rng, on the entered device, their arguments checked
+static int probe_allocations(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                             int32_t working_months, const mcr_allocation_option* options, int32_t n_options, uint64_t* counts,
+                             const JointOut* jo, const mcr_option_outcomes* rows, int device, hipStream_t main) {
+    int rc = zero_counters(counts, (size_t)n_options, main);
+    if (rc != MCR_OK) return rc;
+    mcr_params q = *p;
+    auto launch_option = [&](int k, hipStream_t s, uint8_t* success, double* final_balance, double* years_to_ruin) {
+        const mcr_allocation_option& r = options[k];
+        q.initial_balance = r.initial_balance; q.monthly_contribution = r.monthly_contribution; q.monthly_expenses = r.monthly_expenses;
+        q.allocation_inv1_pct = r.allocation_inv1_pct;
+        const mcr_outputs o = counters_and_columns(counts + (size_t)k * MCR_N_COUNTERS, success, final_balance, years_to_ruin);
+        return launch_paths(&q, rng, stream_id, path_begin, n_paths, working_months, nullptr, &o, s);
+    };
+    auto fanout = [&](uint64_t* masks, const mcr_option_outcomes* fan_rows) {
+        return probe_allocations_fanout(p, rng, stream_id, path_begin, n_paths, working_months, options, n_options, counts, main, masks, fan_rows);
+    };
+    return run_probe_routes(device, main, n_options, n_paths, jo, rows, fanout, launch_option);
+}
+
+int mcr_probe_allocations_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                              uint64_t n_paths, int32_t working_months, const mcr_allocation_option* options, int32_t n_options,
+                              uint64_t* counts, int device, void* hip_stream) {
+    g_last_allocation_fanout_launches = 0;
+    if (int rc = check_allocation_probe(p, rng, working_months, options, n_options, counts)) return rc;
+    if (n_options == 0) return MCR_OK;
+    MCR_ENTER_DEVICE(device);
+    return probe_allocations(p, rng, stream_id, path_begin, n_paths, working_months, options, n_options, counts, nullptr, nullptr, device,
+                             (hipStream_t)hip_stream);
+}
+
+int mcr_probe_allocations_joint_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                    uint64_t n_paths, int32_t working_months, const mcr_allocation_option* options, int32_t n_options,
+                                    uint64_t* counts, uint64_t* masks, uint64_t* joint, uint64_t* extremes, int device, void* hip_stream) {
+    g_last_allocation_fanout_launches = 0;
+    if (int rc = check_joint_args(n_options, joint)) return rc;
+    if (int rc = check_allocation_probe(p, rng, working_months, options, n_options, counts)) return rc;
+    if (n_options == 0) return MCR_OK;
+    MCR_ENTER_DEVICE(device);
+    const JointOut jo{masks, joint, extremes};
+    return probe_allocations(p, rng, stream_id, path_begin, n_paths, working_months, options, n_options, counts, &jo, nullptr, device,
+                             (hipStream_t)hip_stream);
+}
+
+int mcr_probe_allocations_outcomes_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                       uint64_t n_paths, int32_t working_months, const mcr_allocation_option* options, int32_t n_options,
+                                       uint64_t* counts, const mcr_option_outcomes* rows, int device, void* hip_stream) {
+    g_last_allocation_fanout_launches = 0;
+    if (int rc = check_outcome_args(&rows, n_paths)) return rc;
+    if (int rc = check_allocation_probe(p, rng, working_months, options, n_options, counts)) return rc;
+    if (n_options == 0) return MCR_OK;
+    MCR_ENTER_DEVICE(device);
+    return probe_allocations(p, rng, stream_id, path_begin, n_paths, working_months, options, n_options, counts, nullptr, rows, device,
+                             (hipStream_t)hip_stream);
+}
+
+int mcr_probe_allocations_last_fanout_launches(void) { return g_last_allocation_fanout_launches; }
 
 // Everything launch_rule refuses of a launch's shape, for a probe that has no route behind the rule kernels: `who` heads the
 // message ("spending rule" gives launch_rule's own words).  `d` = derive_params' block of the probed month; `summary`: the

@@ -845,6 +845,43 @@ def probe_assumptions_outcomes(params: McrParams, seed, stream_id: int, path_beg
                           device, outcomes=(final_balance, years_to_ruin, path_stride))
 
 
+def _allocation_option_records(options):
+    records = [tuple(float(x) for x in o) for o in options]
+    if any(len(r) != 4 for r in records):
+        raise ValueError("every option is (initial_balance, monthly_contribution, monthly_expenses, allocation_inv1_pct)")
+    return (N.McrAllocationOption * max(1, len(records)))(*[N.McrAllocationOption(*r) for r in records]), len(records)
+
+
+def probe_allocations(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
+                      options, device: int = 0):
+    """Success counters of several splits between the two assets (and versions of the three scenario fields) at one
+    working-month count over the same path range (``mcr_probe_allocations_rng``).  ``options`` is a sequence of
+    ``(initial_balance, monthly_contribution, monthly_expenses, allocation_inv1_pct)`` 4-tuples; option k counts exactly what
+    a count-only launch with those four fields of `params` replaced counts.  Up to ``MCR_MAX_EXPENSE_FANOUT`` options share
+    each path's random numbers.  Returns a device int64 tensor ``[len(options), 2]`` = ``{successes, paths}``; asynchronous
+    (reading it synchronises)."""
+    arr, n = _allocation_option_records(options)
+    return _probe_records("mcr_probe_allocations_rng", params, seed, stream_id, path_begin, n_paths, working_months, (arr,), n, device)
+
+
+def probe_allocations_joint(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
+                            options, device: int = 0, masks=True):
+    """`probe_allocations` plus the joint outcomes of its options (``mcr_probe_allocations_joint_rng``); returns ``(counts,
+    joint, extremes, masks)`` as `probe_scenarios_joint`."""
+    arr, n = _allocation_option_records(options)
+    return _probe_records("mcr_probe_allocations_joint_rng", params, seed, stream_id, path_begin, n_paths, working_months, (arr,), n,
+                          device, joint=True, masks=masks)
+
+
+def probe_allocations_outcomes(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
+                               options, device: int = 0, final_balance=True, years_to_ruin=True, path_stride: Optional[int] = None):
+    """`probe_allocations` plus the per-path outcomes of its options (``mcr_probe_allocations_outcomes_rng``); returns
+    ``(counts, final_rows, ruin_rows)`` as `probe_scenarios_outcomes`."""
+    arr, n = _allocation_option_records(options)
+    return _probe_records("mcr_probe_allocations_outcomes_rng", params, seed, stream_id, path_begin, n_paths, working_months, (arr,), n,
+                          device, outcomes=(final_balance, years_to_ruin, path_stride))
+
+
 def _rule_option_records(options):
     """`options`: ``(initial_balance, monthly_contribution, monthly_expenses, rule)`` 4-tuples, `rule` a
     `spending_rules.SpendingRule`, a ready ``McrSpendingRule`` or None (the neutral rule: fixed spending)."""

@@ -880,7 +880,7 @@ class RetirementMonteCarloSimulator:
         return np.array([self._count_percent(counts[i, N.MCR_CTR_SUCCESS], n) for i in range(len(levels))], dtype=np.float64)
 
     def _option_records(self, family: str, options: Sequence[dict], stream=None) -> Tuple[List[tuple], tuple]:
-        """What is specific to an option family -- ``"scenarios"``, ``"income"``, ``"assumptions"`` or ``"rules"``, which is also
+        """What is specific to an option family -- ``"scenarios"``, ``"income"``, ``"assumptions"``, ``"allocations"`` or ``"rules"``, which is also
         the middle of its three `engine` entry points ``probe_<family>``, ``probe_<family>_joint`` and
         ``probe_<family>_outcomes``: ``(records, lead)``, the validated records of ``options`` and the arguments the engine
         calls take in front of them.  Raises ``ValueError`` as the family's record builder does."""
@@ -898,6 +898,10 @@ class RetirementMonteCarloSimulator:
             from .stress import assumption_records
 
             return assumption_records(p, options), ()
+        if family == "allocations":
+            from .allocation import allocation_records
+
+            return allocation_records(p, options), ()
         from .spending_rules import rule_options
 
         return rule_options(p, options), ()
@@ -1406,6 +1410,88 @@ class RetirementMonteCarloSimulator:
                     logger.info(f"  {e:.2f} per month: initial balance {balance:.2f} with prob {prob:.2f}% "
                                 f"({len(curve)} levels evaluated).")
         return results
+
+    # ---- allocation options and the best-split search ---------------------------------------------------
+    def success_probability_by_allocations(self, working_months: int, allocations: Sequence,
+                                           num_simulations: Optional[int] = None) -> np.ndarray:
+        """Success % of each split between the two assets at ``working_months``, over the active seed stream's batch of
+        ``num_simulations`` paths (default ``num_simulations_main``), from the allocation probe
+        (``mcr_probe_allocations_rng``).  An option is a number (``allocation_inv1_pct``) or a mapping with
+        ``allocation_inv1_pct`` and any subset of ``initial_balance``, ``monthly_contribution``, ``monthly_expenses`` (a
+        missing amount takes the config's value); a bad option raises ``ValueError`` naming it (before any device work).
+        Aligned with the input; each value equals, bit for bit,
+        ``_success_probability(run_monte_carlo_simulations(working_months, n)[0])`` of a simulator whose config differs in
+        those fields only.  Under a process group the options go through ``distributed.probe_candidates`` (as candidate
+        indices), so every rank returns the same array."""
+        return self._option_probabilities("allocations", working_months, allocations, num_simulations)
+
+    def joint_outcomes_by_allocations(self, working_months: int, allocations: Sequence, num_simulations: Optional[int] = None):
+        """The joint outcomes of the options of `success_probability_by_allocations` (same arguments) over their shared
+        paths, from the joint allocation probe (``mcr_probe_allocations_joint_rng``): a `paired.JointOutcomes` whose
+        ``.probabilities`` equal that method's array bit for bit.  At most ``MCR_MAX_JOINT_OPTIONS`` options."""
+        return self._option_probe("joint", "allocations", working_months, allocations, num_simulations)
+
+    def option_outcomes_by_allocations(self, working_months: int, allocations: Sequence, num_simulations: Optional[int] = None,
+                                       quantiles: Sequence[float] = (0.05, 0.25, 0.5, 0.75, 0.95)):
+        """The per-option outcomes of the options of `success_probability_by_allocations` (same arguments and validation)
+        over their shared paths, from the allocation outcomes probe (``mcr_probe_allocations_outcomes_rng``): an
+        `outcomes.OptionOutcomes` whose ``.probabilities`` equal that method's array bit for bit."""
+        return self._option_probe("outcomes", "allocations", working_months, allocations, num_simulations, quantiles=quantiles)
+
+    def compare_allocations(self, working_months: int, allocations: Optional[Sequence] = None,
+                            num_simulations: Optional[int] = None, paired: bool = False, outcomes: bool = False) -> dict:
+        """How to split the money: `success_probability_by_allocations` of ``allocations`` (default: the eleven splits 0, 0.1,
+        ..., 1) as ``{"options": [{the three amounts, "allocation_inv1_pct", "probability"}, ...], "best": index}``, ``best``
+        being the option with the highest probability (the first of equals).  ``paired=True`` adds ``"vs_best"`` to every row
+        and ``"tied_with_best"``, ``"all_succeed"`` and ``"none_succeed"`` to the document (`joint_outcomes_by_allocations`);
+        ``outcomes=True`` adds ``"lasts_until_age"``, ``"median_ruin_age"`` and ``"final_balance"`` to every row
+        (`option_outcomes_by_allocations`) -- both exactly as `compare_claiming_options` adds them, and they compose."""
+        from .allocation import ALLOCATION_OPTION_FIELDS, DEFAULT_ALLOCATIONS, allocation_records
+
+        options = list(DEFAULT_ALLOCATIONS if allocations is None else allocations)
+        records = allocation_records(self.params_model, options)
+        joint = self.joint_outcomes_by_allocations(working_months, options, num_simulations) if paired else None
+        per_option = self.option_outcomes_by_allocations(working_months, options, num_simulations) if outcomes else None
+        probs = (joint.probabilities if paired else per_option.probabilities if outcomes else
+                 self.success_probability_by_allocations(working_months, options, num_simulations))
+        rows = [dict(zip(ALLOCATION_OPTION_FIELDS, r), probability=float(pr)) for r, pr in zip(records, probs)]
+        return self._best_option_document({}, rows, joint, per_option)
+
+    def find_best_allocation(
+        self,
+        working_months: int,
+        resolution: float = 0.01,
+        num_simulations: Optional[int] = None,
+        verbose: bool = True,
+        progress_callback: Optional[Callable[[dict], None]] = None,
+    ) -> Tuple[float, float, List[Dict[str, float]], List[float]]:
+        """The ``allocation_inv1_pct`` (a multiple of ``resolution``) with the highest success probability when retiring after
+        ``working_months``: search stream, ``num_simulations`` paths a point (default ``num_simulations_search``),
+        ``MCR_MAX_EXPENSE_FANOUT`` splits per probe (`allocation.search_best_allocation`: the grid 0, 0.1, ..., 1, then finer
+        grids around the best point; ties go to the split nearest the config's own).  Returns ``(allocation, probability,
+        curve, tied)``; ``tied`` are the splits of the first grid (and the answer) that a paired test on the same paths
+        cannot tell from the answer.  A refined grid does not promise the global optimum of a noisy curve: read ``tied``.
+        Deterministic for a given seed, and the same on every rank."""
+        from .allocation import search_best_allocation
+
+        def plan(p, n_search, target):
+            wm = int(working_months)
+            n_sims = n_search if num_simulations is None else int(num_simulations)
+
+            def search():
+                return search_best_allocation(
+                    lambda splits: list(self.success_probability_by_allocations(wm, list(splits), n_sims)),
+                    float(p.allocation_inv1_pct), resolution=resolution, levels_per_call=N.MCR_MAX_EXPENSE_FANOUT,
+                    on_level=progress_callback,
+                    probe_joint=lambda splits: self.joint_outcomes_by_allocations(wm, list(splits), n_sims))
+
+            return (f"Searching the best allocation at {wm} working months for '{p.Nickname}' "
+                    f"({n_sims} sims per split, resolution {resolution}).", search,
+                    lambda allocation, prob, curve, tied: (True, (
+                        f"  Allocation search complete: {allocation:.4g} in asset 1 with prob {prob:.2f}% "
+                        f"({len(curve)} splits evaluated; {len(tied)} of the first grid indistinguishable from it).")))
+
+        return self._find_level(verbose, plan)
 
     # ---- income-stream options and the required-income search ------------------------------------------
     def success_probability_by_income_options(self, working_months: int, stream, options: Sequence[dict],
