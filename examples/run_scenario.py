@@ -28,6 +28,7 @@ switch to the final seed stream, run the final batch, print the response documen
     python examples/run_scenario.py scenarios/config.json --spending-rule 1.2,0.8,0.1,0.1,0.5,1.5 --frontier 180,240,300
     python examples/run_scenario.py scenarios/config.json --working-months 240 --allocations 0,0.2,0.4,0.6,0.8,1 [--paired] [--outcomes]
     python examples/run_scenario.py scenarios/config.json --working-months 240 --best-allocation [--allocation-resolution 0.01]
+    python examples/run_scenario.py scenarios/config.json --working-months 240 --glide-paths "0.9>0.4@0-20;0.6;0.3>0.6@20-35" [--paired] [--outcomes]
 
 `--rng numpy` uses the reference's own NumPy stream (same seed -> the reference's numbers); `--rng philox`
 (default) the engine's counter-based stream.  `--history FILE.csv` asks every question of a recorded market instead: months
@@ -80,7 +81,13 @@ two assets (`allocation_inv1_pct`) over the same random numbers, `{options: [{th
 probability}], best}`; `--paired` and `--outcomes` add what they add to the claiming table.  `--best-allocation` searches the
 split with the highest success probability on the search stream (a grid 0, 0.1, ..., 1 refined around its best point down to
 `--allocation-resolution`) and prints `{best_allocation_inv1_pct, probability, tied, probes, curve}`; `tied` lists the splits of
-the first grid that a paired test on the same paths cannot tell from the answer."""
+the first grid that a paired test on the same paths cannot tell from the answer.
+`--glide-paths "P;P;..."` (with `--working-months`) prints the glide table: the success probability of each GLIDE PATH, a split
+that changes with the calendar (a table of `allocation_inv1_pct` by whole years from today), over the same random numbers,
+`{options: [{name, the three amounts, weights, probability}], best}`.  A path is a constant (`0.6`) or `start>end@from-to`
+(`start` until year `from`, a straight line to `end` in year `to`, `end` after it).  With no value it compares a small
+catalogue built for `--working-months`: the config's own constant split, all and none of asset 1, two declining target-date
+shapes and one rising-equity shape.  `--paired` and `--outcomes` add what they add to the allocation table.  Engine stream only."""
 
 from __future__ import annotations
 
@@ -167,7 +174,25 @@ def main() -> int:
     ap.add_argument("--best-allocation", action="store_true",
                     help="search the allocation_inv1_pct with the highest success probability at --working-months")
     ap.add_argument("--allocation-resolution", type=float, default=0.01, help="--best-allocation: the grid the answer lies on")
+    ap.add_argument("--glide-paths", nargs="?", const="", default=None, metavar="P;P;...",
+                    help="glide paths compared over the same paths at --working-months: each a constant split or start>end@from-to "
+                         "(years from today), separated by ';'; with no value a default catalogue; composes with --paired and --outcomes")
     args = ap.parse_args()
+    if args.glide_paths is not None:
+        from monte_carlo_retirement_amd.allocation import GlidePath
+
+        if args.working_months is None:
+            ap.error("--glide-paths needs --working-months")
+        if (args.allocations is not None or args.best_allocation or args.min_initial_balance or args.min_contribution or args.max_expenses
+                or args.income_options is not None or args.min_income is not None or args.compare_rules is not None
+                or args.spending_rule is not None or args.stress or args.breakeven or args.cohorts or args.frontier or args.grid_months
+                or args.grid_expenses or args.earliest_retirement or args.streamed or args.compact):
+            ap.error("--glide-paths and the other questions are separate")
+        try:
+            args.glide_paths = [GlidePath.parse(t) for t in args.glide_paths.split(";")] if args.glide_paths.strip() else None
+        except ValueError as e:
+            ap.error(f"--glide-paths: {e}")
+        args.glide_table = True
     if args.allocations is not None or args.best_allocation:
         if args.working_months is None:
             ap.error("--allocations / --best-allocation need --working-months")
@@ -230,10 +255,11 @@ def main() -> int:
         ap.error("--income-options / --min-income and the other searches are separate questions")
     if args.income_options is not None and args.min_income is not None:
         ap.error("--income-options and --min-income are separate questions")
-    if args.paired and args.income_options is None and not args.stress and args.compare_rules is None and args.allocations is None:
-        ap.error("--paired goes with --income-options, --stress, --compare-rules or --allocations")
-    if args.outcomes and args.income_options is None and not args.stress and args.compare_rules is None and args.allocations is None:
-        ap.error("--outcomes goes with --income-options, --stress, --compare-rules or --allocations")
+    glide_table = getattr(args, "glide_table", False)
+    if args.paired and args.income_options is None and not args.stress and args.compare_rules is None and args.allocations is None and not glide_table:
+        ap.error("--paired goes with --income-options, --stress, --compare-rules, --allocations or --glide-paths")
+    if args.outcomes and args.income_options is None and not args.stress and args.compare_rules is None and args.allocations is None and not glide_table:
+        ap.error("--outcomes goes with --income-options, --stress, --compare-rules, --allocations or --glide-paths")
     if (args.claim_ages or args.claim_amounts) and args.income_options is None:
         ap.error("--claim-ages / --claim-amounts go with --income-options")
     if args.claim_age is not None and args.min_income is None:
@@ -298,6 +324,8 @@ def main() -> int:
 
     if args.cohorts:
         return cohorts(args, config, world, rank0)
+    if glide_table:
+        return glide_table_document(args, config, world, rank0)
     if args.allocations is not None:
         return allocation_table(args, config, world, rank0)
     if args.best_allocation:
@@ -644,6 +672,27 @@ def allocation_table(args, config: Config, world: int, rank0: bool) -> int:
     try:
         table = sim.compare_allocations(int(args.working_months), _csv(args.allocations, float), **_table_flags(args))
     except ValueError as e:
+        print(json.dumps({"error": str(e)}))
+        return 2
+    out = {"scenario": config.Nickname, "rng": args.rng, "working_months": int(args.working_months),
+           "num_simulations": int(config.num_simulations_main), **table, "seconds": round(time.perf_counter() - t0, 3)}
+    if rank0:
+        print(json.dumps(_with_market(args, out)))
+    if world > 1:
+        import torch.distributed as dist
+
+        dist.barrier()
+        dist.destroy_process_group()
+    return 0
+
+
+def glide_table_document(args, config: Config, world: int, rank0: bool) -> int:
+    t0 = time.perf_counter()
+    sim = _simulator(args, config)
+    sim.use_final_seeds()
+    try:
+        table = sim.compare_glide_paths(int(args.working_months), args.glide_paths, **_table_flags(args))
+    except (ValueError, RuntimeError) as e:      # (RuntimeError: a shape the glide probe does not support, in the library's words)
         print(json.dumps({"error": str(e)}))
         return 2
     out = {"scenario": config.Nickname, "rng": args.rng, "working_months": int(args.working_months),

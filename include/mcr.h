@@ -858,6 +858,65 @@ int mcr_probe_allocations_outcomes_rng(const mcr_params* p, const mcr_rng* rng, 
                                        uint64_t* counts, const mcr_option_outcomes* rows, int device, void* hip_stream);
 int mcr_probe_allocations_last_fanout_launches(void);
 
+/*
+ * GLIDE PATH: a split between the two assets that changes with the calendar.  A glide path is a table W[0 .. n - 1], n >= 1, of
+ * values of allocation_inv1_pct, every entry finite and in [0, 1], indexed by WHOLE YEARS FROM TODAY.  Let row t be the 0-based
+ * month from today: accumulation month m (simulation.py:513) is row m - 1, retirement month rmi (simulation.py:641) is row
+ * working_months + rmi.  The weight in force while row t is processed is
+ *     w(t)   = W[min(t div 12, n - 1)]
+ *     alloc2 = 1.0 - w(t)                      the operation the plain launch performs on its block, rounded once
+ * and it stands in every place the path reads a weight: the initial split reads W[0]; the contribution split, the monthly
+ * rebalance, the dust sub-case of the withdrawal proportion (capacity <= MCR_SMALL_EPSILON) and the annual-gains tax with its
+ * closing rebalance read w(t) of the row being processed (the annual tax closes row t when (t + 1) % 12 == 0); the terminal
+ * settlement uses the last row's weight, w(total_months - 1).  The weight changes only where t % 12 == 0, t > 0: the closes of
+ * calendar years from today, NOT the retirement-year boundaries unless working_months % 12 == 0 -- so a table means the same
+ * thing at every working-month count.  A table of length 1, or with all entries equal, is a constant split: every result is
+ * the allocation probe's, bit for bit.  Entries past the horizon are never read; a table shorter than the horizon holds its
+ * last entry.  Paths that have failed read no weight.
+ *
+ * Glide probes: SEVERAL glide paths (and versions of the scenario probe's three fields) at one working-month count over the
+ * same path range.  `weights` is a HOST array of n_weights doubles, the tables of all options one behind the other in any
+ * order (they may overlap or be shared); option k's table is weights[first_weight .. first_weight + n_weights).
+ *   counts: DEVICE uint64 [n_options][MCR_N_COUNTERS] = {successes, paths}, ZEROED by the call.
+ * options is a HOST array of n_options >= 0 records (0 does nothing; duplicates allowed).  Everything is validated on the host
+ * before a device is looked for and before anything is enqueued: *p by mcr_validate_params' rules, the three amounts finite and
+ * >= 0, options[k].n_weights >= 1, options[k].first_weight >= 0 and first_weight + n_weights within the table, and every weight
+ * an option names finite and in [0, 1]; on any error every output stays untouched and the message names options[k].<field> (a
+ * weight: options[k].weights[i]).
+ * There is NO plain launch under a glide path, so every option, a single one included, runs in GLIDE FAN-OUT launches: the
+ * allocation fan-out's workgroup in which each of up to MCR_MAX_EXPENSE_FANOUT consumer waves carries its own table and reloads
+ * its weight once a calendar year with one scalar load.  The records, with the weights behind them, are ONE stream-ordered
+ * device table, released behind the launches.  The shapes the fan-out does not cover have no per-option route here and return
+ * MCR_ERR_UNSUPPORTED, every output untouched, with a message that says which: the NumPy stream, the history stream, stream
+ * lists longer than MCR_INLINE_STREAMS or lock slots beyond LDS (the generic variant), the exact month, n_paths > 2^31, fewer
+ * than MCR_GLIDE_FANOUT_MIN_WAVES path-wavefronts (environment, default 0, read per call).  (A refused allocation of the device
+ * table also returns MCR_ERR_UNSUPPORTED, with the counters zeroed.  n_paths == 0 zeroes the counters, and the joint form's
+ * matrix and extremes, and launches nothing.)  Asynchronous like mcr_probe_scenarios_rng.
+ * mcr_probe_glide_paths_joint_rng and mcr_probe_glide_paths_outcomes_rng add the arguments of mcr_probe_scenarios_joint_rng and
+ * mcr_probe_scenarios_outcomes_rng with their contracts (the cap MCR_MAX_JOINT_OPTIONS and a null `joint`, and
+ * rows->path_stride < n_paths, are checked first); elements of a row at or beyond n_paths are never written.
+ * mcr_probe_glide_paths_last_fanout_launches reports, for the calling thread's last call, how many glide fan-out launches it
+ * enqueued: ceil(n_options / options per launch), 0 after an error.
+ * Not offered under a glide path: full-output (summary, trajectory) and yearly-bins launches.
+ */
+typedef struct mcr_glide_option {
+    double initial_balance, monthly_contribution, monthly_expenses;   /* as mcr_scenario */
+    int32_t first_weight;                                             /* index of W[0] in `weights` */
+    int32_t n_weights;                                                /* n >= 1 */
+} mcr_glide_option;                                                   /* 32 bytes */
+int mcr_probe_glide_paths_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                              uint64_t n_paths, int32_t working_months, const double* weights, int32_t n_weights,
+                              const mcr_glide_option* options, int32_t n_options, uint64_t* counts, int device, void* hip_stream);
+int mcr_probe_glide_paths_joint_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                    uint64_t n_paths, int32_t working_months, const double* weights, int32_t n_weights,
+                                    const mcr_glide_option* options, int32_t n_options, uint64_t* counts, uint64_t* masks,
+                                    uint64_t* joint, uint64_t* extremes, int device, void* hip_stream);
+int mcr_probe_glide_paths_outcomes_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                       uint64_t n_paths, int32_t working_months, const double* weights, int32_t n_weights,
+                                       const mcr_glide_option* options, int32_t n_options, uint64_t* counts,
+                                       const mcr_option_outcomes* rows, int device, void* hip_stream);
+int mcr_probe_glide_paths_last_fanout_launches(void);
+
 /* _draw_shock_path (simulation.py:452-466) for n_paths paths: host out [n_paths][n_months][3]. */
 int mcr_draw_shocks_host(uint64_t seed, uint32_t stream_id, uint64_t path_begin,
                          uint64_t n_paths, int32_t n_months, double rho, double* out,

@@ -329,6 +329,19 @@ class McrAllocationOption(C.Structure):
     ]
 
 
+class McrGlideOption(C.Structure):
+    """One record of a glide probe (include/mcr.h: mcr_glide_option): the three scenario levers and the option's table, entries
+    ``first_weight .. first_weight + n_weights`` of the call's flat array of weights."""
+
+    _fields_ = [
+        ("initial_balance", C.c_double),
+        ("monthly_contribution", C.c_double),
+        ("monthly_expenses", C.c_double),
+        ("first_weight", C.c_int32),
+        ("n_weights", C.c_int32),
+    ]
+
+
 class McrSizes(C.Structure):
     _fields_ = [
         ("total_months", C.c_int32),
@@ -447,6 +460,10 @@ ABI_SYMBOLS = (
     "mcr_probe_allocations_joint_rng",
     "mcr_probe_allocations_outcomes_rng",
     "mcr_probe_allocations_last_fanout_launches",
+    "mcr_probe_glide_paths_rng",
+    "mcr_probe_glide_paths_joint_rng",
+    "mcr_probe_glide_paths_outcomes_rng",
+    "mcr_probe_glide_paths_last_fanout_launches",
     "mcr_release_cached",
     "mcr_sample_columns",
     "mcr_eval_helper_host",
@@ -649,6 +666,17 @@ def _declare(lib: C.CDLL) -> None:
         lib.mcr_probe_allocations_outcomes_rng.argtypes = head + [P(McrOptionOutcomes), C.c_int, C.c_void_p]
         lib.mcr_probe_allocations_last_fanout_launches.restype = C.c_int
         lib.mcr_probe_allocations_last_fanout_launches.argtypes = []
+    if hasattr(lib, "mcr_probe_glide_paths_rng"):   # (likewise)
+        head = [P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32, P(C.c_double), C.c_int32, P(McrGlideOption),
+                C.c_int32, C.c_void_p]       # ..., weights, n_weights, options, n_options, counts
+        lib.mcr_probe_glide_paths_rng.restype = C.c_int
+        lib.mcr_probe_glide_paths_rng.argtypes = head + [C.c_int, C.c_void_p]
+        lib.mcr_probe_glide_paths_joint_rng.restype = C.c_int
+        lib.mcr_probe_glide_paths_joint_rng.argtypes = head + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]   # masks, joint, extremes
+        lib.mcr_probe_glide_paths_outcomes_rng.restype = C.c_int
+        lib.mcr_probe_glide_paths_outcomes_rng.argtypes = head + [P(McrOptionOutcomes), C.c_int, C.c_void_p]
+        lib.mcr_probe_glide_paths_last_fanout_launches.restype = C.c_int
+        lib.mcr_probe_glide_paths_last_fanout_launches.argtypes = []
     if hasattr(lib, "mcr_probe_rule_grid_rng"):   # (likewise)
         lib.mcr_probe_rule_grid_rng.restype = C.c_int
         lib.mcr_probe_rule_grid_rng.argtypes = [

@@ -5,6 +5,9 @@ to `find_minimum_working_months` (when), `spending.search_maximum_expenses` (how
 `allocation_records` turns the options a caller writes (a float, or a mapping) into the records of the allocation probes
 (``mcr_probe_allocations_rng``: up to ``MCR_MAX_EXPENSE_FANOUT`` splits over the same random numbers).
 
+`GlidePath` is a split that changes with the calendar (a table of weights by whole years from today) and `glide_records` builds
+the records of the glide probes (``mcr_probe_glide_paths_rng``) from the glide options a caller writes.
+
 `search_best_allocation` is a pure function of a ``probe_levels(splits) -> [success %]`` callable, so it runs (and is tested)
 without a GPU.  Success as a function of the split is NOT monotone (too little of the growth asset starves the plan, too much
 exposes it), so nothing of `search.cent_search` or `search.refine` applies: the search keeps `search.Evaluation` (memo, curve,
@@ -142,3 +145,215 @@ def search_best_allocation(
         joint = probe_joint([value_of(u) for u in units])
         tied = [value_of(units[j]) for j in joint.indistinguishable_from(units.index(best))]
     return answer, ev.memo[best], ev.curve, tied
+
+
+# ---- glide paths: a split that changes with the calendar (include/mcr.h: GLIDE PATH) ------------------------------------
+
+#: the keys a glide option given as a mapping may set
+GLIDE_OPTION_FIELDS = SCENARIO_FIELDS + ("glide_path",)
+
+
+def _weight(x, what: str) -> float:
+    try:
+        v = float(x)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} = {x!r}: must be a number") from None
+    if not (math.isfinite(v) and 0.0 <= v <= 1.0):
+        raise ValueError(f"{what} = {v!r}: must be finite and in [0, 1]")
+    return v
+
+
+def _year(x, what: str) -> int:
+    if isinstance(x, bool) or int(x) != x or int(x) < 0:
+        raise ValueError(f"{what} = {x!r}: must be a whole number of years >= 0")
+    return int(x)
+
+
+class GlidePath:
+    """An immutable table of ``allocation_inv1_pct`` values indexed by WHOLE YEARS FROM TODAY: entry ``y`` is in force during
+    months ``12 y .. 12 y + 11`` from today, whatever the retirement month; a table shorter than the horizon holds its last
+    entry, entries past the horizon are never read.  Every entry is finite and in [0, 1]; there is at least one."""
+
+    __slots__ = ("_weights", "_name")
+
+    def __init__(self, weights: Sequence[float], name: Optional[str] = None):
+        try:
+            entries = list(weights)
+        except TypeError:
+            raise ValueError(f"glide path weights = {weights!r}: must be a sequence of numbers") from None
+        if not entries:
+            raise ValueError("a glide path has at least one weight")
+        object.__setattr__(self, "_weights", tuple(_weight(w, f"weights[{i}]") for i, w in enumerate(entries)))
+        object.__setattr__(self, "_name", None if name is None else str(name))
+
+    def __setattr__(self, key, value):
+        raise AttributeError("a GlidePath is immutable")
+
+    @property
+    def weights(self) -> Tuple[float, ...]:
+        return self._weights
+
+    @property
+    def name(self) -> Optional[str]:
+        return self._name
+
+    def named(self, name: str) -> "GlidePath":
+        return GlidePath(self._weights, name)
+
+    def weight_at(self, month_from_today: int) -> float:
+        """The weight in force while 0-based month ``month_from_today`` is processed: ``W[min(t // 12, n - 1)]``."""
+        if month_from_today < 0:
+            raise ValueError("month_from_today must be >= 0")
+        return self._weights[min(int(month_from_today) // 12, len(self._weights) - 1)]
+
+    def __len__(self) -> int:
+        return len(self._weights)
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, GlidePath) and self._weights == other._weights
+
+    def __hash__(self) -> int:
+        return hash(self._weights)
+
+    def __repr__(self) -> str:
+        return f"GlidePath({self.describe()})"
+
+    @classmethod
+    def constant(cls, allocation: float, name: Optional[str] = None) -> "GlidePath":
+        """The constant split ``allocation``: a table of one entry."""
+        return cls([_weight(allocation, "allocation")], name)
+
+    @classmethod
+    def linear(cls, start: float, end: float, from_year: int, to_year: int, name: Optional[str] = None) -> "GlidePath":
+        """``start`` up to and including year ``from_year``, ``end`` from year ``to_year`` on, and a straight line between them:
+        ``to_year + 1`` entries (``from_year == to_year``: a step to ``end`` in the year after)."""
+        a, b = _weight(start, "start"), _weight(end, "end")
+        y0, y1 = _year(from_year, "from_year"), _year(to_year, "to_year")
+        if y1 < y0:
+            raise ValueError(f"to_year = {y1} < from_year = {y0}")
+        if y1 == y0:
+            return cls([a] * (y0 + 1) + [b], name)
+        table = []
+        for y in range(y1 + 1):
+            if y <= y0:
+                table.append(a)
+            elif y >= y1:
+                table.append(b)
+            else:
+                table.append(min(1.0, max(0.0, a + (b - a) * ((y - y0) / (y1 - y0)))))
+        return cls(table, name)
+
+    @classmethod
+    def around_retirement(cls, working_months: int, before: float, at: float, after: float, years_before: int, years_after: int,
+                          name: Optional[str] = None) -> "GlidePath":
+        """The target-date and the rising-equity shapes, in years from today for a retirement after ``working_months``:
+        ``before`` until ``years_before`` years ahead of the retirement year ``R = working_months // 12``, a straight line to
+        ``at`` in year ``R``, a straight line to ``after`` in year ``R + years_after``, ``after`` from then on.  A line that
+        would begin before today begins today, at the value it has there."""
+        wm = _year(working_months, "working_months")
+        w0, w1, w2 = _weight(before, "before"), _weight(at, "at"), _weight(after, "after")
+        yb, ya = _year(years_before, "years_before"), _year(years_after, "years_after")
+        r = wm // 12
+        table = []
+        for y in range(r + ya + 1):
+            if y <= r:
+                x = w1 if yb == 0 and y == r else w0 if y <= r - yb else w0 + (w1 - w0) * ((y - (r - yb)) / yb)
+            else:
+                x = w2 if ya == 0 else w1 + (w2 - w1) * ((y - r) / ya)
+            table.append(min(1.0, max(0.0, x)))
+        return cls(table, name)
+
+    @classmethod
+    def parse(cls, text: str) -> "GlidePath":
+        """``"0.6"`` (a constant) or ``"start>end@from-to"`` (`linear`), the command-line tool's syntax."""
+        t = str(text).strip()
+        try:
+            if ">" not in t:
+                return cls.constant(float(t), t)
+            levels, _, years = t.partition("@")
+            start, _, end = levels.partition(">")
+            y0, _, y1 = years.partition("-")
+            return cls.linear(float(start), float(end), int(y0), int(y1), t)
+        except ValueError as e:
+            raise ValueError(f"glide path {text!r}: expected a constant or start>end@from-to ({e})") from None
+
+    def describe(self) -> str:
+        """A short description: the name where there is one, else the run-length form of the table."""
+        if self._name:
+            return self._name
+        w = self._weights
+        if all(x == w[0] for x in w):
+            return f"constant {w[0]:.4g}"
+        return f"{w[0]:.4g} -> {w[-1]:.4g} over {len(w)} years"
+
+
+def default_glide_paths(p, working_months: int) -> List[GlidePath]:
+    """The catalogue `RetirementMonteCarloSimulator.compare_glide_paths` compares when it is given no list, built for a
+    retirement after ``working_months``: the config's own constant split, all of asset 1, none of it, two declining target-date
+    shapes and one rising-equity shape."""
+    wm = int(working_months)
+    return [
+        GlidePath.constant(float(p.allocation_inv1_pct), "own constant split"),
+        GlidePath.constant(1.0, "all in asset 1"),
+        GlidePath.constant(0.0, "all in asset 2"),
+        GlidePath.around_retirement(wm, 0.9, 0.5, 0.4, 20, 10, "target date 90 > 50 > 40"),
+        GlidePath.around_retirement(wm, 0.8, 0.6, 0.3, 15, 15, "target date 80 > 60 > 30"),
+        GlidePath.around_retirement(wm, 0.6, 0.3, 0.6, 10, 15, "rising equity 60 > 30 > 60"),
+    ]
+
+
+def glide_paths_of(options: Sequence) -> List[GlidePath]:
+    """The `GlidePath` of every entry of ``options`` (see `glide_records`), validated."""
+    paths = []
+    for k, o in enumerate(options):
+        try:
+            if isinstance(o, dict):
+                if "glide_path" not in o:
+                    raise ValueError("glide_path is missing")
+                o = o["glide_path"]
+            if isinstance(o, GlidePath):
+                paths.append(o)
+            elif isinstance(o, (int, float)) and not isinstance(o, bool):
+                paths.append(GlidePath.constant(o))
+            elif isinstance(o, str):
+                paths.append(GlidePath.parse(o))
+            else:
+                paths.append(GlidePath(o))
+        except ValueError as e:
+            raise ValueError(f"glide_paths[{k}]: {e}") from None
+    return paths
+
+
+def glide_records(p, options: Sequence) -> Tuple[List[tuple], List[float]]:
+    """``(records, table)`` of the glide probes (``mcr_probe_glide_paths_rng``): ``records[k] = (initial_balance,
+    monthly_contribution, monthly_expenses, first_weight, n_weights)`` and ``table`` the flat list of all options' weights,
+    option k's at ``table[first_weight : first_weight + n_weights]`` (equal tables are stored once).  An option is a
+    `GlidePath`, a sequence of weights, a number (a constant split), a string in `GlidePath.parse`'s syntax, or a mapping with
+    ``glide_path`` (any of those) and any subset of the three scenario keys (a missing amount takes the config's value).
+    ``p`` is the config.  Raises ``ValueError`` naming the option and the field, as `allocation_records` does."""
+    defaults = (float(p.initial_balance), float(p.monthly_contribution), float(p.monthly_expenses))
+    for k, o in enumerate(options):
+        if isinstance(o, dict):
+            unknown = sorted(set(o) - set(GLIDE_OPTION_FIELDS))
+            if unknown:
+                raise ValueError(f"glide_paths[{k}]: unknown key(s) {unknown}; an option may set {list(GLIDE_OPTION_FIELDS)}")
+            if "glide_path" not in o:
+                raise ValueError(f"glide_paths[{k}].glide_path is missing")
+    paths = glide_paths_of(options)
+    records, table, first_of = [], [], {}
+    for k, (o, path) in enumerate(zip(options, paths)):
+        amounts = []
+        for f, d in zip(SCENARIO_FIELDS, defaults):
+            v = o.get(f, d) if isinstance(o, dict) else d
+            try:
+                x = float(v)
+            except (TypeError, ValueError):
+                raise ValueError(f"glide_paths[{k}].{f} = {v!r}: must be a number") from None
+            if not (math.isfinite(x) and x >= 0.0):
+                raise ValueError(f"glide_paths[{k}].{f} = {x!r}: must be finite and >= 0")
+            amounts.append(x)
+        if path.weights not in first_of:
+            first_of[path.weights] = len(table)
+            table.extend(path.weights)
+        records.append((*amounts, first_of[path.weights], len(path.weights)))
+    return records, table

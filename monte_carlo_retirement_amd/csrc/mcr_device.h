@@ -103,6 +103,18 @@ struct WaveAllocParams {
     int32_t any_annual_tax;
 };
 struct NoWaveAlloc { static constexpr double alloc1 = 0.0; };   // (named, never read: `kAlcFan ? WA.alloc1 : P.alloc1` folds to the block's)
+// PHASE 13 (the glide fan-out): the same view, whose weight the wave reloads at every calendar-year change from its own table
+// W[0 .. n - 1] (include/mcr.h: GLIDE PATH).  `w` stands at the entry in force, `left` counts the entries behind it, `moy` the
+// rows of the calendar year that are done: three scalars.  The helpers above and below take it as its base.  The table is read
+// through the CONSTANT address space like DevStreamTable: nothing writes it while the kernel runs, and the year's reload is a
+// scalar load (s_load_dwordx2) whatever the alias analysis makes of the kernel's own stores (through a plain pointer the
+// decumulation's reload came out as a vector load of a uniform address).
+typedef const __attribute__((address_space(4))) double* GlideTable;
+struct WaveGlideParams : WaveAllocParams {
+    GlideTable w;
+    int32_t left;
+    int32_t moy;
+};
 // The tolerance form of the month (below) selects the seller's rate and the seller's weight x rate; it needs neither weight
 // on its own (the drift of asset 2 is minus the drift of asset 1).  In the SAME struct, so that the helpers keep one
 // signature: alloc1 / alloc2 then hold the products.
@@ -134,6 +146,23 @@ __device__ __forceinline__ LaneParams month_lane_params(const WaveAllocParams& W
     LaneParams L{W.alloc1, W.alloc2, P.real_rate1, P.real_rate2};    // (lane_params': the exact month's diagnostic build)
     asm volatile("" : "+v"(L.alloc1), "+v"(L.alloc2), "+v"(L.real_rate1), "+v"(L.real_rate2));
     return L;
+}
+// PHASE 13, at the top of every row t = 0, 1, ... of the consumer's path (wave-uniform): behind it W.alloc1 = W[min(t / 12, n - 1)]
+// (include/mcr.h: GLIDE PATH).  The weight changes where t % 12 == 0, t > 0, and only while the table has an entry left: one
+// scalar load, derive_params' subtraction, the lanes' products again.
+template <bool TOL, bool EQR>
+__device__ __forceinline__ void glide_row(WaveGlideParams& W, const DevParams& P, LaneParams& L) {
+    if (W.moy == kMPY) {
+        W.moy = 0;
+        if (W.left > 0) {
+            --W.left;
+            ++W.w;
+            W.alloc1 = *W.w;
+            W.alloc2 = 1.0 - W.alloc1;
+            L = month_lane_params<TOL, EQR>(W, P);
+        }
+    }
+    ++W.moy;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -170,6 +170,19 @@ static_assert(offsetof(RuleGridCell, cell) == 0 && sizeof(RuleGridCell) == sizeo
 // mcr_scenario (initial_balance, monthly_contribution, monthly_expenses), through `cand_params` like the grid's records
 static_assert(sizeof(mcr_scenario) == 3 * sizeof(double), "mcr_scenario is three packed doubles");
 static_assert(sizeof(mcr_allocation_option) == 4 * sizeof(double), "mcr_allocation_option is four packed doubles: the allocation fan-out's table as it comes");
+// PHASE 13 (glide probe, mcr_probe_glide_paths_rng): consumer wave j of a launch runs record j of the launch's device table, the
+// caller's mcr_glide_option with first_weight replaced by the distance, in doubles, from the record ITSELF to its first weight
+// (the weights stand behind the last record of the whole table): a group's launch, which gets the table at its own first record,
+// finds its weights without knowing where the table began
+struct GlideRecord {
+    double initial_balance, monthly_contribution, monthly_expenses;
+    int32_t weights;       // doubles from this record to W[0]
+    int32_t n_weights;     // >= 1
+};
+static_assert(sizeof(mcr_glide_option) == 4 * sizeof(double) && sizeof(GlideRecord) == sizeof(mcr_glide_option) &&
+              offsetof(mcr_glide_option, first_weight) == offsetof(GlideRecord, weights) && offsetof(mcr_glide_option, n_weights) == offsetof(GlideRecord, n_weights) &&
+              offsetof(mcr_glide_option, monthly_expenses) == offsetof(mcr_allocation_option, monthly_expenses),
+              "mcr_glide_option is 32 bytes and begins like mcr_allocation_option: the kernel reads the three amounts through either");
 // PHASE 9 (assumption probe, mcr_probe_assumptions_rng): consumer wave j of a launch runs record j of the launch's device table,
 // through `cand_params` as well: PHASE 8's three values and the market as growth_factors_row reads it (mcr_device.h), derived on
 // the host by the function derive_params uses (derive_market)
@@ -549,7 +562,7 @@ __device__ __forceinline__ void income_put(DevStream& S, const IncomeRegs& R) {
 }
 
 template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault, int GF = 0, int MF = 0, int SF = 0, bool OUT = false, bool LIST = false, int NPROD = 1, bool RULE = false>
-__global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE == 8 || PHASE == 9 || PHASE == 10 || PHASE == 11 || PHASE == 12) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : NPROD == 2 ? 3 * 64 : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
+__global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE == 8 || PHASE == 9 || PHASE == 10 || PHASE == 11 || PHASE == 12 || PHASE == 13) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : NPROD == 2 ? 3 * 64 : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
                                                          const DevParams* __restrict__ cand_params) {
     // MODE 3 (mcr_run_year_bins_rng): YEARLY BINS.  The arithmetic of MODE 2, but wherever that variant stores a yearly sample
     // (nominal balance, real balance, withdrawal rate) the lane bins it instead: cell 0 = below edges[0], cells 1 .. n = the
@@ -573,10 +586,11 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     static_assert(PHASE != 10 || SPLIT, "the income fan-out is a producer / consumer form");
     static_assert(PHASE != 11 || (SPLIT && RULE), "the rule fan-out is a producer / consumer form of the rule kernels");
     static_assert(PHASE != 12 || SPLIT, "the allocation fan-out is a producer / consumer form");
+    static_assert(PHASE != 13 || SPLIT, "the glide fan-out is a producer / consumer form");
     // OUT (mcr_probe_*_outcomes_rng): the PHASE 8 / 9 / 10 consumer waves also store their paths' outcome rows (KernelIO::fan_final,
     // fan_ruin) in the epilogue.  A template flag, not a null check: the month of failure is one more VGPR through the month loop,
     // which the plain and the joint probes' kernels do not pay.
-    static_assert(!OUT || PHASE == 8 || PHASE == 9 || PHASE == 10 || PHASE == 11 || PHASE == 12, "outcome rows exist for the scenario, assumption, income, rule and allocation fan-outs");
+    static_assert(!OUT || PHASE == 8 || PHASE == 9 || PHASE == 10 || PHASE == 11 || PHASE == 12 || PHASE == 13, "outcome rows exist for the scenario, assumption, income, rule, allocation and glide fan-outs");
     // LIST (the re-run of a screened launch; launch_screened): the lanes' local path indices come from a device list that
     // screen_kernel filled earlier on the stream, io.path_list[i] for i < *io.path_list_count; lanes beyond the count behave
     // like tail lanes, and a workgroup whose first index is at or beyond the count returns at once (the host sizes the grid
@@ -619,7 +633,8 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     constexpr bool kStreamRegs = SPLIT && !kAsmFan && !(LIST && (SF & kStreamsInRegs) != 0);   // the first two income streams stay in SGPRs for the whole launch (S0, S1 below; the split re-run's stream form keeps StreamRegs instead)
     constexpr bool kIncFan = PHASE == 10;                 // income fan-out: the scenario fan-out with one income stream per wave as well
     constexpr bool kRuleFan = PHASE == 11;                // rule fan-out: the scenario fan-out with a spending rule per wave as well
-    constexpr bool kAlcFan = PHASE == 12;                 // allocation fan-out: the scenario fan-out with the split between the assets per wave as well
+    constexpr bool kGldFan = PHASE == 13;                 // glide fan-out: the allocation fan-out whose wave reloads its split once a calendar year from its own table
+    constexpr bool kAlcFan = PHASE == 12 || kGldFan;      // allocation fan-out: the scenario fan-out with the split between the assets per wave as well
     constexpr bool kScnFan = PHASE == 8 || kAsmFan || kIncFan || kRuleFan || kAlcFan;   // scenario fan-out: balance, contribution and spending per wave, the whole path
     constexpr bool kFan = kExpFan || kConFan || kScnFan;  // fan-out workgroup: one 64-path block, L consumer waves (levels), one producer wave
     constexpr bool kGrid = PHASE == 6;                    // ... of grid row blockIdx.y (GridCell)
@@ -642,7 +657,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     [[maybe_unused]] std::conditional_t<OUT, RuinMonth, NoRuinMonth> RM;         // (likewise: the outcome probes' month of failure)
     [[maybe_unused]] std::conditional_t<RULE, RuleState, NoRuleState> RS;        // (likewise: the spending rule's multiplier)
     [[maybe_unused]] std::conditional_t<kWaveRule, FanRule, NoFanRule> FR;       // (likewise: PHASE 11 and PHASE 6 with RULE, the consumer wave's own rule)
-    [[maybe_unused]] std::conditional_t<kAlcFan, WaveAllocParams, NoWaveAlloc> WA;   // (likewise: PHASE 12, the consumer wave's own weights, mcr_device.h)
+    [[maybe_unused]] std::conditional_t<kGldFan, WaveGlideParams, std::conditional_t<kAlcFan, WaveAllocParams, NoWaveAlloc>> WA;   // (likewise: PHASE 12 / 13, the consumer wave's own weights, mcr_device.h)
     static_assert(!kSliced || (RNG == 0 && !INJ && !SPLIT && !XS), "time-sliced blocks exist for the plain Philox variants");
     static_assert(PHASE != 4 || MODE == 0, "the search probes count only");
     // TAXED: which assets carry an effective realized-gains rate (bit 0: inv1, bit 1: inv2; DevParams::tax_mask)
@@ -914,13 +929,32 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     // PHASE 12: the wave's weights from its record (wave-uniform: scalar loads from the launch's table, like PHASE 11's rule), and
     // what else the month's helpers read of the block beside them.  alloc2 = 1.0 - alloc1: derive_params' operation.  The producer,
     // wave fan_n, stands one past the group's records: it reads record 0's, and uses none of it.
+    // PHASE 13: the record names the wave's table instead, GlideRecord::weights doubles behind the record itself (probe_glide_paths_fanout:
+    // the host's offset, so that a group's launch, which gets the table at ITS first record, reads its own weights); W[0] is in
+    // force from row 0, `left` = n - 1 entries stand behind it.
+    if constexpr (kGldFan) {
+        const GlideRecord* const rec = reinterpret_cast<const GlideRecord*>(cand_params) + (producer ? 0 : fan_j);
+        WA.w = (GlideTable)(reinterpret_cast<const double*>(rec) + rec->weights);
+        WA.left = rec->n_weights - 1;
+        WA.moy = 0;
+        WA.alloc1 = *WA.w;
+        WA.alloc2 = 1.0 - WA.alloc1;
+        WA.annual_rate1 = P.annual_rate1; WA.annual_rate2 = P.annual_rate2; WA.any_annual_tax = P.any_annual_tax;
+    } else
     if constexpr (kAlcFan) {
         const mcr_allocation_option* const rec = reinterpret_cast<const mcr_allocation_option*>(cand_params) + (producer ? 0 : fan_j);
         WA.alloc1 = rec->allocation_inv1_pct;
         WA.alloc2 = 1.0 - WA.alloc1;
         WA.annual_rate1 = P.annual_rate1; WA.annual_rate2 = P.annual_rate2; WA.any_annual_tax = P.any_annual_tax;
     }
-    const LaneParams L = month_lane_params<TOL, EQR>(WA, P);
+    std::conditional_t<kGldFan, LaneParams, const LaneParams> L = month_lane_params<TOL, EQR>(WA, P);    // (mutable in PHASE 13 only)
+    // PHASE 13, at the top of every row t (wave-uniform, outside every lane mask): where t % 12 == 0, t > 0 -- a calendar year
+    // from today has closed, which is NOT a retirement-year boundary unless working_months % 12 == 0 -- the weight in force
+    // becomes W[min(t / 12, n - 1)]: one scalar load unless the table is exhausted, then derive_params' subtraction and the two
+    // products of month_lane_params again.  The row's every read of a weight, its annual tax and closing rebalance included,
+    // comes behind this.  A scalar counter of its own: the variants without the annual-gains tax have no year-close branch.
+    // Lanes that have failed run no month and read none of it.  glide_row (mcr_device.h) is the statement; its two calls below
+    // stand under `if constexpr (kGldFan)`, which every other instantiation discards.
 
     // ---- initial state (:490-510) ----
     double b1 = P.initial_balance * P.alloc1;  // :499
@@ -1047,7 +1081,8 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         FR.upper = rec->upper; FR.lower = rec->lower; FR.keep = rec->keep; FR.grow = rec->grow; FR.floor = rec->floor; FR.ceiling = rec->ceiling;
         unsigned long long* const yc = rec->year_counts;
         FR.year_counts = yc ? yc + (size_t)fan_j * (size_t)P.retirement_years * MCR_RULE_N_COUNTS : nullptr;
-    } else if constexpr (kAlcFan) {              // PHASE 12: the record's three values likewise, split by the wave's own weight (WA, above)
+    } else if constexpr (kAlcFan) {              // PHASE 12 / 13: the record's three values likewise, split by the wave's own weight (WA, above; PHASE 13: W[0])
+        // (the two records begin alike: mcr_glide_option's static_assert)
         const mcr_allocation_option* const rec = reinterpret_cast<const mcr_allocation_option*>(cand_params) + fan_j;
         const double rec_balance = rec->initial_balance;
         b1 = rec_balance * WA.alloc1;            // :499
@@ -1128,6 +1163,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     // (kScalarCounters: moy = m mod 12 in 1 .. 12, a running month of the year instead of the two % kMPY tests)
     for (int m = 1; m <= ((kPairs || kCand || (kSliced && seg_resumed)) ? 0 : wm); ++m) {    // (kPairs: in pairs, below)
         if constexpr (kScalarCounters) ++SC.moy;
+        if constexpr (kGldFan) glide_row<TOL, EQR>(WA, P, L);          // (PHASE 13: row m - 1's weight)
         if (P.contrib_grows && year_opens(SC, m - 1) && m > 1) {  // :514-517 (wave-uniform: a scalar branch, not a select)
             asm volatile("");
             contrib *= P.contrib_growth_factor;
@@ -1401,6 +1437,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         int fail_rmi = 0;
         for (int mi = 0; mi < kMPY; ++mi) {
             const int rmi = year * kMPY + mi;  // :641-643
+            if constexpr (kGldFan) glide_row<TOL, EQR>(WA, P, L);      // (PHASE 13: row wm + rmi's weight)
             begin_month(month_row(SC, wm + rmi));
             if (alive && !yfail) {
                 double g1, ginf, g2;
@@ -3761,8 +3798,9 @@ struct LevelGroups {
 // in LDS, *lmax = levels per launch; MCR_ERR_UNSUPPORTED for shapes the form does not cover.
 static int plan_level_fanout(const mcr_params* p, const mcr_rng* rng, uint64_t n_paths, int32_t wm, int32_t n_levels, uint64_t min_waves,
                              DevParams* d, int* lmax, bool parts = false /* PHASE 9's larger stage */,
-                             int keep_index = -1, std::vector<std::pair<int, int>>* kept = nullptr /* PHASE 10: derive_params' */) {
-    if (rng->kind != MCR_RNG_PHILOX || n_levels < 2 || n_paths == 0 || n_paths > ((uint64_t)1 << 31)) return MCR_ERR_UNSUPPORTED;
+                             int keep_index = -1, std::vector<std::pair<int, int>>* kept = nullptr /* PHASE 10: derive_params' */,
+                             int min_levels = 2 /* PHASE 13: 1, the family has no plain launch for a single option */) {
+    if (rng->kind != MCR_RNG_PHILOX || n_levels < min_levels || n_paths == 0 || n_paths > ((uint64_t)1 << 31)) return MCR_ERR_UNSUPPORTED;
     if ((n_paths + 63) / 64 < min_waves) return MCR_ERR_UNSUPPORTED;
     int rc = derive_params(p, wm, d, nullptr, kept, keep_index);
     if (rc != MCR_OK) return rc;
@@ -3851,11 +3889,12 @@ static void set_fan_rows(KernelIO& fio, const mcr_option_outcomes* rows, int fir
 template <typename Record, typename Launch>
 static int launch_record_fanout(const DevParams& d, int lmax, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
                                 const Record* host, int32_t n_records, uint64_t* counts, hipStream_t stream, uint64_t* masks,
-                                const mcr_option_outcomes* rows, int* launches, const char* what, Launch&& launch) {
+                                const mcr_option_outcomes* rows, int* launches, const char* what, Launch&& launch,
+                                size_t tail_bytes = 0 /* PHASE 13: what `host` holds behind its records (the weights), uploaded with them */) {
     KernelIO io = make_io(rng, nullptr, stream_id, path_begin, n_paths);
     SnapshotBlock table(stream);
     hipError_t e = hipSuccess;
-    if (!table.attach(io, 0, host, (size_t)n_records * sizeof(Record), &e, SIZE_MAX)) return MCR_ERR_UNSUPPORTED;
+    if (!table.attach(io, 0, host, (size_t)n_records * sizeof(Record) + tail_bytes, &e, SIZE_MAX)) return MCR_ERR_UNSUPPORTED;
     io.snap = nullptr;   // (no snapshot column: the block is the table alone)
     if (e == hipSuccess) {
         const Record* d_table = (const Record*)table.records;
@@ -4215,6 +4254,7 @@ static int check_joint_args(int32_t n_options, const uint64_t* joint) {
 //   fanout(masks): the probe's probe_*_fanout (MCR_ERR_UNSUPPORTED, nothing enqueued, for shapes it does not cover);
 //   launch(k, stream, success, final_balance, years_to_ruin): option k's whole-path launch into its counter block and, where
 //   non-null, a uint8 [n_paths] column and the two summary columns.
+// `fan_one` (the glide probes, whose family has no plain launch): a single option takes the fan-out like several, in all three forms.
 // Plain (jo == nullptr): one option -> its launch; else the fan-out; else one count-only launch per option (fork_join).
 // Joint: the fan-out stores its ballots to the mask rows; where it does not run, one launch per option with `success` and
 // `counters` set fills a scratch uint8 [n][n_paths] and pack_success_kernel turns each column into its row on the option's side
@@ -4225,9 +4265,10 @@ static int check_joint_args(int32_t n_options, const uint64_t* joint) {
 // not ask for it), and nan_failed_kernel then NaNs the final balances of the failed paths on the option's side stream.
 template <typename Fanout, typename Launch>
 static int run_probe_routes(int device, hipStream_t main, int n, uint64_t n_paths, const JointOut* jo, const mcr_option_outcomes* rows,
-                            Fanout&& fanout, Launch&& launch) {
+                            Fanout&& fanout, Launch&& launch, bool fan_one = false /* the glide probes: a single option fans out too */) {
+    const bool one = n == 1 && !fan_one;     // a single option takes its plain launch
     if (rows && n_paths > 0) {
-        int rc = n == 1 ? MCR_ERR_UNSUPPORTED : fanout(nullptr, rows);
+        int rc = one ? MCR_ERR_UNSUPPORTED : fanout(nullptr, rows);
         if (rc != MCR_ERR_UNSUPPORTED) return rc;
         StreamAlloc own_ruin(main);
         double* ruin = rows->years_to_ruin;
@@ -4256,7 +4297,7 @@ static int run_probe_routes(int device, hipStream_t main, int n, uint64_t n_path
     };
     if (!jo || n_paths == 0) {
         int rc = MCR_OK;
-        if (n == 1) rc = launch(0, main, nullptr, nullptr, nullptr);
+        if (one) rc = launch(0, main, nullptr, nullptr, nullptr);
         else if ((rc = fanout(nullptr, nullptr)) == MCR_ERR_UNSUPPORTED) rc = per_option(nullptr, nullptr);   // (unsupported shape / allocation refused)
         return rc == MCR_OK && jo ? launch_joint_counts(nullptr, n, 0, jo->joint, jo->extremes, main) : rc;
     }
@@ -4267,7 +4308,7 @@ static int run_probe_routes(int device, hipStream_t main, int n, uint64_t n_path
         if (!own_masks.alloc((size_t)n * words * sizeof(uint64_t))) { set_error("joint probe: could not allocate %d mask rows", n); return MCR_ERR_HIP; }
         masks = (uint64_t*)own_masks.p;
     }
-    int rc = n == 1 ? MCR_ERR_UNSUPPORTED : fanout(masks, nullptr);
+    int rc = one ? MCR_ERR_UNSUPPORTED : fanout(masks, nullptr);
     if (rc == MCR_ERR_UNSUPPORTED) {
         if (!flags.alloc((size_t)n * n_paths)) { set_error("joint probe: could not allocate %d success columns", n); return MCR_ERR_HIP; }
         rc = per_option((uint8_t*)flags.p, masks);
@@ -4939,6 +4980,146 @@ int mcr_probe_allocations_outcomes_rng(const mcr_params* p, const mcr_rng* rng, 
 }
 
 int mcr_probe_allocations_last_fanout_launches(void) { return g_last_allocation_fanout_launches; }
+
+// ---- glide probes (PHASE 13; include/mcr.h: GLIDE PATH) ----
+// What the glide probes check on the host, before a device is looked for: the block, the month, the stream, every option and
+// every weight an option names
+static int check_glide_probe(const mcr_params* p, const mcr_rng* rng, int32_t working_months, const double* weights, int32_t n_weights,
+                             const mcr_glide_option* options, int32_t n_options, const uint64_t* counts) {
+    if (n_options < 0) { set_error("n_options %d must be >= 0", n_options); return MCR_ERR_INVALID_ARG; }
+    if (n_options == 0) return MCR_OK;
+    if (!options || !counts) { set_error("null options / counts"); return MCR_ERR_INVALID_ARG; }
+    if (n_weights < 0 || (n_weights > 0 && !weights)) { set_error("weights: n_weights %d must be >= 0 and the table non-null", n_weights); return MCR_ERR_INVALID_ARG; }
+    int rc = validate_months(p, &working_months, 1);
+    if (rc != MCR_OK) return rc;
+    if ((rc = check_rng(rng)) != MCR_OK) return rc;
+    for (int32_t k = 0; k < n_options; ++k) {
+        const mcr_glide_option& o = options[k];
+        if (!amounts_valid("options", k, o)) return MCR_ERR_INVALID_ARG;
+        if (o.n_weights < 1) { set_error("options[%d].n_weights = %d: a glide path has at least one entry", k, o.n_weights); return MCR_ERR_INVALID_ARG; }
+        if (o.first_weight < 0 || (int64_t)o.first_weight + (int64_t)o.n_weights > (int64_t)n_weights) {
+            set_error("options[%d].first_weight = %d with n_weights = %d: outside the table of %d weights", k, o.first_weight, o.n_weights, n_weights);
+            return MCR_ERR_INVALID_ARG;
+        }
+        for (int32_t i = 0; i < o.n_weights; ++i) {
+            const double a = weights[(size_t)o.first_weight + (size_t)i];
+            if (!(std::isfinite(a) && a >= 0.0 && a <= 1.0)) {
+                set_error("options[%d].weights[%d] = %.17g: must be finite and in [0, 1] (config.py:70)", k, i, a);
+                return MCR_ERR_INVALID_ARG;
+            }
+        }
+    }
+    return MCR_OK;
+}
+// The shape of a glide probe: MCR_OK with *d, *lmax = plan_level_fanout's (a single option included), or MCR_ERR_UNSUPPORTED with
+// a message that says what the glide fan-out does not cover -- the family has no per-option route behind it.  Host only.
+static int plan_glide_fanout(const mcr_params* p, const mcr_rng* rng, uint64_t n_paths, int32_t wm, int32_t n_options, int32_t n_weights,
+                             DevParams* d, int* lmax) {
+    auto unsupported = [](const char* why) { set_error("glide probe: %s is not supported under a glide path", why); return MCR_ERR_UNSUPPORTED; };
+    if (rng->kind == MCR_RNG_NUMPY) return unsupported("the NumPy stream");
+    if (rng->kind != MCR_RNG_PHILOX) return unsupported("the history stream");
+    if (n_paths > ((uint64_t)1 << 31)) return unsupported("a range of more than 2^31 paths");
+    const uint64_t min_waves = fanout_min_waves("MCR_GLIDE_FANOUT_MIN_WAVES");
+    if ((n_paths + 63) / 64 < min_waves) return unsupported("a range of fewer than MCR_GLIDE_FANOUT_MIN_WAVES path-wavefronts");
+    // (a record names its table by a 32-bit distance in doubles: records and weights of one call stay below 2^31 doubles)
+    if ((int64_t)n_options * (int64_t)(sizeof(GlideRecord) / sizeof(double)) + (int64_t)n_weights > (int64_t)INT32_MAX) return unsupported("a table of 2^31 doubles or more");
+    const int rc = plan_level_fanout(p, rng, n_paths, wm, n_options, min_waves, d, lmax, false, -1, nullptr, 1);
+    if (rc != MCR_ERR_UNSUPPORTED) return rc;
+    DevParams probe;
+    if (derive_params(p, wm, &probe) == MCR_OK) {
+        if (needs_exact_month(probe)) return unsupported("the exact month");
+        if (probe.n_extra_streams > 0) return unsupported("a stream list longer than MCR_INLINE_STREAMS (the generic variant)");
+    }
+    return unsupported("a plan whose lock slots do not fit LDS (the generic variant)");
+}
+// Several glide paths over the same paths, Philox stream (PHASE 13).  The device table is the caller's records, each naming its
+// table by the distance in doubles from the record itself (GlideRecord), and the caller's weights behind the last record: group
+// g's launch, which gets the table at its first record, needs nothing else.  Of everything derive_params gives the block only
+// alloc1 / alloc2 depend on a weight, as in PHASE 12.  `d`, `lmax`: plan_glide_fanout's.
+static thread_local int g_last_glide_fanout_launches = 0;   // (mcr_probe_glide_paths_last_fanout_launches)
+static int probe_glide_paths_fanout(const DevParams& d, int lmax, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                                    const double* weights, int32_t n_weights, const mcr_glide_option* options, int32_t n_options,
+                                    uint64_t* counts, hipStream_t stream, uint64_t* masks, const mcr_option_outcomes* rows) {
+    constexpr size_t kRecDoubles = sizeof(GlideRecord) / sizeof(double);
+    std::vector<GlideRecord> host((size_t)n_options + ((size_t)n_weights + kRecDoubles - 1) / kRecDoubles);
+    for (int32_t k = 0; k < n_options; ++k) {
+        const mcr_glide_option& o = options[k];
+        host[(size_t)k] = GlideRecord{o.initial_balance, o.monthly_contribution, o.monthly_expenses,
+                                      (int32_t)((int64_t)(n_options - k) * (int64_t)kRecDoubles + (int64_t)o.first_weight), o.n_weights};
+    }
+    if (n_weights > 0) std::memcpy((void*)(host.data() + n_options), weights, (size_t)n_weights * sizeof(double));
+    return launch_record_fanout(d, lmax, rng, stream_id, path_begin, n_paths, host.data(), n_options, counts, stream, masks, rows,
+                                &g_last_glide_fanout_launches, "glide fan-out probe",
+                                [&](const KernelIO& fio, int, dim3 grid, dim3 block, size_t lds, const DevParams* table) {
+        for_tax_variant(d, [&](auto T, auto A) {
+            for_bool(rows != nullptr, [&](auto O) {
+                hipLaunchKernelGGL((path_kernel<0, 0, decltype(T)::value, decltype(A)::value, false, 13, true, false, kExactMonthDefault, 0, 0, 0, decltype(O)::value>),
+                                   grid, block, lds, stream, d, fio, table);
+            });
+        });
+    }, (size_t)n_weights * sizeof(double));
+}
+// mcr_probe_glide_paths_rng (jo == nullptr, rows == nullptr), mcr_probe_glide_paths_joint_rng and
+// mcr_probe_glide_paths_outcomes_rng, their arguments checked.  The shape is decided before a device is entered and before an
+// output is touched; run_probe_routes then has the fan-out alone (a single option too: `fan_one`), and its per-option route,
+// reached only when the table's allocation is refused, answers MCR_ERR_UNSUPPORTED.
+static int probe_glide_paths(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                             int32_t working_months, const double* weights, int32_t n_weights, const mcr_glide_option* options,
+                             int32_t n_options, uint64_t* counts, const JointOut* jo, const mcr_option_outcomes* rows, int device, void* hip_stream) {
+    DevParams d;
+    int lmax = 0;
+    if (n_paths > 0) { if (int rc = plan_glide_fanout(p, rng, n_paths, working_months, n_options, n_weights, &d, &lmax)) return rc; }
+    MCR_ENTER_DEVICE(device);
+    const hipStream_t main = (hipStream_t)hip_stream;
+    int rc = zero_counters(counts, (size_t)n_options, main);
+    if (rc != MCR_OK) return rc;
+    if (n_paths == 0) return jo ? launch_joint_counts(nullptr, n_options, 0, jo->joint, jo->extremes, main) : MCR_OK;   // (an empty range: zeroes)
+    auto launch_option = [&](int, hipStream_t, uint8_t*, double*, double*) {
+        set_error("glide probe: the device table could not be allocated, and a glide path has no per-option launch");
+        return (int)MCR_ERR_UNSUPPORTED;
+    };
+    auto fanout = [&](uint64_t* masks, const mcr_option_outcomes* fan_rows) {
+        return probe_glide_paths_fanout(d, lmax, rng, stream_id, path_begin, n_paths, weights, n_weights, options, n_options, counts, main, masks, fan_rows);
+    };
+    return run_probe_routes(device, main, n_options, n_paths, jo, rows, fanout, launch_option, true);
+}
+
+int mcr_probe_glide_paths_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                              uint64_t n_paths, int32_t working_months, const double* weights, int32_t n_weights,
+                              const mcr_glide_option* options, int32_t n_options, uint64_t* counts, int device, void* hip_stream) {
+    g_last_glide_fanout_launches = 0;
+    if (int rc = check_glide_probe(p, rng, working_months, weights, n_weights, options, n_options, counts)) return rc;
+    if (n_options == 0) return MCR_OK;
+    return probe_glide_paths(p, rng, stream_id, path_begin, n_paths, working_months, weights, n_weights, options, n_options, counts, nullptr, nullptr,
+                             device, hip_stream);
+}
+
+int mcr_probe_glide_paths_joint_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                    uint64_t n_paths, int32_t working_months, const double* weights, int32_t n_weights,
+                                    const mcr_glide_option* options, int32_t n_options, uint64_t* counts, uint64_t* masks,
+                                    uint64_t* joint, uint64_t* extremes, int device, void* hip_stream) {
+    g_last_glide_fanout_launches = 0;
+    if (int rc = check_joint_args(n_options, joint)) return rc;
+    if (int rc = check_glide_probe(p, rng, working_months, weights, n_weights, options, n_options, counts)) return rc;
+    if (n_options == 0) return MCR_OK;
+    const JointOut jo{masks, joint, extremes};
+    return probe_glide_paths(p, rng, stream_id, path_begin, n_paths, working_months, weights, n_weights, options, n_options, counts, &jo, nullptr,
+                             device, hip_stream);
+}
+
+int mcr_probe_glide_paths_outcomes_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin,
+                                       uint64_t n_paths, int32_t working_months, const double* weights, int32_t n_weights,
+                                       const mcr_glide_option* options, int32_t n_options, uint64_t* counts,
+                                       const mcr_option_outcomes* rows, int device, void* hip_stream) {
+    g_last_glide_fanout_launches = 0;
+    if (int rc = check_outcome_args(&rows, n_paths)) return rc;
+    if (int rc = check_glide_probe(p, rng, working_months, weights, n_weights, options, n_options, counts)) return rc;
+    if (n_options == 0) return MCR_OK;
+    return probe_glide_paths(p, rng, stream_id, path_begin, n_paths, working_months, weights, n_weights, options, n_options, counts, nullptr, rows,
+                             device, hip_stream);
+}
+
+int mcr_probe_glide_paths_last_fanout_launches(void) { return g_last_glide_fanout_launches; }
 
 // Everything launch_rule refuses of a launch's shape, for a probe that has no route behind the rule kernels: `who` heads the
 // message ("spending rule" gives launch_rule's own words).  `d` = derive_params' block of the probed month; `summary`: the

@@ -882,6 +882,57 @@ def probe_allocations_outcomes(params: McrParams, seed, stream_id: int, path_beg
                           device, outcomes=(final_balance, years_to_ruin, path_stride))
 
 
+def _glide_option_records(options):
+    """`options`: ``(initial_balance, monthly_contribution, monthly_expenses, weights)`` 4-tuples, `weights` the option's glide
+    path (a non-empty sequence of ``allocation_inv1_pct`` values, one per whole year from today).  Returns what the glide
+    probes take between ``working_months`` and ``n_options``: the flat table (equal tables are stored once), its length and the
+    records."""
+    flat, first_of, records = [], {}, []
+    for o in options:
+        if len(o) != 4:
+            raise ValueError("every option is (initial_balance, monthly_contribution, monthly_expenses, weights)")
+        weights = tuple(float(w) for w in o[3])
+        if not weights:
+            raise ValueError("a glide path has at least one weight")
+        if weights not in first_of:
+            first_of[weights] = len(flat)
+            flat.extend(weights)
+        records.append(N.McrGlideOption(float(o[0]), float(o[1]), float(o[2]), first_of[weights], len(weights)))
+    table = (C.c_double * max(1, len(flat)))(*flat)
+    return (table, len(flat), (N.McrGlideOption * max(1, len(records)))(*records)), len(records)
+
+
+def probe_glide_paths(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
+                      options, device: int = 0):
+    """Success counters of several glide paths (and versions of the three scenario fields) at one working-month count over the
+    same path range (``mcr_probe_glide_paths_rng``; include/mcr.h: GLIDE PATH).  ``options`` is a sequence of
+    ``(initial_balance, monthly_contribution, monthly_expenses, weights)`` 4-tuples; a constant table counts exactly what
+    `probe_allocations` counts for that split.  Up to ``MCR_MAX_EXPENSE_FANOUT`` options share each path's random numbers, and
+    a single option runs in the same kernel.  Shapes the glide fan-out does not cover (the NumPy and history streams, the
+    generic variant, the exact month) raise the library's ``MCR_ERR_UNSUPPORTED`` error unchanged.  Returns a device int64
+    tensor ``[len(options), 2]`` = ``{successes, paths}``; asynchronous (reading it synchronises)."""
+    args, n = _glide_option_records(options)
+    return _probe_records("mcr_probe_glide_paths_rng", params, seed, stream_id, path_begin, n_paths, working_months, args, n, device)
+
+
+def probe_glide_paths_joint(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
+                            options, device: int = 0, masks=True):
+    """`probe_glide_paths` plus the joint outcomes of its options (``mcr_probe_glide_paths_joint_rng``); returns ``(counts,
+    joint, extremes, masks)`` as `probe_scenarios_joint`."""
+    args, n = _glide_option_records(options)
+    return _probe_records("mcr_probe_glide_paths_joint_rng", params, seed, stream_id, path_begin, n_paths, working_months, args, n,
+                          device, joint=True, masks=masks)
+
+
+def probe_glide_paths_outcomes(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int,
+                               options, device: int = 0, final_balance=True, years_to_ruin=True, path_stride: Optional[int] = None):
+    """`probe_glide_paths` plus the per-path outcomes of its options (``mcr_probe_glide_paths_outcomes_rng``); returns
+    ``(counts, final_rows, ruin_rows)`` as `probe_scenarios_outcomes`."""
+    args, n = _glide_option_records(options)
+    return _probe_records("mcr_probe_glide_paths_outcomes_rng", params, seed, stream_id, path_begin, n_paths, working_months, args, n,
+                          device, outcomes=(final_balance, years_to_ruin, path_stride))
+
+
 def _rule_option_records(options):
     """`options`: ``(initial_balance, monthly_contribution, monthly_expenses, rule)`` 4-tuples, `rule` a
     `spending_rules.SpendingRule`, a ready ``McrSpendingRule`` or None (the neutral rule: fixed spending)."""

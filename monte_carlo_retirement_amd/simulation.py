@@ -880,7 +880,7 @@ class RetirementMonteCarloSimulator:
         return np.array([self._count_percent(counts[i, N.MCR_CTR_SUCCESS], n) for i in range(len(levels))], dtype=np.float64)
 
     def _option_records(self, family: str, options: Sequence[dict], stream=None) -> Tuple[List[tuple], tuple]:
-        """What is specific to an option family -- ``"scenarios"``, ``"income"``, ``"assumptions"``, ``"allocations"`` or ``"rules"``, which is also
+        """What is specific to an option family -- ``"scenarios"``, ``"income"``, ``"assumptions"``, ``"allocations"``, ``"glide_paths"`` or ``"rules"``, which is also
         the middle of its three `engine` entry points ``probe_<family>``, ``probe_<family>_joint`` and
         ``probe_<family>_outcomes``: ``(records, lead)``, the validated records of ``options`` and the arguments the engine
         calls take in front of them.  Raises ``ValueError`` as the family's record builder does."""
@@ -902,6 +902,11 @@ class RetirementMonteCarloSimulator:
             from .allocation import allocation_records
 
             return allocation_records(p, options), ()
+        if family == "glide_paths":     # (a record carries its own table: a shard of the options is a call of its own)
+            from .allocation import glide_records
+
+            records, table = glide_records(p, options)
+            return [(*r[:3], tuple(table[r[3]:r[3] + r[4]])) for r in records], ()
         from .spending_rules import rule_options
 
         return rule_options(p, options), ()
@@ -1492,6 +1497,53 @@ class RetirementMonteCarloSimulator:
                         f"({len(curve)} splits evaluated; {len(tied)} of the first grid indistinguishable from it).")))
 
         return self._find_level(verbose, plan)
+
+    # ---- glide paths: a split that changes with the calendar ---------------------------------------------
+    def success_probability_by_glide_paths(self, working_months: int, glide_paths: Sequence,
+                                           num_simulations: Optional[int] = None) -> np.ndarray:
+        """Success % of each glide path at ``working_months``, over the active seed stream's batch of ``num_simulations`` paths
+        (default ``num_simulations_main``), from the glide probe (``mcr_probe_glide_paths_rng``; include/mcr.h: GLIDE PATH).
+        An option is an `allocation.GlidePath`, a sequence of weights by whole years from today, a number (a constant split),
+        a string ``start>end@from-to``, or a mapping with ``glide_path`` and any subset of ``initial_balance``,
+        ``monthly_contribution``, ``monthly_expenses``; a bad option raises ``ValueError`` naming it (before any device work).
+        Aligned with the input; a constant table gives `success_probability_by_allocations`' value for that split bit for bit.
+        The NumPy and history streams, stream lists beyond the inline ones and the exact month are not supported under a glide
+        path: the library's error is raised unchanged.  Under a process group the options go through
+        ``distributed.probe_candidates``, so every rank returns the same array."""
+        return self._option_probabilities("glide_paths", working_months, glide_paths, num_simulations)
+
+    def joint_outcomes_by_glide_paths(self, working_months: int, glide_paths: Sequence, num_simulations: Optional[int] = None):
+        """The joint outcomes of the options of `success_probability_by_glide_paths` (same arguments) over their shared paths,
+        from the joint glide probe (``mcr_probe_glide_paths_joint_rng``): a `paired.JointOutcomes` whose ``.probabilities``
+        equal that method's array bit for bit.  At most ``MCR_MAX_JOINT_OPTIONS`` options."""
+        return self._option_probe("joint", "glide_paths", working_months, glide_paths, num_simulations)
+
+    def option_outcomes_by_glide_paths(self, working_months: int, glide_paths: Sequence, num_simulations: Optional[int] = None,
+                                       quantiles: Sequence[float] = (0.05, 0.25, 0.5, 0.75, 0.95)):
+        """The per-option outcomes of the options of `success_probability_by_glide_paths` (same arguments and validation) over
+        their shared paths, from the glide outcomes probe (``mcr_probe_glide_paths_outcomes_rng``): an
+        `outcomes.OptionOutcomes` whose ``.probabilities`` equal that method's array bit for bit."""
+        return self._option_probe("outcomes", "glide_paths", working_months, glide_paths, num_simulations, quantiles=quantiles)
+
+    def compare_glide_paths(self, working_months: int, options: Optional[Sequence] = None, paired: bool = False,
+                            outcomes: bool = False, num_simulations: Optional[int] = None) -> dict:
+        """How the split should change with age: `success_probability_by_glide_paths` of ``options`` (default:
+        `allocation.default_glide_paths` for ``working_months`` -- the config's own constant split, all and none of asset 1, two
+        declining target-date shapes and one rising-equity shape) as ``{"options": [{"name", the three amounts, "weights",
+        "probability"}, ...], "best": index}``, ``best`` being the option with the highest probability (the first of equals).
+        ``paired=True`` and ``outcomes=True`` add what they add to `compare_allocations`, and they compose."""
+        from .allocation import SCENARIO_FIELDS, default_glide_paths, glide_paths_of, glide_records
+
+        options = list(default_glide_paths(self.params_model, int(working_months)) if options is None else options)
+        records, _ = glide_records(self.params_model, options)
+        paths = glide_paths_of(options)
+        joint = self.joint_outcomes_by_glide_paths(working_months, options, num_simulations) if paired else None
+        per_option = self.option_outcomes_by_glide_paths(working_months, options, num_simulations) if outcomes else None
+        probs = (joint.probabilities if paired else per_option.probabilities if outcomes else
+                 self.success_probability_by_glide_paths(working_months, options, num_simulations))
+        rows = [dict(name=g.describe(), **dict(zip(SCENARIO_FIELDS, r[:3])), weights=list(g.weights), probability=float(pr))
+                for g, r, pr in zip(paths, records, probs)]
+        return self._best_option_document({}, rows, joint, per_option)
 
     # ---- income-stream options and the required-income search ------------------------------------------
     def success_probability_by_income_options(self, working_months: int, stream, options: Sequence[dict],
