@@ -29,6 +29,7 @@ switch to the final seed stream, run the final batch, print the response documen
     python examples/run_scenario.py scenarios/config.json --working-months 240 --allocations 0,0.2,0.4,0.6,0.8,1 [--paired] [--outcomes]
     python examples/run_scenario.py scenarios/config.json --working-months 240 --best-allocation [--allocation-resolution 0.01]
     python examples/run_scenario.py scenarios/config.json --working-months 240 --glide-paths "0.9>0.4@0-20;0.6;0.3>0.6@20-35" [--paired] [--outcomes]
+    python examples/run_scenario.py scenarios/config.json --working-months 240 --glide-path "0.9>0.4@0-20" --streamed
 
 `--rng numpy` uses the reference's own NumPy stream (same seed -> the reference's numbers); `--rng philox`
 (default) the engine's counter-based stream.  `--history FILE.csv` asks every question of a recorded market instead: months
@@ -87,7 +88,11 @@ that changes with the calendar (a table of `allocation_inv1_pct` by whole years 
 `{options: [{name, the three amounts, weights, probability}], best}`.  A path is a constant (`0.6`) or `start>end@from-to`
 (`start` until year `from`, a straight line to `end` in year `to`, `end` after it).  With no value it compares a small
 catalogue built for `--working-months`: the config's own constant split, all and none of asset 1, two declining target-date
-shapes and one rising-equity shape.  `--paired` and `--outcomes` add what they add to the allocation table.  Engine stream only."""
+shapes and one rising-equity shape.  `--paired` and `--outcomes` add what they add to the allocation table.  Engine stream only.
+`--glide-path P --streamed` (with `--working-months`) prints the streamed document of ONE glide path, from yearly bins taken
+inside the path kernel under it: the fan charts, the start balance, the final balances of the paths that succeed, and
+`glide_path` / `allocation_by_sample` (the split at each yearly sample).  Engine stream only; not together with
+`--spending-rule`, `--history` or `--glide-paths`."""
 
 from __future__ import annotations
 
@@ -177,7 +182,32 @@ def main() -> int:
     ap.add_argument("--glide-paths", nargs="?", const="", default=None, metavar="P;P;...",
                     help="glide paths compared over the same paths at --working-months: each a constant split or start>end@from-to "
                          "(years from today), separated by ';'; with no value a default catalogue; composes with --paired and --outcomes")
+    ap.add_argument("--glide-path", default=None, metavar="P",
+                    help="ONE glide path (a constant split or start>end@from-to) held by every path of the --streamed document at "
+                         "--working-months")
     args = ap.parse_args()
+    if args.glide_path is not None:
+        from monte_carlo_retirement_amd.allocation import GlidePath
+
+        if args.working_months is None:
+            ap.error("--glide-path needs --working-months")
+        if args.glide_paths is not None:
+            ap.error("--glide-path (one path's document) and --glide-paths (a comparison) are separate questions")
+        if args.spending_rule is not None:
+            ap.error("--glide-path and --spending-rule together are not supported")
+        if args.rng != "philox" or args.history:
+            ap.error("--glide-path runs on the engine's own stream (not with --history or --rng numpy)")
+        if not args.streamed:
+            ap.error("--glide-path goes with --streamed")
+        if (args.allocations is not None or args.best_allocation or args.min_initial_balance or args.min_contribution or args.max_expenses
+                or args.income_options is not None or args.min_income is not None or args.compare_rules is not None
+                or args.stress or args.breakeven or args.cohorts or args.frontier or args.grid_months
+                or args.grid_expenses or args.earliest_retirement or args.compact):
+            ap.error("--glide-path and the other questions are separate")
+        try:
+            args.glide_path = GlidePath.parse(args.glide_path)
+        except ValueError as e:
+            ap.error(f"--glide-path: {e}")
     if args.glide_paths is not None:
         from monte_carlo_retirement_amd.allocation import GlidePath
 
@@ -326,6 +356,8 @@ def main() -> int:
         return cohorts(args, config, world, rank0)
     if glide_table:
         return glide_table_document(args, config, world, rank0)
+    if args.glide_path is not None:
+        return glide_path_document(args, config, world, rank0)
     if args.allocations is not None:
         return allocation_table(args, config, world, rank0)
     if args.best_allocation:
@@ -469,6 +501,25 @@ def spending_rule(args, config: Config, world: int, rank0: bool) -> int:
         dist.barrier()
         dist.destroy_process_group()
     return 0
+
+
+def glide_path_document(args, config: Config, world: int, rank0: bool) -> int:
+    """The streamed document of ONE glide path at --working-months: yearly bins under the path, no per-path memory."""
+    sim = _simulator(args, config)
+    sim.use_final_seeds()
+    rc = 0
+    try:
+        doc = R.streamed_result(config, sim, int(args.working_months), glide_path=args.glide_path)
+    except (ValueError, RuntimeError) as e:      # (RuntimeError: a shape the glide launch does not support, in the library's words)
+        doc, rc = {"error": str(e)}, 1
+    if rank0:
+        print(json.dumps(doc))
+    if world > 1:
+        import torch.distributed as dist
+
+        dist.barrier()
+        dist.destroy_process_group()
+    return rc
 
 
 def earliest_retirement(args, config: Config, world: int, rank0: bool) -> int:

@@ -883,8 +883,8 @@ int mcr_probe_allocations_last_fanout_launches(void);
  * >= 0, options[k].n_weights >= 1, options[k].first_weight >= 0 and first_weight + n_weights within the table, and every weight
  * an option names finite and in [0, 1]; on any error every output stays untouched and the message names options[k].<field> (a
  * weight: options[k].weights[i]).
- * There is NO plain launch under a glide path, so every option, a single one included, runs in GLIDE FAN-OUT launches: the
- * allocation fan-out's workgroup in which each of up to MCR_MAX_EXPENSE_FANOUT consumer waves carries its own table and reloads
+ * The probes run every option, a single one included, in GLIDE FAN-OUT launches (the whole-path launches further down take ONE
+ * table; the probes never route through them): the allocation fan-out's workgroup in which each of up to MCR_MAX_EXPENSE_FANOUT consumer waves carries its own table and reloads
  * its weight once a calendar year with one scalar load.  The records, with the weights behind them, are ONE stream-ordered
  * device table, released behind the launches.  The shapes the fan-out does not cover have no per-option route here and return
  * MCR_ERR_UNSUPPORTED, every output untouched, with a message that says which: the NumPy stream, the history stream, stream
@@ -897,7 +897,31 @@ int mcr_probe_allocations_last_fanout_launches(void);
  * rows->path_stride < n_paths, are checked first); elements of a row at or beyond n_paths are never written.
  * mcr_probe_glide_paths_last_fanout_launches reports, for the calling thread's last call, how many glide fan-out launches it
  * enqueued: ceil(n_options / options per launch), 0 after an error.
- * Not offered under a glide path: full-output (summary, trajectory) and yearly-bins launches.
+ * The probes return counts, ballots and outcome rows only; the summary columns and the yearly tables of ONE glide path come from
+ * the whole-path launches below.
+ *
+ * Glide whole-path launches: ONE glide path over a path range, as a plain launch of the engine's own stream (every wave of the
+ * launch stands in the same row, so the weight in force is launch-uniform and its yearly reload one scalar load).  `weights` is a
+ * HOST array of n_weights >= 1 doubles, the table W; the launch keeps it in a small stream-ordered device block, released behind
+ * the kernel.  *p's allocation_inv1_pct is not read on the path (derived values that do not depend on it are).
+ *   mcr_run_glide_rng: `out` follows mcr_run_rule_rng's contract -- DEVICE counters, wr_obs_counts, ruin_year_bins (accumulated
+ *     into) and any of the per-path summary columns; count-only without a summary column, a summary launch with any of them.
+ *   mcr_run_glide_year_bins_rng / _host_rng: mcr_run_year_bins_rng / _host_rng exactly -- the cell convention, tables accumulated
+ *     into, any table NULL, DEVICE pointers in the first and HOST pointers (edges checked) in the second, which runs on one device.
+ * Everything is validated on the host before a device is looked for: *p and the month, the stream descriptor, n_weights >= 1,
+ * every weight finite and in [0, 1] (the message names weights[i]), and in the yearly-bins forms whatever mcr_run_year_bins_rng
+ * checks of `out` / `yb`.  On any error every output is untouched.  MCR_ERR_UNSUPPORTED, by name and with nothing computed
+ * ("glide path: ... is not supported"): trajectory pointers, hist_bins, the NumPy and the history stream, stream lists longer than
+ * MCR_INLINE_STREAMS or lock slots beyond LDS (the generic variant), the exact month.  (A yearly-bins launch keeps the lock
+ * columns of frozen income streams beside its tables in the workgroup's LDS and gives up resident workgroups where the plain
+ * launch would take its generic form; only columns beyond the workgroup's 64 KB are refused.)  A table whose every entry
+ * equals *p's allocation_inv1_pct gives mcr_run_batch_rng's / mcr_run_year_bins_rng's results for *p bit for bit (a one-entry table
+ * of another value a gives them for *p with allocation_inv1_pct = a); any table
+ * gives, path for path, what the glide probes report for the same option.  Asynchronous like mcr_run_batch_rng (the host form
+ * returns with its tables filled).
+ * Not offered under a glide path: trajectories, a spending rule together with a glide path, time-sliced, split and screened
+ * forms, the NumPy and history streams, and a retirement-month grid or any search (the probes' records carry their own three
+ * amounts for that).
  */
 typedef struct mcr_glide_option {
     double initial_balance, monthly_contribution, monthly_expenses;   /* as mcr_scenario */
@@ -916,6 +940,14 @@ int mcr_probe_glide_paths_outcomes_rng(const mcr_params* p, const mcr_rng* rng, 
                                        const mcr_glide_option* options, int32_t n_options, uint64_t* counts,
                                        const mcr_option_outcomes* rows, int device, void* hip_stream);
 int mcr_probe_glide_paths_last_fanout_launches(void);
+int mcr_run_glide_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                      int32_t working_months, const double* weights, int32_t n_weights, mcr_outputs* out, int device, void* hip_stream);
+int mcr_run_glide_year_bins_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                                int32_t working_months, const double* weights, int32_t n_weights, const mcr_outputs* out,
+                                const mcr_year_bins* yb, int device, void* hip_stream);
+int mcr_run_glide_year_bins_host_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                                     int32_t working_months, const double* weights, int32_t n_weights, const mcr_outputs* out,
+                                     const mcr_year_bins* yb, int device);
 
 /* _draw_shock_path (simulation.py:452-466) for n_paths paths: host out [n_paths][n_months][3]. */
 int mcr_draw_shocks_host(uint64_t seed, uint32_t stream_id, uint64_t path_begin,

@@ -464,6 +464,9 @@ ABI_SYMBOLS = (
     "mcr_probe_glide_paths_joint_rng",
     "mcr_probe_glide_paths_outcomes_rng",
     "mcr_probe_glide_paths_last_fanout_launches",
+    "mcr_run_glide_rng",
+    "mcr_run_glide_year_bins_rng",
+    "mcr_run_glide_year_bins_host_rng",
     "mcr_release_cached",
     "mcr_sample_columns",
     "mcr_eval_helper_host",
@@ -677,6 +680,14 @@ def _declare(lib: C.CDLL) -> None:
         lib.mcr_probe_glide_paths_outcomes_rng.argtypes = head + [P(McrOptionOutcomes), C.c_int, C.c_void_p]
         lib.mcr_probe_glide_paths_last_fanout_launches.restype = C.c_int
         lib.mcr_probe_glide_paths_last_fanout_launches.argtypes = []
+    if hasattr(lib, "mcr_run_glide_rng"):   # (likewise)
+        head = [P(McrParams), P(McrRng), C.c_uint32, C.c_uint64, C.c_uint64, C.c_int32, P(C.c_double), C.c_int32, P(McrOutputs)]   # ..., weights, n_weights, out
+        lib.mcr_run_glide_rng.restype = C.c_int
+        lib.mcr_run_glide_rng.argtypes = head + [C.c_int, C.c_void_p]
+        lib.mcr_run_glide_year_bins_rng.restype = C.c_int
+        lib.mcr_run_glide_year_bins_rng.argtypes = head + [P(McrYearBins), C.c_int, C.c_void_p]
+        lib.mcr_run_glide_year_bins_host_rng.restype = C.c_int
+        lib.mcr_run_glide_year_bins_host_rng.argtypes = head + [P(McrYearBins), C.c_int]
     if hasattr(lib, "mcr_probe_rule_grid_rng"):   # (likewise)
         lib.mcr_probe_rule_grid_rng.restype = C.c_int
         lib.mcr_probe_rule_grid_rng.argtypes = [

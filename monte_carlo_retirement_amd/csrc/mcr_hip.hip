@@ -561,7 +561,7 @@ __device__ __forceinline__ void income_put(DevStream& S, const IncomeRegs& R) {
     S.amount = R.amount; S.amount_keep = R.amount_keep; S.start_month = R.start_month; S.end_month = R.end_month;
 }
 
-template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault, int GF = 0, int MF = 0, int SF = 0, bool OUT = false, bool LIST = false, int NPROD = 1, bool RULE = false>
+template <int MODE, int RNG, int TAXED, bool ANNUAL, bool INJ = false, int PHASE = 0, bool SPLIT = false, bool XS = false, bool EXACT = kExactMonthDefault, int GF = 0, int MF = 0, int SF = 0, bool OUT = false, bool LIST = false, int NPROD = 1, bool RULE = false, bool GLIDE = false>
 __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE == 8 || PHASE == 9 || PHASE == 10 || PHASE == 11 || PHASE == 12 || PHASE == 13) ? 64 * (MCR_MAX_EXPENSE_FANOUT + 1) : NPROD == 2 ? 3 * 64 : SPLIT ? 2 * kBlock : kBlock, SPLIT ? 4 : (MODE == 0 && RNG == 0 && (PHASE == 0 || PHASE == 3 || PHASE == 4)) ? 6 : ((MODE == 1 || MODE == 2) && RNG == 0 && !INJ) ? 5 : 4) void path_kernel(const DevParams P_arg, const KernelIO io,
                                                          const DevParams* __restrict__ cand_params) {
     // MODE 3 (mcr_run_year_bins_rng): YEARLY BINS.  The arithmetic of MODE 2, but wherever that variant stores a yearly sample
@@ -625,6 +625,17 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     static_assert(!RULE || (RNG == (int)MCR_RNG_PHILOX && TAXED == 3 && !INJ && !XS && EXACT == kExactMonthDefault && GF == 0 && MF == 0 && SF == 0 && !LIST && NPROD == 1 &&
                             (((MODE == 0 || MODE == 1 || MODE == 3) && PHASE == 0 && !SPLIT && !OUT) || (MODE == 0 && PHASE == 11 && SPLIT) || (MODE == 0 && PHASE == 6 && SPLIT && !OUT))),
                   "the spending rule exists for the plain whole-path Philox launches, count-only, summary and yearly bins, and for the rule and the rule grid fan-outs, on the generic tax mask");
+    // GLIDE (mcr_run_glide_rng, mcr_run_glide_year_bins_rng; include/mcr.h: GLIDE PATH): the plain whole-path launch whose split
+    // between the assets follows a table W[0 .. n - 1] by calendar year.  Every wave of a launch stands in the same row, so the
+    // weight in force is launch-uniform: PHASE 13's statement (WaveGlideParams, glide_row) with ONE record for the whole launch,
+    // behind `cand_params`, which is otherwise null on a whole-path launch (MODE 3 with RULE reads its one record the same way).
+    // Every read of a weight on the path is the row's: the initial split, the contribution split, the rebalance, the dust
+    // sub-case, the annual tax with its closing rebalance, and the terminal settlement on the last row's.  A wave that leaves the
+    // year loop because all its lanes have failed never reads the weight again (the pad loop bins zeros; the settlement runs for
+    // lanes that succeeded).  Last, with a default, like RULE: every other instantiation keeps its instruction stream.
+    static_assert(!GLIDE || (RNG == (int)MCR_RNG_PHILOX && TAXED == 3 && !INJ && !XS && EXACT == kExactMonthDefault && GF == 0 && MF == 0 && SF == 0 && !LIST && NPROD == 1 &&
+                             !RULE && !OUT && (MODE == 0 || MODE == 1 || MODE == 3) && PHASE == 0 && !SPLIT),
+                  "the glide path exists for the plain whole-path Philox launches, count-only, summary and yearly bins, on the generic tax mask");
     // PHASE 4 = PHASE 2 (a candidate's decumulation resumed from its accumulation snapshot) time-sliced like PHASE 3: the
     // 17-month verification window of the search is 17 x 196 workgroups = 2.17 rounds of the resident slots.
     constexpr bool kExpFan = PHASE == 5 || PHASE == 6;    // expense fan-out: the levels are monthly_expenses, resumed at retirement
@@ -635,6 +646,8 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     constexpr bool kRuleFan = PHASE == 11;                // rule fan-out: the scenario fan-out with a spending rule per wave as well
     constexpr bool kGldFan = PHASE == 13;                 // glide fan-out: the allocation fan-out whose wave reloads its split once a calendar year from its own table
     constexpr bool kAlcFan = PHASE == 12 || kGldFan;      // allocation fan-out: the scenario fan-out with the split between the assets per wave as well
+    constexpr bool kGlide = kGldFan || GLIDE;             // the weight in force is reloaded once a calendar year (glide_row): the glide fan-out's consumer wave, or a GLIDE launch
+    constexpr bool kOwnAlloc = kAlcFan || GLIDE;          // the month reads the weight of WA, not the block's
     constexpr bool kScnFan = PHASE == 8 || kAsmFan || kIncFan || kRuleFan || kAlcFan;   // scenario fan-out: balance, contribution and spending per wave, the whole path
     constexpr bool kFan = kExpFan || kConFan || kScnFan;  // fan-out workgroup: one 64-path block, L consumer waves (levels), one producer wave
     constexpr bool kGrid = PHASE == 6;                    // ... of grid row blockIdx.y (GridCell)
@@ -657,7 +670,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     [[maybe_unused]] std::conditional_t<OUT, RuinMonth, NoRuinMonth> RM;         // (likewise: the outcome probes' month of failure)
     [[maybe_unused]] std::conditional_t<RULE, RuleState, NoRuleState> RS;        // (likewise: the spending rule's multiplier)
     [[maybe_unused]] std::conditional_t<kWaveRule, FanRule, NoFanRule> FR;       // (likewise: PHASE 11 and PHASE 6 with RULE, the consumer wave's own rule)
-    [[maybe_unused]] std::conditional_t<kGldFan, WaveGlideParams, std::conditional_t<kAlcFan, WaveAllocParams, NoWaveAlloc>> WA;   // (likewise: PHASE 12 / 13, the consumer wave's own weights, mcr_device.h)
+    [[maybe_unused]] std::conditional_t<kGlide, WaveGlideParams, std::conditional_t<kAlcFan, WaveAllocParams, NoWaveAlloc>> WA;   // (likewise: PHASE 12 / 13, the consumer wave's own weights, mcr_device.h; GLIDE: the launch's)
     static_assert(!kSliced || (RNG == 0 && !INJ && !SPLIT && !XS), "time-sliced blocks exist for the plain Philox variants");
     static_assert(PHASE != 4 || MODE == 0, "the search probes count only");
     // TAXED: which assets carry an effective realized-gains rate (bit 0: inv1, bit 1: inv2; DevParams::tax_mask)
@@ -932,8 +945,9 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     // PHASE 13: the record names the wave's table instead, GlideRecord::weights doubles behind the record itself (probe_glide_paths_fanout:
     // the host's offset, so that a group's launch, which gets the table at ITS first record, reads its own weights); W[0] is in
     // force from row 0, `left` = n - 1 entries stand behind it.
-    if constexpr (kGldFan) {
-        const GlideRecord* const rec = reinterpret_cast<const GlideRecord*>(cand_params) + (producer ? 0 : fan_j);
+    // GLIDE: the launch's one record (launch_glide: the weights stand directly behind it), the same statements.
+    if constexpr (kGlide) {
+        const GlideRecord* const rec = reinterpret_cast<const GlideRecord*>(cand_params) + ((GLIDE || producer) ? 0 : fan_j);
         WA.w = (GlideTable)(reinterpret_cast<const double*>(rec) + rec->weights);
         WA.left = rec->n_weights - 1;
         WA.moy = 0;
@@ -947,17 +961,17 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         WA.alloc2 = 1.0 - WA.alloc1;
         WA.annual_rate1 = P.annual_rate1; WA.annual_rate2 = P.annual_rate2; WA.any_annual_tax = P.any_annual_tax;
     }
-    std::conditional_t<kGldFan, LaneParams, const LaneParams> L = month_lane_params<TOL, EQR>(WA, P);    // (mutable in PHASE 13 only)
+    std::conditional_t<kGlide, LaneParams, const LaneParams> L = month_lane_params<TOL, EQR>(WA, P);    // (mutable in PHASE 13 and under GLIDE only)
     // PHASE 13, at the top of every row t (wave-uniform, outside every lane mask): where t % 12 == 0, t > 0 -- a calendar year
     // from today has closed, which is NOT a retirement-year boundary unless working_months % 12 == 0 -- the weight in force
     // becomes W[min(t / 12, n - 1)]: one scalar load unless the table is exhausted, then derive_params' subtraction and the two
     // products of month_lane_params again.  The row's every read of a weight, its annual tax and closing rebalance included,
     // comes behind this.  A scalar counter of its own: the variants without the annual-gains tax have no year-close branch.
     // Lanes that have failed run no month and read none of it.  glide_row (mcr_device.h) is the statement; its two calls below
-    // stand under `if constexpr (kGldFan)`, which every other instantiation discards.
+    // stand under `if constexpr (kGlide)`, which every other instantiation discards.
 
     // ---- initial state (:490-510) ----
-    double b1 = P.initial_balance * P.alloc1;  // :499
+    double b1 = P.initial_balance * (GLIDE ? WA.alloc1 : P.alloc1);  // :499 (GLIDE: W[0])
     double b2 = P.initial_balance - b1;        // :500
     double c1 = b1, c2 = b2;                   // :501-502
     double contrib = P.monthly_contribution;   // :504
@@ -1163,7 +1177,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
     // (kScalarCounters: moy = m mod 12 in 1 .. 12, a running month of the year instead of the two % kMPY tests)
     for (int m = 1; m <= ((kPairs || kCand || (kSliced && seg_resumed)) ? 0 : wm); ++m) {    // (kPairs: in pairs, below)
         if constexpr (kScalarCounters) ++SC.moy;
-        if constexpr (kGldFan) glide_row<TOL, EQR>(WA, P, L);          // (PHASE 13: row m - 1's weight)
+        if constexpr (kGlide) glide_row<TOL, EQR>(WA, P, L);           // (PHASE 13, GLIDE: row m - 1's weight)
         if (P.contrib_grows && year_opens(SC, m - 1) && m > 1) {  // :514-517 (wave-uniform: a scalar branch, not a select)
             asm volatile("");
             contrib *= P.contrib_growth_factor;
@@ -1172,7 +1186,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         double g1, ginf, g2;
         growth(m - 1, g1, ginf, g2);                                   // :519-532
         market_step<ANNUAL, TOL>(g1, ginf, g2, b1, b2, gacc1, gacc2, infl); // :534-538
-        const double k1 = contrib * (kAlcFan ? WA.alloc1 : P.alloc1);   // :540-542
+        const double k1 = contrib * (kOwnAlloc ? WA.alloc1 : P.alloc1);   // :540-542
         const double k2 = contrib - k1;                                // :543
         b1 += k1; c1 += k1; b2 += k2; c2 += k2;                        // :544-547
         if (TOL) month_rebalance_tol<TANY, MM, kFastMonth, EQR>(WA, P, L, b1, c1, b2, c2);  // :549-553
@@ -1321,7 +1335,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
             double g1, ginf, g2;
             factors(half, g1, ginf, g2);
             market_step<ANNUAL, TOL>(g1, ginf, g2, b1, b2, gacc1, gacc2, infl); // :534-538
-            const double k1 = contrib * (kAlcFan ? WA.alloc1 : P.alloc1);   // :540-542
+            const double k1 = contrib * (kOwnAlloc ? WA.alloc1 : P.alloc1);   // :540-542
             const double k2 = contrib - k1;                                // :543
             b1 += k1; c1 += k1; b2 += k2; c2 += k2;                        // :544-547
             month_rebalance_tol<TANY, MM, kFastMonth, EQR, kSel>(WA, P, L, b1, c1, b2, c2);  // :549-553
@@ -1365,7 +1379,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
                             double cap1, cap2, gw1, nw1, gw2, nw2;
                             net_liquidation_values2<T1, T2, MM>(b1, c1, L.real_rate1, b2, c2, L.real_rate2, cap1, cap2);
                             const double xcap = cap1 + cap2, xtarget = fmin(need, xcap);
-                            const double prop1 = xcap > kEps ? fdiv<false>(cap1, xcap) : (kAlcFan ? WA.alloc1 : P.alloc1);
+                            const double prop1 = xcap > kEps ? fdiv<false>(cap1, xcap) : (kOwnAlloc ? WA.alloc1 : P.alloc1);
                             withdraw2<T1, T2, MM>(b1, c1, xtarget * prop1, L.real_rate1, gw1, nw1,
                                                   b2, c2, xtarget * (1.0 - prop1), L.real_rate2, gw2, nw2);
                             fail = need > kEps && (xtarget < need - kEps || nw1 + nw2 < need - kEps);
@@ -1437,7 +1451,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
         int fail_rmi = 0;
         for (int mi = 0; mi < kMPY; ++mi) {
             const int rmi = year * kMPY + mi;  // :641-643
-            if constexpr (kGldFan) glide_row<TOL, EQR>(WA, P, L);      // (PHASE 13: row wm + rmi's weight)
+            if constexpr (kGlide) glide_row<TOL, EQR>(WA, P, L);       // (PHASE 13, GLIDE: row wm + rmi's weight)
             begin_month(month_row(SC, wm + rmi));
             if (alive && !yfail) {
                 double g1, ginf, g2;
@@ -1521,7 +1535,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
                             double cap1, cap2, gw1, nw1, gw2, nw2;
                             net_liquidation_values2<T1, T2, MM>(b1, c1, L.real_rate1, b2, c2, L.real_rate2, cap1, cap2);
                             const double xcap = cap1 + cap2, xtarget = fmin(need, xcap);
-                            const double prop1 = xcap > kEps ? fdiv<false>(cap1, xcap) : (kAlcFan ? WA.alloc1 : P.alloc1);
+                            const double prop1 = xcap > kEps ? fdiv<false>(cap1, xcap) : (kOwnAlloc ? WA.alloc1 : P.alloc1);
                             withdraw2<T1, T2, MM>(b1, c1, xtarget * prop1, L.real_rate1, gw1, nw1,
                                                   b2, c2, xtarget * (1.0 - prop1), L.real_rate2, gw2, nw2);
                             fail = need > kEps && (xtarget < need - kEps || nw1 + nw2 < need - kEps);
@@ -1575,7 +1589,7 @@ __global__ __launch_bounds__((PHASE == 5 || PHASE == 6 || PHASE == 7 || PHASE ==
                     const double target = fmin(need, cap);                            // :739-742 (need, cap >= 0: the max(0, .) is a no-op)
                     if (need > kEps && target < need - kEps) yfail = true;            // :743-748 (FAIL-3)
                     double prop1 = fdiv<false>(cap1, cap);                            // :750-754
-                    if (!(cap > kEps)) { MCR_MASKED_MOVE; prop1 = kAlcFan ? WA.alloc1 : P.alloc1; }   // (exec-masked move, not a select)
+                    if (!(cap > kEps)) { MCR_MASKED_MOVE; prop1 = kOwnAlloc ? WA.alloc1 : P.alloc1; }   // (exec-masked move, not a select)
                     const double prop2 = 1.0 - prop1;                                 // :755
                     double gw1, nw1, gw2, nw2;
                     withdraw2<T1, T2, MM>(b1, c1, target * prop1, L.real_rate1, gw1, nw1,  // :757-765
@@ -2679,7 +2693,8 @@ static size_t year_bins_lds(int n_bins, int n_wr_bins) {
 // what is left of the budget of THAT number of workgroups, not of four.
 constexpr size_t kLdsPerCu = 160 * 1024;
 static int plan_path_kernel_lds(DevParams& d, int mode, uint32_t rng_kind, bool injected, bool split, int n_hist_bins, size_t* dynamic_bytes,
-                                size_t year_bins_bytes = 0, uint32_t history_months = 0) {
+                                size_t year_bins_bytes = 0, uint32_t history_months = 0,
+                                bool whole_workgroup = false /* a launch with no generic form behind it: lock columns up to the workgroup's own LDS, at the price of resident workgroups */) {
     const size_t table_bytes = injected ? (size_t)0 : rng_kind == MCR_RNG_NUMPY ? (size_t)kZigLdsBytes
                                : rng_kind == MCR_RNG_HISTORY ? (size_t)history_months * 3u * sizeof(double) : (size_t)0;
     size_t fixed = path_kernel_static_lds(mode, rng_kind, injected, split) + table_bytes +
@@ -2688,7 +2703,7 @@ static int plan_path_kernel_lds(DevParams& d, int mode, uint32_t rng_kind, bool 
     if (fixed > kLdsPerWorkgroup) { set_error("too many retirement years / histogram bins for the LDS of a workgroup"); return MCR_ERR_UNSUPPORTED; }
     constexpr size_t kSlotBytes = (size_t)kBlock * sizeof(double);
     long slots = (long)((kLdsPerWorkgroup - fixed) / kSlotBytes);
-    size_t budget = kLdsForFourResident;
+    size_t budget = whole_workgroup ? kLdsPerWorkgroup : kLdsForFourResident;
     if (rng_kind == MCR_RNG_HISTORY && !injected && fixed >= kLdsForFourResident) budget = std::min(kLdsPerWorkgroup, kLdsPerCu / (kLdsPerCu / fixed));
     const char* e = std::getenv("MCR_K1_LDS_LOCK_SLOTS");
     if (e && *e) slots = std::min(slots, std::max(0l, std::strtol(e, nullptr, 10)));
@@ -4984,6 +4999,17 @@ int mcr_probe_allocations_last_fanout_launches(void) { return g_last_allocation_
 // ---- glide probes (PHASE 13; include/mcr.h: GLIDE PATH) ----
 // What the glide probes check on the host, before a device is looked for: the block, the month, the stream, every option and
 // every weight an option names
+// One table's entries: finite and in [0, 1].  `owner` heads the field's name ("options[2]." for a probe's record, "" for a launch's own table).
+static bool glide_weights_valid(const char* owner, const double* w, int32_t n) {
+    for (int32_t i = 0; i < n; ++i) {
+        const double a = w[i];
+        if (!(std::isfinite(a) && a >= 0.0 && a <= 1.0)) {
+            set_error("%sweights[%d] = %.17g: must be finite and in [0, 1] (config.py:70)", owner, i, a);
+            return false;
+        }
+    }
+    return true;
+}
 static int check_glide_probe(const mcr_params* p, const mcr_rng* rng, int32_t working_months, const double* weights, int32_t n_weights,
                              const mcr_glide_option* options, int32_t n_options, const uint64_t* counts) {
     if (n_options < 0) { set_error("n_options %d must be >= 0", n_options); return MCR_ERR_INVALID_ARG; }
@@ -5001,13 +5027,9 @@ static int check_glide_probe(const mcr_params* p, const mcr_rng* rng, int32_t wo
             set_error("options[%d].first_weight = %d with n_weights = %d: outside the table of %d weights", k, o.first_weight, o.n_weights, n_weights);
             return MCR_ERR_INVALID_ARG;
         }
-        for (int32_t i = 0; i < o.n_weights; ++i) {
-            const double a = weights[(size_t)o.first_weight + (size_t)i];
-            if (!(std::isfinite(a) && a >= 0.0 && a <= 1.0)) {
-                set_error("options[%d].weights[%d] = %.17g: must be finite and in [0, 1] (config.py:70)", k, i, a);
-                return MCR_ERR_INVALID_ARG;
-            }
-        }
+        char owner[32];
+        std::snprintf(owner, sizeof owner, "options[%d].", k);
+        if (!glide_weights_valid(owner, weights + (size_t)o.first_weight, o.n_weights)) return MCR_ERR_INVALID_ARG;
     }
     return MCR_OK;
 }
@@ -5553,6 +5575,144 @@ int mcr_run_rule_year_bins_host_rng(const mcr_params* p, const mcr_rng* rng, uin
     if ((rc = call.begin(device, "device allocation (rule yearly bins)")) != MCR_OK) return rc;
     rc = launch_rule_year_bins(p, rng, stream_id, path_begin, n_paths, working_months, rule, &d.o, &d.y, &dr, call.stream());
     return call.finish(rc, true, "path_kernel execution (rule yearly bins)");
+}
+
+// ---- glide whole-path launches (GLIDE of path_kernel; include/mcr.h: GLIDE PATH) -------------------------------------------
+// One table for the whole launch: path_kernel<MODE 0 | 1 | 3, Philox, mask 3, annual-gains tax or not, ..., GLIDE>, six
+// instantiations.  Everything is checked on the host before a device is looked for, and everything else a caller can ask for
+// is refused by name (launch_rule's list, through refuse_rule_shapes).  `yb` null: a count-only or summary launch, whose `out`
+// follows mcr_run_rule_rng's contract; otherwise a yearly-bins launch under check_year_bins' rules.  On success the parameter
+// block and the launch's dynamic LDS are planned.
+static int plan_glide_run(const mcr_params* p, const mcr_rng* rng, uint64_t path_begin, uint64_t n_paths, int32_t wm, const double* weights,
+                          int32_t n_weights, const mcr_outputs* out, const mcr_year_bins* yb, bool host_edges, DevParams* d_out, int* mode_out, size_t* lds) {
+    DevParams d;
+    std::vector<DevStream> extra;
+    int rc = derive_params(p, wm, &d, &extra);
+    if (rc != MCR_OK) return rc;
+    if ((rc = check_rng(rng, host_edges)) != MCR_OK) return rc;
+    if (!weights) { set_error("glide path: null weights"); return MCR_ERR_INVALID_ARG; }
+    if (n_weights < 1) { set_error("glide path: n_weights = %d: a glide path has at least one entry", n_weights); return MCR_ERR_INVALID_ARG; }
+    if (!glide_weights_valid("", weights, n_weights)) return MCR_ERR_INVALID_ARG;
+    if (!out) { set_error(yb ? "null outputs / year bins" : "null outputs"); return MCR_ERR_INVALID_ARG; }
+    if (out->trajectory || out->real_trajectory || out->withdrawal_rate_trajectory) {
+        set_error("glide path: trajectories are not supported (counters, per-path summary columns and yearly bins only)");
+        return MCR_ERR_UNSUPPORTED;
+    }
+    if (yb) {
+        if ((rc = check_year_bins(out, yb)) != MCR_OK) return rc;
+        if (host_edges && (rc = check_year_bins_edges_host(yb, nullptr, nullptr, 0)) != MCR_OK) return rc;
+    }
+    if (out->hist_bins && out->hist_n_bins != 0) { set_error("glide path: the in-kernel histogram (hist_bins) is not supported"); return MCR_ERR_UNSUPPORTED; }
+    const bool want_summary = out->start_balance || out->final_balance || out->years_to_ruin || out->first_year_gross_withdrawal ||
+                              out->first_year_real_gross_withdrawal || out->inflation_at_retirement || out->success;
+    const int mode = yb ? 3 : want_summary ? 1 : 0;
+    // (refuse_rule_shapes decides on a count-only or summary plan at the four-resident LDS budget: the rule of the MODE 0 / 1 launches,
+    //  and the stricter one where lock columns are concerned -- a yearly-bins launch, which plans again below and may take the whole
+    //  workgroup's LDS, is refused here first for a stream list that a count-only launch under the same table would be refused for)
+    if ((rc = refuse_rule_shapes("glide path", p, rng, path_begin, n_paths, d, mode == 1)) != MCR_OK) return rc;
+    const size_t bins_bytes = yb ? year_bins_lds(wants_balance_tables(yb) ? yb->n_bins : 0, yb->wr_bins ? yb->n_wr_bins : 0) : 0;
+    if ((rc = plan_path_kernel_lds(d, mode, MCR_RNG_PHILOX, false, false, 0, lds, bins_bytes)) != MCR_OK) return rc;
+    // THIS launch's plan, not refuse_rule_shapes': the edges and row buffers of a yearly-bins launch take LDS that a count-only plan
+    // leaves to the lock columns of frozen income streams.  The plain yearly-bins launch then takes its generic form; the glide
+    // kernels have none, and would write the columns that do not fit over the counters, edges and cells behind them.  So the
+    // launch gives up resident workgroups instead (columns up to the workgroup's own 64 KB), and what does not fit even then is
+    // refused by name.
+    if (d.n_lock_slots < d.n_lock_slots_total &&
+        (rc = plan_path_kernel_lds(d, mode, MCR_RNG_PHILOX, false, false, 0, lds, bins_bytes, 0, true)) != MCR_OK) return rc;
+    if (d.n_lock_slots < d.n_lock_slots_total) {
+        set_error("glide path: %d frozen income streams exceed the LDS budget beside the yearly tables and need the generic variant, which is not supported",
+                  (int)d.n_lock_slots_total);
+        return MCR_ERR_UNSUPPORTED;
+    }
+    *d_out = d;
+    *mode_out = mode;
+    return MCR_OK;
+}
+// The launch: device pointers in `out` / `yb`, the table a HOST array.  The record and the weights behind it are one
+// stream-ordered device block filled from the host and released behind the launch, like a fan-out's table; the record is
+// PHASE 13's (GlideRecord), so the kernel finds its table by the same statement.
+static int launch_glide(const DevParams& d, int mode, size_t lds, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                        const double* weights, int32_t n_weights, const mcr_outputs* out, const mcr_year_bins* yb, hipStream_t stream) {
+    if (n_paths == 0) return MCR_OK;
+    KernelIO io = make_io(rng, nullptr, stream_id, path_begin, n_paths);
+    io.out = *out;
+    io.out.hist_bins = nullptr; io.out.hist_edges = nullptr; io.out.hist_n_bins = 0;
+    if (yb) { io.out.path_stride = (int64_t)n_paths; fill_io_year_bins(io, yb); }
+    else if (io.out.path_stride <= 0) io.out.path_stride = (int64_t)n_paths;
+    constexpr size_t kRecDoubles = sizeof(GlideRecord) / sizeof(double);
+    // (pageable host memory: hipMemcpyAsync has staged it when it returns, as for the fan-outs' tables in SnapshotBlock::attach)
+    std::vector<double> host(kRecDoubles + (size_t)n_weights);
+    const GlideRecord rec = {d.initial_balance, d.monthly_contribution, d.monthly_expenses, (int32_t)kRecDoubles, n_weights};
+    std::memcpy(host.data(), &rec, sizeof rec);
+    std::memcpy(host.data() + kRecDoubles, weights, (size_t)n_weights * sizeof(double));
+    StreamAlloc table(stream);
+    if (!table.alloc(host.size() * sizeof(double))) { set_error("glide path: the device table's allocation was refused"); return MCR_ERR_HIP; }
+    hipError_t e = hipMemcpyAsync(table.p, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) {
+        const dim3 grid((unsigned)((n_paths + kBlock - 1) / kBlock)), block(kBlock);
+        for_bool(d.any_annual_tax, [&](auto A) {
+            auto go = [&](auto M) {
+                hipLaunchKernelGGL((path_kernel<decltype(M)::value, 0, 3, decltype(A)::value, false, 0, false, false, kExactMonthDefault, 0, 0, 0, false, false, 1, false, true>),
+                                   grid, block, lds, stream, d, io, (const DevParams*)table.p);
+            };
+            if (mode == 3) go(std::integral_constant<int, 3>{});
+            else if (mode == 1) go(std::integral_constant<int, 1>{});
+            else go(std::integral_constant<int, 0>{});
+        });
+        e = hipGetLastError();
+    }
+    const hipError_t ef = table.release();
+    if (e != hipSuccess) return hip_fail(e, "path_kernel launch (glide path)");
+    if (ef != hipSuccess) return hip_fail(ef, "path_kernel launch (glide path): table release");
+    return MCR_OK;
+}
+
+int mcr_run_glide_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                      int32_t working_months, const double* weights, int32_t n_weights, mcr_outputs* out, int device, void* hip_stream) {
+    DevParams d;
+    int mode = 0;
+    size_t lds = 0;
+    const int rc = plan_glide_run(p, rng, path_begin, n_paths, working_months, weights, n_weights, out, nullptr, false, &d, &mode, &lds);
+    if (rc != MCR_OK) return rc;
+    MCR_ENTER_DEVICE(device);
+    return launch_glide(d, mode, lds, rng, stream_id, path_begin, n_paths, weights, n_weights, out, nullptr, (hipStream_t)hip_stream);
+}
+
+int mcr_run_glide_year_bins_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                                int32_t working_months, const double* weights, int32_t n_weights, const mcr_outputs* out,
+                                const mcr_year_bins* yb, int device, void* hip_stream) {
+    DevParams d;
+    int mode = 0;
+    size_t lds = 0;
+    if (!yb) { set_error("null outputs / year bins"); return MCR_ERR_INVALID_ARG; }
+    const int rc = plan_glide_run(p, rng, path_begin, n_paths, working_months, weights, n_weights, out, yb, false, &d, &mode, &lds);
+    if (rc != MCR_OK) return rc;
+    MCR_ENTER_DEVICE(device);
+    return launch_glide(d, mode, lds, rng, stream_id, path_begin, n_paths, weights, n_weights, out, yb, (hipStream_t)hip_stream);
+}
+
+// HOST pointers, one device: run_year_bins_host_on's plan, the launch under the table
+int mcr_run_glide_year_bins_host_rng(const mcr_params* p, const mcr_rng* rng, uint32_t stream_id, uint64_t path_begin, uint64_t n_paths,
+                                     int32_t working_months, const double* weights, int32_t n_weights, const mcr_outputs* out,
+                                     const mcr_year_bins* yb, int device) {
+    mcr_sizes sz;
+    DevParams dp;
+    int mode = 0;
+    size_t lds = 0;
+    int rc;
+    if (!yb) { set_error("null outputs / year bins"); return MCR_ERR_INVALID_ARG; }
+    if ((rc = query_sizes(p, working_months, &sz)) != MCR_OK) return rc;
+    if ((rc = validate_params(p)) != MCR_OK) return rc;
+    if ((rc = plan_glide_run(p, rng, path_begin, n_paths, working_months, weights, n_weights, out, yb, true, &dp, &mode, &lds)) != MCR_OK) return rc;
+    MCR_ENTER_DEVICE(device);
+    if (n_paths == 0) return MCR_OK;
+    const YearBinsOut host = {*out, *yb};
+    YearBinsOut d = {};
+    HostCall call;
+    plan_year_bins(call, sz, host, &d);
+    if ((rc = call.begin(device, "device allocation (glide yearly bins)")) != MCR_OK) return rc;
+    rc = launch_glide(dp, mode, lds, rng, stream_id, path_begin, n_paths, weights, n_weights, &d.o, &d.y, call.stream());
+    return call.finish(rc, true, "path_kernel execution (glide yearly bins)");
 }
 
 int mcr_validate_params(const mcr_params* p) { return validate_params(p); }

@@ -280,7 +280,7 @@ def run_sharded_bands(params, rng_or_seed, stream_id: int, n_total: int, working
 
 
 def run_sharded_year_bins(params, rng_or_seed, stream_id: int, n_total: int, working_months: int, edges=None, wr_edges=None,
-                          rule=None, m_edges=None):
+                          rule=None, m_edges=None, glide_path=None):
     """The fan chart of ``n_total`` paths on N GPUs with no trajectory slab: every rank runs the yearly-bins kernel over its
     shard of the global path range (``engine.YearBinsBatch``; nothing is kept per path) and the exchange is ONE sum
     all-reduce of the integer vector ``[success, paths | wr_obs[ry] | ruin_bins[ry+2] | trajectory_bins[T][n+2] |
@@ -290,7 +290,10 @@ def run_sharded_year_bins(params, rng_or_seed, stream_id: int, n_total: int, wor
 
     ``rule`` (a `spending_rules.SpendingRule`): the paths spend under that guardrail (``mcr_run_rule_year_bins_rng``) and the
     vector ends ``... | rule_year_counts[ry][4] | multiplier_bins[ry][nm+2]]`` (binned on ``m_edges``, returned too): still ONE
-    sum all-reduce, of the longer vector."""
+    sum all-reduce, of the longer vector.
+
+    ``glide_path`` (what `engine.glide_table` takes): the paths hold that glide path (``mcr_run_glide_year_bins_rng``); the
+    vector, and so the ONE sum all-reduce, is the plain one.  A ``rule`` together with a ``glide_path`` is a ``ValueError``."""
     import torch
     import torch.distributed as dist
 
@@ -298,7 +301,8 @@ def run_sharded_year_bins(params, rng_or_seed, stream_id: int, n_total: int, wor
 
     rank, world = (dist.get_rank(), dist.get_world_size()) if is_active() else (0, 1)
     begin, count = shard_range(int(n_total), rank, world)
-    batch = E.YearBinsBatch(params, working_months, edges, wr_edges, device=torch.cuda.current_device(), rule=rule, m_edges=m_edges)
+    batch = E.YearBinsBatch(params, working_months, edges, wr_edges, device=torch.cuda.current_device(), rule=rule, m_edges=m_edges,
+                            glide_path=glide_path)
     if count > 0:
         batch.launch(rng_or_seed, stream_id, begin, count)
     vec = batch.reduce_vec

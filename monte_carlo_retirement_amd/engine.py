@@ -292,6 +292,16 @@ def eval_helper_host(which: int, params: Optional[McrParams], rows, device: int 
 # ---------------------------------------------------------------------------------------------
 # Yearly bins: the fan chart without a trajectory slab (mcr_run_year_bins_rng)
 # ---------------------------------------------------------------------------------------------
+def glide_table(glide_path):
+    """The table of a glide path as the ABI takes it, a ``c_double`` array: `glide_path` is a non-empty sequence of
+    ``allocation_inv1_pct`` values, one per whole year from today, or an object with such a ``weights`` attribute
+    (`allocation.GlidePath`).  The library checks the values."""
+    weights = tuple(float(w) for w in getattr(glide_path, "weights", glide_path))
+    if not weights:
+        raise ValueError("a glide path has at least one weight")
+    return (C.c_double * len(weights))(*weights)
+
+
 def year_edge_array(edges, what: str = "edges") -> np.ndarray:
     """Bin edges of a yearly-bins table as the contiguous float64 array the ABI wants; ``ValueError`` unless they are
     finite, ascending (equal neighbours allowed: zero-width bins) and 2..MCR_MAX_YEAR_BINS+1 long."""
@@ -365,11 +375,19 @@ class YearBinsBatch:
     ``rule`` (a `spending_rules.SpendingRule` or ``McrSpendingRule``): the paths spend under that guardrail
     (``mcr_run_rule_year_bins_rng``), and the vector gains two blocks behind the others,
     ``[... | final_success_bins | rule_year_counts[ry][4] | multiplier_bins[ry][nm + 2]]``, the multipliers binned on
-    ``m_edges`` (default: `default_multiplier_edges`)."""
+    ``m_edges`` (default: `default_multiplier_edges`).
 
-    def __init__(self, params: McrParams, working_months: int, edges=None, wr_edges=None, device: int = 0, rule=None, m_edges=None):
+    ``glide_path`` (a sequence of ``allocation_inv1_pct`` values, one per whole year from today, or anything with a
+    ``weights`` attribute): the paths hold that glide path (``mcr_run_glide_year_bins_rng``); the vector is the plain one.
+    A ``rule`` together with a ``glide_path`` is refused with a ``ValueError``."""
+
+    def __init__(self, params: McrParams, working_months: int, edges=None, wr_edges=None, device: int = 0, rule=None, m_edges=None,
+                 glide_path=None):
         import torch
 
+        if rule is not None and glide_path is not None:
+            raise ValueError("a spending rule together with a glide path is not supported")
+        self.glide = None if glide_path is None else glide_table(glide_path)
         N.require_device()
         self.torch = torch
         self.params = params
@@ -427,6 +445,13 @@ class YearBinsBatch:
                 C.byref(self.rule), C.byref(self._out), C.byref(self._yb), C.byref(self._rule_yb), self.device, C.c_void_p(stream),
             )
             N.check(rc, "mcr_run_rule_year_bins_rng")
+            return
+        if self.glide is not None:
+            rc = self._lib.mcr_run_glide_year_bins_rng(
+                C.byref(self.params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), self.working_months,
+                self.glide, len(self.glide), C.byref(self._out), C.byref(self._yb), self.device, C.c_void_p(stream),
+            )
+            N.check(rc, "mcr_run_glide_year_bins_rng")
             return
         rc = self._lib.mcr_run_year_bins_rng(
             C.byref(self.params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), self.working_months,
@@ -1239,4 +1264,99 @@ def run_rule_year_bins_host(params: McrParams, seed, stream_id: int, path_begin:
         C.byref(params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), int(working_months), C.byref(rec),
         C.byref(o), C.byref(y), C.byref(r), int(device))
     N.check(rc, "mcr_run_rule_year_bins_host_rng")
+    return res
+
+
+# ---------------------------------------------------------------------------------------------
+# Whole-path launches under a glide path (mcr_run_glide_rng, mcr_run_glide_year_bins_host_rng; include/mcr.h: GLIDE PATH)
+# ---------------------------------------------------------------------------------------------
+def run_glide(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int, glide_path,
+              want: str = "counts", device: int = 0, out_extra: Optional[dict] = None):
+    """One launch under a glide path (``mcr_run_glide_rng``) into device tensors, asynchronous on torch's current stream
+    (reading a tensor synchronises).  `glide_path`: what `glide_table` takes.  Returns a dict: ``counts`` = one int64 vector
+    ``[2 + ry + (ry + 2)]`` = ``[counters | wr_obs_counts | ruin_year_bins]`` (one all-reduce sums it across ranks), which is all
+    of ``want="counts"``; with
+    ``want="summary"`` the six float summary fields and ``success`` (uint8).  ``out_extra``: further ``McrOutputs`` fields by
+    name (device addresses), for callers that test what the entry point refuses."""
+    import torch
+
+    if want not in ("counts", "summary"):
+        raise ValueError(want)
+    table = glide_table(glide_path)
+    N.require_device()
+    n = int(n_paths)
+    sz = query_sizes(params, working_months)
+    ry = int(sz.retirement_years)
+    dev = torch.device("cuda", int(device))
+    res = {"counts": torch.zeros(N.MCR_N_COUNTERS + ry + int(sz.ruin_bins), dtype=torch.int64, device=dev)}
+    o = McrOutputs()
+    o.path_stride = n
+    o.counters = res["counts"].data_ptr()
+    o.wr_obs_counts = res["counts"][N.MCR_N_COUNTERS:].data_ptr()
+    o.ruin_year_bins = res["counts"][N.MCR_N_COUNTERS + ry:].data_ptr()
+    if want == "summary":
+        for k in SUMMARY_FIELDS:
+            res[k] = torch.empty(n, dtype=torch.float64, device=dev)
+            setattr(o, k, res[k].data_ptr())
+        res["success"] = torch.empty(n, dtype=torch.uint8, device=dev)
+        o.success = res["success"].data_ptr()
+    for k, v in (out_extra or {}).items():
+        setattr(o, k, v)
+    rng = _as_rng(seed, int(device))
+    stream = torch.cuda.current_stream(int(device)).cuda_stream
+    rc = N.load_library().mcr_run_glide_rng(
+        C.byref(params), C.byref(rng), int(stream_id), int(path_begin), n, int(working_months), table, len(table), C.byref(o),
+        int(device), C.c_void_p(stream),
+    )
+    N.check(rc, "mcr_run_glide_rng")
+    return res
+
+
+def run_glide_host(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int, glide_path,
+                   want: str = "counts", device: int = 0) -> Dict[str, np.ndarray]:
+    """`run_glide` with numpy arrays out: ``counters`` ``[2]``, ``wr_obs_counts`` ``[ry]``, ``ruin_year_bins`` ``[ry + 2]``, and
+    with ``want="summary"`` the summary fields and ``success`` as `run_batch_host` returns them."""
+    res = run_glide(params, seed, stream_id, path_begin, n_paths, working_months, glide_path, want=want, device=device)
+    out = {k: v.cpu().numpy() for k, v in res.items() if k != "counts"}
+    counts = res["counts"].cpu().numpy().astype(np.uint64)
+    ry = int(query_sizes(params, working_months).retirement_years)
+    out["counters"] = counts[:N.MCR_N_COUNTERS]
+    out["wr_obs_counts"] = counts[N.MCR_N_COUNTERS:N.MCR_N_COUNTERS + ry]
+    out["ruin_year_bins"] = counts[N.MCR_N_COUNTERS + ry:]
+    return out
+
+
+def run_glide_year_bins_host(params: McrParams, seed, stream_id: int, path_begin: int, n_paths: int, working_months: int, glide_path,
+                             edges=None, wr_edges=None, device: int = 0,
+                             into: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, np.ndarray]:
+    """`run_year_bins_host` under a glide path (``mcr_run_glide_year_bins_host_rng``, one device): the same arrays for paths
+    whose split follows `glide_path` (what `glide_table` takes).  ``into``: a previous result to accumulate into (same edges)."""
+    lib = N.load_library()
+    table = glide_table(glide_path)
+    N.require_device()
+    sz = query_sizes(params, working_months)
+    e = year_edge_array(default_year_edges() if edges is None else edges)
+    we = year_edge_array(default_wr_edges() if wr_edges is None else wr_edges, "wr_edges")
+    nb, nw = e.shape[0] - 1, we.shape[0] - 1
+    if into is not None:
+        res = into
+        if not (np.array_equal(res["edges"], e) and np.array_equal(res["wr_edges"], we)):
+            raise ValueError("`into` was binned on other edges")
+    else:
+        res = {name: np.zeros((rows, cells) if name in _YEAR_BINS_TABLES else cells, dtype=np.uint64)
+               for name, rows, cells in _year_bins_layout(sz, nb, nw)}
+        res["edges"], res["wr_edges"] = e, we
+    o = McrOutputs()
+    o.counters = res["counters"].ctypes.data
+    o.wr_obs_counts = res["wr_obs_counts"].ctypes.data
+    o.ruin_year_bins = res["ruin_year_bins"].ctypes.data
+    y = McrYearBins()
+    y.edges, y.n_bins, y.wr_edges, y.n_wr_bins = e.ctypes.data, nb, we.ctypes.data, nw
+    for name in ("trajectory_bins", "real_trajectory_bins", "wr_bins", "final_success_bins"):
+        setattr(y, name, res[name].ctypes.data)
+    rng = _as_rng(seed)
+    rc = lib.mcr_run_glide_year_bins_host_rng(
+        C.byref(params), C.byref(rng), int(stream_id), int(path_begin), int(n_paths), int(working_months), table, len(table),
+        C.byref(o), C.byref(y), int(device))
+    N.check(rc, "mcr_run_glide_year_bins_host_rng")
     return res

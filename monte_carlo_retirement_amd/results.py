@@ -284,7 +284,7 @@ def _bracket_payload(lo: np.ndarray, hi: np.ndarray, qs, digits: int) -> dict:
 
 def streamed_result(config: Config, simulator: RetirementMonteCarloSimulator, required_w_months: int,
                     search_curve: Optional[List[dict]] = None, num_simulations: Optional[int] = None,
-                    edges=None, wr_edges=None, rule=None, m_edges=None) -> dict:
+                    edges=None, wr_edges=None, rule=None, m_edges=None, glide_path=None) -> dict:
     """The keys of ``compact_result`` for ANY number of paths: the path kernel bins every yearly sample itself
     (``mcr_run_year_bins_rng``), so nothing is kept per path — the document comes out of a few hundred KB of integers, and
     under a process group out of ONE all-reduce (``distributed.run_sharded_year_bins``).
@@ -306,20 +306,29 @@ def streamed_result(config: Config, simulator: RetirementMonteCarloSimulator, re
     5 / 25 / 50 / 75 / 95 % real monthly spending among the paths that begin the year alive (`spending_rules.SpendingBands`
     on ``m_edges``; its brackets in ``band_brackets["spending"]``) and the EXACT alive / cut / at-floor / raised shares of the
     year counts.  The five sample paths would need a trajectory launch, which a rule refuses: they are None and named in
-    ``not_available``."""
+    ``not_available``.
+
+    ``glide_path`` (one option of `success_probability_by_glide_paths`: a `GlidePath`, a list, a number or a string): every path
+    holds that glide path (``mcr_run_glide_year_bins_rng``; the engine's own stream only).  The document gains ``glide_path``
+    (name and weights) and ``allocation_by_sample``, the weight of asset 1 at each yearly sample of the trajectory, exact from
+    the table.  The five sample paths are None and named in ``not_available``, as under a rule (there is no trajectory launch
+    under a glide path).  A ``rule`` together with a ``glide_path`` is refused with a ``ValueError``."""
+    if rule is not None and glide_path is not None:
+        raise ValueError("a spending rule together with a glide path is not supported")
     wm = int(required_w_months)
     n = int(config.num_simulations_main if num_simulations is None else num_simulations)
     if n <= 0:
         raise ValueError(f"Simulation for '{config.Nickname}' yielded no results.")
+    path = None if glide_path is None else simulator._one_glide_path(glide_path)
     params = simulator._current_params()
     rng = simulator._batch_rng(n)
     if D.is_active():
-        yb = D.run_sharded_year_bins(params, rng, simulator._stream_id, n, wm, edges, wr_edges, rule=rule, m_edges=m_edges)
+        yb = D.run_sharded_year_bins(params, rng, simulator._stream_id, n, wm, edges, wr_edges, rule=rule, m_edges=m_edges, glide_path=path)
     else:
         import torch
 
         with torch.cuda.device(simulator._local_device()):
-            yb = D.run_sharded_year_bins(params, rng, simulator._stream_id, n, wm, edges, wr_edges, rule=rule, m_edges=m_edges)
+            yb = D.run_sharded_year_bins(params, rng, simulator._stream_id, n, wm, edges, wr_edges, rule=rule, m_edges=m_edges, glide_path=path)
     e, we = yb["edges"], yb["wr_edges"]
     ok_count = int(yb["counters"][0])
     tq, wq = list(A.TRAJECTORY_QUANTILES), list(A.WR_QUANTILES)
@@ -332,7 +341,7 @@ def streamed_result(config: Config, simulator: RetirementMonteCarloSimulator, re
     f_lo, f_hi, f_est = A.bands_from_bins(yb["trajectory_bins"][T - 1], e, FINAL_BALANCE_PERCENTILES)
     m_lo, m_hi, m_est = A.bands_from_bins(yb["final_success_bins"], e, [0.50])
     # the five sample paths, exactly: one-path full-output launches at the picked global indices
-    picked = simulator._sample_columns(n) if rule is None else None
+    picked = simulator._sample_columns(n) if rule is None and path is None else None
     samples = real_samples = None
     if picked is not None:
         samples, real_samples = [], []
@@ -348,7 +357,7 @@ def streamed_result(config: Config, simulator: RetirementMonteCarloSimulator, re
     # an estimate is NaN where the order statistic lies outside the edges (or the row is empty): None in the document, and the
     # field is named in not_available
     not_available = ["summary.swr"]
-    if rule is not None:      # (a sample path is a trajectory launch, which there is none of under a rule)
+    if rule is not None or path is not None:      # (a sample path is a trajectory launch, which there is none of under a rule or a glide path)
         not_available += ["trajectory.samples", "trajectory_real.samples"]
 
     def value(a, field):
@@ -397,6 +406,13 @@ def streamed_result(config: Config, simulator: RetirementMonteCarloSimulator, re
     if search_curve:
         doc["search_curve"] = {"points": dedupe_search_curve(search_curve), "target_probability": config.target_probability,
                                "selected_working_months": wm}
+    if path is not None:
+        from .simulation import allocation_by_sample
+
+        for fam in ("trajectory", "trajectory_real"):
+            doc[fam]["sample_paths"] = None
+        doc["glide_path"] = {"name": path.describe(), "weights": [float(w) for w in path.weights]}
+        doc["allocation_by_sample"] = allocation_by_sample(path, wm, int(config.retirement_years))
     if rule is not None:
         from .spending_rules import SpendingBands, SpendingRuleOutcomes
 

@@ -122,6 +122,24 @@ def trajectory_time_points(working_months: int, retirement_years: int) -> List[f
     return pts
 
 
+def trajectory_sample_months(working_months: int, retirement_years: int) -> List[int]:
+    """`trajectory_time_points` in whole months from today: the sample at ``m`` is the balance behind month ``m``."""
+    wm = int(working_months)
+    full_years, leftover = divmod(wm, MONTHS_PER_YEAR)
+    pts = [MONTHS_PER_YEAR * y for y in range(full_years + 1)]
+    if leftover:
+        pts.append(wm)
+    pts.extend(wm + MONTHS_PER_YEAR * y for y in range(1, int(retirement_years) + 1))
+    return pts
+
+
+def allocation_by_sample(glide_path, working_months: int, retirement_years: int) -> List[float]:
+    """The weight of asset 1 the portfolio stands at in each yearly sample of `trajectory_time_points` under `glide_path` (an
+    `allocation.GlidePath`): the weight in force during the month the sample closes, ``W[min((m - 1) // 12, n - 1)]`` for the
+    sample behind month ``m`` (the month's rebalance brought the balance to it), and ``W[0]`` today.  Exact from the table."""
+    return [float(glide_path.weight_at(max(0, m - 1))) for m in trajectory_sample_months(working_months, retirement_years)]
+
+
 def _gather_columns(rows, picked) -> np.ndarray:
     """``rows[:, picked].T`` as a host array.  Each pick is a strided column VIEW (``select`` is metadata only: the
     64-bit offset is folded into the view's data pointer on the host) and the stack kernel then indexes k tensors of
@@ -1544,6 +1562,56 @@ class RetirementMonteCarloSimulator:
         rows = [dict(name=g.describe(), **dict(zip(SCENARIO_FIELDS, r[:3])), weights=list(g.weights), probability=float(pr))
                 for g, r, pr in zip(paths, records, probs)]
         return self._best_option_document({}, rows, joint, per_option)
+
+    def _one_glide_path(self, glide_path):
+        """The `allocation.GlidePath` of one option as `success_probability_by_glide_paths` takes it (a `GlidePath`, a list, a
+        number or a string); ``ValueError`` naming what is wrong with it."""
+        from .allocation import glide_paths_of
+
+        if isinstance(glide_path, dict):
+            raise ValueError("glide_path: one glide path (a GlidePath, a sequence of weights, a number or a string), not a mapping")
+        return glide_paths_of([glide_path])[0]
+
+    def glide_path_fan_chart(self, working_months: int, glide_path, num_simulations: Optional[int] = None, edges=None,
+                             wr_edges=None) -> Dict[str, object]:
+        """The fan charts of a household that holds `glide_path` at ``working_months``, for any number of paths: one yearly-bins
+        launch under the glide path over the active stream's batch (``mcr_run_glide_year_bins_rng``; nothing is kept per path,
+        one all-reduce under a process group).  Returns the tables of ``distributed.run_sharded_year_bins(glide_path=...)``
+        (balance, real balance, withdrawal rate, final balance and the edges) with ``glide_path`` = ``{"name", "weights"}`` and
+        ``allocation_by_sample`` = the weight in force at each yearly sample of `trajectory_time_points`, exact from the table
+        (`allocation_by_sample`: the weight of the month each sample closes, ``W[0]`` today)."""
+        from . import distributed as D
+
+        n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
+        if n <= 0:
+            raise ValueError("glide_path_fan_chart needs at least one path")
+        path = self._one_glide_path(glide_path)
+        params = self._current_params()
+        rng = self._batch_rng(n)
+        if D.is_active():
+            yb = D.run_sharded_year_bins(params, rng, self._stream_id, n, int(working_months), edges, wr_edges, glide_path=path)
+        else:
+            import torch
+
+            with torch.cuda.device(self._local_device()):
+                yb = D.run_sharded_year_bins(params, rng, self._stream_id, n, int(working_months), edges, wr_edges, glide_path=path)
+        yb["glide_path"] = {"name": path.describe(), "weights": list(path.weights)}
+        yb["allocation_by_sample"] = allocation_by_sample(path, int(working_months), int(self.params_model.retirement_years))
+        return yb
+
+    def glide_path_summary(self, working_months: int, glide_path, num_simulations: Optional[int] = None) -> pd.DataFrame:
+        """The reference's per-path summary frame (the columns of `run_monte_carlo_simulations`' ``summary_df``) of the active
+        stream's batch of ``num_simulations`` paths under `glide_path`: one summary launch (``mcr_run_glide_rng``) on this
+        rank's device.  Its success share equals `success_probability_by_glide_paths`' value for the same option."""
+        n = int(self.params_model.num_simulations_main if num_simulations is None else num_simulations)
+        path = self._one_glide_path(glide_path)
+        if n <= 0:
+            return pd.DataFrame({c: pd.Series(dtype=bool if c == "Success" else np.float64) for c in SUMMARY_COLUMNS})
+        res = E.run_glide_host(self._current_params(), self._batch_rng(n), self._stream_id, 0, n, int(working_months), path,
+                               want="summary", device=self._local_device())
+        cols = {name: res[f] for name, f in _FIELD_OF.items()}
+        cols["Success"] = res["success"].astype(np.bool_)
+        return pd.DataFrame({c: cols[c] for c in SUMMARY_COLUMNS}, copy=False)
 
     # ---- income-stream options and the required-income search ------------------------------------------
     def success_probability_by_income_options(self, working_months: int, stream, options: Sequence[dict],
